@@ -38,6 +38,10 @@ therefore never `value`), each with its own roofline.
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the projection GEMM),
 `roofline_spmm` (the SpMM against HBM), `cpu_baseline` (the oracle timed on host cores, all
 cores and one thread).
+
+    python bench.py ... --dump-outputs DIR
+        also writes the last timed step's loss and updated parameters (rank 0) to DIR/*.npy:
+        the inputs are seeded, so two builds run with the same arguments compare file by file.
 """
 import argparse
 import gc
@@ -116,6 +120,10 @@ def parse():
                     help='bracket the SpMM/GEMM launches of every N-th timed step with HIP events '
                          '(an event pair per launch serialises kernel boundaries: ~80 us/step '
                          'when every step is instrumented, i.e. it would depress `value`)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them handed its caller (the loss and every '
+                         'layer\'s updated weight and bias) to DIR/<name>.npy, float32, at most 64 MB in all: '
+                         'dump_outputs')
     args = ap.parse_args()
     # presets: the default invocation (no --config) is the metric's workload, unchanged
     n = args.gpus
@@ -428,6 +436,36 @@ def _traffic(name):
             ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; not measured in this run)'
     except Exception:
         return None, None
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, arena):
+    """--dump-outputs: what the last timed step handed its caller -- its loss and every layer's weight and bias after
+    that step's Adam update -- as float32 DIR/<name>.npy, so that two builds run with the same arguments (same seeded
+    inputs) can be compared output for output.  Each array may take an equal share of DUMP_BYTES; a larger one is
+    written as a fixed sample, <name>_sample.npy: the elements at sorted flat indices drawn without replacement by
+    numpy's Generator seeded 0, a function of the array's size only.  Returns {name: (shape written, full shape)}."""
+    import torch
+    arrays = [('loss', loss)]
+    for k, (W, b) in enumerate(zip(arena.W, arena.b)):
+        arrays += [('layer%d_weight' % k, W), ('layer%d_bias' % k, b)]
+    cap = DUMP_BYTES // 4 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), cap, replace=False))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+            name += '_sample'
+            out = flat.cpu().numpy().astype(np.float32)
+        else:
+            out = flat.cpu().numpy().astype(np.float32).reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + '.npy'), out)
+        written[name] = (list(out.shape), list(t.shape))
+    return written
 
 
 # --------------------------------------------------------------------------------------------
@@ -1036,6 +1074,9 @@ def main():
     hc_head = counter_delta(hc_head0, host_counters())
     head_gaps = np.diff(np.asarray(host_stamps)) * 1e3
     engine.check_extract()         # no batch of the warm-up / timed region was built from a timed-out extraction
+    dumped = None
+    if args.dump_outputs and rank == 0:      # (before the launch floor's extra steps move the parameters on)
+        dumped = dump_outputs(args.dump_outputs, loss_log[-1], engine.arena)
     n_sync_timed = len(sync_ms)
     sync_timed = list(sync_ms)
 
@@ -1398,6 +1439,8 @@ def main():
             out['partition'] = partition_info
         if launch_floor is not None:
             out['launch_floor'] = launch_floor
+        if dumped is not None:
+            out['dumped_outputs'] = {'dir': os.path.abspath(args.dump_outputs), 'arrays': dumped}
         out.update(legs)
         if world == 1 and not args.no_cpu_baseline:
             try:

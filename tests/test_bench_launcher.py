@@ -211,3 +211,36 @@ def test_dataset_arrays_round_trip_and_launch_tag(tmp_path, monkeypatch):
     os.utime(str(stale), (old, old))
     bench._drop_stale_shared(str(tmp_path))
     assert not stale.exists() and fresh.exists() and d.exists()
+
+
+def test_dump_outputs_writes_float32_within_budget_and_samples_the_same_elements(tmp_path, monkeypatch):
+    """--dump-outputs: the loss and every layer's weight and bias as float32 .npy, within DUMP_BYTES in all; an array
+    larger than its share is a fixed sample (sorted flat indices, the same in every run), a smaller one is written whole."""
+    import importlib.util
+    import numpy as np
+    from gist_amd.engine import ParamArena
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4 * 5 * 1000)       # 5 arrays: 1000 elements each at most
+    arena = ParamArena([(40, 300), (300, 5)], torch.device('cpu'), with_grads=False)
+    arena.params.copy_(torch.arange(arena.numel, dtype=torch.float32))
+    loss = torch.tensor([1.25])
+    a = bench.dump_outputs(str(tmp_path / 'a'), loss, arena)
+    b = bench.dump_outputs(str(tmp_path / 'b'), loss, arena)
+    assert a == b
+    assert sorted(a) == ['layer0_bias', 'layer0_weight_sample', 'layer1_bias', 'layer1_weight_sample', 'loss']
+    total = 0
+    for name, (shape, full) in a.items():
+        x, y = np.load(str(tmp_path / 'a' / (name + '.npy'))), np.load(str(tmp_path / 'b' / (name + '.npy')))
+        assert x.dtype == np.float32 and list(x.shape) == shape and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= bench.DUMP_BYTES
+    d = tmp_path / 'a'
+    assert np.array_equal(np.load(str(d / 'loss.npy')), [1.25])
+    assert np.array_equal(np.load(str(d / 'layer0_bias.npy')), arena.b[0].numpy())
+    assert np.array_equal(np.load(str(d / 'layer1_bias.npy')), arena.b[1].numpy())
+    for k in (0, 1):                                 # the sample: distinct elements of that weight, in flat order
+        s = np.load(str(d / ('layer%d_weight_sample.npy' % k)))
+        w = arena.W[k].numpy().reshape(-1)
+        assert s.size == 1000 and np.all(np.diff(s) > 0) and w[0] <= s[0] and s[-1] <= w[-1]
