@@ -3,13 +3,15 @@
 hipcc cross-compiles without a GPU.  The .so is built IN-TREE
 (gist_amd/libgist_hip.so) so it travels with the repo snapshot to the GPU box.
 """
+import glob
 import os
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-# dev knobs for A/B builds of kernel variants: extra -D flags and a different output name
+# extra hipcc flags and a different output name: for ISA inspection (GIST_EXTRA_FLAGS=-save-temps) and whole-library
+# A/B runs against another build (GIST_LIB_OUT, loaded through GIST_LIB_PATH); the kernels have no build variants
 OUT = os.environ.get('GIST_LIB_OUT', os.path.join(HERE, 'libgist_hip.so'))
 EXTRA = os.environ.get('GIST_EXTRA_FLAGS', '').split()
 SOURCES = ['capi.hip', 'spmm.hip', 'spmm_mfma.hip', 'spmm_dense32.hip', 'gemm.hip', 'gemm_h3.hip', 'gemm_b3.hip', 'gemm_b3c.hip', 'rowops.hip', 'classlayer.hip', 'subgraph.hip', 'step.hip',
@@ -27,7 +29,7 @@ def build(force=False, verbose=False):
     objdir = os.path.join(HERE, 'build' if not EXTRA else 'build_' + '_'.join(
         f.strip('-').replace('=', '_') for f in EXTRA))
     os.makedirs(objdir, exist_ok=True)
-    deps = [os.path.join(CSRC, 'common.h'), os.path.join(HERE, '..', 'include', 'gist_hip.h')]
+    deps = glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(HERE, '..', 'include', 'gist_hip.h')]
     objs, procs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

@@ -309,20 +309,6 @@ __device__ __forceinline__ float f4(const float4 &v, int j) {
     return j == 0 ? v.x : (j == 1 ? v.y : (j == 2 ? v.z : v.w));
 }
 
-#ifdef GIST_GEMM_TRACE   // dev builds only (scripts/gemm_trace.py): per-block phase timestamps
-__device__ unsigned long long g_gemm_trace[12 * 16384];
-#define GIST_TRACE(slot)                                                               \
-    if (threadIdx.x == 0 && blockIdx.z == 0 && blockIdx.x < 16384)                     \
-        g_gemm_trace[12 * blockIdx.x + (slot)] = wall_clock64();
-// phase accounting of wave 0 inside the main loop, in s_memtime ticks
-#define GIST_PHASE_DECL unsigned long long ph_t = clock64(), ph_acc[6] = {0, 0, 0, 0, 0, 0};
-#define GIST_PHASE(i) { const unsigned long long n_ = clock64(); ph_acc[i] += n_ - ph_t; ph_t = n_; }
-#else
-#define GIST_TRACE(slot)
-#define GIST_PHASE_DECL
-#define GIST_PHASE(i)
-#endif
-
 // ALIGNED: both operands have 16-B aligned bases and leading dimensions % 4 == 0
 // (every buffer the engine allocates); otherwise the generic guarded loader runs.
 // T = block tile edge (128 or 64); 4 waves in 2x2, each wave (T/2)x(T/2) = (T/64)^2 MFMA tiles.
@@ -331,7 +317,6 @@ __device__ unsigned long long g_gemm_trace[12 * 16384];
 template <bool A_KC, bool B_KC, bool ALIGNED, int T>
 __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const int block_x, const int block_z) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    GIST_TRACE(0)
     constexpr int BK = T == 128 ? 32 : 64;
     constexpr int TA = A_KC ? Img<T, BK>::KC : Img<T, BK>::MC;
     constexpr int TB = B_KC ? Img<T, BK>::KC : Img<T, BK>::MC;
@@ -421,8 +406,6 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const int block
     }
     __builtin_amdgcn_s_waitcnt(0x0f70);         // vmcnt(0): the DMA has landed in LDS
     __syncthreads();
-    GIST_TRACE(1)
-    GIST_PHASE_DECL
 
     // Fragment addresses.  k-contiguous image: offset of k block q = 0..3 for each slab's row
     // (the XOR swizzle is lane dependent, so these are computed once).  m/n-contiguous image:
@@ -455,7 +438,6 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const int block
         if constexpr (mode == 0) dma(cur ^ 1, kt + 1);      // buffer cur^1 is free since the last barrier
         if constexpr (mode == 1) gload(kt + 1);
         __builtin_amdgcn_sched_barrier(0);      // staging is issued; keep the MFMAs below
-        GIST_PHASE(0)
         const float *a_s = smem + cur * (TA + TB);
         const float *b_s = a_s + TA;
         if (g.setprio) __builtin_amdgcn_s_setprio(1);
@@ -477,17 +459,10 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const int block
         }
         if (g.setprio) __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);      // nothing of the store phase moves above the MFMAs
-        GIST_PHASE(1)
         if constexpr (mode != 2) __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): DMA landed / loads arrived
         __builtin_amdgcn_sched_barrier(0);
-        GIST_PHASE(2)
         if constexpr (mode == 1) sstore(cur ^ 1, kt + 1);
-#ifdef GIST_GEMM_TRACE
-        __builtin_amdgcn_sched_barrier(0);
-        GIST_PHASE(3)
-#endif
         __syncthreads();
-        GIST_PHASE(4)
     };
     {
         using C0 = std::integral_constant<int, 0>;
@@ -511,7 +486,6 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const int block
             }
         }
     }
-    GIST_TRACE(2)
 
     // ---- epilogue: C/D layout col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5) ----
     // A workgroup usually stores its tile while the CU's other workgroup streams MFMAs, and
@@ -571,18 +545,6 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const int block
                 }
             }
     }
-#ifdef GIST_GEMM_TRACE
-    __builtin_amdgcn_s_waitcnt(0);          // this wave's stores are acknowledged
-    GIST_TRACE(3)
-    if (threadIdx.x == 0 && blockIdx.z == 0 && blockIdx.x < 16384) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_gemm_trace[12 * blockIdx.x + 4] = ((unsigned long long)xcc << 32) | hw;
-        for (int i = 0; i < 5; ++i) g_gemm_trace[12 * blockIdx.x + 5 + i] = ph_acc[i];
-        g_gemm_trace[12 * blockIdx.x + 10] = (unsigned long long)n_kt;
-    }
-#endif
 }
 
 template <bool A_KC, bool B_KC, bool ALIGNED, int T>
@@ -680,7 +642,8 @@ static GemmCfg choose_cfg(int64_t m, int64_t n, int64_t k, bool deferred = false
             const double eff = tile == 128 ? eff128[conc] : eff64[conc];
             double cost = (double)per_cu * unit * (double)(kt_per + 3) / eff;
             // (deferred: no reduce launch, but the slabs are written by this kernel and read by the consumer; fitted to
-            // same-box A/B runs of the forward projections of BASELINE configs 2 and 4, scripts/ab_yslabs.sh)
+            // same-box A/B runs of the forward projections of BASELINE configs 2 and 4; probe removed,
+            // `git show 4165530:scripts/ab_yslabs.sh`)
             if (sp > 1) cost += deferred ? 4.5 + 9.0 * sp * mn : 12.0 + 6.5 * sp * mn;
             if (cost < best_cost) { best_cost = cost; best = GemmCfg{tile, sp}; }
         }
@@ -913,12 +876,6 @@ extern "C" int gist_gemm_slabs_f32(int layout, const float *a, int64_t lda, cons
     *n_slabs = ns;
     return rc;
 }
-
-#ifdef GIST_GEMM_TRACE
-extern "C" int gist_gemm_trace_read(unsigned long long *out, int64_t n_blocks) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(gist::g_gemm_trace), n_blocks * 12 * 8);
-}
-#endif
 
 /* 1 if a gist_gemm_* call of this shape splits its own operands in the current mode (f16x3 / bf16x3 pre-split
  * kernels: it needs the large workspace of gist_gemm_workspace_bytes and reduces its k slices itself). */

@@ -52,12 +52,7 @@ typedef float b3_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int B3_TM = 256, B3_TN = 128, B3_BK = 32;
 constexpr int B3_THREADS = 512;
 constexpr int B3_STAGES = 2;
-#ifndef B3_SKEW
-#define B3_SKEW 16               // MFMAs by which waves 4-7 run behind waves 0-3 inside a k step
-#endif
-#ifndef B3_DMA_AFTER
-#define B3_DMA_AFTER 16        // MFMAs of a k step issued before the next tile's DMA
-#endif
+constexpr int B3_SKEW = 16;      // MFMAs by which waves 4-7 run behind waves 0-3 inside a k step
 constexpr int B3_KT_BYTES = B3_BK * 6;                 // 192 B of one row per k tile (12 chunks)
 constexpr int B3_A_BYTES = B3_TM * B3_KT_BYTES;        // 24 KiB
 constexpr int B3_B_BYTES = B3_TN * B3_KT_BYTES;        // 12 KiB
@@ -219,10 +214,6 @@ __device__ __forceinline__ void b3_dma_image(const char *base, const uint32_t (&
             0, 0, 0);
 }
 
-#ifdef B3_CLOCK_PROBE   // dev build (scripts/b3_clock_probe.py): core cycles and 100 MHz ticks of every workgroup's k loop
-__device__ unsigned long long g_b3_clock[2 * 4096];
-#endif
-
 __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
     extern __shared__ __attribute__((aligned(16))) char b3_smem[];
     constexpr int NI = 4, NJ = 4;                 // 16-row slabs per wave: 64 x 64 wave tile
@@ -298,19 +289,18 @@ __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
     // none of these.  The matrix pipe never waits on a post-barrier LDS round trip (with the barrier
     // at the end of the step all eight waves start the next one with 8 KiB of fragment reads each and
     // nothing to issue), and the DMA has a full step to land instead of 80 MFMA slots.
-    // In-kernel stamps (scripts/b3_clock_probe.py, 2046 x 4096 x 8192 / 4096 x 8192 x 2046): MFMA
+    // In-kernel stamps (2046 x 4096 x 8192 / 4096 x 8192 x 2046): MFMA
     // cycles are 0.79 / 0.84 of the k loop's cycles at 1.95 / 1.93 GHz, against 0.71 / 0.80 at
     // 2.08 / 1.96 GHz with the barrier at the end of the step -- the chip gives back in clock most of
-    // what the pipe share gains (power), the loop itself is 2-4 % shorter (508 vs 531 us).
+    // what the pipe share gains (power), the loop itself is 2-4 % shorter (508 vs 531 us)
+    // (probe removed; `git show 4165530:scripts/b3_clock_probe.py`).
     // A wave whose 64 rows all lie past the end of C (the last row tile of a batch a few rows over a multiple of 256)
     // stages its share of the images and meets the barriers, nothing else: its SIMD's other wave has the pipe alone.
     const bool live = __builtin_amdgcn_readfirstlane(row0 + wm * (16 * NI) < g.m);
     bf16x8 a[NI][3], b[NJ][3];
     auto read_head = [&](auto st_c) {
         constexpr int st = decltype(st_c)::value;
-#ifndef B3_NO_DEAD_SKIP
         if (!live) return;
-#endif
 #pragma unroll
         for (int j = 0; j < NJ; ++j) b[j][0] = *reinterpret_cast<const bf16x8 *>(fb[st][0] + j * 3072);
 #pragma unroll
@@ -320,9 +310,7 @@ __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
     };
     auto read_rest = [&](auto st_c) {
         constexpr int st = decltype(st_c)::value;
-#ifndef B3_NO_DEAD_SKIP
         if (!live) return;
-#endif
 #pragma unroll
         for (int j = 0; j < NJ; ++j) b[j][1] = *reinterpret_cast<const bf16x8 *>(fb[st][1] + j * 3072);
 #pragma unroll
@@ -345,9 +333,7 @@ __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
     // (`late`) issue 16 MFMAs before each of the two non-MFMA blocks of the step.
     auto mfmas = [&](auto t0_c, auto t1_c) {
         constexpr int t0 = decltype(t0_c)::value, t1 = decltype(t1_c)::value;
-#ifndef B3_NO_DEAD_SKIP
         if (!live) return;
-#endif
 #pragma unroll
         for (int t = t0; t < t1; ++t) {
             const int term = t / (NI * NJ), i = (t % (NI * NJ)) / NJ, j = t % NJ;
@@ -390,20 +376,8 @@ __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
             kstep(C1{}, late_c, kt + 1);
         }
     };
-#ifdef B3_CLOCK_PROBE
-    const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifndef B3_NO_SKEW
     if (wave >= 4) run(std::integral_constant<int, 1>{});
-    else
-#endif
-        run(std::integral_constant<int, 0>{});
-#ifdef B3_CLOCK_PROBE
-    if (threadIdx.x == 0 && blockIdx.x < 4096) {
-        g_b3_clock[2 * blockIdx.x + 0] = __builtin_amdgcn_s_memtime() - ck0;
-        g_b3_clock[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - rt0;
-    }
-#endif
+    else run(std::integral_constant<int, 0>{});
     __builtin_amdgcn_s_waitcnt(0x0070);              // the wasted DMA and reads of the last step
 
     // the MFMAs above are opaque to the compiler's hazard recognizer: let the last ones retire
@@ -493,7 +467,7 @@ int b3_splits(int64_t m, int64_t n, int64_t k) {
         // between half a chip and 3/4 of one (dW_0 of the H = 4096 step: 160 tiles) one slice runs a single
         // under-full round; the slice count that minimises rounds x k tiles per slice wins even with the
         // slab sum (4096 x 1204 x 2046: 3 slices = 2 rounds of 22 k tiles against 1 of 64; 165 -> 154 us
-        // per call with the sum in the call, scripts/b3_split_probe.py)
+        // per call with the sum in the call; probe removed, `git show 4165530:scripts/b3_split_probe.py`)
         int64_t best = n_kt + 4;      // one slice: no slabs (the +4: a slab sum costs about 4 k tiles)
         for (int64_t c = 2; c <= 4; ++c) {
             const int64_t per = ceil_div(ceil_div(n_kt, c), 2) * 2;
@@ -675,10 +649,3 @@ int b3_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda,
 }
 
 }  // namespace gist
-
-#ifdef B3_CLOCK_PROBE
-extern "C" int gist_b3_clock_read(unsigned long long *out, int64_t n_blocks) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(gist::g_b3_clock), n_blocks * 2 * sizeof(unsigned long long)) ==
-                   hipSuccess ? 0 : -1;
-}
-#endif

@@ -214,16 +214,6 @@ __device__ __forceinline__ void c3_write(const C3Out<T> &out, char *image, const
 //   waves 0-3 CONSUME: fragments of tile j -> registers while the 6 x NI x NJ MFMAs of tile j - 1 run
 //             (2 x 2 waves over the TM x TN tile, two fragment register sets);
 // one workgroup barrier per k step (P_j: tile j is in LDS).
-#ifdef C3_PROBE   // dev build (scripts/b3c_probe.py): where a k step's cycles go, per workgroup
-__device__ unsigned long long g_c3_probe[16 * 4096];
-__device__ __forceinline__ unsigned long long c3_stamp() {
-    __builtin_amdgcn_sched_barrier(0);
-    const unsigned long long t = __builtin_amdgcn_s_memtime();
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define C3_T() c3_stamp()
-#endif
 
 template <bool A_KC, bool B_KC, int TM, int TN>
 __global__ __launch_bounds__(512, 1) void gemm_b3c_kernel(C3Args g) {
@@ -264,10 +254,7 @@ __global__ __launch_bounds__(512, 1) void gemm_b3c_kernel(C3Args g) {
         // flight the producers waited ~2 us per step for their operands and the kernel ran at their pace).
         // The steady state is straight-line code over the FULL tiles: loads past the last full tile re-read
         // it (never consumed), the ragged last tile sits in a register set of its own from the start.
-#ifndef C3_PD64
-#define C3_PD64 3
-#endif
-        constexpr int PD = TM + TN <= 128 ? C3_PD64 : 3;      // 16 values per operand and set at T = 64
+        constexpr int PD = 3;                                 // 16 values per operand and set at T = 64
         C3Stage<A_KC, TM> sa[PD], ta;
         C3Stage<B_KC, TN> sb[PD], tb;
         c3_offsets<A_KC, TM>(g.lda, g.m, row0, ta, t);
@@ -320,30 +307,9 @@ __global__ __launch_bounds__(512, 1) void gemm_b3c_kernel(C3Args g) {
         // wait -> barrier the write latency was on every step's critical path -- the set is refilled with tile
         // j + 1 + PD, and only then comes the wait for the writes and barrier P_j.
         int kt = 0;
-#ifdef C3_PROBE
-        unsigned long long pr_store = 0, pr_load = 0, pr_bar = 0, pr_cvt = 0, pr_ld = 0;
-        const unsigned long long pr_t0 = C3_T();
-#endif
         for (; kt + PD < n_full; kt += PD) {
 #pragma unroll
             for (int d = 0; d < PD; ++d) {
-#ifdef C3_PROBE
-                const unsigned long long p0 = C3_T();
-                write_tile(kt + d);
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned long long p1 = C3_T();
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((PD - 1) * 2 * (TM + TN) / 64) : "memory");
-                const unsigned long long p1b = C3_T();
-                convert_full(sa[(d + 1) % PD], sb[(d + 1) % PD]);
-                const unsigned long long p1c = C3_T();
-                load_full(kt + d + 1 + PD, sa[(d + 1) % PD], sb[(d + 1) % PD]);
-                const unsigned long long p2 = C3_T();
-                __syncthreads();
-                const unsigned long long p3 = C3_T();
-                pr_store += p1 - p0; pr_load += p1b - p1; pr_bar += p3 - p2; pr_cvt += p1c - p1b; pr_ld += p2 - p1c;
-                __builtin_amdgcn_sched_barrier(0);
-                continue;
-#endif
                 write_tile(kt + d);
                 __builtin_amdgcn_sched_barrier(0);            // (the writes stay in front of the conversion)
                 convert_full(sa[(d + 1) % PD], sb[(d + 1) % PD]);
@@ -371,12 +337,6 @@ __global__ __launch_bounds__(512, 1) void gemm_b3c_kernel(C3Args g) {
             write_tile(n_full);
             __syncthreads();
         }
-#ifdef C3_PROBE
-        if (threadIdx.x == 256 && blockIdx.x < 4096 && blockIdx.z == 0) {
-            unsigned long long *o = g_c3_probe + 16 * blockIdx.x;
-            o[4] = C3_T() - pr_t0; o[5] = pr_store; o[6] = pr_load; o[7] = pr_bar; o[8] = pr_cvt; o[9] = pr_ld;
-        }
-#endif
         return;
     }
     // ==================================== consumers ==================================================
@@ -436,18 +396,8 @@ __global__ __launch_bounds__(512, 1) void gemm_b3c_kernel(C3Args g) {
                 for (int j = 0; j < NJ; ++j) rd_b(q, j);
             }
         }
-#ifdef C3_PROBE
-        unsigned long long co_bar = 0;
-        const unsigned long long co_t0 = C3_T();
-#endif
         for (int kt = 1; kt < n_kt; ++kt) {
-#ifdef C3_PROBE
-            const unsigned long long c0 = C3_T();
-            bare_barrier();
-            co_bar += C3_T() - c0;
-#else
             bare_barrier();                                   // P_kt
-#endif
             img = c3_smem + (kt % NSTAGE) * STAGE;
             term(2, 0);
 #pragma unroll
@@ -477,12 +427,6 @@ __global__ __launch_bounds__(512, 1) void gemm_b3c_kernel(C3Args g) {
             for (int i = 0; i < NI; ++i) rd_a(0, i);
             __builtin_amdgcn_sched_barrier(0);
         }
-#ifdef C3_PROBE
-        if (threadIdx.x == 0 && blockIdx.x < 4096 && blockIdx.z == 0) {
-            unsigned long long *o = g_c3_probe + 16 * blockIdx.x;
-            o[0] = C3_T() - co_t0; o[1] = co_bar; o[2] = 0; o[3] = 0;
-        }
-#endif
         if (n_kt > 0) {
             term(2, 0); term(0, 2); term(1, 1); term(1, 0); term(0, 1); term(0, 0);
         }
@@ -519,32 +463,6 @@ __global__ __launch_bounds__(512, 1) void gemm_b3c_kernel(C3Args g) {
     using S0 = std::integral_constant<int, 0>;
     using S1 = std::integral_constant<int, 1>;
     int kt = 0;
-#ifdef C3_PROBE
-    unsigned long long co_bar = 0, co_work = 0, co_wait = 0;
-    const unsigned long long co_t0 = C3_T();
-    for (; kt + 2 <= n_kt; kt += 2) {
-        const unsigned long long c0 = C3_T();
-        __syncthreads();
-        const unsigned long long c1 = C3_T();
-        read_frags(kt, S0{});
-        if (kt > 0) multiply(S1{});
-        const unsigned long long c2 = C3_T();
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        const unsigned long long c3 = C3_T();
-        __syncthreads();
-        const unsigned long long c4 = C3_T();
-        read_frags(kt + 1, S1{});
-        multiply(S0{});
-        const unsigned long long c5 = C3_T();
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        const unsigned long long c6 = C3_T();
-        co_bar += (c1 - c0) + (c4 - c3); co_work += (c2 - c1) + (c5 - c4); co_wait += (c3 - c2) + (c6 - c5);
-    }
-    if (threadIdx.x == 0 && blockIdx.x < 4096 && blockIdx.z == 0) {
-        unsigned long long *o = g_c3_probe + 16 * blockIdx.x;
-        o[0] = C3_T() - co_t0; o[1] = co_bar; o[2] = co_work; o[3] = co_wait;
-    }
-#endif
     for (; kt + 2 <= n_kt; kt += 2) {
         __syncthreads();                                      // P_kt
         read_frags(kt, S0{});
@@ -618,7 +536,7 @@ __global__ __launch_bounds__(256) void gemm_b3c_tail_sum_kernel(C3Args g, int tm
 }
 
 // ---- host side ----------------------------------------------------------------------------------
-// Which calls take this kernel by default.  MEASURED (scripts/b3c_bench.py, profiles/r03_b3c_bench.txt; us,
+// Which calls take this kernel by default.  MEASURED (profiles/r03_b3c_bench.txt; us,
 // standalone calls, fp32 kernel -> this kernel with 64 x 64 tiles and one k slice): NT 2046 x 1024 x 2048
 // 76 -> 59, NT 2046 x 1024 x 1204 50 -> 43, NN 2046 x 2048 x 1024 73 -> 66, NT 2046 x 512 x 1204 24.9 -> 22.3;
 // TN (both operands k-major: 16 scalar row loads per thread and step) 1024 x 2048 x 2046 68.5 -> 64, but
@@ -665,7 +583,7 @@ static int b3c_launch(const char *name, C3Args &g, int splits, hipStream_t st) {
     return rc;
 }
 
-// Tile and k slices (fp32 slabs, reduced by the call or left to the consumer).  Fitted to scripts/b3c_bench.py.
+// Tile and k slices (fp32 slabs, reduced by the call or left to the consumer).  Fitted to profiles/r03_b3c_bench.txt.
 static void b3c_choice(int64_t m, int64_t n, int64_t k, int *tm, int *tn, int *splits) {
     const int t_tile = (int)tune(GIST_TUNE_GEMM_TILE), t_split = (int)tune(GIST_TUNE_GEMM_SPLITS);
     auto tiles = [&](int a, int b) { return ceil_div(m, a) * ceil_div(n, b); };
@@ -675,7 +593,8 @@ static void b3c_choice(int64_t m, int64_t n, int64_t k, int *tm, int *tn, int *s
     // ~2700 cycles for 1536 of MFMA, one of the 64 x 64 tile ~1200 for 384: the producers' step (176 / 88 vector
     // instructions, 12 / 6 ds_write_b128 at ~13 issue cycles, 8 / 4 loads) sets the pace in both, and neither deeper
     // load prefetch (PD 4-6), nor LDS writes issued before the conversion, nor cheaper instructions (v_perm for
-    // v_cvt_pk, v_sub for v_pk_add), nor half as many MFMA issues (32 x 32 x 16) moved it (scripts/b3c_probe.py).
+    // v_cvt_pk, v_sub for v_pk_add), nor half as many MFMA issues (32 x 32 x 16) moved it
+    // (probe removed; `git show 4165530:scripts/b3c_probe.py`).
     *tm = 64; *tn = 64;
     if (tiles(128, 128) >= 256) { *tm = 128; *tn = 128; }
     if (t_tile == 64) { *tm = 64; *tn = 64; }
@@ -767,10 +686,3 @@ int b3c_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda
 }
 
 }  // namespace gist
-
-#ifdef C3_PROBE
-extern "C" int gist_c3_probe_read(unsigned long long *out, int64_t n_blocks) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(gist::g_c3_probe), n_blocks * 16 * sizeof(unsigned long long)) ==
-                   hipSuccess ? 0 : -1;
-}
-#endif

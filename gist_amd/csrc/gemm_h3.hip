@@ -373,10 +373,6 @@ __device__ __forceinline__ void h3_dma_offsets(int64_t ld, int rows, int row0, i
 // TM = rows of the A tile: 128, or 64 for outputs with fewer than two 128x128 tiles per CU
 // (wave tile 32 x 64, 24 MFMAs per k tile, 24 KiB per stage, 512 instead of 256 workgroups on a
 // 2046 x 2048 output).
-#ifdef H3_CLOCK_PROBE   // dev build (scripts/h3_clock_probe.py): in-kernel clock = d(s_memtime) / d(s_memrealtime) x 100 MHz
-__device__ unsigned long long g_h3_clock[4 * 4096];
-#endif
-
 template <int TM>
 __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(H3Args g) {
     extern __shared__ __attribute__((aligned(16))) char h3_smem[];
@@ -447,13 +443,9 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(H3Args g) {
     auto kstep = [&](auto cur_c, auto next_c, int kt) {
         constexpr int cur = decltype(cur_c)::value;
         constexpr bool has_next = decltype(next_c)::value != 0;
-#ifndef H3_DMA_AFTER
-#define H3_DMA_AFTER (-1)    // dev knob: MFMAs of the k step issued before the next tile's DMA
-#endif
         __builtin_amdgcn_sched_barrier(0);
         const char *img = h3_smem + cur * BUF_BYTES;
         __builtin_amdgcn_s_setprio(1);
-#ifndef H3_PROBE_NO_MFMA
         f16x8 ah[NI], al[NI], bh[4], bl[4];
 #pragma unroll
         for (int i = 0; i < NI; ++i) ah[i] = *reinterpret_cast<const f16x8 *>(img + fa[i][0]);
@@ -469,34 +461,23 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(H3Args g) {
         // landed at the barrier (per launch: first 0.2258 ms, after 8 MFMAs 0.2244, after 16 0.2215,
         // after 24 0.2250, after 32 0.2332).  The 64-row kernel (24 MFMAs, 3 workgroups per CU)
         // runs best with the DMA first (h=1024 step 0.525 vs 0.533 ms).
+        constexpr int dma_after = TM == 128 ? 16 : 0;
 #pragma unroll
         for (int t = 0; t < 3 * NI * 4; ++t) {
-            constexpr int dma_after = H3_DMA_AFTER < 0 ? (TM == 128 ? 16 : 0)
-                                                        : (H3_DMA_AFTER < 3 * NI * 4 ? H3_DMA_AFTER : 3 * NI * 4 - 1);
             if (t == dma_after) {
                 __builtin_amdgcn_sched_barrier(0);
-#ifndef H3_PROBE_NO_DMA      // dev probes (scripts/h3_probe.sh): which side bounds the loop
                 if constexpr (has_next) dma(cur ^ 1, kt + 1);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
             const int term = t / (NI * 4), i = (t % (NI * 4)) / 4, j = t % 4;
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(term == 2 ? al[i] : ah[i],
                                                                term == 1 ? bl[j] : bh[j], acc[i][j], 0, 0, 0);
         }
-#else
-#ifndef H3_PROBE_NO_DMA
-        if constexpr (has_next) dma(cur ^ 1, kt + 1);
-#endif
-#endif
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (has_next) __builtin_amdgcn_s_waitcnt(0x0f70);
         __syncthreads();
     };
-#ifdef H3_CLOCK_PROBE
-    const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
     {
         using C0 = std::integral_constant<int, 0>;
         using C1 = std::integral_constant<int, 1>;
@@ -512,12 +493,6 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(H3Args g) {
         }
     }
 
-#ifdef H3_CLOCK_PROBE
-    if (threadIdx.x == 0 && blockIdx.x < 4096) {
-        g_h3_clock[4 * blockIdx.x + 0] = __builtin_amdgcn_s_memtime() - ck0;
-        g_h3_clock[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - rt0;
-    }
-#endif
     // ---- epilogue: C/D of 16x16x32: col = lane & 15, row = 4 (lane >> 4) + e ----
     float *cbase = g.c + (int64_t)row0 * g.ldc + col0;
     const int rows_valid = min(g.m - row0, TM);
@@ -585,8 +560,9 @@ int64_t h3_kpad(int64_t k) { return ceil_div(k, H3_BK) * H3_BK; }
 
 // Shapes the split path takes: enough 128x128 tiles to occupy the chip and enough flops to
 // pay for the pre-pass.  Break-even measured at ~20 GFLOP when every call splits its own
-// operands (scripts/h3_bench.py) and at ~4 GFLOP inside the step, which shares one split of an
-// operand between the GEMMs that use it (bench.py --n-hidden 1024: 0.606 -> 0.551 ms/step).
+// operands (probe removed; `git show 4165530:scripts/h3_bench.py`) and at ~4 GFLOP inside the
+// step, which shares one split of an operand between the GEMMs that use it (bench.py
+// --n-hidden 1024: 0.606 -> 0.551 ms/step).
 // Everything else stays on the fp32 kernel.
 static bool h3_shape_ok(int64_t m, int64_t n, int64_t k, double default_min_gflop) {
     if (h3_mode() != 1) return false;
@@ -725,9 +701,3 @@ extern "C" int gist_gemm_set_mode(int mode) {
 }
 
 extern "C" int gist_gemm_get_mode(void) { return gist::h3_mode(); }
-
-#ifdef H3_CLOCK_PROBE
-extern "C" int gist_h3_clock_read(unsigned long long *out, int64_t n_blocks) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(gist::g_h3_clock), n_blocks * 4 * 8);
-}
-#endif

@@ -136,7 +136,6 @@ __global__ __launch_bounds__(256) void ln_relu_fwd_kernel(float *__restrict__ y,
         }
     }
     float mean = 0.f, rstd = 1.f;
-#ifndef GIST_LN_STREAMING      // dev A/B build flag: always take the streaming path
     if constexpr (TPR == 256 && VEC == 4) {
         // Rows of up to 4096 floats (one workgroup per row): the row is read ONCE into registers
         // (4 x 16 B per thread) instead of three times; same per-thread order of every sum, so
@@ -182,7 +181,6 @@ __global__ __launch_bounds__(256) void ln_relu_fwd_kernel(float *__restrict__ y,
             return;
         }
     }
-#endif
     if (use_lynorm) {
         float s = 0.f;
         if (live)
@@ -247,7 +245,6 @@ __global__ __launch_bounds__(256) void ln_relu_bwd_kernel(
     const float *yr = yhat + (int64_t)(live ? row : 0) * ldy;
     float *dr = dy + (int64_t)(live ? row : 0) * lddy;
     float m1 = 0.f, m2 = 0.f, rstd = 1.f;
-#ifndef GIST_LN_STREAMING
     if constexpr (TPR == 256 && VEC == 4) {
         if (d <= 4096) {      // one read of d_out and yhat into registers (see the forward kernel)
             float4 gq[4], yq[4];
@@ -299,7 +296,6 @@ __global__ __launch_bounds__(256) void ln_relu_bwd_kernel(
             return;
         }
     }
-#endif
     if (use_lynorm) {
         float s1 = 0.f, s2 = 0.f;
         if (live)

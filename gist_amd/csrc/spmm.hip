@@ -312,8 +312,8 @@ __global__ __launch_bounds__(256) void spmm_csr_rowsplit_kernel(
 //   bottleneck); the next row's indices are read before the current row is gathered; cross-block
 //   neighbours (a ballot mask) come from global memory, 4 rows in flight.
 // X leaves L2/HBM once per unit instead of once per neighbour: at D = 4096 on a Reddit-like
-// batch nnz*D*4 = 2.1 GB of L2 gather traffic becomes LDS reads.  Measured (scripts/
-// spmm_probe.py, scripts/lds_gather_probe.hip): 82 -> 51 us at D = 4096;
+// batch nnz*D*4 = 2.1 GB of L2 gather traffic becomes LDS reads.  Measured (DESIGN.md section 4,
+// profiles/r02_lds_gather_probe.txt; probe removed, `git show 4165530:scripts/spmm_probe.py`): 82 -> 51 us at D = 4096;
 // the gather loop itself runs at ~6 cycles per KiB per CU (LDS peak 4), the rest is the
 // start-up of each unit, which one workgroup per CU cannot hide.  Tried and dropped: 512-thread
 // workgroups that loop over column tiles with the next tile prefetched into registers (8 waves
@@ -348,17 +348,6 @@ struct L2Args {
     SpmmLnBwd ln;                // LNB instantiation only
 };
 
-#ifdef L2_PROBE_NO_LDS
-#define L2_LDS_READ(o) make_float4(__builtin_bit_cast(float, o), 0.f, 0.f, 0.f)
-#else
-#define L2_LDS_READ(o) (*reinterpret_cast<const float4 *>(tb + (o)))
-#endif
-#ifdef L2_PROBE_NO_ADD
-#define L2_ADD(v) acc[0] += (v).x
-#else
-#define L2_ADD(v) acc[0] += (v).x; acc[1] += (v).y; acc[2] += (v).z; acc[3] += (v).w
-#endif
-
 // Sum the neighbours [base, base + cnt) of one row into acc: `off` holds, per lane, the LDS
 // byte offset of neighbour base + lane (zero row if it is not in the tile).
 __device__ __forceinline__ void l2_local(const unsigned char *tb, int cnt, int off, float (&acc)[4]) {
@@ -368,17 +357,21 @@ __device__ __forceinline__ void l2_local(const unsigned char *tb, int cnt, int o
     // has work queued)
     float4 v[2][8];
 #pragma unroll
-    for (int t = 0; t < 8; ++t) v[0][t] = L2_LDS_READ(__builtin_amdgcn_readlane(off, t));
+    for (int t = 0; t < 8; ++t) v[0][t] = *reinterpret_cast<const float4 *>(tb + __builtin_amdgcn_readlane(off, t));
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
         const bool more = (g + 1) * 8 < cnt;                   // wave-uniform
         if (g < 7 && more) {
 #pragma unroll
             for (int t = 0; t < 8; ++t)
-                v[(g + 1) & 1][t] = L2_LDS_READ(__builtin_amdgcn_readlane(off, ((g + 1) * 8 + t) & 63));
+                v[(g + 1) & 1][t] =
+                    *reinterpret_cast<const float4 *>(tb + __builtin_amdgcn_readlane(off, ((g + 1) * 8 + t) & 63));
         }
 #pragma unroll
-        for (int t = 0; t < 8; ++t) { L2_ADD(v[g & 1][t]); }
+        for (int t = 0; t < 8; ++t) {
+            const float4 w = v[g & 1][t];
+            acc[0] += w.x; acc[1] += w.y; acc[2] += w.z; acc[3] += w.w;
+        }
         if (!more) break;
     }
 }
@@ -467,7 +460,6 @@ __global__ __launch_bounds__(kL2Threads) void spmm_csr_lds2_kernel(L2Args a) {
         const unsigned long long m = __ballot(lg);
         if (lane == 0) lmask[wave] = m;
     }
-#ifndef L2_PROBE_NO_STAGE
     {
         float4 v[kL2Pre];
         float sc[kL2Pre];
@@ -489,7 +481,6 @@ __global__ __launch_bounds__(kL2Threads) void spmm_csr_lds2_kernel(L2Args a) {
             }
         }
     }
-#endif
     // 1-byte local index of EVERY neighbour of the block's rows (128: not in the tile): it depends
     // on the neighbour and the block only, so all threads classify the block's edge range in one
     // flat coalesced pass whose loads fly together with the tile's
@@ -502,9 +493,6 @@ __global__ __launch_bounds__(kL2Threads) void spmm_csr_lds2_kernel(L2Args a) {
         }
     }
     __syncthreads();
-#ifdef L2_PROBE_NO_GATHER
-    return;
-#endif
     unsigned long long lm[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -588,7 +576,6 @@ __global__ __launch_bounds__(kL2Threads) void spmm_csr_lds2_kernel(L2Args a) {
 
     // ---- long rows first (all waves in step): wave w takes the 64-neighbour chunks w, w + 16, ..;
     //      the partial sums meet in LDS and are added in wave order by wave (k mod 16) ---------------
-#ifndef L2_PROBE_NO_LONG
     if (lm[0] | lm[1]) {
         int k = 0;
 #pragma unroll
@@ -625,7 +612,6 @@ __global__ __launch_bounds__(kL2Threads) void spmm_csr_lds2_kernel(L2Args a) {
             }
         }
     }
-#endif
 
     // ---- the other rows of this unit, one wave per row; the next row's first chunk is classified
     //      (its LDS index read issued) before the current row is gathered ----------------------------
@@ -767,8 +753,9 @@ static int launch_spmm(const int32_t *rowptr, const int32_t *col, const float *x
 
 // Row split R of the second LDS design: units = blocks x column tiles x R on 256 CUs, one unit
 // per CU at a time; every split re-stages the tile (cost ~1) and gathers 1/R of the block's rows
-// (cost ~2.5 / R), fitted to scripts/spmm_probe.py on a Reddit-like batch.  (R up to 16 since round 5: 20 blocks of <= 256
-// columns take R = 12 = 240 units in one round -- config 2 0.2994 -> 0.2918 ms/step against R = 8, h = 256 0.1782 -> 0.1741.)
+// (cost ~2.5 / R), fitted to a probe on a Reddit-like batch (probe removed; `git show 4165530:scripts/spmm_probe.py`).
+// (R up to 16 since round 5: 20 blocks of <= 256 columns take R = 12 = 240 units in one round -- config 2
+// 0.2994 -> 0.2918 ms/step against R = 8, h = 256 0.1782 -> 0.1741.)
 static int l2_row_split(int64_t nb, int n_col_tiles) {
     int best = 1;
     double best_cost = 1e30;

@@ -18,18 +18,12 @@
 // product (more than 8 outside neighbours, a count > 256) and the rows of a block beyond its first 128 are gathered
 // in full.  Masks of the fused dropout (SpmmDrop modes 1 and 2) are applied to what is stored / read.
 #include "common.h"
+#include "spmm_prep.h"
 
 namespace gist {
 namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int DB_ROWS = 128;                    // = MF_ROWS of spmm_mfma.hip (the prepared image's row count)
-#ifndef MF_REM_N
-#define MF_REM_N 8
-#endif
-constexpr int DB_REM = MF_REM_N;                // = MF_REM
-constexpr int DB_PREP_STRIDE = 16 * DB_ROWS * 16 + DB_ROWS * 4 + DB_ROWS * DB_REM * 4 + 16;      // = MF_PREP_STRIDE
 
 struct D32Args {
     const int32_t *rowptr, *col;
@@ -101,18 +95,18 @@ __global__ __launch_bounds__(256) void spmm_dense32_kernel(D32Args a) {
     const int ct = rem_t - grp * a.n_col_tiles;
     int r0, r1;
     if (a.row_blocks) { r0 = a.row_blocks[rbk]; r1 = a.row_blocks[rbk + 1]; }
-    else { r0 = rbk * DB_ROWS; r1 = r0 + DB_ROWS; }
+    else { r0 = rbk * MF_ROWS; r1 = r0 + MF_ROWS; }
     r1 = min(r1, a.n_rows);
     const int nrow = r1 - r0;
     if (nrow <= 0) return;
-    const int nloc = min(nrow, DB_ROWS);
+    const int nloc = min(nrow, MF_ROWS);
     const int n0 = ct * 16;
     const int col = n0 + r;
     const bool col_ok = col < a.d;
     const int colc = min(col, a.d - 1);
-    const unsigned char *pb = a.prep + (int64_t)rbk * DB_PREP_STRIDE;
-    const int32_t *rem_cnt = reinterpret_cast<const int32_t *>(pb + 16 * DB_ROWS * 16);
-    const int32_t *rem_col = rem_cnt + DB_ROWS;
+    const unsigned char *pb = a.prep + (int64_t)rbk * MF_PREP_STRIDE;
+    const int32_t *rem_cnt = reinterpret_cast<const int32_t *>(pb + MF_PREP_REMC);
+    const int32_t *rem_col = reinterpret_cast<const int32_t *>(pb + MF_PREP_REMCOL);
     const int n_rt = (nloc + 15) >> 4;                       // row tiles of the block = its 16-k blocks
     const int rt0 = grp * a.rt_per_group;
     const int rt1 = min(rt0 + a.rt_per_group, n_rt);
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(256) void spmm_dense32_kernel(D32Args a) {
 #pragma unroll
         for (int t = 0; t < RT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         // counts of (row rt * 16 + r, k = 16 kb + 4 q + s): 8 bytes at [(2 kb + (q >> 1)) * 128 + row] * 16 + 8 (q & 1)
-        const unsigned char *arow = pb + (int64_t)((q >> 1) * DB_ROWS + rt0 * 16 + r) * 16 + 8 * (q & 1);
+        const unsigned char *arow = pb + (int64_t)((q >> 1) * MF_ROWS + rt0 * 16 + r) * 16 + 8 * (q & 1);
         // A block has at most eight 16-k blocks: ALL operand loads of the task are issued before the first MFMA, in
         // two batches of four k blocks (the second lands under the first batch's MFMAs) -- a loop that loads one k
         // block, waits and multiplies is one memory latency per block, 5-8 us per task.
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(256) void spmm_dense32_kernel(D32Args a) {
 #pragma unroll
                 for (int t = 0; t < RT; ++t) {
                     const int tt = min(t, rt1 - rt0 - 1);                   // (a short last group re-reads its last tile)
-                    const uint2 v = *reinterpret_cast<const uint2 *>(arow + (int64_t)(2 * kb * DB_ROWS + tt * 16) * 16);
+                    const uint2 v = *reinterpret_cast<const uint2 *>(arow + (int64_t)(2 * kb * MF_ROWS + tt * 16) * 16);
                     cc[u][t] = on ? v : make_uint2(0u, 0u);
                 }
             }
@@ -180,9 +174,9 @@ __global__ __launch_bounds__(256) void spmm_dense32_kernel(D32Args a) {
                 const int row = (rt0 + t) * 16 + 4 * q + i;
                 ok[t][i] = rt0 + t < rt1 && row < nloc && col_ok;
                 const int rowc = min(row, nloc - 1);
-                // (>= 0x100: the row has edges in a pair image of its block, spmm_mfma.hip -- this kernel has no pair
+                // (>= MF_PAIR_FLAG: the row has edges in a pair image of its block -- this kernel has no pair
                 // product: such a row is gathered in full like the negative states)
-                const int c = rem_cnt[rowc] >= 0x100 ? -1 : rem_cnt[rowc];
+                const int c = rem_cnt[rowc] >= MF_PAIR_FLAG ? -1 : rem_cnt[rowc];
                 cnt[t][i] = ok[t][i] ? c : 0;
                 osc[t][i] = a.out_scale ? a.out_scale[r0 + rowc] : 1.f;
                 old[t][i] = (a.accumulate && ok[t][i]) ? a.y[(int64_t)(r0 + rowc) * a.ldy + colc] : 0.f;
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(256) void spmm_dense32_kernel(D32Args a) {
             for (int i = 0; i < 4; ++i)
                 if (cnt[t][i] < 0) acc[t][i] = d32_gather_row<MODE>(a, r0 + (rt0 + t) * 16 + 4 * q + i, col);
         }
-        for (int j = 0; j < DB_REM; ++j) {
+        for (int j = 0; j < MF_REM; ++j) {
             if (!__any(maxc > j)) break;
             int u[RT][4];
 #pragma unroll
@@ -203,7 +197,7 @@ __global__ __launch_bounds__(256) void spmm_dense32_kernel(D32Args a) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int row = min((rt0 + t) * 16 + 4 * q + i, nloc - 1);
-                    u[t][i] = cnt[t][i] > j ? rem_col[row * DB_REM + j] : -1;
+                    u[t][i] = cnt[t][i] > j ? rem_col[row * MF_REM + j] : -1;
                 }
             }
             float xv[RT][4];
@@ -237,8 +231,8 @@ __global__ __launch_bounds__(256) void spmm_dense32_kernel(D32Args a) {
         }
     }
     // rows of an oversized block beyond the dense product: gathered in full by the first group's waves
-    if (grp == 0 && nrow > DB_ROWS && col_ok) {
-        for (int row = DB_ROWS + q; row < nrow; row += 4)
+    if (grp == 0 && nrow > MF_ROWS && col_ok) {
+        for (int row = MF_ROWS + q; row < nrow; row += 4)
             d32_store<MODE>(a, r0 + row, col, d32_gather_row<MODE>(a, r0 + row, col));
     }
 }
@@ -273,7 +267,7 @@ int launch_spmm_dense32(const int32_t *rowptr, const int32_t *col, const float *
     a.prep = static_cast<const unsigned char *>(prepared);
     a.dr = dr ? *dr : SpmmDrop{};
     const int mode = dr ? dr->mode : 0;
-    const int64_t nb = row_blocks ? n_row_blocks : ceil_div(n_rows, DB_ROWS);
+    const int64_t nb = row_blocks ? n_row_blocks : ceil_div(n_rows, MF_ROWS);
     if (nb <= 0) return GIST_OK;
     a.n_blocks = (int)nb;
     a.n_col_tiles = (int)ceil_div(d, 16);

@@ -32,7 +32,7 @@
 // The barriers wait for LDS traffic only (s_waitcnt lgkmcnt(0); s_barrier): __syncthreads() also
 // waits for vmcnt(0), i.e. for the prefetched tile.
 //
-// Measured (scripts/spmm_mf_probe.py under rocprofv3, scripts/spmm_mf_phases.py; Reddit-like batch,
+// Measured (rocprofv3 and in-kernel stamps, profiles/r02_spmm_mfma_phases.txt; Reddit-like batch,
 // 20 blocks x 12 column groups = 240 workgroups at D = 4096): 38 us against 57 us for the LDS gather
 // kernel (29 vs 33 at D = 2048; below that the set-up does not pay and the dispatcher keeps the gather
 // kernel).  Phases of a workgroup: set-up 11 us (row pointers 1, counts 7, conversion 3), then per tile
@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "spmm_prep.h"
 
 namespace gist {
 
@@ -50,7 +51,6 @@ typedef float mf_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 mf_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float mf_f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int MF_ROWS = 128;                       // rows of a block staged = k extent of the product
 constexpr int MF_CT = 128;                         // columns per tile
 constexpr int MF_THREADS = 1024;
 constexpr int MF_WAVES = MF_THREADS / 64;
@@ -61,12 +61,8 @@ constexpr int MF_WAVES = MF_THREADS / 64;
 constexpr int MF_CHUNK_SLOTS = 4 * 36;
 constexpr int MF_PIECE = 16 * MF_CHUNK_SLOTS * 16;
 constexpr int MF_YT_PITCH = 132;                   // floats; the fp32 result tile aliases the X^T image
-#ifndef MF_REM_N      // (dev A/B: -DMF_REM_N=...)
-#define MF_REM_N 8
-#endif
-constexpr int MF_REM = MF_REM_N;                   // outside neighbours listed per row
-constexpr int MF_A_OFF = 3 * MF_PIECE;             // counts, [k chunk 16][row 128][8 k] bf16
-constexpr int MF_RP_OFF = MF_A_OFF + 16 * MF_ROWS * 16;          // int rowptr[132]
+constexpr int MF_A_OFF = 3 * MF_PIECE;             // counts, [k chunk 16][row 128][8 k] bf16 (spmm_prep.h)
+constexpr int MF_RP_OFF = MF_A_OFF + MF_IMG_BYTES;               // int rowptr[132]
 constexpr int MF_REMC_OFF = MF_RP_OFF + 132 * 4;                 // int rem_cnt[128]  (-1: gather the whole row)
 constexpr int MF_REM_OFF = MF_REMC_OFF + MF_ROWS * 4;            // int rem_col[128][8]
 constexpr int MF_REME_OFF = MF_REM_OFF + MF_ROWS * MF_REM * 4;   // their edge indices (to restore CSR order)
@@ -83,27 +79,18 @@ static_assert(MF_LDS_BYTES <= 160 * 1024, "LDS budget of one CU");
 // MF_PAIRS blocks with >= MF_PAIR_MIN of them get their own count image; the aggregation kernel runs them as further k
 // steps of the block's product (the accumulators stay in registers; per pair and tile one more X tile conversion).  Their
 // edges are in no per-row list.
-constexpr int MF_PAIRS = 2;
-constexpr int MF_IMG_BYTES = 16 * MF_ROWS * 16;                  // one count image
-#ifndef MF_PAIR_MIN_N      // (dev A/B: unplanted H = 4096 step, aggregation launch average: 256 49.9 us, 128 50.0, 48 53.0; 128 for the tail: fewer 70-136-us launches)
-#define MF_PAIR_MIN_N 128
-#endif
-constexpr int MF_PAIR_MIN = MF_PAIR_MIN_N;                       // edges into the other block (gist_spmm_pair_min_edges)
-#ifndef MF_FINE_TILES      // column tiles per workgroup of a block with pairs (dev A/B: 2 tiles 53.5 us against 50.0)
-#define MF_FINE_TILES 1
-#endif
+// MF_PAIR_MIN, measured on the unplanted H = 4096 step (aggregation launch average): 256 49.9 us, 128 50.0, 48 53.0;
+// 128 for the tail (fewer 70-136-us launches).
+constexpr int MF_PAIR_MIN = 128;                                 // edges into the other block (gist_spmm_pair_min_edges)
+constexpr int MF_FINE_TILES = 1;      // column tiles per workgroup of a block with pairs (2 tiles: 53.5 us against 50.0)
 constexpr int MF_PAIR_BLOCKS = 256;                              // batches of up to this many blocks look for pairs
 // (prepare kernel only, in the idle X^T region: the pair images, the outside-edge histogram, the row blocks)
 constexpr int MF_PHIST_OFF = MF_PAIRS * MF_IMG_BYTES;
 constexpr int MF_PRB_OFF = MF_PHIST_OFF + MF_PAIR_BLOCKS * 4;
 static_assert(MF_PRB_OFF + (MF_PAIR_BLOCKS + 1) * 4 <= 3 * MF_PIECE, "prepare-time scratch fits the X^T region");
-// a prepared block in memory: the counts image, then rem_cnt[128], then rem_col[128][8] (as in LDS), then pair[2][2].
-// rem_cnt[r] >= 0: bits 0-7 = listed outside neighbours, bit 8 = the row has edges in a pair image (a consumer without
-// the pair images gathers such a row in full); -1: gather the row in full; -2: walk the edge list for the neighbours
-// outside the block and its pairs.  The pair images of all blocks follow the block records (spmm_blocks_bytes).
-constexpr int MF_PREP_STRIDE = MF_IMG_BYTES + MF_ROWS * 4 + MF_ROWS * MF_REM * 4 + 16;
-constexpr int MF_PREP_PINFO = MF_IMG_BYTES + MF_ROWS * 4 + MF_ROWS * MF_REM * 4;
-static_assert(MF_REM_OFF == MF_REMC_OFF + MF_ROWS * 4 && MF_PREP_STRIDE % 16 == 0, "rem_cnt and rem_col are contiguous");
+// a prepared block in memory (spmm_prep.h): rem_cnt and rem_col lie as in LDS, and move as one copy
+static_assert(MF_REM_OFF == MF_REMC_OFF + MF_ROWS * 4 && MF_PREP_REMCOL == MF_PREP_REMC + MF_ROWS * 4,
+              "rem_cnt and rem_col are contiguous");
 
 struct MfArgs {
     const int32_t *rowptr, *col;
@@ -216,20 +203,6 @@ __device__ __forceinline__ void mf_gather_row_outside(const MfArgs &a, int e0, i
     }
 }
 
-#ifdef MF_PROBE      // dev build (scripts/spmm_mf_phases.py): s_memrealtime (100 MHz) stamps of workgroup 0, wave 0
-__device__ unsigned long long g_mf_probe[64];
-#ifdef MF_PROBE_PAIRS   // ... of the first workgroup of the blocks-with-pairs class instead (block 0 must have a pair)
-#define MF_STAMP_B(i) do { } while (0)
-#define MF_STAMP(i) do { if (PAIRK && bid == 0 && threadIdx.x == 0) g_mf_probe[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define MF_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_mf_probe[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define MF_STAMP_B(i) MF_STAMP(i)
-#endif
-#else
-#define MF_STAMP(i) do { } while (0)
-#define MF_STAMP_B(i) do { } while (0)
-#endif
-
 // Edge counts of block [r0, r0 + nloc) as bf16 in `ab`, [k chunk][row][8 k], and per row its neighbours
 // outside the block (rem_cnt: how many, -2 = more than the list holds: the epilogue walks the row's edges for them,
 // -1 = the row leaves the dense product and is gathered in full;
@@ -277,7 +250,6 @@ __device__ __forceinline__ void mf_build_block(const MfArgs &a, int rbk, int r0,
         }
     }
     mf_barrier();
-    MF_STAMP_B(1);
     if constexpr (PAIRS) {
         // outside edges per other block of the batch (the block of a source row by binary search in the row blocks)
         const int E0 = rp[0], E1 = rp[nloc];
@@ -381,7 +353,6 @@ __device__ __forceinline__ void mf_build_block(const MfArgs &a, int rbk, int r0,
         }
     }
     mf_barrier();
-    MF_STAMP_B(2);
     // outside neighbours of a row back into CSR order (the slots were taken in arrival order); a row
     // with more than fit is gathered in full below
     if (tid < nloc) {
@@ -445,7 +416,7 @@ __device__ __forceinline__ void mf_build_block(const MfArgs &a, int rbk, int r0,
     // final state of a row in one place: -1 = gathered in full; bit 8 = edges in a pair image
     if (tid < nloc) {
         if (big_row[tid] & 1) rem_cnt[tid] = -1;
-        else if (rem_cnt[tid] >= 0 && (big_row[tid] & 2)) rem_cnt[tid] |= 0x100;
+        else if (rem_cnt[tid] >= 0 && (big_row[tid] & 2)) rem_cnt[tid] |= MF_PAIR_FLAG;
     }
     mf_barrier();
 }
@@ -466,7 +437,6 @@ __device__ __forceinline__ void mf_build_block(const MfArgs &a, int rbk, int r0,
 // code it ran before pairs existed (this kernel answers epilogue edits with another register allocation: NEGATIVES.md).
 template <bool PREP, int DROP, bool PAIRK, bool PP>
 __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem, int bid, int groups) {
-    MF_STAMP(0);
     // ---- workgroup -> (block, column group); the groups of one block stay on one XCD ----
     const int total = a.n_blocks * groups;
     const int per_xcd = (total + kXcds - 1) / kXcds;
@@ -540,7 +510,7 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
         // ---- the block's counts and outside neighbours were built once for the batch: copy them ----
         const unsigned char *src = a.prep + (int64_t)rbk * MF_PREP_STRIDE;
         const uint4 c0 = reinterpret_cast<const uint4 *>(src)[2 * tid], c1 = reinterpret_cast<const uint4 *>(src)[2 * tid + 1];
-        const int4 rm = tid < (MF_ROWS * (1 + MF_REM)) / 4 ? reinterpret_cast<const int4 *>(src + MF_IMG_BYTES)[tid]
+        const int4 rm = tid < (MF_ROWS * (1 + MF_REM)) / 4 ? reinterpret_cast<const int4 *>(src + MF_PREP_REMC)[tid]
                                                            : make_int4(0, 0, 0, 0);
         const int rpv = (tid <= nloc && a.units == nullptr) ? a.rowptr[r0 + tid] : 0;      // (units: no gathered rows)
         const float scv = (tid < nloc && a.out_scale) ? a.out_scale[r0 + tid] : 1.f;
@@ -554,7 +524,6 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
     } else {
         mf_build_block<false>(a, rbk, r0, nloc, mf_smem, first_loads);
     }
-    MF_STAMP(3);
 
     const int rr = lane & 15, kg = lane >> 4;
     const int mt0 = (wave >> 2) * 2, nt0 = (wave & 3) * 2;
@@ -646,7 +615,6 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
     const int n_units_extra = n_pairs;
     int mf_it = 0;
     for (; ct < a.n_col_tiles; ct += groups, ++mf_it) {
-        MF_STAMP(8 + 8 * mf_it);
         const int gc = ct * MF_CT + 4 * cq;
         const bool colok = gc < a.d;
 #pragma unroll
@@ -661,7 +629,6 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
         for (int u = 0;; ++u) {
             // ---- X tile -> x src_scale -> three bf16 pieces -> X^T image ----
             convert(ct, nsrc);
-            MF_STAMP(9 + 8 * mf_it);
             if (n_units_extra > 0) __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0): this unit's count image has landed
             // what comes next goes out now and lands under the MFMAs: the next pair's tile, or the next tile of the block
             if (u < n_units_extra) {
@@ -682,9 +649,7 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 load_tile(ct + groups);
             }
             mf_barrier();
-            MF_STAMP(10 + 8 * mf_it);
             mma((nsrc + 31) >> 5);
-            MF_STAMP(11 + 8 * mf_it);
             mf_barrier();                                      // every wave is done reading both images
             if (u == n_units_extra) break;
             nsrc = u == 0 ? pin.y : pin.w;
@@ -693,7 +658,6 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
         }
         // (the block's own image comes back for the next tile: its conversion waits for it)
         if (n_units_extra > 0) mf_image_to_lds(a.prep + (int64_t)rbk * MF_PREP_STRIDE, ab, wave, lane);
-        MF_STAMP(12 + 8 * mf_it);
         // ---- accumulators -> fp32 result tile (C/D of 16x16x32: col = lane & 15, row = 4 (lane >> 4) + e) ----
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
@@ -703,7 +667,6 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 for (int e = 0; e < 4; ++e)
                     yt[((mt0 + mi) * 16 + 4 * kg + e) * MF_YT_PITCH + (nt0 + ni) * 16 + rr] = acc[mi][ni][e];
         mf_barrier();
-        MF_STAMP(13 + 8 * mf_it);
 
         // ---- per row: + neighbours outside the block, x out_scale (+ y), store; two rows per pass ----
         // (row offsets inside the block in 32 bits, launcher-checked: as 64-bit products hoisted out of the tile
@@ -736,7 +699,6 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
         // the result tile (which aliases the next X^T image) is in registers: the stores below run
         // under the next tile's conversion
         mf_barrier();
-        MF_STAMP(14 + 8 * mf_it);
 #pragma unroll
         for (int pp = 0; pp < RW / 2; ++pp) {
 #pragma unroll
@@ -788,14 +750,12 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 *reinterpret_cast<float4 *>(yp) = o;
             }
         }
-        MF_STAMP(15 + 8 * mf_it);
     }
             return;
         }
     }
     int mf_it = 0;
     for (; ct < a.n_col_tiles; ct += groups, ++mf_it) {
-        MF_STAMP(8 + 8 * mf_it);
         // ---- X tile -> x src_scale -> three bf16 pieces -> X^T image ----
         {   // rows (0, 1) and (2, 3) of a column are converted in pairs: one v_cvt_pk_bf16_f32 per
             // piece gives the packed word the image wants, its two halves shifted / masked back to fp32
@@ -829,12 +789,10 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                     *reinterpret_cast<uint2 *>(dst + q * MF_PIECE) = make_uint2(w[q][0], w[q][1]);
             }
         }
-        MF_STAMP(9 + 8 * mf_it);
         if (ct + groups < a.n_col_tiles) load_tile(ct + groups);      // next tile, in flight under the MFMAs
         const int gc = ct * MF_CT + 4 * cq;
         const bool colok = gc < a.d;
         mf_barrier();
-        MF_STAMP(10 + 8 * mf_it);
 
         // ---- counts . X^T: 2 x 2 output tiles per wave ----
         mf_f32x4 acc[2][2];
@@ -870,9 +828,7 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 }
             }
         }
-        MF_STAMP(11 + 8 * mf_it);
         mf_barrier();                                      // every wave is done reading the X^T image
-        MF_STAMP(12 + 8 * mf_it);
         // ---- accumulators -> fp32 result tile (C/D of 16x16x32: col = lane & 15, row = 4 (lane >> 4) + e) ----
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
@@ -882,7 +838,6 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 for (int e = 0; e < 4; ++e)
                     yt[((mt0 + mi) * 16 + 4 * kg + e) * MF_YT_PITCH + (nt0 + ni) * 16 + rr] = acc[mi][ni][e];
         mf_barrier();
-        MF_STAMP(13 + 8 * mf_it);
 
         // ---- per row: + neighbours outside the block, x out_scale (+ y), store; two rows per pass ----
         // (row offsets inside the block in 32 bits, launcher-checked: as 64-bit products hoisted out of the tile
@@ -915,7 +870,6 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
         // the result tile (which aliases the next X^T image) is in registers: the stores below run
         // under the next tile's conversion
         mf_barrier();
-        MF_STAMP(14 + 8 * mf_it);
 #pragma unroll
         for (int pp = 0; pp < RW / 2; ++pp) {
 #pragma unroll
@@ -967,7 +921,6 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 *reinterpret_cast<float4 *>(yp) = o;
             }
         }
-        MF_STAMP(15 + 8 * mf_it);
     }
 }
 
@@ -1009,7 +962,7 @@ __global__ __launch_bounds__(MF_THREADS) void spmm_blocks_prepare_kernel(MfArgs 
         reinterpret_cast<uint4 *>(dst)[2 * tid] = reinterpret_cast<const uint4 *>(mf_smem + MF_A_OFF)[2 * tid];
         reinterpret_cast<uint4 *>(dst)[2 * tid + 1] = reinterpret_cast<const uint4 *>(mf_smem + MF_A_OFF)[2 * tid + 1];
         if (tid < (MF_ROWS * (1 + MF_REM)) / 4)
-            reinterpret_cast<int4 *>(dst + MF_IMG_BYTES)[tid] = reinterpret_cast<const int4 *>(mf_smem + MF_REMC_OFF)[tid];
+            reinterpret_cast<int4 *>(dst + MF_PREP_REMC)[tid] = reinterpret_cast<const int4 *>(mf_smem + MF_REMC_OFF)[tid];
         const int4 pin = *reinterpret_cast<const int4 *>(mf_smem + MF_PINFO_OFF);
         if (tid == 0) *reinterpret_cast<int4 *>(dst + MF_PREP_PINFO) = pin;
         if (pairs && pin.y > 0) {      // the block's pair images (the second one only if there is a second pair)
@@ -1405,9 +1358,3 @@ extern "C" int gist_spmm_block_units_f32(const int32_t *units, int64_t n_units, 
     return launch_spmm_mfma_units(units, n_units, images, x, ldx, y, ldy, n_rows_y, d, out_scale, accumulate,
                                   as_stream(stream));
 }
-
-#ifdef MF_PROBE
-extern "C" int gist_mf_probe_read(unsigned long long *out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(gist::g_mf_probe), 64 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -640,11 +640,7 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
             GIST_TRY(b3_dual_split(d, st));
             // (a hidden layer's k slices stay slabs: its LayerNorm, the next launch, sums them as it reads)
             // (with one slice the kernel adds the bias itself; slabs get it from the LayerNorm)
-#ifdef STEP_NO_YSLABS
-            const bool to_ln = false;
-#else
             const bool to_ln = defer && k + 1 < L1;
-#endif
             GIST_TRY(b3_gemm_presplit("gist_sage_step", hl.Zs, hl.Ws, l.b, l.Y, l.ldy, n, l.n_out,
                                       2 * l.n_in, b3.slabs, b3.slab_bytes, st, to_ln ? &y_slabs_n : nullptr));
             if (to_ln) y_slabs = b3.slabs;
@@ -656,14 +652,12 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
             if (defer && k == L1 - 1 && fl.logit_slabs != nullptr) {      // the loss kernel sums the slabs
                 GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
                                     fl.logit_slabs, fl.logit_bytes, &logit_slabs, st));
-#ifndef STEP_NO_YSLABS      // dev A/B build flag
             } else if (defer && k + 1 < L1 && fl.y_slabs != nullptr && !h3_eligible(n, l.n_out, 2 * l.n_in) &&
                        !b3_eligible(n, l.n_out, 2 * l.n_in)) {
                 // the LayerNorm sums the slabs (a projection the per-call split paths take keeps their workspace)
                 GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
                                     fl.y_slabs, fl.y_bytes, &y_slabs_n, st));
                 y_slabs = fl.y_slabs;
-#endif
             } else {
                 GIST_TRY(gist_gemm_nt_f32(l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out,
                                           2 * l.n_in, p->workspace, p->workspace_bytes, s));

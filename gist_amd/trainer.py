@@ -342,6 +342,7 @@ class FullGraphEvaluator(object):
         # (a prepared buffer = one record per block, then -- small block counts -- room for pair images: records only)
         diag = torch.cat([pb[:(rb.numel() - 1) * 2 * stride].view(torch.bfloat16).view(-1, stride)
                           for pb, rb in zip(sp['prepared'], sp['blocks'])], 0)
+        # (bf16 elements: MF_PREP_REMC / 2 and MF_ROWS * 4 / 2 of gist_amd/csrc/spmm_prep.h)
         rem = diag[:, 16384:16384 + 256].contiguous().view(torch.int32)       # rem_cnt[128] of every block
         if diag.shape[0] != nb or bool((rem < 0).any()):
             return

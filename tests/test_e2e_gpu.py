@@ -878,7 +878,7 @@ def test_metric_config_fused_step_equals_unfused_bf16x3(monkeypatch, hidden):
         # (layer 0's aggregation stays its own launch in both runs: formed by the extraction -- the fused default, pinned in
         # tests/test_preagg_gpu.py -- it sums in another order; the losses stay bitwise equal, but among 8 M hidden units
         # three ReLU inputs within that rounding of zero flip their masks and every element of dW_0 moves by ~1e-3 of its
-        # size: scripts/r4_preagg_flip_probe.py, profiles/r04_preagg.txt)
+        # size: profiles/r04_preagg.txt)
         monkeypatch.setenv('GIST_STEP_PREAGG', '0')
         for fuse in ('0', '1'):
             monkeypatch.setenv('GIST_STEP_FUSE', fuse)

@@ -95,8 +95,8 @@ def test_split_error_matches_fp32_mfma(hip, tile, form, m, n, k, kind):
     e1 = ((y1 - ref).abs() / den).max().item()
     r3 = ((y3 - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
     r1 = ((y1 - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
-    # error relative to sum_k |a||b| (the fp32 rounding model).  Measured (scripts/
-    # h3_error_probe.py): the split path's rms error is BELOW the fp32 chain's on long k (the
+    # error relative to sum_k |a||b| (the fp32 rounding model).  Measured (profiles/
+    # r01_gemm_h3_error_vs_float64.txt): the split path's rms error is BELOW the fp32 chain's on long k (the
     # f16 MFMA sums 16 products per rounding), its max error about equal; where mode 'f32' picks
     # split-K its chains are shorter and its max error smaller, hence the absolute floor.
     assert e3 <= max(2.0 * e1, 5e-7), (e3, e1)
