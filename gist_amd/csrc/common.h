@@ -58,8 +58,9 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
 // split operands itself (the step driver).  Split operand = [rows][h3_kpad(k)] 32-bit words
 // + one inverse scale (power of two) per row.
 int64_t h3_kpad(int64_t k);
-bool h3_eligible(int64_t m, int64_t n, int64_t k);        // a call that splits its own operands
-bool h3_eligible_kept(int64_t m, int64_t n, int64_t k);   // operands split once, kept by the step
+bool h3_eligible(int64_t m, int64_t n, int64_t k);        // a call that splits its own operands (in mode 1)
+bool h3_eligible_kept(int64_t m, int64_t n, int64_t k);   // operands split once, kept by the step (shape only:
+                                                          // the step's layout checks the mode it is for)
 struct H3Dual {                       // one read of src[rows, cols] -> up to two split operands
     const float *src; int64_t ld; int64_t rows, cols;
     float p; uint64_t seed, offset;   // dropout applied on the fly (p = 0: none), gist_dropout_f32's stream
@@ -80,10 +81,9 @@ int h3_gemm_presplit(const char *name, const uint32_t *sa, const float *inv_a, c
 // gemm_b3.hip: the bf16x3 split projection path (all 24 operand bits, no scales).  Split operand =
 // [rows][b3_kpad(k)] elements of 6 bytes (three bf16 pieces per element, 16-byte chunks per 8 k).
 int h3_mode();                        // 0 fp32 MFMA, 1 f16x3, 2 bf16x3 (gist_gemm_set_mode)
-void h3_mode_override(int mode);      // >= 0: h3_mode() of THIS thread returns it (sizing queries); -1: off
 int64_t b3_kpad(int64_t k);
-bool b3_eligible(int64_t m, int64_t n, int64_t k);
-bool b3_eligible_kept(int64_t m, int64_t n, int64_t k);
+bool b3_eligible(int64_t m, int64_t n, int64_t k);        // (in mode 2)
+bool b3_eligible_kept(int64_t m, int64_t n, int64_t k);   // (shape only, as h3_eligible_kept)
 struct B3Dual {                       // one read of src[rows, cols] -> up to two split operands
     const float *src; int64_t ld; int64_t rows, cols;
     float p; uint64_t seed, offset;   // dropout applied on the fly (p = 0: none), gist_dropout_f32's stream
@@ -136,7 +136,11 @@ struct SpmmLnBwd {
 int spmm_drop(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y, int64_t ldy,
               int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
               const int32_t *row_blocks, int64_t n_row_blocks, const SpmmDrop &dr, hipStream_t st,
-              const void *prepared = nullptr, const SpmmLnBwd *ln = nullptr);
+              const void *prepared = nullptr, bool pairs = true, const SpmmLnBwd *ln = nullptr);
+// gist_spmm_csr_prepared_f32 with the caller's pairs choice
+int spmm_prepared(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y, int64_t ldy,
+                  int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
+                  const int32_t *row_blocks, int64_t n_row_blocks, const void *prepared, hipStream_t st, bool pairs);
 // can a mode-2 call carry SpmmLnBwd, and how many partial rows does it write?
 bool spmm_lnb_takes(int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y, const int32_t *row_blocks,
                     const void *prepared);
@@ -191,16 +195,14 @@ __device__ __forceinline__ void drop_f4(float4 &v, uint64_t idx0, const SpmmDrop
 
 #endif
 // spmm_mfma.hip: the block-dense aggregation kernel behind gist_spmm_csr_blocked_f32 / _prepared_f32
-// (prepared = NULL: every workgroup builds its block's counts itself)
+// (prepared = NULL: every workgroup builds its block's counts itself).  pairs: may the batch have sibling blocks?  false
+// (gist_sage_step with plan->sibling_parts == 0): the prepare kernel looks for none and no pairs launch follows an
+// aggregation; a structure prepared either way is read correctly either way (spmm_prep.h), the choice is speed only.
 int launch_spmm_mfma(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y,
                      int64_t ldy, int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale,
                      int accumulate, const int32_t *row_blocks, int64_t n_row_blocks, const void *prepared,
                      hipStream_t st, const SpmmDrop *dr = nullptr, bool pairs = true);
 int64_t spmm_blocks_bytes(int64_t n_blocks);
-// Pairs of sibling blocks (spmm_mfma.hip): false while a caller that KNOWS its batch has none is issuing launches
-// (gist_sage_step with plan->sibling_parts == 0): the prepare kernel then looks for none and no pairs launch follows
-// an aggregation.  Everybody else: true.
-extern thread_local bool tl_spmm_pairs;
 // spmm_dense32.hip: the block-dense aggregation on the fp32 matrix cores, operands from memory (prepared blocks only)
 bool spmm_dense32_takes(int64_t d, int64_t ldx, int64_t ldy);
 int launch_spmm_dense32(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y,

@@ -522,7 +522,6 @@ int64_t b3_slab_bytes(int64_t m, int64_t n, int64_t k) {
 // enough flops to pay for the pre-pass (~ the f16x3 path's thresholds).  Everything else stays on the
 // fp32 kernel.
 static bool b3_shape_ok(int64_t m, int64_t n, int64_t k, double default_min_gflop) {
-    if (h3_mode() != 2) return false;
     const double t_gflop = tune(GIST_TUNE_H3_MIN_GFLOP), t_tiles = tune(GIST_TUNE_H3_MIN_TILES);
     const double min_gflop = t_gflop > 0.0 ? t_gflop : default_min_gflop;
     const int min_wgs = t_tiles > 0.0 ? (int)t_tiles : 128;
@@ -537,7 +536,7 @@ static bool b3_shape_ok(int64_t m, int64_t n, int64_t k, double default_min_gflo
     if (b3_kpad(k) * 6 >= (1LL << 23)) return false;          // 32-bit DMA byte offsets: 256 rows * pitch
     return true;
 }
-bool b3_eligible(int64_t m, int64_t n, int64_t k) { return b3_shape_ok(m, n, k, 16.0); }
+bool b3_eligible(int64_t m, int64_t n, int64_t k) { return h3_mode() == 2 && b3_shape_ok(m, n, k, 16.0); }
 // (inside the step, operands split once per tensor: measured break-even between 8.6 GFLOP -- the h = 1024
 // projections, 0.595 vs 0.587 ms/step on the fp32 kernel -- and 10.1 GFLOP -- the layer-0 projections at
 // h = 2048, 1.071 vs 1.095)

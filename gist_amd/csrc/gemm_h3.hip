@@ -533,12 +533,8 @@ template __global__ void gemm_h3_kernel<64>(H3Args);
 
 // ---- host side ----------------------------------------------------------------------------
 static std::atomic<int> g_h3_mode{-1};      // -1: read GIST_GEMM_MODE on first use
-// A sizing query "as if the mode were m" (gist_step_h3_workspace_bytes_mode) sets this for the calling
-// thread only: launches of other threads keep seeing the process-wide mode.
-thread_local int tl_mode_override = -1;
 
 int h3_mode() {
-    if (tl_mode_override >= 0) return tl_mode_override;
     int m = g_h3_mode.load(std::memory_order_relaxed);
     if (m < 0) {
         const char *e = getenv("GIST_GEMM_MODE");
@@ -554,7 +550,6 @@ int h3_mode() {
     }
     return m;
 }
-void h3_mode_override(int mode) { tl_mode_override = mode; }
 
 int64_t h3_kpad(int64_t k) { return ceil_div(k, H3_BK) * H3_BK; }
 
@@ -565,7 +560,6 @@ int64_t h3_kpad(int64_t k) { return ceil_div(k, H3_BK) * H3_BK; }
 // --n-hidden 1024: 0.606 -> 0.551 ms/step).
 // Everything else stays on the fp32 kernel.
 static bool h3_shape_ok(int64_t m, int64_t n, int64_t k, double default_min_gflop) {
-    if (h3_mode() != 1) return false;
     const double t_gflop = tune(GIST_TUNE_H3_MIN_GFLOP), t_tiles = tune(GIST_TUNE_H3_MIN_TILES);
     const double min_gflop = t_gflop > 0.0 ? t_gflop : default_min_gflop;
     const int min_tiles = t_tiles > 0.0 ? (int)t_tiles : 64;
@@ -578,7 +572,7 @@ static bool h3_shape_ok(int64_t m, int64_t n, int64_t k, double default_min_gflo
     if (h3_kpad(k) >= (1LL << 22)) return false;
     return true;
 }
-bool h3_eligible(int64_t m, int64_t n, int64_t k) { return h3_shape_ok(m, n, k, 16.0); }
+bool h3_eligible(int64_t m, int64_t n, int64_t k) { return h3_mode() == 1 && h3_shape_ok(m, n, k, 16.0); }
 bool h3_eligible_kept(int64_t m, int64_t n, int64_t k) { return h3_shape_ok(m, n, k, 4.0); }
 
 // workspace: [inv_a: m floats][inv_b: n floats][max bits: m + n] padded to 256 B, then the splits

@@ -894,7 +894,7 @@ int64_t spmm_lnb_units(int64_t n_row_blocks) { return n_row_blocks * l2_split_fo
 int spmm_drop(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y, int64_t ldy,
               int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
               const int32_t *row_blocks, int64_t n_row_blocks, const SpmmDrop &dr, hipStream_t st,
-              const void *prepared, const SpmmLnBwd *ln) {
+              const void *prepared, bool pairs, const SpmmLnBwd *ln) {
     GIST_REQUIRE(n_rows >= 0 && d >= 0, "gist_spmm_csr_drop_f32: negative size");
     if (n_rows == 0 || d == 0) return GIST_OK;
     GIST_REQUIRE(rowptr && x && y, "gist_spmm_csr_drop_f32: null pointer");
@@ -917,7 +917,7 @@ int spmm_drop(const int32_t *rowptr, const int32_t *col, const float *x, int64_t
                                    row_blocks, n_row_blocks, prepared, st, &dr);
     if (mfma_takes(d, ldx, ldy, x, y, row_blocks))
         return launch_spmm_mfma(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
-                                row_blocks, n_row_blocks, prepared, st, &dr);
+                                row_blocks, n_row_blocks, prepared, st, &dr, pairs);
     if (row_blocks != nullptr && lds2_takes(d, ldx, ldy, x, y))
         return launch_spmm_lds2(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
                                 row_blocks, n_row_blocks, st, &dr);
@@ -967,7 +967,7 @@ extern "C" int gist_spmm_csr_drop_lnbwd_f32(const int32_t *rowptr, const int32_t
     SpmmLnBwd ln{};
     ln.yhat = yhat; ln.ldy = ldyh; ln.rstd = rstd; ln.dy = dy; ln.lddy = lddy; ln.col_partials = col_partials; ln.relu = relu;
     return spmm_drop(rowptr, col, x, ldx, const_cast<float *>(y), ldy, n_rows, d, nullptr, src_scale, 1, row_blocks,
-                     n_row_blocks, dr, as_stream(stream), nullptr, &ln);
+                     n_row_blocks, dr, as_stream(stream), nullptr, true, &ln);
 }
 
 extern "C" int64_t gist_spmm_lnb_units(int64_t n_row_blocks) { return n_row_blocks > 0 ? gist::spmm_lnb_units(n_row_blocks) : 0; }
@@ -1054,12 +1054,12 @@ extern "C" int gist_spmm_blocks_prepare(const int32_t *rowptr, const int32_t *co
                                       nullptr, as_stream(stream));
 }
 
-extern "C" int gist_spmm_csr_prepared_f32(const int32_t *rowptr, const int32_t *col, const float *x,
-                                          int64_t ldx, float *y, int64_t ldy, int64_t n_rows, int64_t d,
-                                          const float *out_scale, const float *src_scale, int accumulate,
-                                          const int32_t *row_blocks, int64_t n_row_blocks,
-                                          const void *prepared, gist_stream_t stream) {
-    using namespace gist;
+namespace gist {
+// gist_spmm_csr_prepared_f32 for a caller that knows whether the batch has sibling blocks (pairs = false: the pairs
+// launch is skipped; a structure prepared with pairs is still read correctly, spmm_prep.h)
+int spmm_prepared(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y, int64_t ldy,
+                  int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
+                  const int32_t *row_blocks, int64_t n_row_blocks, const void *prepared, hipStream_t st, bool pairs) {
     GIST_REQUIRE(n_rows >= 0 && d >= 0, "gist_spmm_csr_prepared_f32: negative size");
     if (n_rows == 0 || d == 0) return GIST_OK;
     GIST_REQUIRE(rowptr && x && y && prepared, "gist_spmm_csr_prepared_f32: null pointer");
@@ -1070,11 +1070,21 @@ extern "C" int gist_spmm_csr_prepared_f32(const int32_t *rowptr, const int32_t *
     // below the bf16x3 matrix-core kernel's widths (and for unaligned rows): the fp32 block-dense kernel
     if (aligned16(prepared) && spmm_dense32_takes(d, ldx, ldy))
         return launch_spmm_dense32(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
-                                   row_blocks, n_row_blocks, prepared, as_stream(stream));
+                                   row_blocks, n_row_blocks, prepared, st);
     // widths / alignments the matrix-core kernel does not take: the unprepared entry point decides
     if (!spmm_prepared_takes(d, ldx, ldy, x, y) || !aligned16(prepared))
         return gist_spmm_csr_blocked_f32(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                                         accumulate, row_blocks, n_row_blocks, stream);
+                                         accumulate, row_blocks, n_row_blocks, st);
     return launch_spmm_mfma(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
-                            row_blocks, n_row_blocks, prepared, as_stream(stream));
+                            row_blocks, n_row_blocks, prepared, st, nullptr, pairs);
+}
+}  // namespace gist
+
+extern "C" int gist_spmm_csr_prepared_f32(const int32_t *rowptr, const int32_t *col, const float *x,
+                                          int64_t ldx, float *y, int64_t ldy, int64_t n_rows, int64_t d,
+                                          const float *out_scale, const float *src_scale, int accumulate,
+                                          const int32_t *row_blocks, int64_t n_row_blocks,
+                                          const void *prepared, gist_stream_t stream) {
+    return gist::spmm_prepared(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate, row_blocks,
+                               n_row_blocks, prepared, gist::as_stream(stream), true);
 }

@@ -432,9 +432,10 @@ __device__ __forceinline__ void mf_build_block(const MfArgs &a, int rbk, int r0,
 // units cost registers this code does not have (128 at 1024 threads): in one kernel, even behind a branch that is never
 // taken, they moved the register allocation of the common path -- 49 us per D = 4096 launch on a batch WITHOUT pairs
 // against 36 (88 spilled registers against 3).
-// PP = false (spmm_csr_mfma_kernel: structures prepared WITHOUT pairs, or not prepared): no pair descriptor is read, no
-// rem_cnt carries bit 8, the edge-list walk knows no pair ranges -- the code every batch without sibling parts runs is the
-// code it ran before pairs existed (this kernel answers epilogue edits with another register allocation: NEGATIVES.md).
+// PP = false (spmm_csr_mfma_kernel: the caller's batch has no pairs, or the structure is not prepared): no pair descriptor
+// is read, the edge-list walk knows no pair ranges, and a prepared row whose rem_cnt carries MF_PAIR_FLAG (a structure
+// prepared with pairs) is gathered in full -- the code every batch without sibling parts runs is the code it ran before
+// pairs existed, plus that one test (this kernel answers epilogue edits with another register allocation: NEGATIVES.md).
 template <bool PREP, int DROP, bool PAIRK, bool PP>
 __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem, int bid, int groups) {
     // ---- workgroup -> (block, column group); the groups of one block stay on one XCD ----
@@ -850,7 +851,8 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
         for (int i = 0; i < RW; ++i) {
             const int r = wave + MF_WAVES * i;
             const int rc = r < nloc ? __builtin_amdgcn_readfirstlane(rem_cnt[r]) : 0;
-            rcnt[i] = (PP && rc >= 0) ? (rc & 0xff) : rc;
+            // (a prepared row with edges in a pair image this kernel does not apply is gathered in full: spmm_prep.h)
+            rcnt[i] = PP ? (rc >= 0 ? (rc & 0xff) : rc) : (PREP && rc >= MF_PAIR_FLAG ? -1 : rc);
         }
 #pragma unroll
         for (int pp = 0; pp < RW / 2; ++pp) rsc[pp] = sc[min(wave + MF_WAVES * (2 * pp + half), MF_ROWS - 1)];
@@ -986,8 +988,6 @@ static int mf_set_lds(const void *kernel, const char *name) {
 }
 
 // the block records, then -- batches of <= MF_PAIR_BLOCKS blocks -- MF_PAIRS pair images per block
-thread_local bool tl_spmm_pairs = true;
-
 int64_t spmm_blocks_bytes(int64_t n_blocks) {
     if (n_blocks <= 0) return 0;
     return n_blocks * (int64_t)MF_PREP_STRIDE + (n_blocks <= MF_PAIR_BLOCKS ? n_blocks * (int64_t)(MF_PAIRS * MF_IMG_BYTES) : 0);
@@ -1000,7 +1000,7 @@ int launch_spmm_blocks_prepare(const int32_t *rowptr, const int32_t *col, const 
                                int64_t n_row_blocks, void *prepared, void *prepared2, hipStream_t st, bool pairs) {
     MfArgs a{};
     a.rowptr = rowptr; a.col = col; a.n_rows = (int)n_rows; a.row_blocks = row_blocks;
-    a.pairs = (pairs && tl_spmm_pairs) ? 1 : 0;
+    a.pairs = pairs ? 1 : 0;
     const int64_t nb = row_blocks ? n_row_blocks : ceil_div(n_rows, MF_ROWS);
     a.n_blocks = (int)nb;
     if (nb <= 0) return GIST_OK;
@@ -1029,7 +1029,7 @@ int launch_spmm_mfma(const int32_t *rowptr, const int32_t *col, const float *x, 
     a.n_rows = (int)n_rows; a.d = (int)d; a.out_scale = out_scale; a.src_scale = src_scale;
     a.accumulate = accumulate; a.row_blocks = row_blocks;
     a.prep = static_cast<const unsigned char *>(prepared);
-    a.pairs = (pairs && tl_spmm_pairs && prepared != nullptr && row_blocks != nullptr && n_row_blocks <= MF_PAIR_BLOCKS) ? 1 : 0;
+    a.pairs = (pairs && prepared != nullptr && row_blocks != nullptr && n_row_blocks <= MF_PAIR_BLOCKS) ? 1 : 0;
     a.dr = dr ? *dr : SpmmDrop{};
     GIST_REQUIRE(a.dr.ld < (1LL << 22), "gist_spmm_csr_drop_f32: mask pitch of 2^22 elements or more");
     const int mode = dr ? dr->mode : 0;

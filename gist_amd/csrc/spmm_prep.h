@@ -4,9 +4,10 @@
 // One record of MF_PREP_STRIDE bytes per block:
 //   the count image       [k chunk 16][row 128][8 k] bf16: the block's edge counts (<= 256, exact in bf16)
 //   int rem_cnt[128]      rem_cnt[r] >= 0: bits 0-7 = listed outside neighbours, bit 8 (MF_PAIR_FLAG) = the row has
-//                         edges in a pair image (a consumer without the pair images gathers such a row in full);
-//                         -1: gather the row in full; -2: walk the edge list for the neighbours outside the block and
-//                         its pairs
+//                         edges in a pair image; -1: gather the row in full; -2: walk the edge list for the neighbours
+//                         outside the block and its pairs.  Every reader that does not apply the pair images treats a
+//                         flagged row as -1, so a structure prepared with or without pairs is correct for any reader
+//                         (the caller's pairs choice is speed only)
 //   int rem_col[128][8]   the listed outside neighbours, CSR order
 //   int pair[2][2]        (first source row, source rows) of the block's pairs
 // When the batch is small enough to look for pairs (spmm_mfma.hip), MF_PAIRS count images per block, the pair

@@ -100,11 +100,6 @@ struct Scope {   // records start now, stop at scope exit
         : t(t_), slot(timer_begin(t_, kind, m, n, k, s_)), s(s_) {}
     ~Scope() { timer_end(t, slot, s); }
 };
-struct PairsHint {     // the aggregations below look for sibling blocks only if the plan says the batch may have them
-    bool prev;
-    explicit PairsHint(bool on) : prev(tl_spmm_pairs) { tl_spmm_pairs = on; }
-    ~PairsHint() { tl_spmm_pairs = prev; }
-};
 struct ActiveTimer {   // kernels below the entry points see the armed timer for this call only
     explicit ActiveTimer(gist_timer *t) { tl_timer = t; }
     ~ActiveTimer() { tl_timer = nullptr; }
@@ -135,12 +130,12 @@ inline int bound_shift(double bound) {      // 2^shift * bound <= 2^13
     return s < -60 ? -60 : (s > 60 ? 60 : s);
 }
 
-// Deterministic carve-up of the workspace from the plan's shapes; base may be NULL (sizing).
-H3Step h3_layout(const gist_step_plan *p, char *base) {
+// Deterministic carve-up of the workspace from the plan's shapes in GEMM mode `mode`; base may be NULL (sizing).
+H3Step h3_layout(const gist_step_plan *p, char *base, int mode) {
     H3Step h{};
     const int L1 = p->n_layers;
     const int64_t n = p->n_max;
-    if (gist_gemm_get_mode() != 1 || n <= 0) return h;
+    if (mode != 1 || n <= 0) return h;
     int64_t off = 0;
     auto take = [&](int64_t bytes) {
         char *q = base ? base + off : nullptr;
@@ -199,11 +194,11 @@ struct B3Step {
     int64_t bytes;
 };
 
-B3Step b3_layout(const gist_step_plan *p, char *base) {
+B3Step b3_layout(const gist_step_plan *p, char *base, int mode) {
     B3Step h{};
     const int L1 = p->n_layers;
     const int64_t n = p->n_max;
-    if (gist_gemm_get_mode() != 2 || n <= 0) return h;
+    if (mode != 2 || n <= 0) return h;
     int64_t off = 0;
     auto take = [&](int64_t bytes) {
         char *q = base ? base + off : nullptr;
@@ -347,30 +342,26 @@ extern "C" int64_t gist_step_col_partials_floats(const gist_step_plan *plan) {
 }
 
 extern "C" int64_t gist_step_h3_workspace_bytes(const gist_step_plan *plan) {
-    if (!plan || plan->n_layers < 1 || plan->n_layers > GIST_MAX_LAYERS) return 0;
-    if (gist_gemm_get_mode() == 2) return b3_layout(plan, nullptr).bytes;
-    return h3_layout(plan, nullptr).bytes;
+    return gist_step_h3_workspace_bytes_mode(plan, gist_gemm_get_mode());
 }
 
 // the same for a given GEMM mode, without touching the process-wide one (a caller that sizes for every
 // mode it may switch to must not change the arithmetic of launches other threads issue meanwhile)
 extern "C" int64_t gist_step_h3_workspace_bytes_mode(const gist_step_plan *plan, int mode) {
-    if (mode < 0 || mode > 2) return 0;
-    h3_mode_override(mode);
-    const int64_t need = gist_step_h3_workspace_bytes(plan);
-    h3_mode_override(-1);
-    return need;
+    if (!plan || plan->n_layers < 1 || plan->n_layers > GIST_MAX_LAYERS || mode < 0 || mode > 2) return 0;
+    return mode == 2 ? b3_layout(plan, nullptr, mode).bytes : h3_layout(plan, nullptr, mode).bytes;
 }
 
 // The step's aggregations: the blocked kernels when the batch comes with its locality blocks; with the
-// batch's prepared block structure (`prepared`: this orientation's) the matrix-core kernel skips its set-up.
+// batch's prepared block structure (`prepared`: this orientation's) the matrix-core kernel skips its set-up,
+// and looks for sibling blocks only if the plan says the batch may have them.
 static int step_spmm(const gist_step_plan *p, const int32_t *rowptr, const int32_t *col, const float *x,
                      int64_t ldx, float *y, int64_t ldy, int64_t n, int64_t d, const float *out_scale,
                      const float *src_scale, int accumulate, const void *prepared, gist_stream_t s) {
     if (p->row_blocks != nullptr && p->n_row_blocks > 0) {
         if (prepared != nullptr)
-            return gist_spmm_csr_prepared_f32(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale,
-                                              accumulate, p->row_blocks, p->n_row_blocks, prepared, s);
+            return spmm_prepared(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale, accumulate, p->row_blocks,
+                                 p->n_row_blocks, prepared, as_stream(s), p->sibling_parts != 0);
         return gist_spmm_csr_blocked_f32(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale,
                                          accumulate, p->row_blocks, p->n_row_blocks, s);
     }
@@ -413,7 +404,6 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
     const int L1 = p->n_layers;
     hipStream_t st = as_stream(s);
     ActiveTimer active(p->timer);
-    PairsHint pairs_hint(p->sibling_parts != 0);
     const bool train = (flags & GIST_STEP_TRAIN) != 0;
     const bool drop = train && p->p_drop > 0.f;
     // Phases (gist_hip.h, GIST_STEP_PHASE_*): a caller whose loop is `pred = model(g); loss = f(pred); loss.backward();
@@ -432,17 +422,19 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
                  "gist_sage_step: one GIST_STEP_PHASE_* per call (or none / all three)");
     const bool dlogits_given = (flags & GIST_STEP_DLOGITS_GIVEN) != 0;
     const bool blocked = p->row_blocks != nullptr && p->n_row_blocks > 0;
+    const bool pairs = p->sibling_parts != 0;      // may the batch have sibling blocks (speed only: gist_hip.h)
 
     // Split operands kept by the step (see gist_step_plan.h3_workspace); off = per-call splits
     // inside gist_gemm_*.
+    const int gemm_mode = gist_gemm_get_mode();
     H3Step h3{};
     if (p->h3_workspace != nullptr && aligned16(p->h3_workspace) && n <= p->n_max) {
-        h3 = h3_layout(p, static_cast<char *>(p->h3_workspace));
+        h3 = h3_layout(p, static_cast<char *>(p->h3_workspace), gemm_mode);
         if (h3.bytes > p->h3_workspace_bytes) h3 = H3Step{};
     }
     B3Step b3{};
     if (p->h3_workspace != nullptr && aligned16(p->h3_workspace) && n <= p->n_max) {
-        b3 = b3_layout(p, static_cast<char *>(p->h3_workspace));
+        b3 = b3_layout(p, static_cast<char *>(p->h3_workspace), gemm_mode);
         if (b3.bytes > p->h3_workspace_bytes) b3 = B3Step{};
     }
 
@@ -589,7 +581,7 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
             if (do_fwd)
             GIST_TRY(launch_spmm_blocks_prepare(p->rowptr, p->col, train ? p->t_rowptr : nullptr,
                                                 train ? p->t_col : nullptr, n, p->row_blocks, p->n_row_blocks,
-                                                base, train ? base + one : nullptr, st));
+                                                base, train ? base + one : nullptr, st, pairs));
             prep_fwd = base;
             prep_bwd = train ? base + one : nullptr;
         }
@@ -609,7 +601,7 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
                 dr.y_base = offs[k] + (uint64_t)l.n_in; dr.src_base = 0; dr.ld = 2 * l.n_in;
                 GIST_TRY(spmm_drop(p->rowptr, p->col, p->hsrc[k], p->ld_hsrc[k], l.Z + l.n_in, l.ldz, n, l.n_in,
                                    p->norm, nullptr, 0, blocked ? p->row_blocks : nullptr, p->n_row_blocks, dr, st,
-                                   prep_fwd));
+                                   prep_fwd, pairs));
             } else {
                 GIST_TRY(step_spmm(p, p->rowptr, p->col, l.Z, l.ldz, l.Z + l.n_in, l.ldz, n, l.n_in,
                                    p->norm, nullptr, 0, prep_fwd, s));
@@ -784,7 +776,8 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
                     dr.mode = 2; dr.p = p->p_drop; dr.scale = keep; dr.sm = sm;
                     dr.y_base = offs[k]; dr.src_base = offs[k] + (uint64_t)l.n_in; dr.ld = 2 * l.n_in;
                     GIST_TRY(spmm_drop(p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n,
-                                       l.n_in, nullptr, p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, prep_bwd));
+                                       l.n_in, nullptr, p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, prep_bwd,
+                                       pairs));
                 } else {
                     if (drop)
                         GIST_TRY(gist_dropout_f32(p->dZ, 2 * l.n_in, n, 2 * l.n_in, p->p_drop, p->seed,
@@ -843,7 +836,8 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
                     dr.mode = 2; dr.p = p->p_drop; dr.scale = keep; dr.sm = sm;
                     dr.y_base = offs[k]; dr.src_base = offs[k] + (uint64_t)l.n_in; dr.ld = 2 * l.n_in;
                     GIST_TRY(spmm_drop(p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n,
-                                       l.n_in, nullptr, p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, prep_bwd));
+                                       l.n_in, nullptr, p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, prep_bwd,
+                                       pairs));
                 } else {
                     if (drop)
                         GIST_TRY(gist_dropout_f32(p->dZ, 2 * l.n_in, n, 2 * l.n_in, p->p_drop, p->seed,
@@ -945,7 +939,7 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
                 }
                 GIST_TRY(spmm_drop(p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n,
                                    l.n_in, nullptr, p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, prep_bwd,
-                                   with_ln ? &ln : nullptr));
+                                   pairs, with_ln ? &ln : nullptr));
             } else {
                 GIST_TRY(step_spmm(p, p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ,
                                    2 * l.n_in, n, l.n_in, nullptr, p->norm, 1, prep_bwd, s));

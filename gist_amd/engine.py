@@ -24,9 +24,6 @@ import torch
 from . import hip
 
 
-_FORCE_PAIRS = os.environ.get('GIST_SPMM_PAIRS') == '1'      # dev: every batch is prepared with pairs / fine blocks
-
-
 def _round_up(x, m):
     return (x + m - 1) // m * m
 
@@ -229,9 +226,6 @@ class SageEngine(object):
         self.plan = None
         self._spmm_prep = None      # prepared block structure of the current batch (native step)
         self._plan_keep = None
-        # inference-only reassociation of the last layer (see forward); GIST_PROJECT_FIRST=0
-        # keeps the reference's aggregate-then-project order
-        self.project_first = os.environ.get('GIST_PROJECT_FIRST', '1') != '0'
 
     # ------------------------------------------------------------------
     def attach_batcher(self, batcher):
@@ -435,7 +429,7 @@ class SageEngine(object):
         if train and phase == 0:
             self.arena.step += 1
         rb = b.row_blocks
-        P.sibling_parts = 1 if (b.siblings or _FORCE_PAIRS) else 0
+        P.sibling_parts = 1 if b.siblings else 0
         if rb is not None and rb.numel() > 1:
             P.row_blocks, P.n_row_blocks = rb.data_ptr(), rb.numel() - 1
             # room for the batch's prepared block structure (include/gist_hip.h, spmm_prepared):
@@ -601,7 +595,7 @@ class SageEngine(object):
         pf = self._prep_fwd
         for k, (i, o) in enumerate(self.dims):
             z = self.Z[k][:n]
-            if not training and o < i and k == self.L1 - 1 and self.project_first:
+            if not training and o < i and k == self.L1 - 1:
                 # Inference, narrowing layer (H -> C): [h | A^h] W^T = h W1^T + A^(h W2^T), so
                 # aggregate the C-wide projection instead of the H-wide activations (full-graph
                 # evaluation: one D=4096 pass over 115 M edges becomes a D=41 pass).  Same

@@ -170,7 +170,7 @@ class ModuleEngine(object):
         ln = layers[0].use_lynorm if len(layers) > 1 else False
         self.engine = eng = SageEngine(dims, ln, layers[0].p_drop, it.n_max, dev, seed=getattr(model, '_drop_seed', 0))
         eng.arena.adopt_module(model)
-        eng.prefetch = os.environ.get('GIST_MODULE_PREFETCH', '1') != '0'
+        eng.prefetch = True
         it.bind(eng)
         if eng.plan is None:
             raise RuntimeError('gist_amd: no native step plan for this model')

@@ -279,8 +279,6 @@ class ClusterIter(object):
                                        in_batch_edges_inside_parts=round(in_batch_inside, 4),
                                        outside_neighbours_per_batch_row=round(outside_in_batch, 3))
             self.locality = in_batch_inside >= 0.8 and outside_in_batch <= 4.0
-            if os.environ.get('GIST_SPMM_LOCALITY') in ('0', '1'):      # dev override
-                self.locality = os.environ['GIST_SPMM_LOCALITY'] == '1'
 
     def bind(self, engine, native=True):
         """Feed `engine`.  native=True attaches the C++ step driver: batches are then only

@@ -80,7 +80,7 @@ class FullGraphEvaluator(object):
         # D = 4096 against 0.6-2.2 ns per gathered edge (cached neighbour parts ... uniform) = break-even ~300-1000.
         # A partition of a real graph cuts few block pairs heavily; the uniform block model cuts all pairs thinly
         # (10 edges per pair) and keeps the gathers.  0 = off.
-        self.pair_min_edges = int(pair_min_edges) if os.environ.get('GIST_EVAL_PAIRS', '1') != '0' else 0
+        self.pair_min_edges = int(pair_min_edges)
         self.pair_bytes = int(pair_bytes)
         self.use_chains = os.environ.get('GIST_EVAL_CHAINS', '1') != '0'      # (0: one launch per pair rank, round 4's form)
         self.row_cuts = list(range(0, n, self.row_block)) + [n]
@@ -92,7 +92,7 @@ class FullGraphEvaluator(object):
             node_blocks = getattr(g, 'node_blocks', None)      # a dataset whose ids are ordered by part says so
         if node_blocks is False:
             node_blocks = None                                  # explicit opt-out: one gather pass
-        if node_blocks is not None and blocked and os.environ.get('GIST_EVAL_SPLIT', '1') != '0':
+        if node_blocks is not None and blocked:
             self._split_graph(np.asarray(node_blocks, np.int64))
         self.logits = torch.empty(n, self.ldc, **f32)
         self.pbuf = torch.empty(n, self.ldc, **f32) if self.project_first else None
@@ -108,7 +108,7 @@ class FullGraphEvaluator(object):
         # not change, the parameters do not enter).  Kept after the first forward ([N, F] floats: 370 MB for the
         # Reddit-like graph) and copied into the row blocks afterwards -- the same values bit for bit.
         # invalidate_input_aggregation() after changing g.ndata['feat'] in place.
-        self.cache_input_aggregation = bool(cache_input_aggregation) and os.environ.get('GIST_EVAL_CACHE_AH0', '1') != '0'
+        self.cache_input_aggregation = bool(cache_input_aggregation)
         self._ah0 = None
         self._ah0_ready = False
 

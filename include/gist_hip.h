@@ -799,7 +799,9 @@ typedef struct gist_step_plan {
      * edges (one community cut in two): the batch's block structure is prepared WITH pairs (gist_spmm_blocks_prepare) and
      * every wide aggregation is followed by its pairs launch.  0 = the caller knows there are none (gist_amd: from the
      * part-to-part edge counts of the training graph, once per run): no search, no second launch.  Either value is
-     * correct for any batch; 0 on a batch that has sibling parts is the slow path (their rows walk their edge lists). */
+     * correct for any batch, and the phase calls of one batch may pass different values (a structure prepared with
+     * pairs by the FORWARD call is read correctly by a BACKWARD call with 0, and the other way round): the value only
+     * affects speed.  0 on a batch that has sibling parts is the slow path (their rows walk their edge lists). */
     int32_t sibling_parts;
 } gist_step_plan;
 

@@ -702,6 +702,71 @@ def test_spmm_sibling_parts_as_dense_pairs(hip, d):
     close(xft, reff)
 
 
+def _phased_sibling_step(fwd_pairs, bwd_pairs):
+    """One training iteration of gist_sage_step as its three phase calls (the module path's form) on a batch with two pairs
+    of sibling parts, width 2048 (the layer-1 aggregations on the prepared matrix-core kernel), plan.sibling_parts =
+    `fwd_pairs` on the forward call (which prepares the block structure) and `bwd_pairs` on the backward call (which reads
+    it).  Returns (loss, gradients, parameters after Adam, rows of the forward structure flagged MF_PAIR_FLAG)."""
+    import random
+    from gist_amd import _lib
+    from gist_amd.graph import Graph
+    from gist_amd.engine import SageEngine, dims_for
+    from gist_amd.sampler import EngineClusterIter
+    n, cuts, src, dst = _sibling_graph(np.random.RandomState(5), siblings=((3, 7), (10, 11)), cross_per_row=8)
+    g = Graph.from_edges(src, dst, n)
+    gen = torch.Generator().manual_seed(5)
+    g.ndata['feat'] = torch.randn(n, 32, generator=gen)
+    g.ndata['label'] = torch.randint(0, 6, (n,), generator=gen)
+    ones = torch.ones(n, dtype=torch.bool)
+    g.ndata['train_mask'], g.ndata['val_mask'], g.ndata['test_mask'] = ones, ~ones, ~ones
+    par_li = [np.arange(cuts[p], cuts[p + 1], dtype=np.int64) for p in range(len(cuts) - 1)]
+    random.seed(4)
+    it = EngineClusterIter('siblings', g, len(par_li), len(par_li), np.arange(n, dtype=np.int64), par_li=par_li,
+                           device=torch.device(DEV))      # one batch: every part
+    dims = dims_for(32, 2048, 6, 2)
+    eng = SageEngine(dims, True, 0.0, it.n_max, torch.device(DEV), seed=11)
+    gen = torch.Generator().manual_seed(1)
+    for k, (i, o) in enumerate(dims):
+        eng.arena.W[k].copy_((torch.rand(o, 2 * i, generator=gen) - 0.5) * 0.3)
+        eng.arena.b[k].copy_((torch.rand(o, generator=gen) - 0.5) * 0.3)
+    it.bind(eng)
+    b = next(iter(it))
+    assert b.row_blocks is not None and b.row_blocks.numel() == len(cuts), 'test data: the batch is not blocked'
+    b.siblings = bool(fwd_pairs)
+    eng._native_step(b, 0.01, 0.0, train=True, phase=_lib.GIST_STEP_PHASE_FORWARD)
+    assert eng.plan.sibling_parts == fwd_pairs
+    loss = eng.loss.clone()
+    # rem_cnt of the forward structure's records (spmm_prep.h: at MF_PREP_REMC = the 32-KiB count image, 128 ints)
+    remc_off, stride = 16 * 128 * 16, int(_lib.load().gist_spmm_block_image_bytes())
+    assert stride == remc_off + 128 * 4 + 128 * 8 * 4 + 16
+    nb = b.row_blocks.numel() - 1
+    rec = eng._spmm_prep[:nb * stride].view(nb, stride)
+    remc = rec[:, remc_off:remc_off + 128 * 4].contiguous().view(torch.int32).cpu().numpy()
+    flagged = int((remc >= 0x100).sum())
+    eng.plan.sibling_parts = bwd_pairs
+    eng._native_step(b, 0.01, 0.0, train=True, phase=_lib.GIST_STEP_PHASE_BACKWARD)
+    grads = eng.arena.grads.clone()
+    eng._native_step(b, 0.01, 0.0, train=True, phase=_lib.GIST_STEP_PHASE_OPTIMIZER)
+    torch.cuda.synchronize()
+    return loss, grads, eng.arena.params.clone(), flagged
+
+
+def test_sibling_parts_may_differ_between_the_phase_calls(hip):
+    """plan.sibling_parts only affects speed: the structure the FORWARD call prepares with pairs is read correctly by a
+    BACKWARD call without them (the kernel without pair images gathers a flagged row in full), and the other way round.
+    Against the consistent (1, 1) iteration: the flagged rows are summed in another order, so to fp32 rounding (the bounds
+    of test_native_step_fused_equals_unfused)."""
+    ref = _phased_sibling_step(1, 1)
+    assert ref[3] > 0, 'test data: no row of the forward structure has edges in a pair image'
+    for fwd, bwd in ((1, 0), (0, 1)):
+        loss, grads, params, flagged = _phased_sibling_step(fwd, bwd)
+        assert (flagged > 0) == (fwd == 1)
+        assert abs(loss.item() - ref[0].item()) < 2e-6 * max(1.0, abs(ref[0].item())), (fwd, bwd)
+        assert (grads - ref[1]).abs().max().item() < 1e-4 * max(1.0, ref[1].abs().max().item()), (fwd, bwd)
+        d = (params - ref[2]).abs()
+        assert float((d > 1e-5).float().mean().item()) < 1e-3 and d.max().item() < 0.02, (fwd, bwd)
+
+
 def _spmm_blocked_case(hip, n, d, deg, hub, blocks, prepared=False):
     rs = np.random.RandomState(n + d)
     # locality: most edges inside chunks of ~100 rows
