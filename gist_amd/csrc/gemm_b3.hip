@@ -37,6 +37,9 @@
 // chunks c and c + 3, and 16 B slot index mod 16 = (12 row + (c ^ swap)) mod 16 takes 16 different
 // values over such a group (exhaustive check over the 3 pieces x 2 group kinds; no rotation by whole
 // 64-byte pieces can do it, the slot index mod 4 would repeat).
+// Outputs with at least 256 tiles of 256 x 256 that run as one k slice take a 256 x 256 x 32 sibling
+// (gemm_b3_wide_kernel, below): same image, a third less staged traffic per flop, fewer rounds;
+// bit for bit the same C.
 #include <stdlib.h>
 #include <string.h>
 
@@ -428,6 +431,213 @@ __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
         }
 }
 
+// ---- the 256 x 256 x 32 tile ----------------------------------------------------------------------
+// For outputs of at least 256 such tiles that run as one k slice (the backward projections of a
+// 4096-wide hidden layer).  Same split operands, same DMA image, same 8 waves in 4 x 2 and the same
+// one workgroup per CU; the wave tile is 64 x 128 (4 x 8 MFMA tiles, 128 accumulator registers), so
+// a full fragment set (48 + 96 registers) no longer fits next to the accumulators.  The wave keeps
+// its A fragments (a1, a2, a3 of 4 slabs) and streams B two 16-column slabs at a time: per slab pair,
+// the six terms in the narrow kernel's order, 8 MFMAs each (an accumulator every 8th MFMA), and each
+// B piece is re-read for the next pair right after the term that last uses it (b1 after a1.b1, b2
+// after a1.b2, b3 after a1.b3).  Every fragment is read once per k tile: 36 ds_read_b128 per 192
+// MFMAs instead of 24 per 96.  Every accumulator still sees k tiles in ascending order and the six
+// terms in the same order, so C is bit for bit the narrow kernel's.
+// LDS: two B images do fit with ONE A image (48 + 2 x 48 = 144 KiB), and A is read early: all of
+// A_t is in registers once the k step's third term has been issued.  Two barriers per k step:
+//   P (after the first slab pair's third term): A_t and B_{t-1} are free -> DMA A_{t+1}, B_{t+1}
+//   Q (after the last slab pair's third term):  A_{t+1}, B_{t+1} complete -> read a2, a3 of A_{t+1}
+//     (dead after a2.b2), then the first slab pair of B_{t+1} piece by piece, then a1 of A_{t+1}
+// The DMA has the 144 MFMAs between P and Q to land.
+constexpr int B3W_TN = 256;
+constexpr int B3W_B_BYTES = B3W_TN * B3_KT_BYTES;                // 48 KiB
+constexpr int B3W_LDS_BYTES = B3_A_BYTES + 2 * B3W_B_BYTES;      // 144 KiB
+
+__global__ __launch_bounds__(B3_THREADS, 1) void gemm_b3_wide_kernel(B3Args g) {
+    extern __shared__ __attribute__((aligned(16))) char b3_smem[];
+    constexpr int NI = 4, NJ = 8;                 // 16-row slabs per wave: 64 x 128 wave tile
+    const int nwg = g.dp_tiles;
+    const int orig = blockIdx.x;
+    const int qd = nwg / kXcds, rm = nwg % kXcds, xcd = orig % kXcds;
+    const int L = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + orig / kXcds;
+    constexpr int GM = 8;
+    const int width = GM * g.tiles_n;
+    const int group = L / width;
+    const int first_m = group * GM;
+    const int gsz = min(g.tiles_m - first_m, GM);
+    const int bm = first_m + (L % width) % gsz;
+    const int bn = (L % width) / gsz;
+    const int row0 = bm * B3_TM, col0 = bn * B3W_TN;
+    const int n_kt = g.kpad / B3_BK;
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int rr = lane & 15, kg = lane >> 4;
+
+    b3_f32x4 acc[NI][NJ];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
+
+    constexpr int NWAVES = B3_THREADS / 64;
+    constexpr int DA = B3_TM / 16 * 3 / NWAVES, DB = B3W_TN / 16 * 3 / NWAVES;
+    uint32_t offA[DA], offB[DB];
+    b3_dma_offsets<DA>(g.lda, g.m, row0, DA * wave, lane, offA);
+    b3_dma_offsets<DB>(g.ldb, g.n, col0, DB * wave, lane, offB);
+    const char *originA = reinterpret_cast<const char *>(g.a) + (int64_t)row0 * g.lda * 6;
+    const char *originB = reinterpret_cast<const char *>(g.b) + (int64_t)col0 * g.ldb * 6;
+    auto dma = [&](int bbuf, int kt) {
+        b3_dma_image<DA>(originA + (int64_t)kt * B3_KT_BYTES, offA, b3_smem, DA * wave);
+        b3_dma_image<DB>(originB + (int64_t)kt * B3_KT_BYTES, offB, b3_smem + B3_A_BYTES + bbuf * B3W_B_BYTES,
+                         DB * wave);
+    };
+
+    // fragment addresses as in gemm_b3_kernel: one per (image, piece), the slab in the offset field
+    const char *fa[3], *fb[2][3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        const int c = 3 * kg + p;
+        const int in_slab = (rr * 12 + (c ^ ((rr >> 3) << 1))) * 16;
+        fa[p] = b3_smem + wm * NI * 3072 + in_slab;
+#pragma unroll
+        for (int st = 0; st < 2; ++st) fb[st][p] = b3_smem + B3_A_BYTES + st * B3W_B_BYTES + wn * NJ * 3072 + in_slab;
+    }
+
+    // A wave whose 64 rows all lie past the end of C stages its share of the images and meets the
+    // barriers, nothing else.  The loop is compiled once per kind of wave: with a run-time test around
+    // each block the compiler's wait counts at the top of the k step turn conservative (lgkmcnt(0)
+    // on the a1 reads just issued).
+    auto body = [&](auto live_c) {
+        constexpr bool live = decltype(live_c)::value;
+        bf16x8 a[NI][3], b[2][3];                     // b: piece p of the two slabs of the current pair
+        auto read_a = [&](auto p_c) {
+            constexpr int p = decltype(p_c)::value;
+            if constexpr (!live) return;
+#pragma unroll
+            for (int i = 0; i < NI; ++i) a[i][p] = *reinterpret_cast<const bf16x8 *>(fa[p] + i * 3072);
+        };
+        auto read_b = [&](auto st_c, auto pair_c, auto p_c) {
+            constexpr int st = decltype(st_c)::value, pair = decltype(pair_c)::value, p = decltype(p_c)::value;
+            if constexpr (!live) return;
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) b[jj][p] = *reinterpret_cast<const bf16x8 *>(fb[st][p] + (2 * pair + jj) * 3072);
+        };
+        constexpr int pa[6] = {1, 2, 1, 0, 0, 0};
+        constexpr int pb[6] = {0, 0, 1, 0, 1, 2};
+        auto mfmas = [&](auto pair_c, auto t0_c, auto t1_c) {
+            constexpr int pair = decltype(pair_c)::value, t0 = decltype(t0_c)::value, t1 = decltype(t1_c)::value;
+            if constexpr (!live) return;
+#pragma unroll
+            for (int term = t0; term < t1; ++term)
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+                    for (int i = 0; i < NI; ++i) b3_mfma(acc[i][2 * pair + jj], a[i][pa[term]], b[jj][pb[term]]);
+        };
+        using I0 = std::integral_constant<int, 0>;
+        using I1 = std::integral_constant<int, 1>;
+        using I2 = std::integral_constant<int, 2>;
+        using I3 = std::integral_constant<int, 3>;
+
+        dma(0, 0);
+        __builtin_amdgcn_s_waitcnt(0x0f70);
+        __syncthreads();
+        read_a(I1{}); read_a(I2{});                  // in the order the end of a k step issues them
+        read_b(I0{}, I0{}, I0{}); read_b(I0{}, I0{}, I1{}); read_b(I0{}, I0{}, I2{});
+        read_a(I0{});
+        __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0) (see the lgkmcnt(2) in the k step)
+
+        // As in gemm_b3_kernel every step is the same straight-line code (k padded to an even number of
+        // tiles; the last step's DMA re-reads the last tile, its reads after Q are wasted).
+        const int last_kt = n_kt - 1;
+        auto kstep = [&](auto cur_c, int kt) {
+            constexpr int cur = decltype(cur_c)::value;
+            auto pair_block = [&](auto pair_c) {
+                constexpr int pair = decltype(pair_c)::value;
+                // where the next pieces come from: the next slab pair of this image, or pair 0 of the next
+                using S = std::integral_constant<int, pair < 3 ? cur : (cur ^ 1)>;
+                using P = std::integral_constant<int, pair < 3 ? pair + 1 : 0>;
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(pair_c, I0{}, I3{});               // a2.b1  a3.b1  a2.b2
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (pair == 0) {
+                    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's reads of A_t are in
+                    __syncthreads();
+                    dma(cur ^ 1, min(kt + 1, last_kt));
+                }
+                if constexpr (pair == 3) {
+                    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0)
+                    __syncthreads();
+                    read_a(I1{}); read_a(I2{});
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(pair_c, I3{}, std::integral_constant<int, 4>{});      // a1.b1
+                __builtin_amdgcn_sched_barrier(0);
+                read_b(S{}, P{}, I0{});
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(pair_c, std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{});   // a1.b2
+                // (the a2 / a3 reads after Q are in by now; said explicitly, it keeps the compiler's count of
+                // reads in flight across the loop edge below 16, else it waits for all of them at the top)
+                if constexpr (pair == 3) __builtin_amdgcn_s_waitcnt(0xc27f);      // lgkmcnt(2)
+                __builtin_amdgcn_sched_barrier(0);
+                read_b(S{}, P{}, I1{});
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(pair_c, std::integral_constant<int, 5>{}, std::integral_constant<int, 6>{});   // a1.b3
+                __builtin_amdgcn_sched_barrier(0);
+                read_b(S{}, P{}, I2{});
+                if constexpr (pair == 3) read_a(I0{});
+            };
+            __builtin_amdgcn_s_setprio(1);
+            pair_block(I0{});
+            pair_block(I1{});
+            pair_block(I2{});
+            pair_block(I3{});
+            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        for (int kt = 0; kt < n_kt; kt += 2) {
+            kstep(I0{}, kt);
+            kstep(I1{}, kt + 1);
+        }
+    };
+    if (__builtin_amdgcn_readfirstlane(row0 + wm * (16 * NI) < g.m)) body(std::true_type{});
+    else body(std::false_type{});
+    __builtin_amdgcn_s_waitcnt(0x0070);              // the wasted DMA and reads of the last step
+
+    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    const int rows_valid = min(g.m - row0, B3_TM);
+    float *cbase = g.c + (int64_t)row0 * g.ldc + col0;
+    __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(
+        cbase, 0, (int)((int64_t)rows_valid * g.ldc * 4), 0x00020000);
+    const uint32_t ldc_b = (uint32_t)g.ldc * 4;
+    uint32_t cvoff[NJ];
+    float bv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int cl = wn * (16 * NJ) + j * 16 + rr;
+        const bool ok = col0 + cl < g.n;
+        cvoff[j] = ok ? (uint32_t)(wm * (16 * NI) + 4 * kg) * ldc_b + (uint32_t)cl * 4 : 0x7fffffffu;
+        bv[j] = (g.bias != nullptr && ok) ? g.bias[col0 + cl] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t roff = (uint32_t)(i * 16 + e) * ldc_b;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const float v = acc[i][j][e] + bv[j];
+                if (rows_valid == B3_TM)
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), crsrc, cvoff[j], roff, 0);
+                else
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), crsrc, cvoff[j] + roff, 0, 0);
+            }
+        }
+}
+
 // The tiles the tail units computed: C tile = sum over its k slices of the partials, in slice order (+ bias).
 // Grid (tile, accumulator register 0..15); a thread holds the element(s) its twin in gemm_b3_kernel held.
 __global__ __launch_bounds__(B3_THREADS) void gemm_b3_tail_sum_kernel(B3Args g) {
@@ -512,6 +722,15 @@ static int64_t b3_tail_bytes(int64_t m, int64_t n, int64_t k) {
     const int64_t r = ceil_div(m, B3_TM) * ceil_div(n, B3_TN) - t.dp_tiles;
     return r * t.splits * (int64_t)(B3_TM * B3_TN * 4);
 }
+// The 256 x 256 tile (gemm_b3_wide_kernel) takes an output that has at least one full round of such tiles
+// and that the 256 x 128 kernel would run as one k slice with no tail units (tuning hook GIST_TUNE_B3_WIDE = 1:
+// never).  On the H = 4096 step: dZ1 (256 wide tiles, one round instead of two) and dW1 (512: two instead of
+// four); the forward Z1.W1 (128) and layer 0's projections stay on the 256 x 128 kernel.
+static bool b3_wide(int64_t m, int64_t n, int64_t k) {
+    if (tune(GIST_TUNE_B3_WIDE) == 1.0) return false;
+    if (ceil_div(m, B3_TM) * ceil_div(n, B3W_TN) < B3_CUS) return false;
+    return b3_splits(m, n, k) == 1 && b3_tail(m, n, k).splits < 2;
+}
 // scratch of one call: fp32 slabs of a split-K call, or the partials of its tail units (never both)
 int64_t b3_slab_bytes(int64_t m, int64_t n, int64_t k) {
     const int s = b3_splits(m, n, k);
@@ -569,6 +788,9 @@ int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, c
     if (once.needed(&dev)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_b3_kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, B3_STAGES * B3_BUF_BYTES);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_b3_wide_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, B3W_LDS_BYTES);
         if (e != hipSuccess) {
             set_error("%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
             return GIST_ELAUNCH;
@@ -605,6 +827,15 @@ int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, c
         }
     }
     const int64_t slot = timer_begin(tl_timer, 2, m, n, k, st);      // kind 2: the main kernel (+ slab sum)
+    if (b3_wide(m, n, k) && splits == 1 && g.tail_splits == 1) {
+        g.tiles_n = (int)ceil_div(n, B3W_TN);
+        g.dp_tiles = g.tiles_m * g.tiles_n;
+        hipLaunchKernelGGL(gemm_b3_wide_kernel, dim3((unsigned)g.dp_tiles), dim3(B3_THREADS), B3W_LDS_BYTES, st, g);
+        const int rc = launch_status(name);
+        if (deferred) *deferred = 1;
+        timer_end(tl_timer, slot, st);
+        return rc;
+    }
     hipLaunchKernelGGL(gemm_b3_kernel, dim3(grid_x, (unsigned)splits),
                        dim3(B3_THREADS), B3_STAGES * B3_BUF_BYTES, st, g);
     int rc = launch_status(name);

@@ -298,7 +298,8 @@ int gist_gemm_get_mode(void);
 #define GIST_TUNE_LNB_FUSED 12    /* 1 = the LayerNorm backward of a <= 256-wide hidden layer as its own launch (not in the store of the reverse aggregation above it) */
 #define GIST_TUNE_B3C_SPLITS 13   /* k slices of the convert-on-load bf16x3 GEMM (0 = its own choice) */
 #define GIST_TUNE_B3_TAIL 14      /* bf16x3 GEMM: 1 = no k slices for the tiles past the last full round of 256 (whole tiles) */
-#define GIST_TUNE_COUNT 15
+#define GIST_TUNE_B3_WIDE 15      /* bf16x3 GEMM: 1 = never the 256x256 output tile (always 256x128) */
+#define GIST_TUNE_COUNT 16
 int gist_tuning_set(int knob, double value);
 double gist_tuning_get(int knob);
 
