@@ -17,6 +17,7 @@ The step follows SURVEY.md appendix A / cluster_gcn_ist_distrib.py:408-417 exact
 forward, mean CE over the batch rows, backward, Adam (coupled L2).
 """
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -78,6 +79,12 @@ class ParamArena(object):
             self.b[k].copy_(layer.linear.bias.data.to(self.device))
             layer.linear.weight.data = self.W[k]
             layer.linear.bias.data = self.b[k]
+
+    def bind_module(self, gcn):
+        """Record on `gcn`, weakly, that its parameters are this arena's views in this arena's layout (made so by its
+        owner, gist_amd.ist.DistributedGNNWrapper): a ModuleEngine for it then steps this arena in place instead of
+        re-homing the module into an arena of its own (module_engine.shared_arena)."""
+        gcn.__dict__['_gist_arena'] = weakref.ref(self)
 
 
 class Batch(object):

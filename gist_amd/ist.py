@@ -129,15 +129,38 @@ class LocalComm(object):
         pass
 
 
+_UNSET = object()          # DistributedGNNWrapper(base_init=...) not passed: the reference-shaped construction
+
+
+def _bind_gcn(arena, gcn, requires_grad=True):
+    """Make every parameter of `gcn` (gist_amd.modules.GCN) a Parameter over its block of `arena` (no copy) and
+    record the arena on the model, so a ModuleEngine built for it trains the arena in place."""
+    import torch.nn as nn
+    for k, layer in enumerate(gcn.layers):
+        layer.linear.weight = nn.Parameter(arena.W[k], requires_grad=requires_grad)
+        layer.linear.bias = nn.Parameter(arena.b[k], requires_grad=requires_grad)
+    arena.bind_module(gcn)
+    return gcn
+
+
 class DistributedGNNWrapper(object):
     """One rank's view of GIST: a replica of the base model + its sub-model.
 
-    Constructor mirrors the reference (`args` needs num_subnet, n_hidden, n_layers, rank,
-    dropout, use_layernorm).  `base_init` = [(W,b)] full-width parameters on rank 0
-    (others pass None and receive them in ini_sync_dispatch_model)."""
+    Constructor mirrors the reference (:68-91; `args` needs num_subnet, n_hidden, n_layers, rank, dropout,
+    use_layernorm).  Called with those five arguments only, it draws the initial weights from the torch RNG as the
+    reference does: on rank 0 the full-width base GCN, then on every rank the split-output sub GCN.  `base_init` =
+    [(W,b)] full-width parameters on rank 0 (others pass None and receive them in ini_sync_dispatch_model): given,
+    even as None, nothing is drawn from the torch RNG.
 
-    def __init__(self, args, g, in_feats, n_classes, device, base_init=None, blocks=None,
+    `sub_model` (every rank) and `base_model` (rank 0; None elsewhere, as in the reference) are
+    gist_amd.modules.GCN whose parameters are views of the flat arenas `sub` and `base`: the in-place block movers
+    of dispatch_model / sync_model are what the modules see, and a `sub_model(cluster)` loop trains `sub` itself
+    on the fused step (gist_amd/module_engine.py).  Every rank keeps the base replica; `base` has no gradients."""
+
+    def __init__(self, args, g, in_feats, n_classes, device, *, base_init=_UNSET, blocks=None,
                  comm=None, n_max=None, seed=0):
+        import torch.nn.functional as F
+        from .modules import GCN
         self.args = args
         self.g = g
         self.in_feats, self.n_classes = in_feats, n_classes
@@ -152,9 +175,32 @@ class DistributedGNNWrapper(object):
         self.sub_dims = dims_for(in_feats, self.H, n_classes, self.L, split_output=True,
                                  num_subnet=self.S)
         self.base = ParamArena(self.base_dims, device, with_grads=False)
-        if base_init is not None:
-            self.base.load(base_init)
         self.sub = ParamArena(self.sub_dims, device)
+
+        def gcn(split):
+            return GCN(in_feats, self.H, n_classes, self.L, F.relu, args.dropout, args.use_layernorm, False, split,
+                       self.S if split else 1, True)
+        if base_init is _UNSET:
+            # :78-90 -- the torch RNG draws of the reference, in its order; the drawn values go into the arenas
+            base_model = gcn(False) if self.rank == 0 else None
+            sub_model = gcn(True)
+            if base_model is not None:
+                self.base.load([(l.linear.weight.data, l.linear.bias.data) for l in base_model.layers])
+            self.sub.load([(l.linear.weight.data, l.linear.bias.data) for l in sub_model.layers])
+        else:
+            if base_init is not None:
+                self.base.load(base_init)
+            with torch.device('meta'):                   # (the modules' own storage: no allocation, no RNG draw)
+                base_model = gcn(False) if self.rank == 0 else None
+                sub_model = gcn(True)
+        self.base_model = _bind_gcn(self.base, base_model, False) if base_model is not None else None
+        self.sub_model = _bind_gcn(self.sub, sub_model)
+        # the fused step's dropout stream of this rank: the same as the engine path's below
+        self.sub_model.set_dropout_seed(seed * 131 + self.rank)
+        if self.base_model is not None:
+            # utils.evaluate(base_model, g, ...) runs FullGraphEvaluator on the replica
+            self.base_model._gist_full_graph = self._full_graph_evaluator
+        self._evaluators = {}
         self.gathered = torch.zeros(self.S * self.sub.numel, dtype=torch.float32, device=device)
         if hasattr(self.comm, 'register'):
             self.comm.register(self.base, self.sub)
@@ -164,6 +210,15 @@ class DistributedGNNWrapper(object):
         if n_max is not None:
             self.engine = SageEngine(self.sub_dims, args.use_layernorm, args.dropout, n_max,
                                      device, seed=seed * 131 + self.rank, arena=self.sub)
+
+    def _full_graph_evaluator(self, g):
+        """The FullGraphEvaluator of the base replica over graph `g` (built at the first evaluation of `g`)."""
+        from .trainer import FullGraphEvaluator
+        ent = self._evaluators.get(id(g))
+        if ent is None or ent[0] is not g:
+            ent = self._evaluators[id(g)] = (g, FullGraphEvaluator(g, self.base_dims, self.args.use_layernorm,
+                                                                   self.base, self.device))
+        return ent[1]
 
     # -- partitions ------------------------------------------------------------------
     def sample_partitions(self):

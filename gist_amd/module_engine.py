@@ -22,8 +22,11 @@ runs the SAME preallocated plan `gist_sage_step` runs for the engine path, as th
   * `gist_amd.optim.Adam.step()` is one launch over the flat arena (with the next batch's extraction in its grid).
 
 The module's parameters are re-homed into the engine's arena (values preserved), so `model.parameters()`,
-`state_dict()`, the IST block movers and the evaluator keep working on the same tensors.  Parameters after a step are
-bitwise those of the engine path (tests/test_module_engine_gpu.py).  GIST_MODULE_ENGINE=0 turns the binding off (the
+`state_dict()`, the IST block movers and the evaluator keep working on the same tensors.  A model whose parameters
+already are the views of one arena (the `sub_model` of gist_amd.ist.DistributedGNNWrapper: ParamArena.bind_module)
+is not re-homed: its engine is built on that arena, so the wrapper's in-place dispatch and sync are what the next
+step reads (they run on the step's stream, after the optimiser launch that extracted the next batch, which reads no
+parameter).  Parameters after a step are bitwise those of the engine path (tests/test_module_engine_gpu.py).  GIST_MODULE_ENGINE=0 turns the binding off (the
 op-by-op module path of gist_amd/autograd.py, one dispatcher op per layer: the parity twin).
 """
 import os
@@ -159,6 +162,19 @@ def eligible(model):
     return True
 
 
+def shared_arena(model, dims):
+    """The ParamArena every parameter of `model` already is a view of, in that arena's layout and with `dims`
+    (ParamArena.bind_module recorded it), or None."""
+    ref = model.__dict__.get('_gist_arena')
+    A = ref() if ref is not None else None
+    if A is None or A.grads is None or [(int(i), int(o)) for i, o in A.dims] != dims:
+        return None
+    for k, l in enumerate(model.layers):
+        if l.linear.weight.data_ptr() != A.W[k].data_ptr() or l.linear.bias.data_ptr() != A.b[k].data_ptr():
+            return None
+    return A
+
+
 class ModuleEngine(object):
     """One nn.Module GCN bound to one ClusterIter: the SageEngine behind `model(cluster)`."""
 
@@ -168,8 +184,13 @@ class ModuleEngine(object):
         dims = [(l.linear.in_features // 2, l.linear.out_features) for l in layers]
         dev = it.g.device
         ln = layers[0].use_lynorm if len(layers) > 1 else False
-        self.engine = eng = SageEngine(dims, ln, layers[0].p_drop, it.n_max, dev, seed=getattr(model, '_drop_seed', 0))
-        eng.arena.adopt_module(model)
+        # a DistributedGNNWrapper's sub_model already IS its arena: the engine steps that arena in place (dispatch and
+        # sync write it between steps); any other model is re-homed into an arena of the engine's own
+        shared = shared_arena(model, dims)
+        self.engine = eng = SageEngine(dims, ln, layers[0].p_drop, it.n_max, dev, seed=getattr(model, '_drop_seed', 0),
+                                       arena=shared)
+        if shared is None:
+            eng.arena.adopt_module(model)
         eng.prefetch = True
         it.bind(eng)
         if eng.plan is None:

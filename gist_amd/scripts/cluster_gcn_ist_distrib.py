@@ -12,6 +12,12 @@ Launch like the reference (script/reddit/run_ist_distrib.sh): one process per ra
     done; wait
 
 `--use_layernorm` keeps the reference's `type=bool` quirk (:538): any non-empty string is True.
+
+`--host-path module` (not a flag of the reference) runs the reference's own loop (:394-447) statement for statement
+on the drop-in classes: `ist_model.sub_model`, gist_amd.nn.CrossEntropyLoss, a new gist_amd.optim.Adam at every
+dispatch point, `evaluate(ist_model.base_model, ...)` on rank 0.  One deviation: the reference adds `float(loss)` to
+its running loss every step, which waits for the device once per step; this loop keeps the step losses on the device
+and averages them at each evaluation, as the engine path does.  The default, `engine`, is gist_amd.ist.train.
 """
 import argparse
 import random
@@ -49,6 +55,9 @@ def build_parser():
     parser.add_argument("--fig-dir", type=str, default='../report/example_pic/')
     parser.add_argument("--fig-name", type=str, default='name')
     parser.add_argument("--use-f1", action='store_true')
+    # (not a flag of the reference) module: the reference's loop on ist_model.sub_model / base_model (main_module_path);
+    # engine: gist_amd.ist.train, one gist_sage_step per iteration
+    parser.add_argument("--host-path", choices=['engine', 'module'], default='engine')
     return parser
 
 
@@ -107,6 +116,13 @@ def main(args=None, dataset=None, log=print, ultra_wide=False):
     train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
     par_li = getattr(data, 'par_li', None)
     psize = len(par_li) if par_li is not None else args.psize
+    if getattr(args, 'host_path', 'engine') == 'module':
+        if ultra_wide:
+            raise SystemExit('gist_amd: --host-path module is not offered for cluster_gcn_ist_ultra_wide (its '
+                             'evaluation needs the bounded row block of the engine path); use --host-path engine')
+        res = main_module_path(args, g, device, in_feats, n_classes, train_nid, par_li, psize, log)
+        dist.destroy_process_group()
+        return res
     it = EngineClusterIter(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li,
                            device=device)                    # :507-509 (one shuffle)
     base_init = None
@@ -133,6 +149,88 @@ def main(args=None, dataset=None, log=print, ultra_wide=False):
         else:
             ist.print_results(res, log=log)                  # :475-479
     dist.destroy_process_group()
+    res['model'] = model
+    return res
+
+
+def main_module_path(args, g, device, in_feats, n_classes, train_nid, par_li, psize, log):
+    """cluster_gcn_ist_distrib.py:370-479 + :593-597 on the drop-in classes.  The step losses stay on the device (the
+    reference's per-step `float(loss)`, :416, would wait for the device once per step); each evaluation averages them.
+    Returns what gist_amd.ist.train returns (total_time, losses, events, accuracies) plus the wrapper as 'model'."""
+    import time
+    from gist_amd import ist
+    from gist_amd.nn import CrossEntropyLoss
+    from gist_amd.optim import Adam
+    from gist_amd.sampler import ClusterIter
+    from gist_amd.utils import evaluate
+    cluster_iterator = ClusterIter(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li,
+                                   device=device)                                    # :507-509 (one shuffle)
+    ist_model = ist.DistributedGNNWrapper(args, g, in_feats, n_classes, device, seed=args.rnd_seed)    # :593
+    log(f'{args.rank}: start initial dispatch', flush=True)
+    ist_model.ini_sync_dispatch_model()                                              # :595
+    log(f'{args.rank}: finish initial dispatch', flush=True)
+    labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
+    multi = dist.get_world_size() > 1
+    method = 'f1' if args.use_f1 else 'acc'
+    test_accs, val_accs, trn_losses, losses, events = [], [], [], [], []
+    loss_fcn = CrossEntropyLoss()                                                    # :384
+    local_epochs = args.n_epochs // args.num_subnet
+    running, total_iter, total_time = [], 0, 0.
+    torch.cuda.synchronize(device)
+    start_time = time.time()
+    for e in range(local_epochs):
+        log(f'{args.rank}: running epoch {e} / {local_epochs}', flush=True)
+        lr = args.lr
+        run_eval = True
+        for j, cluster in enumerate(cluster_iterator):
+            if total_iter % args.iter_per_site == 0:                                 # :400-407
+                if e > 0:
+                    if multi:
+                        dist.barrier()
+                    ist_model.dispatch_model()
+                    events.append('dispatch')
+                ist_model.sub_model.train()
+                optimizer = Adam(ist_model.sub_model.parameters(), lr=lr, weight_decay=args.weight_decay)
+            optimizer.zero_grad()                                                    # :408-417
+            cluster = cluster.to(device)
+            pred = ist_model.sub_model(cluster)
+            batch_labels = cluster.ndata['label']
+            batch_train_mask = cluster.ndata['train_mask']
+            loss = loss_fcn(pred[batch_train_mask], batch_labels[batch_train_mask])
+            loss.backward()
+            running.append(loss.detach())
+            optimizer.step()
+            events.append('step')
+            total_iter += 1
+            last = (j == len(cluster_iterator) - 1) and (e == local_epochs - 1)
+            if total_iter % args.iter_per_site == 0 or last:                         # :422-450
+                if multi:
+                    dist.barrier()
+                ist_model.sync_model()
+                events.append('sync')
+                if run_eval or last:
+                    torch.cuda.synchronize(device)
+                    total_time += time.time() - start_time
+                    run_eval = False
+                    events.append('eval')
+                    if args.rank == 0:
+                        val_accs.append(evaluate(ist_model.base_model, g, labels, val_mask, method))
+                        test_accs.append(evaluate(ist_model.base_model, g, labels, test_mask, method))
+                        trn_losses.append(float(torch.stack(running).mean().item()) if running else 0.0)
+                    losses.extend(running)
+                    running = []
+                    torch.cuda.synchronize(device)
+                    start_time = time.time()
+    losses.extend(running)
+    if multi:
+        dist.barrier()
+    res = dict(total_time=total_time, losses=[losses], events=events, val_accs=val_accs, test_accs=test_accs,
+               trn_losses=trn_losses, model=ist_model)
+    if args.rank == 0:
+        if args.save_results:
+            log('results written to %s' % save_results(args, res, log=log), flush=True)
+        else:
+            ist.print_results(res, log=log)                                          # :475-479
     return res
 
 
