@@ -136,6 +136,14 @@ SIGNATURES = {
     'gist_extract_parts_desc_batch': (_int, [_p, _p]),
     'gist_adam_segments_extract_f32': (_int, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i64, _p, _i64, _p, _i64, _i64,
                                               _p, _p, _p]),
+    'gist_gat_scores_f32': (_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _p]),
+    'gist_gat_aggregate_f32': (_int, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _int, _p, _i64, _p, _p, _p]),
+    'gist_gat_backward_dst_f32': (_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _int,
+                                         _p, _i64, _p, _p, _p]),
+    'gist_gat_backward_src_f32': (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
+                                         _p, _i64, _p, _p]),
+    'gist_gat_attn_grad_workspace_floats': (_i64, [_i64, _i64, _i64]),
+    'gist_gat_attn_grad_f32': (_int, [_p, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p]),
 }
 
 GIST_MAX_LAYERS = 16

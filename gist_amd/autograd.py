@@ -5,6 +5,7 @@ in libgist_hip.so.
 
   spmm_sum(g, x)        g.update_all(copy_src, sum)                (modules.py:224-225)
   sage_layer(...)       one whole ISTSAGELayer.forward, fused      (modules.py:218-237)
+  gat_layer(...)        one whole MultiHeadGATLayer.forward, fused (modules.py:57-76)
   matmul, layer_norm_rows, whole_tensor_layer_norm                 (gcn/gcn.py:30-67)
 """
 import torch
@@ -34,6 +35,13 @@ def sage_layer(g, h, weight, bias, use_lynorm, relu, p_drop=0.0, seed=0):
     out, _z, _yhat, _rstd = torch.ops.gist.sage_layer(
         g.rowptr, g.col, g.t_rowptr, g.t_col, g.norm(), h, weight, bias, bool(use_lynorm),
         bool(relu), p_drop, int(seed), off)
+    return out
+
+
+def gat_layer(g, h, weight, attn, elu=False):
+    """All heads of a GAT layer as one op: weight = the heads' fc weights stacked [H*F, in], attn = their attn_fc
+    weights stacked [H, 2F]; returns the per-node mean over heads [n, F], through ELU when `elu`."""
+    out = torch.ops.gist.gat_layer(g.rowptr, g.col, g.t_rowptr, g.t_col, h, weight, attn, bool(elu))[0]
     return out
 
 

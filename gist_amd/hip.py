@@ -274,6 +274,104 @@ def gemm_tn(g, a, d):
     return d
 
 
+# -- graph attention ----------------------------------------------------------------
+def _gat_dims(z, a):
+    """(n, heads, out_dim) of a GAT layer from Z [n, H*F] and the stacked attention vectors A [H, 2F]."""
+    _mat(a, 'a')
+    if not a.is_contiguous() or a.shape[1] % 2:
+        raise ValueError('gist_amd: attention vectors must be a contiguous [heads, 2 * out_dim] matrix')
+    heads, f = a.shape[0], a.shape[1] // 2
+    if z.dim() != 2 or z.shape[1] != heads * f:
+        raise ValueError('gist_amd: Z must be [n, heads * out_dim] = [n, %d] (got %s)' % (heads * f, tuple(z.shape)))
+    return z.shape[0], heads, f
+
+
+def _nh(t, name, n, heads):
+    if tuple(t.shape) != (n, heads):
+        raise ValueError('gist_amd: %s must be [%d, %d] (got %s)' % (name, n, heads, tuple(t.shape)))
+    return _vec(t, name, torch.float32)
+
+
+def _csr(rowptr, col, n, name):
+    if rowptr.numel() != n + 1:
+        raise ValueError('gist_amd: %s has %d rows, the features %d' % (name, rowptr.numel() - 1, n))
+    return _vec(rowptr, name, torch.int32), _vec(col, name + ' col', torch.int32)
+
+
+def gat_scores(z, a, s_src, s_dst):
+    """s_src[r, h] = z_h[r] . a[h, :F],  s_dst[r, h] = z_h[r] . a[h, F:]  (gist_gat_scores_f32)."""
+    L = _lib.load()
+    n, heads, f = _gat_dims(z, a)
+    zp, ldz = _mat(z, 'z')
+    _lib.check(L.gist_gat_scores_f32(zp, ldz, a.data_ptr(), n, heads, f, _nh(s_src, 's_src', n, heads),
+                                     _nh(s_dst, 's_dst', n, heads), _stream()), 'gist_gat_scores_f32')
+
+
+def gat_aggregate(rowptr, col, z, a, s_src, s_dst, elu, out, m, l):
+    """Edge softmax + weighted sum of every head, head mean, optional ELU (gist_gat_aggregate_f32)."""
+    L = _lib.load()
+    n, heads, f = _gat_dims(z, a)
+    rp, cp = _csr(rowptr, col, n, 'rowptr')
+    zp, ldz = _mat(z, 'z')
+    op, ldo = _mat(out, 'out')
+    if tuple(out.shape) != (n, f):
+        raise ValueError('gist_amd: gat_aggregate output must be [%d, %d]' % (n, f))
+    _lib.check(L.gist_gat_aggregate_f32(rp, cp, zp, ldz, _nh(s_src, 's_src', n, heads), _nh(s_dst, 's_dst', n, heads),
+                                        n, heads, f, int(bool(elu)), op, ldo, _nh(m, 'm', n, heads),
+                                        _nh(l, 'l', n, heads), _stream()), 'gist_gat_aggregate_f32')
+    return out
+
+
+def gat_backward_dst(rowptr, col, z, a, out, d_out, s_src, s_dst, m, l, elu, g, ds_dst, dd):
+    """Destination pass of the GAT backward (gist_gat_backward_dst_f32): g, ds_dst, D."""
+    L = _lib.load()
+    n, heads, f = _gat_dims(z, a)
+    rp, cp = _csr(rowptr, col, n, 'rowptr')
+    zp, ldz = _mat(z, 'z')
+    op, ldo = _mat(out, 'out')
+    dp, ldg = _mat(d_out, 'd_out')
+    gp, ldgm = _mat(g, 'g')
+    for t, name in ((out, 'out'), (d_out, 'd_out'), (g, 'g')):
+        if tuple(t.shape) != (n, f):
+            raise ValueError('gist_amd: gat_backward_dst: %s must be [%d, %d]' % (name, n, f))
+    _lib.check(L.gist_gat_backward_dst_f32(rp, cp, zp, ldz, op, ldo, dp, ldg, _nh(s_src, 's_src', n, heads),
+                                           _nh(s_dst, 's_dst', n, heads), _nh(m, 'm', n, heads),
+                                           _nh(l, 'l', n, heads), n, heads, f, int(bool(elu)), gp, ldgm,
+                                           _nh(ds_dst, 'ds_dst', n, heads), _nh(dd, 'd', n, heads), _stream()),
+               'gist_gat_backward_dst_f32')
+
+
+def gat_backward_src(t_rowptr, t_col, z, a, g, s_src, s_dst, m, l, dd, ds_dst, dz, ds_src):
+    """Source pass of the GAT backward over the reversed CSR (gist_gat_backward_src_f32): dZ, ds_src."""
+    L = _lib.load()
+    n, heads, f = _gat_dims(z, a)
+    rp, cp = _csr(t_rowptr, t_col, n, 't_rowptr')
+    zp, ldz = _mat(z, 'z')
+    gp, ldgm = _mat(g, 'g')
+    dzp, lddz = _mat(dz, 'dz')
+    if tuple(g.shape) != (n, f) or tuple(dz.shape) != tuple(z.shape):
+        raise ValueError('gist_amd: gat_backward_src shape mismatch')
+    _lib.check(L.gist_gat_backward_src_f32(rp, cp, zp, ldz, gp, ldgm, a.data_ptr(), _nh(s_src, 's_src', n, heads),
+                                           _nh(s_dst, 's_dst', n, heads), _nh(m, 'm', n, heads),
+                                           _nh(l, 'l', n, heads), _nh(dd, 'd', n, heads),
+                                           _nh(ds_dst, 'ds_dst', n, heads), n, heads, f, dzp, lddz,
+                                           _nh(ds_src, 'ds_src', n, heads), _stream()),
+               'gist_gat_backward_src_f32')
+
+
+def gat_attn_grad(z, ds_src, ds_dst, da):
+    """da[h, :F] = sum_r ds_src[r, h] z_h[r],  da[h, F:] = sum_r ds_dst[r, h] z_h[r]  (gist_gat_attn_grad_f32)."""
+    L = _lib.load()
+    n, heads, f = _gat_dims(z, da)
+    zp, ldz = _mat(z, 'z')
+    need = int(L.gist_gat_attn_grad_workspace_floats(n, heads, f))
+    ws = torch.empty(max(need, 1), dtype=torch.float32, device=z.device)
+    _lib.check(L.gist_gat_attn_grad_f32(zp, ldz, _nh(ds_src, 'ds_src', n, heads), _nh(ds_dst, 'ds_dst', n, heads),
+                                        n, heads, f, ws.data_ptr(), ws.numel(), da.data_ptr(), _stream()),
+               'gist_gat_attn_grad_f32')
+    return da
+
+
 # -- row epilogues -----------------------------------------------------------------
 def ln_relu_fwd(y, out, rstd, use_lynorm, relu, eps=LN_EPS):
     L = _lib.load()

@@ -1,4 +1,4 @@
-"""GraphSAGE model with the reference's module API (cluster_gcn/modules.py:191-314).
+"""GraphSAGE and GAT models with the reference's module API (cluster_gcn/modules.py:1-98,191-314).
 
 `ISTSAGELayer` and `GCN` take the same constructor arguments, expose the same
 attributes (`layers[i].linear.weight / .bias`, `dropout`, `lynorm`, `activation`)
@@ -6,6 +6,13 @@ and initialise their parameters with the same torch RNG calls in the same order
 (modules.py:201-203,213-216), so a script written against the reference runs
 unchanged and same-seed weights are identical.  forward() runs entirely on the
 HIP kernels through gist_amd.autograd.sage_layer.
+
+`GATLayer`, `MultiHeadGATLayer` and `GAT` (modules.py:24-98) keep the reference's constructors,
+attributes (`layers[k].heads[h].fc.weight`, `.attn_fc.weight`) and initialisation order; a layer
+runs all its heads as ONE op (gist_amd.autograd.gat_layer).  One deliberate deviation: the heads
+of a layer are averaged PER NODE (the reference's torch.mean(torch.stack(head_outs)), :76,
+reduces to a scalar; its constructor sizes layer k+1's input as hidden_dim, :80-84, which rules
+out concatenation), see DESIGN.md "Graph attention".
 """
 import math
 
@@ -144,4 +151,68 @@ class GCN(nn.Module):
         h = g.ndata['feat']
         for layer in self.layers:
             h = layer(g, h)
+        return h
+
+
+def _stack_heads(heads):
+    """The heads' fc weights stacked [H*F, in] and attn_fc weights stacked [H, 2F] (differentiable: the per-head
+    Parameters stay the model's parameters, so a GIST split can slice them head by head)."""
+    if len(heads) == 1:
+        return heads[0].fc.weight, heads[0].attn_fc.weight
+    return (torch.cat([hd.fc.weight for hd in heads], 0), torch.cat([hd.attn_fc.weight for hd in heads], 0))
+
+
+class GATLayer(nn.Module):
+    """One attention head (cluster_gcn/modules.py:24-65): z = fc(h); e = leaky_relu(attn_fc([z_src | z_dst]));
+    softmax over each node's in-edges; h' = sum alpha z."""
+
+    def __init__(self, in_dim, out_dim):
+        super().__init__()
+        self.fc = nn.Linear(in_dim, out_dim, bias=False)                   # equation (1)
+        self.attn_fc = nn.Linear(2 * out_dim, 1, bias=False)               # equation (2)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        """Reinitialize learnable parameters (modules.py:33-37)."""
+        gain = nn.init.calculate_gain('relu')
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn_fc.weight, gain=gain)
+
+    def forward(self, g, h):
+        return autograd.gat_layer(g, h, self.fc.weight, self.attn_fc.weight)
+
+
+class MultiHeadGATLayer(nn.Module):
+    """num_heads GATLayers on the same input (modules.py:67-76), averaged per node; all heads run as one op."""
+
+    def __init__(self, in_dim, out_dim, num_heads):
+        super().__init__()
+        self.heads = nn.ModuleList()
+        for i in range(num_heads):
+            self.heads.append(GATLayer(in_dim, out_dim))
+
+    def forward(self, g, h, elu=False):
+        """(1/H) sum_h head_h(g, h) per node; with elu=True, F.elu of it in the same kernel (GAT.forward)."""
+        weight, attn = _stack_heads(self.heads)
+        return autograd.gat_layer(g, h, weight, attn, elu)
+
+
+class GAT(nn.Module):
+    """Layer sizing of the reference's GAT (modules.py:78-98): num_heads heads in the first layer and in the
+    num_layers - 2 middle ones (width hidden_dim), one head of width out_dim last; ELU after every layer."""
+
+    def __init__(self, num_layers, in_dim, hidden_dim, out_dim, num_heads):
+        super().__init__()
+        layers = [MultiHeadGATLayer(in_dim, hidden_dim, num_heads)]
+        for layer_idx in range(num_layers - 2):
+            layers.append(MultiHeadGATLayer(hidden_dim, hidden_dim, num_heads))
+        # the input of every later layer is hidden_dim wide: the heads are averaged, not concatenated
+        layers.append(MultiHeadGATLayer(hidden_dim, out_dim, 1))
+        self.layers = torch.nn.ModuleList(layers)
+
+    def forward(self, g):
+        """modules.py:93-98 on a ClusterBatch or a full Graph; h = F.elu(layer(g, h)) runs as one op per layer."""
+        h = g.ndata['feat']
+        for layer in self.layers:
+            h = layer(g, h, elu=True)
         return h

@@ -34,7 +34,8 @@ def build_parser():
     parser.add_argument("--use-pp", action='store_true', help="whether to use precomputation")
     parser.add_argument("--normalize", action='store_true', help="whether to use normalized feature")
     parser.add_argument("--weight-decay", type=float, default=0, help="Weight for L2 loss")
-    parser.add_argument("--model-type", type=str, default='sage')
+    parser.add_argument("--model-type", type=str, default='sage', help="sage or gat")
+    parser.add_argument("--n-heads", type=int, default=4, help="attention heads of the GAT layers")
     parser.add_argument("--fig-dir", type=str, default='../report/example_pic/')
     parser.add_argument("--fig-name", type=str, default='name')
     parser.add_argument("--use-layernorm", action='store_true')
@@ -55,7 +56,7 @@ def main(args, dataset=None, log=print):
     random.seed(args.rnd_seed)
     if args.gpu < 0 or args.eval_cpu:
         raise SystemExit('gist_amd runs on the GPU only (no CPU fallback): --gpu >= 0, no --eval-cpu')
-    if args.model_type != 'sage':
+    if args.model_type not in ('sage', 'gat'):
         raise NotImplementedError(f'{args.model_type} is not a supported model type')
     data = dataset if dataset is not None else load_data(args)
     g = data.g
@@ -81,7 +82,8 @@ def main(args, dataset=None, log=print):
                 args.use_layernorm, False, False, 1, True)          # :66-69
         model_holder['m'] = m
         return m
-    if getattr(args, 'host_path', 'engine') == 'module':
+    if args.model_type == 'gat' or getattr(args, 'host_path', 'engine') == 'module':
+        # GAT has no fused step: it always trains on the reference's loop over the drop-in classes
         return main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     trainer = ClusterGCNTrainer(args.dataset, g, par_li, psize, args.batch_size, args.n_hidden,
                                 args.n_layers, n_classes, args.dropout, args.use_layernorm,
@@ -104,9 +106,10 @@ def main(args, dataset=None, log=print):
 
 
 def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log):
-    """cluster_gcn/cluster_gcn.py:24-136 on the drop-in classes: ClusterIter, GCN, CrossEntropyLoss, Adam, evaluate."""
+    """cluster_gcn/cluster_gcn.py:24-136 on the drop-in classes: ClusterIter, GCN (or GAT), CrossEntropyLoss, Adam,
+    evaluate."""
     import time
-    from gist_amd.modules import GCN
+    from gist_amd.modules import GAT, GCN
     from gist_amd.nn import CrossEntropyLoss
     from gist_amd.optim import Adam
     from gist_amd.sampler import ClusterIter
@@ -116,10 +119,14 @@ def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, 
                                    par_li=par_li, device=device)                                      # :44-46
     g = g.to(device)
     labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
-    model = GCN(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout,
-                args.use_layernorm, False, False, 1, True)                                             # :66-69
-    model.cuda()
-    model.set_dropout_seed(args.rnd_seed)
+    if args.model_type == 'gat':
+        model = GAT(args.n_layers, in_feats, args.n_hidden, n_classes, args.n_heads)   # cluster_gcn_ist_distrib_gat.py:77-79
+        model.cuda()
+    else:
+        model = GCN(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout,
+                    args.use_layernorm, False, False, 1, True)                                         # :66-69
+        model.cuda()
+        model.set_dropout_seed(args.rnd_seed)
     loss_f = CrossEntropyLoss()                                                                        # :76
     optimizer = Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)                   # :77-80
     total_time, val_accs, test_accs = 0., [], []

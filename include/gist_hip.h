@@ -878,6 +878,64 @@ int gist_sage_step(const gist_step_plan *plan, const int32_t *ids, int64_t n,
  * flag would be ignored.  Host function. */
 int gist_sage_step_extracts_next(const gist_step_plan *plan, int64_t n, int flags);
 
+/* ---------------------------------------------------------------------------
+ * Graph attention (GAT): cluster_gcn/modules.py:1-98, gcn/gat.py
+ *
+ * A layer of H heads of width F on n rows: Z = x . W^T with the heads' fc weights stacked
+ * ([H*F, in], one gist_gemm_nt_f32), A = the heads' attn_fc weights stacked ([H, 2F], cat
+ * order [src, dst] as modules.py:41-43).  s_src, s_dst, M, L, D, ds_src, ds_dst are [n, H]
+ * contiguous.  Every sum has a fixed order (no float atomics): bitwise reproducible.
+ * Vectorised paths need F % 4 == 0 and 16-byte aligned operands; any F >= 1, H >= 1 is
+ * correct.
+ * ------------------------------------------------------------------------- */
+
+/* s_src[r,h] = Z[r, hF:(h+1)F] . A[h, 0:F],  s_dst[r,h] = Z[r, hF:(h+1)F] . A[h, F:2F].
+ * Replaces self.attn_fc(z2) of GATLayer.edge_attention, cluster_gcn/modules.py:41-43
+ * (one score per node and side; the per-edge score is their sum). */
+int gist_gat_scores_f32(const float *Z, int64_t ldz, const float *A, int64_t n_rows, int64_t heads,
+                        int64_t out_dim, float *s_src, float *s_dst, gist_stream_t stream);
+
+/* out[i] = act((1/H) sum_h sum_{e in row i} alpha_he Z[col[e], hF:(h+1)F]), alpha = softmax over
+ * the row's in-edges of leaky_relu(s_src[col[e],h] + s_dst[i,h], 0.01); act = ELU if elu, else
+ * the identity.  Saves per (row, head) the softmax max M and denominator L (both 0 for a row
+ * without in-edges, whose output is 0).  Online softmax: any degree, any score range.
+ * Replaces g.apply_edges(edge_attention) + g.update_all(message_func, reduce_func) of
+ * GATLayer.forward, cluster_gcn/modules.py:57-65, the head stack of MultiHeadGATLayer.forward
+ * :74-76 (as a per-node mean over heads) and F.elu of GAT.forward :97. */
+int gist_gat_aggregate_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+                           const float *s_src, const float *s_dst, int64_t n_rows, int64_t heads,
+                           int64_t out_dim, int elu, float *out, int64_t ldo, float *M, float *L,
+                           gist_stream_t stream);
+
+/* Backward of gist_gat_aggregate_f32, destination pass over the in-edge CSR:
+ * G = d_out * act'(out) / H ([n, F], ldgm; out may be NULL without elu), and with
+ * gz = G[i] . Z[j, hF:(h+1)F]: D[i,h] = sum_j alpha gz, ds_dst[i,h] = sum_j alpha lr' (gz - D[i,h]).
+ * Autograd of cluster_gcn/modules.py:49-55,97 (softmax, weighted sum, ELU). */
+int gist_gat_backward_dst_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+                              const float *out, int64_t ldo, const float *d_out, int64_t ldg,
+                              const float *s_src, const float *s_dst, const float *M, const float *L,
+                              int64_t n_rows, int64_t heads, int64_t out_dim, int elu, float *G,
+                              int64_t ldgm, float *ds_dst, float *D, gist_stream_t stream);
+
+/* Backward, source pass over the reversed CSR (t_rowptr, t_col: row j lists i for each edge j -> i):
+ * ds_src[j,h] = sum_i alpha (gz - D[i,h]) lr', and
+ * dZ[j, hF:(h+1)F] = sum_i alpha G[i] + ds_src[j,h] A[h, 0:F] + ds_dst[j,h] A[h, F:2F]  (one store).
+ * Autograd of cluster_gcn/modules.py:41-55 (edges.src['z'], the attention scores). */
+int gist_gat_backward_src_f32(const int32_t *t_rowptr, const int32_t *t_col, const float *Z, int64_t ldz,
+                              const float *G, int64_t ldgm, const float *A, const float *s_src,
+                              const float *s_dst, const float *M, const float *L, const float *D,
+                              const float *ds_dst, int64_t n_rows, int64_t heads, int64_t out_dim,
+                              float *dZ, int64_t lddz, float *ds_src, gist_stream_t stream);
+
+/* Floats of the partial-slab workspace gist_gat_attn_grad_f32 needs.  Host function. */
+int64_t gist_gat_attn_grad_workspace_floats(int64_t n_rows, int64_t heads, int64_t out_dim);
+/* dA[h, 0:F] = sum_r ds_src[r,h] Z[r, hF:(h+1)F],  dA[h, F:2F] = sum_r ds_dst[r,h] Z[r, hF:(h+1)F]
+ * (per-slab partial sums, then one ordered sum).  The gradient of attn_fc.weight,
+ * cluster_gcn/modules.py:23,42. */
+int gist_gat_attn_grad_f32(const float *Z, int64_t ldz, const float *ds_src, const float *ds_dst,
+                           int64_t n_rows, int64_t heads, int64_t out_dim, float *partials,
+                           int64_t partial_floats, float *dA, gist_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
