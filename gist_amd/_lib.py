@@ -45,6 +45,7 @@ SIGNATURES = {
     'gist_gemm_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'gist_gemm_set_mode': (_int, [_int]),
     'gist_gemm_get_mode': (_int, []),
+    'gist_b3_split_f32': (_int, [_p, _i64, _i64, _i64, _f, _u64, _u64, _p, _p, _p, _p]),
     'gist_tuning_set': (_int, [_int, ctypes.c_double]),
     'gist_tuning_get': (ctypes.c_double, [_int]),
     'gist_launch_count': (ctypes.c_uint64, []),

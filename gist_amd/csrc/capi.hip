@@ -51,3 +51,16 @@ extern "C" int gist_device_count(void) {
     }
     return n;
 }
+
+extern "C" int gist_b3_split_f32(const float *src, int64_t ld, int64_t rows, int64_t cols, float p, uint64_t seed,
+                                 uint64_t offset, uint16_t *dst_r, uint16_t *dst_t, float *col_partials,
+                                 gist_stream_t stream) {
+    GIST_REQUIRE(src != nullptr && (dst_r != nullptr || dst_t != nullptr), "gist_b3_split_f32: null pointer");
+    GIST_REQUIRE(rows >= 0 && cols >= 0 && ld >= cols, "gist_b3_split_f32: bad shape");
+    GIST_REQUIRE(p >= 0.f && p < 1.f, "gist_b3_split_f32: p outside [0, 1)");
+    gist::B3Dual d{};
+    d.src = src; d.ld = ld; d.rows = rows; d.cols = cols;
+    d.p = p; d.seed = seed; d.offset = offset;
+    d.dst_r = dst_r; d.dst_t = dst_t; d.col_partials = col_partials;
+    return gist::b3_dual_split(d, gist::as_stream(stream));
+}

@@ -91,9 +91,11 @@ struct B3Dual {                       // one read of src[rows, cols] -> up to tw
     uint16_t *dst_t;                  // [cols][kpad(rows)]: k = rows of src      (NULL: skip)
     float *col_partials;              // [ceil(rows / 64)][cols] column sums per 64-row chunk of src (NULL: none):
                                       // the first stage of gist_colsum_f32, taken from the tile the split reads anyway
-    bool vec4;                        // set by b3_dual_split: 16-byte loads allowed
+    bool vec4;                        // set by the launcher: 16-byte loads allowed
 };
 int b3_dual_split(const B3Dual &d, hipStream_t st);
+constexpr int B3_SPLIT_MAX_JOBS = 4;
+int b3_split_jobs(const B3Dual *jobs, int n_jobs, hipStream_t st);      // up to B3_SPLIT_MAX_JOBS splits, one launch
 int64_t b3_slab_bytes(int64_t m, int64_t n, int64_t k);   // fp32 slabs of a split-K call (0: one k slice)
 int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, const float *bias, float *c,
                      int64_t ldc, int64_t m, int64_t n, int64_t k, float *slabs, int64_t slab_bytes,

@@ -62,101 +62,182 @@ constexpr int B3_B_BYTES = B3_TN * B3_KT_BYTES;        // 12 KiB
 constexpr int B3_BUF_BYTES = B3_A_BYTES + B3_B_BYTES;
 
 // ---- pre-pass ---------------------------------------------------------------------------------
+// One read of src[rows, cols] -> the split operand with k = columns (dst_r: [rows][kpad(cols)]) and/or
+// the one with k = rows (dst_t: [cols][kpad(rows)]), one 64 x 64 tile of src per 128-thread block; pitches
+// in k elements (6 bytes each).  Dropout is applied on the fly with gist_dropout_f32's generator (element
+// index offset + r * cols + c), so the fp32 dropped tensor never has to exist.
+//
+// A thread loads 8 rows x 4 columns (float4 per row: a wave instruction reads four whole 256-byte row
+// segments) and splits each element ONCE.  In registers those pieces already form 12 transposed chunks
+// (one column, 8 rows, one piece) and 24 half chunks of the row layout (one row, 4 columns, one piece).
+// Each layout goes through an LDS image [output row][24 chunks + 1 pad] of 16 B, from which the block
+// writes its 64 output rows x 384 B: consecutive lanes store consecutive 16-byte chunks, so a lane quad is
+// one aligned 64-byte piece and a wave instruction covers whole row segments (the previous kernel split
+// every element twice and stored 48 bytes per lane at a 48-byte lane stride: 24 partial lines per
+// instruction).  One 25.6 KiB image is reused by the two layouts: six blocks per CU.
+constexpr int B3S_THREADS = 128;
+constexpr int B3S_PITCH = 25;                          // 16-B chunks per image row (24 + 1: fewer bank conflicts)
+
+struct B3SplitJob {
+    B3Dual d;
+    int64_t ldd_r, ldd_t;
+    float keep;                       // 1 / (1 - p)
+    int gx, gy;                       // 64 x 64 tiles of this job
+    int first;                        // its first block
+};
+struct B3SplitList {
+    B3SplitJob job[B3_SPLIT_MAX_JOBS];
+    int n;
+};
+
 __device__ __forceinline__ uint32_t b3_pack(__bf16 lo, __bf16 hi) {
     return (uint32_t)__builtin_bit_cast(unsigned short, lo) |
            ((uint32_t)__builtin_bit_cast(unsigned short, hi) << 16);
 }
 
-// 8 consecutive k of one row -> 3 x 16 bytes at dst (bf16 pieces 1, 2, 3)
-__device__ __forceinline__ void b3_emit(const float (&v)[8], uint16_t *__restrict__ dst) {
-    uint32_t w[3][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        __bf16 p[2][3];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float x = v[2 * j + h];
-            p[h][0] = (__bf16)x;
-            const float r1 = x - (float)p[h][0];            // exact
-            p[h][1] = (__bf16)r1;
-            const float r2 = r1 - (float)p[h][1];           // exact
-            p[h][2] = (__bf16)r2;
-        }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) w[q][j] = b3_pack(p[0][q], p[1][q]);
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-        *reinterpret_cast<uint4 *>(dst + 8 * q) = make_uint4(w[q][0], w[q][1], w[q][2], w[q][3]);
+// x -> RNE bf16(x), bf16(x - b1), bf16(x - b1 - b2) (both differences exact)
+__device__ __forceinline__ void b3_pieces(float x, __bf16 (&p)[3]) {
+    p[0] = (__bf16)x;
+    const float r1 = x - (float)p[0];
+    p[1] = (__bf16)r1;
+    const float r2 = r1 - (float)p[1];
+    p[2] = (__bf16)r2;
 }
 
-// One read of src[rows, cols] -> the split operand with k = columns (dst_r: [rows][kpad(cols)]) and/or
-// the one with k = rows (dst_t: [cols][kpad(rows)]), 64 x 64 per block through LDS; pitches in k
-// elements (6 bytes each).  Dropout is applied on the fly with gist_dropout_f32's generator (element
-// index offset + r * cols + c), so the fp32 dropped tensor never has to exist.
-__global__ __launch_bounds__(256) void b3_dual_split_kernel(B3Dual d, int64_t ldd_r, int64_t ldd_t,
-                                                            float keep) {
-    __shared__ float tile[64][65];
-    const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
+// the image's 64 rows x 384 B -> dst rows out0 .. out0 + n_out - 1 at k offset k0; nt: non-temporal stores (the
+// transposed layout: read by a backward projection after hundreds of MB of other traffic, while the row layout of W
+// and Z is read by the forward projection right away -- nt on both cost that projection more than it saved here)
+template <bool NT>
+__device__ __forceinline__ void b3_store_image(const uint4 *img, uint16_t *__restrict__ dst, int64_t ldd,
+                                               int64_t out0, int64_t n_out, int64_t k0, int t) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int s = 0; s < 64 * 24 / B3S_THREADS; ++s) {
+        const int g = s * B3S_THREADS + t;
+        const int o = g / 24, w = g - o * 24;
+        if (o >= n_out) continue;
+        const uint4 v = img[o * B3S_PITCH + w];
+        u32x4 *p = reinterpret_cast<u32x4 *>(dst + ((out0 + o) * ldd + k0) * 3 + w * 8);
+        const u32x4 vv = {v.x, v.y, v.z, v.w};
+        if (NT) __builtin_nontemporal_store(vv, p);
+        else *p = vv;
+    }
+}
+
+__global__ __launch_bounds__(B3S_THREADS) void b3_split_kernel(B3SplitList L) {
+    __shared__ uint4 img[64 * B3S_PITCH];                  // (also the fp32 tile of the column sums)
+    static_assert(64 * B3S_PITCH * 16 >= 64 * 65 * 4, "image too small for the column-sum tile");
+    const int bid = blockIdx.x;
+    B3SplitJob J = L.job[0];                               // (copies: fields in SGPRs, not loads by index)
+#pragma unroll
+    for (int q = 1; q < B3_SPLIT_MAX_JOBS; ++q)
+        if (q < L.n && bid >= L.job[q].first) J = L.job[q];
+    const B3Dual &d = J.d;
+    const int lb = bid - J.first;
+    const int c0 = (lb % J.gx) * 64, r0 = (lb / J.gx) * 64;      // (row tiles outer: measured against both other orders)
     const int t = threadIdx.x;
-    const int c4 = (t & 15) * 4;
-    const uint64_t sm = d.seed * 0x9E3779B97F4A7C15ULL;
-    const float inv24 = 1.0f / 16777216.0f;
+    const int cq = t & 15, rg = t >> 4;                    // columns 4 cq .. 4 cq + 3, rows 8 rg .. 8 rg + 7
+    const int c = c0 + 4 * cq;
+
+    float v[8][4];
+    if (d.vec4 && c0 + 64 <= d.cols) {                     // (block-uniform: whole float4s only)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int rr = (t >> 4) + 16 * i;
-        const int64_t r = r0 + rr;
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (r < d.rows) {
-            const float *p = d.src + r * d.ld + c0 + c4;
-            if (c0 + c4 + 3 < d.cols && d.vec4) {
-                const float4 q = *reinterpret_cast<const float4 *>(p);
-                v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (c0 + c4 + j < d.cols) v[j] = p[j];
-            }
-            if (d.p > 0.f) {
-                const uint64_t idx0 = d.offset + (uint64_t)r * (uint64_t)d.cols + (uint64_t)(c0 + c4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint64_t idx = idx0 + j;
-                    const uint64_t h = splitmix64((idx >> 1) + sm);
-                    const uint32_t w = (idx & 1) ? (uint32_t)(h >> 32) : (uint32_t)h;
-                    v[j] *= ((float)(w >> 8) * inv24 >= d.p) ? keep : 0.f;
-                }
-            }
+        for (int i = 0; i < 8; ++i) {
+            const int64_t r = r0 + 8 * rg + i;
+            float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < d.rows) q = *reinterpret_cast<const float4 *>(d.src + r * d.ld + c);
+            v[i][0] = q.x; v[i][1] = q.y; v[i][2] = q.z; v[i][3] = q.w;
         }
-        tile[rr][c4 + 0] = v[0]; tile[rr][c4 + 1] = v[1];
-        tile[rr][c4 + 2] = v[2]; tile[rr][c4 + 3] = v[3];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int64_t r = r0 + 8 * rg + i;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                v[i][e] = r < d.rows && c + e < d.cols ? d.src[r * d.ld + c + e] : 0.f;
+        }
     }
-    __syncthreads();
-    // column sums of this 64-row chunk (rows past the end are zeros in the tile), fixed order
-    if (d.col_partials != nullptr && t < 64 && c0 + t < d.cols && r0 < d.rows) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    if (d.p > 0.f) {
+        const uint64_t sm = d.seed * 0x9E3779B97F4A7C15ULL;
+        const float inv24 = 1.0f / 16777216.0f;
 #pragma unroll
-        for (int r = 0; r < 64; r += 4) {
-            s0 += tile[r][t]; s1 += tile[r + 1][t]; s2 += tile[r + 2][t]; s3 += tile[r + 3][t];
+        for (int i = 0; i < 8; ++i) {
+            const int64_t r = r0 + 8 * rg + i;
+            if (r >= d.rows) continue;
+            const uint64_t idx0 = d.offset + (uint64_t)r * (uint64_t)d.cols + (uint64_t)c;
+            const uint64_t pair = idx0 >> 1;
+            const uint64_t h0 = splitmix64(pair + sm), h1 = splitmix64(pair + 1 + sm), h2 = splitmix64(pair + 2 + sm);
+            // the 32-bit words of element indices idx0 .. idx0 + 3 (pair idx >> 1, low word for even idx)
+            const bool odd = (idx0 & 1) != 0;
+            const uint32_t w[4] = {odd ? (uint32_t)(h0 >> 32) : (uint32_t)h0, odd ? (uint32_t)h1 : (uint32_t)(h0 >> 32),
+                                   odd ? (uint32_t)(h1 >> 32) : (uint32_t)h1, odd ? (uint32_t)h2 : (uint32_t)(h1 >> 32)};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[i][e] *= ((float)(w[e] >> 8) * inv24 >= d.p) ? J.keep : 0.f;
         }
-        d.col_partials[(int64_t)blockIdx.y * d.cols + c0 + t] = (s0 + s1) + (s2 + s3);
     }
-    const int kb = t & 7;
+    if (d.col_partials != nullptr) {      // column sums of this 64-row chunk, in the order gist_colsum_f32 uses
+        float(*tile)[65] = reinterpret_cast<float(*)[65]>(img);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int q = (t >> 3) + 32 * i;
-        if (d.dst_r != nullptr && r0 + q < d.rows && c0 + kb * 8 < ldd_r) {      // row q, 8 columns
-            float v[8];
+        for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = tile[q][kb * 8 + j];
-            b3_emit(v, d.dst_r + ((int64_t)(r0 + q) * ldd_r + c0 + kb * 8) * 3);
+            for (int e = 0; e < 4; ++e) tile[8 * rg + i][4 * cq + e] = v[i][e];
+        __syncthreads();
+        if (t < 64 && c0 + t < d.cols && r0 < d.rows) {
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+            for (int r = 0; r < 64; r += 4) {
+                s0 += tile[r][t]; s1 += tile[r + 1][t]; s2 += tile[r + 2][t]; s3 += tile[r + 3][t];
+            }
+            d.col_partials[(int64_t)(r0 / 64) * d.cols + c0 + t] = (s0 + s1) + (s2 + s3);
         }
-        if (d.dst_t != nullptr && c0 + q < d.cols && r0 + kb * 8 < ldd_t) {      // column q, 8 rows
-            float v[8];
+        __syncthreads();
+    }
+
+    // the pieces, once per element
+    uint32_t tw[4][3][4];                                  // transposed: column e, piece q, rows (2m, 2m + 1)
+    uint2 rw[8][3];                                        // rows: row i, piece q, columns (0, 1), (2, 3)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = tile[kb * 8 + j][q];
-            b3_emit(v, d.dst_t + ((int64_t)(c0 + q) * ldd_t + r0 + kb * 8) * 3);
+    for (int i = 0; i < 8; i += 2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            __bf16 a[3], b[3];
+            b3_pieces(v[i][e], a);
+            b3_pieces(v[i + 1][e], b);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) tw[e][q][i >> 1] = b3_pack(a[q], b[q]);
         }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const uint32_t w0 = tw[0][q][i >> 1], w1 = tw[1][q][i >> 1], w2 = tw[2][q][i >> 1], w3 = tw[3][q][i >> 1];
+            rw[i][q] = (i & 1) ? make_uint2((w0 >> 16) | (w1 & 0xFFFF0000u), (w2 >> 16) | (w3 & 0xFFFF0000u))
+                               : make_uint2((w0 & 0xFFFFu) | (w1 << 16), (w2 & 0xFFFFu) | (w3 << 16));
+        }
+
+    const bool rows_on = d.dst_r != nullptr && r0 < d.rows && c0 < J.ldd_r;
+    const bool trans_on = d.dst_t != nullptr && c0 < d.cols && r0 < J.ldd_t;
+    if (rows_on) {
+        char *base = reinterpret_cast<char *>(img);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                *reinterpret_cast<uint2 *>(base + (8 * rg + i) * (B3S_PITCH * 16) + (cq >> 1) * 48 + q * 16 +
+                                           (cq & 1) * 8) = rw[i][q];
+        __syncthreads();
+        b3_store_image<false>(img, d.dst_r, J.ldd_r, r0, d.rows - r0, c0, t);
+    }
+    if (trans_on) {
+        if (rows_on) __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                img[(4 * cq + e) * B3S_PITCH + rg * 3 + q] = make_uint4(tw[e][q][0], tw[e][q][1], tw[e][q][2], tw[e][q][3]);
+        __syncthreads();
+        b3_store_image<true>(img, d.dst_t, J.ldd_t, c0, d.cols - c0, r0, t);
     }
 }
 
@@ -769,16 +850,36 @@ int64_t b3_workspace_bytes(int64_t m, int64_t n, int64_t k) {
     return b3_operand_bytes(m, n, k) + b3_slab_bytes(m, n, k);
 }
 
-int b3_dual_split(const B3Dual &d, hipStream_t st) {
-    if (d.rows <= 0 || d.cols <= 0) return GIST_OK;
-    const int64_t ldd_r = b3_kpad(d.cols), ldd_t = b3_kpad(d.rows);
-    const int64_t gx = ceil_div(d.dst_r ? ldd_r : d.cols, 64), gy = ceil_div(d.dst_t ? ldd_t : d.rows, 64);
-    B3Dual dd = d;
-    dd.vec4 = aligned16(d.src) && d.ld % 4 == 0;
-    hipLaunchKernelGGL(b3_dual_split_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, dd, ldd_r,
-                       ldd_t, d.p > 0.f ? 1.0f / (1.0f - d.p) : 1.0f);
+// One launch for up to B3_SPLIT_MAX_JOBS splits: the grid is partitioned over the jobs, in list order.
+int b3_split_jobs(const B3Dual *jobs, int n_jobs, hipStream_t st) {
+    if (n_jobs < 1 || n_jobs > B3_SPLIT_MAX_JOBS) {
+        set_error("b3_split_jobs: %d jobs (1 .. %d)", n_jobs, B3_SPLIT_MAX_JOBS);
+        return GIST_EINVAL;
+    }
+    B3SplitList L{};
+    int64_t blocks = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const B3Dual &d = jobs[i];
+        if (d.rows <= 0 || d.cols <= 0) continue;
+        B3SplitJob &J = L.job[L.n++];
+        J.d = d;
+        J.d.vec4 = aligned16(d.src) && d.ld % 4 == 0;
+        J.ldd_r = b3_kpad(d.cols); J.ldd_t = b3_kpad(d.rows);
+        J.keep = d.p > 0.f ? 1.0f / (1.0f - d.p) : 1.0f;
+        J.gx = (int)ceil_div(d.dst_r ? J.ldd_r : d.cols, 64);
+        J.gy = (int)ceil_div(d.dst_t ? J.ldd_t : d.rows, 64);
+        J.first = (int)blocks;
+        blocks += (int64_t)J.gx * J.gy;
+    }
+    if (L.n == 0) return GIST_OK;
+    if (blocks >= (1LL << 31)) {
+        set_error("b3_split_jobs: %lld blocks", (long long)blocks);
+        return GIST_EINVAL;
+    }
+    hipLaunchKernelGGL(b3_split_kernel, dim3((unsigned)blocks), dim3(B3S_THREADS), 0, st, L);
     return launch_status("b3_dual_split");
 }
+int b3_dual_split(const B3Dual &d, hipStream_t st) { return b3_split_jobs(&d, 1, st); }
 
 int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, const float *bias, float *c,
                      int64_t ldc, int64_t m, int64_t n, int64_t k, float *slabs, int64_t slab_bytes,

@@ -492,18 +492,22 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
                                             blocked ? p->row_blocks : nullptr);
     }
 
-    if (b3.any && do_fwd) {      // this step's weights, one read each
+    if (b3.any && do_fwd) {      // this step's weights, one read each, one launch for all of them
         Scope sc(p->timer, 3, 0, 0, 0, st);
+        B3Dual jobs[GIST_MAX_LAYERS];
+        int n_jobs = 0;
         for (int k = 0; k < L1; ++k) {
             const B3Layer &hl = b3.layer[k];
             if (!hl.on) continue;
             const gist_layer_desc &l = p->layer[k];
-            B3Dual d{};
+            B3Dual &d = jobs[n_jobs++];
+            d = B3Dual{};
             d.src = l.W; d.ld = 2 * l.n_in; d.rows = l.n_out; d.cols = 2 * l.n_in;
             d.dst_r = hl.Ws;
             d.dst_t = train ? hl.WsT : nullptr;
-            GIST_TRY(b3_dual_split(d, st));
         }
+        for (int i = 0; i < n_jobs; i += B3_SPLIT_MAX_JOBS)
+            GIST_TRY(b3_split_jobs(jobs + i, n_jobs - i < B3_SPLIT_MAX_JOBS ? n_jobs - i : B3_SPLIT_MAX_JOBS, st));
     }
     if (h3.any && do_fwd) {      // this step's weights: rows split for Y = Z.W^T, transposed for dZ = dY.W
         Scope sc(p->timer, 3, 0, 0, 0, st);

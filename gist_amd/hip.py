@@ -212,6 +212,24 @@ def gemm_splits_own_operands(m, n, k):
     return bool(_lib.load().gist_gemm_splits_operands(int(m), int(n), int(k)))
 
 
+def b3_split(src, rows=True, transposed=True, p=0.0, seed=0, offset=0, col_partials=False):
+    """The bf16x3 pre-pass on its own (gist_b3_split_f32), for tests: src[r, c] (fp32, under
+    gist_dropout_f32's mask when p > 0) -> (dst_r, dst_t, partials).  dst_r is int16 [rows, kpad(cols) * 3],
+    dst_t int16 [cols, kpad(rows) * 3] (kpad: a multiple of 64), each row 16-byte chunks of 8 k of one
+    bf16 piece, pieces 1, 2, 3 in turn; partials fp32 [ceil(rows / 64), cols].  Unrequested outputs are None."""
+    L = _lib.load()
+    sp, ld = _mat(src, 'src')
+    n, d = src.shape
+    kpad = lambda k: -(-k // 64) * 64
+    dr = torch.empty((n, kpad(d) * 3), dtype=torch.int16, device=src.device) if rows else None
+    dt = torch.empty((d, kpad(n) * 3), dtype=torch.int16, device=src.device) if transposed else None
+    cp = torch.empty((-(-n // 64), d), dtype=torch.float32, device=src.device) if col_partials else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(L.gist_b3_split_f32(sp, ld, n, d, float(p), int(seed), int(offset), ptr(dr), ptr(dt), ptr(cp),
+                                   _stream()), 'gist_b3_split_f32')
+    return dr, dt, cp
+
+
 def tuning(knob, value=None):
     """Get (and with a value, set) a tuning hook (include/gist_hip.h gist_tuning_set): explicit
     overrides of the launchers' choices for sweeps and tests; 0 = the launcher decides."""

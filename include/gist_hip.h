@@ -278,6 +278,18 @@ int gist_gemm_slabs_f32(int layout, const float *a, int64_t lda, const float *b,
 int gist_gemm_set_mode(int mode);
 int gist_gemm_get_mode(void);
 
+/* The bf16x3 pre-pass on its own, for tests (an addition: no existing signature changed, ABI 16): one read of src[rows, cols] (row pitch ld, in
+ * elements) under gist_dropout_f32's mask (p = 0: none; element index offset + r * cols + c) written as
+ * the split operand with k = columns, dst_r[rows][kpad(cols)], and/or the one with k = rows,
+ * dst_t[cols][kpad(rows)] (NULL: skip), where kpad(k) = k rounded up to a multiple of 64 and an element
+ * is 6 bytes: row r = [k0..7 bf16(x)] [k0..7 bf16(x - b1)] [k0..7 bf16(x - b1 - b2)] [k8..15 ...],
+ * zeros past k.  col_partials (NULL: none) receives [ceil(rows / 64)][cols] column sums, one row per 64
+ * rows of the dropped tensor, summed as gist_colsum_f32's first stage.  The kernel of gist_sage_step's
+ * and gist_gemm_*'s bf16x3 operands; whatever the GEMM mode.  No reference counterpart. */
+int gist_b3_split_f32(const float *src, int64_t ld, int64_t rows, int64_t cols, float p,
+                      uint64_t seed, uint64_t offset, uint16_t *dst_r, uint16_t *dst_t,
+                      float *col_partials, gist_stream_t stream);
+
 /* Tuning hooks: explicit, process-wide overrides of choices the launchers otherwise make
  * themselves (value 0 = the launcher decides; the default for every knob).  They exist for
  * sweeps (scripts/) and so that tests reach both variants of a kernel on one shape; the library
