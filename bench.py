@@ -30,14 +30,22 @@ fp32 on v_mfma_f32_16x16x32_bf16 -- what is dropped is below one fp32 rounding o
 error against float64 is at the fp32-MFMA kernel's level on every operand class including
 cancellation, 2^40 in-row range and exponent extremes (tests/test_gemm_b3_gpu.py); the golden training
 run is repeated forced onto this kernel (tests/test_e2e_gpu.py).  Small projections (class layer,
-per-rank widths below the tile threshold) run on v_mfma_f32_32x32x2_f32.  At N=1 the same process
-then re-times the workload with every projection on the fp32 MFMA (leg `f32_mfma`, --gemm-mode f32)
-and with the 3-term f16 split (leg `f16x3_split`: 22 of 24 operand bits, narrower than fp32 and
-therefore never `value`), each with its own roofline.
+per-rank widths below the tile threshold) run on v_mfma_f32_32x32x2_f32.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the projection GEMM),
-`roofline_spmm` (the SpMM against HBM), `cpu_baseline` (the oracle timed on host cores, all
-cores and one thread).
+Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the projection GEMM) and
+`roofline_spmm` (the SpMM against HBM), both from HIP events the headline's own timed region
+records on a few of its steps.  A plain run does nothing else: set-up, warm-up, the timed steps,
+--dump-outputs, the line.
+
+    python bench.py ... --full
+        also measures, after the headline and in the same line: at N=1 the workload re-timed with
+        every projection on the fp32 MFMA (leg `f32_mfma`) and with the 3-term f16 split (leg
+        `f16x3_split`: 22 of 24 operand bits, narrower than fp32 and therefore never `value`), each
+        with its own roofline; the reference's loop body (leg `module_path`); the same model on an
+        unplanted graph (leg `unplanted_graph`, a child process); the launch floor; the achievable
+        HBM bandwidth beside `roofline_spmm`; `cpu_baseline` (the oracle timed on host cores, all
+        cores and one thread).  N>1: the weight exchange timed on its own; --config 5 at N=1: the
+        H=32768 exchange.  The --no-*-leg / --no-cpu-baseline options drop single parts of it.
 
     python bench.py ... --dump-outputs DIR
         also writes the last timed step's loss and updated parameters (rank 0) to DIR/*.npy:
@@ -98,19 +106,23 @@ def parse():
                          'own loop body -- pred = model(cluster); loss = loss_f(pred[mask], labels[mask]); '
                          'optimizer.zero_grad(); loss.backward(); optimizer.step() (cluster_gcn/cluster_gcn.py:96-105) -- on '
                          'gist_amd.modules.GCN / nn.CrossEntropyLoss / optim.Adam / sampler.ClusterIter (N = 1 only)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure what its figure does not need: the other GEMM modes, the module '
+                         'path and the unplanted graph (N = 1), the launch floor, the achievable HBM bandwidth, the CPU '
+                         'baseline, the weight exchange on its own (N > 1) and config 5\'s H=32768 exchange (N = 1)')
     ap.add_argument('--no-module-leg', action='store_true',
-                    help='skip the module_path leg of the default N = 1 line')
+                    help='--full: skip the module_path leg of the N = 1 line')
     ap.add_argument('--no-unplanted-leg', action='store_true',
-                    help='skip the unplanted_graph leg of the default N = 1 line (the same model on the power-law community '
+                    help='--full: skip the unplanted_graph leg of the N = 1 line (the same model on the power-law community '
                          'graph cut by gist_partition_graph, in a child process)')
     ap.add_argument('--no-second-leg', action='store_true',
-                    help='N=1: skip re-timing the workload in the other GEMM mode')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                    help='--full, N=1: skip re-timing the workload in the other GEMM modes')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--cpu-steps', type=int, default=0,
-                    help='oracle steps timed on all host cores after one warm-up step (0 = one full epoch); the '
+                    help='--full: oracle steps timed on all host cores after one warm-up step (0 = one full epoch); the '
                          '1-thread figure times 12')
     ap.add_argument('--cpu-budget', type=float, default=90.0,
-                    help='wall-time bound (s) of the all-cores oracle sample; the 1-thread sample gets half')
+                    help='--full: wall-time bound (s) of the all-cores oracle sample; the 1-thread sample gets half')
     ap.add_argument('--tune', action='append', default=[], metavar='KNOB=VALUE',
                     help='development A/B: set a tuning hook of the library (gist_amd._lib.TUNE) before the run; recorded in '
                          'the line as config.tune')
@@ -285,7 +297,7 @@ def cpu_baseline(ds, par_order, dims, use_layernorm, p_drop, n_steps, seed, thre
     forward with dropout masks, CE, backward, Adam) -- the reference's timing definition
     (cluster_gcn.py:91,106-108: the epoch loop's wall time, evaluation excluded).  One untimed
     warm-up step, then up to n_steps steps; `budget_s` bounds the timed steps' wall time (a slow host
-    must not turn the default bench run into a quarter of an hour).
+    must not turn a --full bench run into a quarter of an hour).
     Returns (median step s, steps timed, wall s of the timed steps, thread pools)."""
     from threadpoolctl import threadpool_limits
     from oracle import gist_oracle as O
@@ -670,9 +682,11 @@ def main():
 
     # workspaces are sized for the split path (a superset of what mode f32 needs), then the
     # requested mode is selected for the headline run
-    second_leg = world == 1 and not args.no_second_leg
-    # (sized in the mode with the largest workspaces among the ones this run will use)
-    hip.gemm_mode('bf16x3' if (second_leg or args.gemm_mode == 'bf16x3') else args.gemm_mode)
+    second_leg = world == 1 and args.full and not args.no_second_leg
+    # (sized in the mode with the largest workspaces among the ones a --full run of these arguments uses, with or without
+    # --full: the headline's set-up and timed steps do not depend on it)
+    hip.gemm_mode('bf16x3' if ((world == 1 and not args.no_second_leg) or args.gemm_mode == 'bf16x3')
+                  else args.gemm_mode)
     g = ds.g
     in_feats, n_classes = g.ndata['feat'].shape[1], ds.num_classes
     train_nid = np.arange(g.number_of_nodes(), dtype=np.int64)
@@ -1094,7 +1108,7 @@ def main():
     # (a narrow-width step is launch-bound: 14-27 kernels of 5-50 us; the chain of empty launches is the time below which
     # no arrangement of the same number of kernels can go -- reported in the same line as the step it bounds)
     launch_floor = None
-    if native and world == 1:      # (N > 1: extra steps on one rank would enter a weight exchange alone)
+    if args.full and native and world == 1:      # (N > 1: extra steps on one rank would enter a weight exchange alone)
         try:
             Lc = hip._lib.load()
             c0 = int(Lc.gist_launch_count())
@@ -1124,9 +1138,16 @@ def main():
         except Exception as e:                          # report, never fake
             launch_floor = {'error': repr(e)}
 
-    # ---- weight exchange, measured on its own (outside the timed region) ----------------------
+    # ---- weight exchange: the syncs inside the timed region, and with --full measured on its own (outside it) -----------
     sync_info = None
     if ist_model is not None:
+        P = ist_model.sub.numel
+        sync_info = {
+            'all_gather_bytes_per_rank': int(4 * P), 'all_gather_bytes_total': int(4 * P * world),
+            'syncs_inside_timed_region': n_sync_timed,
+            'sync_ms_inside_timed_region': [round(a.elapsed_time(b_), 4) for a, b_ in sync_timed],
+        }
+    if ist_model is not None and args.full:
         reps = 3
         fence()
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True),
@@ -1146,20 +1167,16 @@ def main():
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         s_ms, d_ms = float(t[0].item()), float(t[1].item())
-        P = ist_model.sub.numel
-        sync_info = {
+        sync_info.update({
             'sync_ms_per_exchange': round(s_ms, 4), 'dispatch_ms': round(d_ms, 4),
             'measured': 'median of %d sync_model + dispatch_model pairs after the timed region, '
                         'max over ranks (HIP events)' % reps,
-            'all_gather_bytes_per_rank': int(4 * P), 'all_gather_bytes_total': int(4 * P * world),
-            'syncs_inside_timed_region': n_sync_timed,
-            'sync_ms_inside_timed_region': [round(a.elapsed_time(b_), 4) for a, b_ in sync_timed],
             'amortized_ms_per_step': round((s_ms + d_ms) / args.iter_per_site, 5),
-        }
+        })
 
     # ---- --config 5 on one GPU: the H=32768, S=8 weight exchange, measured on this GPU ----------
     uw_info = None
-    if args.config == 5 and world == 1 and args.emulated_rank_of:
+    if args.full and args.config == 5 and world == 1 and args.emulated_rank_of:
         uw_info = ultra_wide_exchange(dev, in_feats, n_classes, args.emulated_rank_of * H, args.emulated_rank_of,
                                       L, args.iter_per_site)
 
@@ -1187,7 +1204,7 @@ def main():
         engine.check_extract()
 
     # ---- N=1: the same workload through the reference's own loop body (module path), same process ----------------
-    if world == 1 and ist_model is None and not module_headline and not args.no_module_leg:
+    if args.full and world == 1 and ist_model is None and not module_headline and not args.no_module_leg:
         try:
             ml = ModuleLoop()
             n_re = max(args.steps, 10)      # (as many steps as the headline: a 10-step leg is noise-limited)
@@ -1237,14 +1254,15 @@ def main():
     # by a partitioner are uneven (every second batch of this graph has a ninth row tile) and now and then two parts of one
     # community share a batch: the kernels' schedule for those shapes is part of the product (sampler.py:85-93 batches
     # whatever METIS returns), so its number sits in the same line.
-    if (world == 1 and ist_model is None and not args.no_unplanted_leg and args.dataset == 'reddit-synth'
+    if (args.full and world == 1 and ist_model is None and not args.no_unplanted_leg and args.dataset == 'reddit-synth'
             and args.partition == 'planted' and args.host_path == 'engine'):
         import subprocess
         n_un = max(args.steps // 2, 50)
+        # (--full with its own legs off: the child's roofline_spmm carries the measured-copy bandwidth, like the headline's)
         cmd = [sys.executable, os.path.abspath(__file__), '--dataset', 'reddit-communities', '--steps', str(n_un),
                '--warmup', str(max(min(args.warmup, 10), 3)), '--n-hidden', str(H), '--n-layers', str(L),
                '--dropout', str(args.dropout), '--gemm-mode', args.gemm_mode, '--batch-parts', str(batch_size),
-               '--no-second-leg', '--no-module-leg', '--no-cpu-baseline', '--no-unplanted-leg']
+               '--full', '--no-second-leg', '--no-module-leg', '--no-cpu-baseline', '--no-unplanted-leg']
         for kv in args.tune:
             cmd += ['--tune', kv]
         try:
@@ -1397,13 +1415,9 @@ def main():
                 s_bytes += 4.0 * (n + 1) + 4.0 * z + 4.0 * n_src * d + 4.0 * n * d
             s_ach = s_bytes / (s_ms * 1e-3) / 1e9 if s_ms > 0 else 0.0
             traffic, src = _traffic('spmm_traffic.json')
-            copy_gbs = measured_copy_gbs(dev)
             out['roofline_spmm'] = {
                 'kernel': ('gist::spmm_csr_mfma_kernel (block-dense, wide layers)' if H // S >= 1536 else 'gist::spmm_csr_lds2_kernel (LDS gather, wide layers)') + ("; the F=%d input layer's aggregation is formed by the batch extraction (no launch)" % in_feats if engine.plan is not None and engine.plan.feat_intra else '; gist::spmm_csr_rowsplit_kernel / spmm_csr_kernel for the F=%d input layer' % in_feats), 'bound': 'hbm', 'achieved': round(s_ach, 2),
                 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(s_ach / HBM_PEAK_GBS, 4),
-                # achievable HBM bandwidth on this box: a 1 GiB device-to-device copy (read+write)
-                'peak_measured_copy': round(copy_gbs, 1),
-                'frac_of_measured_copy': round(s_ach / copy_gbs, 4) if copy_gbs > 0 else None,
                 'traffic': traffic, 'traffic_source': src, 'launches': len(sp),
                 'avg_launch_ms': round(s_ms / max(len(sp), 1), 5),
                 'avg_algorithmic_bytes': round(s_bytes / max(len(sp), 1), 1),
@@ -1411,6 +1425,11 @@ def main():
                 'mean_batch_rows': round(float(np.mean(n_log)), 1),
                 'mean_batch_nnz': round(float(nnz.mean()), 1),
             }
+            if args.full:      # achievable HBM bandwidth on this box: a 1 GiB device-to-device copy (read+write)
+                copy_gbs = measured_copy_gbs(dev)
+                out['roofline_spmm'].update({
+                    'peak_measured_copy': round(copy_gbs, 1),
+                    'frac_of_measured_copy': round(s_ach / copy_gbs, 4) if copy_gbs > 0 else None})
         if n_log:
             nl = np.asarray(n_log)
             out['batch_rows'] = {'min': int(nl.min()), 'mean': round(float(nl.mean()), 1), 'max': int(nl.max()),
@@ -1442,7 +1461,7 @@ def main():
         if dumped is not None:
             out['dumped_outputs'] = {'dir': os.path.abspath(args.dump_outputs), 'arrays': dumped}
         out.update(legs)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 ncpu = host_cores()
                 # SURVEY 8d / VERDICT r3 item 7: one warm-up step, then ONE FULL EPOCH on all cores (the reference's

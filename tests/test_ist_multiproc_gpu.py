@@ -63,7 +63,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '6',
-           '--warmup', '2', '--n-hidden', '256', '--iter-per-site', '4', '--timing-every', '2']
+           '--warmup', '2', '--n-hidden', '256', '--iter-per-site', '4', '--timing-every', '2', '--full']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().split('\n') if l.startswith('{')]
