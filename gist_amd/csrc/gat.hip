@@ -377,9 +377,10 @@ using namespace gist;
 
 extern "C" int gist_gat_scores_f32(const float *Z, int64_t ldz, const float *A, int64_t n_rows, int64_t heads,
                                    int64_t out_dim, float *s_src, float *s_dst, gist_stream_t stream) {
-    GIST_REQUIRE(Z && A && s_src && s_dst, "gist_gat_scores_f32: null pointer");
+    // (every entry point: no pointer is read without rows -- torch hands NULL for a tensor without elements)
     GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim, "gist_gat_scores_f32: bad sizes");
     if (n_rows == 0) return GIST_OK;
+    GIST_REQUIRE(Z && A && s_src && s_dst, "gist_gat_scores_f32: null pointer");
     hipLaunchKernelGGL(gat_scores_kernel, dim3((unsigned)ceil_div(n_rows, kGatRowsPerBlock)), dim3(256), 0,
                        as_stream(stream), Z, ldz, A, n_rows, (int)heads, (int)out_dim, s_src, s_dst);
     return launch_status("gist_gat_scores_f32");
@@ -389,10 +390,11 @@ extern "C" int gist_gat_aggregate_f32(const int32_t *rowptr, const int32_t *col,
                                       const float *s_src, const float *s_dst, int64_t n_rows, int64_t heads,
                                       int64_t out_dim, int elu, float *out, int64_t ldo, float *M, float *L,
                                       gist_stream_t stream) {
-    GIST_REQUIRE(rowptr && col && Z && s_src && s_dst && out && M && L, "gist_gat_aggregate_f32: null pointer");
     GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim && ldo >= out_dim,
                  "gist_gat_aggregate_f32: bad sizes");
     if (n_rows == 0) return GIST_OK;
+    // (col is read only inside rowptr's ranges: it may be NULL for a graph without edges, as in gist_spmm_csr_f32)
+    GIST_REQUIRE(rowptr && Z && s_src && s_dst && out && M && L, "gist_gat_aggregate_f32: null pointer");
     const bool v4 = gat_vec4(out_dim, {ldz, ldo}, {Z, out});
     const int lpg = gat_lpg(out_dim, v4 ? 4 : 1);
     const dim3 grid((unsigned)ceil_div(n_rows, kGatRowsPerBlock));
@@ -406,12 +408,12 @@ extern "C" int gist_gat_backward_dst_f32(const int32_t *rowptr, const int32_t *c
                                          const float *s_src, const float *s_dst, const float *M, const float *L,
                                          int64_t n_rows, int64_t heads, int64_t out_dim, int elu, float *G,
                                          int64_t ldgm, float *ds_dst, float *D, gist_stream_t stream) {
-    GIST_REQUIRE(rowptr && col && Z && d_out && s_src && s_dst && M && L && G && ds_dst && D && (out || !elu),
-                 "gist_gat_backward_dst_f32: null pointer");
     GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim && ldg >= out_dim &&
                      ldgm >= out_dim && (!elu || ldo >= out_dim),
                  "gist_gat_backward_dst_f32: bad sizes");
     if (n_rows == 0) return GIST_OK;
+    GIST_REQUIRE(rowptr && Z && d_out && s_src && s_dst && M && L && G && ds_dst && D && (out || !elu),
+                 "gist_gat_backward_dst_f32: null pointer");
     const hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(gat_grad_in_kernel, dim3((unsigned)ceil_div(n_rows * out_dim, 256)), dim3(256), 0, st, d_out,
                        ldg, out, ldo, n_rows, (int)out_dim, (int)heads, elu ? 1 : 0, G, ldgm);
@@ -431,12 +433,12 @@ extern "C" int gist_gat_backward_src_f32(const int32_t *t_rowptr, const int32_t 
                                          const float *D, const float *ds_dst, int64_t n_rows, int64_t heads,
                                          int64_t out_dim, float *dZ, int64_t lddz, float *ds_src,
                                          gist_stream_t stream) {
-    GIST_REQUIRE(t_rowptr && t_col && Z && G && A && s_src && s_dst && M && L && D && ds_dst && dZ && ds_src,
-                 "gist_gat_backward_src_f32: null pointer");
     GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim && lddz >= heads * out_dim &&
                      ldgm >= out_dim,
                  "gist_gat_backward_src_f32: bad sizes");
     if (n_rows == 0) return GIST_OK;
+    GIST_REQUIRE(t_rowptr && Z && G && A && s_src && s_dst && M && L && D && ds_dst && dZ && ds_src,
+                 "gist_gat_backward_src_f32: null pointer");
     const bool v4 = gat_vec4(out_dim, {ldz, ldgm, lddz}, {Z, G, dZ});
     const int lpg = gat_lpg(out_dim, v4 ? 4 : 1);
     const dim3 grid((unsigned)ceil_div(n_rows, kGatRowsPerBlock));
@@ -453,8 +455,8 @@ extern "C" int64_t gist_gat_attn_grad_workspace_floats(int64_t n_rows, int64_t h
 extern "C" int gist_gat_attn_grad_f32(const float *Z, int64_t ldz, const float *ds_src, const float *ds_dst,
                                       int64_t n_rows, int64_t heads, int64_t out_dim, float *partials,
                                       int64_t partial_floats, float *dA, gist_stream_t stream) {
-    GIST_REQUIRE(Z && ds_src && ds_dst && dA, "gist_gat_attn_grad_f32: null pointer");
     GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim, "gist_gat_attn_grad_f32: bad sizes");
+    GIST_REQUIRE(dA && (n_rows == 0 || (Z && ds_src && ds_dst)), "gist_gat_attn_grad_f32: null pointer");
     const int64_t need = gist_gat_attn_grad_workspace_floats(n_rows, heads, out_dim);
     if (need > 0 && (!partials || partial_floats < need)) {
         set_error("gist_gat_attn_grad_f32: workspace too small (%lld < %lld floats)", (long long)partial_floats,

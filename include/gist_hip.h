@@ -898,7 +898,9 @@ int gist_sage_step_extracts_next(const gist_step_plan *plan, int64_t n, int flag
  * order [src, dst] as modules.py:41-43).  s_src, s_dst, M, L, D, ds_src, ds_dst are [n, H]
  * contiguous.  Every sum has a fixed order (no float atomics): bitwise reproducible.
  * Vectorised paths need F % 4 == 0 and 16-byte aligned operands; any F >= 1, H >= 1 is
- * correct.
+ * correct.  col / t_col are read only inside the row pointers' ranges: NULL for a graph
+ * without edges.  With n = 0 nothing is read or written (but dA, the empty sum 0): every
+ * [n, .] pointer may be NULL.
  * ------------------------------------------------------------------------- */
 
 /* s_src[r,h] = Z[r, hF:(h+1)F] . A[h, 0:F],  s_dst[r,h] = Z[r, hF:(h+1)F] . A[h, F:2F].

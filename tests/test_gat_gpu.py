@@ -110,6 +110,12 @@ CASES = [  # (in, out, heads, score scale)
     (602, 256, 3, 1.0),
     (602, 64, 1, 1.0),
     (7, 256, 4, 1.0),
+    # several column passes of the walkers (VEC = 4 past F = 256, VEC = 1 past F = 64) and the rest of the (VEC, LPG)
+    # instantiations: VEC = 4 with 32 lanes per edge group, VEC = 1 with 32
+    (602, 512, 4, 1.0),
+    (7, 130, 2, 60.0),
+    (64, 100, 3, 1.0),
+    (602, 17, 8, 1.0),
 ]
 
 
@@ -198,8 +204,8 @@ def _ref_model_logits(cnt, x, params, n_layers_heads):
     return h
 
 
-def test_gat_teacher_forced_cluster_step_and_evaluate():
-    """One step (forward, CE, backward, gist_amd.optim.Adam) of a 2-layer 4-head GAT on a real ClusterIter batch of
+def _teacher_forced_step_and_evaluate(n_layers, hidden, heads):
+    """One step (forward, CE, backward, gist_amd.optim.Adam) of an n_layers GAT on a real ClusterIter batch of
     datasets.toy(), against the float64 restatement on that batch's CSR; then utils.evaluate on the full graph."""
     import random
     from gist_amd import datasets
@@ -214,7 +220,8 @@ def test_gat_teacher_forced_cluster_step_and_evaluate():
     g = ds.g
     train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
     it = ClusterIter('toy', g, len(ds.par_li), 4, train_nid, par_li=ds.par_li, device=DEV)
-    model = GAT(2, g.ndata['feat'].shape[1], 16, ds.num_classes, 4).cuda()
+    model = GAT(n_layers, g.ndata['feat'].shape[1], hidden, ds.num_classes, heads).cuda()
+    layer_heads = [heads] * (n_layers - 1) + [1]
     p0 = [p.detach().double().clone() for p in model.parameters()]
     loss_f = CrossEntropyLoss()
     opt = Adam(model.parameters(), lr=0.01)
@@ -232,7 +239,7 @@ def test_gat_teacher_forced_cluster_step_and_evaluate():
     cnt = _counts(cluster)
     x = cluster.ndata['feat'].double()
     ps = [p.clone().requires_grad_(True) for p in p0]
-    logits = _ref_model_logits(cnt, x, ps, [4, 1])
+    logits = _ref_model_logits(cnt, x, ps, layer_heads)
     ref_loss = F.cross_entropy(logits[mask.bool()], labels[mask.bool()].long())
     ref_loss.backward()
     assert abs(float(loss.detach()) - float(ref_loss.detach())) <= 1e-5 * max(1.0, abs(float(ref_loss)))
@@ -251,7 +258,19 @@ def test_gat_teacher_forced_cluster_step_and_evaluate():
     acc = evaluate(model, gd, gd.ndata['label'], gd.ndata['val_mask'])
     with torch.no_grad():
         ref_logits = _ref_model_logits(_counts(gd), gd.ndata['feat'].double(),
-                                       [p.detach().double() for p in model.parameters()], [4, 1])
+                                       [p.detach().double() for p in model.parameters()], layer_heads)
     vm = gd.ndata['val_mask'].bool()
     ref_acc = float((ref_logits.argmax(1)[vm] == gd.ndata['label'][vm].long()).double().mean())
     assert abs(acc - ref_acc) < 1e-12
+
+
+def test_gat_teacher_forced_cluster_step_and_evaluate():
+    """A 2-layer 4-head GAT at hidden 16."""
+    _teacher_forced_step_and_evaluate(2, 16, 4)
+
+
+@pytest.mark.parametrize('hidden', [512, 130])
+def test_gat_teacher_forced_three_layers_wide(hidden):
+    """A 3-layer 4-head GAT, so a hidden -> hidden layer runs, at widths the walkers cover in several column passes:
+    512 on the float4 path, 130 on the scalar one."""
+    _teacher_forced_step_and_evaluate(3, hidden, 4)
