@@ -53,13 +53,14 @@ __device__ __forceinline__ void d32_store(const D32Args &a, int g_row, int col, 
     if (a.out_scale) v *= a.out_scale[g_row];
     float *o = a.y + (int64_t)g_row * a.ldy + col;
     const uint64_t yi = a.dr.y_base + (uint64_t)g_row * (uint64_t)a.dr.ld + (uint64_t)col;
-    if constexpr (MODE == 1) v *= drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale);
     if (a.accumulate) {
         float old = *o;
         // (__fmul_rn: no contraction into an FMA with the add -- the separate dropout pass rounds the product)
         if constexpr (MODE == 2) old = __fmul_rn(old, drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale));
         v += old;
     }
+    // (mode 1 masks the whole stored value, the old y included: the dropout pass behind the plain call)
+    if constexpr (MODE == 1) v *= drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale);
     *o = v;
 }
 
@@ -220,12 +221,12 @@ __global__ __launch_bounds__(256) void spmm_dense32_kernel(D32Args a) {
                 const int g_row = r0 + (rt0 + t) * 16 + 4 * q + i;
                 float v = acc[t][i] * osc[t][i];
                 const uint64_t yi = a.dr.y_base + (uint64_t)g_row * (uint64_t)a.dr.ld + (uint64_t)col;
-                if constexpr (MODE == 1) v *= drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale);
                 if (a.accumulate) {
                     float o_ = old[t][i];
                     if constexpr (MODE == 2) o_ = __fmul_rn(o_, drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale));
                     v += o_;
                 }
+                if constexpr (MODE == 1) v *= drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale);
                 a.y[(int64_t)g_row * a.ldy + col] = v;
             }
         }

@@ -274,7 +274,12 @@ int gist_gemm_slabs_f32(int layout, const float *a, int64_t lda, const float *b,
  *     by construction.
  * In the split modes a NaN or Inf in an operand row makes the corresponding output row / column
  * non-finite (NaN where fp32 would give Inf) and leaves all other outputs unchanged.  All three
- * replace the same call, self.linear(h), cluster_gcn/modules.py:233, and its autograd. */
+ * replace the same call, self.linear(h), cluster_gcn/modules.py:233, and its autograd.
+ * The aggregations (gist_spmm_*) and non-finite sources: the gather kernels (lane-group, row-split, LDS-staged) make
+ * non-finite exactly the outputs of the rows that have a NaN or Inf source element as a neighbour, in its column.  The
+ * block-dense kernels (the bf16x3 matrix-core and the fp32 block-dense kernels: prepared structures, wide blocked calls)
+ * multiply whole blocks, so 0 x Inf = NaN may in addition reach that column of the other rows of the source's row block
+ * and of a block whose sibling pair holds it; never another column or another block. */
 int gist_gemm_set_mode(int mode);
 int gist_gemm_get_mode(void);
 
@@ -301,7 +306,9 @@ int gist_b3_split_f32(const float *src, int64_t ld, int64_t rows, int64_t cols, 
 #define GIST_TUNE_GEMM_TILE 3     /* fp32 GEMM tile (64 or 128); needs GEMM_SPLITS too          */
 #define GIST_TUNE_GEMM_SPLITS 4   /* fp32 GEMM split-K factor                                   */
 #define GIST_TUNE_SPMM_CHUNK 5    /* rows per XCD chunk of the row-split SpMM                   */
-#define GIST_TUNE_SPMM_SPLIT 6    /* row split of the LDS-staged SpMM (1..8)                    */
+#define GIST_TUNE_SPMM_SPLIT 6    /* row split of the LDS-staged SpMM: 1..64 (the launcher picks 1..16 itself); the fp32
+                                     block-dense SpMM reads 2 or 4 as its row-tile groups per block (other values: its own
+                                     choice) */
 #define GIST_TUNE_SPMM_KERNEL 7   /* blocked SpMM: 1 = LDS gather kernel, 2 = block-dense bf16x3 MFMA kernel, 3 = fp32 block-dense kernel at every width (prepared calls) */
 #define GIST_TUNE_B3C 8           /* convert-on-load bf16x3 GEMM: 1 = never, 2 = also below 0.25 GFLOP */
 #define GIST_TUNE_CLASS_FUSED 9   /* class layer of the fused step: 1 = the four-launch sequence (gist_class_layer_f32 off), 2 = its dW slabs as their own launch (not in the LayerNorm backward's grid) */
