@@ -1,11 +1,14 @@
 """IST / GIST orchestration: feature-dimension partition of a GraphSAGE model into S
-independent sub-GCNs, local training, periodic weight sync.
+independent sub-GCNs, local training, periodic weight sync -- and the same for a GAT.
 
 Reference: cluster_gcn/cluster_gcn_ist_distrib.py
   create_partition            :51-65
   DistributedGNNWrapper       :68-367   (sample_partitions, ini_sync_dispatch_model,
                                          dispatch_model, sync_model)
   train                       :370-479
+Reference: cluster_gcn/cluster_gcn_ist_distrib_gat.py
+  DistributedGATWrapper       :67-391   (GATArena: the flat per-head layout)
+  train_gat                   :393-480  (the loop on the drop-in classes)
 
 What is kept identical (parity surface): the partition sampler (python `random`,
 same call order on every rank), which block of which base tensor each site owns
@@ -376,6 +379,273 @@ def train(ist_model, args, cluster_iterator, evaluator=None, log=print):
                         val_accs.append(evaluator.accuracy('val_mask'))
                         test_accs.append(evaluator.accuracy('test_mask'))
                         # :432-433,446 -- mean training loss of rank 0 since the last evaluation
+                        seg = losses[0][loss_mark:]
+                        trn_losses.append(float(torch.stack(seg).mean().item()) if seg else 0.0)
+                        loss_mark = len(losses[0])
+                    sync_dev()
+                    start_time = time.time()
+    if multi:
+        comm.barrier()
+    return dict(total_time=total_time, losses=losses, events=events, val_accs=val_accs,
+                test_accs=test_accs, trn_losses=trn_losses)
+
+
+def gat_dims(in_feats, n_hidden, n_classes, n_layers, n_heads):
+    """[(in, out, heads)] of the layers of gist_amd.modules.GAT(n_layers, in_feats, n_hidden, n_classes, n_heads): n_heads
+    heads in the first layer and in the n_layers - 2 middle ones, one head of width n_classes last."""
+    return ([(in_feats, n_hidden, n_heads)] + [(n_hidden, n_hidden, n_heads)] * max(n_layers - 2, 0) +
+            [(n_hidden, n_classes, 1)])
+
+
+def gat_params(gat):
+    """[(W [nh*O, I], A [nh, 2O])] of a gist_amd.modules.GAT: its heads stacked as GATArena lays them out."""
+    from .modules import _stack_heads
+    with torch.no_grad():
+        return [tuple(t.detach().clone() for t in _stack_heads(layer.heads)) for layer in gat.layers]
+
+
+class GATArena(object):
+    """Flat parameter storage of a gist_amd.modules.GAT (ParamArena describes GraphSAGE layers).  Per layer the heads'
+    fc weights stacked [nh*O, I], then their attn vectors stacked [nh, 2O]: the layout of modules._stack_heads and of
+    the gist_gat_* C ABI.  `params` / `numel` are what LocalComm and TorchDistComm move."""
+
+    def __init__(self, dims, device):
+        self.dims = list(dims)
+        self.offsets = []
+        off = 0
+        for (i, o, nh) in self.dims:
+            self.offsets.append((off, off + nh * o * i))
+            off += nh * o * i + nh * 2 * o
+        self.numel = off
+        self.device = device
+        self.params = torch.zeros(off, dtype=torch.float32, device=device)
+        self.W, self.A = [], []
+        for (i, o, nh), (w0, a0) in zip(self.dims, self.offsets):
+            self.W.append(self.params[w0:a0].view(nh * o, i))
+            self.A.append(self.params[a0:a0 + nh * 2 * o].view(nh, 2 * o))
+
+    def load(self, params):
+        """params = [(W [nh*O, I], A [nh, 2O])] numpy arrays or tensors."""
+        for k, (W, A) in enumerate(params):
+            self.W[k].copy_(torch.as_tensor(W).reshape(self.W[k].shape).to(self.device))
+            self.A[k].copy_(torch.as_tensor(A).reshape(self.A[k].shape).to(self.device))
+
+    def bind(self, gat, requires_grad=True):
+        """Make every head's fc.weight / attn_fc.weight of `gat` a Parameter over its rows of the arena (no copy)."""
+        import torch.nn as nn
+        for k, layer in enumerate(gat.layers):
+            o = self.dims[k][1]
+            assert len(layer.heads) == self.dims[k][2]
+            for h, head in enumerate(layer.heads):
+                head.fc.weight = nn.Parameter(self.W[k][h * o:(h + 1) * o], requires_grad=requires_grad)
+                head.attn_fc.weight = nn.Parameter(self.A[k][h:h + 1], requires_grad=requires_grad)
+        return gat
+
+
+class DistributedGATWrapper(object):
+    """One rank's view of GIST for the GAT family (cluster_gcn_ist_distrib_gat.py:67-391): a replica of the base GAT and
+    its sub-GAT of width n_hidden / num_subnet per head, over the flat arenas `base` and `sub` (GATArena).
+
+    Constructor as the reference's (`args` needs num_subnet, n_hidden, n_layers, n_heads, rank).  Called with those
+    five arguments only, it draws the initial weights from the torch RNG in the reference's order: on rank 0 the base
+    GAT, then on every rank the sub GAT.  `base_init` = gat_params() layout on rank 0 (others pass None): given, even
+    as None, nothing is drawn.  `blocks`, `comm` as for DistributedGNNWrapper; `seed` is accepted for the same call
+    shape and has no effect (the GAT has no dropout).
+
+    Every loop runs over the layer's own heads, and hidden boundary k (between layers k and k + 1) takes partition k;
+    sample_partitions still draws n_layers partitions, as the reference does.  The split is the same for
+    every head of a layer:
+
+        layer               fc (stacked [nh*O, I])           attn (stacked [nh, 2O])
+        first               rows h*H + idx_0                 columns full_0
+        middle k            rows h*H + idx_k, cols idx_k-1   columns full_k
+        last (one head)     columns idx_last-1               shared: the mean over the sites"""
+
+    def __init__(self, args, g, in_feats, n_classes, device, *, base_init=_UNSET, blocks=None, comm=None, seed=0):
+        from .modules import GAT
+        self.args = args
+        self.g = g
+        self.in_feats, self.n_classes = in_feats, n_classes
+        self.device = device
+        self.S, self.H, self.L, self.nh = args.num_subnet, args.n_hidden, args.n_layers, args.n_heads
+        assert self.H % self.S == 0
+        self.h = self.H // self.S
+        self.rank = args.rank
+        self.blocks = blocks if blocks is not None else HipBlocks()
+        self.comm = comm if comm is not None else TorchDistComm()
+        self.base_dims = gat_dims(in_feats, self.H, n_classes, self.L, self.nh)
+        self.sub_dims = gat_dims(in_feats, self.h, n_classes, self.L, self.nh)
+        self.n_bound = len(self.sub_dims) - 1                 # hidden boundaries that take a partition
+        self.base = GATArena(self.base_dims, device)
+        self.sub = GATArena(self.sub_dims, device)
+
+        def gat(width):
+            return GAT(self.L, in_feats, width, n_classes, self.nh)
+        if base_init is _UNSET:
+            # :75-83 -- the torch RNG draws of the reference, in its order; the drawn values go into the arenas
+            base_model = gat(self.H) if self.rank == 0 else None
+            sub_model = gat(self.h)
+            if base_model is not None:
+                self.base.load(gat_params(base_model))
+            self.sub.load(gat_params(sub_model))
+        else:
+            if base_init is not None:
+                self.base.load(base_init)
+            with torch.device('meta'):                   # (the modules' own storage: no allocation, no RNG draw)
+                base_model = gat(self.H) if self.rank == 0 else None
+                sub_model = gat(self.h)
+        self.base_model = self.base.bind(base_model, False) if base_model is not None else None
+        self.sub_model = self.sub.bind(sub_model)
+        self.gathered = torch.zeros(self.S * self.sub.numel, dtype=torch.float32, device=device)
+        if hasattr(self.comm, 'register'):
+            self.comm.register(self.base, self.sub)
+        self.current_partition = None
+        self._plan = None
+
+    def sample_partitions(self):
+        """:85-90 -- n_layers create_partition calls on python `random` (the last is unused for n_layers >= 2)."""
+        return [create_partition(self.S, self.H) for _ in range(self.L)]
+
+    def _set_partition(self, part):
+        """Per site and layer the (rows, cols) of its fc block and the cols of its attn block in the base arena (None =
+        all); the fc rows expanded over the heads (h*H + idx) once here."""
+        self.current_partition = part
+        dev, H = self.device, self.H
+
+        def i32(t):
+            return t.to(torch.int32).to(dev)
+        self._plan = []
+        for s in range(self.S):
+            layers = []
+            for k, (_, _, nh) in enumerate(self.sub_dims):
+                idx, full = part[k][s] if k < self.n_bound else (None, None)
+                prev = part[k - 1][s][0] if k > 0 else None
+                rows = (torch.arange(nh)[:, None] * H + idx[None, :]).reshape(-1) if idx is not None else None
+                layers.append((i32(rows) if rows is not None else None, i32(prev) if prev is not None else None,
+                               i32(full) if full is not None else None))
+            self._plan.append(layers)
+
+    def _gather_own(self):
+        """Slice the local base replica into this rank's sub-model (:302-391): one gather per (layer, tensor); the
+        shared last attn is copied whole."""
+        for k, (rows, cols, acols) in enumerate(self._plan[self.rank]):
+            self.blocks.gather(self.base.W[k], rows, cols, self.sub.W[k])
+            self.blocks.gather(self.base.A[k], None, acols, self.sub.A[k])
+
+    def ini_sync_dispatch_model(self, part=None):
+        """:207-300 -- the base leaves rank 0 once (replication), then every rank slices its own sub-model locally."""
+        part = part if part is not None else self.sample_partitions()
+        if self.comm.world_size() > 1:
+            self.comm.broadcast(self.base.params, src=0)
+        self._set_partition(part)
+        self._gather_own()
+
+    def dispatch_model(self, part=None):
+        """:302-391 -- new partition, local gather, no communication."""
+        self._set_partition(part if part is not None else self.sample_partitions())
+        self._gather_own()
+
+    def sync_gather(self):
+        """Phase 1 of sync_model: collect every site's flat sub arena (the one collective)."""
+        if self.comm.world_size() > 1:
+            self.comm.all_gather_flat(self.gathered, self.sub.params)
+        else:
+            self.gathered[:self.sub.numel].copy_(self.sub.params)
+
+    def sync_apply(self):
+        """Phase 2: scatter all S sites' blocks into the local base replica (at most two scatters per site and layer);
+        the shared last attn becomes the mean over the sites in site order (:96-100), in the base and the sub-model."""
+        P = self.sub.numel
+        last = len(self.sub_dims) - 1
+        for s in range(self.S):
+            site = self.gathered[s * P:(s + 1) * P]
+            for k, (rows, cols, acols) in enumerate(self._plan[s]):
+                (i, o, nh), (w0, a0) = self.sub_dims[k], self.sub.offsets[k]
+                self.blocks.scatter(site[w0:a0].view(nh * o, i), rows, cols, self.base.W[k])
+                if k < last:
+                    self.blocks.scatter(site[a0:a0 + nh * 2 * o].view(nh, 2 * o), None, acols, self.base.A[k])
+        a0 = self.sub.offsets[last][1]
+        self.blocks.mean_rows(self.gathered[a0:], P, self.S, self.sub.A[last].numel(), self.base.A[last].view(-1))
+        self.sub.A[last].copy_(self.base.A[last])
+
+    def sync_model(self):
+        """:96-205 -- one all-gather of the flat sub arenas, then on-device scatters."""
+        self.sync_gather()
+        self.sync_apply()
+
+
+def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print):
+    """The GIST loop of cluster_gcn_ist_distrib_gat.py:393-480 on the drop-in classes: `ist_model.sub_model(cluster)`,
+    masked gist_amd.nn.CrossEntropyLoss, a new gist_amd.optim.Adam at every dispatch point, `evaluate(base_model, g,
+    ...)` on rank 0 (`g` on the device).  The schedule is the SAGE one: no re-dispatch in epoch 0, sync at multiples of
+    iter_per_site and at the last iteration, evaluation after the first sync of each epoch.
+
+    `ist_model` is this rank's DistributedGATWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites then
+    run in this process, the partition sampled once per dispatch.  The step losses stay on the device (the reference's
+    per-step `float(loss)` would wait for it every step); each evaluation averages them.  Returns total_time,
+    per-site step losses, events, accuracies and the mean training loss per evaluation."""
+    from .nn import CrossEntropyLoss
+    from .optim import Adam
+    from .utils import evaluate
+    models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
+    local = len(models) > 1
+    comm = models[0].comm
+    multi = (not local) and comm.world_size() > 1
+    is_rank0 = models[0].rank == 0
+    dev = models[0].device
+    sync_dev = (lambda: torch.cuda.synchronize(dev)) if dev.type == 'cuda' else (lambda: None)
+    loss_fcn = CrossEntropyLoss()
+    local_epochs = args.n_epochs // args.num_subnet
+    losses = [[] for _ in models]
+    events, val_accs, test_accs, trn_losses = [], [], [], []
+    optimizers = [None] * len(models)
+    loss_mark, total_iter, total_time = 0, 0, 0.0
+    sync_dev()
+    start_time = time.time()
+    for e in range(local_epochs):
+        log(f'{models[0].rank}: running epoch {e} / {local_epochs}', flush=True)
+        run_eval = True
+        for j, cluster in enumerate(cluster_iterator):
+            if total_iter % args.iter_per_site == 0:
+                if e > 0:
+                    if multi:
+                        comm.barrier()
+                    part = models[0].sample_partitions() if local else None
+                    for m in models:
+                        m.dispatch_model(part)
+                    events.append('dispatch')
+                for si, m in enumerate(models):
+                    m.sub_model.train()
+                    optimizers[si] = Adam(m.sub_model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+            cluster = cluster.to(dev)
+            batch_labels = cluster.ndata['label']
+            batch_train_mask = cluster.ndata['train_mask']
+            for si, m in enumerate(models):
+                optimizers[si].zero_grad()
+                pred = m.sub_model(cluster)
+                loss = loss_fcn(pred[batch_train_mask], batch_labels[batch_train_mask])
+                loss.backward()
+                losses[si].append(loss.detach())
+                optimizers[si].step()
+            events.append('step')
+            total_iter += 1
+            last = (j == len(cluster_iterator) - 1) and (e == local_epochs - 1)
+            if total_iter % args.iter_per_site == 0 or last:
+                if multi:
+                    comm.barrier()
+                for m in models:
+                    m.sync_gather()
+                for m in models:
+                    m.sync_apply()
+                events.append('sync')
+                if run_eval or last:
+                    sync_dev()
+                    total_time += time.time() - start_time
+                    run_eval = False
+                    events.append('eval')
+                    if is_rank0:
+                        val_accs.append(evaluate(models[0].base_model, g, labels, val_mask))
+                        test_accs.append(evaluate(models[0].base_model, g, labels, test_mask))
                         seg = losses[0][loss_mark:]
                         trn_losses.append(float(torch.stack(seg).mean().item()) if seg else 0.0)
                         loss_mark = len(losses[0])

@@ -28,8 +28,9 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 
-def build_parser():
-    parser = argparse.ArgumentParser(description='GCN')
+def add_ist_args(parser):
+    """The flags the reference's IST scripts share (cluster_gcn_ist_distrib.py:520-559,
+    cluster_gcn_ist_distrib_gat.py:538-577)."""
     from gist_amd.dgl_compat.data import register_data_args
     register_data_args(parser)
     parser.add_argument("--iter_per_site", type=int, default=5)
@@ -52,6 +53,11 @@ def build_parser():
     parser.add_argument("--use-pp", action='store_true')
     parser.add_argument("--normalize", action='store_true')
     parser.add_argument("--save_results", action='store_true')
+    return parser
+
+
+def build_parser():
+    parser = add_ist_args(argparse.ArgumentParser(description='GCN'))
     parser.add_argument("--fig-dir", type=str, default='../report/example_pic/')
     parser.add_argument("--fig-name", type=str, default='name')
     parser.add_argument("--use-f1", action='store_true')
@@ -77,23 +83,11 @@ def save_results(args, res, log=print):
     return path
 
 
-def main(args=None, dataset=None, log=print, ultra_wide=False):
-    from gist_amd import ist
+def setup(args, dataset=None, log=print):
+    """:565-591 -- seeds (the same on every rank), this rank's device, the process group of num_subnet ranks, the
+    dataset (`dataset` given: used instead of load_data) and --normalize.  Returns (device, data, g, in_feats,
+    n_classes, train_nid, par_li, psize); `g` stays on the host."""
     from gist_amd.dgl_compat.data import load_data
-    from gist_amd.modules import GCN
-    from gist_amd.sampler import EngineClusterIter
-    from gist_amd.trainer import FullGraphEvaluator
-    if args is None:
-        args = build_parser().parse_args()
-    assert (args.n_hidden % args.num_subnet) == 0
-    if args.use_pp:
-        raise NotImplementedError(
-            'gist_amd: --use-pp cannot work with GCN / ISTSAGELayer in the reference either (the '
-            'feature width doubles after in_feats was read, SURVEY.md appendix C.8); the layer-0 '
-            'pre-aggregation is offered as ClusterIter(..., use_pp=True) + GraphSAGE-style layers')
-    if args.use_f1:
-        log('note: --use-f1 reports micro-F1, which equals argmax accuracy for single-label '
-            'classification (cluster_gcn/utils.py:47-67)', flush=True)
     log('Setting seeds', flush=True)
     torch.manual_seed(args.rnd_seed)                        # :570-572, same seed on every rank
     np.random.seed(args.rnd_seed)
@@ -116,6 +110,26 @@ def main(args=None, dataset=None, log=print, ultra_wide=False):
     train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
     par_li = getattr(data, 'par_li', None)
     psize = len(par_li) if par_li is not None else args.psize
+    return device, data, g, in_feats, n_classes, train_nid, par_li, psize
+
+
+def main(args=None, dataset=None, log=print, ultra_wide=False):
+    from gist_amd import ist
+    from gist_amd.modules import GCN
+    from gist_amd.sampler import EngineClusterIter
+    from gist_amd.trainer import FullGraphEvaluator
+    if args is None:
+        args = build_parser().parse_args()
+    assert (args.n_hidden % args.num_subnet) == 0
+    if args.use_pp:
+        raise NotImplementedError(
+            'gist_amd: --use-pp cannot work with GCN / ISTSAGELayer in the reference either (the '
+            'feature width doubles after in_feats was read, SURVEY.md appendix C.8); the layer-0 '
+            'pre-aggregation is offered as ClusterIter(..., use_pp=True) + GraphSAGE-style layers')
+    if args.use_f1:
+        log('note: --use-f1 reports micro-F1, which equals argmax accuracy for single-label '
+            'classification (cluster_gcn/utils.py:47-67)', flush=True)
+    device, data, g, in_feats, n_classes, train_nid, par_li, psize = setup(args, dataset, log)
     if getattr(args, 'host_path', 'engine') == 'module':
         if ultra_wide:
             raise SystemExit('gist_amd: --host-path module is not offered for cluster_gcn_ist_ultra_wide (its '
