@@ -145,6 +145,9 @@ SIGNATURES = {
                                          _p, _i64, _p, _p]),
     'gist_gat_attn_grad_workspace_floats': (_i64, [_i64, _i64, _i64]),
     'gist_gat_attn_grad_f32': (_int, [_p, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p]),
+    'gist_gat_step_workspace_bytes': (_i64, [_p]),
+    'gist_gat_step_attn_partials_floats': (_i64, [_p]),
+    'gist_gat_step': (_int, [_p, _p, _i64, _f, _f, _f, _f, _f, _i64, _int, _p]),
 }
 
 GIST_MAX_LAYERS = 16
@@ -189,6 +192,28 @@ class StepPlan(ctypes.Structure):
                 ('batch_index', _i32), ('extract_scratch', _p),
                 ('next_ids', _p), ('next_n', _i64), ('next_batch_index', _i32), ('next_drop_offset', _u64),
                 ('feat_intra', _p), ('ld_feat_intra', _i64), ('sibling_parts', ctypes.c_int32)]
+
+
+class GATLayerDesc(ctypes.Structure):
+    """struct gist_gat_layer_desc (include/gist_hip.h)."""
+    _fields_ = [('n_in', _i64), ('n_out', _i64), ('heads', _i64), ('W', _p), ('A', _p), ('dW', _p), ('dA', _p),
+                ('Z', _p), ('out', _p), ('s_src', _p), ('s_dst', _p), ('m', _p), ('l', _p)]
+
+
+class GATStepPlan(ctypes.Structure):
+    """struct gist_gat_step_plan (include/gist_hip.h)."""
+    _fields_ = [('n_layers', _i32), ('layer', GATLayerDesc * GIST_MAX_LAYERS), ('x0', _p),
+                ('dZ', _p), ('g', _p), ('ds_dst', _p), ('dd', _p), ('ds_src', _p), ('d_out', _p * 2),
+                ('attn_partials', _p), ('attn_partial_floats', _i64),
+                ('dlogits', _p), ('row_loss', _p), ('loss', _p), ('workspace', _p), ('workspace_bytes', _i64),
+                ('params', _p), ('grads', _p), ('exp_avg', _p), ('exp_avg_sq', _p), ('n_params', _i64),
+                ('g_rowptr', _p), ('g_col', _p), ('g_t_rowptr', _p), ('g_t_col', _p),
+                ('feat', _p), ('ld_feat', _i64), ('labels_all', _p), ('remap', _p),
+                ('rowptr', _p), ('col', _p), ('t_rowptr', _p), ('t_col', _p),
+                ('col_capacity', _i64), ('norm', _p), ('labels', _p),
+                ('node_part', _p), ('part_slot', _p), ('batch_index', _i32), ('extract_scratch', _p),
+                ('next_ids', _p), ('next_n', _i64), ('next_batch_index', _i32),
+                ('n_max', _i64), ('timer', _p)]
 
 
 class ExtractPartsDesc(ctypes.Structure):

@@ -1,0 +1,255 @@
+// Native step driver of the GAT family: one C-ABI call issues a whole training iteration of gist_amd.modules.GAT
+// (batch extraction -> per layer gemm_nt, scores, aggregate -> CE -> per layer backward_dst, backward_src, attn_grad,
+// gemm_tn, gemm_nn -> Adam over the flat arena, with the next batch's extraction in the optimiser's grid) on one stream.
+// No kernel of its own: it calls the entry points the op-level API exposes (gist_gat_*, gist_gemm_*, gist_softmax_xent_f32,
+// gist_adam_*), in the order and with the leading dimensions, workspaces and edge order of the module path
+// (gist_amd/ops.py gat_layer_fwd / gat_layer_bwd), so the two are bit-identical.  What it removes is everything between
+// the launches: allocations, the head stacking and its gradient split, autograd nodes, per-tensor optimiser launches.
+#include "common.h"
+
+using namespace gist;
+
+#define GIST_TRY(expr)            \
+    do {                          \
+        int rc_ = (expr);         \
+        if (rc_ != GIST_OK) return rc_; \
+    } while (0)
+
+namespace {
+struct Scope {   // records start now, stop at scope exit
+    gist_timer *t; int64_t slot; hipStream_t s;
+    Scope(gist_timer *t_, int kind, int64_t m, int64_t n, int64_t k, hipStream_t s_)
+        : t(t_), slot(timer_begin(t_, kind, m, n, k, s_)), s(s_) {}
+    ~Scope() { timer_end(t, slot, s); }
+};
+struct ActiveTimer {   // kernels below the entry points see the armed timer for this call only
+    explicit ActiveTimer(gist_timer *t) { tl_timer = t; }
+    ~ActiveTimer() { tl_timer = nullptr; }
+};
+
+// layer count and shapes only: what the size helpers and the step both need before they look at a pointer
+bool shapes_ok(const gist_gat_step_plan *p) {
+    if (p == nullptr || p->n_layers < 1 || p->n_layers > GIST_MAX_LAYERS || p->n_max <= 0 || p->n_max >= (1LL << 31))
+        return false;
+    for (int k = 0; k < p->n_layers; ++k) {
+        const gist_gat_layer_desc &l = p->layer[k];
+        if (l.n_in < 1 || l.n_out < 1 || l.heads < 1 || l.heads * l.n_out >= (1LL << 22) || l.n_in >= (1LL << 22))
+            return false;
+        if (k > 0 && l.n_in != p->layer[k - 1].n_out) return false;
+    }
+    return true;
+}
+
+// the three projections of layer k on a batch of n rows as (m, n, k) of gist_gemm_{nt,tn,nn}_f32
+struct GemmShape { int64_t m, n, k; };
+void layer_gemms(const gist_gat_layer_desc &l, int64_t n, GemmShape (&g)[3]) {
+    const int64_t hf = l.heads * l.n_out;
+    g[0] = GemmShape{n, hf, l.n_in};      // Z = x . W^T
+    g[1] = GemmShape{hf, l.n_in, n};      // dW = dZ^T . x
+    g[2] = GemmShape{n, l.n_in, hf};      // dx = dZ . W
+}
+}  // namespace
+
+// Bytes of gist_gat_step_plan.workspace: the largest gist_gemm_workspace_bytes over every projection of every layer and
+// every batch size up to n_max (the split-K choice is not monotone in the row count).  Host function.
+extern "C" int64_t gist_gat_step_workspace_bytes(const gist_gat_step_plan *p) {
+    if (!shapes_ok(p)) return 0;
+    int64_t need = 0;
+    for (int k = 0; k < p->n_layers; ++k)
+        for (int64_t n = 1; n <= p->n_max; ++n) {
+            GemmShape g[3];
+            layer_gemms(p->layer[k], n, g);
+            for (int q = 0; q < (k > 0 ? 3 : 2); ++q) {
+                const int64_t b = gist_gemm_workspace_bytes(g[q].m, g[q].n, g[q].k);
+                need = b > need ? b : need;
+            }
+        }
+    return need;
+}
+
+// Floats of gist_gat_step_plan.attn_partials: the widest layer's gist_gat_attn_grad_workspace_floats at n_max rows.
+extern "C" int64_t gist_gat_step_attn_partials_floats(const gist_gat_step_plan *p) {
+    if (!shapes_ok(p)) return 0;
+    int64_t need = 0;
+    for (int k = 0; k < p->n_layers; ++k) {
+        const int64_t b = gist_gat_attn_grad_workspace_floats(p->n_max, p->layer[k].heads, p->layer[k].n_out);
+        need = b > need ? b : need;
+    }
+    return need;
+}
+
+static void parts_desc(const gist_gat_step_plan *p, const int32_t *ids, int64_t n, int32_t batch,
+                       gist_extract_parts_desc *x) {
+    const gist_gat_layer_desc &l0 = p->layer[0];
+    x->g_rowptr = p->g_rowptr; x->g_col = p->g_col; x->g_t_rowptr = p->g_t_rowptr; x->g_t_col = p->g_t_col;
+    x->ids = ids; x->n = n; x->n_max = p->n_max;
+    x->node_part = p->node_part; x->part_slot = p->part_slot; x->batch = batch;
+    x->rowptr = p->rowptr; x->col = p->col; x->t_rowptr = p->t_rowptr; x->t_col = p->t_col;
+    x->col_capacity = p->col_capacity; x->norm = p->norm;
+    x->feat = p->feat; x->ld_feat = p->ld_feat; x->n_feat = l0.n_in; x->z0 = p->x0; x->ldz0 = l0.n_in;
+    x->labels_all = p->labels_all; x->labels = p->labels;
+    x->scratch = p->extract_scratch;
+}
+
+extern "C" int gist_gat_step(const gist_gat_step_plan *p, const int32_t *ids, int64_t n, float lr, float beta1,
+                             float beta2, float eps, float weight_decay, int64_t adam_step, int flags,
+                             gist_stream_t s) {
+    // ---- validation: all of it before any device work -------------------------------------------------
+    GIST_REQUIRE(p != nullptr, "gist_gat_step: null plan");
+    GIST_REQUIRE(p->n_layers >= 1 && p->n_layers <= GIST_MAX_LAYERS, "gist_gat_step: bad n_layers");
+    GIST_REQUIRE(shapes_ok(p), "gist_gat_step: bad layer shapes or n_max");
+    GIST_REQUIRE(n > 0, "gist_gat_step: empty batch");
+    GIST_REQUIRE(n <= p->n_max, "gist_gat_step: batch of %lld rows exceeds n_max = %lld", (long long)n,
+                 (long long)p->n_max);
+    const int known = GIST_STEP_EXTRACT | GIST_STEP_TRAIN | GIST_STEP_EXTRACT_NEXT | GIST_STEP_PREEXTRACTED;
+    GIST_REQUIRE(!(flags & (GIST_STEP_PHASE_FORWARD | GIST_STEP_PHASE_BACKWARD | GIST_STEP_PHASE_OPTIMIZER |
+                            GIST_STEP_DLOGITS_GIVEN)),
+                 "gist_gat_step: GIST_STEP_PHASE_* / GIST_STEP_DLOGITS_GIVEN are not supported (one call per iteration)");
+    GIST_REQUIRE((flags & ~known) == 0, "gist_gat_step: unknown flag bits");
+    GIST_REQUIRE(!((flags & GIST_STEP_EXTRACT) && (flags & GIST_STEP_PREEXTRACTED)),
+                 "gist_gat_step: GIST_STEP_EXTRACT and GIST_STEP_PREEXTRACTED exclude each other");
+    const bool train = (flags & GIST_STEP_TRAIN) != 0;
+    GIST_REQUIRE(!(flags & (GIST_STEP_EXTRACT_NEXT | GIST_STEP_PREEXTRACTED)) || train,
+                 "gist_gat_step: GIST_STEP_EXTRACT_NEXT / GIST_STEP_PREEXTRACTED belong to training steps");
+    const int L = p->n_layers;
+    GIST_REQUIRE(p->x0 && p->rowptr && p->col && p->t_rowptr && p->t_col && p->labels && p->dlogits && p->row_loss &&
+                     p->loss,
+                 "gist_gat_step: null batch / loss buffer");
+    for (int k = 0; k < L; ++k) {
+        const gist_gat_layer_desc &l = p->layer[k];
+        GIST_REQUIRE(l.W && l.A && l.Z && l.out && l.s_src && l.s_dst && l.m && l.l, "gist_gat_step: null buffer in layer %d", k);
+        GIST_REQUIRE(!train || (l.dW && l.dA), "gist_gat_step: null gradient view in layer %d", k);
+    }
+    if (train) {
+        GIST_REQUIRE(p->dZ && p->g && p->ds_dst && p->dd && p->ds_src && (L == 1 || (p->d_out[0] && p->d_out[1])),
+                     "gist_gat_step: null backward scratch");
+        GIST_REQUIRE(p->params && p->grads && p->exp_avg && p->exp_avg_sq && p->n_params > 0,
+                     "gist_gat_step: null arena");
+        GIST_REQUIRE(adam_step >= 1, "gist_gat_step: adam_step is 1-based");
+        GIST_REQUIRE(p->attn_partial_floats >= 0 && (p->attn_partials || p->attn_partial_floats == 0),
+                     "gist_gat_step: bad attn_partials");
+    }
+    const bool by_parts = p->node_part && p->part_slot && p->extract_scratch && p->batch_index >= 0 &&
+                          gist_extract_parts_supported(p->n_max) == 1;
+    if (flags & GIST_STEP_EXTRACT) {
+        GIST_REQUIRE(ids != nullptr, "gist_gat_step: null ids");
+        GIST_REQUIRE(p->g_rowptr && p->g_col && p->g_t_rowptr && p->g_t_col && p->feat && p->norm &&
+                         p->ld_feat >= p->layer[0].n_in && p->col_capacity >= 0,
+                     "gist_gat_step: null / bad resident graph");
+        GIST_REQUIRE(by_parts || p->remap != nullptr, "gist_gat_step: extraction needs the part tables or remap");
+    }
+    if (flags & GIST_STEP_EXTRACT_NEXT)
+        GIST_REQUIRE(p->node_part && p->part_slot && p->extract_scratch && p->next_ids && p->next_batch_index >= 0 &&
+                         p->next_n > 0 && p->next_n <= p->n_max && gist_extract_parts_supported(p->n_max) == 1 &&
+                         p->g_rowptr && p->g_col && p->g_t_rowptr && p->g_t_col && p->feat && p->norm,
+                     "gist_gat_step: GIST_STEP_EXTRACT_NEXT needs the part tables, the scratch and next_*");
+    // every projection gets what the op-level wrappers give it (the split-K choice depends on the bytes): nothing where
+    // gist_gemm_workspace_bytes says 0, the plan's workspace otherwise
+    struct Ws { void *p; int64_t bytes; } ws[GIST_MAX_LAYERS][3];
+    for (int k = 0; k < L; ++k) {
+        GemmShape g[3];
+        layer_gemms(p->layer[k], n, g);
+        for (int q = 0; q < 3; ++q) {
+            const bool runs = q == 0 || (train && (q == 1 || k > 0));      // (layer 0 has no dx projection)
+            const int64_t need = runs ? gist_gemm_workspace_bytes(g[q].m, g[q].n, g[q].k) : 0;
+            if (need > 0 && (p->workspace == nullptr || p->workspace_bytes < need)) {
+                set_error("gist_gat_step: workspace too small (%lld < %lld bytes)", (long long)p->workspace_bytes,
+                          (long long)need);
+                return GIST_ENOSPACE;
+            }
+            ws[k][q] = need > 0 ? Ws{p->workspace, p->workspace_bytes} : Ws{nullptr, 0};
+        }
+        if (train) {
+            const int64_t need = gist_gat_attn_grad_workspace_floats(n, p->layer[k].heads, p->layer[k].n_out);
+            if (need > p->attn_partial_floats) {
+                set_error("gist_gat_step: attn_partials too small (%lld < %lld floats)", (long long)p->attn_partial_floats,
+                          (long long)need);
+                return GIST_ENOSPACE;
+            }
+        }
+    }
+
+    hipStream_t st = as_stream(s);
+    ActiveTimer active(p->timer);
+
+    // ---- extraction ---------------------------------------------------------------------------------
+    if (flags & GIST_STEP_EXTRACT) {
+        const gist_gat_layer_desc &l0 = p->layer[0];
+        if (by_parts) {
+            gist_extract_parts_desc x{};
+            parts_desc(p, ids, n, p->batch_index, &x);
+            GIST_TRY(gist_extract_parts_desc_batch(&x, s));
+        } else {
+            GIST_TRY(gist_extract_batch(p->g_rowptr, p->g_col, p->g_t_rowptr, p->g_t_col, ids, n, p->remap, p->rowptr,
+                                        p->col, p->t_rowptr, p->t_col, p->col_capacity, p->norm, p->feat, p->ld_feat,
+                                        l0.n_in, p->x0, l0.n_in, p->labels_all, p->labels, s));
+        }
+    }
+
+    // ---- forward (modules.GAT.forward: h = F.elu(layer(g, h)) for every layer, the last included) --------
+    for (int k = 0; k < L; ++k) {
+        const gist_gat_layer_desc &l = p->layer[k];
+        const int64_t hf = l.heads * l.n_out;
+        const float *x = k == 0 ? p->x0 : p->layer[k - 1].out;
+        {
+            Scope sc(p->timer, 1, n, hf, l.n_in, st);
+            GIST_TRY(gist_gemm_nt_f32(x, l.n_in, l.W, l.n_in, nullptr, l.Z, hf, n, hf, l.n_in, ws[k][0].p,
+                                      ws[k][0].bytes, s));
+        }
+        GIST_TRY(gist_gat_scores_f32(l.Z, hf, l.A, n, l.heads, l.n_out, l.s_src, l.s_dst, s));
+        Scope sc(p->timer, 0, n, n, hf, st);
+        GIST_TRY(gist_gat_aggregate_f32(p->rowptr, p->col, l.Z, hf, l.s_src, l.s_dst, n, l.heads, l.n_out, 1, l.out,
+                                        l.n_out, l.m, l.l, s));
+    }
+    const gist_gat_layer_desc &last = p->layer[L - 1];
+    GIST_TRY(gist_softmax_xent_f32(last.out, last.n_out, p->labels, nullptr, n, p->row_loss, p->loss, p->dlogits,
+                                   last.n_out, n, last.n_out, s));
+    if (!train) return GIST_OK;
+
+    // ---- backward (ops.py gat_layer_bwd, layer by layer from the last) ---------------------------------
+    const float *d_out = p->dlogits;      // (the upstream gradient 1.0 of the module path's loss.backward() is exact)
+    for (int k = L - 1; k >= 0; --k) {
+        const gist_gat_layer_desc &l = p->layer[k];
+        const int64_t hf = l.heads * l.n_out;
+        const float *x = k == 0 ? p->x0 : p->layer[k - 1].out;
+        {
+            Scope sc(p->timer, 0, n, n, hf, st);
+            GIST_TRY(gist_gat_backward_dst_f32(p->rowptr, p->col, l.Z, hf, l.out, l.n_out, d_out, l.n_out, l.s_src,
+                                               l.s_dst, l.m, l.l, n, l.heads, l.n_out, 1, p->g, l.n_out, p->ds_dst,
+                                               p->dd, s));
+        }
+        {
+            Scope sc(p->timer, 0, n, n, hf, st);
+            GIST_TRY(gist_gat_backward_src_f32(p->t_rowptr, p->t_col, l.Z, hf, p->g, l.n_out, l.A, l.s_src, l.s_dst,
+                                               l.m, l.l, p->dd, p->ds_dst, n, l.heads, l.n_out, p->dZ, hf, p->ds_src,
+                                               s));
+        }
+        GIST_TRY(gist_gat_attn_grad_f32(l.Z, hf, p->ds_src, p->ds_dst, n, l.heads, l.n_out, p->attn_partials,
+                                        p->attn_partial_floats, l.dA, s));
+        {
+            Scope sc(p->timer, 1, hf, l.n_in, n, st);
+            GIST_TRY(gist_gemm_tn_f32(p->dZ, hf, x, l.n_in, l.dW, l.n_in, hf, l.n_in, n, ws[k][1].p, ws[k][1].bytes,
+                                      s));
+        }
+        if (k > 0) {      // (layer 0's input is the features: no gradient)
+            float *dx = p->d_out[k & 1];
+            Scope sc(p->timer, 1, n, l.n_in, hf, st);
+            GIST_TRY(gist_gemm_nn_f32(p->dZ, hf, l.W, l.n_in, dx, l.n_in, n, l.n_in, hf, ws[k][2].p, ws[k][2].bytes,
+                                      s));
+            d_out = dx;
+        }
+    }
+
+    // ---- one optimiser launch over the arena; with EXTRACT_NEXT the next batch is extracted in its grid -----
+    if (flags & GIST_STEP_EXTRACT_NEXT) {
+        gist_extract_parts_desc x{};
+        parts_desc(p, p->next_ids, p->next_n, p->next_batch_index, &x);
+        GIST_TRY(gist_adam_segments_extract_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1,
+                                                beta2, eps, weight_decay, adam_step, nullptr, 0, nullptr, 0, 0, nullptr,
+                                                &x, s));
+    } else {
+        GIST_TRY(gist_adam_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1, beta2, eps,
+                               weight_decay, adam_step, s));
+    }
+    return GIST_OK;
+}

@@ -423,6 +423,29 @@ class GATArena(object):
         for (i, o, nh), (w0, a0) in zip(self.dims, self.offsets):
             self.W.append(self.params[w0:a0].view(nh * o, i))
             self.A.append(self.params[a0:a0 + nh * 2 * o].view(nh, 2 * o))
+        # gradient and Adam-moment arenas in the same layout: only a fused step needs them (with_grads)
+        self.grads = self.exp_avg = self.exp_avg_sq = None
+        self.dW, self.dA = [], []
+        self.step = 0
+
+    def with_grads(self):
+        """Allocate (once) the flat gradient and Adam-moment arenas beside `params`, dW / dA as views of the gradient
+        arena: what gist_gat_step (gist_amd.gat_engine.GATEngine) reads and writes.  The parameters are not touched."""
+        if self.grads is None:
+            self.grads = torch.zeros_like(self.params)
+            self.exp_avg = torch.zeros_like(self.params)
+            self.exp_avg_sq = torch.zeros_like(self.params)
+            for (i, o, nh), (w0, a0) in zip(self.dims, self.offsets):
+                self.dW.append(self.grads[w0:a0].view(nh * o, i))
+                self.dA.append(self.grads[a0:a0 + nh * 2 * o].view(nh, 2 * o))
+        return self
+
+    def reset_optimizer(self):
+        """Fresh Adam state (the GIST loop builds a new optimizer at every dispatch point)."""
+        if self.grads is not None:
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+        self.step = 0
 
     def load(self, params):
         """params = [(W [nh*O, I], A [nh, 2O])] numpy arrays or tensors."""

@@ -42,7 +42,8 @@ def build_parser():
     parser.add_argument("--use-f1", action='store_true')
     parser.add_argument("--eval-cpu", action='store_true')
     # (not a flag of the reference) module: the reference's own loop body, statement for statement, on gist_amd.modules.GCN /
-    # nn.CrossEntropyLoss / optim.Adam / sampler.ClusterIter (gist_amd/module_engine.py); engine: one gist_sage_step per iteration
+    # nn.CrossEntropyLoss / optim.Adam / sampler.ClusterIter (gist_amd/module_engine.py); engine: one gist_sage_step (sage) or
+    # gist_gat_step (gat) per iteration
     parser.add_argument("--host-path", choices=['engine', 'module'], default='engine')
     return parser
 
@@ -82,8 +83,11 @@ def main(args, dataset=None, log=print):
                 args.use_layernorm, False, False, 1, True)          # :66-69
         model_holder['m'] = m
         return m
-    if args.model_type == 'gat' or getattr(args, 'host_path', 'engine') == 'module':
-        # GAT has no fused step: it always trains on the reference's loop over the drop-in classes
+    host_path = getattr(args, 'host_path', 'engine')
+    if args.model_type == 'gat' and host_path == 'engine' and not args.use_pp:
+        return main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log)
+    if args.model_type == 'gat' or host_path == 'module':
+        # (--use-pp changes the train graph's features under the iterator: the GAT then keeps the reference's loop)
         return main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     trainer = ClusterGCNTrainer(args.dataset, g, par_li, psize, args.batch_size, args.n_hidden,
                                 args.n_layers, n_classes, args.dropout, args.use_layernorm,
@@ -103,6 +107,47 @@ def main(args, dataset=None, log=print):
     log(f'Best Test: {max(test_accs):.4f}', flush=True)
     return dict(total_time=trainer.total_time, val_accs=val_accs, test_accs=test_accs,
                 model=model_holder['m'])
+
+
+def main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log):
+    """--model-type gat on the fused step: one gist_gat_step per iteration (gist_amd/gat_engine.py), fed by
+    EngineClusterIter.  Same construction order, RNG draws, batch order and arithmetic as main_module_path: same-seed
+    weights are bit-identical whatever the host path."""
+    import time
+    from gist_amd.gat_engine import GATEngine
+    from gist_amd.ist import gat_dims, gat_params
+    from gist_amd.modules import GAT
+    from gist_amd.sampler import EngineClusterIter
+    from gist_amd.utils import evaluate
+    train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
+    it = EngineClusterIter(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li, device=device)
+    g = g.to(device)
+    labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
+    model = GAT(args.n_layers, in_feats, args.n_hidden, n_classes, args.n_heads)   # cluster_gcn_ist_distrib_gat.py:77-79
+    engine = GATEngine(gat_dims(in_feats, args.n_hidden, n_classes, args.n_layers, args.n_heads), it.n_max, device)
+    engine.arena.load(gat_params(model))
+    engine.bind(model)                                     # the model's parameters are the arena's views from here on
+    it.bind(engine)
+    engine.prefetch = True                                 # (the loop only reads the loss of a step)
+    total_time, val_accs, test_accs = 0., [], []
+    for epoch in range(args.n_epochs):                     # cluster_gcn.py:89-127
+        log(f'Running epoch {epoch} / {args.n_epochs}', flush=True)
+        torch.cuda.synchronize(device)
+        start_time = time.time()
+        for batch in it:
+            engine.train_step(batch, args.lr, args.weight_decay)
+        torch.cuda.synchronize(device)
+        total_time += time.time() - start_time
+        engine.check_extract()                             # (outside the timed interval)
+        val_accs.append(evaluate(model, g, labels, val_mask, 'f1' if args.use_f1 else 'acc'))
+        test_accs.append(evaluate(model, g, labels, test_mask, 'f1' if args.use_f1 else 'acc'))
+        log(f'Val acc {val_accs[-1]}', flush=True)
+    log(f'Training Time: {total_time:.4f}', flush=True)    # :132-136
+    log(f'Last Val: {val_accs[-1]:.4f}', flush=True)
+    log(f'Best Val: {max(val_accs):.4f}', flush=True)
+    log(f'Last Test: {test_accs[-1]:.4f}', flush=True)
+    log(f'Best Test: {max(test_accs):.4f}', flush=True)
+    return dict(total_time=total_time, val_accs=val_accs, test_accs=test_accs, model=model)
 
 
 def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log):

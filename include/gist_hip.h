@@ -957,6 +957,82 @@ int gist_gat_attn_grad_f32(const float *Z, int64_t ldz, const float *ds_src, con
                            int64_t n_rows, int64_t heads, int64_t out_dim, float *partials,
                            int64_t partial_floats, float *dA, gist_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Whole GAT training iteration in one call (an addition: no existing signature changed, ABI 16)
+ * ------------------------------------------------------------------------- */
+
+/* One MultiHeadGATLayer's buffers (all device pointers, all preallocated by the caller for n_max rows).  W and A are
+ * views of the flat parameter arena in gist_amd.ist.GATArena's layout (per layer the heads' fc weights stacked, then
+ * their attention vectors stacked), dW and dA the same views of the gradient arena.  Every matrix is dense: its leading
+ * dimension is its width, so the first n rows of a buffer are laid out like the [n, width] tensor of the op-level path. */
+typedef struct gist_gat_layer_desc {
+    int64_t n_in, n_out, heads;
+    float *W, *A;              /* [heads*n_out, n_in], [heads, 2*n_out]                        */
+    float *dW, *dA;            /* gradients, same shapes                                       */
+    float *Z;                  /* [n_max, heads*n_out] = x . W^T                               */
+    float *out;                /* [n_max, n_out] = elu(head mean): the next layer's input      */
+    float *s_src, *s_dst;      /* [n_max, heads] attention scores per node and side            */
+    float *m, *l;              /* [n_max, heads] softmax max and denominator                   */
+} gist_gat_layer_desc;
+
+typedef struct gist_gat_step_plan {
+    int32_t n_layers;              /* layers of gist_amd.modules.GAT; layer k's n_in = layer k-1's n_out        */
+    gist_gat_layer_desc layer[GIST_MAX_LAYERS];
+    float *x0;                     /* [n_max, n_in_0]: layer 0's input, filled by the extraction's feature gather */
+    /* backward scratch shared by the layers, sized for the widest one */
+    float *dZ;                     /* [n_max * max_k(heads_k * n_out_k)]                            */
+    float *g;                      /* [n_max * max_k(n_out_k)]  d_out * elu'(out) / heads           */
+    float *ds_dst, *dd, *ds_src;   /* [n_max * max_k(heads_k)] each                                 */
+    float *d_out[2];               /* [n_max * max_{k>=1}(n_in_k)] each: dx of layer k is layer k-1's d_out (ping-pong;
+                                      unused by a one-layer model)                                  */
+    float *attn_partials; int64_t attn_partial_floats;   /* gist_gat_step_attn_partials_floats(plan) */
+    float *dlogits;                /* [n_max, n_classes], n_classes = the last layer's n_out        */
+    float *row_loss, *loss;        /* [n_max], [1]                                                  */
+    void *workspace; int64_t workspace_bytes;            /* split-K scratch: gist_gat_step_workspace_bytes(plan) */
+    float *params, *grads, *exp_avg, *exp_avg_sq; int64_t n_params;   /* flat arenas */
+    /* resident training graph + the batch buffers the extraction fills (as in gist_step_plan) */
+    const int32_t *g_rowptr, *g_col, *g_t_rowptr, *g_t_col;
+    const float *feat; int64_t ld_feat;
+    const int32_t *labels_all;
+    int32_t *remap;                /* only read without the part tables (gist_extract_batch)        */
+    int32_t *rowptr, *col, *t_rowptr, *t_col; int64_t col_capacity;
+    float *norm; int32_t *labels;
+    /* one-launch extraction (gist_extract_parts_batch), as in gist_step_plan: the static node_part, the epoch's
+     * part_slot, this batch's index in the epoch (set per call), the zeroed scratch; and the NEXT batch of the epoch
+     * for GIST_STEP_EXTRACT_NEXT */
+    const int32_t *node_part, *part_slot;
+    int32_t batch_index;
+    void *extract_scratch;
+    const int32_t *next_ids;
+    int64_t next_n;
+    int32_t next_batch_index;
+    int64_t n_max;                 /* rows every per-row buffer was sized for                       */
+    struct gist_timer *timer;      /* NULL = no timing; records the GEMM (kind 1) and edge-walking (kind 0, k = heads *
+                                      n_out) calls like gist_sage_step                              */
+} gist_gat_step_plan;
+
+/* Sizes the caller cannot derive from the shapes alone (host functions; 0 for a NULL plan or bad shapes): the bytes of
+ * `workspace` -- the largest gist_gemm_workspace_bytes over every projection of every layer at every batch size up to
+ * n_max -- and the floats of `attn_partials` (the widest layer's gist_gat_attn_grad_workspace_floats at n_max rows). */
+int64_t gist_gat_step_workspace_bytes(const gist_gat_step_plan *plan);
+int64_t gist_gat_step_attn_partials_floats(const gist_gat_step_plan *plan);
+
+/* One iteration of the reference's GAT loop (cluster_gcn_ist_distrib_gat.py:393-480, cluster_gcn/cluster_gcn.py:96-105
+ * with --model-type gat) on the batch whose node ids are ids[0..n): extraction, GAT.forward (cluster_gcn/modules.py:93-98:
+ * ELU after every layer), mean CE over the batch rows, backward, Adam over the arena -- the launches of the op-level
+ * path (gist_gemm_nt_f32 -> gist_gat_scores_f32 -> gist_gat_aggregate_f32 per layer; gist_softmax_xent_f32; per layer in
+ * reverse gist_gat_backward_dst_f32 -> gist_gat_backward_src_f32 -> gist_gat_attn_grad_f32 -> gist_gemm_tn_f32 ->
+ * gist_gemm_nn_f32; one gist_adam_f32 over the arena) in the same order on the same operand layouts: parameters, loss
+ * and Adam moments are bitwise those of that path.  `plan` is HOST memory; adam_step is 1-based; no host synchronisation.
+ * flags: GIST_STEP_EXTRACT, GIST_STEP_TRAIN (without it: forward + loss only), GIST_STEP_EXTRACT_NEXT (the optimiser
+ * launch is gist_adam_segments_extract_f32 with no segments and also extracts plan->next_*; GIST_EINVAL if the plan
+ * lacks the part tables, the scratch or next_*) and GIST_STEP_PREEXTRACTED, with their gist_sage_step meaning.  The
+ * GIST_STEP_PHASE_* bits and GIST_STEP_DLOGITS_GIVEN are not supported: GIST_EINVAL.  Every argument is checked (null
+ * pointers, sizes, n > n_max, more than GIST_MAX_LAYERS layers: GIST_EINVAL; a workspace too small for this n:
+ * GIST_ENOSPACE) before any device work. */
+int gist_gat_step(const gist_gat_step_plan *plan, const int32_t *ids, int64_t n, float lr, float beta1, float beta2,
+                  float eps, float weight_decay, int64_t adam_step, int flags, gist_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""A GAT training step on the two host paths, ms per step, on real Reddit-like cluster batches
+(datasets.reddit_synth, psize 1500, batch size 20):
+
+  engine   one gist_gat_step call per iteration (gist_amd.gat_engine.GATEngine, fed by EngineClusterIter, the next
+           batch extracted in the optimiser's grid) -- `cluster_gcn --model-type gat --host-path engine`
+  module   the reference's loop body on gist_amd.modules.GAT / nn.CrossEntropyLoss / optim.Adam / ClusterIter --
+           `--host-path module`, unchanged by the fused step
+
+    python scripts/gat_step.py --out profiles/gat_step.json
+
+Both paths compute the same bits (tests/test_gat_step_gpu.py); this tool only times them.  Per shape (layers, heads,
+width per head; in = 602, 41 classes) it runs, after --warmup steps of each path, --reps pairs of windows of --iters
+steps, engine and module ALTERNATING in one process, each window between two HIP events and ended by a synchronise.
+It reports the median ms per step of each path, the run-to-run spread of each ((max - min) / median over the windows),
+the ratio, and the launches the library itself issued per step (gist_launch_count; torch's own kernels of the module
+path -- cat, mul, zero_ -- are not in it).
+
+    rocprofv3 --kernel-trace --stats -d DIR -- python scripts/gat_step.py --trace engine --shape 2,4,64 --steps 40
+
+runs --steps untimed steps of one path for a kernel trace: the difference of the traced kernel calls of two step
+counts, over the difference of the counts, is the path's launches per step, set-up excluded.
+"""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+SHAPES = ([(2, h, w) for h in (1, 4) for w in (16, 32, 64, 256)] + [(3, 4, 32), (3, 4, 64), (3, 4, 256)])
+LR, WD = 0.01, 5e-4
+
+
+def cycle(it):
+    while True:
+        for b in it:
+            yield b
+
+
+class Paths(object):
+    """The two iterators over one dataset (built once) and, per shape, the two step functions."""
+
+    def __init__(self, ds, psize, bsize, dev):
+        from gist_amd.sampler import ClusterIter, EngineClusterIter
+        self.ds, self.dev = ds, dev
+        g = ds.g
+        nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
+        random.seed(0)
+        self.mod_it = ClusterIter(ds.name, g, psize, bsize, nid, par_li=ds.par_li, device=dev)
+        random.seed(0)
+        self.eng_it = EngineClusterIter(ds.name, g, psize, bsize, nid, par_li=ds.par_li, device=dev)
+        self.fin, self.ncls = g.ndata['feat'].shape[1], ds.num_classes
+
+    def shape(self, layers, heads, width):
+        from gist_amd.gat_engine import GATEngine
+        from gist_amd.ist import gat_dims, gat_params
+        from gist_amd.modules import GAT
+        from gist_amd.nn import CrossEntropyLoss
+        from gist_amd.optim import Adam
+        torch.manual_seed(0)
+        model = GAT(layers, self.fin, width, self.ncls, heads).to(self.dev)
+        loss_f = CrossEntropyLoss()
+        opt = Adam(model.parameters(), lr=LR, weight_decay=WD)
+        mod_batches = cycle(self.mod_it)
+
+        def mod_step():
+            cluster = next(mod_batches).to(self.dev)
+            model.train()
+            pred = model(cluster)
+            tm, lab = cluster.ndata['train_mask'], cluster.ndata['label']
+            loss = loss_f(pred[tm], lab[tm])
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+
+        eng = GATEngine(gat_dims(self.fin, width, self.ncls, layers, heads), self.eng_it.n_max, self.dev)
+        eng.arena.load(gat_params(model))
+        self.eng_it.bind(eng)
+        eng.prefetch = True
+        eng_batches = cycle(self.eng_it)
+
+        def eng_step():
+            eng.train_step(next(eng_batches), LR, WD)
+
+        return eng, eng_step, mod_step
+
+
+def window(fn, iters):
+    from gist_amd import _lib
+    L = _lib.load()
+    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    c0 = L.gist_launch_count()
+    a.record()
+    for _ in range(iters):
+        fn()
+    z.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(z) / iters, (L.gist_launch_count() - c0) / float(iters)
+
+
+def spread(v):
+    return (max(v) - min(v)) / float(np.median(v))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default='gat_step.json')
+    ap.add_argument('--iters', type=int, default=150, help='steps per window (two epochs of 75 batches)')
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--quick', action='store_true', help='the toy graph, one shape (rehearsal)')
+    ap.add_argument('--trace', choices=['engine', 'module'], help='untimed steps of one path, for a kernel trace')
+    ap.add_argument('--shape', default='2,4,64', help='--trace: layers,heads,width')
+    ap.add_argument('--steps', type=int, default=40, help='--trace: steps to run')
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), 'gat_step.py measures on the GPU'
+    from gist_amd import datasets, hip
+    dev = torch.device('cuda', 0)
+    torch.cuda.set_device(dev)
+    t0 = time.time()
+    ds = datasets.toy(train_frac=1.0) if args.quick else datasets.reddit_synth()
+    psize, bsize = (len(ds.par_li), 4) if args.quick else (1500, 20)
+    paths = Paths(ds, psize, bsize, dev)
+    setup_s = time.time() - t0
+    if args.trace:
+        layers, heads, width = (int(v) for v in args.shape.split(','))
+        eng, eng_step, mod_step = paths.shape(layers, heads, width)
+        fn = eng_step if args.trace == 'engine' else mod_step
+        for _ in range(args.steps):
+            fn()
+        torch.cuda.synchronize()
+        eng.check_extract()
+        print('gat_step: traced %d %s steps of shape %s' % (args.steps, args.trace, args.shape))
+        return
+    shapes = [(2, 4, 32)] if args.quick else SHAPES
+    res = []
+    for layers, heads, width in shapes:
+        eng, eng_step, mod_step = paths.shape(layers, heads, width)
+        for _ in range(args.warmup):
+            eng_step()
+            mod_step()
+        torch.cuda.synchronize()
+        e_ms, m_ms, e_l, m_l = [], [], [], []
+        for _ in range(args.reps):                     # alternating: a drift of the box hits both paths alike
+            ms, nl = window(eng_step, args.iters)
+            e_ms.append(ms)
+            e_l.append(nl)
+            ms, nl = window(mod_step, args.iters)
+            m_ms.append(ms)
+            m_l.append(nl)
+        eng.check_extract()
+        e, m = float(np.median(e_ms)), float(np.median(m_ms))
+        noise = max(spread(e_ms), spread(m_ms))
+        r = dict(layers=layers, heads=heads, width=width, n_in=paths.fin, engine_ms=round(e, 4), module_ms=round(m, 4),
+                 module_over_engine=round(m / e, 3), engine_spread=round(spread(e_ms), 4),
+                 module_spread=round(spread(m_ms), 4), engine_not_slower=bool(e <= m * (1.0 + noise)),
+                 engine_lib_launches_per_step=round(float(np.median(e_l)), 2),
+                 module_lib_launches_per_step=round(float(np.median(m_l)), 2),
+                 engine_windows=[round(v, 4) for v in e_ms], module_windows=[round(v, 4) for v in m_ms])
+        res.append(r)
+        print(json.dumps({k: v for k, v in r.items() if not k.endswith('_windows')}), flush=True)
+        del eng, eng_step, mod_step
+    doc = dict(tool='scripts/gat_step.py', device=torch.cuda.get_device_name(0), gemm_mode=hip.gemm_mode(),
+               dataset=ds.name, psize=psize, batch_size=bsize, n_max=paths.eng_it.n_max, iters=args.iters,
+               reps=args.reps, warmup=args.warmup, lr=LR, weight_decay=WD, setup_s=round(setup_s, 1), shapes=res)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as fh:
+        json.dump(doc, fh, indent=1)
+    print('gat_step: %d shapes, engine not slower than module beyond the spread on %d of them'
+          % (len(res), sum(r['engine_not_slower'] for r in res)))
+
+
+if __name__ == '__main__':
+    main()
