@@ -1,0 +1,142 @@
+"""Flat parameter arenas: one fp32 tensor per model, every layer's two parameter tensors views of it.
+
+Adam is ONE launch over the arena, the GIST sync all-gathers it as it stands (no packing copies) and the block movers of
+gist_amd.ist work on the views.  FlatArena owns the layout and the storage; a family states the two shapes of a layer
+and the names of its views: ParamArena (GraphSAGE: W [o, 2i], b [o]) and GATArena (GAT: the heads' fc weights stacked
+W [nh*o, i], their attention vectors stacked A [nh, 2o]).
+"""
+import math
+import weakref
+
+import torch
+
+
+class FlatArena(object):
+    """Per layer tensor 1 then tensor 2, layer after layer.  `offsets[k]` = (start of tensor 1, start of tensor 2) of
+    layer k; `views` = (the tensor-1 views, the tensor-2 views) of `params`, also reachable under the family's `names`
+    (and, after with_grads(), 'd' + name over `grads`).  `params` / `numel` are what the GIST collectives move."""
+    names = None                # (tensor 1, tensor 2)
+
+    def shapes(self, dim):
+        """(shape of tensor 1, shape of tensor 2) of a layer with the entry `dim` of dims."""
+        raise NotImplementedError
+
+    def __init__(self, dims, device):
+        self.dims = list(dims)
+        self.device = device
+        self._shapes = [self.shapes(d) for d in self.dims]
+        self.offsets = []
+        off = 0
+        for s1, s2 in self._shapes:
+            self.offsets.append((off, off + math.prod(s1)))
+            off += math.prod(s1) + math.prod(s2)
+        self.numel = off
+        self.params = torch.zeros(off, dtype=torch.float32, device=device)
+        self.views = self._name_views(self.params, '')
+        # gradient and Adam-moment arenas in the same layout: only a training step needs them (with_grads)
+        self.grads = self.exp_avg = self.exp_avg_sq = None
+        for name in self.names:
+            setattr(self, 'd' + name, [])
+        self.step = 0
+
+    def layer_views(self, flat, k):
+        """Layer k's (tensor 1, tensor 2) as views of `flat`, a flat tensor in this arena's layout."""
+        (s1, s2), (o1, o2) = self._shapes[k], self.offsets[k]
+        return flat[o1:o2].view(s1), flat[o2:o2 + math.prod(s2)].view(s2)
+
+    def _name_views(self, flat, prefix):
+        pairs = [self.layer_views(flat, k) for k in range(len(self.dims))]
+        views = ([p[0] for p in pairs], [p[1] for p in pairs])
+        for name, v in zip(self.names, views):
+            setattr(self, prefix + name, v)
+        return views
+
+    def with_grads(self):
+        """Allocate (once) the flat gradient and Adam-moment arenas beside `params`, the 'd' + name views over the
+        gradient arena: what the fused steps read and write.  The parameters are not touched."""
+        if self.grads is None:
+            self.grads = torch.zeros_like(self.params)
+            self.exp_avg = torch.zeros_like(self.params)
+            self.exp_avg_sq = torch.zeros_like(self.params)
+            self._name_views(self.grads, 'd')
+        return self
+
+    def reset_optimizer(self):
+        """Fresh Adam state (the GIST loop builds a new optimizer at every dispatch point)."""
+        if self.grads is not None:
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+        self.step = 0
+
+    def load(self, params):
+        """params = [(tensor 1, tensor 2)] numpy arrays or tensors."""
+        for k, pair in enumerate(params):
+            for view, t in zip((self.views[0][k], self.views[1][k]), pair):
+                view.copy_(torch.as_tensor(t).reshape(view.shape).to(self.device))
+
+    def export(self):
+        return [tuple(t.detach().cpu().numpy().copy() for t in pair) for pair in zip(*self.views)]
+
+
+class ParamArena(FlatArena):
+    """GraphSAGE layers, dims = [(in, out)]: W [out, 2*in] and b [out]."""
+    names = ('W', 'b')
+
+    def shapes(self, dim):
+        i, o = dim
+        return (o, 2 * i), (o,)
+
+    def __init__(self, dims, device, with_grads=True):
+        FlatArena.__init__(self, dims, device)
+        if with_grads:          # a base-model replica (IST) holds parameters only
+            self.with_grads()
+
+    def adopt_module(self, gcn):
+        """Re-home an nn.Module GCN's parameters into the arena (values preserved)."""
+        for k, layer in enumerate(gcn.layers):
+            self.W[k].copy_(layer.linear.weight.data.to(self.device))
+            self.b[k].copy_(layer.linear.bias.data.to(self.device))
+            layer.linear.weight.data = self.W[k]
+            layer.linear.bias.data = self.b[k]
+
+    def bind_module(self, gcn):
+        """Record on `gcn`, weakly, that its parameters are this arena's views in this arena's layout (made so by its
+        owner, gist_amd.ist.DistributedGNNWrapper): a ModuleEngine for it then steps this arena in place instead of
+        re-homing the module into an arena of its own (module_engine.shared_arena)."""
+        gcn.__dict__['_gist_arena'] = weakref.ref(self)
+
+
+def gat_dims(in_feats, n_hidden, n_classes, n_layers, n_heads):
+    """[(in, out, heads)] of the layers of gist_amd.modules.GAT(n_layers, in_feats, n_hidden, n_classes, n_heads): n_heads
+    heads in the first layer and in the n_layers - 2 middle ones, one head of width n_classes last."""
+    return ([(in_feats, n_hidden, n_heads)] + [(n_hidden, n_hidden, n_heads)] * max(n_layers - 2, 0) +
+            [(n_hidden, n_classes, 1)])
+
+
+def gat_params(gat):
+    """[(W [nh*O, I], A [nh, 2O])] of a gist_amd.modules.GAT: its heads stacked as GATArena lays them out."""
+    from .modules import _stack_heads
+    with torch.no_grad():
+        return [tuple(t.detach().clone() for t in _stack_heads(layer.heads)) for layer in gat.layers]
+
+
+class GATArena(FlatArena):
+    """gist_amd.modules.GAT layers, dims = [(in, out, heads)]: the heads' fc weights stacked W [nh*O, I], then their
+    attn vectors stacked A [nh, 2O] -- the layout of modules._stack_heads and of the gist_gat_* C ABI.  Gradients only
+    after with_grads() (gist_amd.gat_engine.GATEngine)."""
+    names = ('W', 'A')
+
+    def shapes(self, dim):
+        i, o, nh = dim
+        return (nh * o, i), (nh, 2 * o)
+
+    def bind(self, gat, requires_grad=True):
+        """Make every head's fc.weight / attn_fc.weight of `gat` a Parameter over its rows of the arena (no copy)."""
+        import torch.nn as nn
+        for k, layer in enumerate(gat.layers):
+            o = self.dims[k][1]
+            assert len(layer.heads) == self.dims[k][2]
+            for h, head in enumerate(layer.heads):
+                head.fc.weight = nn.Parameter(self.W[k][h * o:(h + 1) * o], requires_grad=requires_grad)
+                head.attn_fc.weight = nn.Parameter(self.A[k][h:h + 1], requires_grad=requires_grad)
+        return gat

@@ -17,74 +17,16 @@ The step follows SURVEY.md appendix A / cluster_gcn_ist_distrib.py:408-417 exact
 forward, mean CE over the batch rows, backward, Adam (coupled L2).
 """
 import os
-import weakref
 
 import numpy as np
 import torch
 
 from . import hip
+from .arena import ParamArena
 
 
 def _round_up(x, m):
     return (x + m - 1) // m * m
-
-
-class ParamArena(object):
-    """Flat parameter / gradient / Adam-moment storage with per-layer views."""
-
-    def __init__(self, dims, device, with_grads=True):
-        self.dims = list(dims)
-        self.offsets = []
-        off = 0
-        for (i, o) in self.dims:
-            self.offsets.append((off, off + o * 2 * i))
-            off += o * 2 * i + o
-        self.numel = off
-        self.device = device
-        self.params = torch.zeros(off, dtype=torch.float32, device=device)
-        self.W, self.b, self.dW, self.db = [], [], [], []
-        for (i, o), (w0, b0) in zip(self.dims, self.offsets):
-            self.W.append(self.params[w0:b0].view(o, 2 * i))
-            self.b.append(self.params[b0:b0 + o])
-        self.grads = self.exp_avg = self.exp_avg_sq = None
-        if with_grads:          # a base-model replica (IST) holds parameters only
-            self.grads = torch.zeros(off, dtype=torch.float32, device=device)
-            self.exp_avg = torch.zeros(off, dtype=torch.float32, device=device)
-            self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=device)
-            for (i, o), (w0, b0) in zip(self.dims, self.offsets):
-                self.dW.append(self.grads[w0:b0].view(o, 2 * i))
-                self.db.append(self.grads[b0:b0 + o])
-        self.step = 0
-
-    def reset_optimizer(self):
-        """Fresh Adam state (cluster_gcn_ist_distrib.py:405-407 builds a new optimizer)."""
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
-        self.step = 0
-
-    def load(self, params):
-        """params = [(W, b)] numpy arrays or tensors."""
-        for k, (W, b) in enumerate(params):
-            self.W[k].copy_(torch.as_tensor(W).to(self.device))
-            self.b[k].copy_(torch.as_tensor(b).to(self.device))
-
-    def export(self):
-        return [(W.detach().cpu().numpy().copy(), b.detach().cpu().numpy().copy())
-                for W, b in zip(self.W, self.b)]
-
-    def adopt_module(self, gcn):
-        """Re-home an nn.Module GCN's parameters into the arena (values preserved)."""
-        for k, layer in enumerate(gcn.layers):
-            self.W[k].copy_(layer.linear.weight.data.to(self.device))
-            self.b[k].copy_(layer.linear.bias.data.to(self.device))
-            layer.linear.weight.data = self.W[k]
-            layer.linear.bias.data = self.b[k]
-
-    def bind_module(self, gcn):
-        """Record on `gcn`, weakly, that its parameters are this arena's views in this arena's layout (made so by its
-        owner, gist_amd.ist.DistributedGNNWrapper): a ModuleEngine for it then steps this arena in place instead of
-        re-homing the module into an arena of its own (module_engine.shared_arena)."""
-        gcn.__dict__['_gist_arena'] = weakref.ref(self)
 
 
 class Batch(object):
@@ -175,7 +117,91 @@ class ClusterBatcher(object):
         return b
 
 
-class SageEngine(object):
+class StepEngine(object):
+    """What SageEngine and GATEngine share around their one-call steps: the scratch and the error word of the
+    one-launch extraction and the HIP-event step timer.  Works on the attributes `device`, `n_max`, `plan` (the native
+    step plan, or None before attach_batcher), `_extract_scratch` and `_timer` (both None at first), which the
+    engine's constructor sets."""
+
+    def _extraction_scratch(self):
+        """The barrier ticket + counts of the one-launch extraction (allocated at its first use)."""
+        if self._extract_scratch is None:
+            nb = int(hip._lib.load().gist_extract_parts_scratch_bytes(self.n_max))
+            self._extract_scratch = torch.zeros(nb // 8 + 1, dtype=torch.int64, device=self.device)
+        return self._extract_scratch
+
+    def check_extract(self):
+        """Raises if a workgroup of the one-launch extraction ever gave up at its grid barrier (the
+        error word of gist_extract_parts_batch's scratch); one small D2H read, call it off the hot path."""
+        if self._extract_scratch is not None and int(self._extract_scratch[1].item()) != 0:
+            raise RuntimeError('gist_amd: gist_extract_parts_batch timed out at its grid barrier; '
+                               'the batches extracted since the last check are invalid')
+
+    def check_extract_deferred(self):
+        """The same check without draining the queue: a one-thread kernel writes the error word and a running tag into
+        pinned host memory (gist_publish_i64: no copy command, no event object, no busy-waiting runtime call); this call
+        first makes sure the mark of the PREVIOUS call has arrived -- it normally has, long ago; a host more than one call
+        ahead of the GPU sleeps here in 50-us naps, which is what bounds its run-ahead -- and raises for that mark's
+        error word."""
+        if self._extract_scratch is None:
+            return
+        import time
+        if getattr(self, '_mark', None) is None:
+            self._mark = torch.zeros(2, dtype=torch.int64, pin_memory=True)
+            self._mark_np = self._mark.numpy()
+            self._mark_tag = 0
+        prev = self._mark_tag
+        if prev > 0:
+            deadline = None
+            while int(self._mark_np[1]) < prev:
+                if deadline is None:
+                    deadline = time.time() + 600.0
+                elif time.time() > deadline:
+                    raise RuntimeError('gist_amd: the GPU never reached the progress mark of the previous epoch')
+                time.sleep(5e-5)
+            if int(self._mark_np[0]) != 0:
+                raise RuntimeError('gist_amd: gist_extract_parts_batch timed out at its grid barrier; '
+                                   'the batches extracted since the last check are invalid')
+        self._mark_tag = prev + 1
+        hip.publish_i64_raw(self._extract_scratch[1:2].data_ptr(), self._mark_tag, self._mark.data_ptr())
+
+    def enable_timer(self, capacity):
+        """HIP-event timing of every SpMM/GEMM issued by the native step (gist_timer_*)."""
+        from . import _lib
+        L = _lib.load()
+        if self.plan is None:
+            raise RuntimeError('gist_amd: enable_timer needs attach_batcher first')
+        self.disable_timer()
+        self._timer = L.gist_timer_create(int(capacity))
+        self.plan.timer = self._timer
+        return self._timer
+
+    def disable_timer(self):
+        from . import _lib
+        if getattr(self, '_timer', None):
+            _lib.load().gist_timer_destroy(self._timer)
+        self._timer = None
+        if self.plan is not None:
+            self.plan.timer = None
+
+    def read_timer(self):
+        """[(ms, kind, m, n, k)] -- synchronises the device first."""
+        import ctypes
+        from . import _lib
+        L = _lib.load()
+        torch.cuda.synchronize(self.device)
+        out = []
+        ms, kind = ctypes.c_float(), ctypes.c_int32()
+        m, n, k = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        for i in range(L.gist_timer_count(self._timer)):
+            _lib.check(L.gist_timer_read(self._timer, i, ctypes.byref(ms), ctypes.byref(kind),
+                                         ctypes.byref(m), ctypes.byref(n), ctypes.byref(k)),
+                       'gist_timer_read')
+            out.append((ms.value, kind.value, m.value, n.value, k.value))
+        return out
+
+
+class SageEngine(StepEngine):
     def __init__(self, dims, use_layernorm, dropout, n_max, device, seed=0, arena=None):
         """dims = [(in_k, out_k)] for the L+1 SAGE layers (modules.py:245-308)."""
         self.dims = [(int(i), int(o)) for i, o in dims]
@@ -222,7 +248,7 @@ class SageEngine(object):
                 ld = i if i % 4 == 0 else _round_up(i + 2, 4)
                 self.H[k] = torch.zeros(self.n_max, ld, **f32)
         self._fused = None          # op-by-op path's own slabs / chunk sums (lazy)
-        self._extract_scratch = None    # barrier ticket + counts of the one-launch extraction
+        self._extract_scratch = self._timer = None      # (StepEngine)
         # True: a training step's optimiser launch also extracts the NEXT batch of the epoch into the batch buffers
         # (gist_adam_segments_extract_f32).  For loops that only use the loss: labels, CSR and Z[0] of the batch just
         # stepped are gone when train_step returns.  The trainers and bench.py set it; off by default
@@ -317,76 +343,6 @@ class SageEngine(object):
                            self._col_partials)     # keep every buffer alive
         return P
 
-    def check_extract(self):
-        """Raises if a workgroup of the one-launch extraction ever gave up at its grid barrier (the
-        error word of gist_extract_parts_batch's scratch); one small D2H read, call it off the hot path."""
-        if self._extract_scratch is not None and int(self._extract_scratch[1].item()) != 0:
-            raise RuntimeError('gist_amd: gist_extract_parts_batch timed out at its grid barrier; '
-                               'the batches extracted since the last check are invalid')
-
-    def check_extract_deferred(self):
-        """The same check without draining the queue: a one-thread kernel writes the error word and a running tag into
-        pinned host memory (gist_publish_i64: no copy command, no event object, no busy-waiting runtime call); this call
-        first makes sure the mark of the PREVIOUS call has arrived -- it normally has, long ago; a host more than one call
-        ahead of the GPU sleeps here in 50-us naps, which is what bounds its run-ahead -- and raises for that mark's
-        error word."""
-        if self._extract_scratch is None:
-            return
-        import time
-        if getattr(self, '_mark', None) is None:
-            self._mark = torch.zeros(2, dtype=torch.int64, pin_memory=True)
-            self._mark_np = self._mark.numpy()
-            self._mark_tag = 0
-        prev = self._mark_tag
-        if prev > 0:
-            deadline = None
-            while int(self._mark_np[1]) < prev:
-                if deadline is None:
-                    deadline = time.time() + 600.0
-                elif time.time() > deadline:
-                    raise RuntimeError('gist_amd: the GPU never reached the progress mark of the previous epoch')
-                time.sleep(5e-5)
-            if int(self._mark_np[0]) != 0:
-                raise RuntimeError('gist_amd: gist_extract_parts_batch timed out at its grid barrier; '
-                                   'the batches extracted since the last check are invalid')
-        self._mark_tag = prev + 1
-        hip.publish_i64_raw(self._extract_scratch[1:2].data_ptr(), self._mark_tag, self._mark.data_ptr())
-
-    def enable_timer(self, capacity):
-        """HIP-event timing of every SpMM/GEMM issued by the native step (gist_timer_*)."""
-        from . import _lib
-        L = _lib.load()
-        if self.plan is None:
-            raise RuntimeError('gist_amd: enable_timer needs attach_batcher first')
-        self.disable_timer()
-        self._timer = L.gist_timer_create(int(capacity))
-        self.plan.timer = self._timer
-        return self._timer
-
-    def disable_timer(self):
-        from . import _lib
-        if getattr(self, '_timer', None):
-            _lib.load().gist_timer_destroy(self._timer)
-        self._timer = None
-        if self.plan is not None:
-            self.plan.timer = None
-
-    def read_timer(self):
-        """[(ms, kind, m, n, k)] -- synchronises the device first."""
-        import ctypes
-        from . import _lib
-        L = _lib.load()
-        torch.cuda.synchronize(self.device)
-        out = []
-        ms, kind = ctypes.c_float(), ctypes.c_int32()
-        m, n, k = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        for i in range(L.gist_timer_count(self._timer)):
-            _lib.check(L.gist_timer_read(self._timer, i, ctypes.byref(ms), ctypes.byref(kind),
-                                         ctypes.byref(m), ctypes.byref(n), ctypes.byref(k)),
-                       'gist_timer_read')
-            out.append((ms.value, kind.value, m.value, n.value, k.value))
-        return out
-
     def _native_step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, phase=0, given=False,
                      adam_step=None):
         """One gist_sage_step call.  phase = 0: the whole iteration; GIST_STEP_PHASE_FORWARD / _BACKWARD / _OPTIMIZER: one
@@ -451,11 +407,8 @@ class SageEngine(object):
         # one-launch extraction when the batch comes with its part tables (gist_extract_parts_batch)
         if b.parts is not None and not b.ready and self.fuse and L.gist_extract_parts_supported(self.n_max):
             node_part, tab, j = b.parts
-            if self._extract_scratch is None:
-                self._extract_scratch = torch.zeros(int(L.gist_extract_parts_scratch_bytes(self.n_max)) // 8 + 1,
-                                                    dtype=torch.int64, device=self.device)
             P.node_part, P.part_slot = node_part.data_ptr(), tab.data_ptr()
-            P.batch_index, P.extract_scratch = int(j), self._extract_scratch.data_ptr()
+            P.batch_index, P.extract_scratch = int(j), self._extraction_scratch().data_ptr()
         else:
             P.node_part = P.part_slot = P.extract_scratch = None
             P.batch_index = -1
@@ -577,14 +530,10 @@ class SageEngine(object):
                 # the native step's extraction: one launch that also forms layer 0's aggregation
                 # (gist_extract_parts_desc.feat_intra), which sums in its own order -- so the twin runs the same launch
                 bt = b.batcher
-                if self._extract_scratch is None:
-                    self._extract_scratch = torch.zeros(
-                        int(hip._lib.load().gist_extract_parts_scratch_bytes(self.n_max)) // 8 + 1,
-                        dtype=torch.int64, device=self.device)
                 bt.prefetched = None
                 hip.extract_parts(bt.g, b.ids, self.n_max, b.parts[0], b.parts[1], b.parts[2], bt.rowptr[:n + 1], bt.col,
                                   bt.t_rowptr[:n + 1], bt.t_col, bt.norm, bt.feat, self.z0_left(n), bt.labels, bt.lab,
-                                  self._extract_scratch, drop=dr, feat_intra=fi, ah=self.Z[0][:n, i0:])
+                                  self._extraction_scratch(), drop=dr, feat_intra=fi, ah=self.Z[0][:n, i0:])
                 self._pre_ah = True
             else:
                 b.batcher.extract(b.ids, self.z0_left(n), drop=dr)

@@ -3,7 +3,7 @@
 One engine = one (sub-)GAT on one GPU.  Everything lives in HBM for the whole run and is sized once for the largest
 batch (n_max rows):
 
-  * parameters are a gist_amd.ist.GATArena (per layer the heads' fc weights stacked [nh*O, I], then their attention
+  * parameters are a gist_amd.arena.GATArena (per layer the heads' fc weights stacked [nh*O, I], then their attention
     vectors stacked [nh, 2O]) -- the engine's own, or one it is GIVEN: GATEngine(arena=wrapper.sub) steps a
     DistributedGATWrapper's sub arena in place, no copy, no re-home.  Gradients and Adam moments are flat arenas in the
     same layout (GATArena.with_grads), so Adam is ONE launch and no head is stacked or split per step;
@@ -21,13 +21,13 @@ import ctypes
 import torch
 
 from . import _lib, hip
-from .engine import SageEngine
+from .arena import GATArena
+from .engine import StepEngine
 
 
-class GATEngine(object):
+class GATEngine(StepEngine):
     def __init__(self, dims=None, n_max=None, device=None, arena=None):
-        """dims = [(in_k, out_k, heads_k)] (gist_amd.ist.gat_dims), or `arena` = a GATArena to adopt (its dims)."""
-        from .ist import GATArena
+        """dims = [(in_k, out_k, heads_k)] (gist_amd.arena.gat_dims), or `arena` = a GATArena to adopt (its dims)."""
         if arena is None:
             if dims is None or device is None:
                 raise ValueError('gist_amd: GATEngine needs dims and a device, or an arena')
@@ -125,13 +125,6 @@ class GATEngine(object):
         self._plan_keep = (batcher, g, self._ws, self._attn_partials)      # keep every buffer alive
         return P
 
-    # the extraction's error word and the step timer work on (plan, _extract_scratch, _timer, device): SageEngine's own
-    check_extract = SageEngine.check_extract
-    check_extract_deferred = SageEngine.check_extract_deferred
-    enable_timer = SageEngine.enable_timer
-    disable_timer = SageEngine.disable_timer
-    read_timer = SageEngine.read_timer
-
     def z0_left(self, n):
         """Layer 0's input rows (ld = n_in; a GAT layer has no [h | ah] right half)."""
         return self.X0[:n]
@@ -180,11 +173,8 @@ class GATEngine(object):
         # one-launch extraction when the batch comes with its part tables (gist_extract_parts_batch)
         if b.parts is not None and not b.ready and L.gist_extract_parts_supported(self.n_max):
             node_part, tab, j = b.parts
-            if self._extract_scratch is None:
-                self._extract_scratch = torch.zeros(int(L.gist_extract_parts_scratch_bytes(self.n_max)) // 8 + 1,
-                                                    dtype=torch.int64, device=self.device)
             P.node_part, P.part_slot = node_part.data_ptr(), tab.data_ptr()
-            P.batch_index, P.extract_scratch = int(j), self._extract_scratch.data_ptr()
+            P.batch_index, P.extract_scratch = int(j), self._extraction_scratch().data_ptr()
         else:
             P.node_part = P.part_slot = P.extract_scratch = None
             P.batch_index = -1

@@ -3,7 +3,7 @@ constructor (cluster_gcn_ist_distrib.py:71-91), `sub_model` and `base_model` -- 
 (world size 2 and 4), against the golden vectors recorded from the reference's own wrapper (tests/golden/G4_ist_*.npz).
 
 As in test_ist_gloo.py, the HIP block kernels cannot run here, so the wrapper is given a TEST DOUBLE for the three block
-movers (torch indexing, defined in this file only).  Everything else is the product code: the torch-RNG draws of the
+movers (torch indexing, tests/gat_ist_restatement.py).  Everything else is the product code: the torch-RNG draws of the
 constructor, the modules over the arenas, the partition sampling, the packed all-gather over torch.distributed.
 """
 import argparse
@@ -16,31 +16,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.gat_ist_restatement import TorchBlocks
+
 GOLD = os.path.join(os.path.dirname(__file__), 'golden')
-
-
-class TorchBlocks(object):
-    """Test double for gist_amd.ist.HipBlocks (same contract as gist_block_gather/scatter_f32 and
-    gist_mean_rows_f32)."""
-
-    def gather(self, src, row_idx, col_idx, dst):
-        s = src
-        if row_idx is not None:
-            s = s[row_idx.long()]
-        if col_idx is not None:
-            s = s[:, col_idx.long()]
-        dst.copy_(s)
-
-    def scatter(self, src, row_idx, col_idx, dst):
-        r = row_idx.long() if row_idx is not None else torch.arange(src.shape[0])
-        c = col_idx.long() if col_idx is not None else torch.arange(src.shape[1])
-        dst[r[:, None], c[None, :]] = src
-
-    def mean_rows(self, src_flat, stride, n_src, n, out):
-        acc = torch.zeros(n)
-        for s in range(n_src):
-            acc = acc + src_flat[s * stride:s * stride + n]
-        out.copy_(acc / n_src)
 
 
 def _args(S, H, L, rank):
