@@ -5,28 +5,11 @@
 // gist_adam_*), in the order and with the leading dimensions, workspaces and edge order of the module path
 // (gist_amd/ops.py gat_layer_fwd / gat_layer_bwd), so the two are bit-identical.  What it removes is everything between
 // the launches: allocations, the head stacking and its gradient split, autograd nodes, per-tensor optimiser launches.
-#include "common.h"
+#include "step_host.h"
 
 using namespace gist;
 
-#define GIST_TRY(expr)            \
-    do {                          \
-        int rc_ = (expr);         \
-        if (rc_ != GIST_OK) return rc_; \
-    } while (0)
-
 namespace {
-struct Scope {   // records start now, stop at scope exit
-    gist_timer *t; int64_t slot; hipStream_t s;
-    Scope(gist_timer *t_, int kind, int64_t m, int64_t n, int64_t k, hipStream_t s_)
-        : t(t_), slot(timer_begin(t_, kind, m, n, k, s_)), s(s_) {}
-    ~Scope() { timer_end(t, slot, s); }
-};
-struct ActiveTimer {   // kernels below the entry points see the armed timer for this call only
-    explicit ActiveTimer(gist_timer *t) { tl_timer = t; }
-    ~ActiveTimer() { tl_timer = nullptr; }
-};
-
 // layer count and shapes only: what the size helpers and the step both need before they look at a pointer
 bool shapes_ok(const gist_gat_step_plan *p) {
     if (p == nullptr || p->n_layers < 1 || p->n_layers > GIST_MAX_LAYERS || p->n_max <= 0 || p->n_max >= (1LL << 31))
@@ -76,19 +59,6 @@ extern "C" int64_t gist_gat_step_attn_partials_floats(const gist_gat_step_plan *
         need = b > need ? b : need;
     }
     return need;
-}
-
-static void parts_desc(const gist_gat_step_plan *p, const int32_t *ids, int64_t n, int32_t batch,
-                       gist_extract_parts_desc *x) {
-    const gist_gat_layer_desc &l0 = p->layer[0];
-    x->g_rowptr = p->g_rowptr; x->g_col = p->g_col; x->g_t_rowptr = p->g_t_rowptr; x->g_t_col = p->g_t_col;
-    x->ids = ids; x->n = n; x->n_max = p->n_max;
-    x->node_part = p->node_part; x->part_slot = p->part_slot; x->batch = batch;
-    x->rowptr = p->rowptr; x->col = p->col; x->t_rowptr = p->t_rowptr; x->t_col = p->t_col;
-    x->col_capacity = p->col_capacity; x->norm = p->norm;
-    x->feat = p->feat; x->ld_feat = p->ld_feat; x->n_feat = l0.n_in; x->z0 = p->x0; x->ldz0 = l0.n_in;
-    x->labels_all = p->labels_all; x->labels = p->labels;
-    x->scratch = p->extract_scratch;
 }
 
 extern "C" int gist_gat_step(const gist_gat_step_plan *p, const int32_t *ids, int64_t n, float lr, float beta1,
@@ -176,8 +146,7 @@ extern "C" int gist_gat_step(const gist_gat_step_plan *p, const int32_t *ids, in
     if (flags & GIST_STEP_EXTRACT) {
         const gist_gat_layer_desc &l0 = p->layer[0];
         if (by_parts) {
-            gist_extract_parts_desc x{};
-            parts_desc(p, ids, n, p->batch_index, &x);
+            const gist_extract_parts_desc x = parts_desc(p, ids, n, p->batch_index, l0.n_in, p->x0, l0.n_in);
             GIST_TRY(gist_extract_parts_desc_batch(&x, s));
         } else {
             GIST_TRY(gist_extract_batch(p->g_rowptr, p->g_col, p->g_t_rowptr, p->g_t_col, ids, n, p->remap, p->rowptr,
@@ -242,8 +211,8 @@ extern "C" int gist_gat_step(const gist_gat_step_plan *p, const int32_t *ids, in
 
     // ---- one optimiser launch over the arena; with EXTRACT_NEXT the next batch is extracted in its grid -----
     if (flags & GIST_STEP_EXTRACT_NEXT) {
-        gist_extract_parts_desc x{};
-        parts_desc(p, p->next_ids, p->next_n, p->next_batch_index, &x);
+        const gist_extract_parts_desc x = parts_desc(p, p->next_ids, p->next_n, p->next_batch_index, p->layer[0].n_in, p->x0,
+                                                     p->layer[0].n_in);
         GIST_TRY(gist_adam_segments_extract_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1,
                                                 beta2, eps, weight_decay, adam_step, nullptr, 0, nullptr, 0, 0, nullptr,
                                                 &x, s));

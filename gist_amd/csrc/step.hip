@@ -8,16 +8,10 @@
 
 #include <new>
 
-#include "common.h"
+#include "step_host.h"
 #include "class_dw_body.h"
 
 using namespace gist;
-
-#define GIST_TRY(expr)            \
-    do {                          \
-        int rc_ = (expr);         \
-        if (rc_ != GIST_OK) return rc_; \
-    } while (0)
 
 static inline uint64_t round_up2(uint64_t x) { return x + (x & 1ULL); }
 
@@ -92,19 +86,6 @@ void timer_end(gist_timer *t, int64_t slot, hipStream_t s) {
     if (t && slot >= 0) (void)hipEventRecord(t->stop[slot], s);
 }
 }  // namespace gist
-
-namespace {
-struct Scope {   // records start now, stop at scope exit
-    gist_timer *t; int64_t slot; hipStream_t s;
-    Scope(gist_timer *t_, int kind, int64_t m, int64_t n, int64_t k, hipStream_t s_)
-        : t(t_), slot(timer_begin(t_, kind, m, n, k, s_)), s(s_) {}
-    ~Scope() { timer_end(t, slot, s); }
-};
-struct ActiveTimer {   // kernels below the entry points see the armed timer for this call only
-    explicit ActiveTimer(gist_timer *t) { tl_timer = t; }
-    ~ActiveTimer() { tl_timer = nullptr; }
-};
-}  // namespace
 
 // ---- split projection operands kept by the step (gist_step_plan.h3_workspace) ---------------
 namespace {
@@ -352,48 +333,628 @@ extern "C" int64_t gist_step_h3_workspace_bytes_mode(const gist_step_plan *plan,
     return mode == 2 ? b3_layout(plan, nullptr, mode).bytes : h3_layout(plan, nullptr, mode).bytes;
 }
 
+// ---- one call's decisions, each made once ----------------------------------------------------------------
+namespace {
+constexpr int kPhaseBits = GIST_STEP_PHASE_FORWARD | GIST_STEP_PHASE_BACKWARD | GIST_STEP_PHASE_OPTIMIZER;
+
+// Everything gist_sage_step decides before it launches, filled by decide() from (plan, n, drop_offset, flags).
+// Phases (gist_hip.h, GIST_STEP_PHASE_*): a caller whose loop is `pred = model(g); loss = f(pred); loss.backward();
+// optimizer.step()` issues the same iteration as three calls.  Only do_* and split_phases read the phase bits, so the
+// three calls agree on everything else.
+struct StepDecisions {
+    bool train, drop;
+    bool do_fwd, do_bwd, do_opt;   // the phases this call runs
+    bool split_phases;             // one phase of three calls (not none / all three bits)
+    bool dlogits_given;
+    bool blocked;                  // the batch comes with its locality blocks
+    bool pairs;                    // may the batch have sibling blocks (speed only: gist_hip.h)
+    int gemm_mode;
+    H3Step h3;                     // split operands kept by the step (gist_step_plan.h3_workspace), by GEMM mode;
+    B3Step b3;                     //   a layer that is `on` in neither splits per call inside gist_gemm_*
+    bool fuse;                     // the fused sequence (gist_step_plan.fuse)
+    bool defer;                    // slabs + chunk sums consumed by the loss kernel / the optimiser
+    FusedLayout fl;
+    uint64_t offs[GIST_MAX_LAYERS];        // mask offset of layer k's [h | ah]
+    bool plain[GIST_MAX_LAYERS];           // layer k is on neither kept-split path
+    bool fwd_fold[GIST_MAX_LAYERS];        // forward: dropout([h | ah]) written by the producers, the aggregation reads hsrc[k]
+    bool mask_in_spmm[GIST_MAX_LAYERS];    // backward: the mask of dZ_k applied by the reverse aggregation as it reads dZ_k
+    bool cls_fused;                // the class layer as gist_class_layer_f32 + gist_class_dw_slabs_f32
+    float keep; uint64_t sm;       // dropout's scale and seed multiple
+};
+
+// a kept-split layout carved from the plan's workspace; none if the workspace is missing, misaligned or too small, or
+// the batch has more rows than it was sized for
+template <class Step>
+Step kept_splits(const gist_step_plan *p, int64_t n, int mode, Step (*layout)(const gist_step_plan *, char *, int)) {
+    if (p->h3_workspace == nullptr || !aligned16(p->h3_workspace) || n > p->n_max) return Step{};
+    const Step h = layout(p, static_cast<char *>(p->h3_workspace), mode);
+    return h.bytes > p->h3_workspace_bytes ? Step{} : h;
+}
+
+// May layer k's dropout be folded into the producers of [h | ah] when its mask starts at `offset`?  A function of the
+// layer and the offset, so that the optimiser can apply it to the NEXT batch's layer 0 (gist_extract_parts_desc.x0) the
+// way the next call applies it to itself.  Reads d.fuse, d.drop, d.plain and d.blocked.
+bool folds_forward(const gist_step_plan *p, const StepDecisions &d, int k, uint64_t offset) {
+    const gist_layer_desc &l = p->layer[k];
+    return d.fuse && d.drop && d.plain[k] && p->hsrc[k] != nullptr && (offset & 1) == 0 && p->ld_hsrc[k] >= l.n_in &&
+           spmm_drop_takes(1, l.n_in, p->ld_hsrc[k], l.ldz, p->hsrc[k], l.Z + l.n_in, d.blocked ? p->row_blocks : nullptr);
+}
+
+StepDecisions decide(const gist_step_plan *p, int64_t n, uint64_t drop_offset, int flags) {
+    StepDecisions d{};
+    const int L1 = p->n_layers;
+    const int phases = flags & kPhaseBits;
+    d.train = (flags & GIST_STEP_TRAIN) != 0;
+    d.drop = d.train && p->p_drop > 0.f;
+    d.do_fwd = phases == 0 || (phases & GIST_STEP_PHASE_FORWARD);
+    d.do_bwd = d.train && (phases == 0 || (phases & GIST_STEP_PHASE_BACKWARD));
+    d.do_opt = d.train && (phases == 0 || (phases & GIST_STEP_PHASE_OPTIMIZER));
+    d.split_phases = phases != 0 && phases != kPhaseBits;
+    d.dlogits_given = (flags & GIST_STEP_DLOGITS_GIVEN) != 0;
+    d.blocked = p->row_blocks != nullptr && p->n_row_blocks > 0;
+    d.pairs = p->sibling_parts != 0;
+    d.gemm_mode = gist_gemm_get_mode();
+    d.h3 = kept_splits<H3Step>(p, n, d.gemm_mode, h3_layout);
+    d.b3 = kept_splits<B3Step>(p, n, d.gemm_mode, b3_layout);
+    d.fuse = p->fuse != 0 && n <= p->n_max;
+    if (d.fuse && p->col_partials != nullptr && aligned16(p->col_partials)) {
+        d.fl = fused_layout(p, static_cast<char *>(p->fused_workspace), p->col_partials);
+        d.defer = p->fused_workspace == nullptr ? d.fl.bytes == 0
+                                                : (aligned16(p->fused_workspace) && d.fl.bytes <= p->fused_workspace_bytes);
+        if (!d.defer) d.fl = FusedLayout{};
+    }
+    uint64_t off = drop_offset;
+    for (int k = 0; k < L1; ++k) {
+        const gist_layer_desc &l = p->layer[k];
+        d.offs[k] = off;
+        if (d.drop) off += round_up2((uint64_t)n * 2 * l.n_in);
+        d.plain[k] = !d.h3.layer[k].on && !d.b3.layer[k].on;
+        // (layer 0's producer is the extraction: this call's, or the previous call's GIST_STEP_EXTRACT_NEXT)
+        d.fwd_fold[k] = (k > 0 || (flags & (GIST_STEP_EXTRACT | GIST_STEP_PREEXTRACTED))) && folds_forward(p, d, k, d.offs[k]);
+        d.mask_in_spmm[k] = d.fuse && d.drop && k > 0 && k < L1 - 1 && (d.offs[k] & 1) == 0 &&
+                            spmm_drop_takes(2, l.n_in, 2 * l.n_in, 2 * l.n_in, p->dZ + l.n_in, p->dZ,
+                                            d.blocked ? p->row_blocks : nullptr);
+    }
+    d.keep = d.drop ? 1.0f / (1.0f - p->p_drop) : 1.f;
+    d.sm = p->seed * 0x9E3779B97F4A7C15ULL;
+    // the class layer as gist_class_layer_f32 + gist_class_dw_slabs_f32 (projection, CE, dZ with its mask and the
+    // bias gradient's chunk sums in one launch, dW as slabs for the optimiser) instead of four launches
+    const gist_layer_desc &l = p->layer[L1 - 1];
+    d.cls_fused = d.train && d.defer && d.plain[L1 - 1] && p->ldc <= 64 && (d.offs[L1 - 1] & 1) == 0 &&
+                  (int)tune(GIST_TUNE_CLASS_FUSED) != 1 &&
+                  gist_class_layer_takes(n, l.n_out, 2 * l.n_in, l.ldz, 2 * l.n_in, l.Z, l.W) == 1 &&
+                  d.fl.dw_slabs[L1 - 1] != nullptr &&
+                  d.fl.dw_bytes[L1 - 1] >= gist_class_dw_slab_bytes(n, l.n_out, 2 * l.n_in);
+    return d;
+}
+
+// can batch `batch` = ids[0..n) be extracted by gist_extract_parts_batch's kernel?
+bool extracts_by_parts(const gist_step_plan *p, const StepDecisions &d, const int32_t *ids, int64_t n, int32_t batch) {
+    return d.fuse && p->node_part && p->part_slot && p->extract_scratch && ids && batch >= 0 && n > 0 && n <= p->n_max &&
+           gist_extract_parts_supported(p->n_max) == 1;
+}
+
+// does the optimiser launch of this step also extract the next batch (plan->next_*)?
+// (beside a LARGE optimiser pass the extraction's 1024-thread workgroups cost more than they hide: each holds half a
+// CU's wave slots for the ~20 us of its look-back chain -- 233 against 199 + 21 us at 38.8 M parameters, 32 against
+// 16 + 21 at 1.2 M.  With the aggregating extraction's loads restructured the break-even is at ~11 M: H = 2048,
+// 11.0 M parameters, 0.9788 / 0.9822 ms per step against 0.9807 / 0.9836 without; H = 4096, 38.8 M: +70 us)
+constexpr int64_t kPrefetchMaxParams = 12LL << 20;
+bool prefetches_next(const gist_step_plan *p, const StepDecisions &d) {
+    return d.defer && p->n_params <= kPrefetchMaxParams &&
+           extracts_by_parts(p, d, p->next_ids, p->next_n, p->next_batch_index);
+}
+
+// the one-launch extraction of a batch whose masks start at `offset`: layer 0's mask goes into the feature gather where
+// folds_forward says so, and layer 0's aggregation comes with it when the plan has the intra-part sums
+gist_extract_parts_desc sage_parts_desc(const gist_step_plan *p, const StepDecisions &d, const int32_t *ids, int64_t n,
+                                        int32_t batch, uint64_t offset) {
+    const gist_layer_desc &l0 = p->layer[0];
+    gist_extract_parts_desc x = parts_desc(p, ids, n, batch, l0.n_in, l0.Z, l0.ldz);
+    x.x0 = folds_forward(p, d, 0, offset) ? p->hsrc[0] : nullptr; x.ldx0 = p->ld_hsrc[0]; x.p = p->p_drop; x.seed = p->seed;
+    x.offset = offset; x.mask_ld = 2 * l0.n_in;
+    if (p->feat_intra != nullptr) { x.feat_intra = p->feat_intra; x.ld_intra = p->ld_feat_intra; x.ah = l0.Z + l0.n_in; }
+    return x;
+}
+
+// what crosses the phases of one call
+struct StepState {
+    bool pre_ah;                       // layer 0's aggregation was formed by the extraction
+    const void *prep_fwd, *prep_bwd;   // the batch's prepared block structure, per orientation (NULL: none)
+    gist_grad_segment segs[2 * GIST_MAX_LAYERS];      // gradient sums left to the optimiser
+    int n_segs;
+};
+
+// grads[dst .. dst + count) = the sum of n_src dense partial arrays at src (chunk sums of a bias gradient, split-K slabs
+// of a weight gradient), formed by the optimiser
+void add_segment(const gist_step_plan *p, StepState &x, const float *dst, int64_t count, const float *src, int64_t n_src) {
+    gist_grad_segment &g = x.segs[x.n_segs++];
+    g.begin = dst - p->grads; g.end = g.begin + count;
+    g.src = src; g.stride = count; g.n_src = (int32_t)n_src;
+}
+
 // The step's aggregations: the blocked kernels when the batch comes with its locality blocks; with the
 // batch's prepared block structure (`prepared`: this orientation's) the matrix-core kernel skips its set-up,
 // and looks for sibling blocks only if the plan says the batch may have them.
-static int step_spmm(const gist_step_plan *p, const int32_t *rowptr, const int32_t *col, const float *x,
-                     int64_t ldx, float *y, int64_t ldy, int64_t n, int64_t d, const float *out_scale,
-                     const float *src_scale, int accumulate, const void *prepared, gist_stream_t s) {
-    if (p->row_blocks != nullptr && p->n_row_blocks > 0) {
-        if (prepared != nullptr)
-            return spmm_prepared(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale, accumulate, p->row_blocks,
-                                 p->n_row_blocks, prepared, as_stream(s), p->sibling_parts != 0);
-        return gist_spmm_csr_blocked_f32(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale,
-                                         accumulate, p->row_blocks, p->n_row_blocks, s);
-    }
-    return gist_spmm_csr_f32(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale, accumulate, s);
+int step_spmm(const gist_step_plan *p, const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y,
+              int64_t ldy, int64_t n, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
+              const void *prepared, gist_stream_t s) {
+    if (p->row_blocks == nullptr || p->n_row_blocks <= 0)
+        return gist_spmm_csr_f32(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale, accumulate, s);
+    if (prepared != nullptr)
+        return spmm_prepared(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale, accumulate, p->row_blocks,
+                             p->n_row_blocks, prepared, as_stream(s), p->sibling_parts != 0);
+    return gist_spmm_csr_blocked_f32(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale, accumulate, p->row_blocks,
+                                     p->n_row_blocks, s);
 }
 
-constexpr int64_t kPrefetchMaxParams = 12LL << 20;
-// can the next batch (plan->next_*) be extracted by gist_extract_parts_batch's kernel?
-static bool next_parts_ok(const gist_step_plan *p, bool fuse) {
-    return fuse && p->node_part && p->part_slot && p->extract_scratch && p->next_ids && p->next_batch_index >= 0 &&
-           p->next_n > 0 && p->next_n <= p->n_max && gist_extract_parts_supported(p->n_max) == 1;
+// ---- phase 1: this step's weights as kept split operands ---------------------------------------------------
+int split_weights(const gist_step_plan *p, const StepDecisions &d, hipStream_t st) {
+    const int L1 = p->n_layers;
+    if (d.b3.any) {      // one read each, one launch for all of them
+        Scope sc(p->timer, 3, 0, 0, 0, st);
+        B3Dual jobs[GIST_MAX_LAYERS];
+        int n_jobs = 0;
+        for (int k = 0; k < L1; ++k) {
+            const B3Layer &hl = d.b3.layer[k];
+            if (!hl.on) continue;
+            const gist_layer_desc &l = p->layer[k];
+            B3Dual &j = jobs[n_jobs++];
+            j = B3Dual{};
+            j.src = l.W; j.ld = 2 * l.n_in; j.rows = l.n_out; j.cols = 2 * l.n_in;
+            j.dst_r = hl.Ws;
+            j.dst_t = d.train ? hl.WsT : nullptr;
+        }
+        for (int i = 0; i < n_jobs; i += B3_SPLIT_MAX_JOBS)
+            GIST_TRY(b3_split_jobs(jobs + i, n_jobs - i < B3_SPLIT_MAX_JOBS ? n_jobs - i : B3_SPLIT_MAX_JOBS, st));
+    }
+    if (d.h3.any) {      // rows split for Y = Z.W^T, transposed for dZ = dY.W
+        Scope sc(p->timer, 3, 0, 0, 0, st);
+        bool zeroed = false;
+        for (int k = 0; k < L1; ++k) {
+            const H3Layer &hl = d.h3.layer[k];
+            if (!hl.on) continue;
+            const gist_layer_desc &l = p->layer[k];
+            if (k > 0 && d.train) {      // one read of W_k, one scale for the tensor, both layouts
+                if (!zeroed && hipMemsetAsync(d.h3.amax, 0, GIST_MAX_LAYERS * 4, st) != hipSuccess) {
+                    set_error("gist_sage_step: hipMemsetAsync failed");
+                    return GIST_ELAUNCH;
+                }
+                zeroed = true;
+                GIST_TRY(h3_absmax(l.W, 2 * l.n_in, l.n_out, 2 * l.n_in, d.h3.amax + k, st));
+                H3Dual j{};
+                j.src = l.W; j.ld = 2 * l.n_in; j.rows = l.n_out; j.cols = 2 * l.n_in;
+                j.amax = d.h3.amax + k;
+                j.dst_r = hl.Ws; j.inv_r = hl.inv_wr; j.dst_t = hl.WsT; j.inv_t = hl.inv_wt;
+                GIST_TRY(h3_dual_split(j, st));
+            } else {
+                GIST_TRY(h3_split_rows(l.W, 2 * l.n_in, l.n_out, 2 * l.n_in, hl.Ws, hl.inv_wr, st));
+            }
+        }
+    }
+    return GIST_OK;
 }
+
+// ---- phase 2: the batch (GIST_STEP_EXTRACT) and its block structure, once for all its aggregations -----------
+int extract_and_prepare(const gist_step_plan *p, const StepDecisions &d, StepState &x, const int32_t *ids, int64_t n,
+                        int flags, gist_stream_t s) {
+    const gist_layer_desc &l0 = p->layer[0];
+    x.pre_ah = (flags & GIST_STEP_PREEXTRACTED) && p->feat_intra != nullptr;
+    if ((flags & GIST_STEP_EXTRACT) && d.do_fwd) {
+        if (extracts_by_parts(p, d, ids, n, p->batch_index)) {
+            const gist_extract_parts_desc desc = sage_parts_desc(p, d, ids, n, p->batch_index, d.offs[0]);
+            x.pre_ah = p->feat_intra != nullptr;      // (layer 0's aggregation comes with the extraction)
+            GIST_TRY(gist_extract_parts_desc_batch(&desc, s));
+        } else if (d.fwd_fold[0])
+            GIST_TRY(gist_extract_batch_drop(p->g_rowptr, p->g_col, p->g_t_rowptr, p->g_t_col, ids, n, p->remap, p->rowptr,
+                                             p->col, p->t_rowptr, p->t_col, p->col_capacity, p->norm, p->feat, p->ld_feat,
+                                             l0.n_in, l0.Z, l0.ldz, p->labels_all, p->labels, p->hsrc[0], p->ld_hsrc[0],
+                                             p->p_drop, p->seed, d.offs[0], 2 * l0.n_in, s));
+        else
+            GIST_TRY(gist_extract_batch(p->g_rowptr, p->g_col, p->g_t_rowptr, p->g_t_col, ids, n, p->remap, p->rowptr,
+                                        p->col, p->t_rowptr, p->t_col, p->col_capacity, p->norm, p->feat, p->ld_feat,
+                                        l0.n_in, l0.Z, l0.ldz, p->labels_all, p->labels, s));
+    }
+    if (!d.blocked || p->spmm_prepared == nullptr || !aligned16(p->spmm_prepared)) return GIST_OK;
+    const int64_t one = gist_spmm_blocks_bytes(p->n_row_blocks);
+    bool wide = false;      // is there an aggregation the prepared kernel takes?
+    for (int k = 0; k < p->n_layers; ++k)
+        wide = wide || spmm_prepared_takes(p->layer[k].n_in, p->layer[k].ldz, p->layer[k].ldz, p->layer[k].Z,
+                                           p->layer[k].Z + p->layer[k].n_in);
+    if (!wide || p->spmm_prepared_bytes < (d.train ? 2 : 1) * one) return GIST_OK;
+    char *base = static_cast<char *>(p->spmm_prepared), *back = d.train ? base + one : nullptr;
+    x.prep_fwd = base;
+    x.prep_bwd = back;
+    if (d.do_fwd)      // (a backward-phase call reads what the forward-phase call prepared)
+        GIST_TRY(launch_spmm_blocks_prepare(p->rowptr, p->col, d.train ? p->t_rowptr : nullptr, d.train ? p->t_col : nullptr,
+                                            n, p->row_blocks, p->n_row_blocks, base, back, as_stream(s), d.pairs));
+    return GIST_OK;
+}
+
+// ---- phase 3: forward (modules.py:310-314 / :218-237) and the loss -----------------------------------------
+int forward(const gist_step_plan *p, const StepDecisions &d, const StepState &x, int64_t n, gist_stream_t s) {
+    const int L1 = p->n_layers;
+    hipStream_t st = as_stream(s);
+    const FusedLayout &fl = d.fl;
+    int logit_slabs = 0;           // > 1: the class layer's logits are still split-K slabs
+    for (int k = 0; k < L1; ++k) {
+        const gist_layer_desc &l = p->layer[k];
+        int y_slabs_n = 1;                   // > 1: this layer's pre-norm output is still split-K slabs
+        const float *y_slabs = nullptr;
+        if (!(k == 0 && x.pre_ah)) {
+            Scope sc(p->timer, 0, n, n, l.n_in, st);
+            if (d.fwd_fold[k]) {      // source = the undropped input, store = dropout(ah)
+                SpmmDrop dr{};
+                dr.mode = 1; dr.p = p->p_drop; dr.scale = d.keep; dr.sm = d.sm;
+                dr.y_base = d.offs[k] + (uint64_t)l.n_in; dr.src_base = 0; dr.ld = 2 * l.n_in;
+                GIST_TRY(spmm_drop(p->rowptr, p->col, p->hsrc[k], p->ld_hsrc[k], l.Z + l.n_in, l.ldz, n, l.n_in,
+                                   p->norm, nullptr, 0, d.blocked ? p->row_blocks : nullptr, p->n_row_blocks, dr, st,
+                                   x.prep_fwd, d.pairs));
+            } else {
+                GIST_TRY(step_spmm(p, p->rowptr, p->col, l.Z, l.ldz, l.Z + l.n_in, l.ldz, n, l.n_in, p->norm, nullptr, 0,
+                                   x.prep_fwd, s));
+            }
+        }
+        if (d.h3.layer[k].on) {
+            // dropout + split of Z_k in one pass (both layouts when training); the dropped fp32 Z_k is never written: the
+            // backward only needs its transposed split
+            const H3Layer &hl = d.h3.layer[k];
+            Scope sc(p->timer, 1, n, l.n_out, 2 * l.n_in, st);
+            H3Dual j{};
+            j.src = l.Z; j.ld = l.ldz; j.rows = n; j.cols = 2 * l.n_in;
+            j.p = d.drop ? p->p_drop : 0.f; j.seed = p->seed; j.offset = d.offs[k];
+            j.fixed_shift = hl.shift;
+            j.dst_r = hl.Zs; j.inv_r = hl.inv_zr;
+            j.dst_t = d.train ? hl.ZsT : nullptr; j.inv_t = hl.inv_zt;
+            GIST_TRY(h3_dual_split(j, st));
+            GIST_TRY(h3_gemm_presplit("gist_sage_step", hl.Zs, hl.inv_zr, hl.Ws, hl.inv_wr, l.b, l.Y, l.ldy, n, l.n_out,
+                                      2 * l.n_in, st));
+        } else if (d.b3.layer[k].on) {
+            const B3Layer &hl = d.b3.layer[k];
+            Scope sc(p->timer, 1, n, l.n_out, 2 * l.n_in, st);
+            B3Dual j{};
+            j.src = l.Z; j.ld = l.ldz; j.rows = n; j.cols = 2 * l.n_in;
+            j.p = d.drop ? p->p_drop : 0.f; j.seed = p->seed; j.offset = d.offs[k];
+            j.dst_r = hl.Zs;
+            j.dst_t = d.train ? hl.ZsT : nullptr;
+            GIST_TRY(b3_dual_split(j, st));
+            // (a hidden layer's k slices stay slabs: its LayerNorm, the next launch, sums them as it reads)
+            // (with one slice the kernel adds the bias itself; slabs get it from the LayerNorm)
+            const bool to_ln = d.defer && k + 1 < L1;
+            GIST_TRY(b3_gemm_presplit("gist_sage_step", hl.Zs, hl.Ws, l.b, l.Y, l.ldy, n, l.n_out,
+                                      2 * l.n_in, d.b3.slabs, d.b3.slab_bytes, st, to_ln ? &y_slabs_n : nullptr));
+            if (to_ln) y_slabs = d.b3.slabs;
+        } else {
+            if (d.drop && !d.fwd_fold[k])
+                GIST_TRY(gist_dropout_f32(l.Z, l.ldz, n, 2 * l.n_in, p->p_drop, p->seed, d.offs[k], s));
+            if (d.cls_fused && k == L1 - 1) continue;      // (projection, loss and dZ follow in one launch)
+            Scope sc(p->timer, 1, n, l.n_out, 2 * l.n_in, st);
+            if (d.defer && k == L1 - 1 && fl.logit_slabs != nullptr) {      // the loss kernel sums the slabs
+                GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
+                                    fl.logit_slabs, fl.logit_bytes, &logit_slabs, st));
+            } else if (d.defer && k + 1 < L1 && fl.y_slabs != nullptr && !h3_eligible(n, l.n_out, 2 * l.n_in) &&
+                       !b3_eligible(n, l.n_out, 2 * l.n_in)) {
+                // the LayerNorm sums the slabs (a projection the per-call split paths take keeps their workspace)
+                GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
+                                    fl.y_slabs, fl.y_bytes, &y_slabs_n, st));
+                y_slabs = fl.y_slabs;
+            } else {
+                GIST_TRY(gist_gemm_nt_f32(l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in, p->workspace,
+                                          p->workspace_bytes, s));
+            }
+        }
+        if (k + 1 < L1) {
+            const gist_layer_desc &nx = p->layer[k + 1];
+            const bool fold = d.fwd_fold[k + 1];      // the LayerNorm writes layer k + 1's input with its mask
+            float *rstd = p->use_layernorm ? l.rstd : nullptr;
+            if (y_slabs_n > 1)
+                GIST_TRY(gist_ln_relu_fwd_slabs_f32(l.Y, l.ldy, y_slabs, n * l.n_out, y_slabs_n, l.b, nx.Z, nx.ldz,
+                                                    fold ? p->hsrc[k + 1] : nullptr, fold ? p->ld_hsrc[k + 1] : 0, rstd, n,
+                                                    l.n_out, p->use_layernorm, 1, 1e-5f, fold ? p->p_drop : 0.f, p->seed,
+                                                    fold ? d.offs[k + 1] : 0, fold ? 2 * nx.n_in : l.n_out, s));
+            else if (fold)
+                GIST_TRY(gist_ln_relu_fwd_drop_f32(l.Y, l.ldy, nx.Z, nx.ldz, p->hsrc[k + 1], p->ld_hsrc[k + 1], rstd, n,
+                                                   l.n_out, p->use_layernorm, 1, 1e-5f, p->p_drop, p->seed,
+                                                   d.offs[k + 1], 2 * nx.n_in, s));
+            else
+                GIST_TRY(gist_ln_relu_fwd_f32(l.Y, l.ldy, nx.Z, nx.ldz, rstd, n, l.n_out, p->use_layernorm, 1, 1e-5f, s));
+        }
+    }
+    const gist_layer_desc &last = p->layer[L1 - 1];
+    // the optimiser kernel reduces the loss when it runs with deferred work anyway
+    const bool loss_in_adam = d.train && d.defer;
+    if (d.cls_fused) {
+        Scope sc(p->timer, 1, n, (L1 > 1 ? 2 : 1) * last.n_out, 2 * last.n_in, st);
+        GIST_TRY(gist_class_layer_f32(last.Z, last.ldz, last.W, 2 * last.n_in, last.b, p->labels, n, last.Y, last.ldy,
+                                      p->dlogits, p->ldc, p->row_loss, L1 > 1 ? p->dZ : nullptr, 2 * last.n_in,
+                                      d.drop ? p->p_drop : 0.f, p->seed, d.offs[L1 - 1], fl.partials[L1 - 1], n,
+                                      last.n_out, 2 * last.n_in, s));
+    } else {
+        GIST_TRY(softmax_xent_ex("gist_sage_step", last.Y, last.ldy, logit_slabs > 1 ? fl.logit_slabs : nullptr,
+                                 n * last.n_out, logit_slabs > 1 ? logit_slabs : 0, last.b, p->labels, nullptr, n, p->row_loss,
+                                 loss_in_adam ? nullptr : p->loss, p->dlogits, p->ldc, n, last.n_out, st));
+    }
+    // a forward-phase call leaves the loss complete: its optimiser launch is another call
+    if (d.split_phases && loss_in_adam) GIST_TRY(loss_finish(p->row_loss, n, n, p->loss, st));
+    return GIST_OK;
+}
+
+// ---- phase 4: backward, layer by layer from the last ---------------------------------
+// what a layer's backward leaves for the layer below it
+struct LayerCarry {
+    int64_t lnb_rows;          // > 0: the layer below got its LayerNorm backward (and that many rows of partial sums) from
+                               // the reverse aggregation just launched
+    ClassDwArgs dw_args;       // the class layer's weight-gradient slabs, deferred to the LayerNorm backward below it
+    bool dw_pending;
+};
+
+// dO_{k-1} = A^T-aggregate of dZ_k's right half into its left half, under dZ_k's dropout mask: folded into the
+// aggregation's reader (mask_in_spmm), or, for the unmasked dZ of a split projection, by a pass over dZ_k first (a plain
+// layer's dZ kernel has applied it).  ln: the LayerNorm backward of layer k - 1 riding in this launch's store.
+int reverse_aggregate(const gist_step_plan *p, const StepDecisions &d, const StepState &x, int64_t n, int k,
+                      gist_stream_t s, const SpmmLnBwd *ln = nullptr) {
+    const gist_layer_desc &l = p->layer[k];
+    hipStream_t st = as_stream(s);
+    if (d.mask_in_spmm[k]) {
+        Scope sc(p->timer, 0, n, n, l.n_in, st);
+        SpmmDrop dr{};
+        dr.mode = 2; dr.p = p->p_drop; dr.scale = d.keep; dr.sm = d.sm;
+        dr.y_base = d.offs[k]; dr.src_base = d.offs[k] + (uint64_t)l.n_in; dr.ld = 2 * l.n_in;
+        return spmm_drop(p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n, l.n_in, nullptr,
+                         p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, x.prep_bwd, d.pairs, ln);
+    }
+    if (d.drop && !d.plain[k])
+        GIST_TRY(gist_dropout_f32(p->dZ, 2 * l.n_in, n, 2 * l.n_in, p->p_drop, p->seed, d.offs[k], s));
+    Scope sc(p->timer, 0, n, n, l.n_in, st);
+    return step_spmm(p, p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n, l.n_in, nullptr,
+                     p->norm, 1, x.prep_bwd, s);
+}
+
+// dY_k of a hidden layer from dO_k (the left half of dZ_{k+1}), over yhat in Y_k.  *db_done: the bias gradient's chunk
+// sums were written on the way.
+int hidden_dy(const gist_step_plan *p, const StepDecisions &d, int64_t n, int k, LayerCarry &c, bool *db_done,
+              hipStream_t st) {
+    const gist_layer_desc &l = p->layer[k];
+    const int64_t i_next = p->layer[k + 1].n_in;      // == l.n_out
+    const float *rstd = p->use_layernorm ? l.rstd : nullptr;
+    if (c.lnb_rows > 0) {      // (came with the reverse aggregation of layer k + 1)
+        c.lnb_rows = 0;
+        *db_done = true;
+        return GIST_OK;
+    }
+    if (!d.defer || !d.plain[k])
+        return ln_relu_bwd_ex(p->dZ, 2 * i_next, l.Y, l.ldy, rstd, l.Y, l.ldy, n, l.n_out, p->use_layernorm, 1,
+                              d.h3.layer[k].on ? d.h3.rowmax : nullptr, st);
+    *db_done = true;
+    if (!c.dw_pending)
+        return ln_relu_bwd_colsum(p->dZ, 2 * i_next, l.Y, l.ldy, rstd, l.Y, l.ldy, n, l.n_out, p->use_layernorm, 1,
+                                  d.fl.partials[k], st);
+    c.dw_pending = false;      // ... with the class layer's weight-gradient slabs in the same grid
+    return ln_relu_bwd_colsum_class_dw(p->dZ, 2 * i_next, l.Y, l.ldy, rstd, l.Y, l.ldy, n, l.n_out, p->use_layernorm, 1,
+                                       d.fl.partials[k], c.dw_args, st);
+}
+
+// layer k on kept f16x3 operands: bias gradient + column maxima of dY_k, one read of dY_k -> both split layouts
+// (row maxima came from the LayerNorm backward), then dZ_k and dW_k on the splits
+int backward_h3(const gist_step_plan *p, const StepDecisions &d, const StepState &x, int64_t n, int k, const float *dy,
+                int64_t lddy, gist_stream_t s) {
+    const gist_layer_desc &l = p->layer[k];
+    const H3Step &h3 = d.h3;
+    const H3Layer &hl = h3.layer[k];
+    hipStream_t st = as_stream(s);
+    GIST_TRY(colsum_ex(dy, lddy, n, l.n_out, p->partials, l.db, h3.pmax, h3.colmax, st));
+    {
+        Scope sc(p->timer, 3, 0, 0, 0, st);
+        H3Dual j{};
+        j.src = dy; j.ld = lddy; j.rows = n; j.cols = l.n_out;
+        j.rowmax = h3.rowmax; j.colmax = h3.colmax;
+        j.dst_r = k > 0 ? h3.dYs : nullptr; j.inv_r = h3.inv_dyr;
+        j.dst_t = h3.dYsT; j.inv_t = h3.inv_dyt;
+        GIST_TRY(h3_dual_split(j, st));
+    }
+    if (k > 0) {
+        Scope sc(p->timer, 1, n, 2 * l.n_in, l.n_out, st);
+        GIST_TRY(h3_gemm_presplit("gist_sage_step", h3.dYs, h3.inv_dyr, hl.WsT, hl.inv_wt,
+                                  nullptr, p->dZ, 2 * l.n_in, n, 2 * l.n_in, l.n_out, st));
+    }
+    {
+        Scope sc(p->timer, 1, l.n_out, 2 * l.n_in, n, st);
+        GIST_TRY(h3_gemm_presplit("gist_sage_step", h3.dYsT, h3.inv_dyt, hl.ZsT, hl.inv_zt,
+                                  nullptr, l.dW, 2 * l.n_in, l.n_out, 2 * l.n_in, n, st));
+    }
+    return k > 0 ? reverse_aggregate(p, d, x, n, k, s) : GIST_OK;
+}
+
+// layer k on kept bf16x3 operands: bias gradient, then one read of dY_k -> both split layouts, dZ_k and dW_k on the splits
+int backward_b3(const gist_step_plan *p, const StepDecisions &d, StepState &x, int64_t n, int k, const float *dy,
+                int64_t lddy, gist_stream_t s) {
+    const gist_layer_desc &l = p->layer[k];
+    const B3Step &b3 = d.b3;
+    const B3Layer &hl = b3.layer[k];
+    hipStream_t st = as_stream(s);
+    // (fused step: the split tiles' column sums stay in the layer's own partials and the optimiser forms db_k from them
+    // -- 32 sources per element, a dedicated-block segment -- instead of a 5-us reduce launch per layer)
+    const bool db_in_adam = d.defer && d.fl.partials[k] != nullptr;
+    {   // (the split's 64 x 64 tiles also give the bias gradient's per-chunk column sums)
+        Scope sc(p->timer, 3, 0, 0, 0, st);
+        B3Dual j{};
+        j.src = dy; j.ld = lddy; j.rows = n; j.cols = l.n_out;
+        j.dst_r = k > 0 ? b3.dYs : nullptr;
+        j.dst_t = b3.dYsT;
+        j.col_partials = db_in_adam ? d.fl.partials[k] : p->partials;
+        GIST_TRY(b3_dual_split(j, st));
+    }
+    if (db_in_adam)
+        add_segment(p, x, l.db, l.n_out, d.fl.partials[k], gist_colsum_partials(n));
+    else
+        GIST_TRY(colsum_finish(p->partials, gist_colsum_partials(n), l.n_out, l.db, st));
+    if (k > 0) {
+        Scope sc(p->timer, 1, n, 2 * l.n_in, l.n_out, st);
+        GIST_TRY(b3_gemm_presplit("gist_sage_step", b3.dYs, hl.WsT, nullptr, p->dZ, 2 * l.n_in, n,
+                                  2 * l.n_in, l.n_out, b3.slabs, b3.slab_bytes, st));
+    }
+    {
+        Scope sc(p->timer, 1, l.n_out, 2 * l.n_in, n, st);
+        // the step's LAST projection may leave its k slices to the optimiser (the slab scratch is not reused before it runs)
+        int ns = 1;
+        GIST_TRY(b3_gemm_presplit("gist_sage_step", b3.dYsT, hl.ZsT, nullptr, l.dW, 2 * l.n_in, l.n_out, 2 * l.n_in, n,
+                                  b3.slabs, b3.slab_bytes, st, d.defer && k == 0 ? &ns : nullptr));
+        if (ns > 1) add_segment(p, x, l.dW, l.n_out * 2 * l.n_in, b3.slabs, ns);
+    }
+    return k > 0 ? reverse_aggregate(p, d, x, n, k, s) : GIST_OK;
+}
+
+// dW_k of a plain layer: slabs for the optimiser in the fused step, gist_gemm_tn_f32 otherwise
+int plain_dw(const gist_step_plan *p, const StepDecisions &d, StepState &x, int64_t n, int k, const float *dy,
+             int64_t lddy, LayerCarry &c, gist_stream_t s) {
+    const int L1 = p->n_layers;
+    const gist_layer_desc &l = p->layer[k];
+    const FusedLayout &fl = d.fl;
+    hipStream_t st = as_stream(s);
+    const bool cls = d.cls_fused && k == L1 - 1;
+    // The class layer's weight-gradient slabs need dlogits and the layer's input only; the LayerNorm backward of
+    // the layer below (next in the backward loop, behind the reverse aggregation) runs 128 workgroups for ~6 us:
+    // the slabs' workgroups go into ITS grid (ln_relu_bwd_cs_dw_kernel) -- one launch fewer per step
+    const bool dw_with_ln = cls && L1 >= 2 && d.defer && d.plain[L1 - 2] && (int)tune(GIST_TUNE_CLASS_FUSED) != 2;
+    Scope sc(dw_with_ln ? nullptr : p->timer, 1, l.n_out, 2 * l.n_in, n, st);
+    if (cls) {
+        int32_t ns = 1;
+        if (dw_with_ln) {
+            GIST_TRY(class_dw_args("gist_sage_step", dy, lddy, l.Z, l.ldz, fl.dw_slabs[k], fl.dw_bytes[k], n, l.n_out,
+                                   2 * l.n_in, &c.dw_args, &ns));
+            c.dw_pending = true;
+        } else {
+            GIST_TRY(gist_class_dw_slabs_f32(dy, lddy, l.Z, l.ldz, fl.dw_slabs[k], fl.dw_bytes[k], &ns, n, l.n_out,
+                                             2 * l.n_in, s));
+        }
+        add_segment(p, x, l.dW, l.n_out * 2 * l.n_in, fl.dw_slabs[k], ns);
+    } else if (d.defer && fl.dw_slabs[k] != nullptr) {      // the optimiser sums the slabs
+        int ns = 1;
+        GIST_TRY(gemm_slabs(2, dy, lddy, l.Z, l.ldz, nullptr, l.dW, 2 * l.n_in, l.n_out, 2 * l.n_in, n,
+                            fl.dw_slabs[k], fl.dw_bytes[k], &ns, st));
+        if (ns > 1) add_segment(p, x, l.dW, l.n_out * 2 * l.n_in, fl.dw_slabs[k], ns);
+    } else {
+        GIST_TRY(gist_gemm_tn_f32(dy, lddy, l.Z, l.ldz, l.dW, 2 * l.n_in, l.n_out, 2 * l.n_in, n, p->workspace,
+                                  p->workspace_bytes, s));
+    }
+    return GIST_OK;
+}
+
+// layer k on the fp32 / per-call-split projections.  db_done: dY_k's chunk sums (db_rows rows of them) are written
+int backward_plain(const gist_step_plan *p, const StepDecisions &d, StepState &x, int64_t n, int k, const float *dy,
+                   int64_t lddy, bool db_done, int64_t db_rows, LayerCarry &c, gist_stream_t s) {
+    const int L1 = p->n_layers;
+    const gist_layer_desc &l = p->layer[k];
+    const FusedLayout &fl = d.fl;
+    hipStream_t st = as_stream(s);
+    // dZ_k and dW_k of a narrow hidden layer read the same dY_k: one launch of the fp32 kernel's tiles for both
+    // (gist_gemm_nn_tn_dual_f32) when the mask of dZ_k is the reverse aggregation's business anyway
+    if (d.defer && k > 0 && k < L1 - 1 && db_done && (!d.drop || d.mask_in_spmm[k]) &&
+        gemm_dual_takes(n, 2 * l.n_in, l.n_out, lddy, 2 * l.n_in, l.ldz, 2 * l.n_in, dy, l.W, l.Z, p->dZ)) {
+        Scope sc(p->timer, 1, n, 4 * l.n_in, l.n_out, st);
+        int ns = 1;
+        GIST_TRY(gemm_dual_nn_tn("gist_sage_step", dy, lddy, l.W, 2 * l.n_in, p->dZ, 2 * l.n_in, l.Z, l.ldz, l.dW,
+                                 2 * l.n_in, n, 2 * l.n_in, l.n_out, fl.dw_slabs[k], fl.dw_bytes[k], &ns, st));
+        if (ns > 1) add_segment(p, x, l.dW, l.n_out * 2 * l.n_in, fl.dw_slabs[k], ns);
+    } else {
+        // GIST_STEP_DLOGITS_GIVEN: plan->dlogits was written by the caller (any loss on the logits): the class layer's dZ
+        // and bias chunk sums of the fused forward belong to ANOTHER dlogits and are recomputed from the given one
+        if (d.cls_fused && !d.dlogits_given && k == L1 - 1) {
+            db_done = true;      // (dZ and the bias chunks came with the loss)
+        } else if (k > 0) {      // dZ with its dropout mask (or the mask left to the reverse aggregation)
+            Scope sc(p->timer, 1, n, 2 * l.n_in, l.n_out, st);
+            const bool chunk_db = d.defer && k == L1 - 1;      // the class layer's dZ kernel sees dlogits in 16-row chunks
+            GIST_TRY(gemm_nn_dropout_ex("gist_sage_step", dy, lddy, l.W, 2 * l.n_in, p->dZ, 2 * l.n_in, n,
+                                        2 * l.n_in, l.n_out, (d.drop && !d.mask_in_spmm[k]) ? p->p_drop : 0.f, p->seed,
+                                        d.offs[k], p->workspace, p->workspace_bytes,
+                                        chunk_db ? fl.partials[k] : nullptr, st));
+            db_done = db_done || chunk_db;
+        }
+        GIST_TRY(plain_dw(p, d, x, n, k, dy, lddy, c, s));
+    }
+    if (d.defer) {      // db_k = chunk sums, formed by the optimiser
+        if (!db_done)      // (a one-layer model: no dZ kernel has seen dlogits)
+            GIST_TRY(colsum_rows16(dy, lddy, n, l.n_out, fl.partials[k], k == L1 - 1 ? false : true, st));
+        add_segment(p, x, l.db, l.n_out, fl.partials[k], db_rows);
+    } else {
+        GIST_TRY(gist_colsum_f32(dy, lddy, n, l.n_out, p->partials, l.db, s));
+    }
+    if (k == 0) return GIST_OK;
+    if (!d.mask_in_spmm[k]) return reverse_aggregate(p, d, x, n, k, s);
+    // the LayerNorm + ReLU backward of layer k - 1 in the aggregation's store (its rows are whole in one wave)
+    const gist_layer_desc &lo = p->layer[k - 1];
+    const int64_t units = d.blocked ? spmm_lnb_units(p->n_row_blocks) : 0;
+    const bool with_ln = d.defer && d.plain[k - 1] && !c.dw_pending && (int)tune(GIST_TUNE_LNB_FUSED) != 1 &&
+                         units > 0 && units <= fl.partial_rows[k - 1] && lo.ldy % 4 == 0 && aligned16(lo.Y) &&
+                         (!p->use_layernorm || lo.rstd != nullptr) &&
+                         spmm_lnb_takes(l.n_in, 2 * l.n_in, 2 * l.n_in, p->dZ + l.n_in, p->dZ, p->row_blocks, x.prep_bwd);
+    SpmmLnBwd ln{};
+    if (with_ln) {
+        ln.yhat = lo.Y; ln.ldy = lo.ldy; ln.rstd = p->use_layernorm ? lo.rstd : nullptr;
+        ln.dy = lo.Y; ln.lddy = lo.ldy; ln.col_partials = fl.partials[k - 1]; ln.relu = 1;
+        c.lnb_rows = units;
+    }
+    return reverse_aggregate(p, d, x, n, k, s, with_ln ? &ln : nullptr);
+}
+
+int backward(const gist_step_plan *p, const StepDecisions &d, StepState &x, int64_t n, gist_stream_t s) {
+    const int L1 = p->n_layers;
+    const int64_t chunks16 = gist_row_chunks16(n);
+    LayerCarry c{};
+    for (int k = L1 - 1; k >= 0; --k) {
+        const gist_layer_desc &l = p->layer[k];
+        const float *dy = k == L1 - 1 ? p->dlogits : l.Y;
+        const int64_t lddy = k == L1 - 1 ? p->ldc : l.ldy;
+        bool db_done = false;      // this layer's bias gradient is already in chunks
+        const int64_t db_rows = c.lnb_rows > 0 ? c.lnb_rows : chunks16;
+        if (k < L1 - 1) GIST_TRY(hidden_dy(p, d, n, k, c, &db_done, as_stream(s)));
+        if (d.h3.layer[k].on)
+            GIST_TRY(backward_h3(p, d, x, n, k, dy, lddy, s));
+        else if (d.b3.layer[k].on)
+            GIST_TRY(backward_b3(p, d, x, n, k, dy, lddy, s));
+        else
+            GIST_TRY(backward_plain(p, d, x, n, k, dy, lddy, db_done, db_rows, c, s));
+    }
+    GIST_REQUIRE(!c.dw_pending, "gist_sage_step: internal error (class-layer weight gradient not launched)");
+    // without the optimiser phase the gradient arena is complete on return (p.grad is read by the caller's optimiser,
+    // possibly by its own code first): the deferred sums in the optimiser's order, without the update
+    if (!d.do_opt && d.defer && x.n_segs > 0)
+        GIST_TRY(gist_grad_segments_finish_f32(p->grads, p->n_params, x.segs, x.n_segs, s));
+    return GIST_OK;
+}
+
+// ---- phase 5: the optimiser, with the NEXT batch's extraction in its grid when asked and possible ---------------
+struct AdamArgs { float lr, beta1, beta2, eps, weight_decay; int64_t step; };
+
+int optimise(const gist_step_plan *p, const StepDecisions &d, const StepState &x, int64_t n, const AdamArgs &a, int flags,
+             gist_stream_t s) {
+    // (an optimiser-phase call has no segments -- the backward-phase call finished the gradients -- and no loss to
+    // reduce: the forward-phase call did)
+    const float *row_loss = d.do_bwd || !d.split_phases ? p->row_loss : nullptr;
+    if ((flags & GIST_STEP_EXTRACT_NEXT) && prefetches_next(p, d)) {      // nothing reads the batch buffers any more
+        const gist_extract_parts_desc next =
+            sage_parts_desc(p, d, p->next_ids, p->next_n, p->next_batch_index, p->next_drop_offset);
+        return gist_adam_segments_extract_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, a.lr, a.beta1,
+                                              a.beta2, a.eps, a.weight_decay, a.step, x.segs, x.n_segs, row_loss, n, n,
+                                              p->loss, &next, s);
+    }
+    if (d.defer)
+        return gist_adam_segments_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, a.lr, a.beta1, a.beta2,
+                                      a.eps, a.weight_decay, a.step, x.segs, x.n_segs, row_loss, n, n, p->loss, s);
+    return gist_adam_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, a.lr, a.beta1, a.beta2, a.eps,
+                         a.weight_decay, a.step, s);
+}
+}  // namespace
 
 extern "C" int gist_sage_step_extracts_next(const gist_step_plan *p, int64_t n, int flags) {
-    if (p == nullptr || !(flags & GIST_STEP_TRAIN) || n <= 0) return 0;
-    const bool fuse = p->fuse != 0 && n <= p->n_max;
-    if (!fuse || p->col_partials == nullptr || !aligned16(p->col_partials)) return 0;
-    const FusedLayout fl = fused_layout(p, static_cast<char *>(p->fused_workspace), p->col_partials);
-    const bool defer = p->fused_workspace == nullptr ? fl.bytes == 0
-                                                     : (aligned16(p->fused_workspace) && fl.bytes <= p->fused_workspace_bytes);
-    // (beside a LARGE optimiser pass the extraction's 1024-thread workgroups cost more than they hide: each holds half a
-    // CU's wave slots for the ~20 us of its look-back chain -- 233 against 199 + 21 us at 38.8 M parameters, 32 against
-    // 16 + 21 at 1.2 M.  With the aggregating extraction's loads restructured the break-even is at ~11 M: H = 2048,
-    // 11.0 M parameters, 0.9788 / 0.9822 ms per step against 0.9807 / 0.9836 without; H = 4096, 38.8 M: +70 us)
-    if (p->n_params > kPrefetchMaxParams) return 0;
-    return defer && next_parts_ok(p, fuse) ? 1 : 0;
+    if (p == nullptr || !(flags & GIST_STEP_TRAIN) || n <= 0 || p->n_layers < 1 || p->n_layers > GIST_MAX_LAYERS) return 0;
+    return prefetches_next(p, decide(p, n, 0, flags)) ? 1 : 0;
 }
 
-extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64_t n,
-                              uint64_t drop_offset, float lr, float beta1, float beta2,
-                              float eps, float weight_decay, int64_t adam_step, int flags,
+extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64_t n, uint64_t drop_offset, float lr,
+                              float beta1, float beta2, float eps, float weight_decay, int64_t adam_step, int flags,
                               gist_stream_t s) {
+    // ---- validation: all of it before any device work -------------------------------------------------
     GIST_REQUIRE(p != nullptr, "gist_sage_step: null plan");
     GIST_REQUIRE(p->n_layers >= 1 && p->n_layers <= GIST_MAX_LAYERS, "gist_sage_step: bad n_layers");
     GIST_REQUIRE(n > 0, "gist_sage_step: empty batch");
@@ -401,593 +962,21 @@ extern "C" int gist_sage_step(const gist_step_plan *p, const int32_t *ids, int64
                  "gist_sage_step: GIST_STEP_EXTRACT and GIST_STEP_PREEXTRACTED exclude each other");
     GIST_REQUIRE(!(flags & (GIST_STEP_EXTRACT_NEXT | GIST_STEP_PREEXTRACTED)) || (flags & GIST_STEP_TRAIN),
                  "gist_sage_step: GIST_STEP_EXTRACT_NEXT / GIST_STEP_PREEXTRACTED belong to training steps");
-    const int L1 = p->n_layers;
-    hipStream_t st = as_stream(s);
-    ActiveTimer active(p->timer);
-    const bool train = (flags & GIST_STEP_TRAIN) != 0;
-    const bool drop = train && p->p_drop > 0.f;
-    // Phases (gist_hip.h, GIST_STEP_PHASE_*): a caller whose loop is `pred = model(g); loss = f(pred); loss.backward();
-    // optimizer.step()` issues the same iteration as three calls.  Every decision below is a function of (plan, n,
-    // drop_offset, flags without the phase bits), so the three calls agree on it.
-    const int phase_bits = flags & (GIST_STEP_PHASE_FORWARD | GIST_STEP_PHASE_BACKWARD | GIST_STEP_PHASE_OPTIMIZER);
-    GIST_REQUIRE(phase_bits == 0 || train, "gist_sage_step: GIST_STEP_PHASE_* belong to training steps");
-    GIST_REQUIRE(!(flags & GIST_STEP_DLOGITS_GIVEN) || phase_bits == GIST_STEP_PHASE_BACKWARD,
+    const int phases = flags & kPhaseBits;
+    GIST_REQUIRE(phases == 0 || (flags & GIST_STEP_TRAIN), "gist_sage_step: GIST_STEP_PHASE_* belong to training steps");
+    GIST_REQUIRE(!(flags & GIST_STEP_DLOGITS_GIVEN) || phases == GIST_STEP_PHASE_BACKWARD,
                  "gist_sage_step: GIST_STEP_DLOGITS_GIVEN belongs to a GIST_STEP_PHASE_BACKWARD call");
-    const bool do_fwd = phase_bits == 0 || (phase_bits & GIST_STEP_PHASE_FORWARD);
-    const bool do_bwd = train && (phase_bits == 0 || (phase_bits & GIST_STEP_PHASE_BACKWARD));
-    const bool do_opt = train && (phase_bits == 0 || (phase_bits & GIST_STEP_PHASE_OPTIMIZER));
-    const bool split_phases = phase_bits != 0 && phase_bits != (GIST_STEP_PHASE_FORWARD | GIST_STEP_PHASE_BACKWARD |
-                                                                GIST_STEP_PHASE_OPTIMIZER);
-    GIST_REQUIRE(!split_phases || ((do_fwd ? 1 : 0) + (do_bwd ? 1 : 0) + (do_opt ? 1 : 0)) == 1,
-                 "gist_sage_step: one GIST_STEP_PHASE_* per call (or none / all three)");
-    const bool dlogits_given = (flags & GIST_STEP_DLOGITS_GIVEN) != 0;
-    const bool blocked = p->row_blocks != nullptr && p->n_row_blocks > 0;
-    const bool pairs = p->sibling_parts != 0;      // may the batch have sibling blocks (speed only: gist_hip.h)
+    GIST_REQUIRE(__builtin_popcount(phases) != 2, "gist_sage_step: one GIST_STEP_PHASE_* per call (or none / all three)");
+    const bool extracts = (flags & GIST_STEP_EXTRACT) && (phases == 0 || (phases & GIST_STEP_PHASE_FORWARD));
+    GIST_REQUIRE(!extracts || ids != nullptr, "gist_sage_step: null ids");
 
-    // Split operands kept by the step (see gist_step_plan.h3_workspace); off = per-call splits
-    // inside gist_gemm_*.
-    const int gemm_mode = gist_gemm_get_mode();
-    H3Step h3{};
-    if (p->h3_workspace != nullptr && aligned16(p->h3_workspace) && n <= p->n_max) {
-        h3 = h3_layout(p, static_cast<char *>(p->h3_workspace), gemm_mode);
-        if (h3.bytes > p->h3_workspace_bytes) h3 = H3Step{};
-    }
-    B3Step b3{};
-    if (p->h3_workspace != nullptr && aligned16(p->h3_workspace) && n <= p->n_max) {
-        b3 = b3_layout(p, static_cast<char *>(p->h3_workspace), gemm_mode);
-        if (b3.bytes > p->h3_workspace_bytes) b3 = B3Step{};
-    }
-
-    // ---- the fused sequence (gist_step_plan.fuse): what each layer folds ----------------------------
-    const bool fuse = p->fuse != 0 && n <= p->n_max;
-    FusedLayout fl{};
-    bool defer = false;            // slabs + chunk sums consumed by the loss kernel / the optimiser
-    if (fuse && p->col_partials != nullptr && aligned16(p->col_partials)) {
-        fl = fused_layout(p, static_cast<char *>(p->fused_workspace), p->col_partials);
-        defer = p->fused_workspace == nullptr ? fl.bytes == 0
-                                              : (aligned16(p->fused_workspace) && fl.bytes <= p->fused_workspace_bytes);
-        if (!defer) fl = FusedLayout{};
-    }
-    uint64_t offs[GIST_MAX_LAYERS];
-    {
-        uint64_t off = drop_offset;
-        for (int k = 0; k < L1; ++k) {
-            offs[k] = off;
-            if (drop) off += round_up2((uint64_t)n * 2 * p->layer[k].n_in);
-        }
-    }
-    bool plain[GIST_MAX_LAYERS], fwd_fold[GIST_MAX_LAYERS], bwd_fold[GIST_MAX_LAYERS];
-    for (int k = 0; k < L1; ++k) {
-        const gist_layer_desc &l = p->layer[k];
-        plain[k] = !h3.layer[k].on && !b3.layer[k].on;
-        // forward: dropout([h | ah]) written by the producers, the aggregation reads hsrc[k]
-        fwd_fold[k] = fuse && drop && plain[k] && p->hsrc[k] != nullptr && (offs[k] & 1) == 0 &&
-                      (k > 0 || (flags & (GIST_STEP_EXTRACT | GIST_STEP_PREEXTRACTED))) &&
-                      p->ld_hsrc[k] >= l.n_in &&
-                      spmm_drop_takes(1, l.n_in, p->ld_hsrc[k], l.ldz, p->hsrc[k], l.Z + l.n_in, blocked ? p->row_blocks : nullptr);
-        // backward: the mask of dZ_k applied by the reverse aggregation as it reads dZ_k
-        bwd_fold[k] = fuse && drop && plain[k] && k > 0 && k < L1 - 1 && (offs[k] & 1) == 0 &&
-                      spmm_drop_takes(2, l.n_in, 2 * l.n_in, 2 * l.n_in, p->dZ + l.n_in, p->dZ, blocked ? p->row_blocks : nullptr);
-    }
-    const float keep = drop ? 1.0f / (1.0f - p->p_drop) : 1.f;
-    const uint64_t sm = p->seed * 0x9E3779B97F4A7C15ULL;
-    // the class layer as gist_class_layer_f32 + gist_class_dw_slabs_f32 (projection, CE, dZ with its mask and the
-    // bias gradient's chunk sums in one launch, dW as slabs for the optimiser) instead of four launches
-    bool cls_fused = false;
-    {
-        const gist_layer_desc &l = p->layer[L1 - 1];
-        cls_fused = train && defer && plain[L1 - 1] && p->ldc <= 64 && (offs[L1 - 1] & 1) == 0 &&
-                    (int)tune(GIST_TUNE_CLASS_FUSED) != 1 &&
-                    gist_class_layer_takes(n, l.n_out, 2 * l.n_in, l.ldz, 2 * l.n_in, l.Z, l.W) == 1 &&
-                    fl.dw_slabs[L1 - 1] != nullptr &&
-                    fl.dw_bytes[L1 - 1] >= gist_class_dw_slab_bytes(n, l.n_out, 2 * l.n_in);
-    }
-    // layers on split operands (their dZ comes from a split projection, unmasked): can the reverse aggregation
-    // carry dZ_k's mask instead of a dropout pass over dZ_k?
-    bool bwd_fold_split[GIST_MAX_LAYERS];
-    for (int k = 0; k < L1; ++k) {
-        const gist_layer_desc &l = p->layer[k];
-        bwd_fold_split[k] = fuse && drop && !plain[k] && k > 0 && k < L1 - 1 && (offs[k] & 1) == 0 &&
-                            spmm_drop_takes(2, l.n_in, 2 * l.n_in, 2 * l.n_in, p->dZ + l.n_in, p->dZ,
-                                            blocked ? p->row_blocks : nullptr);
-    }
-
-    if (b3.any && do_fwd) {      // this step's weights, one read each, one launch for all of them
-        Scope sc(p->timer, 3, 0, 0, 0, st);
-        B3Dual jobs[GIST_MAX_LAYERS];
-        int n_jobs = 0;
-        for (int k = 0; k < L1; ++k) {
-            const B3Layer &hl = b3.layer[k];
-            if (!hl.on) continue;
-            const gist_layer_desc &l = p->layer[k];
-            B3Dual &d = jobs[n_jobs++];
-            d = B3Dual{};
-            d.src = l.W; d.ld = 2 * l.n_in; d.rows = l.n_out; d.cols = 2 * l.n_in;
-            d.dst_r = hl.Ws;
-            d.dst_t = train ? hl.WsT : nullptr;
-        }
-        for (int i = 0; i < n_jobs; i += B3_SPLIT_MAX_JOBS)
-            GIST_TRY(b3_split_jobs(jobs + i, n_jobs - i < B3_SPLIT_MAX_JOBS ? n_jobs - i : B3_SPLIT_MAX_JOBS, st));
-    }
-    if (h3.any && do_fwd) {      // this step's weights: rows split for Y = Z.W^T, transposed for dZ = dY.W
-        Scope sc(p->timer, 3, 0, 0, 0, st);
-        bool zeroed = false;
-        for (int k = 0; k < L1; ++k) {
-            const H3Layer &hl = h3.layer[k];
-            if (!hl.on) continue;
-            const gist_layer_desc &l = p->layer[k];
-            if (k > 0 && train) {      // one read of W_k, one scale for the tensor, both layouts
-                if (!zeroed) {
-                    if (hipMemsetAsync(h3.amax, 0, GIST_MAX_LAYERS * 4, st) != hipSuccess) {
-                        set_error("gist_sage_step: hipMemsetAsync failed");
-                        return GIST_ELAUNCH;
-                    }
-                    zeroed = true;
-                }
-                GIST_TRY(h3_absmax(l.W, 2 * l.n_in, l.n_out, 2 * l.n_in, h3.amax + k, st));
-                H3Dual d{};
-                d.src = l.W; d.ld = 2 * l.n_in; d.rows = l.n_out; d.cols = 2 * l.n_in;
-                d.amax = h3.amax + k;
-                d.dst_r = hl.Ws; d.inv_r = hl.inv_wr; d.dst_t = hl.WsT; d.inv_t = hl.inv_wt;
-                GIST_TRY(h3_dual_split(d, st));
-            } else {
-                GIST_TRY(h3_split_rows(l.W, 2 * l.n_in, l.n_out, 2 * l.n_in, hl.Ws, hl.inv_wr, st));
-            }
-        }
-    }
-
-    // layer 0's aggregation formed by the extraction (this call's, or the previous call's GIST_STEP_EXTRACT_NEXT)?
-    bool pre_ah = (flags & GIST_STEP_PREEXTRACTED) && p->feat_intra != nullptr;
-    if ((flags & GIST_STEP_EXTRACT) && do_fwd) {      // (pre_ah only matters to the forward loop)
-        GIST_REQUIRE(ids != nullptr, "gist_sage_step: null ids");
-        const gist_layer_desc &l0 = p->layer[0];
-        const bool by_parts = fuse && p->node_part && p->part_slot && p->extract_scratch && p->batch_index >= 0 && n <= p->n_max &&
-                              gist_extract_parts_supported(p->n_max) == 1;
-        if (by_parts) {
-            gist_extract_parts_desc x{};
-            x.g_rowptr = p->g_rowptr; x.g_col = p->g_col; x.g_t_rowptr = p->g_t_rowptr; x.g_t_col = p->g_t_col;
-            x.ids = ids; x.n = n; x.n_max = p->n_max;
-            x.node_part = p->node_part; x.part_slot = p->part_slot; x.batch = p->batch_index;
-            x.rowptr = p->rowptr; x.col = p->col; x.t_rowptr = p->t_rowptr; x.t_col = p->t_col;
-            x.col_capacity = p->col_capacity; x.norm = p->norm;
-            x.feat = p->feat; x.ld_feat = p->ld_feat; x.n_feat = l0.n_in; x.z0 = l0.Z; x.ldz0 = l0.ldz;
-            x.labels_all = p->labels_all; x.labels = p->labels;
-            x.x0 = fwd_fold[0] ? p->hsrc[0] : nullptr; x.ldx0 = p->ld_hsrc[0]; x.p = p->p_drop; x.seed = p->seed;
-            x.offset = offs[0]; x.mask_ld = 2 * l0.n_in; x.scratch = p->extract_scratch;
-            if (p->feat_intra != nullptr) {      // layer 0's aggregation comes with the extraction
-                x.feat_intra = p->feat_intra; x.ld_intra = p->ld_feat_intra; x.ah = l0.Z + l0.n_in;
-                pre_ah = true;
-            }
-            GIST_TRY(gist_extract_parts_desc_batch(&x, s));
-        } else if (fwd_fold[0])
-            GIST_TRY(gist_extract_batch_drop(p->g_rowptr, p->g_col, p->g_t_rowptr, p->g_t_col, ids, n,
-                                             p->remap, p->rowptr, p->col, p->t_rowptr, p->t_col,
-                                             p->col_capacity, p->norm, p->feat, p->ld_feat, l0.n_in, l0.Z,
-                                             l0.ldz, p->labels_all, p->labels, p->hsrc[0], p->ld_hsrc[0],
-                                             p->p_drop, p->seed, offs[0], 2 * l0.n_in, s));
-        else
-            GIST_TRY(gist_extract_batch(p->g_rowptr, p->g_col, p->g_t_rowptr, p->g_t_col, ids, n,
-                                        p->remap, p->rowptr, p->col, p->t_rowptr, p->t_col,
-                                        p->col_capacity, p->norm, p->feat, p->ld_feat,
-                                        l0.n_in, l0.Z, l0.ldz, p->labels_all, p->labels, s));
-    }
-
-    // ---- block structure of the batch, once for all its aggregations ----------------
-    const void *prep_fwd = nullptr, *prep_bwd = nullptr;
-    if (blocked && p->spmm_prepared != nullptr && aligned16(p->spmm_prepared)) {
-        const int64_t one = gist_spmm_blocks_bytes(p->n_row_blocks);
-        bool wide = false;      // is there an aggregation the prepared kernel takes?
-        for (int k = 0; k < L1; ++k)
-            wide = wide || spmm_prepared_takes(p->layer[k].n_in, p->layer[k].ldz, p->layer[k].ldz,
-                                               p->layer[k].Z, p->layer[k].Z + p->layer[k].n_in);
-        if (wide && p->spmm_prepared_bytes >= (train ? 2 : 1) * one) {
-            char *base = static_cast<char *>(p->spmm_prepared);
-            if (do_fwd)
-            GIST_TRY(launch_spmm_blocks_prepare(p->rowptr, p->col, train ? p->t_rowptr : nullptr,
-                                                train ? p->t_col : nullptr, n, p->row_blocks, p->n_row_blocks,
-                                                base, train ? base + one : nullptr, st, pairs));
-            prep_fwd = base;
-            prep_bwd = train ? base + one : nullptr;
-        }
-    }
-
-    // ---- forward (modules.py:310-314 / :218-237) ---------------------------------
-    int logit_slabs = 0;           // > 1: the class layer's logits are still split-K slabs
-    for (int k = 0; k < L1 && do_fwd; ++k) {
-        const gist_layer_desc &l = p->layer[k];
-        int y_slabs_n = 1;                   // > 1: this layer's pre-norm output is still split-K slabs
-        const float *y_slabs = nullptr;
-        if (!(k == 0 && pre_ah)) {
-            Scope sc(p->timer, 0, n, n, l.n_in, st);
-            if (fwd_fold[k]) {      // source = the undropped input, store = dropout(ah)
-                SpmmDrop dr{};
-                dr.mode = 1; dr.p = p->p_drop; dr.scale = keep; dr.sm = sm;
-                dr.y_base = offs[k] + (uint64_t)l.n_in; dr.src_base = 0; dr.ld = 2 * l.n_in;
-                GIST_TRY(spmm_drop(p->rowptr, p->col, p->hsrc[k], p->ld_hsrc[k], l.Z + l.n_in, l.ldz, n, l.n_in,
-                                   p->norm, nullptr, 0, blocked ? p->row_blocks : nullptr, p->n_row_blocks, dr, st,
-                                   prep_fwd, pairs));
-            } else {
-                GIST_TRY(step_spmm(p, p->rowptr, p->col, l.Z, l.ldz, l.Z + l.n_in, l.ldz, n, l.n_in,
-                                   p->norm, nullptr, 0, prep_fwd, s));
-            }
-        }
-        if (h3.layer[k].on) {
-            // dropout + split of Z_k in one pass (both layouts when training); the dropped
-            // fp32 Z_k is never written: the backward only needs its transposed split
-            const H3Layer &hl = h3.layer[k];
-            Scope sc(p->timer, 1, n, l.n_out, 2 * l.n_in, st);
-            H3Dual d{};
-            d.src = l.Z; d.ld = l.ldz; d.rows = n; d.cols = 2 * l.n_in;
-            d.p = drop ? p->p_drop : 0.f; d.seed = p->seed; d.offset = offs[k];
-            d.fixed_shift = hl.shift;
-            d.dst_r = hl.Zs; d.inv_r = hl.inv_zr;
-            d.dst_t = train ? hl.ZsT : nullptr; d.inv_t = hl.inv_zt;
-            GIST_TRY(h3_dual_split(d, st));
-            GIST_TRY(h3_gemm_presplit("gist_sage_step", hl.Zs, hl.inv_zr, hl.Ws, hl.inv_wr, l.b, l.Y,
-                                      l.ldy, n, l.n_out, 2 * l.n_in, st));
-        } else if (b3.layer[k].on) {
-            const B3Layer &hl = b3.layer[k];
-            Scope sc(p->timer, 1, n, l.n_out, 2 * l.n_in, st);
-            B3Dual d{};
-            d.src = l.Z; d.ld = l.ldz; d.rows = n; d.cols = 2 * l.n_in;
-            d.p = drop ? p->p_drop : 0.f; d.seed = p->seed; d.offset = offs[k];
-            d.dst_r = hl.Zs;
-            d.dst_t = train ? hl.ZsT : nullptr;
-            GIST_TRY(b3_dual_split(d, st));
-            // (a hidden layer's k slices stay slabs: its LayerNorm, the next launch, sums them as it reads)
-            // (with one slice the kernel adds the bias itself; slabs get it from the LayerNorm)
-            const bool to_ln = defer && k + 1 < L1;
-            GIST_TRY(b3_gemm_presplit("gist_sage_step", hl.Zs, hl.Ws, l.b, l.Y, l.ldy, n, l.n_out,
-                                      2 * l.n_in, b3.slabs, b3.slab_bytes, st, to_ln ? &y_slabs_n : nullptr));
-            if (to_ln) y_slabs = b3.slabs;
-        } else {
-            if (drop && !fwd_fold[k])
-                GIST_TRY(gist_dropout_f32(l.Z, l.ldz, n, 2 * l.n_in, p->p_drop, p->seed, offs[k], s));
-            if (cls_fused && k == L1 - 1) continue;      // (projection, loss and dZ follow in one launch)
-            Scope sc(p->timer, 1, n, l.n_out, 2 * l.n_in, st);
-            if (defer && k == L1 - 1 && fl.logit_slabs != nullptr) {      // the loss kernel sums the slabs
-                GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
-                                    fl.logit_slabs, fl.logit_bytes, &logit_slabs, st));
-            } else if (defer && k + 1 < L1 && fl.y_slabs != nullptr && !h3_eligible(n, l.n_out, 2 * l.n_in) &&
-                       !b3_eligible(n, l.n_out, 2 * l.n_in)) {
-                // the LayerNorm sums the slabs (a projection the per-call split paths take keeps their workspace)
-                GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
-                                    fl.y_slabs, fl.y_bytes, &y_slabs_n, st));
-                y_slabs = fl.y_slabs;
-            } else {
-                GIST_TRY(gist_gemm_nt_f32(l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out,
-                                          2 * l.n_in, p->workspace, p->workspace_bytes, s));
-            }
-        }
-        if (k + 1 < L1) {
-            const gist_layer_desc &nx = p->layer[k + 1];
-            if (y_slabs_n > 1)
-                GIST_TRY(gist_ln_relu_fwd_slabs_f32(l.Y, l.ldy, y_slabs, n * l.n_out, y_slabs_n, l.b, nx.Z, nx.ldz,
-                                                    fwd_fold[k + 1] ? p->hsrc[k + 1] : nullptr,
-                                                    fwd_fold[k + 1] ? p->ld_hsrc[k + 1] : 0,
-                                                    p->use_layernorm ? l.rstd : nullptr, n, l.n_out,
-                                                    p->use_layernorm, 1, 1e-5f, fwd_fold[k + 1] ? p->p_drop : 0.f,
-                                                    p->seed, fwd_fold[k + 1] ? offs[k + 1] : 0,
-                                                    fwd_fold[k + 1] ? 2 * nx.n_in : l.n_out, s));
-            else if (fwd_fold[k + 1])
-                GIST_TRY(gist_ln_relu_fwd_drop_f32(l.Y, l.ldy, nx.Z, nx.ldz, p->hsrc[k + 1], p->ld_hsrc[k + 1],
-                                                   p->use_layernorm ? l.rstd : nullptr, n, l.n_out,
-                                                   p->use_layernorm, 1, 1e-5f, p->p_drop, p->seed,
-                                                   offs[k + 1], 2 * nx.n_in, s));
-            else
-                GIST_TRY(gist_ln_relu_fwd_f32(l.Y, l.ldy, nx.Z, nx.ldz,
-                                              p->use_layernorm ? l.rstd : nullptr, n, l.n_out,
-                                              p->use_layernorm, 1, 1e-5f, s));
-        }
-    }
-    const gist_layer_desc &last = p->layer[L1 - 1];
-    // the optimiser kernel reduces the loss when it runs with deferred work anyway
-    const bool loss_in_adam = train && defer;
-    if (!do_fwd) {
-    } else if (cls_fused) {
-        Scope sc(p->timer, 1, n, (L1 > 1 ? 2 : 1) * last.n_out, 2 * last.n_in, st);
-        GIST_TRY(gist_class_layer_f32(last.Z, last.ldz, last.W, 2 * last.n_in, last.b, p->labels, n, last.Y, last.ldy,
-                                      p->dlogits, p->ldc, p->row_loss, L1 > 1 ? p->dZ : nullptr, 2 * last.n_in,
-                                      drop ? p->p_drop : 0.f, p->seed, offs[L1 - 1], fl.partials[L1 - 1], n,
-                                      last.n_out, 2 * last.n_in, s));
-    } else
-    GIST_TRY(softmax_xent_ex("gist_sage_step", last.Y, last.ldy, logit_slabs > 1 ? fl.logit_slabs : nullptr,
-                             n * last.n_out, logit_slabs > 1 ? logit_slabs : 0, last.b, p->labels, nullptr, n,
-                             p->row_loss, loss_in_adam ? nullptr : p->loss, p->dlogits, p->ldc, n,
-                             last.n_out, st));
-    if (!train) return GIST_OK;
-    // a forward-phase call leaves the loss complete: its optimiser launch is another call
-    if (do_fwd && split_phases && loss_in_adam) GIST_TRY(loss_finish(p->row_loss, n, n, p->loss, st));
-
-    // ---- backward --------------------------------------------
-    // GIST_STEP_DLOGITS_GIVEN: plan->dlogits was written by the caller (any loss on the logits): the class layer's dZ and
-    // bias chunk sums of the fused forward belong to ANOTHER dlogits and are recomputed from the given one
-    const bool cls_dz_done = cls_fused && !dlogits_given;
-    gist_grad_segment segs[2 * GIST_MAX_LAYERS];
-    int n_segs = 0;
-    const int64_t chunks16 = gist_row_chunks16(n);
-    int64_t lnb_rows = 0;           // > 0: the layer below got its LayerNorm backward (and that many rows of partial sums) from
-                                    // the reverse aggregation just launched
-    auto bias_segment = [&](int k, int64_t rows) {      // db_k = chunk sums, formed by the optimiser
-        const gist_layer_desc &l = p->layer[k];
-        gist_grad_segment &g = segs[n_segs++];
-        g.begin = l.db - p->grads; g.end = g.begin + l.n_out;
-        g.src = fl.partials[k]; g.stride = l.n_out; g.n_src = (int32_t)rows;
-    };
-    ClassDwArgs dw_args{};          // the class layer's weight-gradient slabs, deferred to the LayerNorm backward below it
-    bool dw_pending = false;
-    for (int k = L1 - 1; k >= 0 && do_bwd; --k) {
-        const gist_layer_desc &l = p->layer[k];
-        const float *dy;
-        int64_t lddy;
-        bool db_done = false;      // this layer's bias gradient is already in chunks
-        const int64_t db_rows = lnb_rows > 0 ? lnb_rows : chunks16;
-        if (k == L1 - 1) {
-            dy = p->dlogits;
-            lddy = p->ldc;
-        } else {
-            const int64_t i_next = p->layer[k + 1].n_in;      // == l.n_out
-            if (lnb_rows > 0) {      // (came with the reverse aggregation of layer k + 1)
-                db_done = true;
-                lnb_rows = 0;
-            } else if (defer && plain[k]) {
-                if (dw_pending) {      // ... with the class layer's weight-gradient slabs in the same grid
-                    GIST_TRY(ln_relu_bwd_colsum_class_dw(p->dZ, 2 * i_next, l.Y, l.ldy, p->use_layernorm ? l.rstd : nullptr,
-                                                         l.Y, l.ldy, n, l.n_out, p->use_layernorm, 1, fl.partials[k], dw_args,
-                                                         st));
-                    dw_pending = false;
-                } else {
-                    GIST_TRY(ln_relu_bwd_colsum(p->dZ, 2 * i_next, l.Y, l.ldy, p->use_layernorm ? l.rstd : nullptr,
-                                                l.Y, l.ldy, n, l.n_out, p->use_layernorm, 1, fl.partials[k], st));
-                }
-                db_done = true;
-            } else {
-                GIST_TRY(ln_relu_bwd_ex(p->dZ, 2 * i_next, l.Y, l.ldy,
-                                        p->use_layernorm ? l.rstd : nullptr, l.Y, l.ldy, n, l.n_out,
-                                        p->use_layernorm, 1, h3.layer[k].on ? h3.rowmax : nullptr, st));
-            }
-            dy = l.Y;
-            lddy = l.ldy;
-        }
-        if (h3.layer[k].on) {
-            // bias gradient + column maxima of dY_k, one read of dY_k -> both split layouts
-            // (row maxima came from the LayerNorm backward), then dZ_k and dW_k on the splits
-            const H3Layer &hl = h3.layer[k];
-            GIST_TRY(colsum_ex(dy, lddy, n, l.n_out, p->partials, l.db, h3.pmax, h3.colmax, st));
-            {
-                Scope sc(p->timer, 3, 0, 0, 0, st);
-                H3Dual d{};
-                d.src = dy; d.ld = lddy; d.rows = n; d.cols = l.n_out;
-                d.rowmax = h3.rowmax; d.colmax = h3.colmax;
-                d.dst_r = k > 0 ? h3.dYs : nullptr; d.inv_r = h3.inv_dyr;
-                d.dst_t = h3.dYsT; d.inv_t = h3.inv_dyt;
-                GIST_TRY(h3_dual_split(d, st));
-            }
-            if (k > 0) {
-                Scope sc(p->timer, 1, n, 2 * l.n_in, l.n_out, st);
-                GIST_TRY(h3_gemm_presplit("gist_sage_step", h3.dYs, h3.inv_dyr, hl.WsT, hl.inv_wt,
-                                          nullptr, p->dZ, 2 * l.n_in, n, 2 * l.n_in, l.n_out, st));
-            }
-            {
-                Scope sc(p->timer, 1, l.n_out, 2 * l.n_in, n, st);
-                GIST_TRY(h3_gemm_presplit("gist_sage_step", h3.dYsT, h3.inv_dyt, hl.ZsT, hl.inv_zt,
-                                          nullptr, l.dW, 2 * l.n_in, l.n_out, 2 * l.n_in, n, st));
-            }
-            if (k > 0) {
-                if (bwd_fold_split[k]) {
-                    Scope sc(p->timer, 0, n, n, l.n_in, st);
-                    SpmmDrop dr{};
-                    dr.mode = 2; dr.p = p->p_drop; dr.scale = keep; dr.sm = sm;
-                    dr.y_base = offs[k]; dr.src_base = offs[k] + (uint64_t)l.n_in; dr.ld = 2 * l.n_in;
-                    GIST_TRY(spmm_drop(p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n,
-                                       l.n_in, nullptr, p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, prep_bwd,
-                                       pairs));
-                } else {
-                    if (drop)
-                        GIST_TRY(gist_dropout_f32(p->dZ, 2 * l.n_in, n, 2 * l.n_in, p->p_drop, p->seed,
-                                                  offs[k], s));
-                    Scope sc(p->timer, 0, n, n, l.n_in, st);
-                    GIST_TRY(step_spmm(p, p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ,
-                                       2 * l.n_in, n, l.n_in, nullptr, p->norm, 1, prep_bwd, s));
-                }
-            }
-            continue;
-        }
-        if (b3.layer[k].on) {
-            // bias gradient, then one read of dY_k -> both split layouts, dZ_k and dW_k on the splits
-            const B3Layer &hl = b3.layer[k];
-            {   // (the split's 64 x 64 tiles also give the bias gradient's per-chunk column sums)
-                Scope sc(p->timer, 3, 0, 0, 0, st);
-                B3Dual d{};
-                d.src = dy; d.ld = lddy; d.rows = n; d.cols = l.n_out;
-                d.dst_r = k > 0 ? b3.dYs : nullptr;
-                d.dst_t = b3.dYsT;
-                // (fused step: the tiles' column sums stay in the layer's own partials and the optimiser forms db_k from them
-                // -- 32 sources per element, a dedicated-block segment -- instead of a 5-us reduce launch per layer)
-                d.col_partials = defer && fl.partials[k] != nullptr ? fl.partials[k] : p->partials;
-                GIST_TRY(b3_dual_split(d, st));
-            }
-            if (defer && fl.partials[k] != nullptr) {
-                gist_grad_segment &g = segs[n_segs++];
-                g.begin = l.db - p->grads; g.end = g.begin + l.n_out;
-                g.src = fl.partials[k]; g.stride = l.n_out; g.n_src = (int32_t)gist_colsum_partials(n);
-            } else {
-                GIST_TRY(colsum_finish(p->partials, gist_colsum_partials(n), l.n_out, l.db, st));
-            }
-            if (k > 0) {
-                Scope sc(p->timer, 1, n, 2 * l.n_in, l.n_out, st);
-                GIST_TRY(b3_gemm_presplit("gist_sage_step", b3.dYs, hl.WsT, nullptr, p->dZ, 2 * l.n_in, n,
-                                          2 * l.n_in, l.n_out, b3.slabs, b3.slab_bytes, st));
-            }
-            {
-                Scope sc(p->timer, 1, l.n_out, 2 * l.n_in, n, st);
-                // the step's LAST projection may leave its k slices to the optimiser (the slab scratch is not
-                // reused before it runs)
-                int ns = 1;
-                GIST_TRY(b3_gemm_presplit("gist_sage_step", b3.dYsT, hl.ZsT, nullptr, l.dW, 2 * l.n_in,
-                                          l.n_out, 2 * l.n_in, n, b3.slabs, b3.slab_bytes, st,
-                                          defer && k == 0 ? &ns : nullptr));
-                if (ns > 1) {
-                    gist_grad_segment &g = segs[n_segs++];
-                    g.begin = l.dW - p->grads; g.end = g.begin + l.n_out * 2 * l.n_in;
-                    g.src = b3.slabs; g.stride = l.n_out * 2 * l.n_in; g.n_src = ns;
-                }
-            }
-            if (k > 0) {
-                if (bwd_fold_split[k]) {
-                    Scope sc(p->timer, 0, n, n, l.n_in, st);
-                    SpmmDrop dr{};
-                    dr.mode = 2; dr.p = p->p_drop; dr.scale = keep; dr.sm = sm;
-                    dr.y_base = offs[k]; dr.src_base = offs[k] + (uint64_t)l.n_in; dr.ld = 2 * l.n_in;
-                    GIST_TRY(spmm_drop(p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n,
-                                       l.n_in, nullptr, p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, prep_bwd,
-                                       pairs));
-                } else {
-                    if (drop)
-                        GIST_TRY(gist_dropout_f32(p->dZ, 2 * l.n_in, n, 2 * l.n_in, p->p_drop, p->seed,
-                                                  offs[k], s));
-                    Scope sc(p->timer, 0, n, n, l.n_in, st);
-                    GIST_TRY(step_spmm(p, p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ,
-                                       2 * l.n_in, n, l.n_in, nullptr, p->norm, 1, prep_bwd, s));
-                }
-            }
-            continue;
-        }
-        // dZ_k and dW_k of a narrow hidden layer read the same dY_k: one launch of the fp32 kernel's tiles for both
-        // (gist_gemm_nn_tn_dual_f32) when the mask of dZ_k is the reverse aggregation's business anyway
-        bool dual_done = false;
-        if (defer && k > 0 && k < L1 - 1 && db_done && (!drop || bwd_fold[k]) &&
-            gemm_dual_takes(n, 2 * l.n_in, l.n_out, lddy, 2 * l.n_in, l.ldz, 2 * l.n_in, dy, l.W, l.Z, p->dZ)) {
-            Scope sc(p->timer, 1, n, 4 * l.n_in, l.n_out, st);
-            int ns = 1;
-            GIST_TRY(gemm_dual_nn_tn("gist_sage_step", dy, lddy, l.W, 2 * l.n_in, p->dZ, 2 * l.n_in, l.Z, l.ldz, l.dW,
-                                     2 * l.n_in, n, 2 * l.n_in, l.n_out, fl.dw_slabs[k], fl.dw_bytes[k], &ns, st));
-            if (ns > 1) {
-                gist_grad_segment &g = segs[n_segs++];
-                g.begin = l.dW - p->grads; g.end = g.begin + l.n_out * 2 * l.n_in;
-                g.src = fl.dw_slabs[k]; g.stride = l.n_out * 2 * l.n_in; g.n_src = ns;
-            }
-            dual_done = true;
-        }
-        if (dual_done) {
-        } else if (cls_dz_done && k == L1 - 1) {
-            db_done = true;      // (dZ and the bias chunks came with the loss)
-        } else if (k > 0) {      // dZ with its dropout mask (or the mask left to the reverse aggregation)
-            Scope sc(p->timer, 1, n, 2 * l.n_in, l.n_out, st);
-            const bool chunk_db = defer && k == L1 - 1;      // the class layer's dZ kernel sees dlogits in 16-row chunks
-            GIST_TRY(gemm_nn_dropout_ex("gist_sage_step", dy, lddy, l.W, 2 * l.n_in, p->dZ, 2 * l.n_in, n,
-                                        2 * l.n_in, l.n_out, (drop && !bwd_fold[k]) ? p->p_drop : 0.f, p->seed,
-                                        offs[k], p->workspace, p->workspace_bytes,
-                                        chunk_db ? fl.partials[k] : nullptr, st));
-            db_done = db_done || chunk_db;
-        }
-        if (!dual_done) {
-            // The class layer's weight-gradient slabs need dlogits and the layer's input only; the LayerNorm backward of
-            // the layer below (next iteration of this loop, behind the reverse aggregation) runs 128 workgroups for ~6 us:
-            // the slabs' workgroups go into ITS grid (ln_relu_bwd_cs_dw_kernel) -- one launch fewer per step
-            const bool dw_with_ln = cls_fused && k == L1 - 1 && L1 >= 2 && defer && plain[L1 - 2] &&
-                                    (int)tune(GIST_TUNE_CLASS_FUSED) != 2;
-            Scope sc(dw_with_ln ? nullptr : p->timer, 1, l.n_out, 2 * l.n_in, n, st);
-            if (cls_fused && k == L1 - 1) {
-                int32_t ns = 1;
-                if (dw_with_ln) {
-                    GIST_TRY(class_dw_args("gist_sage_step", dy, lddy, l.Z, l.ldz, fl.dw_slabs[k], fl.dw_bytes[k], n, l.n_out,
-                                           2 * l.n_in, &dw_args, &ns));
-                    dw_pending = true;
-                } else {
-                    GIST_TRY(gist_class_dw_slabs_f32(dy, lddy, l.Z, l.ldz, fl.dw_slabs[k], fl.dw_bytes[k], &ns, n, l.n_out,
-                                                     2 * l.n_in, s));
-                }
-                gist_grad_segment &g = segs[n_segs++];
-                g.begin = l.dW - p->grads; g.end = g.begin + l.n_out * 2 * l.n_in;
-                g.src = fl.dw_slabs[k]; g.stride = l.n_out * 2 * l.n_in; g.n_src = ns;
-            } else if (defer && fl.dw_slabs[k] != nullptr) {      // the optimiser sums the slabs
-                int ns = 1;
-                GIST_TRY(gemm_slabs(2, dy, lddy, l.Z, l.ldz, nullptr, l.dW, 2 * l.n_in, l.n_out, 2 * l.n_in, n,
-                                    fl.dw_slabs[k], fl.dw_bytes[k], &ns, st));
-                if (ns > 1) {
-                    gist_grad_segment &g = segs[n_segs++];
-                    g.begin = l.dW - p->grads; g.end = g.begin + l.n_out * 2 * l.n_in;
-                    g.src = fl.dw_slabs[k]; g.stride = l.n_out * 2 * l.n_in; g.n_src = ns;
-                }
-            } else {
-                GIST_TRY(gist_gemm_tn_f32(dy, lddy, l.Z, l.ldz, l.dW, 2 * l.n_in, l.n_out,
-                                          2 * l.n_in, n, p->workspace, p->workspace_bytes, s));
-            }
-        }
-        if (defer) {
-            if (!db_done)      // (a one-layer model: no dZ kernel has seen dlogits)
-                GIST_TRY(colsum_rows16(dy, lddy, n, l.n_out, fl.partials[k], k == L1 - 1 ? false : true, st));
-            bias_segment(k, db_rows);
-        } else {
-            GIST_TRY(gist_colsum_f32(dy, lddy, n, l.n_out, p->partials, l.db, s));
-        }
-        if (k > 0) {
-            Scope sc(p->timer, 0, n, n, l.n_in, st);
-            if (bwd_fold[k]) {
-                SpmmDrop dr{};
-                dr.mode = 2; dr.p = p->p_drop; dr.scale = keep; dr.sm = sm;
-                dr.y_base = offs[k]; dr.src_base = offs[k] + (uint64_t)l.n_in; dr.ld = 2 * l.n_in;
-                // the LayerNorm + ReLU backward of layer k - 1 in this launch's store (its rows are whole in one wave)
-                const gist_layer_desc &lo = p->layer[k - 1];
-                SpmmLnBwd ln{};
-                const int64_t units = blocked ? spmm_lnb_units(p->n_row_blocks) : 0;
-                const bool with_ln = defer && plain[k - 1] && !dw_pending && (int)tune(GIST_TUNE_LNB_FUSED) != 1 &&
-                                     units > 0 && units <= fl.partial_rows[k - 1] && lo.ldy % 4 == 0 && aligned16(lo.Y) &&
-                                     (!p->use_layernorm || lo.rstd != nullptr) &&
-                                     spmm_lnb_takes(l.n_in, 2 * l.n_in, 2 * l.n_in, p->dZ + l.n_in, p->dZ, p->row_blocks, prep_bwd);
-                if (with_ln) {
-                    ln.yhat = lo.Y; ln.ldy = lo.ldy; ln.rstd = p->use_layernorm ? lo.rstd : nullptr;
-                    ln.dy = lo.Y; ln.lddy = lo.ldy; ln.col_partials = fl.partials[k - 1]; ln.relu = 1;
-                    lnb_rows = units;
-                }
-                GIST_TRY(spmm_drop(p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n,
-                                   l.n_in, nullptr, p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, prep_bwd,
-                                   pairs, with_ln ? &ln : nullptr));
-            } else {
-                GIST_TRY(step_spmm(p, p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ,
-                                   2 * l.n_in, n, l.n_in, nullptr, p->norm, 1, prep_bwd, s));
-            }
-        }
-    }
-    GIST_REQUIRE(!dw_pending, "gist_sage_step: internal error (class-layer weight gradient not launched)");
-    if (do_bwd && !do_opt) {
-        // the gradient arena complete on return (p.grad is read by the caller's optimiser, possibly by its own code first):
-        // the deferred sums in the optimiser's order, without the update
-        if (defer && n_segs > 0) GIST_TRY(gist_grad_segments_finish_f32(p->grads, p->n_params, segs, n_segs, s));
-        return GIST_OK;
-    }
-    if (!do_opt) return GIST_OK;
-    if (!do_bwd) n_segs = 0;      // (an optimiser-phase call: the backward-phase call finished the gradients)
-    const float *opt_row_loss = do_bwd || !split_phases ? p->row_loss : nullptr;      // (and the forward-phase call the loss)
-    if (defer && (flags & GIST_STEP_EXTRACT_NEXT) && next_parts_ok(p, fuse) && p->n_params <= kPrefetchMaxParams) {
-        // the optimiser and the NEXT batch's extraction in one grid: nothing reads the batch buffers any more.  Layer 0's
-        // mask goes into the next batch's feature gather under the rule the next call applies to itself (fwd_fold[0])
-        const gist_layer_desc &l0 = p->layer[0];
-        const bool fold0 = fuse && drop && plain[0] && p->hsrc[0] != nullptr && (p->next_drop_offset & 1) == 0 &&
-                           p->ld_hsrc[0] >= l0.n_in &&
-                           spmm_drop_takes(1, l0.n_in, p->ld_hsrc[0], l0.ldz, p->hsrc[0], l0.Z + l0.n_in,
-                                           blocked ? p->row_blocks : nullptr);
-        gist_extract_parts_desc x{};
-        x.g_rowptr = p->g_rowptr; x.g_col = p->g_col; x.g_t_rowptr = p->g_t_rowptr; x.g_t_col = p->g_t_col;
-        x.ids = p->next_ids; x.n = p->next_n; x.n_max = p->n_max;
-        x.node_part = p->node_part; x.part_slot = p->part_slot; x.batch = p->next_batch_index;
-        x.rowptr = p->rowptr; x.col = p->col; x.t_rowptr = p->t_rowptr; x.t_col = p->t_col;
-        x.col_capacity = p->col_capacity; x.norm = p->norm;
-        x.feat = p->feat; x.ld_feat = p->ld_feat; x.n_feat = l0.n_in; x.z0 = l0.Z; x.ldz0 = l0.ldz;
-        x.labels_all = p->labels_all; x.labels = p->labels;
-        x.x0 = fold0 ? p->hsrc[0] : nullptr; x.ldx0 = p->ld_hsrc[0]; x.p = p->p_drop; x.seed = p->seed;
-        x.offset = p->next_drop_offset; x.mask_ld = 2 * l0.n_in; x.scratch = p->extract_scratch;
-        if (p->feat_intra != nullptr) { x.feat_intra = p->feat_intra; x.ld_intra = p->ld_feat_intra; x.ah = l0.Z + l0.n_in; }
-        GIST_TRY(gist_adam_segments_extract_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1,
-                                                beta2, eps, weight_decay, adam_step, segs, n_segs, opt_row_loss, n, n,
-                                                p->loss, &x, s));
-    } else if (defer)
-        GIST_TRY(gist_adam_segments_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1,
-                                        beta2, eps, weight_decay, adam_step, segs, n_segs, opt_row_loss, n, n,
-                                        p->loss, s));
-    else
-        GIST_TRY(gist_adam_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1,
-                               beta2, eps, weight_decay, adam_step, s));
+    const StepDecisions d = decide(p, n, drop_offset, flags);
+    StepState x{};
+    ActiveTimer active(p->timer);
+    if (d.do_fwd) GIST_TRY(split_weights(p, d, as_stream(s)));
+    GIST_TRY(extract_and_prepare(p, d, x, ids, n, flags, s));
+    if (d.do_fwd) GIST_TRY(forward(p, d, x, n, s));
+    if (d.do_bwd) GIST_TRY(backward(p, d, x, n, s));
+    if (d.do_opt) GIST_TRY(optimise(p, d, x, n, AdamArgs{lr, beta1, beta2, eps, weight_decay, adam_step}, flags, s));
     return GIST_OK;
 }
