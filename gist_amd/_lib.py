@@ -143,6 +143,11 @@ SIGNATURES = {
                                          _p, _i64, _p, _p, _p]),
     'gist_gat_backward_src_f32': (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                          _p, _i64, _p, _p]),
+    'gist_gat_aggregate_cat_f32': (_int, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _int, _p, _i64, _p, _p, _p]),
+    'gist_gat_backward_dst_cat_f32': (_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64,
+                                             _int, _p, _i64, _p, _p, _p]),
+    'gist_gat_backward_src_cat_f32': (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
+                                             _p, _i64, _p, _p]),
     'gist_gat_attn_grad_workspace_floats': (_i64, [_i64, _i64, _i64]),
     'gist_gat_attn_grad_f32': (_int, [_p, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p]),
     'gist_gat_step_workspace_bytes': (_i64, [_p]),

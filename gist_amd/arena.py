@@ -106,11 +106,15 @@ class ParamArena(FlatArena):
         gcn.__dict__['_gist_arena'] = weakref.ref(self)
 
 
-def gat_dims(in_feats, n_hidden, n_classes, n_layers, n_heads):
-    """[(in, out, heads)] of the layers of gist_amd.modules.GAT(n_layers, in_feats, n_hidden, n_classes, n_heads): n_heads
-    heads in the first layer and in the n_layers - 2 middle ones, one head of width n_classes last."""
-    return ([(in_feats, n_hidden, n_heads)] + [(n_hidden, n_hidden, n_heads)] * max(n_layers - 2, 0) +
-            [(n_hidden, n_classes, 1)])
+def gat_dims(in_feats, n_hidden, n_classes, n_layers, n_heads, merge='mean'):
+    """[(in, out, heads)] of the layers of gist_amd.modules.GAT(n_layers, in_feats, n_hidden, n_classes, n_heads, merge):
+    n_heads heads in the first layer and in the n_layers - 2 middle ones, one head of width n_classes last.  With
+    merge='cat' the heads are concatenated: every layer after the first reads n_heads * n_hidden columns."""
+    if merge not in ('mean', 'cat'):
+        raise ValueError("gist_amd: merge must be 'mean' or 'cat' (got %r)" % (merge,))
+    wide = n_heads * n_hidden if merge == 'cat' else n_hidden
+    return ([(in_feats, n_hidden, n_heads)] + [(wide, n_hidden, n_heads)] * max(n_layers - 2, 0) +
+            [(wide, n_classes, 1)])
 
 
 def gat_params(gat):

@@ -38,10 +38,14 @@ def sage_layer(g, h, weight, bias, use_lynorm, relu, p_drop=0.0, seed=0):
     return out
 
 
-def gat_layer(g, h, weight, attn, elu=False):
+def gat_layer(g, h, weight, attn, elu=False, merge='mean'):
     """All heads of a GAT layer as one op: weight = the heads' fc weights stacked [H*F, in], attn = their attn_fc
-    weights stacked [H, 2F]; returns the per-node mean over heads [n, F], through ELU when `elu`."""
-    out = torch.ops.gist.gat_layer(g.rowptr, g.col, g.t_rowptr, g.t_col, h, weight, attn, bool(elu))[0]
+    weights stacked [H, 2F]; returns the per-node mean over heads [n, F], or with merge='cat' the heads side by side
+    [n, H*F]; through ELU when `elu`."""
+    if merge not in ('mean', 'cat'):
+        raise ValueError("gist_amd: merge must be 'mean' or 'cat' (got %r)" % (merge,))
+    out = torch.ops.gist.gat_layer(g.rowptr, g.col, g.t_rowptr, g.t_col, h, weight, attn, bool(elu),
+                                   merge == 'cat')[0]
     return out
 
 

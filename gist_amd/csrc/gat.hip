@@ -6,6 +6,8 @@
 //   e_hij = leaky_relu(s_src[j,h] + s_dst[i,h], 0.01)      for every in-edge j -> i (duplicates count)
 //   alpha_hij = softmax over the in-edges of i             agg_h[i] = sum_j alpha_hij z_h[j]   (0 without in-edges)
 //   out[i] = act((1/H) sum_h agg_h[i])                     act = ELU or identity
+// or, in the CAT instantiations (the heads concatenated, modules.py:87-89):
+//   out[i, hF:(h+1)F] = act(agg_h[i])                       [n, H*F]; G, the gradient into the heads, likewise
 //
 // Layout of the walkers: one wave per row; the wave's 64 lanes form 64 / LPG edge groups of LPG lanes, a group takes
 // every (64 / LPG)-th edge of the row and its lanes cover VEC consecutive columns each.  The groups' partial results
@@ -86,7 +88,10 @@ __global__ __launch_bounds__(256) void gat_scores_kernel(const float *__restrict
 }
 
 // Forward aggregation: out, and per (row, head) the softmax max M and denominator L (M = L = 0 without in-edges).
-template <int VEC, int LPG>
+// CAT: every head stores its own F columns of the [n, H*F] output (group 0, whole vectors) instead of adding to the mean.
+// Its head loop keeps the mean's shape (o starts at 0 and takes acc / l by the same +=), so that the compiler contracts
+// the online softmax's a x + b y as it does there and a head has the bits of a one-head layer.
+template <int VEC, int LPG, bool CAT>
 __global__ __launch_bounds__(256) void gat_aggregate_kernel(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ Z, int64_t ldz,
     const float *__restrict__ s_src, const float *__restrict__ s_dst, int64_t n, int H, int F, int elu,
@@ -110,6 +115,10 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(
             float m = -INFINITY, l = 0.f, acc[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+            if constexpr (CAT) {      // (no sum over heads: every head starts from 0, as a one-head layer does)
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) o[k] = 0.f;
+            }
             for (int e = e0 + grp; e < e1; e += G) {
                 const int j = col[e];
                 float s = s_src[(int64_t)j * H + h] + sd;
@@ -147,8 +156,15 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(
                 M[row * H + h] = l > 0.f ? m : 0.f;
                 L[row * H + h] = l;
             }
+            if constexpr (CAT) {
+                if (grp == 0 && active) {
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) o[k] = (elu && !(o[k] > 0.f)) ? expm1f(o[k]) : o[k];
+                    gat_store<VEC>(out + row * ldo + (int64_t)h * F + c, o);
+                }
+            }
         }
-        if (grp == 0 && active) {
+        if (!CAT && grp == 0 && active) {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 const float v = o[k] * inv_h;
@@ -160,25 +176,29 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(
 }
 
 // G[i, :] = d_out[i, :] * act'(out[i, :]) / H     (ELU: act' = 1 where out > 0, out + 1 elsewhere)
+// CAT: over the H*F columns of the concatenated output, and no division
+template <bool CAT>
 __global__ __launch_bounds__(256) void gat_grad_in_kernel(const float *__restrict__ d_out, int64_t ldg,
                                                           const float *__restrict__ out, int64_t ldo, int64_t n,
                                                           int F, int H, int elu, float *__restrict__ Gm,
                                                           int64_t ldgm) {
+    const int W = CAT ? H * F : F;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * F) return;
-    const int64_t r = t / F;
-    const int c = (int)(t - r * F);
+    if (t >= n * W) return;
+    const int64_t r = t / W;
+    const int c = (int)(t - r * W);
     float d = d_out[r * ldg + c];
     if (elu) {
         const float o = out[r * ldo + c];
         d *= o > 0.f ? 1.f : o + 1.f;
     }
-    Gm[r * ldgm + c] = d / (float)H;
+    Gm[r * ldgm + c] = CAT ? d : d / (float)H;
 }
 
 // Backward, destination pass over the in-edge CSR: with gz_hij = G[i] . z_h[j],
 //   A = sum_j alpha gz,  B = sum_j alpha lr' gz,  C = sum_j alpha lr'  ->  ds_dst[i,h] = B - A C,  D[i,h] = A
-template <int VEC, int LPG>
+// CAT: head h reads its own slice G[i, hF:(h+1)F] (here and in the source pass)
+template <int VEC, int LPG, bool CAT>
 __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ Z, int64_t ldz,
     const float *__restrict__ Gm, int64_t ldgm, const float *__restrict__ s_src, const float *__restrict__ s_dst,
@@ -190,8 +210,9 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
     const int64_t row = (int64_t)blockIdx.x * kGatRowsPerBlock + (threadIdx.x >> 6);
     if (row >= n) return;
     const int e0 = rowptr[row], e1 = rowptr[row + 1];
-    const float *gi = Gm + row * ldgm;
+    const float *g0 = Gm + row * ldgm;
     for (int h = 0; h < H; ++h) {
+        const float *gi = CAT ? g0 + (int64_t)h * F : g0;
         const float sd = s_dst[row * H + h];
         const float mi = M[row * H + h];
         const float li_ = L[row * H + h];
@@ -229,7 +250,7 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
 // Backward, source pass over the reversed CSR (row j, its out-edges j -> i):
 //   ds_src[j,h] = sum_i alpha_hij (gz_hij - D[i,h]) lr'_hij
 //   dZ[j, hF:(h+1)F] = sum_i alpha_hij G[i] + ds_src[j,h] a_src_h + ds_dst[j,h] a_dst_h
-template <int VEC, int LPG>
+template <int VEC, int LPG, bool CAT>
 __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
     const int32_t *__restrict__ t_rowptr, const int32_t *__restrict__ t_col, const float *__restrict__ Z,
     int64_t ldz, const float *__restrict__ Gm, int64_t ldgm, const float *__restrict__ A,
@@ -257,7 +278,7 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
                 const float lr = pre > 0.f ? 1.f : kGatSlope;
                 const float li_ = L[i * H + h];
                 const float alpha = expf(pre * lr - M[i * H + h]) / li_;
-                const float *gi = Gm + i * ldgm;
+                const float *gi = Gm + i * ldgm + (CAT ? (int64_t)h * F : 0);
                 float part = 0.f;
                 for (int c = li * VEC; c < F; c += LPG * VEC) {
                     float g[VEC], z[VEC];
@@ -348,21 +369,21 @@ static bool gat_vec4(int64_t F, std::initializer_list<int64_t> lds, std::initial
     return true;
 }
 
-#define GAT_DISPATCH(KERNEL, VEC4, LPG, GRID, ST, ...)                                               \
+#define GAT_DISPATCH(KERNEL, CAT, VEC4, LPG, GRID, ST, ...)                                               \
     do {                                                                                             \
         if (VEC4) {                                                                                  \
             switch (LPG) {                                                                           \
-            case 8: hipLaunchKernelGGL((KERNEL<4, 8>), GRID, dim3(256), 0, ST, __VA_ARGS__); break;   \
-            case 16: hipLaunchKernelGGL((KERNEL<4, 16>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
-            case 32: hipLaunchKernelGGL((KERNEL<4, 32>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((KERNEL<4, 64>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
+            case 8: hipLaunchKernelGGL((KERNEL<4, 8, CAT>), GRID, dim3(256), 0, ST, __VA_ARGS__); break;   \
+            case 16: hipLaunchKernelGGL((KERNEL<4, 16, CAT>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
+            case 32: hipLaunchKernelGGL((KERNEL<4, 32, CAT>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
+            default: hipLaunchKernelGGL((KERNEL<4, 64, CAT>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
             }                                                                                        \
         } else {                                                                                     \
             switch (LPG) {                                                                           \
-            case 8: hipLaunchKernelGGL((KERNEL<1, 8>), GRID, dim3(256), 0, ST, __VA_ARGS__); break;   \
-            case 16: hipLaunchKernelGGL((KERNEL<1, 16>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
-            case 32: hipLaunchKernelGGL((KERNEL<1, 32>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((KERNEL<1, 64>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
+            case 8: hipLaunchKernelGGL((KERNEL<1, 8, CAT>), GRID, dim3(256), 0, ST, __VA_ARGS__); break;   \
+            case 16: hipLaunchKernelGGL((KERNEL<1, 16, CAT>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
+            case 32: hipLaunchKernelGGL((KERNEL<1, 32, CAT>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
+            default: hipLaunchKernelGGL((KERNEL<1, 64, CAT>), GRID, dim3(256), 0, ST, __VA_ARGS__); break; \
             }                                                                                        \
         }                                                                                            \
     } while (0)
@@ -386,65 +407,131 @@ extern "C" int gist_gat_scores_f32(const float *Z, int64_t ldz, const float *A, 
     return launch_status("gist_gat_scores_f32");
 }
 
-extern "C" int gist_gat_aggregate_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
-                                      const float *s_src, const float *s_dst, int64_t n_rows, int64_t heads,
-                                      int64_t out_dim, int elu, float *out, int64_t ldo, float *M, float *L,
-                                      gist_stream_t stream) {
-    GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim && ldo >= out_dim,
-                 "gist_gat_aggregate_f32: bad sizes");
+// The three entry points that know how the heads are combined, once for both ways: CAT = false is the head mean
+// (gist_gat_*_f32), CAT = true the concatenation (gist_gat_*_cat_f32), where out, d_out and G are heads * out_dim wide.
+template <bool CAT>
+static int gat_aggregate(const char *who, const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+                         const float *s_src, const float *s_dst, int64_t n_rows, int64_t heads, int64_t out_dim,
+                         int elu, float *out, int64_t ldo, float *M, float *L, gist_stream_t stream) {
+    if constexpr (CAT) {      // (one head: nothing to concatenate, and the mean's * 1.0f is exact)
+        if (heads == 1)
+            return gat_aggregate<false>(who, rowptr, col, Z, ldz, s_src, s_dst, n_rows, heads, out_dim, elu, out, ldo, M,
+                                        L, stream);
+    }
+    GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim &&
+                     ldo >= (CAT ? heads * out_dim : out_dim),
+                 "%s: bad sizes", who);
     if (n_rows == 0) return GIST_OK;
     // (col is read only inside rowptr's ranges: it may be NULL for a graph without edges, as in gist_spmm_csr_f32)
-    GIST_REQUIRE(rowptr && Z && s_src && s_dst && out && M && L, "gist_gat_aggregate_f32: null pointer");
+    GIST_REQUIRE(rowptr && Z && s_src && s_dst && out && M && L, "%s: null pointer", who);
     const bool v4 = gat_vec4(out_dim, {ldz, ldo}, {Z, out});
     const int lpg = gat_lpg(out_dim, v4 ? 4 : 1);
     const dim3 grid((unsigned)ceil_div(n_rows, kGatRowsPerBlock));
-    GAT_DISPATCH(gat_aggregate_kernel, v4, lpg, grid, as_stream(stream), rowptr, col, Z, ldz, s_src, s_dst, n_rows,
-                 (int)heads, (int)out_dim, elu ? 1 : 0, out, ldo, M, L);
-    return launch_status("gist_gat_aggregate_f32");
+    GAT_DISPATCH(gat_aggregate_kernel, CAT, v4, lpg, grid, as_stream(stream), rowptr, col, Z, ldz, s_src, s_dst,
+                 n_rows, (int)heads, (int)out_dim, elu ? 1 : 0, out, ldo, M, L);
+    return launch_status(who);
 }
 
-extern "C" int gist_gat_backward_dst_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
-                                         const float *out, int64_t ldo, const float *d_out, int64_t ldg,
-                                         const float *s_src, const float *s_dst, const float *M, const float *L,
-                                         int64_t n_rows, int64_t heads, int64_t out_dim, int elu, float *G,
-                                         int64_t ldgm, float *ds_dst, float *D, gist_stream_t stream) {
-    GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim && ldg >= out_dim &&
-                     ldgm >= out_dim && (!elu || ldo >= out_dim),
-                 "gist_gat_backward_dst_f32: bad sizes");
+template <bool CAT>
+static int gat_backward_dst(const char *who, const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+                            const float *out, int64_t ldo, const float *d_out, int64_t ldg, const float *s_src,
+                            const float *s_dst, const float *M, const float *L, int64_t n_rows, int64_t heads,
+                            int64_t out_dim, int elu, float *G, int64_t ldgm, float *ds_dst, float *D,
+                            gist_stream_t stream) {
+    if constexpr (CAT) {      // (one head: the mean's / 1.0f is exact)
+        if (heads == 1)
+            return gat_backward_dst<false>(who, rowptr, col, Z, ldz, out, ldo, d_out, ldg, s_src, s_dst, M, L, n_rows,
+                                           heads, out_dim, elu, G, ldgm, ds_dst, D, stream);
+    }
+    const int64_t width = CAT ? heads * out_dim : out_dim;      // of out, d_out and G
+    GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim && ldg >= width && ldgm >= width &&
+                     (!elu || ldo >= width),
+                 "%s: bad sizes", who);
     if (n_rows == 0) return GIST_OK;
     GIST_REQUIRE(rowptr && Z && d_out && s_src && s_dst && M && L && G && ds_dst && D && (out || !elu),
-                 "gist_gat_backward_dst_f32: null pointer");
+                 "%s: null pointer", who);
     const hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(gat_grad_in_kernel, dim3((unsigned)ceil_div(n_rows * out_dim, 256)), dim3(256), 0, st, d_out,
-                       ldg, out, ldo, n_rows, (int)out_dim, (int)heads, elu ? 1 : 0, G, ldgm);
-    int rc = launch_status("gist_gat_backward_dst_f32 (grad_in)");
+    hipLaunchKernelGGL(gat_grad_in_kernel<CAT>, dim3((unsigned)ceil_div(n_rows * width, 256)), dim3(256), 0, st,
+                       d_out, ldg, out, ldo, n_rows, (int)out_dim, (int)heads, elu ? 1 : 0, G, ldgm);
+    int rc = launch_status(who);
     if (rc) return rc;
     const bool v4 = gat_vec4(out_dim, {ldz, ldgm}, {Z, G});
     const int lpg = gat_lpg(out_dim, v4 ? 4 : 1);
     const dim3 grid((unsigned)ceil_div(n_rows, kGatRowsPerBlock));
-    GAT_DISPATCH(gat_bwd_dst_kernel, v4, lpg, grid, st, rowptr, col, Z, ldz, G, ldgm, s_src, s_dst, M, L, n_rows,
+    GAT_DISPATCH(gat_bwd_dst_kernel, CAT, v4, lpg, grid, st, rowptr, col, Z, ldz, G, ldgm, s_src, s_dst, M, L, n_rows,
                  (int)heads, (int)out_dim, ds_dst, D);
-    return launch_status("gist_gat_backward_dst_f32");
+    return launch_status(who);
 }
 
-extern "C" int gist_gat_backward_src_f32(const int32_t *t_rowptr, const int32_t *t_col, const float *Z,
-                                         int64_t ldz, const float *G, int64_t ldgm, const float *A,
-                                         const float *s_src, const float *s_dst, const float *M, const float *L,
-                                         const float *D, const float *ds_dst, int64_t n_rows, int64_t heads,
-                                         int64_t out_dim, float *dZ, int64_t lddz, float *ds_src,
-                                         gist_stream_t stream) {
+template <bool CAT>
+static int gat_backward_src(const char *who, const int32_t *t_rowptr, const int32_t *t_col, const float *Z,
+                            int64_t ldz, const float *G, int64_t ldgm, const float *A, const float *s_src,
+                            const float *s_dst, const float *M, const float *L, const float *D, const float *ds_dst,
+                            int64_t n_rows, int64_t heads, int64_t out_dim, float *dZ, int64_t lddz, float *ds_src,
+                            gist_stream_t stream) {
+    if constexpr (CAT) {
+        if (heads == 1)
+            return gat_backward_src<false>(who, t_rowptr, t_col, Z, ldz, G, ldgm, A, s_src, s_dst, M, L, D, ds_dst,
+                                           n_rows, heads, out_dim, dZ, lddz, ds_src, stream);
+    }
     GIST_REQUIRE(gat_sizes_ok(n_rows, heads, out_dim) && ldz >= heads * out_dim && lddz >= heads * out_dim &&
-                     ldgm >= out_dim,
-                 "gist_gat_backward_src_f32: bad sizes");
+                     ldgm >= (CAT ? heads * out_dim : out_dim),
+                 "%s: bad sizes", who);
     if (n_rows == 0) return GIST_OK;
     GIST_REQUIRE(t_rowptr && Z && G && A && s_src && s_dst && M && L && D && ds_dst && dZ && ds_src,
-                 "gist_gat_backward_src_f32: null pointer");
+                 "%s: null pointer", who);
     const bool v4 = gat_vec4(out_dim, {ldz, ldgm, lddz}, {Z, G, dZ});
     const int lpg = gat_lpg(out_dim, v4 ? 4 : 1);
     const dim3 grid((unsigned)ceil_div(n_rows, kGatRowsPerBlock));
-    GAT_DISPATCH(gat_bwd_src_kernel, v4, lpg, grid, as_stream(stream), t_rowptr, t_col, Z, ldz, G, ldgm, A, s_src,
-                 s_dst, M, L, D, ds_dst, n_rows, (int)heads, (int)out_dim, dZ, lddz, ds_src);
-    return launch_status("gist_gat_backward_src_f32");
+    GAT_DISPATCH(gat_bwd_src_kernel, CAT, v4, lpg, grid, as_stream(stream), t_rowptr, t_col, Z, ldz, G, ldgm, A,
+                 s_src, s_dst, M, L, D, ds_dst, n_rows, (int)heads, (int)out_dim, dZ, lddz, ds_src);
+    return launch_status(who);
+}
+
+extern "C" int gist_gat_aggregate_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+    const float *s_src, const float *s_dst, int64_t n_rows, int64_t heads, int64_t out_dim, int elu, float *out,
+    int64_t ldo, float *M, float *L, gist_stream_t stream) {
+    return gat_aggregate<false>("gist_gat_aggregate_f32", rowptr, col, Z, ldz, s_src, s_dst, n_rows, heads, out_dim, elu, out,
+                              ldo, M, L, stream);
+}
+
+extern "C" int gist_gat_aggregate_cat_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+    const float *s_src, const float *s_dst, int64_t n_rows, int64_t heads, int64_t out_dim, int elu, float *out,
+    int64_t ldo, float *M, float *L, gist_stream_t stream) {
+    return gat_aggregate<true>("gist_gat_aggregate_cat_f32", rowptr, col, Z, ldz, s_src, s_dst, n_rows, heads, out_dim, elu, out,
+                             ldo, M, L, stream);
+}
+
+extern "C" int gist_gat_backward_dst_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+    const float *out, int64_t ldo, const float *d_out, int64_t ldg, const float *s_src, const float *s_dst,
+    const float *M, const float *L, int64_t n_rows, int64_t heads, int64_t out_dim, int elu, float *G, int64_t ldgm,
+    float *ds_dst, float *D, gist_stream_t stream) {
+    return gat_backward_dst<false>("gist_gat_backward_dst_f32", rowptr, col, Z, ldz, out, ldo, d_out, ldg, s_src, s_dst, M, L,
+                                 n_rows, heads, out_dim, elu, G, ldgm, ds_dst, D, stream);
+}
+
+extern "C" int gist_gat_backward_dst_cat_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+    const float *out, int64_t ldo, const float *d_out, int64_t ldg, const float *s_src, const float *s_dst,
+    const float *M, const float *L, int64_t n_rows, int64_t heads, int64_t out_dim, int elu, float *G, int64_t ldgm,
+    float *ds_dst, float *D, gist_stream_t stream) {
+    return gat_backward_dst<true>("gist_gat_backward_dst_cat_f32", rowptr, col, Z, ldz, out, ldo, d_out, ldg, s_src, s_dst, M, L,
+                                n_rows, heads, out_dim, elu, G, ldgm, ds_dst, D, stream);
+}
+
+extern "C" int gist_gat_backward_src_f32(const int32_t *t_rowptr, const int32_t *t_col, const float *Z, int64_t ldz,
+    const float *G, int64_t ldgm, const float *A, const float *s_src, const float *s_dst, const float *M, const float *L,
+    const float *D, const float *ds_dst, int64_t n_rows, int64_t heads, int64_t out_dim, float *dZ, int64_t lddz,
+    float *ds_src, gist_stream_t stream) {
+    return gat_backward_src<false>("gist_gat_backward_src_f32", t_rowptr, t_col, Z, ldz, G, ldgm, A, s_src, s_dst, M, L, D,
+                                 ds_dst, n_rows, heads, out_dim, dZ, lddz, ds_src, stream);
+}
+
+extern "C" int gist_gat_backward_src_cat_f32(const int32_t *t_rowptr, const int32_t *t_col, const float *Z, int64_t ldz,
+    const float *G, int64_t ldgm, const float *A, const float *s_src, const float *s_dst, const float *M, const float *L,
+    const float *D, const float *ds_dst, int64_t n_rows, int64_t heads, int64_t out_dim, float *dZ, int64_t lddz,
+    float *ds_src, gist_stream_t stream) {
+    return gat_backward_src<true>("gist_gat_backward_src_cat_f32", t_rowptr, t_col, Z, ldz, G, ldgm, A, s_src, s_dst, M, L, D,
+                                ds_dst, n_rows, heads, out_dim, dZ, lddz, ds_src, stream);
 }
 
 extern "C" int64_t gist_gat_attn_grad_workspace_floats(int64_t n_rows, int64_t heads, int64_t out_dim) {

@@ -10,6 +10,16 @@
 using namespace gist;
 
 namespace {
+// Does layer k concatenate its heads?  The next layer's input width says so: n_out_k = the head mean, heads_k * n_out_k
+// (heads_k > 1) = the concatenation.  The last layer has one head, where the two coincide: the mean.
+bool layer_cats(const gist_gat_step_plan *p, int k) {
+    return k + 1 < p->n_layers && p->layer[k].heads > 1 && p->layer[k + 1].n_in != p->layer[k].n_out;
+}
+// columns of layer k's output, of its gradient and of G
+int64_t out_width(const gist_gat_step_plan *p, int k) {
+    return layer_cats(p, k) ? p->layer[k].heads * p->layer[k].n_out : p->layer[k].n_out;
+}
+
 // layer count and shapes only: what the size helpers and the step both need before they look at a pointer
 bool shapes_ok(const gist_gat_step_plan *p) {
     if (p == nullptr || p->n_layers < 1 || p->n_layers > GIST_MAX_LAYERS || p->n_max <= 0 || p->n_max >= (1LL << 31))
@@ -18,7 +28,8 @@ bool shapes_ok(const gist_gat_step_plan *p) {
         const gist_gat_layer_desc &l = p->layer[k];
         if (l.n_in < 1 || l.n_out < 1 || l.heads < 1 || l.heads * l.n_out >= (1LL << 22) || l.n_in >= (1LL << 22))
             return false;
-        if (k > 0 && l.n_in != p->layer[k - 1].n_out) return false;
+        if (k > 0 && l.n_in != p->layer[k - 1].n_out && l.n_in != p->layer[k - 1].heads * p->layer[k - 1].n_out)
+            return false;
     }
     return true;
 }
@@ -159,7 +170,7 @@ extern "C" int gist_gat_step(const gist_gat_step_plan *p, const int32_t *ids, in
     for (int k = 0; k < L; ++k) {
         const gist_gat_layer_desc &l = p->layer[k];
         const int64_t hf = l.heads * l.n_out;
-        const float *x = k == 0 ? p->x0 : p->layer[k - 1].out;
+        const float *x = k == 0 ? p->x0 : p->layer[k - 1].out;      // (dense: out_width(k - 1) = n_in wide)
         {
             Scope sc(p->timer, 1, n, hf, l.n_in, st);
             GIST_TRY(gist_gemm_nt_f32(x, l.n_in, l.W, l.n_in, nullptr, l.Z, hf, n, hf, l.n_in, ws[k][0].p,
@@ -167,8 +178,8 @@ extern "C" int gist_gat_step(const gist_gat_step_plan *p, const int32_t *ids, in
         }
         GIST_TRY(gist_gat_scores_f32(l.Z, hf, l.A, n, l.heads, l.n_out, l.s_src, l.s_dst, s));
         Scope sc(p->timer, 0, n, n, hf, st);
-        GIST_TRY(gist_gat_aggregate_f32(p->rowptr, p->col, l.Z, hf, l.s_src, l.s_dst, n, l.heads, l.n_out, 1, l.out,
-                                        l.n_out, l.m, l.l, s));
+        GIST_TRY((layer_cats(p, k) ? gist_gat_aggregate_cat_f32 : gist_gat_aggregate_f32)(
+            p->rowptr, p->col, l.Z, hf, l.s_src, l.s_dst, n, l.heads, l.n_out, 1, l.out, out_width(p, k), l.m, l.l, s));
     }
     const gist_gat_layer_desc &last = p->layer[L - 1];
     GIST_TRY(gist_softmax_xent_f32(last.out, last.n_out, p->labels, nullptr, n, p->row_loss, p->loss, p->dlogits,
@@ -181,17 +192,19 @@ extern "C" int gist_gat_step(const gist_gat_step_plan *p, const int32_t *ids, in
         const gist_gat_layer_desc &l = p->layer[k];
         const int64_t hf = l.heads * l.n_out;
         const float *x = k == 0 ? p->x0 : p->layer[k - 1].out;
+        const bool cat = layer_cats(p, k);
+        const int64_t ow = out_width(p, k);
         {
             Scope sc(p->timer, 0, n, n, hf, st);
-            GIST_TRY(gist_gat_backward_dst_f32(p->rowptr, p->col, l.Z, hf, l.out, l.n_out, d_out, l.n_out, l.s_src,
-                                               l.s_dst, l.m, l.l, n, l.heads, l.n_out, 1, p->g, l.n_out, p->ds_dst,
-                                               p->dd, s));
+            GIST_TRY((cat ? gist_gat_backward_dst_cat_f32 : gist_gat_backward_dst_f32)(
+                p->rowptr, p->col, l.Z, hf, l.out, ow, d_out, ow, l.s_src, l.s_dst, l.m, l.l, n, l.heads, l.n_out, 1,
+                p->g, ow, p->ds_dst, p->dd, s));
         }
         {
             Scope sc(p->timer, 0, n, n, hf, st);
-            GIST_TRY(gist_gat_backward_src_f32(p->t_rowptr, p->t_col, l.Z, hf, p->g, l.n_out, l.A, l.s_src, l.s_dst,
-                                               l.m, l.l, p->dd, p->ds_dst, n, l.heads, l.n_out, p->dZ, hf, p->ds_src,
-                                               s));
+            GIST_TRY((cat ? gist_gat_backward_src_cat_f32 : gist_gat_backward_src_f32)(
+                p->t_rowptr, p->t_col, l.Z, hf, p->g, ow, l.A, l.s_src, l.s_dst, l.m, l.l, p->dd, p->ds_dst, n, l.heads,
+                l.n_out, p->dZ, hf, p->ds_src, s));
         }
         GIST_TRY(gist_gat_attn_grad_f32(l.Z, hf, p->ds_src, p->ds_dst, n, l.heads, l.n_out, p->attn_partials,
                                         p->attn_partial_floats, l.dA, s));

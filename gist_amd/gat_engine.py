@@ -27,7 +27,9 @@ from .engine import StepEngine
 
 class GATEngine(StepEngine):
     def __init__(self, dims=None, n_max=None, device=None, arena=None):
-        """dims = [(in_k, out_k, heads_k)] (gist_amd.arena.gat_dims), or `arena` = a GATArena to adopt (its dims)."""
+        """dims = [(in_k, out_k, heads_k)] (gist_amd.arena.gat_dims), or `arena` = a GATArena to adopt (its dims).  The
+        dims say how a layer's heads are combined, as in the plan: layer k + 1 reading heads_k * out_k columns means
+        concatenated heads (gat_dims(..., merge='cat')), reading out_k the head mean."""
         if arena is None:
             if dims is None or device is None:
                 raise ValueError('gist_amd: GATEngine needs dims and a device, or an arena')
@@ -41,6 +43,9 @@ class GATEngine(StepEngine):
             raise ValueError('gist_amd: more than %d GAT layers' % _lib.GIST_MAX_LAYERS)
         self.n_max = n = int(n_max)
         self.n_classes = self.dims[-1][1]
+        # columns of every layer's output: the next layer's input width (the step checks it is out_k or heads_k * out_k)
+        widths = [i for (i, o, h) in self.dims[1:]] + [self.n_classes]
+        self.merge = 'cat' if any(w != o for w, (i, o, h) in zip(widths, self.dims)) else 'mean'
         # EngineClusterIter's surface: no fused sequence of the SAGE kind (layer 0's aggregation is attention, the
         # extraction cannot form it), a dense layer-0 input buffer
         self.fuse = False
@@ -48,13 +53,13 @@ class GATEngine(StepEngine):
         f32 = dict(dtype=torch.float32, device=self.device)
         self.X0 = torch.zeros(n, self.dims[0][0], **f32)
         self.Z = [torch.zeros(n, h * o, **f32) for (i, o, h) in self.dims]
-        self.out = [torch.zeros(n, o, **f32) for (i, o, h) in self.dims]
+        self.out = [torch.zeros(n, w, **f32) for w in widths]
         self.s_src = [torch.zeros(n, h, **f32) for (i, o, h) in self.dims]
         self.s_dst = [torch.zeros(n, h, **f32) for (i, o, h) in self.dims]
         self.m = [torch.zeros(n, h, **f32) for (i, o, h) in self.dims]
         self.l = [torch.zeros(n, h, **f32) for (i, o, h) in self.dims]
         self.dZ = torch.zeros(n * max(h * o for (i, o, h) in self.dims), **f32)
-        self.g = torch.zeros(n * max(o for (i, o, h) in self.dims), **f32)
+        self.g = torch.zeros(n * max(widths), **f32)
         max_h = max(h for (i, o, h) in self.dims)
         self.ds_dst = torch.zeros(n * max_h, **f32)
         self.dd = torch.zeros(n * max_h, **f32)
@@ -142,7 +147,8 @@ class GATEngine(StepEngine):
         if self._model is None:
             from .modules import GAT
             with torch.device('meta'):
-                gat = GAT(len(self.dims), self.dims[0][0], self.dims[0][1], self.dims[-1][1], self.dims[0][2])
+                gat = GAT(len(self.dims), self.dims[0][0], self.dims[0][1], self.dims[-1][1], self.dims[0][2],
+                          merge=self.merge)
             self.bind(gat)
         return self._model
 

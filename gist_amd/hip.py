@@ -325,23 +325,27 @@ def gat_scores(z, a, s_src, s_dst):
                                      _nh(s_dst, 's_dst', n, heads), _stream()), 'gist_gat_scores_f32')
 
 
-def gat_aggregate(rowptr, col, z, a, s_src, s_dst, elu, out, m, l):
-    """Edge softmax + weighted sum of every head, head mean, optional ELU (gist_gat_aggregate_f32)."""
+def gat_aggregate(rowptr, col, z, a, s_src, s_dst, elu, out, m, l, cat=False):
+    """Edge softmax + weighted sum of every head, head mean, optional ELU (gist_gat_aggregate_f32); cat: the heads side
+    by side instead, out [n, heads * out_dim] (gist_gat_aggregate_cat_f32)."""
     L = _lib.load()
     n, heads, f = _gat_dims(z, a)
     rp, cp = _csr(rowptr, col, n, 'rowptr')
     zp, ldz = _mat(z, 'z')
     op, ldo = _mat(out, 'out')
-    if tuple(out.shape) != (n, f):
-        raise ValueError('gist_amd: gat_aggregate output must be [%d, %d]' % (n, f))
-    _lib.check(L.gist_gat_aggregate_f32(rp, cp, zp, ldz, _nh(s_src, 's_src', n, heads), _nh(s_dst, 's_dst', n, heads),
-                                        n, heads, f, int(bool(elu)), op, ldo, _nh(m, 'm', n, heads),
-                                        _nh(l, 'l', n, heads), _stream()), 'gist_gat_aggregate_f32')
+    w = heads * f if cat else f
+    if tuple(out.shape) != (n, w):
+        raise ValueError('gist_amd: gat_aggregate output must be [%d, %d]' % (n, w))
+    fn, name = ((L.gist_gat_aggregate_cat_f32, 'gist_gat_aggregate_cat_f32') if cat else
+                (L.gist_gat_aggregate_f32, 'gist_gat_aggregate_f32'))
+    _lib.check(fn(rp, cp, zp, ldz, _nh(s_src, 's_src', n, heads), _nh(s_dst, 's_dst', n, heads), n, heads, f,
+                  int(bool(elu)), op, ldo, _nh(m, 'm', n, heads), _nh(l, 'l', n, heads), _stream()), name)
     return out
 
 
-def gat_backward_dst(rowptr, col, z, a, out, d_out, s_src, s_dst, m, l, elu, g, ds_dst, dd):
-    """Destination pass of the GAT backward (gist_gat_backward_dst_f32): g, ds_dst, D."""
+def gat_backward_dst(rowptr, col, z, a, out, d_out, s_src, s_dst, m, l, elu, g, ds_dst, dd, cat=False):
+    """Destination pass of the GAT backward (gist_gat_backward_dst_f32): g, ds_dst, D; cat: out, d_out and g are
+    [n, heads * out_dim] (gist_gat_backward_dst_cat_f32)."""
     L = _lib.load()
     n, heads, f = _gat_dims(z, a)
     rp, cp = _csr(rowptr, col, n, 'rowptr')
@@ -349,32 +353,34 @@ def gat_backward_dst(rowptr, col, z, a, out, d_out, s_src, s_dst, m, l, elu, g, 
     op, ldo = _mat(out, 'out')
     dp, ldg = _mat(d_out, 'd_out')
     gp, ldgm = _mat(g, 'g')
+    w = heads * f if cat else f
     for t, name in ((out, 'out'), (d_out, 'd_out'), (g, 'g')):
-        if tuple(t.shape) != (n, f):
-            raise ValueError('gist_amd: gat_backward_dst: %s must be [%d, %d]' % (name, n, f))
-    _lib.check(L.gist_gat_backward_dst_f32(rp, cp, zp, ldz, op, ldo, dp, ldg, _nh(s_src, 's_src', n, heads),
-                                           _nh(s_dst, 's_dst', n, heads), _nh(m, 'm', n, heads),
-                                           _nh(l, 'l', n, heads), n, heads, f, int(bool(elu)), gp, ldgm,
-                                           _nh(ds_dst, 'ds_dst', n, heads), _nh(dd, 'd', n, heads), _stream()),
-               'gist_gat_backward_dst_f32')
+        if tuple(t.shape) != (n, w):
+            raise ValueError('gist_amd: gat_backward_dst: %s must be [%d, %d]' % (name, n, w))
+    fn, name = ((L.gist_gat_backward_dst_cat_f32, 'gist_gat_backward_dst_cat_f32') if cat else
+                (L.gist_gat_backward_dst_f32, 'gist_gat_backward_dst_f32'))
+    _lib.check(fn(rp, cp, zp, ldz, op, ldo, dp, ldg, _nh(s_src, 's_src', n, heads), _nh(s_dst, 's_dst', n, heads),
+                  _nh(m, 'm', n, heads), _nh(l, 'l', n, heads), n, heads, f, int(bool(elu)), gp, ldgm,
+                  _nh(ds_dst, 'ds_dst', n, heads), _nh(dd, 'd', n, heads), _stream()), name)
 
 
-def gat_backward_src(t_rowptr, t_col, z, a, g, s_src, s_dst, m, l, dd, ds_dst, dz, ds_src):
-    """Source pass of the GAT backward over the reversed CSR (gist_gat_backward_src_f32): dZ, ds_src."""
+def gat_backward_src(t_rowptr, t_col, z, a, g, s_src, s_dst, m, l, dd, ds_dst, dz, ds_src, cat=False):
+    """Source pass of the GAT backward over the reversed CSR (gist_gat_backward_src_f32): dZ, ds_src; cat: g is
+    [n, heads * out_dim] (gist_gat_backward_src_cat_f32)."""
     L = _lib.load()
     n, heads, f = _gat_dims(z, a)
     rp, cp = _csr(t_rowptr, t_col, n, 't_rowptr')
     zp, ldz = _mat(z, 'z')
     gp, ldgm = _mat(g, 'g')
     dzp, lddz = _mat(dz, 'dz')
-    if tuple(g.shape) != (n, f) or tuple(dz.shape) != tuple(z.shape):
+    if tuple(g.shape) != (n, heads * f if cat else f) or tuple(dz.shape) != tuple(z.shape):
         raise ValueError('gist_amd: gat_backward_src shape mismatch')
-    _lib.check(L.gist_gat_backward_src_f32(rp, cp, zp, ldz, gp, ldgm, a.data_ptr(), _nh(s_src, 's_src', n, heads),
-                                           _nh(s_dst, 's_dst', n, heads), _nh(m, 'm', n, heads),
-                                           _nh(l, 'l', n, heads), _nh(dd, 'd', n, heads),
-                                           _nh(ds_dst, 'ds_dst', n, heads), n, heads, f, dzp, lddz,
-                                           _nh(ds_src, 'ds_src', n, heads), _stream()),
-               'gist_gat_backward_src_f32')
+    fn, name = ((L.gist_gat_backward_src_cat_f32, 'gist_gat_backward_src_cat_f32') if cat else
+                (L.gist_gat_backward_src_f32, 'gist_gat_backward_src_f32'))
+    _lib.check(fn(rp, cp, zp, ldz, gp, ldgm, a.data_ptr(), _nh(s_src, 's_src', n, heads),
+                  _nh(s_dst, 's_dst', n, heads), _nh(m, 'm', n, heads), _nh(l, 'l', n, heads), _nh(dd, 'd', n, heads),
+                  _nh(ds_dst, 'ds_dst', n, heads), n, heads, f, dzp, lddz, _nh(ds_src, 'ds_src', n, heads), _stream()),
+               name)
 
 
 def gat_attn_grad(z, ds_src, ds_dst, da):

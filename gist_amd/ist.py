@@ -359,23 +359,28 @@ class DistributedGATWrapper(_DistributedWrapper):
         layer               fc (stacked [nh*O, I])           attn (stacked [nh, 2O])
         first               rows h*H + idx_0                 columns full_0
         middle k            rows h*H + idx_k, cols idx_k-1   columns full_k
-        last (one head)     columns idx_last-1               shared: the mean over the sites"""
+        last (one head)     columns idx_last-1               shared: the mean over the sites
+
+    `args.head_merge` = 'cat' (absent: 'mean'): the hidden layers concatenate their heads, so layer k > 0 reads
+    nh * H columns (the sub-GAT nh * h) and its fc columns -- the last layer's too -- are the previous boundary's indices
+    expanded over the previous layer's heads, h'*H + idx_k-1, as the rows are.  Rows and attn columns are the same."""
 
     def __init__(self, args, g, in_feats, n_classes, device, *, base_init=_UNSET, blocks=None, comm=None, seed=0):
         from .modules import GAT
         self._GAT = GAT                  # (imported here, not in _new_model: that also runs under torch.device('meta'))
         self.nh = args.n_heads
+        self.merge = getattr(args, 'head_merge', 'mean')
         _DistributedWrapper.__init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm)
         self.n_bound = len(self.sub_dims) - 1                 # hidden boundaries that take a partition
 
     def _dims(self, sub):
-        return gat_dims(self.in_feats, self.h if sub else self.H, self.n_classes, self.L, self.nh)
+        return gat_dims(self.in_feats, self.h if sub else self.H, self.n_classes, self.L, self.nh, self.merge)
 
     def _new_arena(self, dims, trains):
         return GATArena(dims, self.device)                    # (gradients: the autograd's, or GATEngine's with_grads)
 
     def _new_model(self, sub):
-        return self._GAT(self.L, self.in_feats, self.h if sub else self.H, self.n_classes, self.nh)
+        return self._GAT(self.L, self.in_feats, self.h if sub else self.H, self.n_classes, self.nh, merge=self.merge)
 
     _module_params = staticmethod(gat_params)
 
@@ -383,12 +388,18 @@ class DistributedGATWrapper(_DistributedWrapper):
         return arena.bind(gat, requires_grad)
 
     def _site_plan(self, part, site):
-        """The fc rows expanded over the heads (h*H + idx) once here."""
+        """The fc rows expanded over the heads (h*H + idx) once here; with concatenated heads the fc columns too, over
+        the previous layer's heads."""
+        def over_heads(idx, nh):
+            return (torch.arange(nh)[:, None] * self.H + idx[None, :]).reshape(-1)
         layers = []
         for k, (_, _, nh) in enumerate(self.sub_dims):
             idx, full = part[k][site] if k < len(self.sub_dims) - 1 else (None, None)
-            rows = (torch.arange(nh)[:, None] * self.H + idx[None, :]).reshape(-1) if idx is not None else None
-            layers.append((rows, part[k - 1][site][0] if k > 0 else None, full))
+            rows = over_heads(idx, nh) if idx is not None else None
+            cols = part[k - 1][site][0] if k > 0 else None
+            if cols is not None and self.merge == 'cat':
+                cols = over_heads(cols, self.sub_dims[k - 1][2])
+            layers.append((rows, cols, full))
         return layers
 
 

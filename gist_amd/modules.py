@@ -12,7 +12,8 @@ attributes (`layers[k].heads[h].fc.weight`, `.attn_fc.weight`) and initialisatio
 runs all its heads as ONE op (gist_amd.autograd.gat_layer).  One deliberate deviation: the heads
 of a layer are averaged PER NODE (the reference's torch.mean(torch.stack(head_outs)), :76,
 reduces to a scalar; its constructor sizes layer k+1's input as hidden_dim, :80-84, which rules
-out concatenation), see DESIGN.md "Graph attention".
+out concatenation), see DESIGN.md "Graph attention".  `merge='cat'` (not an argument of the
+reference) builds the model its comment :87-89 describes: hidden layers concatenate their heads.
 """
 import math
 
@@ -183,31 +184,42 @@ class GATLayer(nn.Module):
 
 
 class MultiHeadGATLayer(nn.Module):
-    """num_heads GATLayers on the same input (modules.py:67-76), averaged per node; all heads run as one op."""
+    """num_heads GATLayers on the same input (modules.py:67-76), averaged per node or, with merge='cat',
+    concatenated [n, num_heads * out_dim]; all heads run as one op."""
 
-    def __init__(self, in_dim, out_dim, num_heads):
+    def __init__(self, in_dim, out_dim, num_heads, merge='mean'):
         super().__init__()
+        if merge not in ('mean', 'cat'):
+            raise ValueError("gist_amd: merge must be 'mean' or 'cat' (got %r)" % (merge,))
+        self.merge = merge
         self.heads = nn.ModuleList()
         for i in range(num_heads):
             self.heads.append(GATLayer(in_dim, out_dim))
 
     def forward(self, g, h, elu=False):
-        """(1/H) sum_h head_h(g, h) per node; with elu=True, F.elu of it in the same kernel (GAT.forward)."""
+        """(1/H) sum_h head_h(g, h) per node, or the heads side by side (merge='cat'); with elu=True, F.elu of it in
+        the same kernel (GAT.forward)."""
         weight, attn = _stack_heads(self.heads)
-        return autograd.gat_layer(g, h, weight, attn, elu)
+        return autograd.gat_layer(g, h, weight, attn, elu, self.merge)
 
 
 class GAT(nn.Module):
     """Layer sizing of the reference's GAT (modules.py:78-98): num_heads heads in the first layer and in the
-    num_layers - 2 middle ones (width hidden_dim), one head of width out_dim last; ELU after every layer."""
+    num_layers - 2 middle ones (width hidden_dim), one head of width out_dim last; ELU after every layer.  With
+    merge='cat' the hidden layers concatenate their heads (the reference's comment, modules.py:87-89): only the in_dim
+    of the later layers changes, to num_heads * hidden_dim; the one-head output layer is the same."""
 
-    def __init__(self, num_layers, in_dim, hidden_dim, out_dim, num_heads):
+    def __init__(self, num_layers, in_dim, hidden_dim, out_dim, num_heads, merge='mean'):
         super().__init__()
-        layers = [MultiHeadGATLayer(in_dim, hidden_dim, num_heads)]
+        if merge not in ('mean', 'cat'):
+            raise ValueError("gist_amd: merge must be 'mean' or 'cat' (got %r)" % (merge,))
+        self.merge = merge
+        # the input of every later layer: hidden_dim where the heads are averaged, all of them where concatenated
+        wide = num_heads * hidden_dim if merge == 'cat' else hidden_dim
+        layers = [MultiHeadGATLayer(in_dim, hidden_dim, num_heads, merge)]
         for layer_idx in range(num_layers - 2):
-            layers.append(MultiHeadGATLayer(hidden_dim, hidden_dim, num_heads))
-        # the input of every later layer is hidden_dim wide: the heads are averaged, not concatenated
-        layers.append(MultiHeadGATLayer(hidden_dim, out_dim, 1))
+            layers.append(MultiHeadGATLayer(wide, hidden_dim, num_heads, merge))
+        layers.append(MultiHeadGATLayer(wide, out_dim, 1))
         self.layers = torch.nn.ModuleList(layers)
 
     def forward(self, g):

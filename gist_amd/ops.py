@@ -180,14 +180,15 @@ sage_layer.register_autograd(_sage_backward, setup_context=_sage_setup)
 
 # -- one multi-head GAT layer ------------------------------------------------------------------
 # x [n, in], weight = the heads' fc weights stacked [H*F, in], attn = their attn_fc weights stacked [H, 2F]; the
-# output is act(mean over heads) [n, F] (act = ELU when `elu`, modules.py:97); see include/gist_hip.h "Graph attention".
+# output is act(mean over heads) [n, F] (act = ELU when `elu`, modules.py:97), or with `cat` act(heads side by side)
+# [n, H*F] (modules.py:87-89); see include/gist_hip.h "Graph attention".
 def _gat_shapes(x, weight, attn):
     return x.shape[0], attn.shape[0], attn.shape[1] // 2
 
 
 @torch.library.custom_op('gist::gat_layer_fwd', mutates_args=(), device_types='cuda')
 def gat_layer_fwd(rowptr: Tensor, col: Tensor, x: Tensor, weight: Tensor, attn: Tensor,
-                  elu: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+                  elu: bool, cat: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
     """(out, z = x . weight^T, s_src, s_dst, m = softmax max, l = softmax denominator)."""
     n, heads, f = _gat_shapes(x, weight, attn)
     dev = x.device
@@ -197,41 +198,41 @@ def gat_layer_fwd(rowptr: Tensor, col: Tensor, x: Tensor, weight: Tensor, attn: 
     s_src = torch.empty(n, heads, dtype=torch.float32, device=dev)
     s_dst = torch.empty(n, heads, dtype=torch.float32, device=dev)
     hip.gat_scores(z, attn, s_src, s_dst)
-    out = torch.empty(n, f, dtype=torch.float32, device=dev)
+    out = torch.empty(n, heads * f if cat else f, dtype=torch.float32, device=dev)
     m = torch.empty(n, heads, dtype=torch.float32, device=dev)
     l = torch.empty(n, heads, dtype=torch.float32, device=dev)
-    hip.gat_aggregate(rowptr, col, z, attn, s_src, s_dst, elu, out, m, l)
+    hip.gat_aggregate(rowptr, col, z, attn, s_src, s_dst, elu, out, m, l, cat)
     return out, z, s_src, s_dst, m, l
 
 
-def _gat_fwd_fake(x, weight, attn):
+def _gat_fwd_fake(x, weight, attn, cat):
     n, heads, f = _gat_shapes(x, weight, attn)
-    return (x.new_empty(n, f), x.new_empty(n, heads * f), x.new_empty(n, heads), x.new_empty(n, heads),
-            x.new_empty(n, heads), x.new_empty(n, heads))
+    return (x.new_empty(n, heads * f if cat else f), x.new_empty(n, heads * f), x.new_empty(n, heads),
+            x.new_empty(n, heads), x.new_empty(n, heads), x.new_empty(n, heads))
 
 
 @gat_layer_fwd.register_fake
-def _(rowptr, col, x, weight, attn, elu):
-    return _gat_fwd_fake(x, weight, attn)
+def _(rowptr, col, x, weight, attn, elu, cat=False):
+    return _gat_fwd_fake(x, weight, attn, cat)
 
 
 @torch.library.custom_op('gist::gat_layer_bwd', mutates_args=(), device_types='cuda')
 def gat_layer_bwd(rowptr: Tensor, col: Tensor, t_rowptr: Tensor, t_col: Tensor, x: Tensor, weight: Tensor,
                   attn: Tensor, z: Tensor, s_src: Tensor, s_dst: Tensor, m: Tensor, l: Tensor, out: Tensor,
-                  d_out: Tensor, elu: bool, need_dx: bool) -> Tuple[Tensor, Tensor, Tensor]:
+                  d_out: Tensor, elu: bool, need_dx: bool, cat: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
     """(dx [n, in] or empty, d weight [H*F, in], d attn [H, 2F]): a destination pass over the in-edge CSR, a source
     pass over the reversed CSR (dZ in one store), the attention-vector sums, then two GEMMs."""
     n, heads, f = _gat_shapes(x, weight, attn)
     n_in = x.shape[1]
     dev = x.device
     attn = attn.contiguous()
-    g = torch.empty(n, f, dtype=torch.float32, device=dev)
+    g = torch.empty(n, heads * f if cat else f, dtype=torch.float32, device=dev)
     ds_dst = torch.empty(n, heads, dtype=torch.float32, device=dev)
     dd = torch.empty(n, heads, dtype=torch.float32, device=dev)
-    hip.gat_backward_dst(rowptr, col, z, attn, out, _c(d_out), s_src, s_dst, m, l, elu, g, ds_dst, dd)
+    hip.gat_backward_dst(rowptr, col, z, attn, out, _c(d_out), s_src, s_dst, m, l, elu, g, ds_dst, dd, cat)
     dz = torch.empty(n, heads * f, dtype=torch.float32, device=dev)
     ds_src = torch.empty(n, heads, dtype=torch.float32, device=dev)
-    hip.gat_backward_src(t_rowptr, t_col, z, attn, g, s_src, s_dst, m, l, dd, ds_dst, dz, ds_src)
+    hip.gat_backward_src(t_rowptr, t_col, z, attn, g, s_src, s_dst, m, l, dd, ds_dst, dz, ds_src, cat)
     d_attn = torch.empty(heads, 2 * f, dtype=torch.float32, device=dev)
     hip.gat_attn_grad(z, ds_src, ds_dst, d_attn)
     d_weight = torch.empty(heads * f, n_in, dtype=torch.float32, device=dev)
@@ -244,37 +245,37 @@ def gat_layer_bwd(rowptr: Tensor, col: Tensor, t_rowptr: Tensor, t_col: Tensor, 
 
 
 @gat_layer_bwd.register_fake
-def _(rowptr, col, t_rowptr, t_col, x, weight, attn, z, s_src, s_dst, m, l, out, d_out, elu, need_dx):
+def _(rowptr, col, t_rowptr, t_col, x, weight, attn, z, s_src, s_dst, m, l, out, d_out, elu, need_dx, cat=False):
     n, heads, f = _gat_shapes(x, weight, attn)
     return x.new_empty(n if need_dx else 0, x.shape[1]), weight.new_empty(weight.shape), attn.new_empty(attn.shape)
 
 
 @torch.library.custom_op('gist::gat_layer', mutates_args=(), device_types='cuda')
 def gat_layer(rowptr: Tensor, col: Tensor, t_rowptr: Tensor, t_col: Tensor, x: Tensor, weight: Tensor,
-              attn: Tensor, elu: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+              attn: Tensor, elu: bool, cat: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
     """MultiHeadGATLayer.forward (+ GAT's ELU) as ONE differentiable op: (out, z, s_src, s_dst, m, l); only `out`
     carries a gradient, the others are what the backward formula needs."""
-    return torch.ops.gist.gat_layer_fwd(rowptr, col, x, weight, attn, elu)
+    return torch.ops.gist.gat_layer_fwd(rowptr, col, x, weight, attn, elu, cat)
 
 
 @gat_layer.register_fake
-def _(rowptr, col, t_rowptr, t_col, x, weight, attn, elu):
-    return _gat_fwd_fake(x, weight, attn)
+def _(rowptr, col, t_rowptr, t_col, x, weight, attn, elu, cat=False):
+    return _gat_fwd_fake(x, weight, attn, cat)
 
 
 def _gat_setup(ctx, inputs, output):
-    rowptr, col, t_rowptr, t_col, x, weight, attn, elu = inputs
+    rowptr, col, t_rowptr, t_col, x, weight, attn, elu, cat = inputs
     out, z, s_src, s_dst, m, l = output
     ctx.save_for_backward(rowptr, col, t_rowptr, t_col, x, weight, attn, z, s_src, s_dst, m, l, out)
-    ctx.elu = elu
+    ctx.elu, ctx.cat = elu, cat
     ctx.need_dx = ctx.needs_input_grad[4]
 
 
 def _gat_backward(ctx, d_out, d_z, d_s_src, d_s_dst, d_m, d_l):
     rowptr, col, t_rowptr, t_col, x, weight, attn, z, s_src, s_dst, m, l, out = ctx.saved_tensors
     dx, d_weight, d_attn = torch.ops.gist.gat_layer_bwd(rowptr, col, t_rowptr, t_col, x, weight, attn, z, s_src,
-                                                        s_dst, m, l, out, d_out, ctx.elu, ctx.need_dx)
-    return None, None, None, None, dx if ctx.need_dx else None, d_weight, d_attn, None
+                                                        s_dst, m, l, out, d_out, ctx.elu, ctx.need_dx, ctx.cat)
+    return None, None, None, None, dx if ctx.need_dx else None, d_weight, d_attn, None, None
 
 
 gat_layer.register_autograd(_gat_backward, setup_context=_gat_setup)

@@ -36,6 +36,9 @@ def build_parser():
     parser.add_argument("--weight-decay", type=float, default=0, help="Weight for L2 loss")
     parser.add_argument("--model-type", type=str, default='sage', help="sage or gat")
     parser.add_argument("--n-heads", type=int, default=4, help="attention heads of the GAT layers")
+    # (not a flag of the reference) cat: the hidden GAT layers concatenate their heads (its comment, modules.py:87-89)
+    parser.add_argument("--head-merge", choices=['mean', 'cat'], default='mean',
+                        help="how a GAT layer combines its heads")
     parser.add_argument("--fig-dir", type=str, default='../report/example_pic/')
     parser.add_argument("--fig-name", type=str, default='name')
     parser.add_argument("--use-layernorm", action='store_true')
@@ -123,8 +126,11 @@ def main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, l
     it = EngineClusterIter(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li, device=device)
     g = g.to(device)
     labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
-    model = GAT(args.n_layers, in_feats, args.n_hidden, n_classes, args.n_heads)   # cluster_gcn_ist_distrib_gat.py:77-79
-    engine = GATEngine(gat_dims(in_feats, args.n_hidden, n_classes, args.n_layers, args.n_heads), it.n_max, device)
+    merge = getattr(args, 'head_merge', 'mean')
+    model = GAT(args.n_layers, in_feats, args.n_hidden, n_classes, args.n_heads,   # cluster_gcn_ist_distrib_gat.py:77-79
+                merge=merge)
+    engine = GATEngine(gat_dims(in_feats, args.n_hidden, n_classes, args.n_layers, args.n_heads, merge), it.n_max,
+                       device)
     engine.arena.load(gat_params(model))
     engine.bind(model)                                     # the model's parameters are the arena's views from here on
     it.bind(engine)
@@ -165,7 +171,8 @@ def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, 
     g = g.to(device)
     labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
     if args.model_type == 'gat':
-        model = GAT(args.n_layers, in_feats, args.n_hidden, n_classes, args.n_heads)   # cluster_gcn_ist_distrib_gat.py:77-79
+        model = GAT(args.n_layers, in_feats, args.n_hidden, n_classes, args.n_heads,   # cluster_gcn_ist_distrib_gat.py:77-79
+                    merge=getattr(args, 'head_merge', 'mean'))
         model.cuda()
     else:
         model = GCN(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout,

@@ -25,6 +25,8 @@ from gist_amd.scripts.cluster_gcn_ist_distrib import add_ist_args, setup
 def build_parser():
     parser = add_ist_args(argparse.ArgumentParser(description='GCN'))
     parser.add_argument('--n-heads', type=int, default=4)
+    # (not a flag of the reference) cat: the hidden layers concatenate their heads (its comment, modules.py:87-89)
+    parser.add_argument('--head-merge', choices=['mean', 'cat'], default='mean')
     parser.add_argument("--exp_name", type=str, default='distributed_gnn_ist')
     return parser
 

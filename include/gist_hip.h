@@ -948,6 +948,30 @@ int gist_gat_backward_src_f32(const int32_t *t_rowptr, const int32_t *t_col, con
                               const float *ds_dst, int64_t n_rows, int64_t heads, int64_t out_dim,
                               float *dZ, int64_t lddz, float *ds_src, gist_stream_t stream);
 
+/* The same three with the heads CONCATENATED instead of averaged (an addition: ABI 16) -- what the reference's
+ * comment at cluster_gcn/modules.py:87-89 says the hidden layers' heads are meant to be, and what its
+ * MultiHeadGATLayer.forward :74-76 would be with merge = 'cat':
+ *   out[i, hF:(h+1)F] = act(sum_{e in row i} alpha_he Z[col[e], hF:(h+1)F])        [n, H*F], ldo >= H*F
+ *   G[i, hF:(h+1)F]   = d_out[i, hF:(h+1)F] * act'(out[i, hF:(h+1)F])              [n, H*F], ldg, ldgm >= H*F (no 1/H)
+ * and head h of both backward passes reads its own slice G[i, hF:(h+1)F].  Everything else -- arguments, M, L, D,
+ * ds_dst, ds_src, dZ, the argument checks, the edge order and so the bits of every per-head sum -- is as above; with
+ * H = 1 there is nothing to concatenate and these run the kernels of the entries above (the same bits).  The vectorised
+ * paths need ldo and ldgm % 4 == 0 as before. */
+int gist_gat_aggregate_cat_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+                               const float *s_src, const float *s_dst, int64_t n_rows, int64_t heads,
+                               int64_t out_dim, int elu, float *out, int64_t ldo, float *M, float *L,
+                               gist_stream_t stream);
+int gist_gat_backward_dst_cat_f32(const int32_t *rowptr, const int32_t *col, const float *Z, int64_t ldz,
+                                  const float *out, int64_t ldo, const float *d_out, int64_t ldg,
+                                  const float *s_src, const float *s_dst, const float *M, const float *L,
+                                  int64_t n_rows, int64_t heads, int64_t out_dim, int elu, float *G,
+                                  int64_t ldgm, float *ds_dst, float *D, gist_stream_t stream);
+int gist_gat_backward_src_cat_f32(const int32_t *t_rowptr, const int32_t *t_col, const float *Z, int64_t ldz,
+                                  const float *G, int64_t ldgm, const float *A, const float *s_src,
+                                  const float *s_dst, const float *M, const float *L, const float *D,
+                                  const float *ds_dst, int64_t n_rows, int64_t heads, int64_t out_dim,
+                                  float *dZ, int64_t lddz, float *ds_src, gist_stream_t stream);
+
 /* Floats of the partial-slab workspace gist_gat_attn_grad_f32 needs.  Host function. */
 int64_t gist_gat_attn_grad_workspace_floats(int64_t n_rows, int64_t heads, int64_t out_dim);
 /* dA[h, 0:F] = sum_r ds_src[r,h] Z[r, hF:(h+1)F],  dA[h, F:2F] = sum_r ds_dst[r,h] Z[r, hF:(h+1)F]
@@ -970,18 +994,21 @@ typedef struct gist_gat_layer_desc {
     float *W, *A;              /* [heads*n_out, n_in], [heads, 2*n_out]                        */
     float *dW, *dA;            /* gradients, same shapes                                       */
     float *Z;                  /* [n_max, heads*n_out] = x . W^T                               */
-    float *out;                /* [n_max, n_out] = elu(head mean): the next layer's input      */
+    float *out;                /* [n_max, n_out] = elu(head mean): the next layer's input; or
+                                  [n_max, heads*n_out] = elu(heads concatenated), see n_layers */
     float *s_src, *s_dst;      /* [n_max, heads] attention scores per node and side            */
     float *m, *l;              /* [n_max, heads] softmax max and denominator                   */
 } gist_gat_layer_desc;
 
 typedef struct gist_gat_step_plan {
-    int32_t n_layers;              /* layers of gist_amd.modules.GAT; layer k's n_in = layer k-1's n_out        */
+    int32_t n_layers;              /* layers of gist_amd.modules.GAT.  Layer k averages its heads if layer k+1's n_in =
+                                      n_out_k, and concatenates them (gist_gat_*_cat_f32) if heads_k > 1 and layer k+1's
+                                      n_in = heads_k * n_out_k; anything else is GIST_EINVAL.  The last layer averages. */
     gist_gat_layer_desc layer[GIST_MAX_LAYERS];
     float *x0;                     /* [n_max, n_in_0]: layer 0's input, filled by the extraction's feature gather */
     /* backward scratch shared by the layers, sized for the widest one */
     float *dZ;                     /* [n_max * max_k(heads_k * n_out_k)]                            */
-    float *g;                      /* [n_max * max_k(n_out_k)]  d_out * elu'(out) / heads           */
+    float *g;                      /* [n_max * max_k(width of out_k)]  d_out * elu'(out) (/ heads: mean) */
     float *ds_dst, *dd, *ds_src;   /* [n_max * max_k(heads_k)] each                                 */
     float *d_out[2];               /* [n_max * max_{k>=1}(n_in_k)] each: dx of layer k is layer k-1's d_out (ping-pong;
                                       unused by a one-layer model)                                  */

@@ -18,6 +18,9 @@ path -- cat, mul, zero_ -- are not in it).
 
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/gat_step.py --trace engine --shape 2,4,64 --steps 40
 
+--head-merge cat times the model with concatenated heads (layer k + 1 reads heads * width columns), --head-merge both
+every multi-head shape in both modes in the same run (rows carry `merge`).
+
 runs --steps untimed steps of one path for a kernel trace: the difference of the traced kernel calls of two step
 counts, over the difference of the counts, is the path's launches per step, set-up excluded.
 """
@@ -59,14 +62,14 @@ class Paths(object):
         self.eng_it = EngineClusterIter(ds.name, g, psize, bsize, nid, par_li=ds.par_li, device=dev)
         self.fin, self.ncls = g.ndata['feat'].shape[1], ds.num_classes
 
-    def shape(self, layers, heads, width):
+    def shape(self, layers, heads, width, merge='mean'):
         from gist_amd.gat_engine import GATEngine
         from gist_amd.ist import gat_dims, gat_params
         from gist_amd.modules import GAT
         from gist_amd.nn import CrossEntropyLoss
         from gist_amd.optim import Adam
         torch.manual_seed(0)
-        model = GAT(layers, self.fin, width, self.ncls, heads).to(self.dev)
+        model = GAT(layers, self.fin, width, self.ncls, heads, merge=merge).to(self.dev)
         loss_f = CrossEntropyLoss()
         opt = Adam(model.parameters(), lr=LR, weight_decay=WD)
         mod_batches = cycle(self.mod_it)
@@ -81,7 +84,7 @@ class Paths(object):
             loss.backward()
             opt.step()
 
-        eng = GATEngine(gat_dims(self.fin, width, self.ncls, layers, heads), self.eng_it.n_max, self.dev)
+        eng = GATEngine(gat_dims(self.fin, width, self.ncls, layers, heads, merge), self.eng_it.n_max, self.dev)
         eng.arena.load(gat_params(model))
         self.eng_it.bind(eng)
         eng.prefetch = True
@@ -120,6 +123,7 @@ def main():
     ap.add_argument('--trace', choices=['engine', 'module'], help='untimed steps of one path, for a kernel trace')
     ap.add_argument('--shape', default='2,4,64', help='--trace: layers,heads,width')
     ap.add_argument('--steps', type=int, default=40, help='--trace: steps to run')
+    ap.add_argument('--head-merge', choices=['mean', 'cat', 'both'], default='mean')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'gat_step.py measures on the GPU'
     from gist_amd import datasets, hip
@@ -132,7 +136,7 @@ def main():
     setup_s = time.time() - t0
     if args.trace:
         layers, heads, width = (int(v) for v in args.shape.split(','))
-        eng, eng_step, mod_step = paths.shape(layers, heads, width)
+        eng, eng_step, mod_step = paths.shape(layers, heads, width, 'cat' if args.head_merge == 'cat' else 'mean')
         fn = eng_step if args.trace == 'engine' else mod_step
         for _ in range(args.steps):
             fn()
@@ -141,9 +145,12 @@ def main():
         print('gat_step: traced %d %s steps of shape %s' % (args.steps, args.trace, args.shape))
         return
     shapes = [(2, 4, 32)] if args.quick else SHAPES
+    merges = ('mean', 'cat') if args.head_merge == 'both' else (args.head_merge,)
+    # (one head: the two modes are the same model, measured once as 'mean')
+    shapes = [s + (m,) for s in shapes for m in merges if m == 'mean' or s[1] > 1 or len(merges) == 1]
     res = []
-    for layers, heads, width in shapes:
-        eng, eng_step, mod_step = paths.shape(layers, heads, width)
+    for layers, heads, width, merge in shapes:
+        eng, eng_step, mod_step = paths.shape(layers, heads, width, merge)
         for _ in range(args.warmup):
             eng_step()
             mod_step()
@@ -159,7 +166,7 @@ def main():
         eng.check_extract()
         e, m = float(np.median(e_ms)), float(np.median(m_ms))
         noise = max(spread(e_ms), spread(m_ms))
-        r = dict(layers=layers, heads=heads, width=width, n_in=paths.fin, engine_ms=round(e, 4), module_ms=round(m, 4),
+        r = dict(merge=merge, layers=layers, heads=heads, width=width, n_in=paths.fin, engine_ms=round(e, 4), module_ms=round(m, 4),
                  module_over_engine=round(m / e, 3), engine_spread=round(spread(e_ms), 4),
                  module_spread=round(spread(m_ms), 4), engine_not_slower=bool(e <= m * (1.0 + noise)),
                  engine_lib_launches_per_step=round(float(np.median(e_l)), 2),
