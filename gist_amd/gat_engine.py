@@ -36,12 +36,12 @@ class GATEngine(StepEngine):
             arena = GATArena([(int(i), int(o), int(h)) for (i, o, h) in dims], device)
         self.arena = arena.with_grads()
         self.dims = [(int(i), int(o), int(h)) for (i, o, h) in arena.dims]
-        self.device = arena.device if device is None else device
         if n_max is None or int(n_max) <= 0:
             raise ValueError('gist_amd: GATEngine needs n_max > 0 (the iterator\'s n_max)')
         if len(self.dims) > _lib.GIST_MAX_LAYERS:
             raise ValueError('gist_amd: more than %d GAT layers' % _lib.GIST_MAX_LAYERS)
-        self.n_max = n = int(n_max)
+        StepEngine.__init__(self, arena.device if device is None else device, n_max)
+        n = self.n_max
         self.n_classes = self.dims[-1][1]
         # columns of every layer's output: the next layer's input width (the step checks it is out_k or heads_k * out_k)
         widths = [i for (i, o, h) in self.dims[1:]] + [self.n_classes]
@@ -49,7 +49,6 @@ class GATEngine(StepEngine):
         # EngineClusterIter's surface: no fused sequence of the SAGE kind (layer 0's aggregation is attention, the
         # extraction cannot form it), a dense layer-0 input buffer
         self.fuse = False
-        self.prefetch = False
         f32 = dict(dtype=torch.float32, device=self.device)
         self.X0 = torch.zeros(n, self.dims[0][0], **f32)
         self.Z = [torch.zeros(n, h * o, **f32) for (i, o, h) in self.dims]
@@ -69,28 +68,17 @@ class GATEngine(StepEngine):
         self.dlogits = torch.zeros(n, self.n_classes, **f32)
         self.row_loss = torch.zeros(n, **f32)
         self.loss = torch.zeros(1, **f32)
-        self.plan = None
-        self._extract_scratch = None
-        self._timer = None
         self._model = None
-        self._plan_keep = None
-
-    # ------------------------------------------------------------------
-    def _shape_plan(self):
-        P = _lib.GATStepPlan()
-        P.n_layers = len(self.dims)
-        P.n_max = self.n_max
-        for k, (i, o, h) in enumerate(self.dims):
-            P.layer[k].n_in, P.layer[k].n_out, P.layer[k].heads = i, o, h
-        return P
 
     def attach_batcher(self, batcher):
         """Build the native step plan (struct gist_gat_step_plan) over `batcher`'s resident graph and batch buffers."""
         A = self.arena
         L = _lib.load()
-        P = self._shape_plan()
-        for k in range(len(self.dims)):
+        P = _lib.GATStepPlan()
+        P.n_layers, P.n_max = len(self.dims), self.n_max
+        for k, (i, o, h) in enumerate(self.dims):
             l = P.layer[k]
+            l.n_in, l.n_out, l.heads = i, o, h
             l.W, l.A, l.dW, l.dA = A.W[k].data_ptr(), A.A[k].data_ptr(), A.dW[k].data_ptr(), A.dA[k].data_ptr()
             l.Z, l.out = self.Z[k].data_ptr(), self.out[k].data_ptr()
             l.s_src, l.s_dst = self.s_src[k].data_ptr(), self.s_dst[k].data_ptr()
@@ -111,23 +99,15 @@ class GATEngine(StepEngine):
         P.params, P.grads = A.params.data_ptr(), A.grads.data_ptr()
         P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
         P.n_params = A.numel
-        g = batcher.g
         if batcher.n_max > self.n_max:
             raise ValueError('gist_amd: the batcher yields up to %d rows, the engine was sized for %d'
                              % (batcher.n_max, self.n_max))
         if batcher.feat.shape[1] != self.dims[0][0]:
             raise ValueError('gist_amd: %d input features, layer 0 takes %d' % (batcher.feat.shape[1], self.dims[0][0]))
-        P.g_rowptr, P.g_col = g.rowptr.data_ptr(), g.col.data_ptr()
-        P.g_t_rowptr, P.g_t_col = g.t_rowptr.data_ptr(), g.t_col.data_ptr()
-        P.feat, P.ld_feat = batcher.feat.data_ptr(), batcher.feat.stride(0)
-        P.labels_all, P.remap = batcher.labels.data_ptr(), batcher.remap.data_ptr()
-        P.rowptr, P.col = batcher.rowptr.data_ptr(), batcher.col.data_ptr()
-        P.t_rowptr, P.t_col = batcher.t_rowptr.data_ptr(), batcher.t_col.data_ptr()
-        P.col_capacity = batcher.col.numel()
-        P.norm, P.labels = batcher.norm.data_ptr(), batcher.lab.data_ptr()
+        self._bind_graph(P, batcher)
         P.batch_index = P.next_batch_index = -1
         self.plan = P
-        self._plan_keep = (batcher, g, self._ws, self._attn_partials)      # keep every buffer alive
+        self._plan_keep = (batcher, batcher.g, self._ws, self._attn_partials)      # keep every buffer alive
         return P
 
     def z0_left(self, n):
@@ -157,51 +137,26 @@ class GATEngine(StepEngine):
         self._model = self.arena.bind(gat)
         return self._model
 
-    # ------------------------------------------------------------------
     def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8):
         if self.plan is None:
             raise RuntimeError('gist_amd: GATEngine needs attach_batcher (EngineClusterIter.bind) first')
-        L = _lib.load()
-        P = self.plan
-        ids_ptr = b.ids.data_ptr() if b.ids is not None else None
-        batcher = b.batcher
-        # was this batch extracted beside the previous step's optimiser launch (self.prefetch)?
-        pre = batcher.prefetched if batcher is not None else None
-        if batcher is not None:
-            batcher.prefetched = None
-        pre_ok = (pre is not None and train and not b.ready and b.parts is not None and
-                  pre == (b.parts[1].data_ptr(), int(b.parts[2]), b.n, ids_ptr, id(self)))
-        flags = _lib.GIST_STEP_TRAIN if train else 0
-        if pre_ok:
-            flags |= _lib.GIST_STEP_PREEXTRACTED
-        elif not b.ready:
-            flags |= _lib.GIST_STEP_EXTRACT
-        # one-launch extraction when the batch comes with its part tables (gist_extract_parts_batch)
-        if b.parts is not None and not b.ready and L.gist_extract_parts_supported(self.n_max):
-            node_part, tab, j = b.parts
-            P.node_part, P.part_slot = node_part.data_ptr(), tab.data_ptr()
-            P.batch_index, P.extract_scratch = int(j), self._extraction_scratch().data_ptr()
-        else:
-            P.node_part = P.part_slot = P.extract_scratch = None
-            P.batch_index = -1
+        L, P = _lib.load(), self.plan
+        flags, ids_ptr = self._begin_step(b, train, ())
         # the NEXT batch of the epoch, extracted in the optimiser's grid: only for callers that promise not to look at
         # the batch buffers (labels, CSR, layer 0's input) after a training step
-        P.next_ids, P.next_n, P.next_batch_index = None, 0, -1
         nxt = None
-        if self.prefetch and train and batcher is not None and b.next_info is not None and P.node_part is not None:
+        if self.prefetch and train and b.batcher is not None and b.next_info is not None and P.node_part is not None:
             nids, nj = b.next_info
             if 0 < nids.numel() <= self.n_max:
                 P.next_ids, P.next_n, P.next_batch_index = nids.data_ptr(), nids.numel(), int(nj)
                 flags |= _lib.GIST_STEP_EXTRACT_NEXT
-                nxt = (P.part_slot, int(nj), nids.numel(), nids.data_ptr(), id(self))
+                nxt = self._batch_key(P.part_slot, nj, nids.numel(), nids.data_ptr(), ())
         if train:
             self.arena.step += 1
         rc = L.gist_gat_step(ctypes.byref(P), ids_ptr, b.n, lr, betas[0], betas[1], eps, weight_decay,
                              max(self.arena.step, 1), flags, hip._stream())
         _lib.check(rc, 'gist_gat_step')
-        if batcher is not None:
-            batcher.prefetched = nxt
-        b.ready = True
+        self._end_step(b, nxt)
         return self.loss
 
     def train_step(self, b, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
