@@ -26,10 +26,14 @@ from .engine import StepEngine
 
 
 class GATEngine(StepEngine):
-    def __init__(self, dims=None, n_max=None, device=None, arena=None):
+    def __init__(self, dims=None, n_max=None, device=None, arena=None, x0=None):
         """dims = [(in_k, out_k, heads_k)] (gist_amd.arena.gat_dims), or `arena` = a GATArena to adopt (its dims).  The
         dims say how a layer's heads are combined, as in the plan: layer k + 1 reading heads_k * out_k columns means
-        concatenated heads (gat_dims(..., merge='cat')), reading out_k the head mean."""
+        concatenated heads (gat_dims(..., merge='cat')), reading out_k the head mean.
+
+        x0 = ANOTHER engine's X0 to read layer 0's input rows from instead of a buffer of its own: several sub-GATs of
+        one process (gist_amd.ist.train_gat) bound to the same batcher step on the batch the first of them extracted.
+        The step only reads it."""
         if arena is None:
             if dims is None or device is None:
                 raise ValueError('gist_amd: GATEngine needs dims and a device, or an arena')
@@ -50,7 +54,13 @@ class GATEngine(StepEngine):
         # extraction cannot form it), a dense layer-0 input buffer
         self.fuse = False
         f32 = dict(dtype=torch.float32, device=self.device)
-        self.X0 = torch.zeros(n, self.dims[0][0], **f32)
+        if x0 is None:
+            x0 = torch.zeros(n, self.dims[0][0], **f32)
+        elif (x0.shape != (n, self.dims[0][0]) or x0.dtype != torch.float32 or x0.device.type != torch.device(self.device).type
+              or not x0.is_contiguous()):
+            raise ValueError('gist_amd: a shared x0 must be a contiguous fp32 [%d, %d] tensor on %s'
+                             % (n, self.dims[0][0], self.device))
+        self.X0 = x0
         self.Z = [torch.zeros(n, h * o, **f32) for (i, o, h) in self.dims]
         self.out = [torch.zeros(n, w, **f32) for w in widths]
         self.s_src = [torch.zeros(n, h, **f32) for (i, o, h) in self.dims]

@@ -8,7 +8,7 @@ Reference: cluster_gcn/cluster_gcn_ist_distrib.py
   train                       :370-479
 Reference: cluster_gcn/cluster_gcn_ist_distrib_gat.py
   DistributedGATWrapper       :67-391   (gist_amd.arena.GATArena: the flat per-head layout)
-  train_gat                   :393-480  (the loop on the drop-in classes)
+  train_gat                   :393-480  (the loop on the drop-in classes, or on GATEngine's one-call step)
 
 The two families share everything but a few facts, and those are all that a family's subclass states.
 _DistributedWrapper holds construction, dispatch and sync, written against a per-site, per-layer plan of index
@@ -42,6 +42,7 @@ import torch.distributed as dist
 
 from .arena import GATArena, ParamArena, gat_dims, gat_params      # (also where their callers import them from)
 from .engine import SageEngine, dims_for
+from .gat_engine import GATEngine
 
 
 def create_partition(num_subnet, size, rng=_pyrandom):
@@ -372,6 +373,16 @@ class DistributedGATWrapper(_DistributedWrapper):
         self.merge = getattr(args, 'head_merge', 'mean')
         _DistributedWrapper.__init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm)
         self.n_bound = len(self.sub_dims) - 1                 # hidden boundaries that take a partition
+        self.engine = None                                    # attach_engine: train_gat(..., host_path='engine')
+
+    def attach_engine(self, n_max, x0=None):
+        """The GATEngine that steps `sub` in place (adopted: dispatch and sync keep moving the same storage, `sub_model`
+        keeps viewing it), sized for batches of up to n_max rows; kept as `engine`.  x0: the first site's layer-0 input
+        buffer, for the further sites of one process (GATEngine)."""
+        e = self.engine
+        if e is None or e.n_max != int(n_max) or (x0 is not None and e.X0 is not x0):
+            self.engine = GATEngine(arena=self.sub, n_max=n_max, x0=x0)
+        return self.engine
 
     def _dims(self, sub):
         return gat_dims(self.in_feats, self.h if sub else self.H, self.n_classes, self.L, self.nh, self.merge)
@@ -511,19 +522,37 @@ def train(ist_model, args, cluster_iterator, evaluator=None, log=print):
                          accuracies if evaluator is not None else None)
 
 
-def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print):
+def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module'):
     """The GIST loop of cluster_gcn_ist_distrib_gat.py:393-480 on the drop-in classes: `ist_model.sub_model(cluster)`,
     masked gist_amd.nn.CrossEntropyLoss, a new gist_amd.optim.Adam at every dispatch point, `evaluate(base_model, g,
     ...)` on rank 0 (`g` on the device).  The schedule is the SAGE one (_run_schedule).
+
+    host_path='engine': every site's step is ONE gist_gat_step call on its wrapper's GATEngine (_gat_engine_steps)
+    instead; `cluster_iterator` is then an EngineClusterIter.  Same launches in the same order on the same layouts:
+    losses, arenas and accuracies are those of 'module' bit for bit.
 
     `ist_model` is this rank's DistributedGATWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites then
     run in this process, the partition sampled once per dispatch.  The step losses stay on the device (the reference's
     per-step `float(loss)` would wait for it every step); each evaluation averages them.  Returns total_time,
     per-site step losses, events, accuracies and the mean training loss per evaluation."""
-    from .nn import CrossEntropyLoss
-    from .optim import Adam
     from .utils import evaluate
     models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
+    if host_path not in ('module', 'engine'):
+        raise ValueError("gist_amd: train_gat host_path must be 'module' or 'engine' (got %r)" % (host_path,))
+    steps = _gat_engine_steps if host_path == 'engine' else _gat_module_steps
+    at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
+
+    def accuracies():
+        base_model = models[0].base_model
+        return evaluate(base_model, g, labels, val_mask), evaluate(base_model, g, labels, test_mask)
+    return _run_schedule(models, args, cluster_iterator, lambda line: log(line, flush=True), at_dispatch, step,
+                         before_eval, accuracies)
+
+
+def _gat_module_steps(models, args, cluster_iterator):
+    """train_gat's (at_dispatch, step, before_eval) on the drop-in classes: the reference's loop body."""
+    from .nn import CrossEntropyLoss
+    from .optim import Adam
     dev = models[0].device
     loss_fcn = CrossEntropyLoss()
     optimizers = [None] * len(models)
@@ -545,12 +574,47 @@ def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask,
         loss.backward()
         optimizers[si].step()
         return loss.detach()
+    return at_dispatch, step, lambda: None
 
-    def accuracies():
-        base_model = models[0].base_model
-        return evaluate(base_model, g, labels, val_mask), evaluate(base_model, g, labels, test_mask)
-    return _run_schedule(models, args, cluster_iterator, lambda line: log(line, flush=True), at_dispatch, step,
-                         lambda: None, accuracies)
+
+def _gat_engine_steps(models, args, cluster_iterator):
+    """train_gat's (at_dispatch, step, before_eval) on the fused step: one GATEngine per wrapper over its sub arena.
+
+    One site in the process (the distributed run): the optimiser launch of a step extracts the next batch of the epoch
+    beside it, as in train().  S sites in one process: a GAT's first layer takes the full input width, so the extracted
+    batch -- CSR, reversed CSR, labels, layer 0's input rows -- is the same for every site.  All engines are bound to
+    the iterator's batcher and read ONE layer-0 input buffer, the first engine's; the first site's step extracts the
+    batch, the others step on the buffers as they stand."""
+    from .sampler import EngineClusterIter
+    if models[0].device.type != 'cuda':
+        raise ValueError("gist_amd: train_gat(host_path='engine') runs the fused step gist_gat_step, which is GPU-only "
+                         "(the wrapper is on %s); use host_path='module' there" % (models[0].device,))
+    if not isinstance(cluster_iterator, EngineClusterIter):
+        raise ValueError("gist_amd: train_gat(host_path='engine') needs a gist_amd.sampler.EngineClusterIter as "
+                         "cluster_iterator (got %s): it describes the batches the step extracts on the device"
+                         % type(cluster_iterator).__name__)
+    it = cluster_iterator
+    first = models[0].attach_engine(it.n_max)
+    if it.engine is not first:
+        it.bind(first)
+    for m in models[1:]:
+        engine = m.attach_engine(it.n_max, x0=first.X0)
+        if engine.plan is None or engine._plan_keep[0] is not it.batcher:
+            engine.attach_batcher(it.batcher)
+    for m in models:
+        m.engine.prefetch = len(models) == 1
+
+    def at_dispatch():
+        for m in models:
+            m.sub.reset_optimizer()
+
+    def step(si, batch):
+        return models[si].engine.train_step(batch, args.lr, args.weight_decay)[0].clone()      # (0-dim, as 'module')
+
+    def before_eval():                               # (the device is idle: every extraction so far was complete)
+        for m in models:
+            m.engine.check_extract()
+    return at_dispatch, step, before_eval
 
 
 def print_results(res, log=print):

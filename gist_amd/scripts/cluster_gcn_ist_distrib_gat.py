@@ -2,6 +2,8 @@
 """GIST for the GAT family -- CLI and output contract of the reference's cluster_gcn/cluster_gcn_ist_distrib_gat.py
 (flags :538-580, four result lines or the results pickle :481-499), one process per GPU, running on the gist_amd HIP
 path: gist_amd.ist.DistributedGATWrapper and gist_amd.ist.train_gat, the reference's loop on the drop-in classes.
+`--host-path engine` (not a flag of the reference) runs every step as one gist_gat_step call on the wrapper's
+GATEngine instead: the same numbers bit for bit, fewer launches.
 
 Launch like the reference's GAT sweep (script/reddit/run_gat_distrib_sweep.py): one process per rank,
 
@@ -28,6 +30,9 @@ def build_parser():
     # (not a flag of the reference) cat: the hidden layers concatenate their heads (its comment, modules.py:87-89)
     parser.add_argument('--head-merge', choices=['mean', 'cat'], default='mean')
     parser.add_argument("--exp_name", type=str, default='distributed_gnn_ist')
+    # (not a flag of the reference) module: the reference's loop on ist_model.sub_model / base_model; engine: one
+    # gist_gat_step per iteration (gist_amd.ist.train_gat, host_path)
+    parser.add_argument("--host-path", choices=['module', 'engine'], default='module')
     return parser
 
 
@@ -52,24 +57,31 @@ def report(args, res, log=print):
 
 def main(args=None, dataset=None, log=print):
     from gist_amd import ist
-    from gist_amd.sampler import ClusterIter
+    from gist_amd.sampler import ClusterIter, EngineClusterIter
     if args is None:
         args = build_parser().parse_args()
     assert (args.n_hidden % args.num_subnet) == 0
+    host_path = getattr(args, 'host_path', 'module')
+    if host_path == 'engine' and (args.use_pp or args.cuda_id < 0):
+        raise SystemExit('gist_amd: --host-path engine is the fused GAT step: it runs on a GPU (--cuda-id >= 0) and '
+                         'extracts its batches from the plain features (no --use-pp); use --host-path module')
     if args.use_pp:
         raise NotImplementedError(
             'gist_amd: --use-pp cannot work with the GAT in the reference either (the feature width doubles after '
             'in_feats was read)')
     device, data, g, in_feats, n_classes, train_nid, par_li, psize = setup(args, dataset, log)
-    cluster_iterator = ClusterIter(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li,
-                                   device=device)                                    # get_data (one shuffle)
+    iter_cls = EngineClusterIter if host_path == 'engine' else ClusterIter
+    cluster_iterator = iter_cls(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li,
+                                device=device)                                       # get_data (one shuffle)
     g = g.to(device)
     ist_model = ist.DistributedGATWrapper(args, g, in_feats, n_classes, device, seed=args.rnd_seed)   # :609
     log(f'{args.rank}: start initial dispatch', flush=True)
     ist_model.ini_sync_dispatch_model()
     log(f'{args.rank}: finish initial dispatch', flush=True)
+    if host_path == 'engine':
+        cluster_iterator.bind(ist_model.attach_engine(cluster_iterator.n_max))
     res = ist.train_gat(ist_model, args, g, cluster_iterator, g.ndata['label'], g.ndata['val_mask'],
-                        g.ndata['test_mask'], log=log)
+                        g.ndata['test_mask'], log=log, host_path=host_path)
     if args.rank == 0:
         path = report(args, res, log=log)
         if path is not None:
