@@ -108,6 +108,7 @@ SIGNATURES = {
     'gist_ln_relu_fwd_slabs_f32': (_int, [_p, _i64, _p, _i64, _int, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _int, _int,
                                           _f, _f, _u64, _u64, _i64, _p]),
     'gist_gemm_splits_operands': (_int, [_i64, _i64, _i64]),
+    'gist_gemm_plan_query': (_int, [_int, _i64, _i64, _i64, _int, _int, _int, _i64, _p]),
     'gist_row_chunks16': (_i64, [_i64]),
     'gist_ln_relu_bwd_colsum_f32': (_int, [_p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _int, _int, _p, _p]),
     'gist_colsum_chunks_f32': (_int, [_p, _i64, _i64, _p, _p]),
@@ -167,6 +168,14 @@ GIST_STEP_PHASE_FORWARD = 16
 GIST_STEP_PHASE_BACKWARD = 32
 GIST_STEP_PHASE_OPTIMIZER = 64
 GIST_STEP_DLOGITS_GIVEN = 128
+
+
+class GemmPlan(ctypes.Structure):
+    """struct gist_gemm_plan (include/gist_hip.h)."""
+    _fields_ = [('path', _i32), ('kept_ok', _i32), ('tile_m', _i32), ('tile_n', _i32), ('splits', _i32),
+                ('whole_tiles', _i32), ('tail_splits', _i32), ('launches', _i32), ('k_per_split', _i64), ('tail_k', _i64),
+                ('operand_offset', _i64), ('operand_bytes', _i64), ('scratch_offset', _i64), ('scratch_bytes', _i64),
+                ('workspace_bytes', _i64)]
 
 
 class LayerDesc(ctypes.Structure):

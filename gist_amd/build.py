@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, 'csrc')
 # A/B runs against another build (GIST_LIB_OUT, loaded through GIST_LIB_PATH); the kernels have no build variants
 OUT = os.environ.get('GIST_LIB_OUT', os.path.join(HERE, 'libgist_hip.so'))
 EXTRA = os.environ.get('GIST_EXTRA_FLAGS', '').split()
-SOURCES = ['capi.hip', 'spmm.hip', 'spmm_mfma.hip', 'spmm_dense32.hip', 'gemm.hip', 'gemm_h3.hip', 'gemm_b3.hip', 'gemm_b3c.hip', 'rowops.hip', 'classlayer.hip', 'subgraph.hip', 'step.hip',
+SOURCES = ['capi.hip', 'spmm.hip', 'spmm_mfma.hip', 'spmm_dense32.hip', 'gemm.hip', 'gemm_h3.hip', 'gemm_b3.hip', 'gemm_b3c.hip', 'gemm_plan.cpp', 'rowops.hip', 'classlayer.hip', 'subgraph.hip', 'step.hip',
            'partition.hip', 'prep.hip', 'gat.hip', 'gat_step.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall',
@@ -33,7 +33,7 @@ def build(force=False, verbose=False):
     objs, procs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
-        obj = os.path.join(objdir, s.replace('.hip', '.o'))
+        obj = os.path.join(objdir, os.path.splitext(s)[0] + '.o')
         objs.append(obj)
         if force or _newer(src, obj) or any(_newer(d, obj) for d in deps):
             cmd = [HIPCC] + FLAGS + EXTRA + ['-c', src, '-o', obj]

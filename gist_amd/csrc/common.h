@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "../../include/gist_hip.h"
+#include "gemm_plan.h"
 
 namespace gist {
 
@@ -54,13 +55,11 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
+// The projection family.  How a projection runs -- path, tile, k slices, tail units, scratch -- is plan_gemm()'s answer
+// (gemm_plan.h); what follows are the launchers that read it and the pre-passes.
 // gemm_h3.hip: building blocks of the split projection path for a caller that manages the
 // split operands itself (the step driver).  Split operand = [rows][h3_kpad(k)] 32-bit words
 // + one inverse scale (power of two) per row.
-int64_t h3_kpad(int64_t k);
-bool h3_eligible(int64_t m, int64_t n, int64_t k);        // a call that splits its own operands (in mode 1)
-bool h3_eligible_kept(int64_t m, int64_t n, int64_t k);   // operands split once, kept by the step (shape only:
-                                                          // the step's layout checks the mode it is for)
 struct H3Dual {                       // one read of src[rows, cols] -> up to two split operands
     const float *src; int64_t ld; int64_t rows, cols;
     float p; uint64_t seed, offset;   // dropout applied on the fly (p = 0: none), gist_dropout_f32's stream
@@ -80,10 +79,6 @@ int h3_gemm_presplit(const char *name, const uint32_t *sa, const float *inv_a, c
 
 // gemm_b3.hip: the bf16x3 split projection path (all 24 operand bits, no scales).  Split operand =
 // [rows][b3_kpad(k)] elements of 6 bytes (three bf16 pieces per element, 16-byte chunks per 8 k).
-int h3_mode();                        // 0 fp32 MFMA, 1 f16x3, 2 bf16x3 (gist_gemm_set_mode)
-int64_t b3_kpad(int64_t k);
-bool b3_eligible(int64_t m, int64_t n, int64_t k);        // (in mode 2)
-bool b3_eligible_kept(int64_t m, int64_t n, int64_t k);   // (shape only, as h3_eligible_kept)
 struct B3Dual {                       // one read of src[rows, cols] -> up to two split operands
     const float *src; int64_t ld; int64_t rows, cols;
     float p; uint64_t seed, offset;   // dropout applied on the fly (p = 0: none), gist_dropout_f32's stream
@@ -96,7 +91,7 @@ struct B3Dual {                       // one read of src[rows, cols] -> up to tw
 int b3_dual_split(const B3Dual &d, hipStream_t st);
 constexpr int B3_SPLIT_MAX_JOBS = 4;
 int b3_split_jobs(const B3Dual *jobs, int n_jobs, hipStream_t st);      // up to B3_SPLIT_MAX_JOBS splits, one launch
-int64_t b3_slab_bytes(int64_t m, int64_t n, int64_t k);   // fp32 slabs of a split-K call (0: one k slice)
+// (slabs: the scratch of the GEMM_CALL_KEPT plan -- fp32 slabs of the k slices or the tail units' partials)
 int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, const float *bias, float *c,
                      int64_t ldc, int64_t m, int64_t n, int64_t k, float *slabs, int64_t slab_bytes,
                      hipStream_t st, int *deferred = nullptr);
@@ -104,8 +99,7 @@ int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, c
 // [*n_slabs][m][n] at `slabs` for the consumer to sum in slab order (+ bias); *n_slabs = 1: c is final
 int gemm_slabs(int layout, const float *a, int64_t lda, const float *b, int64_t ldb, const float *bias, float *c,
                int64_t ldc, int64_t m, int64_t n, int64_t k, void *slabs, int64_t slab_bytes, int *n_slabs,
-               hipStream_t st);
-int64_t gemm_f32_slab_bytes(int64_t m, int64_t n, int64_t k, bool tn = false);      // tn: a weight gradient (A and B k-major)
+               hipStream_t st, GemmCall call = GEMM_CALL_SPLITS);      // GEMM_CALL_SLABS: `slabs` was sized by gemm_slab_bytes
 // gemm.hip: dz = dy . w (NN) and dW = dy^T . z (TN, slabs) in one launch of the fp32 kernel's tiles
 bool gemm_dual_takes(int64_t m, int64_t n1, int64_t k1, int64_t lddy, int64_t ldw, int64_t ldz, int64_t lddz,
                      const float *dy, const float *w, const float *z, const float *dz);

@@ -587,69 +587,15 @@ int splitk_reduce(const char *name, const float *slabs, int64_t slab, int splits
     return launch_status(name);
 }
 
-// ---- tile / split-K choice ---------------------------------------------------------------
-// Everything here is fp32 MFMA work, so time ~ MFMA work of the busiest SIMD.  A block is 4
-// waves (one per SIMD of a CU); blocks are dealt round-robin to 256 CUs, a CU keeps up to
-// `cap` of them resident (128-tile: 2, 64-tile: 4) and fewer co-resident waves hide less
-// latency.  Model, in units of one 64x64x32 MFMA block (16 MFMAs, ~0.43 us), calibrated on
-// scripts/gemm_sweep.py measurements (MI355X, 34 shapes, within ~10% of the best config):
-//   per_cu  = ceil(blocks / 256)
-//   cost    = per_cu * unit(tile) * (k_tiles_per_split + 3) / eff(min(cap, per_cu))
-//           + [splits > 1] * (12 + 6.5 * splits * m*n/1e6)      (slab traffic + reduce launch)
-struct GemmCfg { int tile; int splits; };
-
-// gemm_h3.hip: the f16x3 split path (fp32-accurate products on the f16 matrix cores)
-int h3_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
-            int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k,
-            void *ws, int64_t ws_bytes, hipStream_t st);
-int64_t h3_workspace_bytes(int64_t m, int64_t n, int64_t k);
-// gemm_b3.hip: the bf16x3 split path (all 24 operand bits on the bf16 matrix cores)
-int b3_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
-            int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k,
-            void *ws, int64_t ws_bytes, hipStream_t st);
-int64_t b3_workspace_bytes(int64_t m, int64_t n, int64_t k);
-// gemm_b3c.hip: the bf16x3 path that converts on load (shapes below the pre-split path's thresholds)
-int b3c_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
-             int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k,
-             void *ws, int64_t ws_bytes, hipStream_t st, int *deferred);
-int64_t b3c_slab_bytes(int64_t m, int64_t n, int64_t k, bool tail = true);      // -1: shape not taken
-
-// deferred: the k slices are summed by the kernel that consumes the result (gist_gemm_slabs_f32) -- no reduce
-// launch, only the slabs' write and read.
-static GemmCfg choose_cfg(int64_t m, int64_t n, int64_t k, bool deferred = false) {
-    const int64_t kt = ceil_div(k, 32);      // the model counts k in units of 32
-    // explicit override for tuning sweeps (scripts/gemm_sweep.py) and tests; 0 = the model decides
-    const int t_tile = (int)tune(GIST_TUNE_GEMM_TILE), t_split = (int)tune(GIST_TUNE_GEMM_SPLITS);
-    if (t_tile && t_split) {
-        int sp = t_split;
-        while (sp > 1 && kt / sp < 1) sp >>= 1;
-        return GemmCfg{t_tile == 64 ? 64 : 128, sp < 1 ? 1 : sp};
-    }
-    static const double eff128[3] = {0.0, 0.90, 1.00};
-    static const double eff64[5] = {0.0, 0.60, 0.80, 0.92, 1.00};
-    GemmCfg best{128, 1};
-    double best_cost = 1e300;
-    const double mn = (double)m * (double)n / 1e6;
-    for (int tile : {128, 64}) {
-        const int64_t tiles = ceil_div(m, tile) * ceil_div(n, tile);
-        const int cap = tile == 128 ? 2 : 4;
-        const double unit = tile == 128 ? 4.0 : 1.12;
-        for (int sp : {1, 2, 4, 8, 16, 32}) {
-            if (sp > 1 && kt / sp < 2) break;
-            const int64_t per_cu = ceil_div(tiles * sp, 256);
-            const int64_t kt_per = ceil_div(kt, sp);
-            const int conc = (int)(per_cu < cap ? per_cu : cap);
-            const double eff = tile == 128 ? eff128[conc] : eff64[conc];
-            double cost = (double)per_cu * unit * (double)(kt_per + 3) / eff;
-            // (deferred: no reduce launch, but the slabs are written by this kernel and read by the consumer; fitted to
-            // same-box A/B runs of the forward projections of BASELINE configs 2 and 4; probe removed,
-            // `git show 4165530:scripts/ab_yslabs.sh`)
-            if (sp > 1) cost += deferred ? 4.5 + 9.0 * sp * mn : 12.0 + 6.5 * sp * mn;
-            if (cost < best_cost) { best_cost = cost; best = GemmCfg{tile, sp}; }
-        }
-    }
-    return best;
-}
+// ---- host side: plan (gemm_plan.h), fill the kernel's argument struct, launch ---------------------------
+// gemm_h3.hip / gemm_b3.hip / gemm_b3c.hip: a gist_gemm_* call that the plan sends to their kernels
+int h3_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
+            int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws, hipStream_t st);
+int b3_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
+            int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws, hipStream_t st);
+int b3c_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
+             int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws,
+             hipStream_t st, int *deferred);
 
 template <bool A_KC, bool B_KC, int T>
 static int launch_tile(const char *name, GemmArgs &g, bool aligned, int splits, hipStream_t st) {
@@ -689,7 +635,8 @@ static int launch_tile(const char *name, GemmArgs &g, bool aligned, int splits, 
 template <bool A_KC, bool B_KC>
 static int launch_gemm(const char *name, const float *a, int64_t lda, const float *b, int64_t ldb,
                        const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k,
-                       void *ws, int64_t ws_bytes, hipStream_t st, int *deferred = nullptr) {
+                       void *ws, int64_t ws_bytes, hipStream_t st, int *deferred = nullptr,
+                       GemmCall call = GEMM_CALL_SPLITS) {
     if (deferred) *deferred = 1;
     if (m < 0 || n < 0 || k < 0) { set_error("%s: negative size", name); return GIST_EINVAL; }
     if (m == 0 || n == 0) return GIST_OK;
@@ -701,32 +648,21 @@ static int launch_gemm(const char *name, const float *a, int64_t lda, const floa
     if (lda >= (1LL << 22) || ldb >= (1LL << 22) || ldc >= (1LL << 22)) {
         set_error("%s: leading dimension >= 2^22 elements", name); return GIST_EINVAL;
     }
-    {   // large, chip-filling shapes: split operands + f16 MFMA (mode 1); 0 = not taken
-        int rc = h3_gemm(name, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, ws_bytes, st);
-        if (rc != 0) return rc < 0 ? rc : GIST_OK;
-        rc = b3_gemm(name, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, ws_bytes, st);   // mode 2
-        if (rc != 0) return rc < 0 ? rc : GIST_OK;
-        rc = b3c_gemm(name, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, ws_bytes, st, deferred);
-        if (rc != 0) return rc < 0 ? rc : GIST_OK;                                                   // mode 2, small
+    const bool aligned = aligned16(a) && (lda % 4 == 0) && lda >= 4 && aligned16(b) && (ldb % 4 == 0) && ldb >= 4;
+    const GemmPlan pl = plan_gemm(GemmQuery{A_KC, B_KC, m, n, k, gemm_mode(), aligned, ldc, call,
+                                            deferred != nullptr, ws != nullptr && ws_bytes > 0 ? ws_bytes : 0, aligned16(ws)});
+    switch (pl.path) {
+        case GEMM_PATH_H3: return h3_gemm(name, pl, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, st);
+        case GEMM_PATH_B3: return b3_gemm(name, pl, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, st);
+        case GEMM_PATH_B3C: return b3c_gemm(name, pl, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, st, deferred);
+        default: break;
     }
     GemmArgs g;
     g.a = a; g.lda = lda; g.b = b; g.ldb = ldb; g.bias = bias; g.c = c; g.ldc = ldc;
     g.m = (int)m; g.n = (int)n; g.k = (int)k;
-    const bool aligned = aligned16(a) && (lda % 4 == 0) && lda >= 4 && aligned16(b) &&
-                         (ldb % 4 == 0) && ldb >= 4 && k > 0;
     g.setprio = 1;
-    GemmCfg cfg = choose_cfg(m, n, k, deferred != nullptr);
-    int splits = cfg.splits;
-    // a slab buffer too small for the model's slice count: the largest power of two that fits, not one slice
-    // (the class layer's 41 x 4096 x 2046 weight gradient fell from 8 slices to 1 for most batch sizes of the
-    // h = 2048 step -- 39 us instead of 13 -- because the count is not monotone in k and the step had sized its
-    // buffer from a few sampled batch sizes)
-    while (splits > 1 && (ws == nullptr || ws_bytes < (int64_t)splits * m * n * 4)) splits >>= 1;
-    g.k_per_split = (int)(ceil_div(ceil_div(k, 64), splits) * 64);   // multiple of either BK
-    splits = (int)ceil_div(k, g.k_per_split > 0 ? g.k_per_split : 1);
-    if (splits < 1) splits = 1;
-    if (k == 0) { g.k_per_split = 64; splits = 1; }
-    if (splits == 1) {
+    g.k_per_split = (int)pl.k_per_split;
+    if (pl.splits == 1) {
         g.split_stride = 0;
     } else {
         g.c = static_cast<float *>(ws);
@@ -734,50 +670,33 @@ static int launch_gemm(const char *name, const float *a, int64_t lda, const floa
         g.split_stride = m * n;
         g.bias = nullptr;
     }
-    int rc = cfg.tile == 128 ? launch_tile<A_KC, B_KC, 128>(name, g, aligned, splits, st)
-                             : launch_tile<A_KC, B_KC, 64>(name, g, aligned, splits, st);
-    if (rc || splits == 1) return rc;
-    if (deferred) { *deferred = splits; return rc; }
-    const int64_t total = m * n;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0,
-                       st, static_cast<const float *>(ws), m * n, splits, bias, c, ldc, (int)m,
-                       (int)n);
-    return launch_status(name);
+    int rc = pl.tile_m == 128 ? launch_tile<A_KC, B_KC, 128>(name, g, aligned && k > 0, pl.splits, st)
+                              : launch_tile<A_KC, B_KC, 64>(name, g, aligned && k > 0, pl.splits, st);
+    if (rc || pl.splits == 1) return rc;
+    if (deferred) { *deferred = pl.splits; return rc; }
+    return splitk_reduce(name, static_cast<const float *>(ws), m * n, pl.splits, bias, c, ldc, m, n, st);
 }
 
 // dz[m, n1] = dy[m, k1] . w[k1, n1]  (NN)   and   dW[k1, n1] = dy[m, k1]^T . z[m, n1]  (TN: k = m rows, left as
-// *n_slabs dense slabs [k1][n1] at `slabs` for the consumer, or written to dw when one slice) in ONE launch.
-// Taken (gemm_dual_takes) when both run on the fp32 kernel's 64 x 64 tiles anyway and together fit ~one round of the
-// chip's workgroup slots: the per-rank widths <= 512 and config 2.
-static bool dual_shapes_ok(int64_t m, int64_t n1, int64_t k1, int *splits_out) {
-    if (m <= 0 || n1 <= 0 || k1 <= 0 || (int)tune(GIST_TUNE_GEMM_DUAL) == 1) return false;
-    if (tune(GIST_TUNE_GEMM_TILE) != 0.0 || tune(GIST_TUNE_GEMM_SPLITS) != 0.0) return false;
-    if (h3_eligible(m, n1, k1) || b3_eligible(m, n1, k1) || h3_eligible(k1, n1, m) || b3_eligible(k1, n1, m)) return false;
-    const GemmCfg c1 = choose_cfg(m, n1, k1), c2 = choose_cfg(k1, n1, m, true);
-    if (c1.tile != 64 || c2.tile != 64 || c1.splits != 1) return false;
-    const int64_t blocks = ceil_div(m, 64) * ceil_div(n1, 64) + ceil_div(k1, 64) * ceil_div(n1, 64) * c2.splits;
-    if (blocks > 1280) return false;           // (2 workgroups per CU resident: beyond ~2.5 rounds each product fills the chip alone)
-    if (splits_out) *splits_out = c2.splits;
-    return true;
-}
-
+// *n_slabs dense slabs [k1][n1] at `slabs` for the consumer, or written to dw when one slice) in ONE launch
+// (plan_gemm_dual says for which shapes).
 bool gemm_dual_takes(int64_t m, int64_t n1, int64_t k1, int64_t lddy, int64_t ldw, int64_t ldz, int64_t lddz,
                      const float *dy, const float *w, const float *z, const float *dz) {
-    return dual_shapes_ok(m, n1, k1, nullptr) && lddy % 4 == 0 && ldw % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0 &&
+    return lddy % 4 == 0 && ldw % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0 &&
            lddy >= k1 && ldw >= n1 && ldz >= n1 && lddz >= n1 && lddy < (1LL << 22) && ldw < (1LL << 22) &&
            ldz < (1LL << 22) && lddz < (1LL << 22) && m < (1LL << 31) && aligned16(dy) && aligned16(w) && aligned16(z) &&
-           aligned16(dz);
+           aligned16(dz) && plan_gemm_dual(m, n1, k1, gemm_mode(), kScratchUnbounded).takes;
 }
 
 int gemm_dual_nn_tn(const char *name, const float *dy, int64_t lddy, const float *w, int64_t ldw, float *dz,
                     int64_t lddz, const float *z, int64_t ldz, float *dw, int64_t lddw, int64_t m, int64_t n1,
                     int64_t k1, void *slabs, int64_t slab_bytes, int *n_slabs, hipStream_t st) {
-    int splits = 1;
-    if (!dual_shapes_ok(m, n1, k1, &splits) || !gemm_dual_takes(m, n1, k1, lddy, ldw, ldz, lddz, dy, w, z, dz)) {
+    if (!gemm_dual_takes(m, n1, k1, lddy, ldw, ldz, lddz, dy, w, z, dz)) {
         set_error("%s: shape not taken (gist_gemm_dual_takes)", name);
         return GIST_EINVAL;
     }
     if (!dw || !n_slabs || lddw < n1) { set_error("%s: bad dW / n_slabs", name); return GIST_EINVAL; }
+    const GemmDualPlan pl = plan_gemm_dual(m, n1, k1, gemm_mode(), slabs != nullptr && slab_bytes > 0 ? slab_bytes : 0);
     GemmArgs g1{}, g2{};
     g1.a = dy; g1.lda = lddy; g1.b = w; g1.ldb = ldw; g1.bias = nullptr; g1.c = dz; g1.ldc = lddz;
     g1.m = (int)m; g1.n = (int)n1; g1.k = (int)k1; g1.setprio = 1;
@@ -785,11 +704,8 @@ int gemm_dual_nn_tn(const char *name, const float *dy, int64_t lddy, const float
     g1.tiles_m = (int)ceil_div(m, 64); g1.tiles_n = (int)ceil_div(n1, 64);
     g2.a = dy; g2.lda = lddy; g2.b = z; g2.ldb = ldz; g2.bias = nullptr; g2.setprio = 1;
     g2.m = (int)k1; g2.n = (int)n1; g2.k = (int)m;
-    while (splits > 1 && (slabs == nullptr || slab_bytes < (int64_t)splits * k1 * n1 * 4)) splits >>= 1;
-    g2.k_per_split = (int)(ceil_div(ceil_div(m, 64), splits) * 64);
-    splits = (int)ceil_div(m, g2.k_per_split > 0 ? g2.k_per_split : 1);
-    if (splits < 1) splits = 1;
-    if (splits == 1) { g2.c = dw; g2.ldc = lddw; g2.split_stride = 0; }
+    g2.k_per_split = (int)pl.k_per_split;
+    if (pl.splits == 1) { g2.c = dw; g2.ldc = lddw; g2.split_stride = 0; }
     else { g2.c = static_cast<float *>(slabs); g2.ldc = n1; g2.split_stride = k1 * n1; }
     g2.tiles_m = (int)ceil_div(k1, 64); g2.tiles_n = (int)ceil_div(n1, 64);
     constexpr int T = 64, BK = 64;
@@ -804,44 +720,28 @@ int gemm_dual_nn_tn(const char *name, const float *dy, int64_t lddy, const float
     }
     const int tiles1 = g1.tiles_m * g1.tiles_n, tiles2 = g2.tiles_m * g2.tiles_n;
     const int n1b = tiles1;
-    hipLaunchKernelGGL((gemm_f32_dual_kernel<64>), dim3((unsigned)(n1b + tiles2 * splits)), dim3(256), smem, st, g1, g2,
+    hipLaunchKernelGGL((gemm_f32_dual_kernel<64>), dim3((unsigned)(n1b + tiles2 * pl.splits)), dim3(256), smem, st, g1, g2,
                        n1b, tiles1, tiles2);
-    *n_slabs = splits;
+    *n_slabs = pl.splits;
     return launch_status(name);
-}
-
-void gemm_f32_choice(int64_t m, int64_t n, int64_t k, int *tile, int *splits) {
-    const GemmCfg c = choose_cfg(m, n, k);
-    *tile = c.tile;
-    *splits = c.splits;
-}
-
-// slab bytes of the split-K choice for this shape on the fp32 kernel or the convert-on-load bf16x3 kernel,
-// whichever is larger (0: one k slice)
-int64_t gemm_f32_slab_bytes(int64_t m, int64_t n, int64_t k, bool tn) {
-    if (m <= 0 || n <= 0 || k <= 0) return 0;
-    const int sp = choose_cfg(m, n, k, true).splits;      // (sized for the deferred form: what these slabs are for)
-    const int64_t f32 = sp > 1 ? (int64_t)sp * m * n * 4 : 0;
-    const int64_t c3 = b3c_slab_bytes(m, n, k, !tn);
-    return c3 > f32 ? c3 : f32;
 }
 
 int gemm_slabs(int layout, const float *a, int64_t lda, const float *b, int64_t ldb, const float *bias, float *c,
                int64_t ldc, int64_t m, int64_t n, int64_t k, void *slabs, int64_t slab_bytes, int *n_slabs,
-               hipStream_t st) {
+               hipStream_t st, GemmCall call) {
     switch (layout) {
         case 0:
             GIST_REQUIRE(lda >= k && ldb >= k && ldc >= n, "gist_gemm_slabs_f32: leading dimension too small");
             return launch_gemm<true, true>("gist_gemm_slabs_f32", a, lda, b, ldb, bias, c, ldc, m, n, k, slabs,
-                                           slab_bytes, st, n_slabs);
+                                           slab_bytes, st, n_slabs, call);
         case 1:
             GIST_REQUIRE(lda >= k && ldb >= n && ldc >= n, "gist_gemm_slabs_f32: leading dimension too small");
             return launch_gemm<true, false>("gist_gemm_slabs_f32", a, lda, b, ldb, bias, c, ldc, m, n, k, slabs,
-                                            slab_bytes, st, n_slabs);
+                                            slab_bytes, st, n_slabs, call);
         case 2:
             GIST_REQUIRE(lda >= m && ldb >= n && ldc >= n, "gist_gemm_slabs_f32: leading dimension too small");
             return launch_gemm<false, false>("gist_gemm_slabs_f32", a, lda, b, ldb, bias, c, ldc, m, n, k, slabs,
-                                             slab_bytes, st, n_slabs);
+                                             slab_bytes, st, n_slabs, call);
     }
     set_error("gist_gemm_slabs_f32: layout must be 0 (NT), 1 (NN) or 2 (TN)");
     return GIST_EINVAL;
@@ -875,26 +775,6 @@ extern "C" int gist_gemm_slabs_f32(int layout, const float *a, int64_t lda, cons
                                     gist::as_stream(stream));
     *n_slabs = ns;
     return rc;
-}
-
-/* 1 if a gist_gemm_* call of this shape splits its own operands in the current mode (f16x3 / bf16x3 pre-split
- * kernels: it needs the large workspace of gist_gemm_workspace_bytes and reduces its k slices itself). */
-extern "C" int gist_gemm_splits_operands(int64_t m, int64_t n, int64_t k) {
-    if (m <= 0 || n <= 0 || k <= 0) return 0;
-    return (gist::h3_eligible(m, n, k) || gist::b3_eligible(m, n, k)) ? 1 : 0;
-}
-
-extern "C" int64_t gist_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k) {
-    if (m <= 0 || n <= 0 || k <= 0) return 0;
-    const int64_t h3 = gist::h3_workspace_bytes(m, n, k);
-    if (h3 > 0) return h3;
-    const int64_t b3 = gist::b3_workspace_bytes(m, n, k);
-    if (b3 > 0) return b3;
-    const int64_t c3 = gist::b3c_slab_bytes(m, n, k);      // >= 0: the convert-on-load bf16x3 path takes the shape
-    const int s0 = gist::choose_cfg(m, n, k).splits, s1 = gist::choose_cfg(m, n, k, true).splits;
-    const int s = s0 > s1 ? s0 : s1;                       // (the call that reduces itself / gist_gemm_slabs_f32)
-    const int64_t f32 = s > 1 ? (int64_t)s * m * n * 4 : 0;
-    return c3 > f32 ? c3 : f32;                            // (unaligned operands fall back to the fp32 kernel)
 }
 
 extern "C" int gist_gemm_nt_f32(const float *a, int64_t lda, const float *w, int64_t ldw,

@@ -52,7 +52,7 @@ namespace gist {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float b3_f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int B3_TM = 256, B3_TN = 128, B3_BK = 32;
+// (the tile B3_TM x B3_TN = 256 x 128 and k per tile B3_BK = 32: gemm_plan.h)
 constexpr int B3_THREADS = 512;
 constexpr int B3_STAGES = 2;
 constexpr int B3_SKEW = 16;      // MFMAs by which waves 4-7 run behind waves 0-3 inside a k step
@@ -529,7 +529,7 @@ __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
 //   Q (after the last slab pair's third term):  A_{t+1}, B_{t+1} complete -> read a2, a3 of A_{t+1}
 //     (dead after a2.b2), then the first slab pair of B_{t+1} piece by piece, then a1 of A_{t+1}
 // The DMA has the 144 MFMAs between P and Q to land.
-constexpr int B3W_TN = 256;
+// (B3W_TN = 256: gemm_plan.h)
 constexpr int B3W_B_BYTES = B3W_TN * B3_KT_BYTES;                // 48 KiB
 constexpr int B3W_LDS_BYTES = B3_A_BYTES + 2 * B3W_B_BYTES;      // 144 KiB
 
@@ -743,113 +743,7 @@ __global__ __launch_bounds__(B3_THREADS) void gemm_b3_tail_sum_kernel(B3Args g) 
         if (row + e < g.m) g.c[(int64_t)(row + e) * g.ldc + col] = sum[e] + bv;
 }
 
-// ---- host side ------------------------------------------------------------------------------------
-int64_t b3_kpad(int64_t k) { return ceil_div(k, 2 * B3_BK) * (2 * B3_BK); }      // an even number of k tiles
-
-// Split-K: an output with fewer than ~3/4 of 256 tiles leaves CUs idle (one 512-thread workgroup per
-// CU), so its k range is cut into `splits` slices, one workgroup each (blockIdx.y), which write fp32
-// slabs that one pass sums (+ bias).  A slice keeps >= 8 k tiles; slices are an even number of tiles.
-int b3_splits(int64_t m, int64_t n, int64_t k) {
-    const int64_t tiles = ceil_div(m, B3_TM) * ceil_div(n, B3_TN);
-    const int64_t n_kt = b3_kpad(k) / B3_BK;
-    const int forced = (int)tune(GIST_TUNE_GEMM_SPLITS);
-    int64_t s = forced > 0 ? forced : (tiles >= 192 ? 1 : 256 / tiles);
-    if (forced <= 0 && tiles > 128 && tiles < 192) {
-        // between half a chip and 3/4 of one (dW_0 of the H = 4096 step: 160 tiles) one slice runs a single
-        // under-full round; the slice count that minimises rounds x k tiles per slice wins even with the
-        // slab sum (4096 x 1204 x 2046: 3 slices = 2 rounds of 22 k tiles against 1 of 64; 165 -> 154 us
-        // per call with the sum in the call; probe removed, `git show 4165530:scripts/b3_split_probe.py`)
-        int64_t best = n_kt + 4;      // one slice: no slabs (the +4: a slab sum costs about 4 k tiles)
-        for (int64_t c = 2; c <= 4; ++c) {
-            const int64_t per = ceil_div(ceil_div(n_kt, c), 2) * 2;
-            const int64_t cost = ceil_div(tiles * c, 256) * per + 8;
-            if (per >= 8 && cost < best) { best = cost; s = c; }
-        }
-    }
-    if (forced <= 0 && s > n_kt / 8) s = n_kt / 8;
-    if (s > n_kt / 2) s = n_kt / 2;
-    if (s < 1) s = 1;
-    const int64_t per = ceil_div(ceil_div(n_kt, s), 2) * 2;
-    return (int)ceil_div(n_kt, per);
-}
-// Tail units: with one k slice and T tiles on P = 256 one-workgroup CUs the last round holds r = T mod P
-// tiles and leaves P - r CUs idle for a whole tile's k loop (a batch of 2049-2304 rows has a ninth row
-// tile: 288 tiles = one round + 32, twice the time of 256).  The r tiles of that round are cut into
-// floor(P / r) k slices of >= 8 k tiles, one workgroup each, so the round lasts 1 / slices of a tile;
-// the slices of a tile leave fp32 partials that gemm_b3_tail_sum_kernel, the next launch, adds in slice
-// order (a hand-over inside the kernel -- the last slice to arrive sums -- was measured first: its
-// device-scope fences cost 45-70 us per launch).  Nothing here depends on anything but the shape.
-struct B3Tail { int dp_tiles, splits, kt; };
-constexpr int B3_CUS = 256;
-static B3Tail b3_tail(int64_t m, int64_t n, int64_t k) {
-    const int64_t tiles = ceil_div(m, B3_TM) * ceil_div(n, B3_TN);
-    B3Tail t{(int)tiles, 1, 0};
-    if (tune(GIST_TUNE_B3_TAIL) == 1.0 || tiles <= B3_CUS) return t;
-    const int64_t r = tiles % B3_CUS;
-    if (r == 0 || r > B3_CUS / 2) return t;
-    const int64_t n_kt = b3_kpad(k) / B3_BK;
-    int64_t s = B3_CUS / r;
-    if (s > n_kt / 8) s = n_kt / 8;
-    if (s < 2) return t;
-    const int64_t per = ceil_div(ceil_div(n_kt, s), 2) * 2;
-    s = ceil_div(n_kt, per);
-    if (s < 2) return t;
-    t.dp_tiles = (int)(tiles - r); t.splits = (int)s; t.kt = (int)per;
-    return t;
-}
-static int64_t b3_tail_bytes(int64_t m, int64_t n, int64_t k) {
-    const B3Tail t = b3_tail(m, n, k);
-    if (t.splits < 2) return 0;
-    const int64_t r = ceil_div(m, B3_TM) * ceil_div(n, B3_TN) - t.dp_tiles;
-    return r * t.splits * (int64_t)(B3_TM * B3_TN * 4);
-}
-// The 256 x 256 tile (gemm_b3_wide_kernel) takes an output that has at least one full round of such tiles
-// and that the 256 x 128 kernel would run as one k slice with no tail units (tuning hook GIST_TUNE_B3_WIDE = 1:
-// never).  On the H = 4096 step: dZ1 (256 wide tiles, one round instead of two) and dW1 (512: two instead of
-// four); the forward Z1.W1 (128) and layer 0's projections stay on the 256 x 128 kernel.
-static bool b3_wide(int64_t m, int64_t n, int64_t k) {
-    if (tune(GIST_TUNE_B3_WIDE) == 1.0) return false;
-    if (ceil_div(m, B3_TM) * ceil_div(n, B3W_TN) < B3_CUS) return false;
-    return b3_splits(m, n, k) == 1 && b3_tail(m, n, k).splits < 2;
-}
-// scratch of one call: fp32 slabs of a split-K call, or the partials of its tail units (never both)
-int64_t b3_slab_bytes(int64_t m, int64_t n, int64_t k) {
-    const int s = b3_splits(m, n, k);
-    return s > 1 ? (int64_t)s * m * n * 4 : b3_tail_bytes(m, n, k);
-}
-
-// Shapes the bf16x3 path takes: enough workgroups (256 x 128 tiles x k slices) to occupy the chip, and
-// enough flops to pay for the pre-pass (~ the f16x3 path's thresholds).  Everything else stays on the
-// fp32 kernel.
-static bool b3_shape_ok(int64_t m, int64_t n, int64_t k, double default_min_gflop) {
-    const double t_gflop = tune(GIST_TUNE_H3_MIN_GFLOP), t_tiles = tune(GIST_TUNE_H3_MIN_TILES);
-    const double min_gflop = t_gflop > 0.0 ? t_gflop : default_min_gflop;
-    const int min_wgs = t_tiles > 0.0 ? (int)t_tiles : 128;
-    // (an explicit tile threshold -- tests -- also lifts the minimum extents: the kernel itself
-    // handles any m, n, k >= 1)
-    if (t_tiles <= 0.0 && (m < 64 || n < 64 || k < 64)) return false;
-    if (m < 1 || n < 1 || k < 1) return false;
-    const int64_t tiles = ceil_div(m, B3_TM) * ceil_div(n, B3_TN);
-    if (tiles * b3_splits(m, n, k) < min_wgs) return false;
-    if (t_tiles <= 0.0 && (double)m * (double)n < 0.6 * (double)(tiles * B3_TM * B3_TN)) return false;   // mostly padding
-    if (2.0 * (double)m * (double)n * (double)k < min_gflop * 1e9) return false;
-    if (b3_kpad(k) * 6 >= (1LL << 23)) return false;          // 32-bit DMA byte offsets: 256 rows * pitch
-    return true;
-}
-bool b3_eligible(int64_t m, int64_t n, int64_t k) { return h3_mode() == 2 && b3_shape_ok(m, n, k, 16.0); }
-// (inside the step, operands split once per tensor: measured break-even between 8.6 GFLOP -- the h = 1024
-// projections, 0.595 vs 0.587 ms/step on the fp32 kernel -- and 10.1 GFLOP -- the layer-0 projections at
-// h = 2048, 1.071 vs 1.095)
-bool b3_eligible_kept(int64_t m, int64_t n, int64_t k) { return b3_shape_ok(m, n, k, 9.0); }
-
-static int64_t b3_operand_bytes(int64_t m, int64_t n, int64_t k) {
-    return ceil_div((m + n) * b3_kpad(k) * 6 + 512, 256) * 256;
-}
-int64_t b3_workspace_bytes(int64_t m, int64_t n, int64_t k) {
-    if (!b3_eligible(m, n, k)) return 0;
-    return b3_operand_bytes(m, n, k) + b3_slab_bytes(m, n, k);
-}
-
+// ---- host side: the plan (gemm_plan.h) says slices, tail units, tile and where the scratch sits ------------
 // One launch for up to B3_SPLIT_MAX_JOBS splits: the grid is partitioned over the jobs, in list order.
 int b3_split_jobs(const B3Dual *jobs, int n_jobs, hipStream_t st) {
     if (n_jobs < 1 || n_jobs > B3_SPLIT_MAX_JOBS) {
@@ -881,9 +775,10 @@ int b3_split_jobs(const B3Dual *jobs, int n_jobs, hipStream_t st) {
 }
 int b3_dual_split(const B3Dual &d, hipStream_t st) { return b3_split_jobs(&d, 1, st); }
 
-int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, const float *bias, float *c,
-                     int64_t ldc, int64_t m, int64_t n, int64_t k, float *slabs, int64_t slab_bytes,
-                     hipStream_t st, int *deferred) {
+// slabs: the plan's scratch (fp32 slabs of the k slices, or the tail units' partials).  deferred != NULL: the caller's
+// consumer sums the slabs (slab s at slabs + s m n, in slab order; bias must be null), *deferred = their number.
+static int b3_launch(const char *name, const GemmPlan &pl, const uint16_t *sa, const uint16_t *sb, const float *bias,
+                     float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, float *slabs, hipStream_t st, int *deferred) {
     static DeviceOnce once;
     int dev;
     if (once.needed(&dev)) {
@@ -898,72 +793,55 @@ int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, c
         }
         once.done(dev);
     }
-    if (ldc * B3_TM * 4 >= (1LL << 31)) {      // the store epilogue's 32-bit byte offsets: 256 rows x ldc
-        set_error("%s: leading dimension of the output >= 2^21 elements on the bf16x3 path", name);
-        return GIST_EINVAL;
-    }
     B3Args g;
     const int64_t kpad = b3_kpad(k);
     g.a = sa; g.lda = kpad; g.b = sb; g.ldb = kpad; g.bias = bias; g.c = c; g.ldc = ldc;
     g.m = (int)m; g.n = (int)n; g.kpad = (int)kpad;
-    g.tiles_m = (int)ceil_div(m, B3_TM);
-    g.tiles_n = (int)ceil_div(n, B3_TN);
-    const int64_t n_kt = kpad / B3_BK;
-    int splits = b3_splits(m, n, k);
-    if (splits > 1 && (slabs == nullptr || slab_bytes < (int64_t)splits * m * n * 4)) splits = 1;
-    g.kt_per_split = (int)(ceil_div(ceil_div(n_kt, splits), 2) * 2);
-    splits = (int)ceil_div(n_kt, g.kt_per_split);
+    g.tiles_m = (int)ceil_div(m, pl.tile_m);
+    g.tiles_n = (int)ceil_div(n, pl.tile_n);
+    g.kt_per_split = (int)(pl.k_per_split / B3_BK);
     g.split_stride = 0;
-    if (splits > 1) { g.c = slabs; g.ldc = n; g.split_stride = m * n; g.bias = nullptr; }
-    g.dp_tiles = g.tiles_m * g.tiles_n; g.tail_splits = 1; g.tail_kt = 0;
-    g.tail_partials = nullptr;
-    unsigned grid_x = (unsigned)g.dp_tiles;
-    if (splits == 1 && slabs != nullptr && aligned16(slabs)) {
-        const B3Tail t = b3_tail(m, n, k);
-        if (t.splits > 1 && slab_bytes >= b3_tail_bytes(m, n, k)) {
-            const int r = g.dp_tiles - t.dp_tiles;
-            g.dp_tiles = t.dp_tiles; g.tail_splits = t.splits; g.tail_kt = t.kt;
-            g.tail_partials = slabs;
-            grid_x = (unsigned)(t.dp_tiles + r * t.splits);
-        }
-    }
+    if (pl.splits > 1) { g.c = slabs; g.ldc = n; g.split_stride = m * n; g.bias = nullptr; }
+    const int tail_tiles = g.tiles_m * g.tiles_n - pl.whole_tiles;
+    g.dp_tiles = pl.whole_tiles; g.tail_splits = pl.tail_splits; g.tail_kt = (int)(pl.tail_k / B3_BK);
+    g.tail_partials = pl.tail_splits > 1 ? slabs : nullptr;
     const int64_t slot = timer_begin(tl_timer, 2, m, n, k, st);      // kind 2: the main kernel (+ slab sum)
-    if (b3_wide(m, n, k) && splits == 1 && g.tail_splits == 1) {
-        g.tiles_n = (int)ceil_div(n, B3W_TN);
-        g.dp_tiles = g.tiles_m * g.tiles_n;
+    if (pl.tile_n == B3W_TN)
         hipLaunchKernelGGL(gemm_b3_wide_kernel, dim3((unsigned)g.dp_tiles), dim3(B3_THREADS), B3W_LDS_BYTES, st, g);
-        const int rc = launch_status(name);
-        if (deferred) *deferred = 1;
-        timer_end(tl_timer, slot, st);
-        return rc;
-    }
-    hipLaunchKernelGGL(gemm_b3_kernel, dim3(grid_x, (unsigned)splits),
-                       dim3(B3_THREADS), B3_STAGES * B3_BUF_BYTES, st, g);
+    else
+        hipLaunchKernelGGL(gemm_b3_kernel, dim3((unsigned)(pl.whole_tiles + tail_tiles * pl.tail_splits), (unsigned)pl.splits),
+                           dim3(B3_THREADS), B3_STAGES * B3_BUF_BYTES, st, g);
     int rc = launch_status(name);
-    if (rc == GIST_OK && g.tail_splits > 1) {
-        hipLaunchKernelGGL(gemm_b3_tail_sum_kernel, dim3((grid_x - (unsigned)g.dp_tiles) / (unsigned)g.tail_splits, 16),
-                           dim3(B3_THREADS), 0, st, g);
+    if (rc == GIST_OK && pl.tail_splits > 1) {
+        hipLaunchKernelGGL(gemm_b3_tail_sum_kernel, dim3((unsigned)tail_tiles, 16), dim3(B3_THREADS), 0, st, g);
         rc = launch_status(name);
     }
-    // deferred: the caller's consumer sums the slabs (slab s at slabs + s m n, in slab order); bias must be null
-    if (deferred) *deferred = splits;
-    else if (rc == GIST_OK && splits > 1) rc = splitk_reduce(name, slabs, m * n, splits, bias, c, ldc, m, n, st);
+    if (deferred) *deferred = pl.splits;
+    else if (rc == GIST_OK && pl.splits > 1) rc = splitk_reduce(name, slabs, m * n, pl.splits, bias, c, ldc, m, n, st);
     timer_end(tl_timer, slot, st);
     return rc;
 }
 
-// A: a_kc ? [m][k] : [k][m];  B: b_kc ? [n][k] : [k][n].  Returns 1 if the GEMM was issued,
-// 0 if this call is not for the bf16x3 path (caller falls back to fp32), < 0 on error.
-int b3_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
-            int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k,
-            void *ws, int64_t ws_bytes, hipStream_t st) {
-    if (!b3_eligible(m, n, k)) return 0;
-    if (ldc * B3_TM * 4 >= (1LL << 31)) return 0;      // the store epilogue's 32-bit byte offsets: 256 rows x ldc
-    if (ws == nullptr || !aligned16(ws) || ws_bytes < b3_workspace_bytes(m, n, k)) return 0;
+// operands split once and kept by the caller (the step); slabs: its scratch for k slices or tail units
+int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, const float *bias, float *c,
+                     int64_t ldc, int64_t m, int64_t n, int64_t k, float *slabs, int64_t slab_bytes,
+                     hipStream_t st, int *deferred) {
+    if (ldc * B3_TM * 4 >= (1LL << 31)) {      // the store epilogue's 32-bit byte offsets: 256 rows x ldc
+        set_error("%s: leading dimension of the output >= 2^21 elements on the bf16x3 path", name);
+        return GIST_EINVAL;
+    }
+    const GemmPlan pl = plan_gemm(GemmQuery{true, true, m, n, k, 2, true, ldc, GEMM_CALL_KEPT, deferred != nullptr,
+                                            slabs != nullptr && slab_bytes > 0 ? slab_bytes : 0, aligned16(slabs)});
+    return b3_launch(name, pl, sa, sb, bias, c, ldc, m, n, k, slabs, st, deferred);
+}
+
+// A gist_gemm_* call on this path.  A: a_kc ? [m][k] : [k][m];  B: b_kc ? [n][k] : [k][n].
+int b3_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
+            int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws, hipStream_t st) {
     const int64_t kpad = b3_kpad(k);
-    uint16_t *sa = static_cast<uint16_t *>(ws);
+    uint16_t *sa = reinterpret_cast<uint16_t *>(static_cast<char *>(ws) + pl.operand_offset);
     uint16_t *sb = sa + m * kpad * 3;
-    float *slabs = reinterpret_cast<float *>(static_cast<char *>(ws) + b3_operand_bytes(m, n, k));
+    float *slabs = reinterpret_cast<float *>(static_cast<char *>(ws) + pl.scratch_offset);
     auto split = [&](bool kc, const float *src, int64_t ld, int64_t rows, uint16_t *dst) {
         B3Dual d{};
         d.src = src; d.ld = ld;
@@ -972,11 +850,9 @@ int b3_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda,
         return b3_dual_split(d, st);
     };
     int rc = split(a_kc, a, lda, m, sa);
+    if (rc == GIST_OK) rc = split(b_kc, b, ldb, n, sb);
     if (rc != GIST_OK) return rc;
-    rc = split(b_kc, b, ldb, n, sb);
-    if (rc != GIST_OK) return rc;
-    rc = b3_gemm_presplit(name, sa, sb, bias, c, ldc, m, n, k, slabs, b3_slab_bytes(m, n, k), st, nullptr);
-    return rc == GIST_OK ? 1 : rc;
+    return b3_launch(name, pl, sa, sb, bias, c, ldc, m, n, k, slabs, st, nullptr);
 }
 
 }  // namespace gist

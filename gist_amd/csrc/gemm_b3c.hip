@@ -22,7 +22,6 @@
 // chunk kg (k = 8 kg .. 8 kg + 7) of row r sits at position kg ^ ((r >> 1) & 3) of its row, so the eight
 // lanes of a ds_read_b128 group (rows r .. r + 7, one kg) hit eight different 16-byte slots of the
 // 128-byte bank line, and so do the writes of eight consecutive chunks.
-#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -49,7 +48,7 @@ struct C3Args {
     float *tail;
 };
 
-constexpr int C3_BK = 32;
+// (C3_BK = 32, k per tile: gemm_plan.h)
 
 typedef float c3_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 c3_bf16x2 __attribute__((ext_vector_type(2)));
@@ -536,23 +535,6 @@ __global__ __launch_bounds__(256) void gemm_b3c_tail_sum_kernel(C3Args g, int tm
 }
 
 // ---- host side ----------------------------------------------------------------------------------
-// Which calls take this kernel by default.  MEASURED (profiles/r03_b3c_bench.txt; us,
-// standalone calls, fp32 kernel -> this kernel with 64 x 64 tiles and one k slice): NT 2046 x 1024 x 2048
-// 76 -> 59, NT 2046 x 1024 x 1204 50 -> 43, NN 2046 x 2048 x 1024 73 -> 66, NT 2046 x 512 x 1204 24.9 -> 22.3;
-// TN (both operands k-major: 16 scalar row loads per thread and step) 1024 x 2048 x 2046 68.5 -> 64, but
-// 1024 x 1204 x 2046 54 -> 60 and 512 x 1024 x 2046 25 -> 43.  So by default the NT and NN layouts from
-// 2 GFLOP with at least 256 tiles of 64 x 64 come here and TN stays on the fp32 kernel; the tuning hook
-// GIST_TUNE_B3C = 2 sends every shape with m, n, k >= 64 (tests, sweeps), 1 none.  A k step still costs
-// several hundred cycles on top of its MFMAs; the matrix pipe is far from saturated.
-static bool b3c_geometry_ok(int64_t m, int64_t n, int64_t k) {
-    return h3_mode() == 2 && (int)tune(GIST_TUNE_B3C) != 1 && m >= 64 && n >= 64 && k >= 64;
-}
-bool b3c_shape_ok(int64_t m, int64_t n, int64_t k) {
-    if (!b3c_geometry_ok(m, n, k)) return false;
-    if ((int)tune(GIST_TUNE_B3C) == 2) return true;
-    return ceil_div(m, 64) * ceil_div(n, 64) >= 256 && 2.0 * (double)m * (double)n * (double)k >= 2e9;
-}
-
 template <bool A_KC, bool B_KC, int TM, int TN>
 static int b3c_launch(const char *name, C3Args &g, int splits, hipStream_t st) {
     const size_t smem = (size_t)3 * 3 * (TM + TN) * 64;      // three stages of (A, B) x 3 planes
@@ -583,96 +565,28 @@ static int b3c_launch(const char *name, C3Args &g, int splits, hipStream_t st) {
     return rc;
 }
 
-// Tile and k slices (fp32 slabs, reduced by the call or left to the consumer).  Fitted to profiles/r03_b3c_bench.txt.
-static void b3c_choice(int64_t m, int64_t n, int64_t k, int *tm, int *tn, int *splits) {
-    const int t_tile = (int)tune(GIST_TUNE_GEMM_TILE), t_split = (int)tune(GIST_TUNE_GEMM_SPLITS);
-    auto tiles = [&](int a, int b) { return ceil_div(m, a) * ceil_div(n, b); };
-    // 64 x 64 unless the output has 256 tiles of 128 x 128 (measured: NN 2046 x 2048 x 1024 62 -> 54 us; with fewer
-    // tiles the 128 x 128 grid leaves CUs idle or needs k slices and loses: NT 2046 x 1024 x 2048 59 vs 82 / 60 with
-    // 1 / 2 slices; 128 x 64 is slower than 64 x 64 on every per-rank shape).  A k step of the 128 x 128 tile takes
-    // ~2700 cycles for 1536 of MFMA, one of the 64 x 64 tile ~1200 for 384: the producers' step (176 / 88 vector
-    // instructions, 12 / 6 ds_write_b128 at ~13 issue cycles, 8 / 4 loads) sets the pace in both, and neither deeper
-    // load prefetch (PD 4-6), nor LDS writes issued before the conversion, nor cheaper instructions (v_perm for
-    // v_cvt_pk, v_sub for v_pk_add), nor half as many MFMA issues (32 x 32 x 16) moved it
-    // (probe removed; `git show 4165530:scripts/b3c_probe.py`).
-    *tm = 64; *tn = 64;
-    if (tiles(128, 128) >= 256) { *tm = 128; *tn = 128; }
-    if (t_tile == 64) { *tm = 64; *tn = 64; }
-    if (t_tile == 128 || t_tile == 12864) { *tm = 128; *tn = 64; }
-    if (t_tile == 128128) { *tm = 128; *tn = 128; }
-    const int64_t wgs = tiles(*tm, *tn);
-    const int64_t kt = ceil_div(k, C3_BK);
-    int64_t sp = 1;
-    if (wgs < 128) sp = 256 / wgs;                            // (only reachable through the tuning hook)
-    if (sp > kt / 8) sp = kt / 8;                             // a slice keeps >= 8 k tiles
-    if (t_split > 0) sp = t_split;
-    if ((int)tune(GIST_TUNE_B3C_SPLITS) > 0) sp = (int)tune(GIST_TUNE_B3C_SPLITS);
-    if (sp > kt) sp = kt;
-    *splits = (int)(sp < 1 ? 1 : sp);
-}
-
-// Tail units (as gemm_b3.hip's): one k slice and T tiles on S workgroup slots (64 x 64 tiles: two workgroups per CU = 512,
-// the larger tiles one = 256) with 0 < T mod S <= S / 2 -- a batch of 2049-2112 rows makes 528 tiles of 64 x 64 out of 512,
-// 272 of 128 x 128 out of 256: a second round for 16 tiles -- cut the tiles of the last round into k slices of >= 4 k tiles.
-struct C3Tail { int dp_tiles, splits, k_per; };
-static C3Tail b3c_tail(int64_t m, int64_t n, int64_t k, int tm, int tn) {
-    const int64_t tiles = ceil_div(m, tm) * ceil_div(n, tn), slots = (tm == 64 && tn == 64) ? 512 : 256;
-    C3Tail t{(int)tiles, 1, 0};
-    if ((int)tune(GIST_TUNE_B3_TAIL) == 1 || tiles <= slots) return t;
-    const int64_t r = tiles % slots, kt = ceil_div(k, C3_BK);
-    if (r == 0 || r > slots / 2) return t;
-    int64_t s = std::min<int64_t>(slots / r, kt / 4);
-    if (s < 2) return t;
-    const int64_t per = ceil_div(kt, s);
-    s = ceil_div(kt, per);
-    if (s < 2) return t;
-    t.dp_tiles = (int)(tiles - r); t.splits = (int)s; t.k_per = (int)(per * C3_BK);
-    return t;
-}
-// (tail = false: a layout this path does not take by default -- TN, the weight gradients: its scratch must not make a
-// slab buffer exist that the caller's routing reads as "this projection's slices are summed by its consumer")
-int64_t b3c_slab_bytes(int64_t m, int64_t n, int64_t k, bool tail) {
-    if (!b3c_shape_ok(m, n, k)) return -1;
-    int tm, tn, sp;
-    b3c_choice(m, n, k, &tm, &tn, &sp);
-    if (sp > 1) return (int64_t)sp * m * n * 4;
-    if (!tail) return 0;
-    const C3Tail t = b3c_tail(m, n, k, tm, tn);
-    return t.splits > 1 ? (ceil_div(m, tm) * ceil_div(n, tn) - t.dp_tiles) * (int64_t)t.splits * tm * tn * 4 : 0;
-}
-
-// Returns 1 if the projection was issued here, 0 if this call is not for this path (the caller falls back
-// to the fp32 kernel), < 0 on error.  deferred as in gemm.hip's launch_gemm.
-int b3c_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b, int64_t ldb,
-             const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws,
-             int64_t ws_bytes, hipStream_t st, int *deferred) {
-    if (!b3c_shape_ok(m, n, k)) return 0;
-    if (!(aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0 && lda >= 4 && ldb >= 4)) return 0;
-    if (!a_kc && b_kc) return 0;                                     // (no caller uses this layout)
-    if ((int)tune(GIST_TUNE_B3C) != 2 && !a_kc) return 0;            // by default: NT and NN only (see above)
-    int tm = 128, tn = 128, splits = 1;
-    b3c_choice(m, n, k, &tm, &tn, &splits);
-    if (splits > 1 && (ws == nullptr || ws_bytes < (int64_t)splits * m * n * 4)) splits = 1;
+// A gist_gemm_* call on this path (which shapes, tile, slices and tail units: gemm_plan.cpp).  ws: fp32 slabs of the k
+// slices, or the tail units' partials.  deferred as in gemm.hip's launch_gemm.
+int b3c_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
+             int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws,
+             hipStream_t st, int *deferred) {
+    const int splits = pl.splits;
     C3Args g;
     g.a = a; g.lda = lda; g.b = b; g.ldb = ldb; g.bias = bias; g.c = c; g.ldc = ldc;
     g.m = (int)m; g.n = (int)n; g.k = (int)k;
-    g.k_per_split = (int)(ceil_div(ceil_div(k, C3_BK), splits) * C3_BK);
-    splits = (int)ceil_div(k, g.k_per_split);
+    g.k_per_split = (int)pl.k_per_split;
     g.split_stride = 0;
     if (splits > 1) { g.c = static_cast<float *>(ws); g.ldc = n; g.split_stride = m * n; g.bias = nullptr; }
     g.dp_tiles = 0; g.tail_splits = 1; g.tail_k = 0; g.tail = nullptr;
-    if (splits == 1 && ws != nullptr && aligned16(ws)) {
-        const C3Tail t = b3c_tail(m, n, k, tm, tn);
-        if (t.splits > 1 && ws_bytes >= (ceil_div(m, tm) * ceil_div(n, tn) - t.dp_tiles) * (int64_t)t.splits * tm * tn * 4) {
-            g.dp_tiles = t.dp_tiles; g.tail_splits = t.splits; g.tail_k = t.k_per; g.tail = static_cast<float *>(ws);
-        }
+    if (pl.tail_splits > 1) {
+        g.dp_tiles = pl.whole_tiles; g.tail_splits = pl.tail_splits; g.tail_k = (int)pl.tail_k; g.tail = static_cast<float *>(ws);
     }
     const int64_t slot = timer_begin(tl_timer, 2, m, n, k, st);      // kind 2: a bf16x3 main kernel
     int rc;
 #define C3_GO(AK, BK_)                                                                        \
-    rc = tm == 64 ? b3c_launch<AK, BK_, 64, 64>(name, g, splits, st)                          \
-         : tn == 64 ? b3c_launch<AK, BK_, 128, 64>(name, g, splits, st)                       \
-                    : b3c_launch<AK, BK_, 128, 128>(name, g, splits, st)
+    rc = pl.tile_m == 64 ? b3c_launch<AK, BK_, 64, 64>(name, g, splits, st)                   \
+         : pl.tile_n == 64 ? b3c_launch<AK, BK_, 128, 64>(name, g, splits, st)                \
+                           : b3c_launch<AK, BK_, 128, 128>(name, g, splits, st)
     if (a_kc && b_kc) { C3_GO(true, true); }
     else if (a_kc) { C3_GO(true, false); }
     else { C3_GO(false, false); }
@@ -682,7 +596,7 @@ int b3c_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda
         else rc = splitk_reduce(name, static_cast<const float *>(ws), m * n, splits, bias, c, ldc, m, n, st);
     }
     timer_end(tl_timer, slot, st);
-    return rc == GIST_OK ? 1 : rc;
+    return rc;
 }
 
 }  // namespace gist

@@ -33,8 +33,7 @@ namespace gist {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int H3_T = 128;        // block tile edge
-constexpr int H3_BK = 32;        // k per tile = 32-bit words per image row
+// (H3_T = 128, the block tile edge, and H3_BK = 32, k per tile = 32-bit words per image row: gemm_plan.h)
 constexpr int H3_IMG = H3_T * H3_BK;              // words per image (16 KiB)
 constexpr int H3_BUF_BYTES = 2 * H3_IMG * 4;      // A + B image of one stage
 
@@ -531,61 +530,10 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(H3Args g) {
 template __global__ void gemm_h3_kernel<128>(H3Args);
 template __global__ void gemm_h3_kernel<64>(H3Args);
 
-// ---- host side ----------------------------------------------------------------------------
-static std::atomic<int> g_h3_mode{-1};      // -1: read GIST_GEMM_MODE on first use
-
-int h3_mode() {
-    int m = g_h3_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char *e = getenv("GIST_GEMM_MODE");
-        // default: large projections as three bf16 pieces per operand (all 24 bits, six cross terms:
-        // error at the fp32-MFMA kernel's level, gemm_b3.hip), everything else fp32 MFMA
-        m = 2;
-        if (e && (!strcmp(e, "f32") || !strcmp(e, "0"))) m = 0;
-        else if (e && (!strcmp(e, "f16x3") || !strcmp(e, "1"))) m = 1;
-        else if (e && (!strcmp(e, "bf16x3") || !strcmp(e, "2"))) m = 2;
-        int expected = -1;
-        g_h3_mode.compare_exchange_strong(expected, m, std::memory_order_relaxed);
-        m = g_h3_mode.load(std::memory_order_relaxed);
-    }
-    return m;
-}
-
-int64_t h3_kpad(int64_t k) { return ceil_div(k, H3_BK) * H3_BK; }
-
-// Shapes the split path takes: enough 128x128 tiles to occupy the chip and enough flops to
-// pay for the pre-pass.  Break-even measured at ~20 GFLOP when every call splits its own
-// operands (probe removed; `git show 4165530:scripts/h3_bench.py`) and at ~4 GFLOP inside the
-// step, which shares one split of an operand between the GEMMs that use it (bench.py
-// --n-hidden 1024: 0.606 -> 0.551 ms/step).
-// Everything else stays on the fp32 kernel.
-static bool h3_shape_ok(int64_t m, int64_t n, int64_t k, double default_min_gflop) {
-    const double t_gflop = tune(GIST_TUNE_H3_MIN_GFLOP), t_tiles = tune(GIST_TUNE_H3_MIN_TILES);
-    const double min_gflop = t_gflop > 0.0 ? t_gflop : default_min_gflop;
-    const int min_tiles = t_tiles > 0.0 ? (int)t_tiles : 64;
-    // (an explicit tile threshold -- tests -- also lifts the minimum extents: the kernel itself
-    // handles any m, n, k >= 1)
-    if (t_tiles <= 0.0 && (m < 64 || n < 64 || k < 64)) return false;
-    if (m < 1 || n < 1 || k < 1) return false;
-    if (ceil_div(m, H3_T) * ceil_div(n, H3_T) < min_tiles) return false;
-    if (2.0 * (double)m * (double)n * (double)k < min_gflop * 1e9) return false;
-    if (h3_kpad(k) >= (1LL << 22)) return false;
-    return true;
-}
-bool h3_eligible(int64_t m, int64_t n, int64_t k) { return h3_mode() == 1 && h3_shape_ok(m, n, k, 16.0); }
-bool h3_eligible_kept(int64_t m, int64_t n, int64_t k) { return h3_shape_ok(m, n, k, 4.0); }
-
-// workspace: [inv_a: m floats][inv_b: n floats][max bits: m + n] padded to 256 B, then the splits
-static inline int64_t h3_head_bytes(int64_t m, int64_t n) { return ceil_div((m + n) * 8, 256) * 256; }
-
-int64_t h3_workspace_bytes(int64_t m, int64_t n, int64_t k) {
-    if (!h3_eligible(m, n, k)) return 0;
-    return h3_head_bytes(m, n) + (m + n) * h3_kpad(k) * 4;
-}
-
-int h3_gemm_presplit(const char *name, const uint32_t *sa, const float *inv_a, const uint32_t *sb,
-                     const float *inv_b, const float *bias, float *c, int64_t ldc, int64_t m,
-                     int64_t n, int64_t k, hipStream_t st) {
+// ---- host side: the plan (gemm_plan.h) says tile and workspace layout --------------------------------
+static int h3_launch(const char *name, const GemmPlan &pl, const uint32_t *sa, const float *inv_a, const uint32_t *sb,
+                     const float *inv_b, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k,
+                     hipStream_t st) {
     const int64_t kpad = h3_kpad(k);
     static DeviceOnce once;
     int dev;
@@ -606,12 +554,9 @@ int h3_gemm_presplit(const char *name, const uint32_t *sa, const float *inv_a, c
     g.a = sa; g.lda = kpad; g.b = sb; g.ldb = kpad; g.inv_a = inv_a; g.inv_b = inv_b; g.bias = bias;
     g.c = c; g.ldc = ldc; g.m = (int)m; g.n = (int)n; g.kpad = (int)kpad;
     g.tiles_n = (int)ceil_div(n, H3_T);
-    // 64-row A tiles when 128-row tiles would leave CUs without a second workgroup
-    const int t_tm = (int)tune(GIST_TUNE_H3_TM);      // 0 = auto, 64 / 128 = forced
-    const bool tm64 = t_tm ? t_tm == 64 : ceil_div(m, 128) * g.tiles_n < 512;
-    g.tiles_m = (int)ceil_div(m, tm64 ? 64 : 128);
+    g.tiles_m = (int)ceil_div(m, pl.tile_m);
     const int64_t slot = timer_begin(tl_timer, 2, m, n, k, st);      // kind 2: the main kernel alone
-    if (tm64)
+    if (pl.tile_m == 64)
         hipLaunchKernelGGL(gemm_h3_kernel<64>, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(256),
                            2 * (64 * 128 + H3_IMG * 4), st, g);
     else
@@ -619,6 +564,14 @@ int h3_gemm_presplit(const char *name, const uint32_t *sa, const float *inv_a, c
                            2 * H3_BUF_BYTES, st, g);
     timer_end(tl_timer, slot, st);
     return launch_status(name);
+}
+
+// operands split once and kept by the caller (the step)
+int h3_gemm_presplit(const char *name, const uint32_t *sa, const float *inv_a, const uint32_t *sb,
+                     const float *inv_b, const float *bias, float *c, int64_t ldc, int64_t m,
+                     int64_t n, int64_t k, hipStream_t st) {
+    const GemmPlan pl = plan_gemm(gemm_query(0, m, n, k, 1, GEMM_CALL_KEPT, false));
+    return h3_launch(name, pl, sa, inv_a, sb, inv_b, bias, c, ldc, m, n, k, st);
 }
 
 int h3_split_rows(const float *src, int64_t ld, int64_t rows, int64_t k, uint32_t *dst, float *inv,
@@ -645,18 +598,13 @@ int h3_dual_split(const H3Dual &d, hipStream_t st) {
     return launch_status("h3_dual_split");
 }
 
-// A: a_kc ? [m][k] : [k][m];  B: b_kc ? [n][k] : [k][n].  Returns 1 if the GEMM was issued,
-// 0 if this call is not for the split path (caller falls back to fp32), < 0 on error.
-int h3_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
-            int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k,
-            void *ws, int64_t ws_bytes, hipStream_t st) {
-    if (!h3_eligible(m, n, k)) return 0;
-    if (!(aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0)) return 0;
-    if (ws == nullptr || !aligned16(ws) || ws_bytes < h3_workspace_bytes(m, n, k)) return 0;
+// A gist_gemm_* call on this path.  A: a_kc ? [m][k] : [k][m];  B: b_kc ? [n][k] : [k][n].
+int h3_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
+            int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws, hipStream_t st) {
     const int64_t kpad = h3_kpad(k);
     float *inv_a = static_cast<float *>(ws), *inv_b = inv_a + m;
     unsigned *max_a = reinterpret_cast<unsigned *>(inv_b + n), *max_b = max_a + m;
-    uint32_t *sa = reinterpret_cast<uint32_t *>(static_cast<char *>(ws) + h3_head_bytes(m, n));
+    uint32_t *sa = reinterpret_cast<uint32_t *>(static_cast<char *>(ws) + pl.operand_offset);
     uint32_t *sb = sa + m * kpad;
     if ((!a_kc || !b_kc) && hipMemsetAsync(max_a, 0, (size_t)(m + n) * 4, st) != hipSuccess) {
         set_error("%s: hipMemsetAsync failed", name);
@@ -669,29 +617,22 @@ int h3_gemm(const char *name, bool a_kc, bool b_kc, const float *a, int64_t lda,
         if (kc) {
             hipLaunchKernelGGL(h3_split_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, src, ld,
                                (int)k, dst, kpad, iv);
-        } else {
-            hipLaunchKernelGGL(h3_colmax_kernel,
-                               dim3((unsigned)ceil_div(rows, 64), (unsigned)ceil_div(k, 256)),
-                               dim3(256), 0, st, src, ld, (int)k, (int)rows, mx);
-            hipLaunchKernelGGL(h3_split_t_kernel,
-                               dim3((unsigned)ceil_div(rows, 64), (unsigned)ceil_div(kpad, 64)),
-                               dim3(256), 0, st, src, ld, (int)k, (int)rows, dst, kpad, mx, iv);
+            return launch_status(name);
         }
+        hipLaunchKernelGGL(h3_colmax_kernel,
+                           dim3((unsigned)ceil_div(rows, 64), (unsigned)ceil_div(k, 256)),
+                           dim3(256), 0, st, src, ld, (int)k, (int)rows, mx);
+        const int rc = launch_status(name);
+        if (rc != GIST_OK) return rc;
+        hipLaunchKernelGGL(h3_split_t_kernel,
+                           dim3((unsigned)ceil_div(rows, 64), (unsigned)ceil_div(kpad, 64)),
+                           dim3(256), 0, st, src, ld, (int)k, (int)rows, dst, kpad, mx, iv);
+        return launch_status(name);
     };
-    split(a_kc, a, lda, m, sa, max_a, inv_a);
-    split(b_kc, b, ldb, n, sb, max_b, inv_b);
-
-    const int rc = h3_gemm_presplit(name, sa, inv_a, sb, inv_b, bias, c, ldc, m, n, k, st);
-    return rc == GIST_OK ? 1 : rc;
+    int rc = split(a_kc, a, lda, m, sa, max_a, inv_a);
+    if (rc == GIST_OK) rc = split(b_kc, b, ldb, n, sb, max_b, inv_b);
+    if (rc != GIST_OK) return rc;
+    return h3_launch(name, pl, sa, inv_a, sb, inv_b, bias, c, ldc, m, n, k, st);
 }
 
 }  // namespace gist
-
-extern "C" int gist_gemm_set_mode(int mode) {
-    GIST_REQUIRE(mode >= 0 && mode <= 2,
-                 "gist_gemm_set_mode: mode must be 0 (fp32 MFMA), 1 (f16x3 split) or 2 (bf16x3 split)");
-    gist::g_h3_mode.store(mode, std::memory_order_relaxed);
-    return GIST_OK;
-}
-
-extern "C" int gist_gemm_get_mode(void) { return gist::h3_mode(); }

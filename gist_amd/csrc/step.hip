@@ -104,6 +104,13 @@ struct H3Step {
     int64_t bytes;
 };
 
+// the plan (gemm_plan.h) of a projection on the step's kept split operands in `mode`, with all the scratch it asks for
+inline GemmPlan kept_plan(int mode, int64_t m, int64_t n, int64_t k, int64_t ldc = 0) {
+    GemmQuery q = gemm_query(0, m, n, k, mode, GEMM_CALL_KEPT, false);
+    q.ldc = ldc;
+    return plan_gemm(q);
+}
+
 inline int bound_shift(double bound) {      // 2^shift * bound <= 2^13
     int e = 0;
     (void)frexp(bound, &e);                  // bound = f * 2^e, f in [0.5, 1)
@@ -133,8 +140,8 @@ H3Step h3_layout(const gist_step_plan *p, char *base, int mode) {
                                     : (p->use_layernorm ? sqrt((double)(l.n_in > 1 ? l.n_in - 1 : 1)) * keep : 0.0);
         // the class layer (k == L1-1) stays on the per-call path: its dY = dlogits comes from the CE
         // kernel, which writes no row maxima for the gradient split
-        hl.on = k < L1 - 1 && bound > 0.0 && h3_eligible_kept(n, o, i2) && h3_eligible_kept(o, i2, n) &&
-                (k == 0 || h3_eligible_kept(n, i2, o)) && l.ldz % 4 == 0 && l.ldy % 4 == 0 &&
+        hl.on = k < L1 - 1 && bound > 0.0 && kept_plan(mode, n, o, i2).kept_ok && kept_plan(mode, o, i2, n).kept_ok &&
+                (k == 0 || kept_plan(mode, n, i2, o).kept_ok) && l.ldz % 4 == 0 && l.ldy % 4 == 0 &&
                 aligned16(l.W) && aligned16(l.Z) && aligned16(l.Y) && aligned16(l.dW);
         if (!hl.on) continue;
         h.any = true;
@@ -191,9 +198,9 @@ B3Step b3_layout(const gist_step_plan *p, char *base, int mode) {
         const gist_layer_desc &l = p->layer[k];
         const int64_t i2 = 2 * l.n_in, o = l.n_out;
         B3Layer &hl = h.layer[k];
-        hl.on = b3_eligible_kept(n, o, i2) && b3_eligible_kept(o, i2, n) &&
-                (k == 0 || b3_eligible_kept(n, i2, o)) &&
-                l.ldy < (1LL << 21) && i2 < (1LL << 21);      // 32-bit byte offsets of a 256-row C tile
+        // (Y = Z . W^T, dW = dY^T . Z, dZ = dY . W, each with its output's leading dimension)
+        hl.on = kept_plan(mode, n, o, i2, l.ldy).kept_ok && kept_plan(mode, o, i2, n, i2).kept_ok &&
+                (k == 0 || kept_plan(mode, n, i2, o, i2).kept_ok);
         if (!hl.on) continue;
         h.any = true;
         hl.Zs = take(n * b3_kpad(i2) * 6);
@@ -208,8 +215,8 @@ B3Step b3_layout(const gist_step_plan *p, char *base, int mode) {
         // number of 64-row k pairs of the dW projection: the slice count is not monotone in either)
         int64_t sb = 0;
         for (int64_t rows = n; rows > 0; rows = (rows - 1) / 64 * 64) {
-            const int64_t need[3] = {b3_slab_bytes(rows, o, i2), b3_slab_bytes(o, i2, rows),
-                                     k > 0 ? b3_slab_bytes(rows, i2, o) : 0};
+            const int64_t need[3] = {kept_plan(mode, rows, o, i2).scratch_bytes, kept_plan(mode, o, i2, rows).scratch_bytes,
+                                     k > 0 ? kept_plan(mode, rows, i2, o).scratch_bytes : 0};
             for (int q = 0; q < 3; ++q) sb = need[q] > sb ? need[q] : sb;
         }
         if (sb > h.slab_bytes) h.slab_bytes = sb;
@@ -253,7 +260,7 @@ int64_t slab_need(int64_t m, int64_t n, int64_t k_max, bool k_is_rows) {
     // every 32 rows down to half the largest batch (the model's slice count is not monotone in the reduction
     // length: two neighbouring batch sizes can differ by a factor of two)
     for (int64_t rows = k_max; rows > 0 && rows >= k_max / 2; rows -= 32) {
-        const int64_t b = k_is_rows ? gemm_f32_slab_bytes(m, n, rows, true) : gemm_f32_slab_bytes(rows, n, m);
+        const int64_t b = k_is_rows ? gemm_slab_bytes(2, m, n, rows, mode) : gemm_slab_bytes(0, rows, n, m, mode);
         need = b > need ? b : need;
     }
     if (!tuned) {      // a full table overwrites its oldest entry instead of recomputing every call
@@ -631,12 +638,12 @@ int forward(const gist_step_plan *p, const StepDecisions &d, const StepState &x,
             Scope sc(p->timer, 1, n, l.n_out, 2 * l.n_in, st);
             if (d.defer && k == L1 - 1 && fl.logit_slabs != nullptr) {      // the loss kernel sums the slabs
                 GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
-                                    fl.logit_slabs, fl.logit_bytes, &logit_slabs, st));
-            } else if (d.defer && k + 1 < L1 && fl.y_slabs != nullptr && !h3_eligible(n, l.n_out, 2 * l.n_in) &&
-                       !b3_eligible(n, l.n_out, 2 * l.n_in)) {
+                                    fl.logit_slabs, fl.logit_bytes, &logit_slabs, st, GEMM_CALL_SLABS));
+            } else if (d.defer && k + 1 < L1 && fl.y_slabs != nullptr &&
+                       !splits_operands(plan_gemm(gemm_query(0, n, l.n_out, 2 * l.n_in, d.gemm_mode, GEMM_CALL_SPLITS, true)))) {
                 // the LayerNorm sums the slabs (a projection the per-call split paths take keeps their workspace)
                 GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
-                                    fl.y_slabs, fl.y_bytes, &y_slabs_n, st));
+                                    fl.y_slabs, fl.y_bytes, &y_slabs_n, st, GEMM_CALL_SLABS));
                 y_slabs = fl.y_slabs;
             } else {
                 GIST_TRY(gist_gemm_nt_f32(l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in, p->workspace,
@@ -831,7 +838,7 @@ int plain_dw(const gist_step_plan *p, const StepDecisions &d, StepState &x, int6
     } else if (d.defer && fl.dw_slabs[k] != nullptr) {      // the optimiser sums the slabs
         int ns = 1;
         GIST_TRY(gemm_slabs(2, dy, lddy, l.Z, l.ldz, nullptr, l.dW, 2 * l.n_in, l.n_out, 2 * l.n_in, n,
-                            fl.dw_slabs[k], fl.dw_bytes[k], &ns, st));
+                            fl.dw_slabs[k], fl.dw_bytes[k], &ns, st, GEMM_CALL_SLABS));
         if (ns > 1) add_segment(p, x, l.dW, l.n_out * 2 * l.n_in, fl.dw_slabs[k], ns);
     } else {
         GIST_TRY(gist_gemm_tn_f32(dy, lddy, l.Z, l.ldz, l.dW, 2 * l.n_in, l.n_out, 2 * l.n_in, n, p->workspace,

@@ -5,6 +5,8 @@ that already live in HBM, checks dtype / device / layout (the TORCH_CHECK role)
 and passes raw pointers to libgist_hip.so on torch's current HIP stream.
 CPU tensors are rejected -- there is no fallback path.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -210,6 +212,25 @@ def gemm_mode(mode=None):
 def gemm_splits_own_operands(m, n, k):
     """Does a projection of this shape take a pre-split kernel in the current GEMM mode (gist_gemm_splits_operands)?"""
     return bool(_lib.load().gist_gemm_splits_operands(int(m), int(n), int(k)))
+
+
+GEMM_LAYOUTS = {'nt': 0, 'nn': 1, 'tn': 2}
+GEMM_PATHS = ('f32', 'f16x3', 'bf16x3', 'bf16x3_load')
+GEMM_CALLS = {'splits': 0, 'kept': 1, 'slabs': 2}
+
+
+def gemm_plan(layout, m, n, k, aligned=True, call='splits', deferred=False, scratch_bytes=-1):
+    """How a projection of this shape runs in the current GEMM mode and under the current tuning hooks
+    (gist_gemm_plan_query; host only): a dict of struct gist_gemm_plan's fields, `path` as its name.  call: 'splits' (a
+    gist_gemm_* call), 'kept' (the step's kept pre-split operands) or 'slabs' (a gist_gemm_* call on a slab buffer);
+    scratch_bytes < 0: as much as the plan asks (a size query)."""
+    out = _lib.GemmPlan()
+    _lib.check(_lib.load().gist_gemm_plan_query(GEMM_LAYOUTS[layout], int(m), int(n), int(k), int(bool(aligned)),
+                                                GEMM_CALLS[call], int(bool(deferred)), int(scratch_bytes),
+                                                ctypes.byref(out)), 'gist_gemm_plan_query')
+    plan = {name: int(getattr(out, name)) for name, _ in out._fields_}
+    plan['path'] = GEMM_PATHS[plan['path']]
+    return plan
 
 
 def b3_split(src, rows=True, transposed=True, p=0.0, seed=0, offset=0, col_partials=False):

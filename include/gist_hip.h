@@ -283,6 +283,37 @@ int gist_gemm_slabs_f32(int layout, const float *a, int64_t lda, const float *b,
 int gist_gemm_set_mode(int mode);
 int gist_gemm_get_mode(void);
 
+/* How one projection runs: the record every size query above and every launcher reads (an addition: no existing
+ * signature changed, ABI 16).  A host function that touches no device, so the decision can be tested without one. */
+#define GIST_GEMM_PATH_F32 0          /* v_mfma_f32_32x32x2_f32                                          */
+#define GIST_GEMM_PATH_F16X3 1        /* mode 1, operands split by a pre-pass                            */
+#define GIST_GEMM_PATH_BF16X3 2       /* mode 2, operands split by a pre-pass (or kept by gist_sage_step) */
+#define GIST_GEMM_PATH_BF16X3_LOAD 3  /* mode 2, operands converted on load                              */
+#define GIST_GEMM_CALL_SPLITS 0       /* a gist_gemm_* call: a pre-split path splits its operands into the workspace */
+#define GIST_GEMM_CALL_KEPT 1         /* gist_sage_step's kept pre-split operands; scratch = the slab buffer        */
+#define GIST_GEMM_CALL_SLABS 2        /* a gist_gemm_* call whose workspace is a slab buffer: no room for operands  */
+typedef struct gist_gemm_plan {
+    int32_t path;              /* GIST_GEMM_PATH_*                                                                  */
+    int32_t kept_ok;           /* GIST_GEMM_CALL_KEPT: the shape passes the thresholds for keeping split operands  */
+    int32_t tile_m, tile_n;    /* output tile of the main kernel                                                   */
+    int32_t splits;            /* k slices of the main kernel (>= 1)                                               */
+    int32_t whole_tiles;       /* tiles that run their whole k range; the rest, the last round's, as tail units    */
+    int32_t tail_splits;       /* k slices of a tail unit's tile (1: no tail units)                                */
+    int32_t launches;          /* kernel launches of the call: pre-passes + main + tail sum + slab reduce          */
+    int64_t k_per_split;       /* k of one slice                                                                   */
+    int64_t tail_k;            /* k of one slice of a tail unit (0: none)                                          */
+    int64_t operand_offset;    /* per-call split operands: where they start in the workspace ...                   */
+    int64_t operand_bytes;     /* ... and their bytes (0: the call splits none)                                    */
+    int64_t scratch_offset;    /* fp32 slabs of the k slices, or the tail units' partials (never both): start ...  */
+    int64_t scratch_bytes;     /* ... and bytes                                                                    */
+    int64_t workspace_bytes;   /* all of it: what the call needs to run as planned                                 */
+} gist_gemm_plan;
+/* layout 0 NT, 1 NN, 2 TN; aligned: operands 16-byte aligned with leading dimensions % 4 == 0; call: GIST_GEMM_CALL_*;
+ * deferred: the k slices may stay slabs for the consumer (gist_gemm_slabs_f32); scratch_bytes: the workspace on hand, < 0
+ * for "as much as it asks" (a size query).  In the current mode and under the current tuning hooks. */
+int gist_gemm_plan_query(int layout, int64_t m, int64_t n, int64_t k, int aligned, int call, int deferred,
+                         int64_t scratch_bytes, gist_gemm_plan *out);
+
 /* The bf16x3 pre-pass on its own, for tests (an addition: no existing signature changed, ABI 16): one read of src[rows, cols] (row pitch ld, in
  * elements) under gist_dropout_f32's mask (p = 0: none; element index offset + r * cols + c) written as
  * the split operand with k = columns, dst_r[rows][kpad(cols)], and/or the one with k = rows,

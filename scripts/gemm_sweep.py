@@ -1,5 +1,5 @@
 """Dev tool: sweep (tile, splits) per GEMM shape in SUBPROCESSES (the override is read once
-per process) and print the best configuration -- input for gemm.hip:choose_cfg."""
+per process) and print the best configuration -- input for gemm_plan.cpp:choose_cfg (hip.gemm_plan prints what the planner chooses)."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [('nt', 2046, 4096, 8192), ('nt', 2046, 4096, 1204), ('tn', 4096, 1204, 2046),
