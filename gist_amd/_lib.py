@@ -154,6 +154,7 @@ SIGNATURES = {
     'gist_gat_step_workspace_bytes': (_i64, [_p]),
     'gist_gat_step_attn_partials_floats': (_i64, [_p]),
     'gist_gat_step': (_int, [_p, _p, _i64, _f, _f, _f, _f, _f, _i64, _int, _p]),
+    'gist_gat_step_phase': (_int, [_p, _p, _i64, _f, _f, _f, _f, _f, _i64, _int, _p]),
 }
 
 GIST_MAX_LAYERS = 16

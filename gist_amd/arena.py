@@ -143,4 +143,27 @@ class GATArena(FlatArena):
             for h, head in enumerate(layer.heads):
                 head.fc.weight = nn.Parameter(self.W[k][h * o:(h + 1) * o], requires_grad=requires_grad)
                 head.attn_fc.weight = nn.Parameter(self.A[k][h:h + 1], requires_grad=requires_grad)
+        gat.__dict__['_gist_arena'] = weakref.ref(self)      # (module_engine.shared_gat_arena: a binding adopts it)
         return gat
+
+    def head_views(self, flat=None):
+        """Per parameter of a gist_amd.modules.GAT, in `gat.parameters()` order (layer, head: fc.weight [O, I], then
+        attn_fc.weight [1, 2O]), its rows of `flat` -- a flat tensor in this arena's layout; None: `params`."""
+        out = []
+        for k, (i, o, nh) in enumerate(self.dims):
+            W, A = (self.W[k], self.A[k]) if flat is None else self.layer_views(flat, k)
+            for h in range(nh):
+                out += [W[h * o:(h + 1) * o], A[h:h + 1]]
+        return out
+
+    def adopt_module(self, gat):
+        """Re-home a gist_amd.modules.GAT's parameters onto their per-head rows of the arena, values preserved.  The
+        Parameters keep their identity (an optimiser built before the binding keeps stepping them); only their .data
+        moves."""
+        views = self.head_views()
+        params = [p for layer in gat.layers for head in layer.heads for p in (head.fc.weight, head.attn_fc.weight)]
+        assert len(params) == len(views)
+        for p, v in zip(params, views):
+            if p.data_ptr() != v.data_ptr():
+                v.copy_(p.data.to(self.device))
+            p.data = v

@@ -17,6 +17,7 @@ optim.Adam) in the same order on the same operand layouts: losses, parameters an
 (tests/test_gat_step_gpu.py).  DESIGN.md section 9.
 """
 import ctypes
+import weakref
 
 import torch
 
@@ -39,6 +40,7 @@ class GATEngine(StepEngine):
                 raise ValueError('gist_amd: GATEngine needs dims and a device, or an arena')
             arena = GATArena([(int(i), int(o), int(h)) for (i, o, h) in dims], device)
         self.arena = arena.with_grads()
+        arena.__dict__['_engine'] = weakref.ref(self)      # (module_engine.bind_gat steps an adopted arena through it)
         self.dims = [(int(i), int(o), int(h)) for (i, o, h) in arena.dims]
         if n_max is None or int(n_max) <= 0:
             raise ValueError('gist_amd: GATEngine needs n_max > 0 (the iterator\'s n_max)')
@@ -79,6 +81,8 @@ class GATEngine(StepEngine):
         self.row_loss = torch.zeros(n, **f32)
         self.loss = torch.zeros(1, **f32)
         self._model = None
+        self._lent = False                      # the plan's logits / loss / moment pointers are a GATModuleEngine's
+        self._phase_ctx = (None, 0, None)       # (batch, flags, ids pointer) of the last forward phase
 
     def attach_batcher(self, batcher):
         """Build the native step plan (struct gist_gat_step_plan) over `batcher`'s resident graph and batch buffers."""
@@ -147,27 +151,67 @@ class GATEngine(StepEngine):
         self._model = self.arena.bind(gat)
         return self._model
 
-    def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8):
-        if self.plan is None:
-            raise RuntimeError('gist_amd: GATEngine needs attach_batcher (EngineClusterIter.bind) first')
-        L, P = _lib.load(), self.plan
-        flags, ids_ptr = self._begin_step(b, train, ())
-        # the NEXT batch of the epoch, extracted in the optimiser's grid: only for callers that promise not to look at
-        # the batch buffers (labels, CSR, layer 0's input) after a training step
-        nxt = None
-        if self.prefetch and train and b.batcher is not None and b.next_info is not None and P.node_part is not None:
+    def _plan_next(self, b, flags):
+        """The NEXT batch of the epoch, extracted in the optimiser's grid (GIST_STEP_EXTRACT_NEXT): only for callers that
+        promise not to look at the batch buffers (labels, CSR, layer 0's input) after a training step.  Returns (the
+        key the next step must match, flags)."""
+        P = self.plan
+        if (self.prefetch and (flags & _lib.GIST_STEP_TRAIN) and b.batcher is not None and b.next_info is not None
+                and P.node_part is not None):
             nids, nj = b.next_info
             if 0 < nids.numel() <= self.n_max:
                 P.next_ids, P.next_n, P.next_batch_index = nids.data_ptr(), nids.numel(), int(nj)
-                flags |= _lib.GIST_STEP_EXTRACT_NEXT
-                nxt = self._batch_key(P.part_slot, nj, nids.numel(), nids.data_ptr(), ())
-        if train:
-            self.arena.step += 1
-        rc = L.gist_gat_step(ctypes.byref(P), ids_ptr, b.n, lr, betas[0], betas[1], eps, weight_decay,
-                             max(self.arena.step, 1), flags, hip._stream())
-        _lib.check(rc, 'gist_gat_step')
-        self._end_step(b, nxt)
+                return (self._batch_key(P.part_slot, nj, nids.numel(), nids.data_ptr(), ()),
+                        flags | _lib.GIST_STEP_EXTRACT_NEXT)
+        return None, flags
+
+    def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, phase=0, given=False, adam_step=None,
+              lent=False):
+        """One gist_gat_step call (phase = 0: the whole iteration), or one gist_gat_step_phase call: GIST_STEP_PHASE_FORWARD
+        / _BACKWARD / _OPTIMIZER, one third of it (the bound module path: GAT.forward, loss.backward(), optimizer.step(),
+        gist_amd/module_engine.py).  The backward and optimiser calls reuse the forward call's batch and flags.  given:
+        the caller wrote its own dlogits.  adam_step: the optimiser's own count (else the arena's)."""
+        if self.plan is None:
+            raise RuntimeError('gist_amd: GATEngine needs attach_batcher (EngineClusterIter.bind) first')
+        if self._lent and not lent:
+            self._reclaim()
+        L, P, nxt = _lib.load(), self.plan, None
+        if phase in (_lib.GIST_STEP_PHASE_BACKWARD, _lib.GIST_STEP_PHASE_OPTIMIZER):
+            cb, flags, ids_ptr = self._phase_ctx
+            if cb is not b:
+                raise RuntimeError('gist_amd: backward / optimiser phase of a batch that is not the last one forwarded')
+            if phase == _lib.GIST_STEP_PHASE_OPTIMIZER:
+                nxt, flags = self._plan_next(b, flags)
+                self.arena.step += 1
+            elif given:
+                flags |= _lib.GIST_STEP_DLOGITS_GIVEN
+        else:
+            flags, ids_ptr = self._begin_step(b, train, ())
+            if phase == 0:
+                nxt, flags = self._plan_next(b, flags)
+                if train:
+                    self.arena.step += 1
+            else:
+                self._phase_ctx = (b, flags, ids_ptr)
+        step = L.gist_gat_step_phase if phase else L.gist_gat_step
+        rc = step(ctypes.byref(P), ids_ptr, b.n, lr, betas[0], betas[1], eps, weight_decay,
+                  max(adam_step if adam_step is not None else self.arena.step, 1), flags | phase, hip._stream())
+        _lib.check(rc, 'gist_gat_step_phase' if phase else 'gist_gat_step')
+        if phase != _lib.GIST_STEP_PHASE_BACKWARD:      # (a backward phase leaves the batcher's prefetch key alone)
+            self._end_step(b, nxt)
         return self.loss
+
+    def _native_step(self, *args, **kw):
+        """_step for module_engine.GATModuleEngine (the name ModuleEngine calls its engine's phases by), which points
+        the plan's logits, loss and Adam moments at buffers of its own before it calls."""
+        return self._step(*args, lent=True, **kw)
+
+    def _reclaim(self):
+        """Point the plan's logits, loss and Adam moments back at the engine's own buffers (a binding lent them)."""
+        P, A = self.plan, self.arena
+        P.layer[len(self.dims) - 1].out, P.loss = self.out[-1].data_ptr(), self.loss.data_ptr()
+        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
+        self._lent = False
 
     def train_step(self, b, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
         """One iteration of the reference's GAT loop as ONE gist_gat_step call.  Returns the device loss tensor (mean CE

@@ -531,15 +531,21 @@ def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask,
     instead; `cluster_iterator` is then an EngineClusterIter.  Same launches in the same order on the same layouts:
     losses, arenas and accuracies are those of 'module' bit for bit.
 
+    host_path='phases': the loop body of 'module', statement for statement, with every `sub_model` bound to the
+    iterator (gist_amd.module_engine.bind_gat): the forward, `loss.backward()` and `optimizer.step()` are the three
+    gist_gat_step_phase calls on the wrapper's GATEngine (_gat_phase_steps).  `cluster_iterator` is a plain ClusterIter
+    on the GPU.  Bit for bit 'module' again.
+
     `ist_model` is this rank's DistributedGATWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites then
     run in this process, the partition sampled once per dispatch.  The step losses stay on the device (the reference's
     per-step `float(loss)` would wait for it every step); each evaluation averages them.  Returns total_time,
     per-site step losses, events, accuracies and the mean training loss per evaluation."""
     from .utils import evaluate
     models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
-    if host_path not in ('module', 'engine'):
-        raise ValueError("gist_amd: train_gat host_path must be 'module' or 'engine' (got %r)" % (host_path,))
-    steps = _gat_engine_steps if host_path == 'engine' else _gat_module_steps
+    if host_path not in ('module', 'engine', 'phases'):
+        raise ValueError("gist_amd: train_gat host_path must be 'module' or 'engine', or 'phases' for the module loop "
+                         "bound to the fused step (got %r)" % (host_path,))
+    steps = {'module': _gat_module_steps, 'engine': _gat_engine_steps, 'phases': _gat_phase_steps}[host_path]
     at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
 
     def accuracies():
@@ -575,6 +581,33 @@ def _gat_module_steps(models, args, cluster_iterator):
         optimizers[si].step()
         return loss.detach()
     return at_dispatch, step, lambda: None
+
+
+def _gat_phase_steps(models, args, cluster_iterator):
+    """train_gat's (at_dispatch, step, before_eval) for host_path='phases': _gat_module_steps' loop body, with every
+    site's sub_model bound to the iterator first.  Each wrapper's GATEngine steps its sub arena in place (attach_engine;
+    the further sites of one process read the first engine's layer-0 input buffer), so dispatch and sync keep moving
+    the storage the step trains."""
+    from .module_engine import bind_gat
+    from .sampler import ClusterIter
+    if models[0].device.type != 'cuda':
+        raise ValueError("gist_amd: train_gat(host_path='phases') runs the fused step's phase calls, which are GPU-only "
+                         "(the wrapper is on %s); use host_path='module' there" % (models[0].device,))
+    it = cluster_iterator
+    if not isinstance(it, ClusterIter) or not it.feed():
+        raise ValueError("gist_amd: train_gat(host_path='phases') needs a gist_amd.sampler.ClusterIter that describes its "
+                         "batches for on-device extraction (on the GPU, no use_pp; got %s)" % type(it).__name__)
+    first = None
+    for m in models:
+        engine = m.attach_engine(it.n_max, x0=None if first is None else first.X0)
+        first = engine if first is None else first
+        bind_gat(m.sub_model, it)
+    at_dispatch, step, _ = _gat_module_steps(models, args, cluster_iterator)
+
+    def before_eval():                               # (the device is idle: every extraction so far was complete)
+        for m in models:
+            m.engine.check_extract()
+    return at_dispatch, step, before_eval
 
 
 def _gat_engine_steps(models, args, cluster_iterator):

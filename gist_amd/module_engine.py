@@ -28,6 +28,10 @@ is not re-homed: its engine is built on that arena, so the wrapper's in-place di
 step reads (they run on the step's stream, after the optimiser launch that extracted the next batch, which reads no
 parameter).  Parameters after a step are bitwise those of the engine path (tests/test_module_engine_gpu.py).  GIST_MODULE_ENGINE=0 turns the binding off (the
 op-by-op module path of gist_amd/autograd.py, one dispatcher op per layer: the parity twin).
+
+The GAT family has the same surface on gist_gat_step_phase (GATModuleEngine at the end of this file), but only for a
+model that was bound explicitly: `bind_gat(model, cluster_iterator)`.  An unbound gist_amd.modules.GAT keeps the
+op-by-op path, the independent twin its tests compare the fused step with.
 """
 import os
 import weakref
@@ -50,6 +54,9 @@ def _storage_uses(t):
 _lib_def = torch.library.Library('gist', 'FRAGMENT')
 _lib_def.define('gcn_forward(Tensor[] params, int handle, int token, int n, int ldc, bool train) -> Tensor')
 _lib_def.define('gcn_backward(Tensor d_logits, int handle, int token, bool given) -> Tensor[]')
+# the GAT family's pair (GATModuleEngine below): the forward and backward phases of gist_gat_step_phase
+_lib_def.define('gat_forward(Tensor[] params, int handle, int token, int n, int ldc, bool train) -> Tensor')
+_lib_def.define('gat_backward(Tensor d_logits, int handle, int token, bool given) -> Tensor[]')
 
 
 def _gcn_forward_cuda(params, handle, token, n, ldc, train):
@@ -67,6 +74,8 @@ def _gcn_backward_cuda(d_logits, handle, token, given):
 
 _lib_def.impl('gcn_forward', _gcn_forward_cuda, 'CUDA')
 _lib_def.impl('gcn_backward', _gcn_backward_cuda, 'CUDA')
+_lib_def.impl('gat_forward', _gcn_forward_cuda, 'CUDA')        # (the same look-up: the handle names the engine)
+_lib_def.impl('gat_backward', _gcn_backward_cuda, 'CUDA')
 
 
 @torch.library.register_fake('gist::gcn_forward')
@@ -75,6 +84,16 @@ def _(params, handle, token, n, ldc, train):
 
 
 @torch.library.register_fake('gist::gcn_backward')
+def _(d_logits, handle, token, given):
+    return [d_logits.new_empty(v.shape) for v in _REGISTRY[handle].grad_views]
+
+
+@torch.library.register_fake('gist::gat_forward')
+def _(params, handle, token, n, ldc, train):
+    return params[0].new_empty(n, ldc)
+
+
+@torch.library.register_fake('gist::gat_backward')
 def _(d_logits, handle, token, given):
     return [d_logits.new_empty(v.shape) for v in _REGISTRY[handle].grad_views]
 
@@ -177,6 +196,7 @@ def shared_arena(model, dims):
 
 class ModuleEngine(object):
     """One nn.Module GCN bound to one ClusterIter: the SageEngine behind `model(cluster)`."""
+    _backward_op = torch.ops.gist.gcn_backward      # (GATModuleEngine: gist::gat_backward)
 
     def __init__(self, model, it):
         layers = list(model.layers)
@@ -304,7 +324,7 @@ class ModuleEngine(object):
         for p in self.params:
             if p.grad is not None or not p.requires_grad:
                 return False
-        views = torch.ops.gist.gcn_backward(self.engine.dlogits, self.handle, token, False)
+        views = self._backward_op(self.engine.dlogits, self.handle, token, False)
         for p, v in zip(self.params, views):
             p.grad = v
         return True
@@ -326,7 +346,7 @@ class ModuleEngine(object):
         """The tape's way in (any loss on the logits): d_y is the gradient w.r.t. the padded logits.  Gradients are
         delivered like torch's AccumulateGrad would: p.grad = the arena view, or added to what is there."""
         olds = [(v, v.clone()) for p, v in zip(self.params, self.grad_views) if p.grad is v]
-        views = torch.ops.gist.gcn_backward(d_y, self.handle, token, True)
+        views = self._backward_op(d_y, self.handle, token, True)
         for v, o in olds:
             v.add_(o)
         for p, v in zip(self.params, views):
@@ -404,3 +424,238 @@ def engine_for(model, g):
         me = mes[id(it)] = ModuleEngine(model, it) if ok else False
         # (me.it keeps id(it) unique for the model's lifetime)
     return me or None
+
+
+# ---- the GAT family: gist_amd.modules.GAT bound to a ClusterIter, on the three phase calls of gist_gat_step_phase --------
+class _GATForward(torch.autograd.Function):
+    """The tape entry of gist::gat_forward: its backward is gist::gat_backward.  The last layer's ELU backward reads the
+    logits, so they are saved on the tape: torch's version check refuses a backward after an in-place edit of them."""
+
+    @staticmethod
+    def forward(ctx, me, token, n, ldc, *params):
+        ctx.me, ctx.token, ctx.n_in = weakref.ref(me), token, 4 + len(params)
+        y = torch.ops.gist.gat_forward(list(params), me.handle, token, n, ldc, True)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        me = ctx.me()
+        if me is None:
+            raise RuntimeError('gist_amd: backward through the forward of a model that no longer exists')
+        ctx.saved_tensors                              # (raises if the logits were modified in place)
+        me.autograd_backward(ctx.token, d_y)
+        return (None,) * ctx.n_in                      # (the gradients were delivered to p.grad: arena views)
+
+
+def _gat_params(model):
+    return [p for layer in model.layers for head in layer.heads for p in (head.fc.weight, head.attn_fc.weight)]
+
+
+def gat_model_dims(model):
+    """[(in, out, heads)] of a gist_amd.modules.GAT as GATArena lays it out; ValueError if it is not the network
+    gist_gat_step implements."""
+    from .modules import GATLayer, MultiHeadGATLayer
+    layers = list(getattr(model, 'layers', ()))
+    if not layers:
+        raise ValueError('gist_amd: bind_gat needs a gist_amd.modules.GAT (got %s)' % type(model).__name__)
+    if len(layers) > _lib.GIST_MAX_LAYERS:
+        raise ValueError('gist_amd: bind_gat: %d layers, the step plan holds %d' % (len(layers), _lib.GIST_MAX_LAYERS))
+    dims = []
+    for k, layer in enumerate(layers):
+        if type(layer) is not MultiHeadGATLayer or not len(layer.heads) or not all(type(h) is GATLayer for h in layer.heads):
+            raise ValueError('gist_amd: bind_gat: layer %d is not a MultiHeadGATLayer of GATLayers' % k)
+        shapes = set((tuple(h.fc.weight.shape), tuple(h.attn_fc.weight.shape)) for h in layer.heads)
+        (o, i), a = next(iter(shapes))
+        if len(shapes) != 1 or a != (1, 2 * o):
+            raise ValueError('gist_amd: bind_gat: the heads of layer %d differ in shape' % k)
+        dims.append((i, o, len(layer.heads)))
+    merge = getattr(model, 'merge', 'mean')
+    for k in range(1, len(dims)):
+        i0, o0, h0 = dims[k - 1]
+        want = h0 * o0 if (merge == 'cat' and layers[k - 1].merge == 'cat') else o0
+        if dims[k][0] != want or layers[k - 1].merge != merge:
+            raise ValueError("gist_amd: bind_gat: layer %d reads %d columns, merge='%s' of layer %d gives %d"
+                             % (k, dims[k][0], merge, k - 1, want))
+    if dims[-1][2] != 1:
+        raise ValueError('gist_amd: bind_gat: the last layer has %d heads, the step plan takes one' % dims[-1][2])
+    return dims
+
+
+def shared_gat_arena(model, dims):
+    """The GATArena every parameter of `model` already is a view of, in that arena's layout and with `dims`
+    (GATArena.bind recorded it: a DistributedGATWrapper's sub_model), or None.  By data_ptr, as shared_arena."""
+    ref = model.__dict__.get('_gist_arena')
+    A = ref() if ref is not None else None
+    if A is None or [tuple(int(x) for x in d) for d in A.dims] != dims:
+        return None
+    for p, v in zip(_gat_params(model), A.head_views()):
+        if p.data_ptr() != v.data_ptr() or p.shape != v.shape:
+            return None
+    return A
+
+
+class GATModuleEngine(ModuleEngine):
+    """One gist_amd.modules.GAT bound to one ClusterIter (bind_gat): the GATEngine behind `model(cluster)`.  The surface
+    is ModuleEngine's -- forward, fused loss, fast and taped backward, the optimiser's hooks -- on gist_gat_step_phase."""
+    _backward_op = torch.ops.gist.gat_backward
+
+    def __init__(self, model, it, dims):
+        from .gat_engine import GATEngine
+        self._model, self.it = weakref.ref(model), it
+        dev = it.g.device
+        others = [m for m in (r() for r in it.__dict__.setdefault('_gat_bound', [])) if m is not None]
+        first = others[0] if others else None
+        x0 = first.engine.X0 if first is not None else None
+        # a DistributedGATWrapper's sub_model already IS its arena: the engine steps that arena in place (dispatch and
+        # sync write it between steps) -- the wrapper's own engine if it has a fitting one; any other model is re-homed
+        # into an arena of the engine's own
+        shared = shared_gat_arena(model, dims)
+        eng = None
+        if shared is not None:
+            ref = shared.__dict__.get('_engine')
+            eng = ref() if ref is not None else None
+            if eng is not None and eng.n_max != it.n_max:
+                eng = None
+        if eng is None:
+            eng = GATEngine(dims, it.n_max, dev, arena=shared, x0=x0)
+        self.engine = eng
+        if shared is None:
+            eng.arena.adopt_module(model)
+        if first is None:
+            if it.engine is not eng or eng.plan is None:
+                it.bind(eng)                  # the iterator's engine: its epoch-end extraction check
+        elif eng.plan is None or eng._plan_keep[0] is not it.batcher:
+            eng.attach_batcher(it.batcher)
+        if eng.plan is None:
+            raise RuntimeError('gist_amd: no native step plan for this model')
+        # one model on the iterator: the optimiser launch extracts the next batch.  Several (the S sites of one process):
+        # they share the batch buffers and layer 0's input rows (the first engine's X0), so nobody extracts ahead and
+        # every forward phase extracts its batch itself (one launch; the buffers then hold what they held)
+        it._gat_bound = [weakref.ref(m) for m in others] + [weakref.ref(self)]
+        for m in others:
+            m.engine.prefetch = False
+        eng.prefetch = not others
+        A = eng.arena
+        self.params = _gat_params(model)
+        self.grad_views = A.head_views(A.grads)
+        self._home_ptrs = [v.data_ptr() for v in A.head_views()]
+        self.n_classes = self.ldc = eng.n_classes
+        self.handle = _NEXT_HANDLE[0]
+        _NEXT_HANDLE[0] += 1
+        _REGISTRY[self.handle] = self
+        for p in self.params:
+            p._gist_me = self.handle
+        self.token = 0
+        self.state = _IDLE
+        self._pending = None        # (engine Batch, cluster, logits tensor)
+        self._loss0 = None
+        self._pred = None           # (weak reference to the logits handed out, their version when handed out)
+        self._f32 = dict(dtype=torch.float32, device=dev)
+        self._last = len(dims) - 1
+        self._first_step = True
+        self._logit_ring = [torch.empty(it.n_max, self.ldc, **self._f32) for _ in range(4)]
+        self._loss_ring = [torch.zeros((), **self._f32) for _ in range(64)]
+        self._idle_uses = _storage_uses(self._logit_ring[0])
+
+    def forward(self, g, training):
+        eng = self.engine
+        if not self.homed():          # model.to(...) / .data replaced: bring the values back into the arena
+            eng.arena.adopt_module(self._model())
+        n = g._n
+        b = self.it.batcher.lazy(g._ids)
+        b.row_blocks, b.parts, b.next_info = g.row_blocks, g.parts, g.next_info
+        b.siblings = g.siblings
+        P = eng.plan
+        self.token += 1
+        self._pending = self._pred = None          # (the previous step's view of its ring slot)
+        if not training:
+            y = torch.empty(n, self.ldc, **self._f32)      # evaluation: every call's logits are their own tensor
+        else:
+            y = self._ring_slot(self._logit_ring, self.token & 3,
+                                lambda: torch.empty(self.it.n_max, self.ldc, **self._f32))[:n]
+        eng._lent = True              # (the plan's logits, loss and moment pointers are this binding's until reclaimed)
+        P.layer[self._last].out = y.data_ptr()
+        self._loss0 = self._ring_slot(self._loss_ring, self.token & 63, lambda: torch.zeros((), **self._f32))
+        P.loss = self._loss0.data_ptr()
+        self._pending = (b, g, y)
+        if not training:
+            eng._native_step(b, 0.0, 0.0, train=False)
+            self.state = _IDLE
+            return y
+        if torch.is_grad_enabled():
+            pred = _GATForward.apply(self, self.token, n, self.ldc, *self.params)
+        else:
+            pred = torch.ops.gist.gat_forward(self.params, self.handle, self.token, n, self.ldc, True)
+        pred._gist_step = (self, self.token)
+        self._pred = (weakref.ref(pred), pred._version)
+        return pred
+
+    def _run_forward(self, token, n, ldc, train):
+        y = ModuleEngine._run_forward(self, token, n, ldc, train)
+        # the logits are the caller's from here (the plan has their address, the ring their storage): holding them would
+        # close a cycle through pred._gist_step that only the cyclic collector frees
+        self._pending = self._pending[:2] + (None,)
+        return y
+
+    def _logits_edited(self):
+        pred = self._pred[0]() if self._pred is not None else None
+        return pred is not None and pred._version != self._pred[1]
+
+    def fast_backward(self, token):
+        if token == self.token and self.state == _FWD_DONE and self._logits_edited():
+            raise RuntimeError('gist_amd: the logits of this forward were modified in place before backward(); the last '
+                               'GAT layer\'s ELU backward reads them')
+        return ModuleEngine.fast_backward(self, token)
+
+    def _run_backward(self, token, d_logits, given):
+        if token != self.token or self.state != _FWD_DONE:
+            raise RuntimeError('gist_amd: backward through a GAT forward that is no longer the model\'s latest (the '
+                               'engine reuses its buffers; an unbound model runs op by op)')
+        return ModuleEngine._run_backward(self, token, d_logits, given)
+
+
+def bind_gat(model, cluster_iterator):
+    """Bind a gist_amd.modules.GAT to a gist_amd.sampler.ClusterIter: from now on `model(cluster)` on that iterator's
+    batches, gist_amd.nn.CrossEntropyLoss on the result, `loss.backward()` and gist_amd.optim.Adam.step() are the three
+    phase calls of gist_gat_step_phase on one preallocated plan -- the engine path's launches, bitwise its training.
+    Explicit and opt-in: an unbound GAT runs op by op, as before.  Legal before or after the optimiser is built (the
+    Parameters keep their identity; their .data moves onto the arena).  Returns the GATModuleEngine; a second call with
+    the same iterator returns the same one.  ValueError, with the reason, if the model or the iterator cannot run on
+    the fused step: nothing falls back silently."""
+    from .sampler import ClusterIter
+    dims = gat_model_dims(model)
+    it = cluster_iterator
+    if not isinstance(it, ClusterIter):
+        raise ValueError('gist_amd: bind_gat needs a gist_amd.sampler.ClusterIter (got %s)' % type(it).__name__)
+    mes = model.__dict__.get('_gat_engines')
+    if mes:
+        me = mes.get(id(it))
+        if me is not None:
+            return me
+        if any(m is not None for m in mes.values()):
+            raise ValueError('gist_amd: bind_gat: this model is already bound to another iterator')
+    params = _gat_params(model)
+    dev = it.g.device
+    if dev.type != 'cuda' or not it.feed():
+        raise ValueError('gist_amd: bind_gat: the iterator does not describe its batches for on-device extraction '
+                         '(use_pp=%s, device %s, GIST_MODULE_ENGINE=%s): the fused step is GPU-only and extracts the '
+                         'batch itself' % (it.use_pp, dev, os.environ.get('GIST_MODULE_ENGINE', '1')))
+    for p in params:
+        if p.dtype != torch.float32 or p.device != dev:
+            raise ValueError('gist_amd: bind_gat: parameters must be fp32 on %s (found %s on %s); model.to(device) first'
+                             % (dev, p.dtype, p.device))
+    if dims[0][0] != it.batcher.feat.shape[1]:
+        raise ValueError('gist_amd: bind_gat: the model takes %d input features, the iterator\'s graph has %d'
+                         % (dims[0][0], it.batcher.feat.shape[1]))
+    if hip._prof is not None:
+        raise ValueError('gist_amd: bind_gat: the op profiler is on; the fused step has no per-op records')
+    me = GATModuleEngine(model, it, dims)
+    model.__dict__.setdefault('_gat_engines', {})[id(it)] = me
+    return me
+
+
+def gat_engine_for(model, g):
+    """The GATModuleEngine bind_gat made for the iterator of cluster batch g, or None."""
+    mes = model.__dict__.get('_gat_engines')
+    return mes.get(id(g._it)) if mes else None

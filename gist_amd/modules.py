@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import autograd, module_engine
+from .graph import ClusterBatch
 
 
 def _is_relu(fn):
@@ -223,7 +224,14 @@ class GAT(nn.Module):
         self.layers = torch.nn.ModuleList(layers)
 
     def forward(self, g):
-        """modules.py:93-98 on a ClusterBatch or a full Graph; h = F.elu(layer(g, h)) runs as one op per layer."""
+        """modules.py:93-98 on a ClusterBatch or a full Graph; h = F.elu(layer(g, h)) runs as one op per layer.  A model
+        that module_engine.bind_gat bound to an iterator runs that iterator's batches on the fused step instead (one
+        dispatcher op, gist::gat_forward); everything else -- the full graph of an evaluation, a hand-built graph, a
+        batch of another iterator, an unbound model -- takes the layers below."""
+        if type(g) is ClusterBatch and '_gat_engines' in self.__dict__:
+            me = module_engine.gat_engine_for(self, g)
+            if me is not None:
+                return me.forward(g, self.training)
         h = g.ndata['feat']
         for layer in self.layers:
             h = layer(g, h, elu=True)

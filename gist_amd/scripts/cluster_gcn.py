@@ -46,8 +46,9 @@ def build_parser():
     parser.add_argument("--eval-cpu", action='store_true')
     # (not a flag of the reference) module: the reference's own loop body, statement for statement, on gist_amd.modules.GCN /
     # nn.CrossEntropyLoss / optim.Adam / sampler.ClusterIter (gist_amd/module_engine.py); engine: one gist_sage_step (sage) or
-    # gist_gat_step (gat) per iteration
-    parser.add_argument("--host-path", choices=['engine', 'module'], default='engine')
+    # gist_gat_step (gat) per iteration; phases (gat): the module loop with the model bound to its iterator
+    # (module_engine.bind_gat) -- the engine's launches as three gist_gat_step_phase calls per iteration
+    parser.add_argument("--host-path", choices=['engine', 'module', 'phases'], default='engine')
     return parser
 
 
@@ -87,9 +88,13 @@ def main(args, dataset=None, log=print):
         model_holder['m'] = m
         return m
     host_path = getattr(args, 'host_path', 'engine')
+    if host_path == 'phases' and args.model_type != 'gat':
+        raise SystemExit('gist_amd: --host-path phases binds a GAT to its iterator (--model-type gat); the SAGE module '
+                         'path already runs on the phase calls of the fused step: use --host-path module')
     if args.model_type == 'gat' and host_path == 'engine' and not args.use_pp:
         return main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     if args.model_type == 'gat' or host_path == 'module':
+        # (--host-path phases: the same loop, the GAT bound to the iterator first)
         # (--use-pp changes the train graph's features under the iterator: the GAT then keeps the reference's loop)
         return main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     trainer = ClusterGCNTrainer(args.dataset, g, par_li, psize, args.batch_size, args.n_hidden,
@@ -179,6 +184,9 @@ def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, 
                     args.use_layernorm, False, False, 1, True)                                         # :66-69
         model.cuda()
         model.set_dropout_seed(args.rnd_seed)
+    if args.model_type == 'gat' and getattr(args, 'host_path', 'engine') == 'phases':
+        from gist_amd.module_engine import bind_gat
+        bind_gat(model, cluster_iterator)            # model(cluster), loss.backward(), optimizer.step(): the fused step's phases
     loss_f = CrossEntropyLoss()                                                                        # :76
     optimizer = Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)                   # :77-80
     total_time, val_accs, test_accs = 0., [], []

@@ -3,7 +3,8 @@
 (flags :538-580, four result lines or the results pickle :481-499), one process per GPU, running on the gist_amd HIP
 path: gist_amd.ist.DistributedGATWrapper and gist_amd.ist.train_gat, the reference's loop on the drop-in classes.
 `--host-path engine` (not a flag of the reference) runs every step as one gist_gat_step call on the wrapper's
-GATEngine instead: the same numbers bit for bit, fewer launches.
+GATEngine instead: the same numbers bit for bit, fewer launches.  `--host-path phases` keeps the reference's loop body and
+binds `sub_model` to the iterator (gist_amd.module_engine.bind_gat): the engine's launches as three phase calls.
 
 Launch like the reference's GAT sweep (script/reddit/run_gat_distrib_sweep.py): one process per rank,
 
@@ -31,8 +32,9 @@ def build_parser():
     parser.add_argument('--head-merge', choices=['mean', 'cat'], default='mean')
     parser.add_argument("--exp_name", type=str, default='distributed_gnn_ist')
     # (not a flag of the reference) module: the reference's loop on ist_model.sub_model / base_model; engine: one
-    # gist_gat_step per iteration (gist_amd.ist.train_gat, host_path)
-    parser.add_argument("--host-path", choices=['module', 'engine'], default='module')
+    # gist_gat_step per iteration; phases: the module loop with sub_model bound to the iterator, three
+    # gist_gat_step_phase calls per iteration (gist_amd.ist.train_gat, host_path)
+    parser.add_argument("--host-path", choices=['module', 'engine', 'phases'], default='module')
     return parser
 
 
@@ -62,9 +64,10 @@ def main(args=None, dataset=None, log=print):
         args = build_parser().parse_args()
     assert (args.n_hidden % args.num_subnet) == 0
     host_path = getattr(args, 'host_path', 'module')
-    if host_path == 'engine' and (args.use_pp or args.cuda_id < 0):
-        raise SystemExit('gist_amd: --host-path engine is the fused GAT step: it runs on a GPU (--cuda-id >= 0) and '
-                         'extracts its batches from the plain features (no --use-pp); use --host-path module')
+    if host_path in ('engine', 'phases') and (args.use_pp or args.cuda_id < 0):
+        raise SystemExit('gist_amd: --host-path %s is the fused GAT step: it runs on a GPU (--cuda-id >= 0) and '
+                         'extracts its batches from the plain features (no --use-pp); use --host-path module'
+                         % host_path)
     if args.use_pp:
         raise NotImplementedError(
             'gist_amd: --use-pp cannot work with the GAT in the reference either (the feature width doubles after '

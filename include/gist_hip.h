@@ -1085,11 +1085,35 @@ int64_t gist_gat_step_attn_partials_floats(const gist_gat_step_plan *plan);
  * flags: GIST_STEP_EXTRACT, GIST_STEP_TRAIN (without it: forward + loss only), GIST_STEP_EXTRACT_NEXT (the optimiser
  * launch is gist_adam_segments_extract_f32 with no segments and also extracts plan->next_*; GIST_EINVAL if the plan
  * lacks the part tables, the scratch or next_*) and GIST_STEP_PREEXTRACTED, with their gist_sage_step meaning.  The
- * GIST_STEP_PHASE_* bits and GIST_STEP_DLOGITS_GIVEN are not supported: GIST_EINVAL.  Every argument is checked (null
- * pointers, sizes, n > n_max, more than GIST_MAX_LAYERS layers: GIST_EINVAL; a workspace too small for this n:
- * GIST_ENOSPACE) before any device work. */
+ * GIST_STEP_PHASE_* bits and GIST_STEP_DLOGITS_GIVEN are gist_gat_step_phase's (below), here GIST_EINVAL.  Every
+ * argument is checked (null pointers, sizes, n > n_max, more than GIST_MAX_LAYERS layers: GIST_EINVAL; a workspace too
+ * small for this n: GIST_ENOSPACE) before any device work. */
 int gist_gat_step(const gist_gat_step_plan *plan, const int32_t *ids, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int64_t adam_step, int flags, gist_stream_t stream);
+
+/* The same iteration as three calls, for a script that keeps the reference's loop body (`pred = model(cluster)`,
+ * `loss = loss_f(...)`, `loss.backward()`, `optimizer.step()`: gist_amd/module_engine.py, bind_gat).  flags =
+ * GIST_STEP_TRAIN | exactly one GIST_STEP_PHASE_* bit | the iteration's other flags; the three calls get the same
+ * (plan, ids, n, other flags):
+ *   FORWARD    reads EXTRACT / PREEXTRACTED: the extraction, then per layer gist_gemm_nt_f32 -> gist_gat_scores_f32 ->
+ *              gist_gat_aggregate(_cat)_f32, then gist_softmax_xent_f32.  In stream order plan->loss, plan->dlogits and
+ *              the logits in layer[n_layers - 1].out are complete;
+ *   BACKWARD   the reverse layer loop from plan->dlogits; the gradient arena is COMPLETE on return.  With
+ *              GIST_STEP_DLOGITS_GIVEN the caller has overwritten plan->dlogits [n, n_classes] with the gradient of ITS
+ *              loss w.r.t. the logits: for a GAT that is simply the last layer's d_out, nothing is recomputed;
+ *   OPTIMIZER  the one Adam launch over the arena from plan->grads and plan->exp_avg / exp_avg_sq as they stand at the
+ *              call (lr ... adam_step are read by this phase only); with EXTRACT_NEXT it is
+ *              gist_adam_segments_extract_f32 with no segments, which also extracts plan->next_*.
+ * The three calls issue exactly the launches of one gist_gat_step call, in its order, through the same functions:
+ * parameters, loss and moments are bitwise the one-call step's.  The ORDER of the phases is the caller's contract: the
+ * driver keeps no state between calls (the plan's buffers are the state), so a BACKWARD without its FORWARD reads
+ * whatever the buffers hold.  The logits, loss and moment pointers are plan fields the host may set per call.
+ * Every call checks what ITS phase reads before any device work: no phase bit or more than one, no GIST_STEP_TRAIN,
+ * DLOGITS_GIVEN without BACKWARD, EXTRACT with PREEXTRACTED, null buffers, bad shapes, n > n_max: GIST_EINVAL; a
+ * workspace or attn_partials too small for this n: GIST_ENOSPACE. */
+int gist_gat_step_phase(const gist_gat_step_plan *plan, const int32_t *ids, int64_t n, float lr, float beta1,
+                        float beta2, float eps, float weight_decay, int64_t adam_step, int flags,
+                        gist_stream_t stream);
 
 #ifdef __cplusplus
 }

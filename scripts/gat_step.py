@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
-"""A GAT training step on the two host paths, ms per step, on real Reddit-like cluster batches
+"""A GAT training step on the three host paths, ms per step, on real Reddit-like cluster batches
 (datasets.reddit_synth, psize 1500, batch size 20):
 
   engine   one gist_gat_step call per iteration (gist_amd.gat_engine.GATEngine, fed by EngineClusterIter, the next
            batch extracted in the optimiser's grid) -- `cluster_gcn --model-type gat --host-path engine`
+  phases   the module loop body with the model bound to its iterator (gist_amd.module_engine.bind_gat): the engine's
+           launches as three gist_gat_step_phase calls per iteration -- `--host-path phases`
   module   the reference's loop body on gist_amd.modules.GAT / nn.CrossEntropyLoss / optim.Adam / ClusterIter --
            `--host-path module`, unchanged by the fused step
+
+    python scripts/gat_step.py --paths engine,phases,module --head-merge both --out profiles/gat_step_phases.json
 
     python scripts/gat_step.py --out profiles/gat_step.json
 
 Both paths compute the same bits (tests/test_gat_step_gpu.py); this tool only times them.  Per shape (layers, heads,
 width per head; in = 602, 41 classes) it runs, after --warmup steps of each path, --reps pairs of windows of --iters
-steps, engine and module ALTERNATING in one process, each window between two HIP events and ended by a synchronise.
+steps, the paths (--paths, default engine,module) ALTERNATING in one process, each window between two HIP events and ended by a synchronise.
 It reports the median ms per step of each path, the run-to-run spread of each ((max - min) / median over the windows),
 the ratio, and the launches the library itself issued per step (gist_launch_count; torch's own kernels of the module
 path -- cat, mul, zero_ -- are not in it).
@@ -25,6 +29,7 @@ runs --steps untimed steps of one path for a kernel trace: the difference of the
 counts, over the difference of the counts, is the path's launches per step, set-up excluded.
 """
 import argparse
+import gc
 import json
 import os
 import random
@@ -49,7 +54,7 @@ def cycle(it):
 
 
 class Paths(object):
-    """The two iterators over one dataset (built once) and, per shape, the two step functions."""
+    """The three iterators over one dataset (built once) and, per shape, the three step functions."""
 
     def __init__(self, ds, psize, bsize, dev):
         from gist_amd.sampler import ClusterIter, EngineClusterIter
@@ -60,6 +65,8 @@ class Paths(object):
         self.mod_it = ClusterIter(ds.name, g, psize, bsize, nid, par_li=ds.par_li, device=dev)
         random.seed(0)
         self.eng_it = EngineClusterIter(ds.name, g, psize, bsize, nid, par_li=ds.par_li, device=dev)
+        random.seed(0)
+        self.ph_it = ClusterIter(ds.name, g, psize, bsize, nid, par_li=ds.par_li, device=dev)
         self.fin, self.ncls = g.ndata['feat'].shape[1], ds.num_classes
 
     def shape(self, layers, heads, width, merge='mean'):
@@ -71,18 +78,31 @@ class Paths(object):
         torch.manual_seed(0)
         model = GAT(layers, self.fin, width, self.ncls, heads, merge=merge).to(self.dev)
         loss_f = CrossEntropyLoss()
-        opt = Adam(model.parameters(), lr=LR, weight_decay=WD)
-        mod_batches = cycle(self.mod_it)
 
-        def mod_step():
-            cluster = next(mod_batches).to(self.dev)
-            model.train()
-            pred = model(cluster)
-            tm, lab = cluster.ndata['train_mask'], cluster.ndata['label']
-            loss = loss_f(pred[tm], lab[tm])
-            opt.zero_grad()
-            loss.backward()
-            opt.step()
+        def module_loop(model, it):
+            """The reference's loop body on `model` and the batches of `it`."""
+            opt = Adam(model.parameters(), lr=LR, weight_decay=WD)
+            batches = cycle(it)
+
+            def step():
+                cluster = next(batches).to(self.dev)
+                model.train()
+                pred = model(cluster)
+                tm, lab = cluster.ndata['train_mask'], cluster.ndata['label']
+                loss = loss_f(pred[tm], lab[tm])
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+            return step
+        mod_step = module_loop(model, self.mod_it)
+        # the same loop, the same initial weights, the model bound to its iterator
+        from gist_amd.module_engine import bind_gat
+        torch.manual_seed(0)
+        bound = GAT(layers, self.fin, width, self.ncls, heads, merge=merge).to(self.dev)
+        gc.collect()                                   # (the previous shape's bound model is gone: one model per iterator)
+        me = bind_gat(bound, self.ph_it)
+        assert me.engine.prefetch, 'another model is still bound to the phases iterator'
+        ph_step = module_loop(bound, self.ph_it)
 
         eng = GATEngine(gat_dims(self.fin, width, self.ncls, layers, heads, merge), self.eng_it.n_max, self.dev)
         eng.arena.load(gat_params(model))
@@ -93,7 +113,7 @@ class Paths(object):
         def eng_step():
             eng.train_step(next(eng_batches), LR, WD)
 
-        return eng, eng_step, mod_step
+        return eng, dict(engine=eng_step, phases=ph_step, module=mod_step)
 
 
 def window(fn, iters):
@@ -120,7 +140,9 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--quick', action='store_true', help='the toy graph, one shape (rehearsal)')
-    ap.add_argument('--trace', choices=['engine', 'module'], help='untimed steps of one path, for a kernel trace')
+    ap.add_argument('--trace', choices=['engine', 'phases', 'module'],
+                    help='untimed steps of one path, for a kernel trace')
+    ap.add_argument('--paths', default='engine,module', help='the paths to time, of engine,phases,module')
     ap.add_argument('--shape', default='2,4,64', help='--trace: layers,heads,width')
     ap.add_argument('--steps', type=int, default=40, help='--trace: steps to run')
     ap.add_argument('--head-merge', choices=['mean', 'cat', 'both'], default='mean')
@@ -136,8 +158,8 @@ def main():
     setup_s = time.time() - t0
     if args.trace:
         layers, heads, width = (int(v) for v in args.shape.split(','))
-        eng, eng_step, mod_step = paths.shape(layers, heads, width, 'cat' if args.head_merge == 'cat' else 'mean')
-        fn = eng_step if args.trace == 'engine' else mod_step
+        eng, steps = paths.shape(layers, heads, width, 'cat' if args.head_merge == 'cat' else 'mean')
+        fn = steps[args.trace]
         for _ in range(args.steps):
             fn()
         torch.cuda.synchronize()
@@ -148,41 +170,55 @@ def main():
     merges = ('mean', 'cat') if args.head_merge == 'both' else (args.head_merge,)
     # (one head: the two modes are the same model, measured once as 'mean')
     shapes = [s + (m,) for s in shapes for m in merges if m == 'mean' or s[1] > 1 or len(merges) == 1]
+    names = [n for n in args.paths.split(',') if n]
+    assert names and all(n in ('engine', 'phases', 'module') for n in names), '--paths: of engine,phases,module'
     res = []
     for layers, heads, width, merge in shapes:
-        eng, eng_step, mod_step = paths.shape(layers, heads, width, merge)
+        eng, steps = paths.shape(layers, heads, width, merge)
         for _ in range(args.warmup):
-            eng_step()
-            mod_step()
+            for n in names:
+                steps[n]()
         torch.cuda.synchronize()
-        e_ms, m_ms, e_l, m_l = [], [], [], []
-        for _ in range(args.reps):                     # alternating: a drift of the box hits both paths alike
-            ms, nl = window(eng_step, args.iters)
-            e_ms.append(ms)
-            e_l.append(nl)
-            ms, nl = window(mod_step, args.iters)
-            m_ms.append(ms)
-            m_l.append(nl)
+        ms, nl = dict((n, []) for n in names), dict((n, []) for n in names)
+        for _ in range(args.reps):                     # alternating: a drift of the box hits every path alike
+            for n in names:
+                t, c = window(steps[n], args.iters)
+                ms[n].append(t)
+                nl[n].append(c)
         eng.check_extract()
-        e, m = float(np.median(e_ms)), float(np.median(m_ms))
-        noise = max(spread(e_ms), spread(m_ms))
-        r = dict(merge=merge, layers=layers, heads=heads, width=width, n_in=paths.fin, engine_ms=round(e, 4), module_ms=round(m, 4),
-                 module_over_engine=round(m / e, 3), engine_spread=round(spread(e_ms), 4),
-                 module_spread=round(spread(m_ms), 4), engine_not_slower=bool(e <= m * (1.0 + noise)),
-                 engine_lib_launches_per_step=round(float(np.median(e_l)), 2),
-                 module_lib_launches_per_step=round(float(np.median(m_l)), 2),
-                 engine_windows=[round(v, 4) for v in e_ms], module_windows=[round(v, 4) for v in m_ms])
+        med = dict((n, float(np.median(ms[n]))) for n in names)
+        r = dict(merge=merge, layers=layers, heads=heads, width=width, n_in=paths.fin)
+        for n in names:
+            r[n + '_ms'] = round(med[n], 4)
+            r[n + '_spread'] = round(spread(ms[n]), 4)
+            r[n + '_lib_launches_per_step'] = round(float(np.median(nl[n])), 2)
+            r[n + '_windows'] = [round(v, 4) for v in ms[n]]
+        if 'engine' in med and 'module' in med:
+            noise = max(spread(ms['engine']), spread(ms['module']))
+            r['module_over_engine'] = round(med['module'] / med['engine'], 3)
+            r['engine_not_slower'] = bool(med['engine'] <= med['module'] * (1.0 + noise))
+        if 'phases' in med:
+            if 'engine' in med:
+                r['phases_over_engine'] = round(med['phases'] / med['engine'], 3)
+            if 'module' in med:
+                r['module_over_phases'] = round(med['module'] / med['phases'], 3)
+                # the criterion of profiles/gat_ist_step.md: every phases window shorter than every module window
+                r['phases_below_every_module_window'] = bool(max(ms['phases']) < min(ms['module']))
         res.append(r)
         print(json.dumps({k: v for k, v in r.items() if not k.endswith('_windows')}), flush=True)
-        del eng, eng_step, mod_step
+        del eng, steps
     doc = dict(tool='scripts/gat_step.py', device=torch.cuda.get_device_name(0), gemm_mode=hip.gemm_mode(),
                dataset=ds.name, psize=psize, batch_size=bsize, n_max=paths.eng_it.n_max, iters=args.iters,
-               reps=args.reps, warmup=args.warmup, lr=LR, weight_decay=WD, setup_s=round(setup_s, 1), shapes=res)
+               reps=args.reps, warmup=args.warmup, paths=names, lr=LR, weight_decay=WD, setup_s=round(setup_s, 1), shapes=res)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as fh:
         json.dump(doc, fh, indent=1)
-    print('gat_step: %d shapes, engine not slower than module beyond the spread on %d of them'
-          % (len(res), sum(r['engine_not_slower'] for r in res)))
+    if 'engine_not_slower' in res[0]:
+        print('gat_step: %d shapes, engine not slower than module beyond the spread on %d of them'
+              % (len(res), sum(r['engine_not_slower'] for r in res)))
+    if 'phases_below_every_module_window' in res[0]:
+        print('gat_step: %d shapes, every phases window shorter than every module window on %d of them'
+              % (len(res), sum(r['phases_below_every_module_window'] for r in res)))
 
 
 if __name__ == '__main__':
