@@ -155,6 +155,9 @@ SIGNATURES = {
     'gist_gat_step_attn_partials_floats': (_i64, [_p]),
     'gist_gat_step': (_int, [_p, _p, _i64, _f, _f, _f, _f, _f, _i64, _int, _p]),
     'gist_gat_step_phase': (_int, [_p, _p, _i64, _f, _f, _f, _f, _f, _i64, _int, _p]),
+    'gist_gat_row_stats_f32': (_int, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p]),
+    'gist_gat_aggregate_blocks_f32': (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int,
+                                             _p, _i64, _p]),
 }
 
 GIST_MAX_LAYERS = 16

@@ -364,6 +364,41 @@ def gat_aggregate(rowptr, col, z, a, s_src, s_dst, elu, out, m, l, cat=False):
     return out
 
 
+def gat_row_stats(rowptr, col, s_src, s_dst, m, l):
+    """Softmax max m and denominator l per (row, head) from the scores alone (gist_gat_row_stats_f32)."""
+    L = _lib.load()
+    if s_src.dim() != 2:
+        raise ValueError('gist_amd: s_src must be [n, heads]')
+    n, heads = s_src.shape
+    rp, cp = _csr(rowptr, col, n, 'rowptr')
+    _lib.check(L.gist_gat_row_stats_f32(rp, cp, _nh(s_src, 's_src', n, heads), _nh(s_dst, 's_dst', n, heads), n, heads,
+                                        _nh(m, 'm', n, heads), _nh(l, 'l', n, heads), _stream()),
+               'gist_gat_row_stats_f32')
+
+
+def gat_aggregate_blocks(rowptr, col, block_ptr, z, a, s_src, s_dst, m, l, elu, out, cat=False):
+    """gat_aggregate with m and l given (gat_row_stats) and the rows cut into blocks of at most 128 (block_ptr: device
+    int32 boundaries 0..n): in-block edges as a dense product on the fp32 matrix cores, the others walked
+    (gist_gat_aggregate_blocks_f32)."""
+    L = _lib.load()
+    n, heads, f = _gat_dims(z, a)
+    rp, cp = _csr(rowptr, col, n, 'rowptr')
+    bp = _vec(block_ptr, 'block_ptr', torch.int32)
+    if block_ptr.numel() < 1:
+        raise ValueError('gist_amd: block_ptr must hold n_blocks + 1 boundaries')
+    zp, ldz = _mat(z, 'z')
+    op, ldo = _mat(out, 'out')
+    w = heads * f if cat else f
+    if tuple(out.shape) != (n, w):
+        raise ValueError('gist_amd: gat_aggregate_blocks output must be [%d, %d]' % (n, w))
+    _lib.check(L.gist_gat_aggregate_blocks_f32(rp, cp, bp, block_ptr.numel() - 1, zp, ldz,
+                                               _nh(s_src, 's_src', n, heads), _nh(s_dst, 's_dst', n, heads),
+                                               _nh(m, 'm', n, heads), _nh(l, 'l', n, heads), n, heads, f,
+                                               int(bool(elu)), int(bool(cat)), op, ldo, _stream()),
+               'gist_gat_aggregate_blocks_f32')
+    return out
+
+
 def gat_backward_dst(rowptr, col, z, a, out, d_out, s_src, s_dst, m, l, elu, g, ds_dst, dd, cat=False):
     """Destination pass of the GAT backward (gist_gat_backward_dst_f32): g, ds_dst, D; cat: out, d_out and g are
     [n, heads * out_dim] (gist_gat_backward_dst_cat_f32)."""

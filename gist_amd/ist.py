@@ -522,7 +522,8 @@ def train(ist_model, args, cluster_iterator, evaluator=None, log=print):
                          accuracies if evaluator is not None else None)
 
 
-def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module'):
+def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module',
+              eval_path='layers'):
     """The GIST loop of cluster_gcn_ist_distrib_gat.py:393-480 on the drop-in classes: `ist_model.sub_model(cluster)`,
     masked gist_amd.nn.CrossEntropyLoss, a new gist_amd.optim.Adam at every dispatch point, `evaluate(base_model, g,
     ...)` on rank 0 (`g` on the device).  The schedule is the SAGE one (_run_schedule).
@@ -537,7 +538,9 @@ def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask,
     on the GPU.  Bit for bit 'module' again.
 
     `ist_model` is this rank's DistributedGATWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites then
-    run in this process, the partition sampled once per dispatch.  The step losses stay on the device (the reference's
+    run in this process, the partition sampled once per dispatch.  eval_path='blocked': rank 0's `base_model` is
+    evaluated by a gist_amd.gat_eval.GATFullGraphEvaluator over the base arena ('layers': its own forward, layer by
+    layer).  The step losses stay on the device (the reference's
     per-step `float(loss)` would wait for it every step); each evaluation averages them.  Returns total_time,
     per-site step losses, events, accuracies and the mean training loss per evaluation."""
     from .utils import evaluate
@@ -545,6 +548,11 @@ def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask,
     if host_path not in ('module', 'engine', 'phases'):
         raise ValueError("gist_amd: train_gat host_path must be 'module' or 'engine', or 'phases' for the module loop "
                          "bound to the fused step (got %r)" % (host_path,))
+    if eval_path not in ('layers', 'blocked'):
+        raise ValueError("gist_amd: train_gat eval_path must be 'layers' or 'blocked' (got %r)" % (eval_path,))
+    if eval_path == 'blocked' and models[0].base_model is not None:
+        from .gat_eval import GATFullGraphEvaluator
+        GATFullGraphEvaluator.attach(models[0].base_model, arena=models[0].base)
     steps = {'module': _gat_module_steps, 'engine': _gat_engine_steps, 'phases': _gat_phase_steps}[host_path]
     at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
 

@@ -49,7 +49,18 @@ def build_parser():
     # gist_gat_step (gat) per iteration; phases (gat): the module loop with the model bound to its iterator
     # (module_engine.bind_gat) -- the engine's launches as three gist_gat_step_phase calls per iteration
     parser.add_argument("--host-path", choices=['engine', 'module', 'phases'], default='engine')
+    # (not a flag of the reference; --model-type gat) how evaluate() runs the full-graph forward: layers = the model's own
+    # forward, layer by layer on the training kernels; blocked = gist_amd.gat_eval.GATFullGraphEvaluator (preallocated
+    # buffers, two-pass softmax, the graph's node blocks as dense products on the matrix cores)
+    parser.add_argument("--eval-path", choices=['layers', 'blocked'], default='layers')
     return parser
+
+
+def attach_eval_path(args, model, arena=None):
+    """--eval-path blocked: route evaluate(model, g, ...) through a GATFullGraphEvaluator."""
+    if getattr(args, 'eval_path', 'layers') == 'blocked':
+        from gist_amd.gat_eval import GATFullGraphEvaluator
+        GATFullGraphEvaluator.attach(model, arena=arena)
 
 
 def main(args, dataset=None, log=print):
@@ -88,6 +99,9 @@ def main(args, dataset=None, log=print):
         model_holder['m'] = m
         return m
     host_path = getattr(args, 'host_path', 'engine')
+    if getattr(args, 'eval_path', 'layers') != 'layers' and args.model_type != 'gat':
+        raise SystemExit('gist_amd: --eval-path blocked is the GAT evaluator (--model-type gat); the SAGE engine path '
+                         'already evaluates with trainer.FullGraphEvaluator')
     if host_path == 'phases' and args.model_type != 'gat':
         raise SystemExit('gist_amd: --host-path phases binds a GAT to its iterator (--model-type gat); the SAGE module '
                          'path already runs on the phase calls of the fused step: use --host-path module')
@@ -140,6 +154,7 @@ def main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, l
     engine.bind(model)                                     # the model's parameters are the arena's views from here on
     it.bind(engine)
     engine.prefetch = True                                 # (the loop only reads the loss of a step)
+    attach_eval_path(args, model, engine.arena)
     total_time, val_accs, test_accs = 0., [], []
     for epoch in range(args.n_epochs):                     # cluster_gcn.py:89-127
         log(f'Running epoch {epoch} / {args.n_epochs}', flush=True)
@@ -187,6 +202,8 @@ def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, 
     if args.model_type == 'gat' and getattr(args, 'host_path', 'engine') == 'phases':
         from gist_amd.module_engine import bind_gat
         bind_gat(model, cluster_iterator)            # model(cluster), loss.backward(), optimizer.step(): the fused step's phases
+    if args.model_type == 'gat':
+        attach_eval_path(args, model)
     loss_f = CrossEntropyLoss()                                                                        # :76
     optimizer = Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)                   # :77-80
     total_time, val_accs, test_accs = 0., [], []

@@ -35,6 +35,9 @@ def build_parser():
     # gist_gat_step per iteration; phases: the module loop with sub_model bound to the iterator, three
     # gist_gat_step_phase calls per iteration (gist_amd.ist.train_gat, host_path)
     parser.add_argument("--host-path", choices=['module', 'engine', 'phases'], default='module')
+    # (not a flag of the reference) blocked: rank 0's evaluate(base_model, g, ...) runs gist_amd.gat_eval's
+    # GATFullGraphEvaluator instead of the model's own forward (gist_amd.ist.train_gat, eval_path)
+    parser.add_argument("--eval-path", choices=['layers', 'blocked'], default='layers')
     return parser
 
 
@@ -84,7 +87,8 @@ def main(args=None, dataset=None, log=print):
     if host_path == 'engine':
         cluster_iterator.bind(ist_model.attach_engine(cluster_iterator.n_max))
     res = ist.train_gat(ist_model, args, g, cluster_iterator, g.ndata['label'], g.ndata['val_mask'],
-                        g.ndata['test_mask'], log=log, host_path=host_path)
+                        g.ndata['test_mask'], log=log, host_path=host_path,
+                        eval_path=getattr(args, 'eval_path', 'layers'))
     if args.rank == 0:
         path = report(args, res, log=log)
         if path is not None:

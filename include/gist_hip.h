@@ -1003,6 +1003,33 @@ int gist_gat_backward_src_cat_f32(const int32_t *t_rowptr, const int32_t *t_col,
                                   const float *ds_dst, int64_t n_rows, int64_t heads, int64_t out_dim,
                                   float *dZ, int64_t lddz, float *ds_src, gist_stream_t stream);
 
+/* Full-graph evaluation of a layer in two passes (an addition: ABI 16), for a graph whose ids are ordered by part.
+ *
+ * M[i,h] = max, L[i,h] = sum of exp(e - M[i,h]) of e = leaky_relu(s_src[col[e],h] + s_dst[i,h], 0.01) over row i's
+ * in-edges (duplicates count; M = L = 0 for a row without in-edges).  Reads no Z.  M is the exact fp32 max: bitwise the
+ * M of gist_gat_aggregate_f32; L has its own, fixed, sum order.
+ * Replaces the softmax statistics of reduce_func inside utils.evaluate's full-graph forward,
+ * cluster_gcn/utils.py:70-80 over GAT.forward, cluster_gcn/modules.py:93-98. */
+int gist_gat_row_stats_f32(const int32_t *rowptr, const int32_t *col, const float *s_src, const float *s_dst,
+                           int64_t n_rows, int64_t heads, float *M, float *L, gist_stream_t stream);
+
+/* gist_gat_aggregate_f32 (cat = 0) or gist_gat_aggregate_cat_f32 (cat != 0) with M and L GIVEN (read, not written)
+ * and the rows cut into blocks: block_ptr = device int32[n_blocks + 1], increasing boundaries 0 .. n_rows, every
+ * block 1..128 consecutive rows (the caller's promise; a row outside every block is not written).  rowptr / col are
+ * the whole in-edge CSR.  The edges j -> i with j in i's block run as a dense product per block and head,
+ * W_h[i][j] = c_ij exp(e_hij - M[i,h]) / L[i,h] (c_ij = the cell's edge count, integer LDS counters of 32 bits) times
+ * Z_h of the block's rows on the fp32 matrix cores; every other edge is walked and added; then the epilogue of the
+ * entries above (head mean or concatenation, ELU, 0 for a row without in-edges).  Two launches (dense sums into out,
+ * then remainder + epilogue over out), no float atomics: bitwise reproducible.  The walker's vectorised path needs
+ * out_dim, ldz, ldo % 4 == 0 and 16-byte aligned Z and out; any out_dim >= 1 and heads >= 1 is correct.
+ * Replaces the full-graph forward of utils.evaluate, cluster_gcn/utils.py:70-80 over cluster_gcn/modules.py:93-98
+ * (per layer g.apply_edges + g.update_all, the head merge and F.elu). */
+int gist_gat_aggregate_blocks_f32(const int32_t *rowptr, const int32_t *col, const int32_t *block_ptr,
+                                  int64_t n_blocks, const float *Z, int64_t ldz, const float *s_src,
+                                  const float *s_dst, const float *M, const float *L, int64_t n_rows,
+                                  int64_t heads, int64_t out_dim, int elu, int cat, float *out, int64_t ldo,
+                                  gist_stream_t stream);
+
 /* Floats of the partial-slab workspace gist_gat_attn_grad_f32 needs.  Host function. */
 int64_t gist_gat_attn_grad_workspace_floats(int64_t n_rows, int64_t heads, int64_t out_dim);
 /* dA[h, 0:F] = sum_r ds_src[r,h] Z[r, hF:(h+1)F],  dA[h, F:2F] = sum_r ds_dst[r,h] Z[r, hF:(h+1)F]
