@@ -77,6 +77,17 @@ class FlatArena(object):
     def export(self):
         return [tuple(t.detach().cpu().numpy().copy() for t in pair) for pair in zip(*self.views)]
 
+    @staticmethod
+    def module_params(model):
+        """The Parameters of the family's nn.Module that live in this arena, in `model.parameters()` order."""
+        raise NotImplementedError
+
+    def param_views(self, flat=None):
+        """Per Parameter of module_params, its block of `flat` -- a flat tensor in this arena's layout; None: `params`.
+        (Here: per layer tensor 1, then tensor 2.)"""
+        pairs = zip(*self.views) if flat is None else (self.layer_views(flat, k) for k in range(len(self.dims)))
+        return [v for pair in pairs for v in pair]
+
 
 class ParamArena(FlatArena):
     """GraphSAGE layers, dims = [(in, out)]: W [out, 2*in] and b [out]."""
@@ -90,6 +101,10 @@ class ParamArena(FlatArena):
         FlatArena.__init__(self, dims, device)
         if with_grads:          # a base-model replica (IST) holds parameters only
             self.with_grads()
+
+    @staticmethod
+    def module_params(gcn):
+        return [p for layer in gcn.layers for p in (layer.linear.weight, layer.linear.bias)]
 
     def adopt_module(self, gcn):
         """Re-home an nn.Module GCN's parameters into the arena (values preserved)."""
@@ -143,7 +158,7 @@ class GATArena(FlatArena):
             for h, head in enumerate(layer.heads):
                 head.fc.weight = nn.Parameter(self.W[k][h * o:(h + 1) * o], requires_grad=requires_grad)
                 head.attn_fc.weight = nn.Parameter(self.A[k][h:h + 1], requires_grad=requires_grad)
-        gat.__dict__['_gist_arena'] = weakref.ref(self)      # (module_engine.shared_gat_arena: a binding adopts it)
+        gat.__dict__['_gist_arena'] = weakref.ref(self)      # (module_engine.shared_arena: a binding adopts it)
         return gat
 
     def head_views(self, flat=None):
@@ -156,12 +171,17 @@ class GATArena(FlatArena):
                 out += [W[h * o:(h + 1) * o], A[h:h + 1]]
         return out
 
+    param_views = head_views
+
+    @staticmethod
+    def module_params(gat):
+        return [p for layer in gat.layers for head in layer.heads for p in (head.fc.weight, head.attn_fc.weight)]
+
     def adopt_module(self, gat):
         """Re-home a gist_amd.modules.GAT's parameters onto their per-head rows of the arena, values preserved.  The
         Parameters keep their identity (an optimiser built before the binding keeps stepping them); only their .data
         moves."""
-        views = self.head_views()
-        params = [p for layer in gat.layers for head in layer.heads for p in (head.fc.weight, head.attn_fc.weight)]
+        views, params = self.head_views(), self.module_params(gat)
         assert len(params) == len(views)
         for p, v in zip(params, views):
             if p.data_ptr() != v.data_ptr():

@@ -132,6 +132,8 @@ class StepEngine(object):
         self.prefetch = False
         self._extract_scratch = self._timer = None
         self._mark, self._mark_np, self._mark_tag = None, None, 0     # check_extract_deferred's pinned progress mark
+        # the last forward phase: (batch, flags, ids pointer, what else the family's call takes -- SageEngine's dropout offset)
+        self._phase_ctx = (None, 0, None, None)
 
     def _bind_graph(self, P, batcher):
         """The fields both plan structs share: the resident training graph and the batcher's batch buffers."""
@@ -184,6 +186,41 @@ class StepEngine(object):
         if b.batcher is not None:
             b.batcher.prefetched = nxt
         b.ready = True
+
+    def _run(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, phase=0, given=False, adam_step=None):
+        """One call of the family's step.  phase = 0: the whole iteration; GIST_STEP_PHASE_FORWARD / _BACKWARD /
+        _OPTIMIZER: one third of it (the module path: model(cluster), loss.backward(), optimizer.step(),
+        gist_amd/module_engine.py); the backward and optimiser calls reuse the forward call's batch, flags and extra
+        argument.  given: the caller wrote its own dlogits.  adam_step: the optimiser's own count (else the arena's).
+        A family states _open_step (the start of a forward: -> flags, ids pointer, extra), _plan_next, _call_step (the
+        one C-ABI call) and, if it has one, _close_step."""
+        nxt = None
+        if phase in (_lib.GIST_STEP_PHASE_BACKWARD, _lib.GIST_STEP_PHASE_OPTIMIZER):
+            cb, flags, ids_ptr, extra = self._phase_ctx
+            if cb is not b:
+                raise RuntimeError('gist_amd: backward / optimiser phase of a batch that is not the last one forwarded')
+            if phase == _lib.GIST_STEP_PHASE_OPTIMIZER:
+                nxt, flags = self._plan_next(b, flags)
+                self.arena.step += 1
+            elif given:
+                flags |= _lib.GIST_STEP_DLOGITS_GIVEN
+        else:
+            flags, ids_ptr, extra = self._open_step(b, train)
+            if phase == 0:
+                nxt, flags = self._plan_next(b, flags)      # (after _open_step: SageEngine's reads the advanced drop_calls)
+                if train:
+                    self.arena.step += 1
+            else:
+                self._phase_ctx = (b, flags, ids_ptr, extra)
+        self._call_step(ids_ptr, b.n, extra, lr, betas, eps, weight_decay,
+                        max(adam_step if adam_step is not None else self.arena.step, 1), flags, phase)
+        self._close_step(b, train)
+        if phase != _lib.GIST_STEP_PHASE_BACKWARD:      # (a backward phase leaves the batcher's prefetch key alone)
+            self._end_step(b, nxt)
+        return self.loss
+
+    def _close_step(self, b, train):
+        pass
 
     def _extraction_scratch(self):
         """The barrier ticket + counts of the one-launch extraction (allocated at its first use)."""
@@ -299,7 +336,6 @@ class SageEngine(StepEngine):
                 self.H[k] = torch.zeros(self.n_max, ld, **f32)
         self._prefetch_refused = None
         self._spmm_prep = None      # prepared block structure of the current batch (native step)
-        self._phase_ctx = (None, 0, 0, None)    # (batch, dropout offset, flags, ids pointer) of the last forward phase
         self._twin = op_by_op.Step()            # the op-by-op path's record of its last forward: nothing forwarded yet
         self._fused = None                      # ... and its own slabs / chunk sums (op_by_op.fused_buffers)
 
@@ -373,56 +409,41 @@ class SageEngine(StepEngine):
                            self._col_partials)     # keep every buffer alive
         return P
 
-    def _native_step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, phase=0, given=False,
-                     adam_step=None):
-        """One gist_sage_step call.  phase = 0: the whole iteration; GIST_STEP_PHASE_FORWARD / _BACKWARD / _OPTIMIZER: one
-        third of it (the module path: GCN.forward, loss.backward(), optimizer.step()); the backward and optimiser calls
-        reuse the forward call's batch, dropout offset and flags.  given: the caller wrote its own dlogits."""
-        L, P, nxt = _lib.load(), self.plan, None
-        if phase in (_lib.GIST_STEP_PHASE_BACKWARD, _lib.GIST_STEP_PHASE_OPTIMIZER):
-            cb, off, flags, ids_ptr = self._phase_ctx
-            if cb is not b:
-                raise RuntimeError('gist_amd: backward / optimiser phase of a batch that is not the last one forwarded')
-            if phase == _lib.GIST_STEP_PHASE_OPTIMIZER:
-                nxt, flags = self._plan_next(b, flags)
-                self.arena.step += 1
-            elif given:
-                flags |= _lib.GIST_STEP_DLOGITS_GIVEN
+    # One gist_sage_step call (StepEngine._run), under the name ModuleEngine, the tests and bench.py call it by
+    _native_step = StepEngine._run
+
+    def _open_step(self, b, train):
+        """-> (flags, ids pointer, this step's dropout offset); the per-batch fields of the plan are written."""
+        L, P = _lib.load(), self.plan
+        off = self.drop_calls
+        # (the GEMM mode decides whether layer 0's mask was folded into a pre-extraction's feature gather)
+        flags, ids_ptr = self._begin_step(b, train, (off, L.gist_gemm_get_mode()), one_launch=self.fuse)
+        if train and self.p_drop > 0.0:
+            for (i, o) in self.dims:
+                numel = b.n * 2 * i
+                self.drop_calls += numel + (numel & 1)
+        rb = b.row_blocks
+        P.sibling_parts = 1 if b.siblings else 0
+        if rb is not None and rb.numel() > 1:
+            P.row_blocks, P.n_row_blocks = rb.data_ptr(), rb.numel() - 1
+            # room for the batch's prepared block structure (include/gist_hip.h, spmm_prepared):
+            # both orientations, grown to the largest block count seen
+            need = 2 * L.gist_spmm_blocks_bytes(rb.numel() - 1)
+            if self._spmm_prep is None or self._spmm_prep.numel() < need:
+                self._spmm_prep = torch.empty(need + need // 4, dtype=torch.uint8, device=self.device)
+                P.spmm_prepared, P.spmm_prepared_bytes = self._spmm_prep.data_ptr(), self._spmm_prep.numel()
         else:
-            off = self.drop_calls
-            # (the GEMM mode decides whether layer 0's mask was folded into a pre-extraction's feature gather)
-            flags, ids_ptr = self._begin_step(b, train, (off, L.gist_gemm_get_mode()), one_launch=self.fuse)
-            if train and self.p_drop > 0.0:
-                for (i, o) in self.dims:
-                    numel = b.n * 2 * i
-                    self.drop_calls += numel + (numel & 1)
-            if train and phase == 0:
-                self.arena.step += 1
-            rb = b.row_blocks
-            P.sibling_parts = 1 if b.siblings else 0
-            if rb is not None and rb.numel() > 1:
-                P.row_blocks, P.n_row_blocks = rb.data_ptr(), rb.numel() - 1
-                # room for the batch's prepared block structure (include/gist_hip.h, spmm_prepared):
-                # both orientations, grown to the largest block count seen
-                need = 2 * L.gist_spmm_blocks_bytes(rb.numel() - 1)
-                if self._spmm_prep is None or self._spmm_prep.numel() < need:
-                    self._spmm_prep = torch.empty(need + need // 4, dtype=torch.uint8, device=self.device)
-                    P.spmm_prepared, P.spmm_prepared_bytes = self._spmm_prep.data_ptr(), self._spmm_prep.numel()
-            else:
-                P.row_blocks, P.n_row_blocks = None, 0
-            if phase == 0:
-                nxt, flags = self._plan_next(b, flags)
-            else:
-                self._phase_ctx = (b, off, flags, ids_ptr)
-        rc = L.gist_sage_step(ctypes.byref(P), ids_ptr, b.n, off, lr, betas[0], betas[1], eps, weight_decay,
-                              max(adam_step if adam_step is not None else self.arena.step, 1), flags | phase,
-                              hip._stream())
+            P.row_blocks, P.n_row_blocks = None, 0
+        return flags, ids_ptr, off
+
+    def _call_step(self, ids_ptr, n, off, lr, betas, eps, weight_decay, t, flags, phase):
+        rc = _lib.load().gist_sage_step(ctypes.byref(self.plan), ids_ptr, n, off, lr, betas[0], betas[1], eps,
+                                        weight_decay, t, flags | phase, hip._stream())
         _lib.check(rc, 'gist_sage_step')
+
+    def _close_step(self, b, train):
         if not b.ready and train and self.fuse and self.p_drop > 0.0 and self.H[0] is not None:
             b.z0_dropped = True      # (one training step per extraction: Batch contract)
-        if phase != _lib.GIST_STEP_PHASE_BACKWARD:      # (a backward phase leaves the batcher's key alone)
-            self._end_step(b, nxt)
-        return self.loss
 
     def _plan_next(self, b, flags):
         """The NEXT batch of the epoch, extracted beside this step's optimiser launch (GIST_STEP_EXTRACT_NEXT): only for

@@ -48,7 +48,7 @@ class GATEngine(StepEngine):
             raise ValueError('gist_amd: more than %d GAT layers' % _lib.GIST_MAX_LAYERS)
         StepEngine.__init__(self, arena.device if device is None else device, n_max)
         n = self.n_max
-        self.n_classes = self.dims[-1][1]
+        self.n_classes = self.ldc = self.dims[-1][1]         # (the logits are dense: no padded columns)
         # columns of every layer's output: the next layer's input width (the step checks it is out_k or heads_k * out_k)
         widths = [i for (i, o, h) in self.dims[1:]] + [self.n_classes]
         self.merge = 'cat' if any(w != o for w, (i, o, h) in zip(widths, self.dims)) else 'mean'
@@ -82,7 +82,6 @@ class GATEngine(StepEngine):
         self.loss = torch.zeros(1, **f32)
         self._model = None
         self._lent = False                      # the plan's logits / loss / moment pointers are a GATModuleEngine's
-        self._phase_ctx = (None, 0, None)       # (batch, flags, ids pointer) of the last forward phase
 
     def attach_batcher(self, batcher):
         """Build the native step plan (struct gist_gat_step_plan) over `batcher`'s resident graph and batch buffers."""
@@ -165,41 +164,24 @@ class GATEngine(StepEngine):
                         flags | _lib.GIST_STEP_EXTRACT_NEXT)
         return None, flags
 
+    def _open_step(self, b, train):
+        return self._begin_step(b, train, ()) + (None,)
+
+    def _call_step(self, ids_ptr, n, extra, lr, betas, eps, weight_decay, t, flags, phase):
+        name = 'gist_gat_step_phase' if phase else 'gist_gat_step'
+        rc = getattr(_lib.load(), name)(ctypes.byref(self.plan), ids_ptr, n, lr, betas[0], betas[1], eps, weight_decay, t,
+                                        flags | phase, hip._stream())
+        _lib.check(rc, name)
+
     def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, phase=0, given=False, adam_step=None,
               lent=False):
-        """One gist_gat_step call (phase = 0: the whole iteration), or one gist_gat_step_phase call: GIST_STEP_PHASE_FORWARD
-        / _BACKWARD / _OPTIMIZER, one third of it (the bound module path: GAT.forward, loss.backward(), optimizer.step(),
-        gist_amd/module_engine.py).  The backward and optimiser calls reuse the forward call's batch and flags.  given:
-        the caller wrote its own dlogits.  adam_step: the optimiser's own count (else the arena's)."""
+        """One gist_gat_step call (phase = 0: the whole iteration), or one gist_gat_step_phase call, one third of it
+        (StepEngine._run), on the engine's own logits, loss and moment buffers unless a binding lent the plan its own."""
         if self.plan is None:
             raise RuntimeError('gist_amd: GATEngine needs attach_batcher (EngineClusterIter.bind) first')
         if self._lent and not lent:
             self._reclaim()
-        L, P, nxt = _lib.load(), self.plan, None
-        if phase in (_lib.GIST_STEP_PHASE_BACKWARD, _lib.GIST_STEP_PHASE_OPTIMIZER):
-            cb, flags, ids_ptr = self._phase_ctx
-            if cb is not b:
-                raise RuntimeError('gist_amd: backward / optimiser phase of a batch that is not the last one forwarded')
-            if phase == _lib.GIST_STEP_PHASE_OPTIMIZER:
-                nxt, flags = self._plan_next(b, flags)
-                self.arena.step += 1
-            elif given:
-                flags |= _lib.GIST_STEP_DLOGITS_GIVEN
-        else:
-            flags, ids_ptr = self._begin_step(b, train, ())
-            if phase == 0:
-                nxt, flags = self._plan_next(b, flags)
-                if train:
-                    self.arena.step += 1
-            else:
-                self._phase_ctx = (b, flags, ids_ptr)
-        step = L.gist_gat_step_phase if phase else L.gist_gat_step
-        rc = step(ctypes.byref(P), ids_ptr, b.n, lr, betas[0], betas[1], eps, weight_decay,
-                  max(adam_step if adam_step is not None else self.arena.step, 1), flags | phase, hip._stream())
-        _lib.check(rc, 'gist_gat_step_phase' if phase else 'gist_gat_step')
-        if phase != _lib.GIST_STEP_PHASE_BACKWARD:      # (a backward phase leaves the batcher's prefetch key alone)
-            self._end_step(b, nxt)
-        return self.loss
+        return self._run(b, lr, weight_decay, train, betas, eps, phase, given, adam_step)
 
     def _native_step(self, *args, **kw):
         """_step for module_engine.GATModuleEngine (the name ModuleEngine calls its engine's phases by), which points

@@ -29,9 +29,12 @@ step reads (they run on the step's stream, after the optimiser launch that extra
 parameter).  Parameters after a step are bitwise those of the engine path (tests/test_module_engine_gpu.py).  GIST_MODULE_ENGINE=0 turns the binding off (the
 op-by-op module path of gist_amd/autograd.py, one dispatcher op per layer: the parity twin).
 
-The GAT family has the same surface on gist_gat_step_phase (GATModuleEngine at the end of this file), but only for a
-model that was bound explicitly: `bind_gat(model, cluster_iterator)`.  An unbound gist_amd.modules.GAT keeps the
-op-by-op path, the independent twin its tests compare the fused step with.
+That is ONE binding, ModuleEngine, for two families.  What is said above of the GCN holds for gist_amd.modules.GAT on
+gist_gat_step_phase, with `gist::gat_forward` / `gist::gat_backward` as its two ops: GATModuleEngine states only where
+the families differ -- how the engine is built and tied to the iterator, which plan field takes the logits, and that the
+logits are saved on the tape (the last GAT layer's ELU backward reads them).  A GAT gets it only when it was bound
+explicitly: `bind_gat(model, cluster_iterator)`.  An unbound gist_amd.modules.GAT keeps the op-by-op path, the
+independent twin its tests compare the fused step with.
 """
 import os
 import weakref
@@ -39,6 +42,7 @@ import weakref
 import torch
 
 from . import _lib, hip
+from .arena import GATArena
 from .engine import SageEngine
 
 _REGISTRY = weakref.WeakValueDictionary()      # handle -> ModuleEngine (owned by its model)
@@ -52,67 +56,61 @@ def _storage_uses(t):
     return torch._C._storage_Use_Count(t.untyped_storage()._cdata)
 
 _lib_def = torch.library.Library('gist', 'FRAGMENT')
-_lib_def.define('gcn_forward(Tensor[] params, int handle, int token, int n, int ldc, bool train) -> Tensor')
-_lib_def.define('gcn_backward(Tensor d_logits, int handle, int token, bool given) -> Tensor[]')
-# the GAT family's pair (GATModuleEngine below): the forward and backward phases of gist_gat_step_phase
-_lib_def.define('gat_forward(Tensor[] params, int handle, int token, int n, int ldc, bool train) -> Tensor')
-_lib_def.define('gat_backward(Tensor d_logits, int handle, int token, bool given) -> Tensor[]')
 
 
-def _gcn_forward_cuda(params, handle, token, n, ldc, train):
-    """GCN.forward (cluster_gcn/modules.py:310-314) on the pending cluster batch of module engine `handle`: returns the
-    padded logits [n, ldc] (columns >= n_classes are padding)."""
+def _forward_cuda(params, handle, token, n, ldc, train):
+    """GCN.forward (cluster_gcn/modules.py:310-314) / GAT.forward on the pending cluster batch of module engine `handle`:
+    returns the padded logits [n, ldc] (columns >= n_classes are padding)."""
     return _REGISTRY[handle]._run_forward(token, n, ldc, train)
 
 
-def _gcn_backward_cuda(d_logits, handle, token, given):
+def _backward_cuda(d_logits, handle, token, given):
     """The backward pass of the forward `token` into the gradient arena; returns its per-parameter views
     [dW_0, db_0, dW_1, ...].  given: d_logits [n, ldc] is the caller's gradient w.r.t. the padded logits (else the mean
     CE's, already formed by the forward)."""
     return _REGISTRY[handle]._run_backward(token, d_logits, given)
 
 
-_lib_def.impl('gcn_forward', _gcn_forward_cuda, 'CUDA')
-_lib_def.impl('gcn_backward', _gcn_backward_cuda, 'CUDA')
-_lib_def.impl('gat_forward', _gcn_forward_cuda, 'CUDA')        # (the same look-up: the handle names the engine)
-_lib_def.impl('gat_backward', _gcn_backward_cuda, 'CUDA')
-
-
-@torch.library.register_fake('gist::gcn_forward')
-def _(params, handle, token, n, ldc, train):
+def _forward_fake(params, handle, token, n, ldc, train):
     return params[0].new_empty(n, ldc)
 
 
-@torch.library.register_fake('gist::gcn_backward')
-def _(d_logits, handle, token, given):
+def _backward_fake(d_logits, handle, token, given):
     return [d_logits.new_empty(v.shape) for v in _REGISTRY[handle].grad_views]
 
 
-@torch.library.register_fake('gist::gat_forward')
-def _(params, handle, token, n, ldc, train):
-    return params[0].new_empty(n, ldc)
+# one pair of ops per family, the forward and backward phases of gist_sage_step / gist_gat_step_phase: the same look-up
+# (the handle names the engine) under the names the traces and the tests know
+for _family in ('gcn', 'gat'):
+    _lib_def.define(_family + '_forward(Tensor[] params, int handle, int token, int n, int ldc, bool train) -> Tensor')
+    _lib_def.define(_family + '_backward(Tensor d_logits, int handle, int token, bool given) -> Tensor[]')
+    _lib_def.impl(_family + '_forward', _forward_cuda, 'CUDA')
+    _lib_def.impl(_family + '_backward', _backward_cuda, 'CUDA')
+    torch.library.register_fake('gist::%s_forward' % _family, _forward_fake)
+    torch.library.register_fake('gist::%s_backward' % _family, _backward_fake)
 
 
-@torch.library.register_fake('gist::gat_backward')
-def _(d_logits, handle, token, given):
-    return [d_logits.new_empty(v.shape) for v in _REGISTRY[handle].grad_views]
-
-
-class _GCNForward(torch.autograd.Function):
-    """The tape entry of gist::gcn_forward: its backward is gist::gcn_backward."""
+class _StepForward(torch.autograd.Function):
+    """The tape entry of gist::gcn_forward / gist::gat_forward: its backward is the family's backward op.  An engine whose
+    backward reads the logits (GAT: the last layer's ELU) has them saved on the tape: torch's version check refuses a
+    backward after an in-place edit of them."""
 
     # (the node knows its engine weakly: autograd hangs it on the output -- a view of the engine's own ring buffer --
     # and a strong reference would close engine -> buffer -> node -> engine through C++, where no collector looks)
     @staticmethod
     def forward(ctx, me, token, n, ldc, *params):
         ctx.me, ctx.token, ctx.n_in = weakref.ref(me), token, 4 + len(params)
-        return torch.ops.gist.gcn_forward(list(params), me.handle, token, n, ldc, True)
+        y = me._forward_op(list(params), me.handle, token, n, ldc, True)
+        if me._saves_logits:
+            ctx.save_for_backward(y)
+        return y
 
     @staticmethod
     def backward(ctx, d_y):
         me = ctx.me()
         if me is None:
             raise RuntimeError('gist_amd: backward through the forward of a model that no longer exists')
+        ctx.saved_tensors                              # (raises if saved logits were modified in place)
         me.autograd_backward(ctx.token, d_y)
         return (None,) * ctx.n_in                      # (the gradients were delivered to p.grad: arena views)
 
@@ -181,44 +179,57 @@ def eligible(model):
     return True
 
 
-def shared_arena(model, dims):
-    """The ParamArena every parameter of `model` already is a view of, in that arena's layout and with `dims`
-    (ParamArena.bind_module recorded it), or None."""
+def shared_arena(model, dims, need_grads=True):
+    """The arena (ParamArena, GATArena) every parameter of `model` already is a view of, in that arena's layout and with
+    `dims` (ParamArena.bind_module / GATArena.bind recorded it: the sub_model of a gist_amd.ist wrapper), or None.
+    need_grads: not one without gradients (SageEngine allocates none; GATEngine does, with_grads)."""
     ref = model.__dict__.get('_gist_arena')
     A = ref() if ref is not None else None
-    if A is None or A.grads is None or [(int(i), int(o)) for i, o in A.dims] != dims:
+    if A is None or (need_grads and A.grads is None) or [tuple(int(x) for x in d) for d in A.dims] != dims:
         return None
-    for k, l in enumerate(model.layers):
-        if l.linear.weight.data_ptr() != A.W[k].data_ptr() or l.linear.bias.data_ptr() != A.b[k].data_ptr():
+    for p, v in zip(A.module_params(model), A.param_views()):
+        if p.data_ptr() != v.data_ptr() or p.shape != v.shape:
             return None
     return A
 
 
 class ModuleEngine(object):
-    """One nn.Module GCN bound to one ClusterIter: the SageEngine behind `model(cluster)`."""
-    _backward_op = torch.ops.gist.gcn_backward      # (GATModuleEngine: gist::gat_backward)
+    """One nn.Module GCN bound to one ClusterIter: the SageEngine behind `model(cluster)`.  Also the whole binding of the
+    GAT family, whose GATModuleEngine restates the attributes and the two hooks that follow."""
+    family = 'GCN'
+    _forward_op, _backward_op = torch.ops.gist.gcn_forward, torch.ops.gist.gcn_backward
+    _saves_logits = False       # does the backward read the logits?  (then an in-place edit of them is refused)
+    _twin_hint = 'GIST_MODULE_ENGINE=0 for the op-by-op path'
 
-    def __init__(self, model, it):
+    def _bind_engine(self, model, it, dims):
+        """The step engine of `model`, tied to `it`, the model's parameters views of its arena."""
         layers = list(model.layers)
-        self._model, self.it = weakref.ref(model), it
         dims = [(l.linear.in_features // 2, l.linear.out_features) for l in layers]
-        dev = it.g.device
         ln = layers[0].use_lynorm if len(layers) > 1 else False
         # a DistributedGNNWrapper's sub_model already IS its arena: the engine steps that arena in place (dispatch and
         # sync write it between steps); any other model is re-homed into an arena of the engine's own
         shared = shared_arena(model, dims)
-        self.engine = eng = SageEngine(dims, ln, layers[0].p_drop, it.n_max, dev, seed=getattr(model, '_drop_seed', 0),
-                                       arena=shared)
+        eng = SageEngine(dims, ln, layers[0].p_drop, it.n_max, it.g.device, seed=getattr(model, '_drop_seed', 0),
+                         arena=shared)
         if shared is None:
             eng.arena.adopt_module(model)
         eng.prefetch = True
         it.bind(eng)
+        return eng
+
+    def _point_logits(self, P, ptr):
+        """Where the plan takes the address of this step's logits."""
+        P.layer[self._last].Y = ptr
+
+    def __init__(self, model, it, dims=None):
+        self._model, self.it = weakref.ref(model), it
+        self.engine = eng = self._bind_engine(model, it, dims)
         if eng.plan is None:
             raise RuntimeError('gist_amd: no native step plan for this model')
         A = eng.arena
-        self.params = [p for l in layers for p in (l.linear.weight, l.linear.bias)]
-        self.grad_views = [v for k in range(len(layers)) for v in (A.dW[k], A.db[k])]
-        self._home_ptrs = [v.data_ptr() for k in range(len(layers)) for v in (A.W[k], A.b[k])]
+        self.params = A.module_params(model)
+        self.grad_views = A.param_views(A.grads)
+        self._home_ptrs = [v.data_ptr() for v in A.param_views()]
         # (a Parameter knows its engine by HANDLE: a strong reference here would close a Parameter <-> ModuleEngine cycle
         # that only the cyclic collector could free -- and never does once the objects are in its permanent generation)
         self.n_classes, self.ldc = eng.n_classes, eng.ldc
@@ -229,10 +240,11 @@ class ModuleEngine(object):
             p._gist_me = self.handle
         self.token = 0
         self.state = _IDLE
-        self._pending = None        # (engine Batch, cluster, logits tensor)
+        self._pending = None        # (engine Batch, cluster) of the last forward
         self._loss0 = None
-        self._f32 = dict(dtype=torch.float32, device=dev)
-        self._last = len(layers) - 1
+        self._pred = None           # _saves_logits: (weak reference to the logits handed out, their version then)
+        self._f32 = dict(dtype=torch.float32, device=it.g.device)
+        self._last = len(eng.dims) - 1
         self._first_step = True
         # logits and loss of a step live in small rings (no allocator call in the loop).  A slot whose tensor the caller
         # still holds (the tensor, a view of it, `preds.append(model(c))`) is NOT reused: the ring gets a fresh buffer
@@ -270,35 +282,39 @@ class ModuleEngine(object):
         b.siblings = g.siblings
         P = eng.plan
         self.token += 1
-        self._pending = None          # (the previous step's view of its ring slot)
+        self._pending = self._pred = None
         if not training:
             y = torch.empty(n, self.ldc, **self._f32)      # evaluation: every call's logits are their own tensor
-        else:
+        else:                                              # (the first n rows of the slot: _run_forward hands them out)
             y = self._ring_slot(self._logit_ring, self.token & 3,
-                                lambda: torch.empty(self.it.n_max, self.ldc, **self._f32))[:n]
-        P.layer[self._last].Y = y.data_ptr()
+                                lambda: torch.empty(self.it.n_max, self.ldc, **self._f32))
+        self._point_logits(P, y.data_ptr())
         self._loss0 = self._ring_slot(self._loss_ring, self.token & 63, lambda: torch.zeros((), **self._f32))
         P.loss = self._loss0.data_ptr()
-        self._pending = (b, g, y)
+        self._pending = (b, g)
         if not training:
             eng._native_step(b, 0.0, 0.0, train=False)
             self.state = _IDLE
             return y if self.ldc == self.n_classes else y[:, :self.n_classes]
         if torch.is_grad_enabled():
-            out = _GCNForward.apply(self, self.token, n, self.ldc, *self.params)
+            out = _StepForward.apply(self, self.token, n, self.ldc, *self.params)
         else:
-            out = torch.ops.gist.gcn_forward(self.params, self.handle, self.token, n, self.ldc, True)
+            out = self._forward_op(self.params, self.handle, self.token, n, self.ldc, True)
         pred = out if self.ldc == self.n_classes else out[:, :self.n_classes]
         pred._gist_step = (self, self.token)
+        if self._saves_logits:
+            self._pred = (weakref.ref(pred), pred._version)
         return pred
 
     def _run_forward(self, token, n, ldc, train):
-        b, g, y = self._pending
+        b = self._pending[0]
         if token != self.token or n != b.n:
-            raise RuntimeError('gist_amd: gist::gcn_forward called with a stale token')
+            raise RuntimeError('gist_amd: gist::%s_forward called with a stale token' % self.family.lower())
         self.engine._native_step(b, 0.0, 0.0, train=True, phase=_lib.GIST_STEP_PHASE_FORWARD)
         self.state = _FWD_DONE
-        return y
+        # the logits are the caller's from here (the plan has their address, the ring their storage): the engine holds
+        # no view of them, which would close a cycle through pred._gist_step that only the cyclic collector frees
+        return self._logit_ring[token & 3][:n]
 
     # ---- loss ----------------------------------------------------------------------------------------------------
     def fused_loss(self, logits, labels, token):
@@ -321,6 +337,10 @@ class ModuleEngine(object):
         """loss.backward() of the standard loop: True if the backward phase ran (gradients in p.grad)."""
         if token != self.token or self.state != _FWD_DONE:
             return False
+        pred = self._pred[0]() if self._pred is not None else None
+        if pred is not None and pred._version != self._pred[1]:
+            raise RuntimeError('gist_amd: the logits of this forward were modified in place before backward(); the last '
+                               '%s layer\'s backward reads them' % self.family)
         for p in self.params:
             if p.grad is not None or not p.requires_grad:
                 return False
@@ -331,8 +351,8 @@ class ModuleEngine(object):
 
     def _run_backward(self, token, d_logits, given):
         if token != self.token or self.state != _FWD_DONE:
-            raise RuntimeError('gist_amd: backward through a GCN forward that is no longer the model\'s latest (the '
-                               'engine reuses its buffers; GIST_MODULE_ENGINE=0 for the op-by-op path)')
+            raise RuntimeError('gist_amd: backward through a %s forward that is no longer the model\'s latest (the '
+                               'engine reuses its buffers; %s)' % (self.family, self._twin_hint))
         eng = self.engine
         b = self._pending[0]
         if given:
@@ -371,9 +391,7 @@ class ModuleEngine(object):
             A = self.engine.arena
             m = torch.zeros(A.numel, **self._f32)
             v = torch.zeros(A.numel, **self._f32)
-            for i, (p, gv) in enumerate(zip(self.params, self.grad_views)):
-                off = (gv.data_ptr() - A.grads.data_ptr()) // 4
-                mv, vv = m[off:off + p.numel()].view_as(p), v[off:off + p.numel()].view_as(p)
+            for i, (mv, vv) in enumerate(zip(A.param_views(m), A.param_views(v))):
                 if opt.state[i] is not None:          # moments of earlier per-tensor steps
                     mv.copy_(opt.state[i][0])
                     vv.copy_(opt.state[i][1])
@@ -427,31 +445,6 @@ def engine_for(model, g):
 
 
 # ---- the GAT family: gist_amd.modules.GAT bound to a ClusterIter, on the three phase calls of gist_gat_step_phase --------
-class _GATForward(torch.autograd.Function):
-    """The tape entry of gist::gat_forward: its backward is gist::gat_backward.  The last layer's ELU backward reads the
-    logits, so they are saved on the tape: torch's version check refuses a backward after an in-place edit of them."""
-
-    @staticmethod
-    def forward(ctx, me, token, n, ldc, *params):
-        ctx.me, ctx.token, ctx.n_in = weakref.ref(me), token, 4 + len(params)
-        y = torch.ops.gist.gat_forward(list(params), me.handle, token, n, ldc, True)
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, d_y):
-        me = ctx.me()
-        if me is None:
-            raise RuntimeError('gist_amd: backward through the forward of a model that no longer exists')
-        ctx.saved_tensors                              # (raises if the logits were modified in place)
-        me.autograd_backward(ctx.token, d_y)
-        return (None,) * ctx.n_in                      # (the gradients were delivered to p.grad: arena views)
-
-
-def _gat_params(model):
-    return [p for layer in model.layers for head in layer.heads for p in (head.fc.weight, head.attn_fc.weight)]
-
-
 def gat_model_dims(model):
     """[(in, out, heads)] of a gist_amd.modules.GAT as GATArena lays it out; ValueError if it is not the network
     gist_gat_step implements."""
@@ -482,35 +475,23 @@ def gat_model_dims(model):
     return dims
 
 
-def shared_gat_arena(model, dims):
-    """The GATArena every parameter of `model` already is a view of, in that arena's layout and with `dims`
-    (GATArena.bind recorded it: a DistributedGATWrapper's sub_model), or None.  By data_ptr, as shared_arena."""
-    ref = model.__dict__.get('_gist_arena')
-    A = ref() if ref is not None else None
-    if A is None or [tuple(int(x) for x in d) for d in A.dims] != dims:
-        return None
-    for p, v in zip(_gat_params(model), A.head_views()):
-        if p.data_ptr() != v.data_ptr() or p.shape != v.shape:
-            return None
-    return A
-
-
 class GATModuleEngine(ModuleEngine):
     """One gist_amd.modules.GAT bound to one ClusterIter (bind_gat): the GATEngine behind `model(cluster)`.  The surface
     is ModuleEngine's -- forward, fused loss, fast and taped backward, the optimiser's hooks -- on gist_gat_step_phase."""
-    _backward_op = torch.ops.gist.gat_backward
+    family = 'GAT'
+    _forward_op, _backward_op = torch.ops.gist.gat_forward, torch.ops.gist.gat_backward
+    _saves_logits = True        # (the last layer's ELU backward reads them)
+    _twin_hint = 'an unbound model runs op by op'
 
-    def __init__(self, model, it, dims):
+    def _bind_engine(self, model, it, dims):
         from .gat_engine import GATEngine
-        self._model, self.it = weakref.ref(model), it
-        dev = it.g.device
         others = [m for m in (r() for r in it.__dict__.setdefault('_gat_bound', [])) if m is not None]
         first = others[0] if others else None
         x0 = first.engine.X0 if first is not None else None
         # a DistributedGATWrapper's sub_model already IS its arena: the engine steps that arena in place (dispatch and
         # sync write it between steps) -- the wrapper's own engine if it has a fitting one; any other model is re-homed
         # into an arena of the engine's own
-        shared = shared_gat_arena(model, dims)
+        shared = shared_arena(model, dims, need_grads=False)
         eng = None
         if shared is not None:
             ref = shared.__dict__.get('_engine')
@@ -518,8 +499,7 @@ class GATModuleEngine(ModuleEngine):
             if eng is not None and eng.n_max != it.n_max:
                 eng = None
         if eng is None:
-            eng = GATEngine(dims, it.n_max, dev, arena=shared, x0=x0)
-        self.engine = eng
+            eng = GATEngine(dims, it.n_max, it.g.device, arena=shared, x0=x0)
         if shared is None:
             eng.arena.adopt_module(model)
         if first is None:
@@ -527,8 +507,6 @@ class GATModuleEngine(ModuleEngine):
                 it.bind(eng)                  # the iterator's engine: its epoch-end extraction check
         elif eng.plan is None or eng._plan_keep[0] is not it.batcher:
             eng.attach_batcher(it.batcher)
-        if eng.plan is None:
-            raise RuntimeError('gist_amd: no native step plan for this model')
         # one model on the iterator: the optimiser launch extracts the next batch.  Several (the S sites of one process):
         # they share the batch buffers and layer 0's input rows (the first engine's X0), so nobody extracts ahead and
         # every forward phase extracts its batch itself (one launch; the buffers then hold what they held)
@@ -536,83 +514,11 @@ class GATModuleEngine(ModuleEngine):
         for m in others:
             m.engine.prefetch = False
         eng.prefetch = not others
-        A = eng.arena
-        self.params = _gat_params(model)
-        self.grad_views = A.head_views(A.grads)
-        self._home_ptrs = [v.data_ptr() for v in A.head_views()]
-        self.n_classes = self.ldc = eng.n_classes
-        self.handle = _NEXT_HANDLE[0]
-        _NEXT_HANDLE[0] += 1
-        _REGISTRY[self.handle] = self
-        for p in self.params:
-            p._gist_me = self.handle
-        self.token = 0
-        self.state = _IDLE
-        self._pending = None        # (engine Batch, cluster, logits tensor)
-        self._loss0 = None
-        self._pred = None           # (weak reference to the logits handed out, their version when handed out)
-        self._f32 = dict(dtype=torch.float32, device=dev)
-        self._last = len(dims) - 1
-        self._first_step = True
-        self._logit_ring = [torch.empty(it.n_max, self.ldc, **self._f32) for _ in range(4)]
-        self._loss_ring = [torch.zeros((), **self._f32) for _ in range(64)]
-        self._idle_uses = _storage_uses(self._logit_ring[0])
+        return eng
 
-    def forward(self, g, training):
-        eng = self.engine
-        if not self.homed():          # model.to(...) / .data replaced: bring the values back into the arena
-            eng.arena.adopt_module(self._model())
-        n = g._n
-        b = self.it.batcher.lazy(g._ids)
-        b.row_blocks, b.parts, b.next_info = g.row_blocks, g.parts, g.next_info
-        b.siblings = g.siblings
-        P = eng.plan
-        self.token += 1
-        self._pending = self._pred = None          # (the previous step's view of its ring slot)
-        if not training:
-            y = torch.empty(n, self.ldc, **self._f32)      # evaluation: every call's logits are their own tensor
-        else:
-            y = self._ring_slot(self._logit_ring, self.token & 3,
-                                lambda: torch.empty(self.it.n_max, self.ldc, **self._f32))[:n]
-        eng._lent = True              # (the plan's logits, loss and moment pointers are this binding's until reclaimed)
-        P.layer[self._last].out = y.data_ptr()
-        self._loss0 = self._ring_slot(self._loss_ring, self.token & 63, lambda: torch.zeros((), **self._f32))
-        P.loss = self._loss0.data_ptr()
-        self._pending = (b, g, y)
-        if not training:
-            eng._native_step(b, 0.0, 0.0, train=False)
-            self.state = _IDLE
-            return y
-        if torch.is_grad_enabled():
-            pred = _GATForward.apply(self, self.token, n, self.ldc, *self.params)
-        else:
-            pred = torch.ops.gist.gat_forward(self.params, self.handle, self.token, n, self.ldc, True)
-        pred._gist_step = (self, self.token)
-        self._pred = (weakref.ref(pred), pred._version)
-        return pred
-
-    def _run_forward(self, token, n, ldc, train):
-        y = ModuleEngine._run_forward(self, token, n, ldc, train)
-        # the logits are the caller's from here (the plan has their address, the ring their storage): holding them would
-        # close a cycle through pred._gist_step that only the cyclic collector frees
-        self._pending = self._pending[:2] + (None,)
-        return y
-
-    def _logits_edited(self):
-        pred = self._pred[0]() if self._pred is not None else None
-        return pred is not None and pred._version != self._pred[1]
-
-    def fast_backward(self, token):
-        if token == self.token and self.state == _FWD_DONE and self._logits_edited():
-            raise RuntimeError('gist_amd: the logits of this forward were modified in place before backward(); the last '
-                               'GAT layer\'s ELU backward reads them')
-        return ModuleEngine.fast_backward(self, token)
-
-    def _run_backward(self, token, d_logits, given):
-        if token != self.token or self.state != _FWD_DONE:
-            raise RuntimeError('gist_amd: backward through a GAT forward that is no longer the model\'s latest (the '
-                               'engine reuses its buffers; an unbound model runs op by op)')
-        return ModuleEngine._run_backward(self, token, d_logits, given)
+    def _point_logits(self, P, ptr):
+        self.engine._lent = True      # (the plan's logits, loss and moment pointers are this binding's until reclaimed)
+        P.layer[self._last].out = ptr
 
 
 def bind_gat(model, cluster_iterator):
@@ -635,7 +541,7 @@ def bind_gat(model, cluster_iterator):
             return me
         if any(m is not None for m in mes.values()):
             raise ValueError('gist_amd: bind_gat: this model is already bound to another iterator')
-    params = _gat_params(model)
+    params = GATArena.module_params(model)
     dev = it.g.device
     if dev.type != 'cuda' or not it.feed():
         raise ValueError('gist_amd: bind_gat: the iterator does not describe its batches for on-device extraction '

@@ -335,6 +335,29 @@ def test_stale_and_edited_logits_are_refused():
     assert all(p.grad is None for p in model.parameters())
 
 
+def test_dispatcher_ops_schema_and_fake():
+    """gist::gat_forward / gist::gat_backward as tests/test_module_engine_gpu.py checks the GCN pair."""
+    from torch.library import opcheck
+    ds = _ds()
+    model, it, me = _bound(ds)
+    model.train()
+    cluster = next(iter(it))
+    with torch.no_grad():                   # (the pending forward's logits tensor must not be a tape output)
+        model(cluster)
+    assert 'gat_forward' in str(torch.ops.gist.gat_forward.default._schema)
+    with torch.no_grad():
+        args = ([p.detach() for p in me.params], me.handle, me.token, cluster.number_of_nodes(), me.ldc, True)
+        opcheck(torch.ops.gist.gat_forward.default, args, test_utils=('test_schema', 'test_faketensor'))
+    # (a backward consumes its forward's activations in place: it runs once per forward, so no repeated-call checks)
+    assert 'gat_backward' in str(torch.ops.gist.gat_backward.default._schema)
+    views = torch.ops.gist.gat_backward(me.engine.dlogits, me.handle, me.token, False)
+    assert len(views) == len(me.params) == len(me.grad_views)
+    for v, gv, p in zip(views, me.grad_views, me.params):
+        assert v.data_ptr() == gv.data_ptr() and v.shape == gv.shape == p.shape
+    with pytest.raises((RuntimeError, NotImplementedError)):
+        torch.ops.gist.gat_forward([p.cpu() for p in me.params], me.handle, me.token, 4, me.ldc, True)
+
+
 def test_eval_mode_and_full_graph_evaluation():
     from gist_amd.utils import evaluate
     ds = _ds()
