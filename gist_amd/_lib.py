@@ -158,6 +158,9 @@ SIGNATURES = {
     'gist_gat_row_stats_f32': (_int, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     'gist_gat_aggregate_blocks_f32': (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int,
                                              _p, _i64, _p]),
+    'gist_ln_all_partials': (_i64, [_i64]),
+    'gist_ln_all_fwd_f32': (_int, [_p, _p, _p, _i64, _f, _p, _p]),
+    'gist_ln_all_bwd_f32': (_int, [_p, _p, _p, _p, _i64, _p, _p]),
 }
 
 GIST_MAX_LAYERS = 16

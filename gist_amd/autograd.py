@@ -6,7 +6,7 @@ in libgist_hip.so.
   spmm_sum(g, x)        g.update_all(copy_src, sum)                (modules.py:224-225)
   sage_layer(...)       one whole ISTSAGELayer.forward, fused      (modules.py:218-237)
   gat_layer(...)        one whole MultiHeadGATLayer.forward, fused (modules.py:57-76)
-  matmul, layer_norm_rows, whole_tensor_layer_norm                 (gcn/gcn.py:30-67)
+  matmul, layer_norm_rows, whole_tensor_layer_norm, layer_norm_all (gcn/gcn.py:30-67)
 """
 import torch
 
@@ -63,3 +63,9 @@ def whole_tensor_layer_norm(h):
     """F.layer_norm(h, h.shape) as gcn/gcn.py:65-66 uses it: ONE mean/variance over the whole
     [N, hidden] tensor."""
     return layer_norm_rows(h.reshape(1, -1)).reshape(h.shape)
+
+
+def layer_norm_all(h):
+    """The same function as whole_tensor_layer_norm on the grid-wide kernels (torch.ops.gist.layer_norm_all): every
+    workgroup reduces a slice, instead of one workgroup walking the whole tensor as a single row."""
+    return torch.ops.gist.layer_norm_all(h)[0]

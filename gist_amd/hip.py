@@ -480,6 +480,40 @@ def ln_relu_bwd(d_out, yhat, rstd, dy, use_lynorm, relu):
     return dy
 
 
+def _flat(t, name, n=None):
+    """fp32, contiguous, any shape -> ptr (a whole-tensor kernel walks it as n floats)."""
+    _dev(t, name, torch.float32)
+    if not t.is_contiguous():
+        raise ValueError('gist_amd: %s must be contiguous' % name)
+    if n is not None and t.numel() != n:
+        raise ValueError('gist_amd: %s has %d elements, expected %d' % (name, t.numel(), n))
+    return t.data_ptr()
+
+
+def _ln_all_partials(n, device):
+    need = int(_lib.load().gist_ln_all_partials(n))
+    return workspace(4 * need, device).data_ptr()
+
+
+def ln_all_fwd(x, yhat, stats, eps=LN_EPS):
+    """yhat = (x - mean) * rstd over ALL elements of x (gist_ln_all_fwd_f32); stats <- (mean, rstd)."""
+    L = _lib.load()
+    n = x.numel()
+    _lib.check(L.gist_ln_all_fwd_f32(_flat(x, 'x'), _flat(yhat, 'yhat', n), _vec(stats, 'stats', torch.float32, 2), n,
+                                     eps, _ln_all_partials(n, x.device), _stream()), 'gist_ln_all_fwd_f32')
+    return yhat
+
+
+def ln_all_bwd(g, yhat, stats, dx):
+    """dx = rstd * (g - mean(g) - yhat * mean(g * yhat)) over all elements (gist_ln_all_bwd_f32)."""
+    L = _lib.load()
+    n = yhat.numel()
+    _lib.check(L.gist_ln_all_bwd_f32(_flat(g, 'g', n), _flat(yhat, 'yhat'), _vec(stats, 'stats', torch.float32, 2),
+                                     _flat(dx, 'dx', n), n, _ln_all_partials(n, yhat.device), _stream()),
+               'gist_ln_all_bwd_f32')
+    return dx
+
+
 def dropout_(z, p, seed, offset):
     L = _lib.load()
     zp, ldz = _mat(z, 'z')

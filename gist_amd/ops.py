@@ -18,6 +18,7 @@ are themselves gist ops.  There is NO CPU implementation: a CPU tensor fails in 
   gist::block_scatter_     base[rows, cols] = block  (IST sync)           :126-133
   gist::adam_step_         torch.optim.Adam.step on one tensor            :405-407,417
   gist::matmul, gist::layer_norm_rows   pieces of the GraphConv path      gcn/gcn.py:30-67
+  gist::layer_norm_all     F.layer_norm(h, h.shape) over the grid         gcn/gcn.py:65-66
 
 The reversed CSR travels with every aggregation op (t_rowptr, t_col): the backward of an
 aggregation is the same op on the reversed graph with the two scales swapped.
@@ -437,7 +438,47 @@ def _ln_backward(ctx, g, g_yhat, g_rstd):
 
 layer_norm_rows_fwd.register_autograd(_ln_backward, setup_context=_ln_setup)
 
+
+@torch.library.custom_op('gist::layer_norm_all', mutates_args=(), device_types='cuda')
+def layer_norm_all(x: Tensor) -> Tuple[Tensor, Tensor]:
+    """F.layer_norm(x, x.shape) (gcn/gcn.py:65-66: one mean and variance over the WHOLE tensor, eps 1e-5) on the
+    grid-wide kernels: (yhat, stats = [mean, rstd])."""
+    x = x.contiguous()
+    yhat = torch.empty_like(x)
+    stats = torch.empty(2, dtype=torch.float32, device=x.device)
+    hip.ln_all_fwd(x, yhat, stats)
+    return yhat, stats
+
+
+@layer_norm_all.register_fake
+def _(x):
+    return x.new_empty(x.shape), x.new_empty(2)
+
+
+@torch.library.custom_op('gist::layer_norm_all_bwd', mutates_args=(), device_types='cuda')
+def layer_norm_all_bwd(g: Tensor, yhat: Tensor, stats: Tensor) -> Tensor:
+    dx = torch.empty_like(yhat)
+    hip.ln_all_bwd(g.contiguous(), yhat, stats, dx)
+    return dx
+
+
+@layer_norm_all_bwd.register_fake
+def _(g, yhat, stats):
+    return yhat.new_empty(yhat.shape)
+
+
+def _ln_all_setup(ctx, inputs, output):
+    ctx.save_for_backward(*output)
+
+
+def _ln_all_backward(ctx, g, g_stats):
+    yhat, stats = ctx.saved_tensors
+    return torch.ops.gist.layer_norm_all_bwd(g, yhat, stats)
+
+
+layer_norm_all.register_autograd(_ln_all_backward, setup_context=_ln_all_setup)
+
 OPS = ('spmm_sum', 'sage_layer', 'sage_layer_fwd', 'sage_layer_bwd', 'gat_layer', 'gat_layer_fwd', 'gat_layer_bwd',
        'induced_subgraph',
        'block_gather', 'block_scatter_', 'adam_step_', 'matmul', 'matmul_nt', 'matmul_tn',
-       'layer_norm_rows_fwd', 'layer_norm_rows_bwd')
+       'layer_norm_rows_fwd', 'layer_norm_rows_bwd', 'layer_norm_all', 'layer_norm_all_bwd')

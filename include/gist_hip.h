@@ -429,6 +429,24 @@ int gist_ln_relu_bwd_f32(const float *d_out, int64_t ldg, const float *yhat, int
                          int64_t n_rows, int64_t d, int use_lynorm, int relu,
                          gist_stream_t stream);
 
+/* LayerNorm without affine over a WHOLE tensor of n floats, spread over the chip: one mean and one biased variance
+ * over all elements.  Replaces F.layer_norm(h, h.shape), gcn/gcn.py:65-66 (gist_ln_relu_fwd_f32 on a [1, n] row gives
+ * the same function on one workgroup).
+ *   forward   yhat[i] = (x[i] - mean) * rstd, rstd = 1 / sqrt(var + eps); stats[0] = mean, stats[1] = rstd
+ *   backward  dx[i] = stats[1] * (g[i] - mean(g) - yhat[i] * mean(g * yhat))
+ * Two launches each: every workgroup reduces its slice to a partial (forward: the slice's mean and M2; backward: two
+ * sums), then every workgroup merges the whole partial array in one fixed order (fp64) and rewrites its slice.  No
+ * atomics and no hand-off inside a launch; the grid depends on n alone (gist_ln_all_partials(n) / 4 workgroups, at
+ * most 1024; past that each workgroup loops), so for a given n and base alignment the result is bitwise a function
+ * of the values.  16-byte accesses where the tensors of a call share their alignment (a scalar head and tail around
+ * them), scalar accesses otherwise; every tensor 4-byte aligned.  `partials`: gist_ln_all_partials(n) floats of
+ * scratch (host-only query), 8-byte aligned.  n = 0: OK, nothing is touched.  n < 2^31 * 4. */
+int64_t gist_ln_all_partials(int64_t n);
+int gist_ln_all_fwd_f32(const float *x, float *yhat, float *stats, int64_t n, float eps, float *partials,
+                        gist_stream_t stream);
+int gist_ln_all_bwd_f32(const float *g, const float *yhat, const float *stats, float *dx, int64_t n,
+                        float *partials, gist_stream_t stream);
+
 /* In place inverted dropout on z[n_rows, d]: keep with prob 1-p, scale by
  * 1/(1-p).  The mask is a pure function of (seed, offset + row*d + col) so
  * the backward regenerates it by calling the same function on the gradient.
