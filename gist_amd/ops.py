@@ -32,7 +32,12 @@ from . import hip
 
 
 def _c(t):
-    return t if t.stride(-1) == 1 else t.contiguous()
+    """t itself when its rows are dense (unit inner stride and, past one row, a row stride that covers a row), else a
+    packed copy: autograd hands a backward broadcast gradients -- strides (0, 1) behind `out.sum(0)` -- whose rows
+    alias each other, and the C entries refuse a leading dimension below the width."""
+    if t.stride(-1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        return t.contiguous()
+    return t
 
 
 # -- aggregation ----------------------------------------------------------------------------
