@@ -161,6 +161,10 @@ SIGNATURES = {
     'gist_ln_all_partials': (_i64, [_i64]),
     'gist_ln_all_fwd_f32': (_int, [_p, _p, _p, _i64, _f, _p, _p]),
     'gist_ln_all_bwd_f32': (_int, [_p, _p, _p, _p, _i64, _p, _p]),
+    'gist_ln_affine_fwd_f32': (_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _int, _f, _p]),
+    'gist_ln_affine_bwd_workspace_floats': (_i64, [_i64, _i64]),
+    'gist_ln_affine_bwd_f32': (_int, [_p, _i64, _p, _i64, _p, _p, _p, _int, _p, _i64, _p, _p, _p, _i64, _i64, _p, _i64,
+                                      _p]),
 }
 
 GIST_MAX_LAYERS = 16

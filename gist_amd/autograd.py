@@ -6,6 +6,7 @@ in libgist_hip.so.
   spmm_sum(g, x)        g.update_all(copy_src, sum)                (modules.py:224-225)
   sage_layer(...)       one whole ISTSAGELayer.forward, fused      (modules.py:218-237)
   gat_layer(...)        one whole MultiHeadGATLayer.forward, fused (modules.py:57-76)
+  layer_norm_affine(...) bias + nn.LayerNorm(affine) + relu of a GraphSAGELayer (modules.py:120,144-147)
   matmul, layer_norm_rows, whole_tensor_layer_norm, layer_norm_all (gcn/gcn.py:30-67)
 """
 import torch
@@ -57,6 +58,12 @@ def matmul(x, w):
 def layer_norm_rows(x, relu=False):
     """LayerNorm without affine over the last dim of a 2-D tensor (eps 1e-5), optional relu."""
     return torch.ops.gist.layer_norm_rows_fwd(x, bool(relu))[0]
+
+
+def layer_norm_affine(x, weight, bias, lin_bias=None, relu=False):
+    """nn.LayerNorm(d, elementwise_affine=True) of x + lin_bias (the projection's bias; None: x), optional relu, as one
+    launch in each direction (modules.py:120,144-147)."""
+    return torch.ops.gist.layer_norm_affine_fwd(x, weight, bias, lin_bias, bool(relu))[0]
 
 
 def whole_tensor_layer_norm(h):

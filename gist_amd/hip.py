@@ -514,6 +514,47 @@ def ln_all_bwd(g, yhat, stats, dx):
     return dx
 
 
+def ln_affine_fwd(x, lin_bias, gamma, beta, yhat, out, rstd, relu, eps=LN_EPS):
+    """yhat, rstd, out = the GraphSAGELayer tail of x [n, d] (gist_ln_affine_fwd_f32): LayerNorm of x + lin_bias
+    (None: x), then gamma * yhat + beta, through ReLU when `relu`."""
+    L = _lib.load()
+    xp, ldx = _mat(x, 'x')
+    yp, ldy = _mat(yhat, 'yhat')
+    op, ldo = _mat(out, 'out')
+    n, d = x.shape
+    if tuple(yhat.shape) != (n, d) or tuple(out.shape) != (n, d):
+        raise ValueError('gist_amd: ln_affine_fwd shape mismatch')
+    _lib.check(L.gist_ln_affine_fwd_f32(xp, ldx, _opt(lin_bias, 'lin_bias', torch.float32, d),
+                                        _vec(gamma, 'gamma', torch.float32, d), _vec(beta, 'beta', torch.float32, d),
+                                        yp, ldy, op, ldo, _vec(rstd, 'rstd', torch.float32, n), n, d, int(bool(relu)),
+                                        eps, _stream()), 'gist_ln_affine_fwd_f32')
+    return out
+
+
+def ln_affine_bwd(d_out, yhat, rstd, gamma, beta, relu, dx, dgamma, dbeta, dlin_bias=None, ws=None):
+    """dx and the column sums dgamma, dbeta (and dlin_bias = the column sums of dx, unless None) of ln_affine_fwd
+    (gist_ln_affine_bwd_f32).  ws: float32 scratch of gist_ln_affine_bwd_workspace_floats(n, d) elements (None: taken
+    here)."""
+    L = _lib.load()
+    gp, ldg = _mat(d_out, 'd_out')
+    yp, ldy = _mat(yhat, 'yhat')
+    dp, ldd = _mat(dx, 'dx')
+    n, d = yhat.shape
+    if tuple(d_out.shape) != (n, d) or tuple(dx.shape) != (n, d):
+        raise ValueError('gist_amd: ln_affine_bwd shape mismatch')
+    need = int(L.gist_ln_affine_bwd_workspace_floats(n, d))
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=yhat.device)
+    _lib.check(L.gist_ln_affine_bwd_f32(gp, ldg, yp, ldy, _vec(rstd, 'rstd', torch.float32, n),
+                                        _vec(gamma, 'gamma', torch.float32, d), _vec(beta, 'beta', torch.float32, d),
+                                        int(bool(relu)), dp, ldd, _vec(dgamma, 'dgamma', torch.float32, d),
+                                        _vec(dbeta, 'dbeta', torch.float32, d),
+                                        _opt(dlin_bias, 'dlin_bias', torch.float32, d), n, d,
+                                        _vec(ws, 'ws', torch.float32, need), ws.numel(), _stream()),
+               'gist_ln_affine_bwd_f32')
+    return dx
+
+
 def dropout_(z, p, seed, offset):
     L = _lib.load()
     zp, ldz = _mat(z, 'z')

@@ -7,6 +7,9 @@ and initialise their parameters with the same torch RNG calls in the same order
 unchanged and same-seed weights are identical.  forward() runs entirely on the
 HIP kernels through gist_amd.autograd.sage_layer.
 
+`GraphSAGELayer` and `GraphSAGE` (modules.py:100-189) likewise; their layers run op by op (aggregation, projection,
+and the tail -- bias, LayerNorm with affine, ReLU -- as gist_amd.autograd.layer_norm_affine).
+
 `GATLayer`, `MultiHeadGATLayer` and `GAT` (modules.py:24-98) keep the reference's constructors,
 attributes (`layers[k].heads[h].fc.weight`, `.attn_fc.weight`) and initialisation order; a layer
 runs all its heads as ONE op (gist_amd.autograd.gat_layer).  One deliberate deviation: the heads
@@ -21,7 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import autograd, module_engine
+from . import autograd, hip, module_engine
 from .graph import ClusterBatch
 
 
@@ -68,7 +71,9 @@ class GraphSAGELayer(nn.Module):
     """The reference's GraphSAGELayer (cluster_gcn/modules.py:100-159) -- the layer --use-pp was
     written for: with use_pp=True and in training mode the input already is [h | A^h] (built once
     by ClusterIter.precalc, sampler.py:58-69) and the layer only projects it; otherwise it
-    aggregates like ISTSAGELayer.  LayerNorm here is elementwise_affine=True (modules.py:123)."""
+    aggregates like ISTSAGELayer.  LayerNorm here is elementwise_affine=True (modules.py:120): `lynorm` stays an
+    nn.LayerNorm, and forward() hands its weight and bias, with the projection's bias, to one kernel
+    (autograd.layer_norm_affine)."""
 
     def __init__(self, in_feats, out_feats, activation, dropout, bias=True, use_pp=False,
                  use_lynorm=True):
@@ -93,11 +98,43 @@ class GraphSAGELayer(nn.Module):
         if self.dropout:
             h = self.dropout(h)
         h = autograd.matmul(h, self.linear.weight.t())
+        ln = self.lynorm
+        if (isinstance(ln, nn.LayerNorm) and ln.elementwise_affine and ln.eps == hip.LN_EPS and
+                self.linear.bias is not None and h.is_cuda and h.dtype == torch.float32):
+            # bias add, LayerNorm with affine and (a ReLU) activation: one kernel in each direction
+            fused_relu = bool(self.activation) and _is_relu(self.activation)
+            h = autograd.layer_norm_affine(h, ln.weight, ln.bias, self.linear.bias, fused_relu)
+            if self.activation and not fused_relu:
+                h = self.activation(h)
+            return h
         if self.linear.bias is not None:
             h = h + self.linear.bias
         h = self.lynorm(h)
         if self.activation:
             h = self.activation(h)
+        return h
+
+
+class GraphSAGE(nn.Module):
+    """Layer list of the reference's GraphSAGE (cluster_gcn/modules.py:161-189): an input layer (with use_pp),
+    n_layers - 1 hidden layers, an output layer without norm and activation; same-seed RNG draws as the reference."""
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout, use_pp):
+        super().__init__()
+        self.layers = nn.ModuleList()
+        self.layers.append(GraphSAGELayer(in_feats, n_hidden, activation=activation, dropout=dropout, use_pp=use_pp,
+                                          use_lynorm=True))
+        for i in range(n_layers - 1):
+            self.layers.append(GraphSAGELayer(n_hidden, n_hidden, activation=activation, dropout=dropout,
+                                              use_pp=False, use_lynorm=True))
+        self.layers.append(GraphSAGELayer(n_hidden, n_classes, activation=None, dropout=dropout, use_pp=False,
+                                          use_lynorm=False))
+
+    def forward(self, g):
+        """modules.py:185-189, on a cluster batch and on the full graph alike."""
+        h = g.ndata['feat']
+        for layer in self.layers:
+            h = layer(g, h)
         return h
 
 

@@ -19,6 +19,7 @@ are themselves gist ops.  There is NO CPU implementation: a CPU tensor fails in 
   gist::adam_step_         torch.optim.Adam.step on one tensor            :405-407,417
   gist::matmul, gist::layer_norm_rows   pieces of the GraphConv path      gcn/gcn.py:30-67
   gist::layer_norm_all     F.layer_norm(h, h.shape) over the grid         gcn/gcn.py:65-66
+  gist::layer_norm_affine_fwd/bwd  bias + nn.LayerNorm(affine) + relu of a GraphSAGELayer   modules.py:120,144-147
 
 The reversed CSR travels with every aggregation op (t_rowptr, t_col): the backward of an
 aggregation is the same op on the reversed graph with the two scales swapped.
@@ -483,7 +484,69 @@ def _ln_all_backward(ctx, g, g_stats):
 
 layer_norm_all.register_autograd(_ln_all_backward, setup_context=_ln_all_setup)
 
+# -- the GraphSAGELayer tail (modules.py:120,144-147) ----------------------------------------------
+@torch.library.custom_op('gist::layer_norm_affine_fwd', mutates_args=(), device_types='cuda')
+def layer_norm_affine_fwd(x: Tensor, weight: Tensor, bias: Tensor, lin_bias: Optional[Tensor],
+                          relu: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """LayerNorm(x + lin_bias) * weight + bias over the last dim (eps 1e-5), optional relu, in one launch:
+    (out, yhat, rstd)."""
+    x = _c(x)
+    n, d = x.shape
+    yhat = torch.empty(n, d, dtype=torch.float32, device=x.device)
+    out = torch.empty_like(yhat)
+    rstd = torch.empty(n, dtype=torch.float32, device=x.device)
+    hip.ln_affine_fwd(x, None if lin_bias is None else lin_bias.contiguous(), weight.contiguous(), bias.contiguous(),
+                      yhat, out, rstd, relu)
+    return out, yhat, rstd
+
+
+@layer_norm_affine_fwd.register_fake
+def _(x, weight, bias, lin_bias, relu):
+    return x.new_empty(x.shape), x.new_empty(x.shape), x.new_empty(x.shape[0])
+
+
+@torch.library.custom_op('gist::layer_norm_affine_bwd', mutates_args=(), device_types='cuda')
+def layer_norm_affine_bwd(g: Tensor, yhat: Tensor, rstd: Tensor, weight: Tensor, bias: Tensor, relu: bool,
+                          need_lin_bias: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(dx, dweight, dbias, dlin_bias or empty): the sums of no rows are zeros."""
+    n, d = yhat.shape
+    new = torch.zeros if n == 0 else torch.empty
+    dx = torch.empty_like(yhat)
+    dw, db, dlb = (new(k, dtype=torch.float32, device=yhat.device) for k in (d, d, d if need_lin_bias else 0))
+    hip.ln_affine_bwd(_c(g), yhat, rstd, weight.contiguous(), bias.contiguous(), relu, dx, dw, db,
+                      dlb if need_lin_bias else None)
+    return dx, dw, db, dlb
+
+
+@layer_norm_affine_bwd.register_fake
+def _(g, yhat, rstd, weight, bias, relu, need_lin_bias):
+    d = yhat.shape[1]
+    return yhat.new_empty(yhat.shape), yhat.new_empty(d), yhat.new_empty(d), yhat.new_empty(d if need_lin_bias else 0)
+
+
+def _lna_setup(ctx, inputs, output):
+    x, weight, bias, lin_bias, relu = inputs
+    out, yhat, rstd = output
+    ctx.save_for_backward(yhat, rstd, weight, bias)
+    ctx.relu = relu
+    ctx.lin_bias_shape = None if lin_bias is None else lin_bias.shape
+
+
+def _lna_backward(ctx, g, g_yhat, g_rstd):
+    yhat, rstd, weight, bias = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    if not any(need[:4]):
+        return None, None, None, None, None
+    need_lb = ctx.lin_bias_shape is not None and need[3]
+    dx, dw, db, dlb = torch.ops.gist.layer_norm_affine_bwd(g, yhat, rstd, weight, bias, ctx.relu, need_lb)
+    return (dx if need[0] else None, dw if need[1] else None, db if need[2] else None,
+            dlb.reshape(ctx.lin_bias_shape) if need_lb else None, None)
+
+
+layer_norm_affine_fwd.register_autograd(_lna_backward, setup_context=_lna_setup)
+
 OPS = ('spmm_sum', 'sage_layer', 'sage_layer_fwd', 'sage_layer_bwd', 'gat_layer', 'gat_layer_fwd', 'gat_layer_bwd',
        'induced_subgraph',
        'block_gather', 'block_scatter_', 'adam_step_', 'matmul', 'matmul_nt', 'matmul_tn',
-       'layer_norm_rows_fwd', 'layer_norm_rows_bwd', 'layer_norm_all', 'layer_norm_all_bwd')
+       'layer_norm_rows_fwd', 'layer_norm_rows_bwd', 'layer_norm_all', 'layer_norm_all_bwd',
+       'layer_norm_affine_fwd', 'layer_norm_affine_bwd')

@@ -34,7 +34,7 @@ def build_parser():
     parser.add_argument("--use-pp", action='store_true', help="whether to use precomputation")
     parser.add_argument("--normalize", action='store_true', help="whether to use normalized feature")
     parser.add_argument("--weight-decay", type=float, default=0, help="Weight for L2 loss")
-    parser.add_argument("--model-type", type=str, default='sage', help="sage or gat")
+    parser.add_argument("--model-type", type=str, default='sage', help="sage, gat or graphsage")
     parser.add_argument("--n-heads", type=int, default=4, help="attention heads of the GAT layers")
     # (not a flag of the reference) cat: the hidden GAT layers concatenate their heads (its comment, modules.py:87-89)
     parser.add_argument("--head-merge", choices=['mean', 'cat'], default='mean',
@@ -72,7 +72,7 @@ def main(args, dataset=None, log=print):
     random.seed(args.rnd_seed)
     if args.gpu < 0 or args.eval_cpu:
         raise SystemExit('gist_amd runs on the GPU only (no CPU fallback): --gpu >= 0, no --eval-cpu')
-    if args.model_type not in ('sage', 'gat'):
+    if args.model_type not in ('sage', 'gat', 'graphsage'):
         raise NotImplementedError(f'{args.model_type} is not a supported model type')
     data = dataset if dataset is not None else load_data(args)
     g = data.g
@@ -105,6 +105,10 @@ def main(args, dataset=None, log=print):
     if host_path == 'phases' and args.model_type != 'gat':
         raise SystemExit('gist_amd: --host-path phases binds a GAT to its iterator (--model-type gat); the SAGE module '
                          'path already runs on the phase calls of the fused step: use --host-path module')
+    if args.model_type == 'graphsage':
+        # modules.GraphSAGE (the model --use-pp was written for) has no fused step: the reference's loop on its layers
+        log('--model-type graphsage has no fused step: --host-path %s runs the module loop, layer by layer' % host_path)
+        return main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     if args.model_type == 'gat' and host_path == 'engine' and not args.use_pp:
         return main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     if args.model_type == 'gat' or host_path == 'module':
@@ -177,10 +181,10 @@ def main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, l
 
 
 def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log):
-    """cluster_gcn/cluster_gcn.py:24-136 on the drop-in classes: ClusterIter, GCN (or GAT), CrossEntropyLoss, Adam,
-    evaluate."""
+    """cluster_gcn/cluster_gcn.py:24-136 on the drop-in classes: ClusterIter, GCN (or GAT, or GraphSAGE),
+    CrossEntropyLoss, Adam, evaluate."""
     import time
-    from gist_amd.modules import GAT, GCN
+    from gist_amd.modules import GAT, GCN, GraphSAGE
     from gist_amd.nn import CrossEntropyLoss
     from gist_amd.optim import Adam
     from gist_amd.sampler import ClusterIter
@@ -193,6 +197,9 @@ def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, 
     if args.model_type == 'gat':
         model = GAT(args.n_layers, in_feats, args.n_hidden, n_classes, args.n_heads,   # cluster_gcn_ist_distrib_gat.py:77-79
                     merge=getattr(args, 'head_merge', 'mean'))
+        model.cuda()
+    elif args.model_type == 'graphsage':
+        model = GraphSAGE(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout, args.use_pp)
         model.cuda()
     else:
         model = GCN(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout,

@@ -447,6 +447,32 @@ int gist_ln_all_fwd_f32(const float *x, float *yhat, float *stats, int64_t n, fl
 int gist_ln_all_bwd_f32(const float *g, const float *yhat, const float *stats, float *dx, int64_t n,
                         float *partials, gist_stream_t stream);
 
+/* The tail of a GraphSAGELayer in one launch: for every row
+ *   v = x[r, :] + lin_bias (NULL: none; the projection's bias, added on load);  yhat = (v - mean) * rstd (biased
+ *   variance);  pre = gamma * yhat + beta (one fused multiply-add);  out = relu ? max(pre, 0) : pre
+ * writing yhat, rstd[r] and out; x, yhat and out carry their own leading dimensions and do not overlap.  16-byte
+ * accesses when d, the leading dimensions and every base (the three vectors included) allow, scalar otherwise; a wave
+ * owns a row for d <= 1024, a workgroup above; rows up to 4096 floats are read once, wider ones three times.
+ * n_rows = 0 or d = 0: OK, no launch.  Replaces self.linear's bias add, self.lynorm (nn.LayerNorm with
+ * elementwise_affine=True) and self.activation, modules.py:120,144-147. */
+int gist_ln_affine_fwd_f32(const float *x, int64_t ldx, const float *lin_bias, const float *gamma, const float *beta,
+                           float *yhat, int64_t ldy, float *out, int64_t ldo, float *rstd, int64_t n_rows, int64_t d,
+                           int relu, float eps, gist_stream_t stream);
+/* Its backward from the saved yhat and rstd (autograd of modules.py:120,144-147):
+ *   g' = (pre > 0) ? d_out : 0 when relu (pre recomputed by the forward's own fused multiply-add: the gate agrees
+ *   with the forward's out bit for bit; no gradient at pre = 0), else d_out;  dyh = g' * gamma;
+ *   dx = rstd * (dyh - mean(dyh) - yhat * mean(dyh * yhat));
+ *   dgamma = sum_r g' * yhat,  dbeta = sum_r g',  dlin_bias = sum_r dx (NULL: not formed).
+ * Two launches, no float atomics: a workgroup per 16 rows writes dx and its chunk's column sums into `workspace`
+ * ([3][gist_row_chunks16(n_rows)][d]; gist_ln_affine_bwd_workspace_floats, a host function, gives the size), the second
+ * launch adds the chunks in gist_colsum_chunks_f32's order: the same input gives the same bits.  dx overlaps no input.
+ * n_rows = 0 or d = 0: OK, no launch, nothing written (the sums of no rows are the caller's zeros). */
+int64_t gist_ln_affine_bwd_workspace_floats(int64_t n_rows, int64_t d);
+int gist_ln_affine_bwd_f32(const float *d_out, int64_t ldg, const float *yhat, int64_t ldy, const float *rstd,
+                           const float *gamma, const float *beta, int relu, float *dx, int64_t lddx, float *dgamma,
+                           float *dbeta, float *dlin_bias, int64_t n_rows, int64_t d, float *workspace,
+                           int64_t workspace_floats, gist_stream_t stream);
+
 /* In place inverted dropout on z[n_rows, d]: keep with prob 1-p, scale by
  * 1/(1-p).  The mask is a pure function of (seed, offset + row*d + col) so
  * the backward regenerates it by calling the same function on the gradient.
