@@ -17,6 +17,9 @@ constexpr int kWave = 64;
 void set_error(const char *fmt, ...);
 
 static inline hipStream_t as_stream(gist_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Kernel launches issued by this process through the library (gist_launch_count): a measurement aid -- the launch count
 // of a step, next to the cost of as many EMPTY launches (gist_empty_launches), is the floor of a launch-bound step.
@@ -129,20 +132,58 @@ struct SpmmLnBwd {
     float *col_partials;
     int relu;
 };
-int spmm_drop(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y, int64_t ldy,
-              int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
-              const int32_t *row_blocks, int64_t n_row_blocks, const SpmmDrop &dr, hipStream_t st,
-              const void *prepared = nullptr, bool pairs = true, const SpmmLnBwd *ln = nullptr);
-// gist_spmm_csr_prepared_f32 with the caller's pairs choice
-int spmm_prepared(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y, int64_t ldy,
-                  int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
-                  const int32_t *row_blocks, int64_t n_row_blocks, const void *prepared, hipStream_t st, bool pairs);
-// can a mode-2 call carry SpmmLnBwd, and how many partial rows does it write?
-bool spmm_lnb_takes(int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y, const int32_t *row_blocks,
-                    const void *prepared);
-int64_t spmm_lnb_units(int64_t n_row_blocks);
-bool spmm_drop_takes(int mode, int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y,
-                     const int32_t *row_blocks);
+// gist_spmm_csr_drop_f32's arguments as a SpmmDrop (a mode other than 1 and 2 becomes -1, which spmm_run refuses)
+static inline SpmmDrop spmm_drop_of(int mode, float p, uint64_t seed, uint64_t y_offset, uint64_t src_offset, int64_t ld) {
+    SpmmDrop dr{};
+    dr.mode = (mode == 1 || mode == 2) ? mode : -1; dr.p = p; dr.scale = (p > 0.f && p < 1.f) ? 1.0f / (1.0f - p) : 1.f;
+    dr.sm = seed * 0x9E3779B97F4A7C15ULL; dr.y_base = y_offset; dr.src_base = src_offset; dr.ld = ld;
+    return dr;
+}
+// rows of x and y start on 16-byte boundaries and are whole float4s
+static inline bool spmm_rows16(int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y) {
+    return d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y);
+}
+// blocks of a blocked aggregation: the caller's, or uniform blocks of 128 rows (kL2Rows, MF_ROWS)
+static inline int64_t spmm_block_count(const int32_t *row_blocks, int64_t n_row_blocks, int64_t n_rows) {
+    return row_blocks ? n_row_blocks : ceil_div(n_rows, 128);
+}
+// One aggregation call y (+)= out_scale . A . (src_scale . x), as every function between a C entry point (or the step)
+// and a kernel launch sees it.  Aggregate order: entry .. accumulate are the leading arguments of the C entry points.
+enum SpmmBlocks { SPMM_BLOCKS_NONE, SPMM_BLOCKS_UNIFORM, SPMM_BLOCKS_GIVEN };
+struct SpmmCall {
+    const char *entry;                // the entry point that was called, for error texts
+    const int32_t *rowptr, *col; int64_t n_rows;
+    const float *x; int64_t ldx;
+    float *y; int64_t ldy;
+    int64_t d;
+    const float *out_scale, *src_scale;
+    int accumulate;
+    SpmmBlocks blocks;                // NONE: the plain entry, a drop entry without row_blocks; UNIFORM: the blocked and
+    const int32_t *row_blocks;        // prepared entries without row_blocks; GIVEN: row_blocks[0 .. n_row_blocks]
+    int64_t n_row_blocks;
+    const void *prepared;             // the blocks' prepared structure (gist_spmm_blocks_prepare), or NULL
+    bool need_prepared;               // gist_spmm_csr_prepared_f32: prepared == NULL is a null-pointer error
+    bool pairs;                       // may the batch have sibling blocks (launch_spmm_mfma)
+    SpmmDrop dr;                      // mode 0: none
+    const SpmmLnBwd *ln;              // NULL: none
+    hipStream_t st;
+    void set_blocks(const int32_t *rb, int64_t nb, SpmmBlocks without) {
+        blocks = rb ? SPMM_BLOCKS_GIVEN : without; row_blocks = rb; n_row_blocks = nb;
+    }
+    bool rows16() const { return spmm_rows16(d, ldx, ldy, x, y); }
+    int64_t n_blocks() const { return spmm_block_count(row_blocks, n_row_blocks, n_rows); }
+};
+// Which kernel family runs a call (spmm.hip: the decision table is above spmm_choose), and the one path from a record
+// to a launch: validate, choose, launch.
+enum SpmmKernel { SPMM_ROWS, SPMM_LDS2, SPMM_MFMA, SPMM_DENSE32 };      // ROWS: the lane-group / row-split kernels
+struct SpmmChoice {
+    SpmmKernel kernel;
+    bool reads_prepared;
+    const char *refusal;              // not NULL: the call is refused (GIST_EINVAL) with this text
+};
+SpmmChoice spmm_choose(const SpmmCall &c);
+int spmm_run(const SpmmCall &c);
+int64_t spmm_lnb_units(int64_t n_row_blocks);      // partial rows a call with SpmmLnBwd writes
 #ifdef __HIPCC__
 // Sum over the 64 lanes of a wave, the same bits in every lane.  Within a row of 16 lanes on the DPP path of the vector unit
 // (lane ^ 1, lane ^ 2 as quad permutes; the other quad of the half row and the other half row as mirrors -- every lane of a
@@ -194,17 +235,11 @@ __device__ __forceinline__ void drop_f4(float4 &v, uint64_t idx0, const SpmmDrop
 // (prepared = NULL: every workgroup builds its block's counts itself).  pairs: may the batch have sibling blocks?  false
 // (gist_sage_step with plan->sibling_parts == 0): the prepare kernel looks for none and no pairs launch follows an
 // aggregation; a structure prepared either way is read correctly either way (spmm_prep.h), the choice is speed only.
-int launch_spmm_mfma(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y,
-                     int64_t ldy, int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale,
-                     int accumulate, const int32_t *row_blocks, int64_t n_row_blocks, const void *prepared,
-                     hipStream_t st, const SpmmDrop *dr = nullptr, bool pairs = true);
+int launch_spmm_mfma(const SpmmCall &c, const void *prepared);
 int64_t spmm_blocks_bytes(int64_t n_blocks);
 // spmm_dense32.hip: the block-dense aggregation on the fp32 matrix cores, operands from memory (prepared blocks only)
 bool spmm_dense32_takes(int64_t d, int64_t ldx, int64_t ldy);
-int launch_spmm_dense32(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y,
-                        int64_t ldy, int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale,
-                        int accumulate, const int32_t *row_blocks, int64_t n_row_blocks, const void *prepared,
-                        hipStream_t st, const SpmmDrop *dr = nullptr);
+int launch_spmm_dense32(const SpmmCall &c);
 bool spmm_prepared_takes(int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y);   // spmm.hip
 int launch_spmm_blocks_prepare(const int32_t *rowptr, const int32_t *col, const int32_t *rowptr2,
                                const int32_t *col2, int64_t n_rows, const int32_t *row_blocks,
@@ -260,9 +295,5 @@ struct DeviceOnce {
 // XCDs of the device the library runs on (gfx950: 8); blockIdx -> tile maps deal work round-robin
 // to XCDs the way the hardware dispatches consecutive workgroups.
 constexpr int kXcds = 8;
-
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace gist

@@ -693,53 +693,43 @@ __global__ void in_degree_norm_kernel(const int32_t *__restrict__ rowptr, int64_
 }
 
 template <int VEC, bool HALF = false>
-static int launch_spmm(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx,
-                       float *y, int64_t ldy, int64_t n_rows, int64_t d, const float *out_scale,
-                       const float *src_scale, int accumulate, hipStream_t st,
-                       const SpmmDrop *drop = nullptr) {
-    const bool dropping = drop != nullptr && drop->mode == 1 && drop->p > 0.f;
-    SpmmDrop dr{};
-    if (dropping) dr = *drop;
-    const int lanes = (int)ceil_div(d, VEC);
+static int launch_spmm(const SpmmCall &c) {
+    const bool dropping = c.dr.mode == 1 && c.dr.p > 0.f;
+    const SpmmDrop dr = dropping ? c.dr : SpmmDrop{};
+    const int lanes = (int)ceil_div(c.d, VEC);
     int lpr = 8;
     while (lpr < 64 && lpr < lanes) lpr <<= 1;
     const int n_col_tiles = (int)ceil_div(lanes, lpr);
-    const int n_row_blocks = (int)ceil_div(n_rows, kSpmmWavesPerBlock);
+    const int n_row_blocks = (int)ceil_div(c.n_rows, kSpmmWavesPerBlock);
     const int xcd_tiles = n_col_tiles >= 8 ? 1 : 0;
     if (lpr == 64) {   // wide rows: one workgroup per (row, column tile), waves share the row
         const int chunk_rows = tune(GIST_TUNE_SPMM_CHUNK) > 0.0 ? (int)tune(GIST_TUNE_SPMM_CHUNK) : 128;
-        const int64_t n_chunks = ceil_div(n_rows, chunk_rows);
+        const int64_t n_chunks = ceil_div(c.n_rows, chunk_rows);
         const int64_t g2 = kXcds * ceil_div(n_chunks, kXcds) * chunk_rows * n_col_tiles;
-        if (g2 > 0x7fffffffLL) {
-            set_error("gist_spmm_csr_f32: grid too large");
-            return GIST_EINVAL;
-        }
+        GIST_REQUIRE(g2 <= 0x7fffffffLL, "%s: grid too large", c.entry);
         if (dropping)
             hipLaunchKernelGGL((spmm_csr_rowsplit_kernel<VEC, HALF, true>), dim3((unsigned)g2), dim3(256), 0,
-                               st, rowptr, col, x, ldx, y, ldy, (int)n_rows, (int)d, out_scale,
-                               src_scale, accumulate, n_col_tiles, chunk_rows, dr);
+                               c.st, c.rowptr, c.col, c.x, c.ldx, c.y, c.ldy, (int)c.n_rows, (int)c.d, c.out_scale,
+                               c.src_scale, c.accumulate, n_col_tiles, chunk_rows, dr);
         else
             hipLaunchKernelGGL((spmm_csr_rowsplit_kernel<VEC, HALF, false>), dim3((unsigned)g2), dim3(256), 0,
-                               st, rowptr, col, x, ldx, y, ldy, (int)n_rows, (int)d, out_scale,
-                               src_scale, accumulate, n_col_tiles, chunk_rows, dr);
-        return launch_status("gist_spmm_csr_f32");
+                               c.st, c.rowptr, c.col, c.x, c.ldx, c.y, c.ldy, (int)c.n_rows, (int)c.d, c.out_scale,
+                               c.src_scale, c.accumulate, n_col_tiles, chunk_rows, dr);
+        return launch_status(c.entry);
     }
     const int64_t grid = xcd_tiles ? (int64_t)kXcds * ceil_div(n_col_tiles, kXcds) * n_row_blocks
                                    : (int64_t)n_row_blocks * n_col_tiles;
-    if (grid > 0x7fffffffLL) {
-        set_error("gist_spmm_csr_f32: grid too large");
-        return GIST_EINVAL;
-    }
+    GIST_REQUIRE(grid <= 0x7fffffffLL, "%s: grid too large", c.entry);
 #define GIST_SPMM_LAUNCH(L)                                                                       \
     do {                                                                                          \
         if (dropping)                                                                             \
-            hipLaunchKernelGGL((spmm_csr_kernel<VEC, L, true>), dim3((unsigned)grid), dim3(256), 0, st, \
-                               rowptr, col, x, ldx, y, ldy, (int)n_rows, (int)d, out_scale,       \
-                               src_scale, accumulate, n_row_blocks, n_col_tiles, xcd_tiles, dr);  \
+            hipLaunchKernelGGL((spmm_csr_kernel<VEC, L, true>), dim3((unsigned)grid), dim3(256), 0, c.st, \
+                               c.rowptr, c.col, c.x, c.ldx, c.y, c.ldy, (int)c.n_rows, (int)c.d, c.out_scale, \
+                               c.src_scale, c.accumulate, n_row_blocks, n_col_tiles, xcd_tiles, dr);  \
         else                                                                                      \
-            hipLaunchKernelGGL((spmm_csr_kernel<VEC, L, false>), dim3((unsigned)grid), dim3(256), 0, st, \
-                               rowptr, col, x, ldx, y, ldy, (int)n_rows, (int)d, out_scale,       \
-                               src_scale, accumulate, n_row_blocks, n_col_tiles, xcd_tiles, dr);  \
+            hipLaunchKernelGGL((spmm_csr_kernel<VEC, L, false>), dim3((unsigned)grid), dim3(256), 0, c.st, \
+                               c.rowptr, c.col, c.x, c.ldx, c.y, c.ldy, (int)c.n_rows, (int)c.d, c.out_scale, \
+                               c.src_scale, c.accumulate, n_row_blocks, n_col_tiles, xcd_tiles, dr);  \
     } while (0)
     switch (lpr) {
         case 8: GIST_SPMM_LAUNCH(8); break;
@@ -748,7 +738,7 @@ static int launch_spmm(const int32_t *rowptr, const int32_t *col, const float *x
         default: GIST_SPMM_LAUNCH(64); break;
     }
 #undef GIST_SPMM_LAUNCH
-    return launch_status("gist_spmm_csr_f32");
+    return launch_status(c.entry);
 }
 
 // Row split R of the second LDS design: units = blocks x column tiles x R on 256 CUs, one unit
@@ -772,26 +762,24 @@ static int l2_split_for(int64_t nb, int n_col_tiles) {
     return r < 1 ? 1 : (r > 64 ? 64 : r);
 }
 
-static int launch_spmm_lds2(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx,
-                            float *y, int64_t ldy, int64_t n_rows, int64_t d, const float *out_scale,
-                            const float *src_scale, int accumulate, const int32_t *row_blocks,
-                            int64_t n_row_blocks, hipStream_t st, const SpmmDrop *drop = nullptr,
-                            const SpmmLnBwd *ln = nullptr) {
+static_assert(kL2Rows == 128, "spmm_block_count's uniform blocks");
+// (a call with the rider is mode 2, d <= 256 -- one column tile -- on given blocks: spmm_choose)
+static int launch_spmm_lds2(const SpmmCall &c) {
     L2Args a;
     a.dr = SpmmDrop{};
-    a.ln = ln ? *ln : SpmmLnBwd{};
-    const int dmode = (drop != nullptr && drop->p > 0.f) ? drop->mode : 0;
-    if (dmode) a.dr = *drop;
-    a.rowptr = rowptr; a.col = col; a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy;
-    a.n_rows = (int)n_rows; a.d = (int)d; a.out_scale = out_scale; a.src_scale = src_scale;
-    a.accumulate = accumulate; a.row_blocks = row_blocks;
-    const int64_t nb = row_blocks ? n_row_blocks : ceil_div(n_rows, kL2Rows);
+    a.ln = c.ln ? *c.ln : SpmmLnBwd{};
+    const int dmode = c.dr.p > 0.f ? c.dr.mode : 0;
+    if (dmode) a.dr = c.dr;
+    a.rowptr = c.rowptr; a.col = c.col; a.x = c.x; a.ldx = c.ldx; a.y = c.y; a.ldy = c.ldy;
+    a.n_rows = (int)c.n_rows; a.d = (int)c.d; a.out_scale = c.out_scale; a.src_scale = c.src_scale;
+    a.accumulate = c.accumulate; a.row_blocks = c.row_blocks;
+    const int64_t nb = c.n_blocks();
     a.n_blocks = (int)nb;
-    a.n_col_tiles = (int)ceil_div(d, 256);
+    a.n_col_tiles = (int)ceil_div(c.d, 256);
     a.row_split = l2_split_for(nb, a.n_col_tiles);
     const int64_t total = nb * a.n_col_tiles * a.row_split;
     const int64_t grid = kXcds * ceil_div(total, kXcds);
-    if (grid > 0x7fffffffLL) { set_error("gist_spmm_csr_blocked_f32: grid too large"); return GIST_EINVAL; }
+    GIST_REQUIRE(grid <= 0x7fffffffLL, "%s: grid too large", c.entry);
     static DeviceOnce once;
     int dev;
     if (once.needed(&dev)) {
@@ -803,24 +791,20 @@ static int launch_spmm_lds2(const int32_t *rowptr, const int32_t *col, const flo
             if (e == hipSuccess)
                 e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kL2LdsBytes);
         if (e != hipSuccess) {
-            set_error("gist_spmm_csr_blocked_f32: hipFuncSetAttribute: %s", hipGetErrorString(e));
+            set_error("%s: hipFuncSetAttribute: %s", c.entry, hipGetErrorString(e));
             return GIST_ELAUNCH;
         }
         once.done(dev);
     }
-    if (ln != nullptr) {
-        if (dmode != 2 || a.n_col_tiles != 1 || row_blocks == nullptr) {
-            set_error("gist_spmm_csr_drop_f32: the LayerNorm-backward store needs mode 2, d <= 256 and row blocks");
-            return GIST_EINVAL;
-        }
-        hipLaunchKernelGGL((spmm_csr_lds2_kernel<2, true>), dim3((unsigned)grid), dim3(kL2Threads), kL2LdsBytes, st, a);
-    } else if (dmode == 1)
-        hipLaunchKernelGGL(spmm_csr_lds2_kernel<1>, dim3((unsigned)grid), dim3(kL2Threads), kL2LdsBytes, st, a);
+    if (c.ln != nullptr)
+        hipLaunchKernelGGL((spmm_csr_lds2_kernel<2, true>), dim3((unsigned)grid), dim3(kL2Threads), kL2LdsBytes, c.st, a);
+    else if (dmode == 1)
+        hipLaunchKernelGGL(spmm_csr_lds2_kernel<1>, dim3((unsigned)grid), dim3(kL2Threads), kL2LdsBytes, c.st, a);
     else if (dmode == 2)
-        hipLaunchKernelGGL(spmm_csr_lds2_kernel<2>, dim3((unsigned)grid), dim3(kL2Threads), kL2LdsBytes, st, a);
+        hipLaunchKernelGGL(spmm_csr_lds2_kernel<2>, dim3((unsigned)grid), dim3(kL2Threads), kL2LdsBytes, c.st, a);
     else
-        hipLaunchKernelGGL(spmm_csr_lds2_kernel<0>, dim3((unsigned)grid), dim3(kL2Threads), kL2LdsBytes, st, a);
-    return launch_status("gist_spmm_csr_blocked_f32");
+        hipLaunchKernelGGL(spmm_csr_lds2_kernel<0>, dim3((unsigned)grid), dim3(kL2Threads), kL2LdsBytes, c.st, a);
+    return launch_status(c.entry);
 }
 
 // Calls the prepared matrix-core kernel takes (everything else: gist_spmm_csr_blocked_f32's choice).
@@ -828,8 +812,7 @@ static int launch_spmm_lds2(const int32_t *rowptr, const int32_t *col, const flo
 // every workgroup builds its own, 57 on the LDS gather kernel), 2048 21 (29, 33), 1024 13.5 (21.5, 16),
 // 512 13.4 (20, 12); the preparation is one 13 us launch per batch, so it pays from D = 2048 on.
 bool spmm_prepared_takes(int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y) {
-    return d >= 1536 && d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y) &&
-           (int)tune(GIST_TUNE_SPMM_KERNEL) != 1;
+    return d >= 1536 && spmm_rows16(d, ldx, ldy, x, y) && (int)tune(GIST_TUNE_SPMM_KERNEL) != 1;
 }
 
 }  // namespace gist
@@ -845,83 +828,107 @@ extern "C" int gist_in_degree_norm_f32(const int32_t *rowptr, int64_t n_rows, fl
 }
 
 namespace gist {
-static int spmm_generic(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y,
-                        int64_t ldy, int64_t n_rows, int64_t d, const float *out_scale,
-                        const float *src_scale, int accumulate, hipStream_t st, const SpmmDrop *drop) {
-    if (d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y))
-        return launch_spmm<4>(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                              accumulate, st, drop);
+// the lane-group / row-split kernels: the widest vector the rows allow
+static int spmm_generic(const SpmmCall &c) {
+    if (c.rows16()) return launch_spmm<4>(c);
     // d = 4q + 2 wide enough for the workgroup-per-row kernel, 16-byte source rows with room
     // for the last lane's over-read, 8-byte destination: gather 16 bytes per lane anyway
-    if (d % 4 == 2 && d >= 4 * kWave && ldx % 4 == 0 && ldx >= d + 2 && aligned16(x) && ldy % 2 == 0 &&
-        aligned8(y))
-        return launch_spmm<4, true>(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                                    accumulate, st, drop);
-    if (d % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && aligned8(x) && aligned8(y))
-        return launch_spmm<2>(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                              accumulate, st, drop);
-    return launch_spmm<1>(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                          accumulate, st, drop);
+    if (c.d % 4 == 2 && c.d >= 4 * kWave && c.ldx % 4 == 0 && c.ldx >= c.d + 2 && aligned16(c.x) && c.ldy % 2 == 0 &&
+        aligned8(c.y))
+        return launch_spmm<4, true>(c);
+    if (c.d % 2 == 0 && c.ldx % 2 == 0 && c.ldy % 2 == 0 && aligned8(c.x) && aligned8(c.y)) return launch_spmm<2>(c);
+    return launch_spmm<1>(c);
 }
 
-static bool lds2_takes(int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y) {
-    return d >= 128 && d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y);
+// Which kernel runs a call.  Pure host code: no HIP call, no allocation, no state beyond the tuning hooks.
+//   W     rows are 16-byte (c.rows16());  L = W and d >= 128
+//   knob  GIST_TUNE_SPMM_KERNEL (0 none, 1 the LDS gather kernel, 2 the matrix-core kernel, 3 dense32 at every width)
+//   P     prepared given and 16-byte aligned;  D32 = P and spmm_dense32_takes(d, ldx, ldy)
+//   M     blocks GIVEN, L, knob != 1, and (d >= 1536 or knob == 2)
+// Plain entry (mode 0, blocks NONE):
+//   always                                                     rows (the lane-group or row-split kernel by VEC / HALF /
+//                                                              LPR: spmm_generic, launch_spmm)
+// Blocked entry (mode 0, no prepared, blocks UNIFORM or GIVEN):
+//   not L                                                      rows
+//   knob == 2, or knob != 1 and d >= 1536 and blocks GIVEN     mfma, unprepared
+//   otherwise                                                  lds2, on the given or the uniform blocks
+// Prepared entry (mode 0, prepared given, blocks UNIFORM or GIVEN):
+//   D32                                                        dense32
+//   P and spmm_prepared_takes (d >= 1536, W, knob != 1)        mfma, prepared, also on uniform blocks
+//   otherwise                                                  the blocked entry's row, not reading prepared
+// Drop entries (mode 1 or 2, blocks NONE or GIVEN, prepared optional):
+//   mode 2 unless blocks GIVEN and L and not M                 refused (backward: only the LDS-staged kernel carries the
+//       mask -- it reads every source element of a block once; the row kernels would hash every gathered element, and on
+//       the matrix-core kernel the hashes in the tile conversion cost more than the pass: spmm_mfma.hip)
+//   with the rider (SpmmLnBwd)                                 lds2<2, true>; refused unless mode 2, p > 0, d <= 256,
+//                                                              not D32, rider pointers given and 16-byte
+//   D32                                                        dense32
+//   M                                                          mfma, reading prepared if one is given
+//   blocks GIVEN and L                                         lds2
+//   otherwise                                                  rows
+// Corners, kept as they were found:
+//   (a) knob 2 forces mfma on the blocked entry's uniform blocks, but not on the drop entries (M wants GIVEN)
+//   (b) without row blocks the blocked entry runs lds2 on uniform blocks, the drop entries the row kernels
+//   (c) the prepared entry on uniform blocks at d >= 1536 runs mfma; the blocked entry runs lds2 for the same call
+//   (d) the prepared entry under knob 2 at d < 1536 runs mfma WITHOUT reading prepared; the drop entries read it
+//   (e) the drop entries hand mfma a prepared structure that is not 16-byte aligned (row M does not ask P); the
+//       prepared entry does not read such a structure
+//   (f) a mask with p == 0: the row kernels and lds2 run their unmasked instantiation, mfma and dense32 the masked
+//       one (every element kept, scale 1: the same values)
+SpmmChoice spmm_choose(const SpmmCall &c) {
+    const int knob = (int)tune(GIST_TUNE_SPMM_KERNEL);
+    const bool given = c.blocks == SPMM_BLOCKS_GIVEN;
+    const bool L = c.rows16() && c.d >= 128;
+    const bool P = c.prepared != nullptr && aligned16(c.prepared);
+    const bool D32 = P && spmm_dense32_takes(c.d, c.ldx, c.ldy);
+    const bool M = given && L && knob != 1 && (c.d >= 1536 || knob == 2);
+    if (c.dr.mode != 0) {
+        if (c.dr.mode == 2 && !(given && L && !M))
+            return {SPMM_ROWS, false, "this shape cannot carry the mask (use gist_dropout_f32)"};
+        if (c.ln != nullptr) {
+            const SpmmLnBwd &ln = *c.ln;
+            const bool ok = c.dr.mode == 2 && c.dr.p > 0.f && c.d <= 256 && !D32 && ln.yhat && ln.dy && ln.col_partials &&
+                            ln.ldy >= c.d && ln.lddy >= c.d && ln.ldy % 4 == 0 && ln.lddy % 4 == 0 && aligned16(ln.yhat) &&
+                            aligned16(ln.dy) && aligned16(ln.col_partials);
+            return {SPMM_LDS2, false, ok ? nullptr : "this call cannot carry the LayerNorm backward"};
+        }
+        if (D32) return {SPMM_DENSE32, true, nullptr};
+        if (M) return {SPMM_MFMA, c.prepared != nullptr, nullptr};
+        return {given && L ? SPMM_LDS2 : SPMM_ROWS, false, nullptr};
+    }
+    if (c.blocks == SPMM_BLOCKS_NONE) return {SPMM_ROWS, false, nullptr};
+    if (D32) return {SPMM_DENSE32, true, nullptr};
+    if (P && spmm_prepared_takes(c.d, c.ldx, c.ldy, c.x, c.y)) return {SPMM_MFMA, true, nullptr};
+    if (!L) return {SPMM_ROWS, false, nullptr};      // narrow rows keep every lane busy only in the lane-group kernel
+    // wide rows: the block-dense matrix-core kernel (spmm_mfma.hip), whose per-workgroup set-up
+    // (the block's counts, ~11 us) pays from two 128-column tiles per workgroup on -- measured on
+    // the Reddit-like batch: D = 4096 38 vs 57 us, 2048 29 vs 33, 1024 21 vs 16, 512 20 vs 12.
+    // (uniform 128-row blocks cut across the parts: too many neighbours fall outside a block for
+    // the dense product, the gather kernel degrades more gracefully there)
+    if (knob == 2 || (knob != 1 && c.d >= 1536 && given)) return {SPMM_MFMA, false, nullptr};
+    return {SPMM_LDS2, false, nullptr};
 }
 
-// Which calls can carry the dropout mask themselves: forward (mode 1) every kernel; backward (mode 2) the
-// LDS-staged kernel only (it reads every source element of a block once; the row-split kernels would hash every
-// gathered element, and on the matrix-core kernel the hashes in the tile conversion cost more than the pass:
-// spmm_mfma.hip).
-static bool mfma_takes(int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y,
-                       const int32_t *row_blocks) {
-    const int forced = (int)tune(GIST_TUNE_SPMM_KERNEL);
-    return row_blocks != nullptr && lds2_takes(d, ldx, ldy, x, y) && forced != 1 && (d >= 1536 || forced == 2);
-}
-bool spmm_drop_takes(int mode, int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y,
-                     const int32_t *row_blocks) {
-    if (mode == 1) return true;
-    if (mode == 2) return row_blocks != nullptr && lds2_takes(d, ldx, ldy, x, y) && !mfma_takes(d, ldx, ldy, x, y, row_blocks);
-    return false;
-}
-
-bool spmm_lnb_takes(int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y, const int32_t *row_blocks,
-                    const void *prepared) {
-    if (d > 256 || !spmm_drop_takes(2, d, ldx, ldy, x, y, row_blocks)) return false;
-    return !(prepared != nullptr && aligned16(prepared) && spmm_dense32_takes(d, ldx, ldy));
-}
 int64_t spmm_lnb_units(int64_t n_row_blocks) { return n_row_blocks * l2_split_for(n_row_blocks, 1); }
 
-int spmm_drop(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y, int64_t ldy,
-              int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
-              const int32_t *row_blocks, int64_t n_row_blocks, const SpmmDrop &dr, hipStream_t st,
-              const void *prepared, bool pairs, const SpmmLnBwd *ln) {
-    GIST_REQUIRE(n_rows >= 0 && d >= 0, "gist_spmm_csr_drop_f32: negative size");
-    if (n_rows == 0 || d == 0) return GIST_OK;
-    GIST_REQUIRE(rowptr && x && y, "gist_spmm_csr_drop_f32: null pointer");
-    GIST_REQUIRE(ldx >= d && ldy >= d, "gist_spmm_csr_drop_f32: leading dimension < d");
-    GIST_REQUIRE(n_rows < (1LL << 31) && d < (1LL << 31), "gist_spmm_csr_drop_f32: size >= 2^31");
-    GIST_REQUIRE(dr.mode == 1 || dr.mode == 2, "gist_spmm_csr_drop_f32: mode must be 1 or 2");
-    GIST_REQUIRE(dr.p >= 0.f && dr.p < 1.f && dr.ld >= d, "gist_spmm_csr_drop_f32: bad mask description");
-    GIST_REQUIRE(spmm_drop_takes(dr.mode, d, ldx, ldy, x, y, row_blocks),
-                 "gist_spmm_csr_drop_f32: this shape cannot carry the mask (use gist_dropout_f32)");
-    if (ln != nullptr) {
-        GIST_REQUIRE(dr.mode == 2 && dr.p > 0.f && spmm_lnb_takes(d, ldx, ldy, x, y, row_blocks, prepared) && ln->yhat &&
-                         ln->dy && ln->col_partials && ln->ldy >= d && ln->lddy >= d && ln->ldy % 4 == 0 &&
-                         ln->lddy % 4 == 0 && aligned16(ln->yhat) && aligned16(ln->dy) && aligned16(ln->col_partials),
-                     "gist_spmm_csr_drop_f32: this call cannot carry the LayerNorm backward");
-        return launch_spmm_lds2(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate, row_blocks,
-                                n_row_blocks, st, &dr, ln);
+// Every aggregation call: validate, choose, launch.
+int spmm_run(const SpmmCall &c) {
+    GIST_REQUIRE(c.n_rows >= 0 && c.d >= 0, "%s: negative size", c.entry);
+    if (c.n_rows == 0 || c.d == 0) return GIST_OK;
+    GIST_REQUIRE(c.rowptr && c.x && c.y && (c.prepared || !c.need_prepared), "%s: null pointer", c.entry);
+    GIST_REQUIRE(c.ldx >= c.d && c.ldy >= c.d, "%s: leading dimension < d", c.entry);
+    GIST_REQUIRE(c.n_rows < (1LL << 31) && c.d < (1LL << 31), "%s: size >= 2^31", c.entry);
+    GIST_REQUIRE(c.blocks != SPMM_BLOCKS_GIVEN || c.n_row_blocks > 0, "%s: row_blocks given but n_row_blocks <= 0", c.entry);
+    GIST_REQUIRE(c.dr.mode >= 0, "%s: mode must be 1 or 2", c.entry);
+    GIST_REQUIRE(c.dr.mode == 0 || (c.dr.p >= 0.f && c.dr.p < 1.f && c.dr.ld >= c.d), "%s: bad mask description", c.entry);
+    const SpmmChoice ch = spmm_choose(c);
+    GIST_REQUIRE(ch.refusal == nullptr, "%s: %s", c.entry, ch.refusal);
+    switch (ch.kernel) {
+        case SPMM_LDS2: return launch_spmm_lds2(c);
+        case SPMM_MFMA: return launch_spmm_mfma(c, ch.reads_prepared ? c.prepared : nullptr);
+        case SPMM_DENSE32: return launch_spmm_dense32(c);
+        default: return spmm_generic(c);
     }
-    if (prepared != nullptr && aligned16(prepared) && spmm_dense32_takes(d, ldx, ldy))
-        return launch_spmm_dense32(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
-                                   row_blocks, n_row_blocks, prepared, st, &dr);
-    if (mfma_takes(d, ldx, ldy, x, y, row_blocks))
-        return launch_spmm_mfma(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
-                                row_blocks, n_row_blocks, prepared, st, &dr, pairs);
-    if (row_blocks != nullptr && lds2_takes(d, ldx, ldy, x, y))
-        return launch_spmm_lds2(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
-                                row_blocks, n_row_blocks, st, &dr);
-    return spmm_generic(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate, st, &dr);
 }
 }  // namespace gist
 
@@ -929,14 +936,32 @@ extern "C" int gist_spmm_csr_f32(const int32_t *rowptr, const int32_t *col, cons
                                  int64_t ldx, float *y, int64_t ldy, int64_t n_rows, int64_t d,
                                  const float *out_scale, const float *src_scale, int accumulate,
                                  gist_stream_t stream) {
-    using namespace gist;
-    GIST_REQUIRE(n_rows >= 0 && d >= 0, "gist_spmm_csr_f32: negative size");
-    if (n_rows == 0 || d == 0) return GIST_OK;
-    GIST_REQUIRE(rowptr && x && y, "gist_spmm_csr_f32: null pointer");
-    GIST_REQUIRE(ldx >= d && ldy >= d, "gist_spmm_csr_f32: leading dimension < d");
-    GIST_REQUIRE(n_rows < (1LL << 31) && d < (1LL << 31), "gist_spmm_csr_f32: size >= 2^31");
-    return spmm_generic(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
-                        as_stream(stream), nullptr);
+    gist::SpmmCall c{"gist_spmm_csr_f32", rowptr, col, n_rows, x, ldx, y, ldy, d, out_scale, src_scale, accumulate};
+    c.st = gist::as_stream(stream);
+    return gist::spmm_run(c);
+}
+
+extern "C" int gist_spmm_csr_blocked_f32(const int32_t *rowptr, const int32_t *col, const float *x,
+                                         int64_t ldx, float *y, int64_t ldy, int64_t n_rows,
+                                         int64_t d, const float *out_scale,
+                                         const float *src_scale, int accumulate,
+                                         const int32_t *row_blocks, int64_t n_row_blocks,
+                                         gist_stream_t stream) {
+    gist::SpmmCall c{"gist_spmm_csr_blocked_f32", rowptr, col, n_rows, x, ldx, y, ldy, d, out_scale, src_scale, accumulate};
+    c.set_blocks(row_blocks, n_row_blocks, gist::SPMM_BLOCKS_UNIFORM);
+    c.st = gist::as_stream(stream);
+    return gist::spmm_run(c);
+}
+
+extern "C" int gist_spmm_csr_prepared_f32(const int32_t *rowptr, const int32_t *col, const float *x,
+                                          int64_t ldx, float *y, int64_t ldy, int64_t n_rows, int64_t d,
+                                          const float *out_scale, const float *src_scale, int accumulate,
+                                          const int32_t *row_blocks, int64_t n_row_blocks,
+                                          const void *prepared, gist_stream_t stream) {
+    gist::SpmmCall c{"gist_spmm_csr_prepared_f32", rowptr, col, n_rows, x, ldx, y, ldy, d, out_scale, src_scale, accumulate};
+    c.set_blocks(row_blocks, n_row_blocks, gist::SPMM_BLOCKS_UNIFORM);
+    c.prepared = prepared; c.need_prepared = true; c.pairs = true; c.st = gist::as_stream(stream);
+    return gist::spmm_run(c);
 }
 
 /* Aggregation with gist_dropout_f32's mask folded in (see SpmmDrop); row_blocks = NULL: no locality blocks. */
@@ -945,11 +970,24 @@ extern "C" int gist_spmm_csr_drop_f32(const int32_t *rowptr, const int32_t *col,
                                       const float *src_scale, int accumulate, const int32_t *row_blocks,
                                       int64_t n_row_blocks, int mode, float p, uint64_t seed, uint64_t y_offset,
                                       uint64_t src_offset, int64_t mask_ld, gist_stream_t stream) {
-    gist::SpmmDrop dr{};
-    dr.mode = mode; dr.p = p; dr.scale = (p > 0.f && p < 1.f) ? 1.0f / (1.0f - p) : 1.f;
-    dr.sm = seed * 0x9E3779B97F4A7C15ULL; dr.y_base = y_offset; dr.src_base = src_offset; dr.ld = mask_ld;
-    return gist::spmm_drop(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate, row_blocks,
-                           n_row_blocks, dr, gist::as_stream(stream));
+    gist::SpmmCall c{"gist_spmm_csr_drop_f32", rowptr, col, n_rows, x, ldx, y, ldy, d, out_scale, src_scale, accumulate};
+    c.set_blocks(row_blocks, n_row_blocks, gist::SPMM_BLOCKS_NONE);
+    c.dr = gist::spmm_drop_of(mode, p, seed, y_offset, src_offset, mask_ld);
+    c.st = gist::as_stream(stream);
+    return gist::spmm_run(c);
+}
+
+extern "C" int gist_spmm_csr_drop_prepared_f32(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx,
+                                               float *y, int64_t ldy, int64_t n_rows, int64_t d,
+                                               const float *out_scale, const float *src_scale, int accumulate,
+                                               const int32_t *row_blocks, int64_t n_row_blocks, int mode, float p,
+                                               uint64_t seed, uint64_t y_offset, uint64_t src_offset,
+                                               int64_t mask_ld, const void *prepared, gist_stream_t stream) {
+    gist::SpmmCall c{"gist_spmm_csr_drop_prepared_f32", rowptr, col, n_rows, x, ldx, y, ldy, d, out_scale, src_scale, accumulate};
+    c.set_blocks(row_blocks, n_row_blocks, gist::SPMM_BLOCKS_NONE);
+    c.dr = gist::spmm_drop_of(mode, p, seed, y_offset, src_offset, mask_ld);
+    c.prepared = prepared; c.pairs = true; c.st = gist::as_stream(stream);
+    return gist::spmm_run(c);
 }
 
 extern "C" int gist_spmm_csr_drop_lnbwd_f32(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx,
@@ -961,29 +999,15 @@ extern "C" int gist_spmm_csr_drop_lnbwd_f32(const int32_t *rowptr, const int32_t
     using namespace gist;
     GIST_REQUIRE(row_blocks != nullptr && n_row_blocks > 0 && partial_rows >= spmm_lnb_units(n_row_blocks),
                  "gist_spmm_csr_drop_lnbwd_f32: col_partials has fewer than gist_spmm_lnb_units(n_row_blocks) rows");
-    SpmmDrop dr{};
-    dr.mode = 2; dr.p = p; dr.scale = (p > 0.f && p < 1.f) ? 1.0f / (1.0f - p) : 1.f;
-    dr.sm = seed * 0x9E3779B97F4A7C15ULL; dr.y_base = y_offset; dr.src_base = src_offset; dr.ld = mask_ld;
-    SpmmLnBwd ln{};
-    ln.yhat = yhat; ln.ldy = ldyh; ln.rstd = rstd; ln.dy = dy; ln.lddy = lddy; ln.col_partials = col_partials; ln.relu = relu;
-    return spmm_drop(rowptr, col, x, ldx, const_cast<float *>(y), ldy, n_rows, d, nullptr, src_scale, 1, row_blocks,
-                     n_row_blocks, dr, as_stream(stream), nullptr, true, &ln);
+    const SpmmLnBwd ln{yhat, ldyh, rstd, dy, lddy, col_partials, relu};
+    SpmmCall c{"gist_spmm_csr_drop_lnbwd_f32", rowptr, col, n_rows, x, ldx, const_cast<float *>(y), ldy, d, nullptr, src_scale, 1};
+    c.set_blocks(row_blocks, n_row_blocks, SPMM_BLOCKS_NONE);
+    c.dr = spmm_drop_of(2, p, seed, y_offset, src_offset, mask_ld);
+    c.ln = &ln; c.st = as_stream(stream);
+    return spmm_run(c);
 }
 
 extern "C" int64_t gist_spmm_lnb_units(int64_t n_row_blocks) { return n_row_blocks > 0 ? gist::spmm_lnb_units(n_row_blocks) : 0; }
-
-extern "C" int gist_spmm_csr_drop_prepared_f32(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx,
-                                               float *y, int64_t ldy, int64_t n_rows, int64_t d,
-                                               const float *out_scale, const float *src_scale, int accumulate,
-                                               const int32_t *row_blocks, int64_t n_row_blocks, int mode, float p,
-                                               uint64_t seed, uint64_t y_offset, uint64_t src_offset,
-                                               int64_t mask_ld, const void *prepared, gist_stream_t stream) {
-    gist::SpmmDrop dr{};
-    dr.mode = mode; dr.p = p; dr.scale = (p > 0.f && p < 1.f) ? 1.0f / (1.0f - p) : 1.f;
-    dr.sm = seed * 0x9E3779B97F4A7C15ULL; dr.y_base = y_offset; dr.src_base = src_offset; dr.ld = mask_ld;
-    return gist::spmm_drop(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate, row_blocks,
-                           n_row_blocks, dr, gist::as_stream(stream), prepared);
-}
 
 extern "C" int gist_spmm_prepared_useful(int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y) {
     // (the fp32 block-dense kernel rides along when the structure exists; alone it does not pay for the 11-us
@@ -991,48 +1015,14 @@ extern "C" int gist_spmm_prepared_useful(int64_t d, int64_t ldx, int64_t ldy, co
     return gist::spmm_prepared_takes(d, ldx, ldy, x, y) ? 1 : 0;
 }
 
+// does gist_spmm_csr_drop_f32 carry the mask for this shape?  (spmm_choose's answer for that call)
 extern "C" int gist_spmm_drop_takes(int mode, int64_t d, int64_t ldx, int64_t ldy, const float *x, const float *y,
                                     int has_row_blocks) {
     static const int32_t dummy = 0;
-    return gist::spmm_drop_takes(mode, d, ldx, ldy, x, y, has_row_blocks ? &dummy : nullptr) ? 1 : 0;
-}
-
-extern "C" int gist_spmm_csr_blocked_f32(const int32_t *rowptr, const int32_t *col, const float *x,
-                                         int64_t ldx, float *y, int64_t ldy, int64_t n_rows,
-                                         int64_t d, const float *out_scale,
-                                         const float *src_scale, int accumulate,
-                                         const int32_t *row_blocks, int64_t n_row_blocks,
-                                         gist_stream_t stream) {
-    using namespace gist;
-    GIST_REQUIRE(n_rows >= 0 && d >= 0, "gist_spmm_csr_blocked_f32: negative size");
-    if (n_rows == 0 || d == 0) return GIST_OK;
-    GIST_REQUIRE(rowptr && x && y, "gist_spmm_csr_blocked_f32: null pointer");
-    GIST_REQUIRE(ldx >= d && ldy >= d, "gist_spmm_csr_blocked_f32: leading dimension < d");
-    GIST_REQUIRE(n_rows < (1LL << 31) && d < (1LL << 31), "gist_spmm_csr_blocked_f32: size >= 2^31");
-    GIST_REQUIRE(row_blocks == nullptr || n_row_blocks > 0,
-                 "gist_spmm_csr_blocked_f32: row_blocks given but n_row_blocks <= 0");
-    // narrow rows keep every lane busy only in the lane-group kernel
-    if (d < 128)
-        return gist_spmm_csr_f32(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                                 accumulate, stream);
-    hipStream_t st = as_stream(stream);
-    if (d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y)) {
-        // wide rows: the block-dense matrix-core kernel (spmm_mfma.hip), whose per-workgroup set-up
-        // (the block's counts, ~11 us) pays from two 128-column tiles per workgroup on -- measured on
-        // the Reddit-like batch: D = 4096 38 vs 57 us, 2048 29 vs 33, 1024 21 vs 16, 512 20 vs 12.
-        // Tuning hook: 1 = always the LDS gather kernel, 2 = always the matrix-core kernel.
-        const int want = (int)tune(GIST_TUNE_SPMM_KERNEL);
-        // (uniform 128-row blocks -- row_blocks = NULL -- cut across the parts: too many neighbours fall
-        // outside a block for the dense product, the gather kernel degrades more gracefully there)
-        if (want == 2 || (want != 1 && d >= 1536 && row_blocks != nullptr))
-            return launch_spmm_mfma(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                                    accumulate, row_blocks, n_row_blocks, nullptr, st);
-        return launch_spmm_lds2(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                                accumulate, row_blocks, n_row_blocks, st);
-    }
-    // other widths / alignments (the layer-0 aggregation of F = 602 features): the row-split kernel
-    return gist_spmm_csr_f32(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                             accumulate, stream);
+    gist::SpmmCall c{};
+    c.x = x; c.ldx = ldx; c.y = const_cast<float *>(y); c.ldy = ldy; c.d = d; c.dr.mode = mode;
+    c.set_blocks(has_row_blocks ? &dummy : nullptr, 1, gist::SPMM_BLOCKS_NONE);
+    return (mode == 1 || mode == 2) && gist::spmm_choose(c).refusal == nullptr ? 1 : 0;
 }
 
 extern "C" int64_t gist_spmm_blocks_bytes(int64_t n_row_blocks) { return gist::spmm_blocks_bytes(n_row_blocks); }
@@ -1047,44 +1037,8 @@ extern "C" int gist_spmm_blocks_prepare(const int32_t *rowptr, const int32_t *co
     GIST_REQUIRE(n_rows < (1LL << 31), "gist_spmm_blocks_prepare: size >= 2^31");
     GIST_REQUIRE(row_blocks == nullptr || n_row_blocks > 0,
                  "gist_spmm_blocks_prepare: row_blocks given but n_row_blocks <= 0");
-    const int64_t nb = row_blocks ? n_row_blocks : ceil_div(n_rows, 128);
-    GIST_REQUIRE(aligned16(prepared) && prepared_bytes >= spmm_blocks_bytes(nb),
+    GIST_REQUIRE(aligned16(prepared) && prepared_bytes >= spmm_blocks_bytes(spmm_block_count(row_blocks, n_row_blocks, n_rows)),
                  "gist_spmm_blocks_prepare: buffer too small or not 16-byte aligned");
     return launch_spmm_blocks_prepare(rowptr, col, nullptr, nullptr, n_rows, row_blocks, n_row_blocks, prepared,
                                       nullptr, as_stream(stream));
-}
-
-namespace gist {
-// gist_spmm_csr_prepared_f32 for a caller that knows whether the batch has sibling blocks (pairs = false: the pairs
-// launch is skipped; a structure prepared with pairs is still read correctly, spmm_prep.h)
-int spmm_prepared(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y, int64_t ldy,
-                  int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
-                  const int32_t *row_blocks, int64_t n_row_blocks, const void *prepared, hipStream_t st, bool pairs) {
-    GIST_REQUIRE(n_rows >= 0 && d >= 0, "gist_spmm_csr_prepared_f32: negative size");
-    if (n_rows == 0 || d == 0) return GIST_OK;
-    GIST_REQUIRE(rowptr && x && y && prepared, "gist_spmm_csr_prepared_f32: null pointer");
-    GIST_REQUIRE(ldx >= d && ldy >= d, "gist_spmm_csr_prepared_f32: leading dimension < d");
-    GIST_REQUIRE(n_rows < (1LL << 31) && d < (1LL << 31), "gist_spmm_csr_prepared_f32: size >= 2^31");
-    GIST_REQUIRE(row_blocks == nullptr || n_row_blocks > 0,
-                 "gist_spmm_csr_prepared_f32: row_blocks given but n_row_blocks <= 0");
-    // below the bf16x3 matrix-core kernel's widths (and for unaligned rows): the fp32 block-dense kernel
-    if (aligned16(prepared) && spmm_dense32_takes(d, ldx, ldy))
-        return launch_spmm_dense32(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
-                                   row_blocks, n_row_blocks, prepared, st);
-    // widths / alignments the matrix-core kernel does not take: the unprepared entry point decides
-    if (!spmm_prepared_takes(d, ldx, ldy, x, y) || !aligned16(prepared))
-        return gist_spmm_csr_blocked_f32(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale,
-                                         accumulate, row_blocks, n_row_blocks, st);
-    return launch_spmm_mfma(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate,
-                            row_blocks, n_row_blocks, prepared, st, nullptr, pairs);
-}
-}  // namespace gist
-
-extern "C" int gist_spmm_csr_prepared_f32(const int32_t *rowptr, const int32_t *col, const float *x,
-                                          int64_t ldx, float *y, int64_t ldy, int64_t n_rows, int64_t d,
-                                          const float *out_scale, const float *src_scale, int accumulate,
-                                          const int32_t *row_blocks, int64_t n_row_blocks,
-                                          const void *prepared, gist_stream_t stream) {
-    return gist::spmm_prepared(rowptr, col, x, ldx, y, ldy, n_rows, d, out_scale, src_scale, accumulate, row_blocks,
-                               n_row_blocks, prepared, gist::as_stream(stream), true);
 }

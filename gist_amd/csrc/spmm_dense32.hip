@@ -254,24 +254,21 @@ bool spmm_dense32_takes(int64_t d, int64_t ldx, int64_t ldy) {
     return d >= 128 && (d % 4 != 0 || ldx % 4 != 0 || ldy % 4 != 0);
 }
 
-int launch_spmm_dense32(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y,
-                        int64_t ldy, int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale,
-                        int accumulate, const int32_t *row_blocks, int64_t n_row_blocks, const void *prepared,
-                        hipStream_t st, const SpmmDrop *dr) {
-    GIST_REQUIRE(prepared != nullptr, "gist_spmm_csr_prepared_f32: null prepared blocks");
-    GIST_REQUIRE(ldy < (1LL << 22) && ldx < (1LL << 22) && d < (1LL << 22),
-                 "gist_spmm_csr_prepared_f32: row pitch of 2^22 floats or more");
+int launch_spmm_dense32(const SpmmCall &c) {
+    GIST_REQUIRE(c.prepared != nullptr, "%s: null prepared blocks", c.entry);
+    GIST_REQUIRE(c.ldy < (1LL << 22) && c.ldx < (1LL << 22) && c.d < (1LL << 22), "%s: row pitch of 2^22 floats or more",
+                 c.entry);
     D32Args a{};
-    a.rowptr = rowptr; a.col = col; a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy;
-    a.n_rows = (int)n_rows; a.d = (int)d; a.out_scale = out_scale; a.src_scale = src_scale;
-    a.accumulate = accumulate; a.row_blocks = row_blocks;
-    a.prep = static_cast<const unsigned char *>(prepared);
-    a.dr = dr ? *dr : SpmmDrop{};
-    const int mode = dr ? dr->mode : 0;
-    const int64_t nb = row_blocks ? n_row_blocks : ceil_div(n_rows, MF_ROWS);
+    a.rowptr = c.rowptr; a.col = c.col; a.x = c.x; a.ldx = c.ldx; a.y = c.y; a.ldy = c.ldy;
+    a.n_rows = (int)c.n_rows; a.d = (int)c.d; a.out_scale = c.out_scale; a.src_scale = c.src_scale;
+    a.accumulate = c.accumulate; a.row_blocks = c.row_blocks;
+    a.prep = static_cast<const unsigned char *>(c.prepared);
+    a.dr = c.dr;
+    const int mode = c.dr.mode;
+    const int64_t nb = c.n_blocks();
     if (nb <= 0) return GIST_OK;
     a.n_blocks = (int)nb;
-    a.n_col_tiles = (int)ceil_div(d, 16);
+    a.n_col_tiles = (int)ceil_div(c.d, 16);
     // row-tile groups: enough wave tasks for the chip's 1024 SIMDs (a block has up to 8 row tiles)
     const int64_t col_tasks = nb * a.n_col_tiles;
     int rt = 2;                                                  // (measured: four groups of two row tiles beat two of four up to D = 1024)
@@ -282,8 +279,8 @@ int launch_spmm_dense32(const int32_t *rowptr, const int32_t *col, const float *
     a.groups = 8 / rt;
     const int64_t tasks = col_tasks * a.groups;
     const int64_t grid = ceil_div(tasks, 4);
-    if (grid > 0x7fffffffLL) { set_error("gist_spmm_csr_prepared_f32: grid too large"); return GIST_EINVAL; }
-#define D32_GO(M, R) hipLaunchKernelGGL((spmm_dense32_kernel<M, R>), dim3((unsigned)grid), dim3(256), 0, st, a)
+    GIST_REQUIRE(grid <= 0x7fffffffLL, "%s: grid too large", c.entry);
+#define D32_GO(M, R) hipLaunchKernelGGL((spmm_dense32_kernel<M, R>), dim3((unsigned)grid), dim3(256), 0, c.st, a)
 #define D32_MODE(M)                                          \
     do {                                                     \
         if (rt == 4) D32_GO(M, 4);                           \
@@ -294,7 +291,7 @@ int launch_spmm_dense32(const int32_t *rowptr, const int32_t *col, const float *
     else D32_MODE(0);
 #undef D32_MODE
 #undef D32_GO
-    return launch_status("gist_spmm_csr_prepared_f32");
+    return launch_status(c.entry);
 }
 
 }  // namespace gist

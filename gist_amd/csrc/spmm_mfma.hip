@@ -1001,7 +1001,7 @@ int launch_spmm_blocks_prepare(const int32_t *rowptr, const int32_t *col, const 
     MfArgs a{};
     a.rowptr = rowptr; a.col = col; a.n_rows = (int)n_rows; a.row_blocks = row_blocks;
     a.pairs = pairs ? 1 : 0;
-    const int64_t nb = row_blocks ? n_row_blocks : ceil_div(n_rows, MF_ROWS);
+    const int64_t nb = spmm_block_count(row_blocks, n_row_blocks, n_rows);
     a.n_blocks = (int)nb;
     if (nb <= 0) return GIST_OK;
     static DeviceOnce once;
@@ -1018,25 +1018,23 @@ int launch_spmm_blocks_prepare(const int32_t *rowptr, const int32_t *col, const 
     return launch_status("gist_spmm_blocks_prepare");
 }
 
-int launch_spmm_mfma(const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y,
-                     int64_t ldy, int64_t n_rows, int64_t d, const float *out_scale, const float *src_scale,
-                     int accumulate, const int32_t *row_blocks, int64_t n_row_blocks, const void *prepared,
-                     hipStream_t st, const SpmmDrop *dr, bool pairs) {
-    GIST_REQUIRE(ldy < (1LL << 22) && ldx < (1LL << 22) && d < (1LL << 22),
-                 "gist_spmm_csr_blocked_f32: row pitch of 2^22 floats or more");       // 32-bit offsets inside a block
+static_assert(MF_ROWS == 128, "spmm_block_count's uniform blocks");
+int launch_spmm_mfma(const SpmmCall &c, const void *prepared) {
+    GIST_REQUIRE(c.ldy < (1LL << 22) && c.ldx < (1LL << 22) && c.d < (1LL << 22),
+                 "%s: row pitch of 2^22 floats or more", c.entry);       // 32-bit offsets inside a block
+    const int64_t nb = c.n_blocks();
     MfArgs a{};
-    a.rowptr = rowptr; a.col = col; a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy;
-    a.n_rows = (int)n_rows; a.d = (int)d; a.out_scale = out_scale; a.src_scale = src_scale;
-    a.accumulate = accumulate; a.row_blocks = row_blocks;
+    a.rowptr = c.rowptr; a.col = c.col; a.x = c.x; a.ldx = c.ldx; a.y = c.y; a.ldy = c.ldy;
+    a.n_rows = (int)c.n_rows; a.d = (int)c.d; a.out_scale = c.out_scale; a.src_scale = c.src_scale;
+    a.accumulate = c.accumulate; a.row_blocks = c.row_blocks;
     a.prep = static_cast<const unsigned char *>(prepared);
-    a.pairs = (pairs && prepared != nullptr && row_blocks != nullptr && n_row_blocks <= MF_PAIR_BLOCKS) ? 1 : 0;
-    a.dr = dr ? *dr : SpmmDrop{};
-    GIST_REQUIRE(a.dr.ld < (1LL << 22), "gist_spmm_csr_drop_f32: mask pitch of 2^22 elements or more");
-    const int mode = dr ? dr->mode : 0;
-    GIST_REQUIRE(mode == 0 || mode == 1, "gist_spmm_csr_drop_f32: the matrix-core kernel carries the forward mask only");
-    const int64_t nb = row_blocks ? n_row_blocks : ceil_div(n_rows, MF_ROWS);
+    a.pairs = (c.pairs && prepared != nullptr && c.row_blocks != nullptr && nb <= MF_PAIR_BLOCKS) ? 1 : 0;
+    a.dr = c.dr;
+    GIST_REQUIRE(a.dr.ld < (1LL << 22), "%s: mask pitch of 2^22 elements or more", c.entry);
+    const int mode = c.dr.mode;
+    GIST_REQUIRE(mode == 0 || mode == 1, "%s: the matrix-core kernel carries the forward mask only", c.entry);
     a.n_blocks = (int)nb;
-    a.n_col_tiles = (int)ceil_div(d, MF_CT);
+    a.n_col_tiles = (int)ceil_div(c.d, MF_CT);
     // one workgroup per CU at a time: as many column groups per block as fill the chip once
     int64_t groups = nb > 0 ? 256 / nb : 1;
     if (groups < 1) groups = 1;
@@ -1044,7 +1042,7 @@ int launch_spmm_mfma(const int32_t *rowptr, const int32_t *col, const float *x, 
     a.groups = (int)groups;
     const int64_t total = nb * groups;
     const int64_t grid = kXcds * ceil_div(total, kXcds);
-    if (grid > 0x7fffffffLL) { set_error("gist_spmm_csr_blocked_f32: grid too large"); return GIST_EINVAL; }
+    GIST_REQUIRE(grid <= 0x7fffffffLL, "%s: grid too large", c.entry);
     static DeviceOnce once;
     int dev;
     if (once.needed(&dev)) {
@@ -1055,17 +1053,18 @@ int launch_spmm_mfma(const int32_t *rowptr, const int32_t *col, const float *x, 
                              reinterpret_cast<const void *>(&spmm_csr_mfma_pairs_kernel<0>),
                              reinterpret_cast<const void *>(&spmm_csr_mfma_pairs_kernel<1>)};
         for (const void *k : ks) {
-            const int rc = mf_set_lds(k, "gist_spmm_csr_blocked_f32");
+            const int rc = mf_set_lds(k, c.entry);
             if (rc != GIST_OK) return rc;
         }
         once.done(dev);
     }
+    hipStream_t st = c.st;
 #define MF_GO(P, D)                                                                                             \
     hipLaunchKernelGGL((spmm_csr_mfma_kernel<P, D>), dim3((unsigned)grid), dim3(MF_THREADS), MF_LDS_BYTES, st, a)
     if (prepared && a.pairs) {
         // + the blocks with pairs, one workgroup per (block, column tile), behind the others in the same grid
         const int64_t grid_p = kXcds * ceil_div(nb * ((a.n_col_tiles + MF_FINE_TILES - 1) / MF_FINE_TILES), kXcds);
-        if (grid + grid_p > 0x7fffffffLL) { set_error("gist_spmm_csr_blocked_f32: grid too large"); return GIST_EINVAL; }
+        GIST_REQUIRE(grid + grid_p <= 0x7fffffffLL, "%s: grid too large", c.entry);
         if (mode == 1)
             hipLaunchKernelGGL((spmm_csr_mfma_pairs_kernel<1>), dim3((unsigned)(grid + grid_p)), dim3(MF_THREADS), MF_LDS_BYTES,
                                st, a, (int)grid);
@@ -1078,7 +1077,7 @@ int launch_spmm_mfma(const int32_t *rowptr, const int32_t *col, const float *x, 
         if (mode == 1) MF_GO(false, 1); else MF_GO(false, 0);
     }
 #undef MF_GO
-    return launch_status("gist_spmm_csr_blocked_f32");
+    return launch_status(c.entry);
 }
 
 // Off-diagonal block pairs of a part-ordered graph (full-graph evaluation): unit u = (r0, r1, xs0, xs1) computes
@@ -1338,8 +1337,7 @@ extern "C" int gist_spmm_block_chains_f32(const int32_t *chain_ptr, int64_t n_ch
     GIST_REQUIRE(n_chains >= 0 && d >= 0 && n_rows_y >= 0, "gist_spmm_block_chains_f32: negative size");
     if (n_chains == 0 || d == 0) return GIST_OK;
     GIST_REQUIRE(chain_ptr && units && images && x && y, "gist_spmm_block_chains_f32: null pointer");
-    GIST_REQUIRE(d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d && aligned16(x) && aligned16(y) &&
-                     aligned16(images),
+    GIST_REQUIRE(spmm_rows16(d, ldx, ldy, x, y) && ldx >= d && ldy >= d && aligned16(images),
                  "gist_spmm_block_chains_f32: rows must be 16-byte aligned multiples of 4 floats");
     return launch_spmm_mfma_chains(chain_ptr, n_chains, units, images, x, ldx, y, ldy, n_rows_y, d, out_scale, accumulate,
                                    as_stream(stream));
@@ -1352,8 +1350,7 @@ extern "C" int gist_spmm_block_units_f32(const int32_t *units, int64_t n_units, 
     GIST_REQUIRE(n_units >= 0 && d >= 0 && n_rows_y >= 0, "gist_spmm_block_units_f32: negative size");
     if (n_units == 0 || d == 0) return GIST_OK;
     GIST_REQUIRE(units && images && x && y, "gist_spmm_block_units_f32: null pointer");
-    GIST_REQUIRE(d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d && aligned16(x) && aligned16(y) &&
-                     aligned16(images),
+    GIST_REQUIRE(spmm_rows16(d, ldx, ldy, x, y) && ldx >= d && ldy >= d && aligned16(images),
                  "gist_spmm_block_units_f32: rows must be 16-byte aligned multiples of 4 floats");
     return launch_spmm_mfma_units(units, n_units, images, x, ldx, y, ldy, n_rows_y, d, out_scale, accumulate,
                                   as_stream(stream));

@@ -366,7 +366,6 @@ struct StepDecisions {
     bool fwd_fold[GIST_MAX_LAYERS];        // forward: dropout([h | ah]) written by the producers, the aggregation reads hsrc[k]
     bool mask_in_spmm[GIST_MAX_LAYERS];    // backward: the mask of dZ_k applied by the reverse aggregation as it reads dZ_k
     bool cls_fused;                // the class layer as gist_class_layer_f32 + gist_class_dw_slabs_f32
-    float keep; uint64_t sm;       // dropout's scale and seed multiple
 };
 
 // a kept-split layout carved from the plan's workspace; none if the workspace is missing, misaligned or too small, or
@@ -380,11 +379,26 @@ Step kept_splits(const gist_step_plan *p, int64_t n, int mode, Step (*layout)(co
 
 // May layer k's dropout be folded into the producers of [h | ah] when its mask starts at `offset`?  A function of the
 // layer and the offset, so that the optimiser can apply it to the NEXT batch's layer 0 (gist_extract_parts_desc.x0) the
-// way the next call applies it to itself.  Reads d.fuse, d.drop, d.plain and d.blocked.
+// way the next call applies it to itself.  Reads d.fuse, d.drop and d.plain.  (Every aggregation kernel carries the
+// forward mask, whatever the shape: spmm_choose.)
 bool folds_forward(const gist_step_plan *p, const StepDecisions &d, int k, uint64_t offset) {
     const gist_layer_desc &l = p->layer[k];
-    return d.fuse && d.drop && d.plain[k] && p->hsrc[k] != nullptr && (offset & 1) == 0 && p->ld_hsrc[k] >= l.n_in &&
-           spmm_drop_takes(1, l.n_in, p->ld_hsrc[k], l.ldz, p->hsrc[k], l.Z + l.n_in, d.blocked ? p->row_blocks : nullptr);
+    return d.fuse && d.drop && d.plain[k] && p->hsrc[k] != nullptr && (offset & 1) == 0 && p->ld_hsrc[k] >= l.n_in;
+}
+
+// The step's aggregations run on the batch's locality blocks when it comes with them (otherwise on the row kernels), read
+// the batch's prepared block structure of their orientation where there is one (StepState), and look for sibling blocks
+// only if the plan says the batch may have them.
+// Layer k's reverse aggregation: dO_{k-1} = the A^T-aggregate of dZ_k's right half, added into its left half; masked:
+// under dZ_k's dropout mask, applied by the aggregation as it reads dZ_k.
+SpmmCall reverse_call(const gist_step_plan *p, const StepDecisions &d, int64_t n, int k, bool masked) {
+    const gist_layer_desc &l = p->layer[k];
+    SpmmCall c{"gist_sage_step", p->t_rowptr, p->t_col, n, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, l.n_in, nullptr,
+               p->norm, 1};
+    c.set_blocks(d.blocked ? p->row_blocks : nullptr, p->n_row_blocks, SPMM_BLOCKS_NONE);
+    c.pairs = d.pairs;
+    if (masked) c.dr = spmm_drop_of(2, p->p_drop, p->seed, d.offs[k], d.offs[k] + (uint64_t)l.n_in, 2 * l.n_in);
+    return c;
 }
 
 StepDecisions decide(const gist_step_plan *p, int64_t n, uint64_t drop_offset, int flags) {
@@ -419,11 +433,8 @@ StepDecisions decide(const gist_step_plan *p, int64_t n, uint64_t drop_offset, i
         // (layer 0's producer is the extraction: this call's, or the previous call's GIST_STEP_EXTRACT_NEXT)
         d.fwd_fold[k] = (k > 0 || (flags & (GIST_STEP_EXTRACT | GIST_STEP_PREEXTRACTED))) && folds_forward(p, d, k, d.offs[k]);
         d.mask_in_spmm[k] = d.fuse && d.drop && k > 0 && k < L1 - 1 && (d.offs[k] & 1) == 0 &&
-                            spmm_drop_takes(2, l.n_in, 2 * l.n_in, 2 * l.n_in, p->dZ + l.n_in, p->dZ,
-                                            d.blocked ? p->row_blocks : nullptr);
+                            spmm_choose(reverse_call(p, d, n, k, true)).refusal == nullptr;
     }
-    d.keep = d.drop ? 1.0f / (1.0f - p->p_drop) : 1.f;
-    d.sm = p->seed * 0x9E3779B97F4A7C15ULL;
     // the class layer as gist_class_layer_f32 + gist_class_dw_slabs_f32 (projection, CE, dZ with its mask and the
     // bias gradient's chunk sums in one launch, dW as slabs for the optimiser) instead of four launches
     const gist_layer_desc &l = p->layer[L1 - 1];
@@ -478,21 +489,6 @@ void add_segment(const gist_step_plan *p, StepState &x, const float *dst, int64_
     gist_grad_segment &g = x.segs[x.n_segs++];
     g.begin = dst - p->grads; g.end = g.begin + count;
     g.src = src; g.stride = count; g.n_src = (int32_t)n_src;
-}
-
-// The step's aggregations: the blocked kernels when the batch comes with its locality blocks; with the
-// batch's prepared block structure (`prepared`: this orientation's) the matrix-core kernel skips its set-up,
-// and looks for sibling blocks only if the plan says the batch may have them.
-int step_spmm(const gist_step_plan *p, const int32_t *rowptr, const int32_t *col, const float *x, int64_t ldx, float *y,
-              int64_t ldy, int64_t n, int64_t d, const float *out_scale, const float *src_scale, int accumulate,
-              const void *prepared, gist_stream_t s) {
-    if (p->row_blocks == nullptr || p->n_row_blocks <= 0)
-        return gist_spmm_csr_f32(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale, accumulate, s);
-    if (prepared != nullptr)
-        return spmm_prepared(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale, accumulate, p->row_blocks,
-                             p->n_row_blocks, prepared, as_stream(s), p->sibling_parts != 0);
-    return gist_spmm_csr_blocked_f32(rowptr, col, x, ldx, y, ldy, n, d, out_scale, src_scale, accumulate, p->row_blocks,
-                                     p->n_row_blocks, s);
 }
 
 // ---- phase 1: this step's weights as kept split operands ---------------------------------------------------
@@ -590,17 +586,14 @@ int forward(const gist_step_plan *p, const StepDecisions &d, const StepState &x,
         const float *y_slabs = nullptr;
         if (!(k == 0 && x.pre_ah)) {
             Scope sc(p->timer, 0, n, n, l.n_in, st);
+            SpmmCall c{"gist_sage_step", p->rowptr, p->col, n, l.Z, l.ldz, l.Z + l.n_in, l.ldz, l.n_in, p->norm, nullptr, 0};
+            c.set_blocks(d.blocked ? p->row_blocks : nullptr, p->n_row_blocks, SPMM_BLOCKS_NONE);
+            c.prepared = x.prep_fwd; c.pairs = d.pairs; c.st = st;
             if (d.fwd_fold[k]) {      // source = the undropped input, store = dropout(ah)
-                SpmmDrop dr{};
-                dr.mode = 1; dr.p = p->p_drop; dr.scale = d.keep; dr.sm = d.sm;
-                dr.y_base = d.offs[k] + (uint64_t)l.n_in; dr.src_base = 0; dr.ld = 2 * l.n_in;
-                GIST_TRY(spmm_drop(p->rowptr, p->col, p->hsrc[k], p->ld_hsrc[k], l.Z + l.n_in, l.ldz, n, l.n_in,
-                                   p->norm, nullptr, 0, d.blocked ? p->row_blocks : nullptr, p->n_row_blocks, dr, st,
-                                   x.prep_fwd, d.pairs));
-            } else {
-                GIST_TRY(step_spmm(p, p->rowptr, p->col, l.Z, l.ldz, l.Z + l.n_in, l.ldz, n, l.n_in, p->norm, nullptr, 0,
-                                   x.prep_fwd, s));
+                c.x = p->hsrc[k]; c.ldx = p->ld_hsrc[k];
+                c.dr = spmm_drop_of(1, p->p_drop, p->seed, d.offs[k] + (uint64_t)l.n_in, 0, 2 * l.n_in);
             }
+            GIST_TRY(spmm_run(c));
         }
         if (d.h3.layer[k].on) {
             // dropout + split of Z_k in one pass (both layouts when training); the dropped fp32 Z_k is never written: the
@@ -695,26 +688,18 @@ struct LayerCarry {
     bool dw_pending;
 };
 
-// dO_{k-1} = A^T-aggregate of dZ_k's right half into its left half, under dZ_k's dropout mask: folded into the
-// aggregation's reader (mask_in_spmm), or, for the unmasked dZ of a split projection, by a pass over dZ_k first (a plain
-// layer's dZ kernel has applied it).  ln: the LayerNorm backward of layer k - 1 riding in this launch's store.
+// reverse_call under dZ_k's dropout mask: folded into the aggregation's reader (mask_in_spmm), or, for the unmasked dZ of
+// a split projection, by a pass over dZ_k first (a plain layer's dZ kernel has applied it).  ln: the LayerNorm backward of
+// layer k - 1 riding in this launch's store.
 int reverse_aggregate(const gist_step_plan *p, const StepDecisions &d, const StepState &x, int64_t n, int k,
                       gist_stream_t s, const SpmmLnBwd *ln = nullptr) {
     const gist_layer_desc &l = p->layer[k];
-    hipStream_t st = as_stream(s);
-    if (d.mask_in_spmm[k]) {
-        Scope sc(p->timer, 0, n, n, l.n_in, st);
-        SpmmDrop dr{};
-        dr.mode = 2; dr.p = p->p_drop; dr.scale = d.keep; dr.sm = d.sm;
-        dr.y_base = d.offs[k]; dr.src_base = d.offs[k] + (uint64_t)l.n_in; dr.ld = 2 * l.n_in;
-        return spmm_drop(p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n, l.n_in, nullptr,
-                         p->norm, 1, p->row_blocks, p->n_row_blocks, dr, st, x.prep_bwd, d.pairs, ln);
-    }
-    if (d.drop && !d.plain[k])
+    if (!d.mask_in_spmm[k] && d.drop && !d.plain[k])
         GIST_TRY(gist_dropout_f32(p->dZ, 2 * l.n_in, n, 2 * l.n_in, p->p_drop, p->seed, d.offs[k], s));
-    Scope sc(p->timer, 0, n, n, l.n_in, st);
-    return step_spmm(p, p->t_rowptr, p->t_col, p->dZ + l.n_in, 2 * l.n_in, p->dZ, 2 * l.n_in, n, l.n_in, nullptr,
-                     p->norm, 1, x.prep_bwd, s);
+    Scope sc(p->timer, 0, n, n, l.n_in, as_stream(s));
+    SpmmCall c = reverse_call(p, d, n, k, d.mask_in_spmm[k]);
+    c.prepared = x.prep_bwd; c.ln = ln; c.st = as_stream(s);
+    return spmm_run(c);
 }
 
 // dY_k of a hidden layer from dO_k (the left half of dZ_{k+1}), over yhat in Y_k.  *db_done: the bias gradient's chunk
@@ -891,16 +876,13 @@ int backward_plain(const gist_step_plan *p, const StepDecisions &d, StepState &x
     // the LayerNorm + ReLU backward of layer k - 1 in the aggregation's store (its rows are whole in one wave)
     const gist_layer_desc &lo = p->layer[k - 1];
     const int64_t units = d.blocked ? spmm_lnb_units(p->n_row_blocks) : 0;
+    const SpmmLnBwd ln{lo.Y, lo.ldy, p->use_layernorm ? lo.rstd : nullptr, lo.Y, lo.ldy, fl.partials[k - 1], 1};
+    SpmmCall ask = reverse_call(p, d, n, k, true);      // can the call carry it?
+    ask.prepared = x.prep_bwd; ask.ln = &ln;
     const bool with_ln = d.defer && d.plain[k - 1] && !c.dw_pending && (int)tune(GIST_TUNE_LNB_FUSED) != 1 &&
-                         units > 0 && units <= fl.partial_rows[k - 1] && lo.ldy % 4 == 0 && aligned16(lo.Y) &&
-                         (!p->use_layernorm || lo.rstd != nullptr) &&
-                         spmm_lnb_takes(l.n_in, 2 * l.n_in, 2 * l.n_in, p->dZ + l.n_in, p->dZ, p->row_blocks, x.prep_bwd);
-    SpmmLnBwd ln{};
-    if (with_ln) {
-        ln.yhat = lo.Y; ln.ldy = lo.ldy; ln.rstd = p->use_layernorm ? lo.rstd : nullptr;
-        ln.dy = lo.Y; ln.lddy = lo.ldy; ln.col_partials = fl.partials[k - 1]; ln.relu = 1;
-        c.lnb_rows = units;
-    }
+                         units > 0 && units <= fl.partial_rows[k - 1] && (!p->use_layernorm || lo.rstd != nullptr) &&
+                         spmm_choose(ask).refusal == nullptr;
+    if (with_ln) c.lnb_rows = units;
     return reverse_aggregate(p, d, x, n, k, s, with_ln ? &ln : nullptr);
 }
 

@@ -1,6 +1,6 @@
 """CPU: the cases of test_spmm_kernels_gpu.py reach every aggregation kernel instantiation, through that module's mirror
-of the host dispatch (spmm.hip spmm_generic / launch_spmm / mfma_takes / lds2_takes / spmm_prepared_takes /
-l2_split_for, spmm_dense32.hip spmm_dense32_takes and its row-tile choice); and the mirror agrees with the library's
+of the host dispatch (spmm.hip spmm_choose / spmm_generic / launch_spmm / spmm_prepared_takes / l2_split_for,
+spmm_dense32.hip spmm_dense32_takes and its row-tile choice); and the mirror agrees with the library's
 own answers (gist_spmm_drop_takes, gist_spmm_prepared_useful) over a grid of widths, pitches, pointer alignments, row
 blocks and every spmm_kernel tuning value, so a change to the C++ dispatch the mirror misses fails here."""
 import itertools

@@ -475,7 +475,14 @@ DENSE32 = [
       tune={'spmm_kernel': 3, 'spmm_split': 2}),
     C('d32_many_blocks', 'many_blocks', 'prepared', 129, modes=(0, 1)),
 ]
-CASES = PLAIN + LDS + LNB + MFMA + DENSE32
+# the prepared entries falling through to the kernels that do not read the structure (knob 2 below 1536 columns: the
+# plain form runs the matrix-core kernel unprepared, the masked form reads the structure)
+PREP_FALLS = [
+    C('prep_to_lds_d256', 'parts_small', 'prepared', 256, modes=(0, 1, 2)),
+    C('prep_to_csr_d64', 'parts_small', 'prepared', 64, modes=(0, 1)),
+    C('prep_to_mfma_forced_d256', 'parts_small', 'prepared', 256, modes=(0, 1), tune={'spmm_kernel': 2}),
+]
+CASES = PLAIN + LDS + LNB + MFMA + DENSE32 + PREP_FALLS
 
 
 def case_instantiations(c):
