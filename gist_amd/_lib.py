@@ -162,6 +162,12 @@ SIGNATURES = {
     'gist_ln_all_fwd_f32': (_int, [_p, _p, _p, _i64, _f, _p, _p]),
     'gist_ln_all_bwd_f32': (_int, [_p, _p, _p, _p, _i64, _p, _p]),
     'gist_ln_affine_fwd_f32': (_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _int, _f, _p]),
+    'gist_ln_affine_fwd_drop_f32': (_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _int, _f,
+                                           _f, _u64, _u64, _i64, _p]),
+    'gist_graphsage_step_workspace_bytes': (_i64, [_p]),
+    'gist_graphsage_step_ln_workspace_floats': (_i64, [_p]),
+    'gist_graphsage_step_folds': (_int, [_p, _i32]),
+    'gist_graphsage_step': (_int, [_p, _p, _i64, _u64, _f, _f, _f, _f, _f, _i64, _int, _p]),
     'gist_ln_affine_bwd_workspace_floats': (_i64, [_i64, _i64]),
     'gist_ln_affine_bwd_f32': (_int, [_p, _i64, _p, _i64, _p, _p, _p, _int, _p, _i64, _p, _p, _p, _i64, _i64, _p, _i64,
                                       _p]),
@@ -236,6 +242,31 @@ class GATStepPlan(ctypes.Structure):
                 ('feat', _p), ('ld_feat', _i64), ('labels_all', _p), ('remap', _p),
                 ('rowptr', _p), ('col', _p), ('t_rowptr', _p), ('t_col', _p),
                 ('col_capacity', _i64), ('norm', _p), ('labels', _p),
+                ('node_part', _p), ('part_slot', _p), ('batch_index', _i32), ('extract_scratch', _p),
+                ('next_ids', _p), ('next_n', _i64), ('next_batch_index', _i32),
+                ('n_max', _i64), ('timer', _p)]
+
+
+class GraphSAGELayerDesc(ctypes.Structure):
+    """struct gist_graphsage_layer_desc (include/gist_hip.h)."""
+    _fields_ = [('n_in', _i64), ('n_out', _i64), ('W', _p), ('b', _p), ('gamma', _p), ('beta', _p),
+                ('dW', _p), ('db', _p), ('dgamma', _p), ('dbeta', _p), ('Z', _p), ('H', _p), ('Y', _p),
+                ('yhat', _p), ('rstd', _p)]
+
+
+class GraphSAGEStepPlan(ctypes.Structure):
+    """struct gist_graphsage_step_plan (include/gist_hip.h)."""
+    _fields_ = [('n_layers', _i32), ('use_pp', _i32), ('p_drop', _f), ('seed', _u64),
+                ('layer', GraphSAGELayerDesc * GIST_MAX_LAYERS),
+                ('dZ', _p), ('dlogits', _p), ('row_loss', _p), ('loss', _p), ('loss_mask', _p),
+                ('loss_count', _i64), ('partials', _p),
+                ('ln_workspace', _p), ('ln_workspace_floats', _i64), ('workspace', _p), ('workspace_bytes', _i64),
+                ('params', _p), ('grads', _p), ('exp_avg', _p), ('exp_avg_sq', _p), ('n_params', _i64),
+                ('g_rowptr', _p), ('g_col', _p), ('g_t_rowptr', _p), ('g_t_col', _p),
+                ('feat', _p), ('ld_feat', _i64), ('labels_all', _p), ('remap', _p),
+                ('rowptr', _p), ('col', _p), ('t_rowptr', _p), ('t_col', _p),
+                ('col_capacity', _i64), ('norm', _p), ('labels', _p),
+                ('row_blocks', _p), ('n_row_blocks', _i64),
                 ('node_part', _p), ('part_slot', _p), ('batch_index', _i32), ('extract_scratch', _p),
                 ('next_ids', _p), ('next_n', _i64), ('next_batch_index', _i32),
                 ('n_max', _i64), ('timer', _p)]

@@ -3,7 +3,9 @@
 Adam is ONE launch over the arena, the GIST sync all-gathers it as it stands (no packing copies) and the block movers of
 gist_amd.ist work on the views.  FlatArena owns the layout and the storage; a family states the two shapes of a layer
 and the names of its views: ParamArena (GraphSAGE: W [o, 2i], b [o]) and GATArena (GAT: the heads' fc weights stacked
-W [nh*o, i], their attention vectors stacked A [nh, 2o]).
+W [nh*o, i], their attention vectors stacked A [nh, 2o]).  GraphSAGEArena (modules.GraphSAGE: W, b and the LayerNorm's
+gamma, beta per layer) has four tensors per hidden layer and pads every view to a 16-byte boundary, so it keeps its own
+layout code beside FlatArena's, which stays byte for byte what ParamArena and GATArena were built on.
 """
 import math
 import weakref
@@ -119,6 +121,116 @@ class ParamArena(FlatArena):
         owner, gist_amd.ist.DistributedGNNWrapper): a ModuleEngine for it then steps this arena in place instead of
         re-homing the module into an arena of its own (module_engine.shared_arena)."""
         gcn.__dict__['_gist_arena'] = weakref.ref(self)
+
+
+def graphsage_dims(in_feats, n_hidden, n_classes, n_layers):
+    """[(in, out)] of the n_layers + 1 layers of gist_amd.modules.GraphSAGE(in_feats, n_hidden, n_classes, n_layers, ...):
+    the input layer, n_layers - 1 hidden ones, the output layer (cluster_gcn/modules.py:161-189)."""
+    return [(in_feats, n_hidden)] + [(n_hidden, n_hidden)] * (n_layers - 1) + [(n_hidden, n_classes)]
+
+
+class GraphSAGEArena(object):
+    """gist_amd.modules.GraphSAGE layers, dims = [(in, out)] (graphsage_dims): per layer W [out, 2*in] and b [out] and,
+    for every layer but the last (the output layer has no norm), the LayerNorm's gamma [out] and beta [out] -- one flat
+    fp32 tensor, layer after layer.  Unlike FlatArena's two-tensor layers, EVERY view starts on a 16-byte boundary (the
+    gaps are zero floats that Adam leaves zero): the three vectors of a layer never push its tail kernels off their
+    16-byte path, whatever the widths.  `W`, `b`, `gamma`, `beta` are the views of `params` (gamma / beta: None for the
+    output layer), after with_grads() `dW`, `db`, `dgamma`, `dbeta` those of `grads` at the same offsets."""
+    names = ('W', 'b', 'gamma', 'beta')
+    ALIGN = 4                   # floats
+
+    def __init__(self, dims, device):
+        self.dims = [(int(i), int(o)) for (i, o) in dims]
+        self.device = device
+        self._shapes, self.offsets = [], []
+        off = 0
+        for k, (i, o) in enumerate(self.dims):
+            shapes = [(o, 2 * i), (o,)] + ([(o,), (o,)] if k + 1 < len(self.dims) else [])
+            offs = []
+            for s in shapes:
+                off = (off + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+                offs.append(off)
+                off += math.prod(s)
+            self._shapes.append(shapes)
+            self.offsets.append(tuple(offs))
+        self.numel = (off + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        self.params = torch.zeros(self.numel, dtype=torch.float32, device=device)
+        self._name_views(self.params, '')
+        for g in self.gamma:
+            if g is not None:
+                g.fill_(1.0)                # nn.LayerNorm's initial weight
+        self.grads = self.exp_avg = self.exp_avg_sq = None
+        for name in self.names:
+            setattr(self, 'd' + name, [])
+        self.step = 0
+
+    def layer_views(self, flat, k):
+        """Layer k's (W, b, gamma, beta) -- (W, b) for the output layer -- as views of `flat`, a flat tensor in this
+        arena's layout."""
+        return tuple(flat[o:o + math.prod(s)].view(s) for s, o in zip(self._shapes[k], self.offsets[k]))
+
+    def _name_views(self, flat, prefix):
+        per_layer = [self.layer_views(flat, k) for k in range(len(self.dims))]
+        for j, name in enumerate(self.names):
+            setattr(self, prefix + name, [v[j] if j < len(v) else None for v in per_layer])
+        return per_layer
+
+    def with_grads(self):
+        """Allocate (once) the flat gradient and Adam-moment arenas beside `params` and the 'd' + name views over the
+        gradient arena.  The parameters are not touched."""
+        if self.grads is None:
+            self.grads = torch.zeros_like(self.params)
+            self.exp_avg = torch.zeros_like(self.params)
+            self.exp_avg_sq = torch.zeros_like(self.params)
+            self._name_views(self.grads, 'd')
+        return self
+
+    def reset_optimizer(self):
+        if self.grads is not None:
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+        self.step = 0
+
+    def param_views(self, flat=None):
+        """Per Parameter of module_params, its block of `flat` (None: `params`)."""
+        flat = self.params if flat is None else flat
+        return [v for k in range(len(self.dims)) for v in self.layer_views(flat, k)]
+
+    def load(self, params):
+        """params = per layer (W, b, gamma, beta) -- (W, b) for the output layer -- numpy arrays or tensors."""
+        for k, group in enumerate(params):
+            views = self.layer_views(self.params, k)
+            if len(group) != len(views):
+                raise ValueError('gist_amd: layer %d takes %d tensors, got %d' % (k, len(views), len(group)))
+            for view, t in zip(views, group):
+                view.copy_(torch.as_tensor(t).reshape(view.shape).to(self.device))
+
+    def export(self):
+        return [tuple(v.detach().cpu().numpy().copy() for v in self.layer_views(self.params, k))
+                for k in range(len(self.dims))]
+
+    @staticmethod
+    def module_params(model):
+        """The Parameters of a gist_amd.modules.GraphSAGE, in `model.parameters()` order."""
+        import torch.nn as nn
+        out = []
+        for layer in model.layers:
+            out += [layer.linear.weight, layer.linear.bias]
+            if isinstance(layer.lynorm, nn.LayerNorm):
+                out += [layer.lynorm.weight, layer.lynorm.bias]
+        return out
+
+    def adopt_module(self, model):
+        """Re-home a gist_amd.modules.GraphSAGE's parameters into the arena, values preserved.  The Parameters keep their
+        identity, names and state_dict keys; only their .data moves."""
+        views, params = self.param_views(), self.module_params(model)
+        if len(params) != len(views) or any(tuple(p.shape) != tuple(v.shape) for p, v in zip(params, views)):
+            raise ValueError('gist_amd: the model\'s layers do not match the arena\'s dims %s' % (self.dims,))
+        for p, v in zip(params, views):
+            if p.data_ptr() != v.data_ptr():
+                v.copy_(p.data.to(self.device))
+            p.data = v
+        return model
 
 
 def gat_dims(in_feats, n_hidden, n_classes, n_layers, n_heads, merge='mean'):

@@ -1,6 +1,8 @@
 // The tail of a GraphSAGELayer on gfx950 (cluster_gcn/modules.py:120,144-147): projection bias + LayerNorm WITH affine
 // + ReLU in one forward launch, and a backward that leaves dx and the three column sums (d gamma, d beta, d bias of the
-// projection) as partials per 16-row chunk, finished in a fixed order by a second launch.  No float atomics.
+// projection) as partials per 16-row chunk, finished in a fixed order by a second launch.  No float atomics.  The
+// forward's DROP instantiations (gist_ln_affine_fwd_drop_f32) also fold the NEXT layer's dropout into the store: out
+// under gist_dropout_f32's mask, the undropped value to out2.
 //
 // A row is owned by one wave (d <= 1024) or by one 256-thread workgroup; with up to kE = 16 elements per thread it
 // stays in registers (d <= 16 * TPR: every wave row, workgroup rows up to 4096) and is read once; wider rows are
@@ -113,14 +115,55 @@ __device__ __forceinline__ float sum_pack(const Pack<VEC> &r) {
     else return r.v[0];
 }
 
+// The next layer's dropout folded into the forward's store (gist_ln_affine_fwd_drop_f32): what goes to row r, column c
+// of `out` is multiplied by gist_dropout_f32's keep/scale factor of element m.y_base + r * m.ld + c (m.p = 0: no mask,
+// nothing hashed); the value before the mask goes to out2 (NULL: none).  Only the DROP instantiations read it.
+struct LnaDrop {
+    float *out2; int64_t ldo2;
+    SpmmDrop m;
+};
+
+// the mask on the thread's kE elements of the row whose element 0 has index ibase
+template <int TPR, int VEC>
+__device__ __forceinline__ void mask_elems(float (&v)[kE], uint64_t ibase, int t, int d, const SpmmDrop &m) {
+    if constexpr (VEC == 4) {
+#pragma unroll
+        for (int u = 0; u < kE / 4; ++u) {
+            const int c = t * 4 + u * (TPR * 4);
+            if (c < d) {
+                float4 q = make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
+                drop_f4(q, ibase + (uint64_t)c, m);
+                v[4 * u] = q.x; v[4 * u + 1] = q.y; v[4 * u + 2] = q.z; v[4 * u + 3] = q.w;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < kE; ++e) {
+            const int c = t + e * TPR;
+            if (c < d) v[e] *= drop_keep(ibase + (uint64_t)c, m.sm, m.p, m.scale);
+        }
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void mask_pack(Pack<VEC> &r, uint64_t idx0, const SpmmDrop &m) {
+    if constexpr (VEC == 4) {
+        float4 q = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+        drop_f4(q, idx0, m);
+        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
+    } else {
+        r.v[0] *= drop_keep(idx0, m.sm, m.p, m.scale);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // forward: v = x + lin_bias; yhat = (v - mean) * rstd; out = relu?(gamma * yhat + beta)
+// DROP: out2 = that value, out = it under the next layer's dropout mask (LnaDrop)
 // ---------------------------------------------------------------------------
-template <int TPR, int VEC>
+template <int TPR, int VEC, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
     const float *__restrict__ x, int64_t ldx, const float *__restrict__ lin_bias, const float *__restrict__ gamma,
     const float *__restrict__ beta, float *__restrict__ yhat, int64_t ldy, float *__restrict__ out, int64_t ldo,
-    float *__restrict__ rstd_out, int n_rows, int d, int relu, float eps) {
+    float *__restrict__ rstd_out, int n_rows, int d, int relu, float eps, LnaDrop dr) {
     __shared__ float red[4];
     constexpr int RPB = 256 / TPR;
     const int row = blockIdx.x * RPB + threadIdx.x / TPR;
@@ -129,6 +172,12 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
     const float *xr = x + (int64_t)(live ? row : 0) * ldx;
     float *yr = yhat + (int64_t)(live ? row : 0) * ldy;
     float *orow = out + (int64_t)(live ? row : 0) * ldo;
+    float *o2row = nullptr;
+    uint64_t ibase = 0;
+    if constexpr (DROP) {
+        if (dr.out2 != nullptr) o2row = dr.out2 + (int64_t)(live ? row : 0) * dr.ldo2;
+        ibase = dr.m.y_base + (uint64_t)(live ? row : 0) * (uint64_t)dr.m.ld;
+    }
     if (TPR == 64 || d <= kE * TPR) {
         float v[kE];
         load_elems<TPR, VEC>(v, xr, t, d, live);
@@ -159,6 +208,10 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
         for (int e = 0; e < kE; ++e) {
             v[e] = affine_pre(v[e], g[e], b[e]);
             if (relu) v[e] = fmaxf(v[e], 0.f);
+        }
+        if constexpr (DROP) {
+            if (o2row != nullptr) store_elems<TPR, VEC>(v, o2row, t, d);
+            if (dr.m.p > 0.f) mask_elems<TPR, VEC>(v, ibase, t, d, dr.m);
         }
         store_elems<TPR, VEC>(v, orow, t, d);
         return;
@@ -196,6 +249,10 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
             for (int k = 0; k < VEC; ++k) {
                 p.v[k] = affine_pre(p.v[k], g.v[k], b.v[k]);
                 if (relu) p.v[k] = fmaxf(p.v[k], 0.f);
+            }
+            if constexpr (DROP) {
+                if (o2row != nullptr) st<VEC>(o2row + c, p);
+                if (dr.m.p > 0.f) mask_pack<VEC>(p, ibase + (uint64_t)c, dr.m);
             }
             st<VEC>(orow + c, p);
         }
@@ -369,28 +426,66 @@ __global__ __launch_bounds__(256) void ln_affine_finish_kernel(const float *__re
 }  // namespace
 }  // namespace gist
 
+namespace gist {
+// drop = NULL, or p = 0 and out2 = NULL: the plain instantiations
+static int ln_affine_fwd_ex(const char *name, const float *x, int64_t ldx, const float *lin_bias, const float *gamma,
+                            const float *beta, float *yhat, int64_t ldy, float *out, int64_t ldo, float *rstd,
+                            int64_t n_rows, int64_t d, int relu, float eps, const LnaDrop *drop, hipStream_t st) {
+    GIST_REQUIRE(n_rows >= 0 && d >= 0, "%s: negative size", name);
+    if (n_rows == 0 || d == 0) return GIST_OK;
+    GIST_REQUIRE(x && gamma && beta && yhat && out && rstd, "%s: null pointer", name);
+    GIST_REQUIRE(ldx >= d && ldy >= d && ldo >= d, "%s: leading dimension < d", name);
+    GIST_REQUIRE(n_rows < (1LL << 31) && d < (1LL << 31), "%s: size >= 2^31", name);
+    GIST_REQUIRE(eps >= 0.f, "%s: negative eps", name);
+    bool v4 = d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(yhat) &&
+              aligned16(out) && aligned16(gamma) && aligned16(beta) && aligned16(lin_bias);
+    LnaDrop dr{};
+    const bool dropping = drop != nullptr && (drop->m.p > 0.f || drop->out2 != nullptr);
+    if (dropping) {
+        dr = *drop;
+        if (dr.out2 != nullptr) {
+            GIST_REQUIRE(dr.ldo2 >= d, "%s: leading dimension < d", name);
+            v4 = v4 && dr.ldo2 % 4 == 0 && aligned16(dr.out2);
+        }
+    }
+    const bool wide = d > 1024;
+    const unsigned grid = (unsigned)(wide ? n_rows : ceil_div(n_rows, 4));
+#define L(TPR, V)                                                                                                    \
+    do {                                                                                                             \
+        if (dropping)                                                                                                \
+            hipLaunchKernelGGL((ln_affine_fwd_kernel<TPR, V, true>), dim3(grid), dim3(256), 0, st, x, ldx, lin_bias, \
+                               gamma, beta, yhat, ldy, out, ldo, rstd, (int)n_rows, (int)d, relu, eps, dr);          \
+        else                                                                                                         \
+            hipLaunchKernelGGL((ln_affine_fwd_kernel<TPR, V, false>), dim3(grid), dim3(256), 0, st, x, ldx, lin_bias, \
+                               gamma, beta, yhat, ldy, out, ldo, rstd, (int)n_rows, (int)d, relu, eps, dr);          \
+    } while (0)
+    if (wide) { if (v4) L(256, 4); else L(256, 1); }
+    else { if (v4) L(64, 4); else L(64, 1); }
+#undef L
+    return launch_status(name);
+}
+}  // namespace gist
+
 extern "C" int gist_ln_affine_fwd_f32(const float *x, int64_t ldx, const float *lin_bias, const float *gamma,
                                       const float *beta, float *yhat, int64_t ldy, float *out, int64_t ldo,
                                       float *rstd, int64_t n_rows, int64_t d, int relu, float eps,
                                       gist_stream_t stream) {
-    using namespace gist;
-    GIST_REQUIRE(n_rows >= 0 && d >= 0, "gist_ln_affine_fwd_f32: negative size");
-    if (n_rows == 0 || d == 0) return GIST_OK;
-    GIST_REQUIRE(x && gamma && beta && yhat && out && rstd, "gist_ln_affine_fwd_f32: null pointer");
-    GIST_REQUIRE(ldx >= d && ldy >= d && ldo >= d, "gist_ln_affine_fwd_f32: leading dimension < d");
-    GIST_REQUIRE(n_rows < (1LL << 31) && d < (1LL << 31), "gist_ln_affine_fwd_f32: size >= 2^31");
-    GIST_REQUIRE(eps >= 0.f, "gist_ln_affine_fwd_f32: negative eps");
-    const bool v4 = d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(yhat) &&
-                    aligned16(out) && aligned16(gamma) && aligned16(beta) && aligned16(lin_bias);
-    const bool wide = d > 1024;
-    const unsigned grid = (unsigned)(wide ? n_rows : ceil_div(n_rows, 4));
-#define L(TPR, V)                                                                                                \
-    hipLaunchKernelGGL((ln_affine_fwd_kernel<TPR, V>), dim3(grid), dim3(256), 0, as_stream(stream), x, ldx, lin_bias, \
-                       gamma, beta, yhat, ldy, out, ldo, rstd, (int)n_rows, (int)d, relu, eps)
-    if (wide) { if (v4) L(256, 4); else L(256, 1); }
-    else { if (v4) L(64, 4); else L(64, 1); }
-#undef L
-    return launch_status("gist_ln_affine_fwd_f32");
+    return gist::ln_affine_fwd_ex("gist_ln_affine_fwd_f32", x, ldx, lin_bias, gamma, beta, yhat, ldy, out, ldo, rstd,
+                                  n_rows, d, relu, eps, nullptr, gist::as_stream(stream));
+}
+
+extern "C" int gist_ln_affine_fwd_drop_f32(const float *x, int64_t ldx, const float *lin_bias, const float *gamma,
+                                           const float *beta, float *yhat, int64_t ldy, float *out, int64_t ldo,
+                                           float *out2, int64_t ldo2, float *rstd, int64_t n_rows, int64_t d, int relu,
+                                           float eps, float p, uint64_t seed, uint64_t offset, int64_t mask_ld,
+                                           gist_stream_t stream) {
+    GIST_REQUIRE(p >= 0.f && p < 1.f, "gist_ln_affine_fwd_drop_f32: p must be in [0,1)");
+    GIST_REQUIRE(mask_ld >= d || p == 0.f, "gist_ln_affine_fwd_drop_f32: mask_ld < d");
+    gist::LnaDrop dr{};
+    dr.out2 = out2; dr.ldo2 = ldo2;
+    dr.m = gist::spmm_drop_of(1, p, seed, offset, 0, mask_ld);
+    return gist::ln_affine_fwd_ex("gist_ln_affine_fwd_drop_f32", x, ldx, lin_bias, gamma, beta, yhat, ldy, out, ldo,
+                                  rstd, n_rows, d, relu, eps, &dr, gist::as_stream(stream));
 }
 
 extern "C" int64_t gist_ln_affine_bwd_workspace_floats(int64_t n_rows, int64_t d) {

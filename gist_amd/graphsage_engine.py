@@ -1,0 +1,203 @@
+"""GraphSAGEEngine: the GraphSAGE family's counterpart of SageEngine and GATEngine -- one gist_graphsage_step call per
+training iteration of gist_amd.modules.GraphSAGE (cluster_gcn/modules.py:100-189, the model --use-pp was written for).
+
+One engine = one model on one GPU.  Everything lives in HBM for the whole run and is sized once for the largest batch
+(n_max rows):
+
+  * parameters are a gist_amd.arena.GraphSAGEArena (per layer W [out, 2*in], b [out] and, for every layer but the
+    output layer, the LayerNorm's gamma and beta, every view on a 16-byte boundary); gradients and Adam moments are flat
+    arenas in the same layout, so Adam is ONE launch;
+  * per layer Z = the dropped [h | ah] (torch.cat never materialises: the tail of layer k - 1 writes the left half, the
+    aggregation the right one), H = the undropped h where the dropout is folded into those two producers, Y = the
+    projection (overwritten by dY in the backward), yhat and rstd of the tail;
+  * the cluster batch is extracted on the device from the resident training graph by the step itself, fed by
+    EngineClusterIter(..., use_pp=...) exactly as the other engines are.  With use_pp the resident features are the
+    iterator's [X | A^X]: a training step lets them fill Z_0 whole and layer 0 aggregates nothing.
+
+Dropout is gist_dropout_f32's counter-based generator under the SAGE step's counter scheme (`seed`, a running element
+offset `drop_calls`), not torch's Philox stream: same distribution, other masks than nn.Dropout's.  With p = 0 the step
+computes the module path's function (tests/test_graphsage_step_gpu.py).  DESIGN.md section 10.
+"""
+import ctypes
+
+import torch
+
+from . import _lib, hip
+from .arena import GraphSAGEArena
+from .engine import StepEngine
+
+
+class GraphSAGEEngine(StepEngine):
+    def __init__(self, dims, dropout, n_max, device, seed=0, use_pp=False, arena=None):
+        """dims = [(in_k, out_k)] of ALL layers, the output layer included (gist_amd.arena.graphsage_dims)."""
+        if n_max is None or int(n_max) <= 0:
+            raise ValueError('gist_amd: GraphSAGEEngine needs n_max > 0 (the iterator\'s n_max)')
+        StepEngine.__init__(self, device, n_max)
+        self.dims = [(int(i), int(o)) for (i, o) in dims]
+        if len(self.dims) > _lib.GIST_MAX_LAYERS:
+            raise ValueError('gist_amd: more than %d GraphSAGE layers' % _lib.GIST_MAX_LAYERS)
+        if arena is not None and [tuple(d) for d in arena.dims] != self.dims:
+            raise ValueError('gist_amd: the arena\'s dims %s are not the engine\'s %s' % (arena.dims, self.dims))
+        self.arena = (arena if arena is not None else GraphSAGEArena(self.dims, device)).with_grads()
+        self.p_drop = float(dropout) if dropout else 0.0
+        self.seed = int(seed)
+        self.use_pp = bool(use_pp)
+        self.drop_calls = 0
+        self.n_classes = self.ldc = self.dims[-1][1]        # (the logits are dense: no padded columns)
+        # EngineClusterIter's surface: no part-internal input sums (layer 0's aggregation is the step's own launch)
+        self.fuse = False
+        n = self.n_max
+        f32 = dict(dtype=torch.float32, device=device)
+        self.Z = [torch.zeros(n, 2 * i, **f32) for (i, o) in self.dims]
+        self.H = [None] + [torch.zeros(n, i, **f32) if self.p_drop > 0.0 else None for (i, o) in self.dims[1:]]
+        self.Y = [torch.zeros(n, o, **f32) for (i, o) in self.dims]
+        self.yhat = [torch.zeros(n, o, **f32) for (i, o) in self.dims[:-1]]
+        self.rstd = [torch.zeros(n, **f32) for _ in self.dims[:-1]]
+        self.dZ = torch.zeros(n * max([2 * i for (i, o) in self.dims[1:]] + [4]), **f32)
+        self.dlogits = torch.zeros(n, self.n_classes, **f32)
+        self.row_loss = torch.zeros(n, **f32)
+        self.loss = torch.zeros(1, **f32)
+        self.partials = torch.zeros(max(1, _lib.load().gist_colsum_partials(n)) * self.n_classes, **f32)
+        self._model = None
+
+    def attach_batcher(self, batcher):
+        """Build the native step plan (struct gist_graphsage_step_plan) over `batcher`'s resident graph and batch
+        buffers."""
+        A = self.arena
+        L = _lib.load()
+        P = _lib.GraphSAGEStepPlan()
+        P.n_layers, P.n_max, P.use_pp = len(self.dims), self.n_max, int(self.use_pp)
+        P.p_drop, P.seed = self.p_drop, self.seed
+        last = len(self.dims) - 1
+        for k, (i, o) in enumerate(self.dims):
+            l = P.layer[k]
+            l.n_in, l.n_out = i, o
+            l.W, l.b, l.dW, l.db = A.W[k].data_ptr(), A.b[k].data_ptr(), A.dW[k].data_ptr(), A.db[k].data_ptr()
+            l.Z, l.Y = self.Z[k].data_ptr(), self.Y[k].data_ptr()
+            l.H = self.H[k].data_ptr() if self.H[k] is not None else None
+            if k < last:
+                l.gamma, l.beta = A.gamma[k].data_ptr(), A.beta[k].data_ptr()
+                l.dgamma, l.dbeta = A.dgamma[k].data_ptr(), A.dbeta[k].data_ptr()
+                l.yhat, l.rstd = self.yhat[k].data_ptr(), self.rstd[k].data_ptr()
+        P.dZ, P.dlogits = self.dZ.data_ptr(), self.dlogits.data_ptr()
+        P.row_loss, P.loss, P.partials = self.row_loss.data_ptr(), self.loss.data_ptr(), self.partials.data_ptr()
+        nf = int(L.gist_graphsage_step_ln_workspace_floats(ctypes.byref(P)))
+        self._ln_ws = torch.zeros(max(nf, 4), dtype=torch.float32, device=self.device)
+        P.ln_workspace, P.ln_workspace_floats = self._ln_ws.data_ptr(), self._ln_ws.numel()
+        # split-K scratch of the projections: each gets what hip._ws_for(m, n, k) gives the op-level call (nothing where
+        # the library asks for nothing), so the split decisions -- and the bits -- are the op-by-op sequence's
+        nb = int(L.gist_graphsage_step_workspace_bytes(ctypes.byref(P)))
+        self._ws = torch.empty(max(nb, 1 << 20), dtype=torch.uint8, device=self.device)
+        P.workspace, P.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
+        P.params, P.grads = A.params.data_ptr(), A.grads.data_ptr()
+        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
+        P.n_params = A.numel
+        if batcher.n_max > self.n_max:
+            raise ValueError('gist_amd: the batcher yields up to %d rows, the engine was sized for %d'
+                             % (batcher.n_max, self.n_max))
+        want = (2 if self.use_pp else 1) * self.dims[0][0]
+        if batcher.feat.shape[1] != want:
+            raise ValueError('gist_amd: %d resident feature columns, layer 0 takes %d%s'
+                             % (batcher.feat.shape[1], want,
+                                ' (use_pp: the iterator\'s [X | A^X])' if self.use_pp else ''))
+        self._bind_graph(P, batcher)
+        P.batch_index = P.next_batch_index = -1
+        self.plan = P
+        self._plan_keep = (batcher, batcher.g, self._ws, self._ln_ws)      # keep every buffer alive
+        return P
+
+    def z0_left(self, n):
+        """Where an eager extraction gathers the resident features: layer 0's h, or with use_pp all of [h | ah]."""
+        return self.Z[0][:n] if self.use_pp else self.Z[0][:n, :self.dims[0][0]]
+
+    def logits(self, n):
+        return self.Y[-1][:n]
+
+    def reset_optimizer(self):
+        self.arena.reset_optimizer()
+
+    def folds(self, k):
+        """Does a training step fold layer k's dropout into its producers (gist_graphsage_step_folds, for the plan's
+        current row blocks)?"""
+        return int(_lib.load().gist_graphsage_step_folds(ctypes.byref(self.plan), k)) == 1
+
+    def bind(self, model):
+        """Make a gist_amd.modules.GraphSAGE's Parameters views of the arena (values: the model's; names and state_dict
+        keys unchanged) and remember it as `model`: utils.evaluate(model, g, ...) scores the live weights."""
+        self._model = self.arena.adopt_module(model)
+        return self._model
+
+    @property
+    def model(self):
+        return self._model
+
+    def _plan_next(self, b, flags):
+        """The NEXT batch of the epoch, extracted in the optimiser's grid (GIST_STEP_EXTRACT_NEXT): only for callers that
+        promise not to look at the batch buffers (labels, CSR, layer 0's input) after a training step.  Returns (the
+        key the next step must match, flags)."""
+        P = self.plan
+        if (self.prefetch and (flags & _lib.GIST_STEP_TRAIN) and b.batcher is not None and b.next_info is not None
+                and P.node_part is not None):
+            nids, nj = b.next_info
+            if 0 < nids.numel() <= self.n_max:
+                P.next_ids, P.next_n, P.next_batch_index = nids.data_ptr(), nids.numel(), int(nj)
+                return (self._batch_key(P.part_slot, nj, nids.numel(), nids.data_ptr(), ()),
+                        flags | _lib.GIST_STEP_EXTRACT_NEXT)
+        return None, flags
+
+    def _open_step(self, b, train):
+        """-> (flags, ids pointer, this step's dropout offset); drop_calls advances as op_by_op.decide does."""
+        P = self.plan
+        off = self.drop_calls
+        flags, ids_ptr = self._begin_step(b, train, ())
+        if train and self.p_drop > 0.0:
+            for (i, o) in self.dims:
+                numel = b.n * 2 * i
+                self.drop_calls += numel + (numel & 1)
+        rb = b.row_blocks
+        if rb is not None and rb.numel() > 1:
+            P.row_blocks, P.n_row_blocks = rb.data_ptr(), rb.numel() - 1
+        else:
+            P.row_blocks, P.n_row_blocks = None, 0
+        return flags, ids_ptr, off
+
+    def _call_step(self, ids_ptr, n, off, lr, betas, eps, weight_decay, t, flags, phase):
+        if phase:
+            raise RuntimeError('gist_amd: gist_graphsage_step has no phase calls')
+        rc = _lib.load().gist_graphsage_step(ctypes.byref(self.plan), ids_ptr, n, off, lr, betas[0], betas[1], eps,
+                                             weight_decay, t, flags, hip._stream())
+        _lib.check(rc, 'gist_graphsage_step')
+
+    def _close_step(self, b, train):
+        if train and self.p_drop > 0.0:
+            b.z0_dropped = True      # (one training step per extraction: Z_0 now holds dropped values)
+
+    def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
+        if self.plan is None:
+            raise RuntimeError('gist_amd: GraphSAGEEngine needs attach_batcher (EngineClusterIter.bind) first')
+        if b.ready and b.z0_dropped:
+            raise RuntimeError('gist_amd: one step per extraction -- this Batch was already trained on with dropout, '
+                               'its layer-0 buffer holds dropped values; take a fresh batch from the iterator')
+        P = self.plan
+        if mask is None:
+            P.loss_mask, P.loss_count = None, 0
+        else:
+            if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or mask.numel() < b.n:
+                raise ValueError('gist_amd: the loss mask must be a contiguous uint8 GPU tensor of at least n elements')
+            P.loss_mask = mask.data_ptr()
+            P.loss_count = int(count) if count is not None else int(mask[:b.n].count_nonzero().item())
+        return self._run(b, lr, weight_decay, train, betas, eps)
+
+    def train_step(self, b, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
+        """One iteration of the reference's loop as ONE gist_graphsage_step call.  Returns the device loss tensor: the mean
+        CE over the batch rows, or over the `count` rows where `mask` (uint8 [n]) is not zero -- pred[train_mask] of the
+        reference's loop; a cluster of the train graph needs none.  Nothing synchronises with the host (give `count`
+        with a mask), nothing is allocated."""
+        return self._step(b, lr, weight_decay, True, betas, eps, mask, count)
+
+    def forward(self, b):
+        """GraphSAGE.forward in evaluation mode on the batch (extracted first if it is only described; every layer
+        aggregates, no dropout) and its loss; parameters untouched.  Returns the logits view [n, C]; the loss is in
+        `self.loss`."""
+        self._step(b, 0.0, 0.0, False)
+        return self.logits(b.n)

@@ -531,6 +531,26 @@ def ln_affine_fwd(x, lin_bias, gamma, beta, yhat, out, rstd, relu, eps=LN_EPS):
     return out
 
 
+def ln_affine_fwd_drop(x, lin_bias, gamma, beta, yhat, out, out2, rstd, relu, p, seed, offset, mask_ld, eps=LN_EPS):
+    """ln_affine_fwd with the next layer's dropout folded in (gist_ln_affine_fwd_drop_f32): `out` receives the tail's
+    result under gist_dropout_f32's mask at element index offset + row * mask_ld + c, `out2` (None: none) the result
+    itself.  p = 0: out = the result."""
+    L = _lib.load()
+    xp, ldx = _mat(x, 'x')
+    yp, ldy = _mat(yhat, 'yhat')
+    op, ldo = _mat(out, 'out')
+    o2p, ldo2 = _mat(out2, 'out2') if out2 is not None else (None, 0)
+    n, d = x.shape
+    if tuple(yhat.shape) != (n, d) or tuple(out.shape) != (n, d) or (out2 is not None and tuple(out2.shape) != (n, d)):
+        raise ValueError('gist_amd: ln_affine_fwd_drop shape mismatch')
+    _lib.check(L.gist_ln_affine_fwd_drop_f32(xp, ldx, _opt(lin_bias, 'lin_bias', torch.float32, d),
+                                             _vec(gamma, 'gamma', torch.float32, d), _vec(beta, 'beta', torch.float32, d),
+                                             yp, ldy, op, ldo, o2p, ldo2, _vec(rstd, 'rstd', torch.float32, n), n, d,
+                                             int(bool(relu)), eps, float(p), int(seed), int(offset), int(mask_ld),
+                                             _stream()), 'gist_ln_affine_fwd_drop_f32')
+    return out
+
+
 def ln_affine_bwd(d_out, yhat, rstd, gamma, beta, relu, dx, dgamma, dbeta, dlin_bias=None, ws=None):
     """dx and the column sums dgamma, dbeta (and dlin_bias = the column sums of dx, unless None) of ln_affine_fwd
     (gist_ln_affine_bwd_f32).  ws: float32 scratch of gist_ln_affine_bwd_workspace_floats(n, d) elements (None: taken

@@ -47,8 +47,9 @@ def build_parser():
     # (not a flag of the reference) module: the reference's own loop body, statement for statement, on gist_amd.modules.GCN /
     # nn.CrossEntropyLoss / optim.Adam / sampler.ClusterIter (gist_amd/module_engine.py); engine: one gist_sage_step (sage) or
     # gist_gat_step (gat) per iteration; phases (gat): the module loop with the model bound to its iterator
-    # (module_engine.bind_gat) -- the engine's launches as three gist_gat_step_phase calls per iteration
-    parser.add_argument("--host-path", choices=['engine', 'module', 'phases'], default='engine')
+    # (module_engine.bind_gat) -- the engine's launches as three gist_gat_step_phase calls per iteration; step (graphsage):
+    # one gist_graphsage_step per iteration (gist_amd/graphsage_engine.py); engine and module keep that family's module loop
+    parser.add_argument("--host-path", choices=['engine', 'module', 'phases', 'step'], default='engine')
     # (not a flag of the reference; --model-type gat) how evaluate() runs the full-graph forward: layers = the model's own
     # forward, layer by layer on the training kernels; blocked = gist_amd.gat_eval.GATFullGraphEvaluator (preallocated
     # buffers, two-pass softmax, the graph's node blocks as dense products on the matrix cores)
@@ -105,8 +106,14 @@ def main(args, dataset=None, log=print):
     if host_path == 'phases' and args.model_type != 'gat':
         raise SystemExit('gist_amd: --host-path phases binds a GAT to its iterator (--model-type gat); the SAGE module '
                          'path already runs on the phase calls of the fused step: use --host-path module')
+    if host_path == 'step' and args.model_type != 'graphsage':
+        raise SystemExit('gist_amd: --host-path step is the GraphSAGE family\'s one-call step (--model-type graphsage); '
+                         'the other families run theirs under --host-path engine')
+    if args.model_type == 'graphsage' and host_path == 'step':
+        return main_graphsage_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     if args.model_type == 'graphsage':
-        # modules.GraphSAGE (the model --use-pp was written for) has no fused step: the reference's loop on its layers
+        # modules.GraphSAGE (the model --use-pp was written for): its fused step is opt-in (--host-path step); every other
+        # host path keeps the reference's loop on its layers
         log('--model-type graphsage has no fused step: --host-path %s runs the module loop, layer by layer' % host_path)
         return main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     if args.model_type == 'gat' and host_path == 'engine' and not args.use_pp:
@@ -178,6 +185,49 @@ def main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, l
     log(f'Last Test: {test_accs[-1]:.4f}', flush=True)
     log(f'Best Test: {max(test_accs):.4f}', flush=True)
     return dict(total_time=total_time, val_accs=val_accs, test_accs=test_accs, model=model)
+
+
+def main_graphsage_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log):
+    """--model-type graphsage --host-path step: one gist_graphsage_step per iteration (gist_amd/graphsage_engine.py), fed
+    by EngineClusterIter (with --use-pp: its [X | A^X] features).  Same construction order, RNG draws for the weights and
+    batch order as main_module_path; the dropout masks come from the step's counter-based generator, not torch's."""
+    import time
+    from gist_amd.arena import graphsage_dims
+    from gist_amd.graphsage_engine import GraphSAGEEngine
+    from gist_amd.modules import GraphSAGE
+    from gist_amd.sampler import EngineClusterIter
+    from gist_amd.utils import evaluate
+    train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
+    it = EngineClusterIter(args.dataset, g, psize, args.batch_size, train_nid, use_pp=args.use_pp, par_li=par_li,
+                           device=device)
+    g = g.to(device)
+    labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
+    model = GraphSAGE(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout, args.use_pp)
+    model.cuda()
+    engine = GraphSAGEEngine(graphsage_dims(in_feats, args.n_hidden, n_classes, args.n_layers), args.dropout, it.n_max,
+                             device, seed=args.rnd_seed, use_pp=args.use_pp)
+    engine.bind(model)                                     # the model's parameters are the arena's views from here on
+    it.bind(engine)
+    engine.prefetch = True                                 # (the loop only reads the loss of a step)
+    total_time, val_accs, test_accs = 0., [], []
+    for epoch in range(args.n_epochs):                     # cluster_gcn.py:89-127
+        log(f'Running epoch {epoch} / {args.n_epochs}', flush=True)
+        torch.cuda.synchronize(device)
+        start_time = time.time()
+        for batch in it:
+            engine.train_step(batch, args.lr, args.weight_decay)
+        torch.cuda.synchronize(device)
+        total_time += time.time() - start_time
+        engine.check_extract()                             # (outside the timed interval)
+        val_accs.append(evaluate(model, g, labels, val_mask, 'f1' if args.use_f1 else 'acc'))
+        test_accs.append(evaluate(model, g, labels, test_mask, 'f1' if args.use_f1 else 'acc'))
+        log(f'Val acc {val_accs[-1]}', flush=True)
+    log(f'Training Time: {total_time:.4f}', flush=True)    # :132-136
+    log(f'Last Val: {val_accs[-1]:.4f}', flush=True)
+    log(f'Best Val: {max(val_accs):.4f}', flush=True)
+    log(f'Last Test: {test_accs[-1]:.4f}', flush=True)
+    log(f'Best Test: {max(test_accs):.4f}', flush=True)
+    return dict(total_time=total_time, val_accs=val_accs, test_accs=test_accs, model=model, engine=engine)
 
 
 def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log):

@@ -458,6 +458,19 @@ int gist_ln_all_bwd_f32(const float *g, const float *yhat, const float *stats, f
 int gist_ln_affine_fwd_f32(const float *x, int64_t ldx, const float *lin_bias, const float *gamma, const float *beta,
                            float *yhat, int64_t ldy, float *out, int64_t ldo, float *rstd, int64_t n_rows, int64_t d,
                            int relu, float eps, gist_stream_t stream);
+/* gist_ln_affine_fwd_f32 with the NEXT layer's dropout folded in (cluster_gcn/modules.py:100-189: :144-147 of layer k and
+ * the left half of self.dropout, :140-142, of layer k + 1), as gist_ln_relu_fwd_drop_f32 does for the ISTSAGELayer:
+ * `out` (the left half of the next layer's [h | ah]) receives h times gist_dropout_f32's keep/scale factor at element
+ * index offset + row * mask_ld + c, `out2` (NULL: none) the undropped h -- the source of the next layer's aggregation,
+ * which modules.py:133-142 runs BEFORE it drops.  p = 0: out = h, nothing is hashed.  yhat and rstd are the plain entry's:
+ * the backward's gate recomputes pre from yhat and never sees the mask.  Bit for bit: yhat, rstd and out2 equal the plain
+ * entry's yhat, rstd and out for pointers of the same alignment class, out equals gist_dropout_f32 applied to that out as
+ * a column window of a [n_rows, mask_ld] tensor.  16-byte accesses need what the plain entry needs plus ldo2 % 4 == 0
+ * and a 16-byte aligned out2.  p = 0 and out2 = NULL: the plain entry's own launch. */
+int gist_ln_affine_fwd_drop_f32(const float *x, int64_t ldx, const float *lin_bias, const float *gamma, const float *beta,
+                                float *yhat, int64_t ldy, float *out, int64_t ldo, float *out2, int64_t ldo2, float *rstd,
+                                int64_t n_rows, int64_t d, int relu, float eps, float p, uint64_t seed, uint64_t offset,
+                                int64_t mask_ld, gist_stream_t stream);
 /* Its backward from the saved yhat and rstd (autograd of modules.py:120,144-147):
  *   g' = (pre > 0) ? d_out : 0 when relu (pre recomputed by the forward's own fused multiply-add: the gate agrees
  *   with the forward's out bit for bit; no gradient at pre = 0), else d_out;  dyh = g' * gamma;
@@ -1185,6 +1198,104 @@ int gist_gat_step(const gist_gat_step_plan *plan, const int32_t *ids, int64_t n,
 int gist_gat_step_phase(const gist_gat_step_plan *plan, const int32_t *ids, int64_t n, float lr, float beta1,
                         float beta2, float eps, float weight_decay, int64_t adam_step, int flags,
                         gist_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Whole GraphSAGE training iteration in one call (an addition: no existing signature changed, ABI 16)
+ * ------------------------------------------------------------------------- */
+
+/* One GraphSAGELayer's buffers (cluster_gcn/modules.py:100-189; all device pointers, all preallocated by the caller for
+ * n_max rows, every matrix dense: its leading dimension is its width).  W, b, gamma, beta are views of the flat parameter
+ * arena (gist_amd.arena.GraphSAGEArena), dW ... dbeta the same views of the gradient arena.  The output layer (the last
+ * one: no norm, no activation, modules.py:100-189) has no gamma / beta / yhat / rstd: they are ignored there. */
+typedef struct gist_graphsage_layer_desc {
+    int64_t n_in, n_out;
+    float *W, *b;              /* [n_out, 2*n_in], [n_out]: self.linear                        */
+    float *gamma, *beta;       /* [n_out] each: self.lynorm (hidden layers)                    */
+    float *dW, *db, *dgamma, *dbeta;
+    float *Z;                  /* [n_max, 2*n_in]: the dropped [h | ah], the projection's input */
+    float *H;                  /* [n_max, n_in]: the undropped h of layers >= 1, the source of the aggregation when the
+                                  dropout is folded into its producers (gist_graphsage_step_folds); NULL: never folded */
+    float *Y;                  /* [n_max, n_out]: hidden layers: h . W^T (the tail adds b), overwritten in the backward
+                                  by dY; output layer: the logits                                */
+    float *yhat, *rstd;        /* [n_max, n_out], [n_max]: kept by the tail for its backward    */
+} gist_graphsage_layer_desc;
+
+typedef struct gist_graphsage_step_plan {
+    int32_t n_layers;              /* ALL layers of gist_amd.modules.GraphSAGE, the output layer included; layer k + 1's
+                                      n_in must be layer k's n_out                                  */
+    int32_t use_pp;                /* modules.py:133: the resident features are ClusterIter.precalc's [X | A^X], 2 * n_in_0
+                                      wide; a TRAINING call lets them fill Z_0 whole and layer 0 aggregates nothing; a
+                                      forward-only call takes their left half and aggregates (self.training is off) */
+    float p_drop; uint64_t seed;   /* self.dropout on [h | ah] under gist_dropout_f32's generator: layer k's element
+                                      (r, c) has index drop_offset + sum_{j<k} round_up2(n * 2 n_in_j) + r * 2 n_in_k + c */
+    gist_graphsage_layer_desc layer[GIST_MAX_LAYERS];
+    float *dZ;                     /* [n_max * max_{k>=1}(2 n_in_k)]: backward scratch (unused by a one-layer model) */
+    float *dlogits;                /* [n_max, n_classes], n_classes = the last layer's n_out        */
+    float *row_loss, *loss;        /* [n_max], [1]                                                  */
+    const uint8_t *loss_mask; int64_t loss_count;   /* set per call: the rows the mean CE is taken over and how many of the
+                                      batch's n rows they are (gist_softmax_xent_f32's mask and count: pred[train_mask] of
+                                      cluster_gcn.py:98-104); NULL: all n rows -- every row of a cluster of the train
+                                      graph is a train node                                          */
+    float *partials;               /* [gist_colsum_partials(n_max) * n_classes]: the output layer's db */
+    float *ln_workspace; int64_t ln_workspace_floats;    /* gist_graphsage_step_ln_workspace_floats(plan) */
+    void *workspace; int64_t workspace_bytes;            /* split-K scratch: gist_graphsage_step_workspace_bytes(plan) */
+    float *params, *grads, *exp_avg, *exp_avg_sq; int64_t n_params;   /* flat arenas */
+    /* resident training graph + the batch buffers the extraction fills (as in gist_step_plan) */
+    const int32_t *g_rowptr, *g_col, *g_t_rowptr, *g_t_col;
+    const float *feat; int64_t ld_feat;
+    const int32_t *labels_all;
+    int32_t *remap;                /* only read without the part tables (gist_extract_batch)        */
+    int32_t *rowptr, *col, *t_rowptr, *t_col; int64_t col_capacity;
+    float *norm; int32_t *labels;
+    /* locality blocks of the batch's rows (set per call; NULL: none): every aggregation then runs
+     * gist_spmm_csr_blocked_f32 (prepared block structures are not used by this step) */
+    const int32_t *row_blocks; int64_t n_row_blocks;
+    /* one-launch extraction, as in gist_gat_step_plan */
+    const int32_t *node_part, *part_slot;
+    int32_t batch_index;
+    void *extract_scratch;
+    const int32_t *next_ids;
+    int64_t next_n;
+    int32_t next_batch_index;
+    int64_t n_max;                 /* rows every per-row buffer was sized for                       */
+    struct gist_timer *timer;      /* NULL = no timing; records the GEMM (kind 1) and aggregation (kind 0) calls */
+} gist_graphsage_step_plan;
+
+/* Sizes the caller cannot derive from the shapes alone (modules.py:100-189; host functions; 0 for a NULL plan or bad
+ * shapes): the bytes of `workspace` -- the largest gist_gemm_workspace_bytes over every projection of every layer at
+ * every batch size up to n_max -- and the floats of `ln_workspace` (the largest gist_ln_affine_bwd_workspace_floats of a
+ * hidden layer at n_max rows). */
+int64_t gist_graphsage_step_workspace_bytes(const gist_graphsage_step_plan *plan);
+int64_t gist_graphsage_step_ln_workspace_floats(const gist_graphsage_step_plan *plan);
+
+/* Does a training call fold layer k's dropout into its producers (modules.py:100-189, :140-142)?  1: the tail of layer
+ * k - 1 is gist_ln_affine_fwd_drop_f32 (out = Z_k's left half, out2 = H_k) and the aggregation gist_spmm_csr_drop_f32
+ * mode 1 from H_k; 0: the plain tail, the plain aggregation, then gist_dropout_f32 in place on Z_k (always for layer 0
+ * and for p_drop = 0, where nothing is dropped at all).  A function of shapes and pointers (k >= 1, p_drop > 0, H_k
+ * given, gist_spmm_drop_takes(1, ...) for the plan's row_blocks), the same bits either way.  Host function; -1 for a
+ * bad plan or k. */
+int gist_graphsage_step_folds(const gist_graphsage_step_plan *plan, int32_t k);
+
+/* One iteration of the reference's loop with --model-type graphsage (cluster_gcn/cluster_gcn.py:96-105 on
+ * cluster_gcn/modules.py:100-189) on the batch whose node ids are ids[0..n): extraction (features into Z_0's left half;
+ * with use_pp into all of Z_0), per layer the aggregation left half -> right half with out_scale = norm
+ * (gist_spmm_csr_f32 / _blocked_f32), the dropout on [h | ah] (folded or in place, gist_graphsage_step_folds),
+ * gist_gemm_nt_f32 (hidden layers without the bias: the tail adds it) and the tail gist_ln_affine_fwd(_drop)_f32;
+ * gist_softmax_xent_f32 (mean over the batch rows, or over the rows of plan->loss_mask); per layer in reverse gist_gemm_tn_f32 (dW), gist_colsum_f32 (the
+ * output layer's db) and for k > 0 gist_gemm_nn_dropout_f32 into dZ, the reverse aggregation (transposed CSR, src_scale
+ * = norm, accumulated into dZ's left half) and gist_ln_affine_bwd_f32 from that left half, writing dY_{k-1} (over
+ * Y_{k-1}), dgamma, dbeta and db straight into the gradient arena; one gist_adam_f32 over the arena.  The driver launches
+ * no kernel of its own, so an op-by-op caller that issues the same entry points gets the same bits.  `plan` is HOST
+ * memory; drop_offset is the step's base in the dropout counter space; adam_step is 1-based; no host synchronisation.
+ * flags: GIST_STEP_EXTRACT, GIST_STEP_TRAIN (without it: forward + loss only, no dropout, no parameter touched),
+ * GIST_STEP_EXTRACT_NEXT (the optimiser launch is gist_adam_segments_extract_f32 with no segments and also extracts
+ * plan->next_*) and GIST_STEP_PREEXTRACTED, with their gist_sage_step meaning.  The GIST_STEP_PHASE_* bits and
+ * GIST_STEP_DLOGITS_GIVEN are GIST_EINVAL: this step has no phase calls.  Every argument is checked (null pointers,
+ * sizes, n > n_max, more than GIST_MAX_LAYERS layers, mismatched widths: GIST_EINVAL; a workspace too small for this n:
+ * GIST_ENOSPACE) before any device work. */
+int gist_graphsage_step(const gist_graphsage_step_plan *plan, const int32_t *ids, int64_t n, uint64_t drop_offset,
+                        float lr, float beta1, float beta2, float eps, float weight_decay, int64_t adam_step,
+                        int flags, gist_stream_t stream);
 
 #ifdef __cplusplus
 }
