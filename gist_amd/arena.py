@@ -1,11 +1,11 @@
-"""Flat parameter arenas: one fp32 tensor per model, every layer's two parameter tensors views of it.
+"""Flat parameter arenas: one fp32 tensor per model, every layer's parameter tensors views of it.
 
 Adam is ONE launch over the arena, the GIST sync all-gathers it as it stands (no packing copies) and the block movers of
-gist_amd.ist work on the views.  FlatArena owns the layout and the storage; a family states the two shapes of a layer
-and the names of its views: ParamArena (GraphSAGE: W [o, 2i], b [o]) and GATArena (GAT: the heads' fc weights stacked
-W [nh*o, i], their attention vectors stacked A [nh, 2o]).  GraphSAGEArena (modules.GraphSAGE: W, b and the LayerNorm's
-gamma, beta per layer) has four tensors per hidden layer and pads every view to a 16-byte boundary, so it keeps its own
-layout code beside FlatArena's, which stays byte for byte what ParamArena and GATArena were built on.
+gist_amd.ist work on the views.  FlatArena owns the layout, the storage and the re-homing of a module's Parameters; a
+family states the names of its views, the shapes of a layer, the alignment of a view and its module's Parameters:
+ParamArena (the SAGE GCN: W [o, 2i], b [o]) and GATArena (GAT: the heads' fc weights stacked W [nh*o, i], their attention
+vectors stacked A [nh, 2o]) pack their two tensors per layer without gaps; GraphSAGEArena (modules.GraphSAGE: W, b and,
+but for the output layer, the LayerNorm's gamma, beta) starts every view on a 16-byte boundary.
 """
 import math
 import weakref
@@ -14,41 +14,54 @@ import torch
 
 
 class FlatArena(object):
-    """Per layer tensor 1 then tensor 2, layer after layer.  `offsets[k]` = (start of tensor 1, start of tensor 2) of
-    layer k; `views` = (the tensor-1 views, the tensor-2 views) of `params`, also reachable under the family's `names`
-    (and, after with_grads(), 'd' + name over `grads`).  `params` / `numel` are what the GIST collectives move."""
-    names = None                # (tensor 1, tensor 2)
+    """Per layer its tensors in `names` order, layer after layer, every one starting on a multiple of ALIGN floats (the
+    gaps, and `numel`'s own rounding, are zero floats that Adam leaves zero).  `offsets[k]` = the starts of layer k's
+    tensors; `views` = per name the list of its views of `params` (None where a layer has no such tensor), also
+    reachable under the family's `names` (and, after with_grads(), 'd' + name over `grads`).  `params` / `numel` are
+    what the GIST collectives move."""
+    names = None                # one per tensor of the widest layer
+    ALIGN = 1                   # floats
 
-    def shapes(self, dim):
-        """(shape of tensor 1, shape of tensor 2) of a layer with the entry `dim` of dims."""
+    def shapes(self, dim, k):
+        """The shapes of layer k's tensors, `dim` its entry of dims: the first len(shapes) of `names`."""
         raise NotImplementedError
+
+    def _init_params(self):
+        """What of the fresh (zero) `params` is not zero."""
 
     def __init__(self, dims, device):
         self.dims = list(dims)
         self.device = device
-        self._shapes = [self.shapes(d) for d in self.dims]
+        self._shapes = [tuple(self.shapes(d, k)) for k, d in enumerate(self.dims)]
         self.offsets = []
         off = 0
-        for s1, s2 in self._shapes:
-            self.offsets.append((off, off + math.prod(s1)))
-            off += math.prod(s1) + math.prod(s2)
-        self.numel = off
-        self.params = torch.zeros(off, dtype=torch.float32, device=device)
+        for shapes in self._shapes:
+            offs = []
+            for s in shapes:
+                off = self._aligned(off)
+                offs.append(off)
+                off += math.prod(s)
+            self.offsets.append(tuple(offs))
+        self.numel = self._aligned(off)
+        self.params = torch.zeros(self.numel, dtype=torch.float32, device=device)
         self.views = self._name_views(self.params, '')
+        self._init_params()
         # gradient and Adam-moment arenas in the same layout: only a training step needs them (with_grads)
         self.grads = self.exp_avg = self.exp_avg_sq = None
         for name in self.names:
             setattr(self, 'd' + name, [])
         self.step = 0
 
+    def _aligned(self, off):
+        return (off + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+
     def layer_views(self, flat, k):
-        """Layer k's (tensor 1, tensor 2) as views of `flat`, a flat tensor in this arena's layout."""
-        (s1, s2), (o1, o2) = self._shapes[k], self.offsets[k]
-        return flat[o1:o2].view(s1), flat[o2:o2 + math.prod(s2)].view(s2)
+        """Layer k's tensors as views of `flat`, a flat tensor in this arena's layout."""
+        return tuple(flat[o:o + math.prod(s)].view(s) for s, o in zip(self._shapes[k], self.offsets[k]))
 
     def _name_views(self, flat, prefix):
-        pairs = [self.layer_views(flat, k) for k in range(len(self.dims))]
-        views = ([p[0] for p in pairs], [p[1] for p in pairs])
+        per_layer = [self.layer_views(flat, k) for k in range(len(self.dims))]
+        views = tuple([v[j] if j < len(v) else None for v in per_layer] for j in range(len(self.names)))
         for name, v in zip(self.names, views):
             setattr(self, prefix + name, v)
         return views
@@ -71,13 +84,17 @@ class FlatArena(object):
         self.step = 0
 
     def load(self, params):
-        """params = [(tensor 1, tensor 2)] numpy arrays or tensors."""
-        for k, pair in enumerate(params):
-            for view, t in zip((self.views[0][k], self.views[1][k]), pair):
+        """params = per layer its tensors (layer_views order), numpy arrays or tensors."""
+        for k, group in enumerate(params):
+            views = self.layer_views(self.params, k)
+            if len(group) != len(views):
+                raise ValueError('gist_amd: layer %d takes %d tensors, got %d' % (k, len(views), len(group)))
+            for view, t in zip(views, group):
                 view.copy_(torch.as_tensor(t).reshape(view.shape).to(self.device))
 
     def export(self):
-        return [tuple(t.detach().cpu().numpy().copy() for t in pair) for pair in zip(*self.views)]
+        return [tuple(v.detach().cpu().numpy().copy() for v in self.layer_views(self.params, k))
+                for k in range(len(self.dims))]
 
     @staticmethod
     def module_params(model):
@@ -86,16 +103,28 @@ class FlatArena(object):
 
     def param_views(self, flat=None):
         """Per Parameter of module_params, its block of `flat` -- a flat tensor in this arena's layout; None: `params`.
-        (Here: per layer tensor 1, then tensor 2.)"""
-        pairs = zip(*self.views) if flat is None else (self.layer_views(flat, k) for k in range(len(self.dims)))
-        return [v for pair in pairs for v in pair]
+        (Here: layer after layer, its tensors.)"""
+        flat = self.params if flat is None else flat
+        return [v for k in range(len(self.dims)) for v in self.layer_views(flat, k)]
+
+    def adopt_module(self, model):
+        """Re-home the parameters of the family's nn.Module into the arena, values preserved.  The Parameters keep their
+        identity (an optimiser built before keeps stepping them), names and state_dict keys; only their .data moves."""
+        views, params = self.param_views(), self.module_params(model)
+        if len(params) != len(views) or any(tuple(p.shape) != tuple(v.shape) for p, v in zip(params, views)):
+            raise ValueError('gist_amd: the model\'s layers do not match the arena\'s dims %s' % (self.dims,))
+        for p, v in zip(params, views):
+            if p.data_ptr() != v.data_ptr():
+                v.copy_(p.data.to(self.device))
+            p.data = v
+        return model
 
 
 class ParamArena(FlatArena):
     """GraphSAGE layers, dims = [(in, out)]: W [out, 2*in] and b [out]."""
     names = ('W', 'b')
 
-    def shapes(self, dim):
+    def shapes(self, dim, k):
         i, o = dim
         return (o, 2 * i), (o,)
 
@@ -107,14 +136,6 @@ class ParamArena(FlatArena):
     @staticmethod
     def module_params(gcn):
         return [p for layer in gcn.layers for p in (layer.linear.weight, layer.linear.bias)]
-
-    def adopt_module(self, gcn):
-        """Re-home an nn.Module GCN's parameters into the arena (values preserved)."""
-        for k, layer in enumerate(gcn.layers):
-            self.W[k].copy_(layer.linear.weight.data.to(self.device))
-            self.b[k].copy_(layer.linear.bias.data.to(self.device))
-            layer.linear.weight.data = self.W[k]
-            layer.linear.bias.data = self.b[k]
 
     def bind_module(self, gcn):
         """Record on `gcn`, weakly, that its parameters are this arena's views in this arena's layout (made so by its
@@ -129,85 +150,22 @@ def graphsage_dims(in_feats, n_hidden, n_classes, n_layers):
     return [(in_feats, n_hidden)] + [(n_hidden, n_hidden)] * (n_layers - 1) + [(n_hidden, n_classes)]
 
 
-class GraphSAGEArena(object):
+class GraphSAGEArena(FlatArena):
     """gist_amd.modules.GraphSAGE layers, dims = [(in, out)] (graphsage_dims): per layer W [out, 2*in] and b [out] and,
-    for every layer but the last (the output layer has no norm), the LayerNorm's gamma [out] and beta [out] -- one flat
-    fp32 tensor, layer after layer.  Unlike FlatArena's two-tensor layers, EVERY view starts on a 16-byte boundary (the
-    gaps are zero floats that Adam leaves zero): the three vectors of a layer never push its tail kernels off their
-    16-byte path, whatever the widths.  `W`, `b`, `gamma`, `beta` are the views of `params` (gamma / beta: None for the
-    output layer), after with_grads() `dW`, `db`, `dgamma`, `dbeta` those of `grads` at the same offsets."""
+    for every layer but the last (the output layer has no norm), the LayerNorm's gamma [out] and beta [out]; gamma /
+    beta (and dgamma / dbeta) are None for the output layer.  EVERY view starts on a 16-byte boundary: the three
+    vectors of a layer never push its tail kernels off their 16-byte path, whatever the widths."""
     names = ('W', 'b', 'gamma', 'beta')
-    ALIGN = 4                   # floats
+    ALIGN = 4
 
-    def __init__(self, dims, device):
-        self.dims = [(int(i), int(o)) for (i, o) in dims]
-        self.device = device
-        self._shapes, self.offsets = [], []
-        off = 0
-        for k, (i, o) in enumerate(self.dims):
-            shapes = [(o, 2 * i), (o,)] + ([(o,), (o,)] if k + 1 < len(self.dims) else [])
-            offs = []
-            for s in shapes:
-                off = (off + self.ALIGN - 1) // self.ALIGN * self.ALIGN
-                offs.append(off)
-                off += math.prod(s)
-            self._shapes.append(shapes)
-            self.offsets.append(tuple(offs))
-        self.numel = (off + self.ALIGN - 1) // self.ALIGN * self.ALIGN
-        self.params = torch.zeros(self.numel, dtype=torch.float32, device=device)
-        self._name_views(self.params, '')
+    def shapes(self, dim, k):
+        i, o = dim
+        return ((o, 2 * i), (o,)) + (((o,), (o,)) if k + 1 < len(self.dims) else ())
+
+    def _init_params(self):
         for g in self.gamma:
             if g is not None:
                 g.fill_(1.0)                # nn.LayerNorm's initial weight
-        self.grads = self.exp_avg = self.exp_avg_sq = None
-        for name in self.names:
-            setattr(self, 'd' + name, [])
-        self.step = 0
-
-    def layer_views(self, flat, k):
-        """Layer k's (W, b, gamma, beta) -- (W, b) for the output layer -- as views of `flat`, a flat tensor in this
-        arena's layout."""
-        return tuple(flat[o:o + math.prod(s)].view(s) for s, o in zip(self._shapes[k], self.offsets[k]))
-
-    def _name_views(self, flat, prefix):
-        per_layer = [self.layer_views(flat, k) for k in range(len(self.dims))]
-        for j, name in enumerate(self.names):
-            setattr(self, prefix + name, [v[j] if j < len(v) else None for v in per_layer])
-        return per_layer
-
-    def with_grads(self):
-        """Allocate (once) the flat gradient and Adam-moment arenas beside `params` and the 'd' + name views over the
-        gradient arena.  The parameters are not touched."""
-        if self.grads is None:
-            self.grads = torch.zeros_like(self.params)
-            self.exp_avg = torch.zeros_like(self.params)
-            self.exp_avg_sq = torch.zeros_like(self.params)
-            self._name_views(self.grads, 'd')
-        return self
-
-    def reset_optimizer(self):
-        if self.grads is not None:
-            self.exp_avg.zero_()
-            self.exp_avg_sq.zero_()
-        self.step = 0
-
-    def param_views(self, flat=None):
-        """Per Parameter of module_params, its block of `flat` (None: `params`)."""
-        flat = self.params if flat is None else flat
-        return [v for k in range(len(self.dims)) for v in self.layer_views(flat, k)]
-
-    def load(self, params):
-        """params = per layer (W, b, gamma, beta) -- (W, b) for the output layer -- numpy arrays or tensors."""
-        for k, group in enumerate(params):
-            views = self.layer_views(self.params, k)
-            if len(group) != len(views):
-                raise ValueError('gist_amd: layer %d takes %d tensors, got %d' % (k, len(views), len(group)))
-            for view, t in zip(views, group):
-                view.copy_(torch.as_tensor(t).reshape(view.shape).to(self.device))
-
-    def export(self):
-        return [tuple(v.detach().cpu().numpy().copy() for v in self.layer_views(self.params, k))
-                for k in range(len(self.dims))]
 
     @staticmethod
     def module_params(model):
@@ -219,18 +177,6 @@ class GraphSAGEArena(object):
             if isinstance(layer.lynorm, nn.LayerNorm):
                 out += [layer.lynorm.weight, layer.lynorm.bias]
         return out
-
-    def adopt_module(self, model):
-        """Re-home a gist_amd.modules.GraphSAGE's parameters into the arena, values preserved.  The Parameters keep their
-        identity, names and state_dict keys; only their .data moves."""
-        views, params = self.param_views(), self.module_params(model)
-        if len(params) != len(views) or any(tuple(p.shape) != tuple(v.shape) for p, v in zip(params, views)):
-            raise ValueError('gist_amd: the model\'s layers do not match the arena\'s dims %s' % (self.dims,))
-        for p, v in zip(params, views):
-            if p.data_ptr() != v.data_ptr():
-                v.copy_(p.data.to(self.device))
-            p.data = v
-        return model
 
 
 def gat_dims(in_feats, n_hidden, n_classes, n_layers, n_heads, merge='mean'):
@@ -257,7 +203,7 @@ class GATArena(FlatArena):
     after with_grads() (gist_amd.gat_engine.GATEngine)."""
     names = ('W', 'A')
 
-    def shapes(self, dim):
+    def shapes(self, dim, k):
         i, o, nh = dim
         return (nh * o, i), (nh, 2 * o)
 
@@ -288,14 +234,3 @@ class GATArena(FlatArena):
     @staticmethod
     def module_params(gat):
         return [p for layer in gat.layers for head in layer.heads for p in (head.fc.weight, head.attn_fc.weight)]
-
-    def adopt_module(self, gat):
-        """Re-home a gist_amd.modules.GAT's parameters onto their per-head rows of the arena, values preserved.  The
-        Parameters keep their identity (an optimiser built before the binding keeps stepping them); only their .data
-        moves."""
-        views, params = self.head_views(), self.module_params(gat)
-        assert len(params) == len(views)
-        for p, v in zip(params, views):
-            if p.data_ptr() != v.data_ptr():
-                v.copy_(p.data.to(self.device))
-            p.data = v

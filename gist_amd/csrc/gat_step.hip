@@ -22,8 +22,7 @@ int64_t out_width(const gist_gat_step_plan *p, int k) {
 
 // layer count and shapes only: what the size helpers and the step both need before they look at a pointer
 bool shapes_ok(const gist_gat_step_plan *p) {
-    if (p == nullptr || p->n_layers < 1 || p->n_layers > GIST_MAX_LAYERS || p->n_max <= 0 || p->n_max >= (1LL << 31))
-        return false;
+    if (!plan_sizes_ok(p)) return false;
     for (int k = 0; k < p->n_layers; ++k) {
         const gist_gat_layer_desc &l = p->layer[k];
         if (l.n_in < 1 || l.n_out < 1 || l.heads < 1 || l.heads * l.n_out >= (1LL << 22) || l.n_in >= (1LL << 22))
@@ -34,8 +33,7 @@ bool shapes_ok(const gist_gat_step_plan *p) {
     return true;
 }
 
-// the three projections of layer k on a batch of n rows as (m, n, k) of gist_gemm_{nt,tn,nn}_f32
-struct GemmShape { int64_t m, n, k; };
+// the three projections of layer k on a batch of n rows
 void layer_gemms(const gist_gat_layer_desc &l, int64_t n, GemmShape (&g)[3]) {
     const int64_t hf = l.heads * l.n_out;
     g[0] = GemmShape{n, hf, l.n_in};      // Z = x . W^T
@@ -44,21 +42,9 @@ void layer_gemms(const gist_gat_layer_desc &l, int64_t n, GemmShape (&g)[3]) {
 }
 }  // namespace
 
-// Bytes of gist_gat_step_plan.workspace: the largest gist_gemm_workspace_bytes over every projection of every layer and
-// every batch size up to n_max (the split-K choice is not monotone in the row count).  Host function.
+// Bytes of gist_gat_step_plan.workspace (step_host.h, step_workspace_bytes).  Host function.
 extern "C" int64_t gist_gat_step_workspace_bytes(const gist_gat_step_plan *p) {
-    if (!shapes_ok(p)) return 0;
-    int64_t need = 0;
-    for (int k = 0; k < p->n_layers; ++k)
-        for (int64_t n = 1; n <= p->n_max; ++n) {
-            GemmShape g[3];
-            layer_gemms(p->layer[k], n, g);
-            for (int q = 0; q < (k > 0 ? 3 : 2); ++q) {
-                const int64_t b = gist_gemm_workspace_bytes(g[q].m, g[q].n, g[q].k);
-                need = b > need ? b : need;
-            }
-        }
-    return need;
+    return shapes_ok(p) ? step_workspace_bytes(p, layer_gemms) : 0;
 }
 
 // Floats of gist_gat_step_plan.attn_partials: the widest layer's gist_gat_attn_grad_workspace_floats at n_max rows.
@@ -78,7 +64,6 @@ namespace {
 enum { RUN_FORWARD = 1, RUN_BACKWARD = 2, RUN_OPTIMIZER = 4 };
 
 // One call's decisions, made once by validate() before any device work and read by the phase functions.
-struct Ws { void *p; int64_t bytes; };
 struct Call {
     const gist_gat_step_plan *p;
     const int32_t *ids;
@@ -94,38 +79,11 @@ struct Call {
 // point in the messages; phase_call: the flags are gist_gat_step_phase's (one phase bit, GIST_STEP_TRAIN).
 int validate(const char *who, const gist_gat_step_plan *p, const int32_t *ids, int64_t n, int64_t adam_step, int flags,
              int run, bool phase_call, gist_stream_t s, Call &c) {
-    GIST_REQUIRE(p != nullptr, "%s: null plan", who);
-    GIST_REQUIRE(p->n_layers >= 1 && p->n_layers <= GIST_MAX_LAYERS, "%s: bad n_layers", who);
-    GIST_REQUIRE(shapes_ok(p), "%s: bad layer shapes or n_max", who);
-    GIST_REQUIRE(n > 0, "%s: empty batch", who);
-    GIST_REQUIRE(n <= p->n_max, "%s: batch of %lld rows exceeds n_max = %lld", who, (long long)n, (long long)p->n_max);
-    const int phases = GIST_STEP_PHASE_FORWARD | GIST_STEP_PHASE_BACKWARD | GIST_STEP_PHASE_OPTIMIZER;
-    int known = GIST_STEP_EXTRACT | GIST_STEP_TRAIN | GIST_STEP_EXTRACT_NEXT | GIST_STEP_PREEXTRACTED;
-    if (phase_call) {
-        known |= phases | GIST_STEP_DLOGITS_GIVEN;
-        const int ph = flags & phases;
-        GIST_REQUIRE(ph != 0, "%s: no GIST_STEP_PHASE_* bit (the whole iteration in one call is gist_gat_step)", who);
-        GIST_REQUIRE((ph & (ph - 1)) == 0, "%s: more than one GIST_STEP_PHASE_* bit (one phase per call)", who);
-        GIST_REQUIRE(flags & GIST_STEP_TRAIN, "%s: a phase call needs GIST_STEP_TRAIN (forward only: gist_gat_step)", who);
-        GIST_REQUIRE(!(flags & GIST_STEP_DLOGITS_GIVEN) || ph == GIST_STEP_PHASE_BACKWARD,
-                     "%s: GIST_STEP_DLOGITS_GIVEN belongs to GIST_STEP_PHASE_BACKWARD", who);
-    } else {
-        GIST_REQUIRE(!(flags & (phases | GIST_STEP_DLOGITS_GIVEN)),
-                     "%s: GIST_STEP_PHASE_* / GIST_STEP_DLOGITS_GIVEN are not supported (one call per iteration; the "
-                     "phase calls are gist_gat_step_phase)", who);
-    }
-    GIST_REQUIRE((flags & ~known) == 0, "%s: unknown flag bits", who);
-    GIST_REQUIRE(!((flags & GIST_STEP_EXTRACT) && (flags & GIST_STEP_PREEXTRACTED)),
-                 "%s: GIST_STEP_EXTRACT and GIST_STEP_PREEXTRACTED exclude each other", who);
-    const bool train = (flags & GIST_STEP_TRAIN) != 0;
-    GIST_REQUIRE(!(flags & (GIST_STEP_EXTRACT_NEXT | GIST_STEP_PREEXTRACTED)) || train,
-                 "%s: GIST_STEP_EXTRACT_NEXT / GIST_STEP_PREEXTRACTED belong to training steps", who);
+    GIST_TRY(check_plan(who, p, shapes_ok(p), n));
+    GIST_TRY(check_flags(who, flags, phase_call, phase_call ? "gist_gat_step" : "gist_gat_step_phase"));
     const int L = p->n_layers;
     const bool fwd = (run & RUN_FORWARD) != 0, bwd = (run & RUN_BACKWARD) != 0, opt = (run & RUN_OPTIMIZER) != 0;
-    if (fwd || bwd)
-        GIST_REQUIRE(p->x0 && p->rowptr && p->col && p->t_rowptr && p->t_col && p->labels && p->dlogits && p->row_loss &&
-                         p->loss,
-                     "%s: null batch / loss buffer", who);
+    if (fwd || bwd) GIST_TRY(check_batch_buffers(who, p, p->x0 != nullptr));
     for (int k = 0; (fwd || bwd) && k < L; ++k) {
         const gist_gat_layer_desc &l = p->layer[k];
         GIST_REQUIRE(l.W && l.A && l.Z && l.out && l.s_src && l.s_dst && l.m && l.l, "%s: null buffer in layer %d", who, k);
@@ -134,70 +92,31 @@ int validate(const char *who, const gist_gat_step_plan *p, const int32_t *ids, i
     if (bwd)
         GIST_REQUIRE(p->dZ && p->g && p->ds_dst && p->dd && p->ds_src && (L == 1 || (p->d_out[0] && p->d_out[1])),
                      "%s: null backward scratch", who);
-    if (opt) {
-        GIST_REQUIRE(p->params && p->grads && p->exp_avg && p->exp_avg_sq && p->n_params > 0, "%s: null arena", who);
-        GIST_REQUIRE(adam_step >= 1, "%s: adam_step is 1-based", who);
-    }
+    if (opt) GIST_TRY(check_arena(who, p, adam_step));
     if (bwd)
         GIST_REQUIRE(p->attn_partial_floats >= 0 && (p->attn_partials || p->attn_partial_floats == 0),
                      "%s: bad attn_partials", who);
     c.p = p; c.ids = ids; c.n = n; c.flags = flags; c.s = s; c.st = as_stream(s);
-    c.by_parts = p->node_part && p->part_slot && p->extract_scratch && p->batch_index >= 0 &&
-                 gist_extract_parts_supported(p->n_max) == 1;
-    if (fwd && (flags & GIST_STEP_EXTRACT)) {
-        GIST_REQUIRE(ids != nullptr, "%s: null ids", who);
-        GIST_REQUIRE(p->g_rowptr && p->g_col && p->g_t_rowptr && p->g_t_col && p->feat && p->norm &&
-                         p->ld_feat >= p->layer[0].n_in && p->col_capacity >= 0,
-                     "%s: null / bad resident graph", who);
-        GIST_REQUIRE(c.by_parts || p->remap != nullptr, "%s: extraction needs the part tables or remap", who);
-    }
-    if (opt && (flags & GIST_STEP_EXTRACT_NEXT))
-        GIST_REQUIRE(p->node_part && p->part_slot && p->extract_scratch && p->next_ids && p->next_batch_index >= 0 &&
-                         p->next_n > 0 && p->next_n <= p->n_max && gist_extract_parts_supported(p->n_max) == 1 &&
-                         p->g_rowptr && p->g_col && p->g_t_rowptr && p->g_t_col && p->feat && p->norm && p->x0 &&
-                         p->rowptr && p->col && p->t_rowptr && p->t_col && p->labels,
-                     "%s: GIST_STEP_EXTRACT_NEXT needs the part tables, the scratch and next_*", who);
-    // every projection gets what the op-level wrappers give it (the split-K choice depends on the bytes): nothing where
-    // gist_gemm_workspace_bytes says 0, the plan's workspace otherwise
+    c.by_parts = extracts_by_parts(p);
+    if (fwd && (flags & GIST_STEP_EXTRACT))
+        GIST_TRY(check_extract(who, p, ids, c.by_parts, p->norm && p->ld_feat >= p->layer[0].n_in, ""));
+    if (opt && (flags & GIST_STEP_EXTRACT_NEXT))      // (it writes every batch buffer the next forward reads)
+        GIST_TRY(check_extract_next(who, p, p->norm && p->x0 && p->rowptr && p->col && p->t_rowptr && p->t_col && p->labels));
     for (int k = 0; k < L; ++k) {
         GemmShape g[3];
         layer_gemms(p->layer[k], n, g);
-        for (int q = 0; q < 3; ++q) {
-            const bool runs = q == 0 ? fwd : (bwd && (q == 1 || k > 0));      // (layer 0 has no dx projection)
-            const int64_t need = runs ? gist_gemm_workspace_bytes(g[q].m, g[q].n, g[q].k) : 0;
-            if (need > 0 && (p->workspace == nullptr || p->workspace_bytes < need)) {
-                set_error("%s: workspace too small (%lld < %lld bytes)", who, (long long)p->workspace_bytes,
-                          (long long)need);
-                return GIST_ENOSPACE;
-            }
-            c.ws[k][q] = need > 0 ? Ws{p->workspace, p->workspace_bytes} : Ws{nullptr, 0};
-        }
-        if (bwd) {
-            const int64_t need = gist_gat_attn_grad_workspace_floats(n, p->layer[k].heads, p->layer[k].n_out);
-            if (need > p->attn_partial_floats) {
-                set_error("%s: attn_partials too small (%lld < %lld floats)", who, (long long)p->attn_partial_floats,
-                          (long long)need);
-                return GIST_ENOSPACE;
-            }
-        }
+        GIST_TRY(pick_workspaces(who, p, k, g, fwd, bwd, c.ws[k]));
+        if (bwd)
+            GIST_TRY(enough(who, "attn_partials", p->attn_partial_floats,
+                            gist_gat_attn_grad_workspace_floats(n, p->layer[k].heads, p->layer[k].n_out), "floats"));
     }
     return GIST_OK;
 }
 
-// ---- extraction ---------------------------------------------------------------------------------------
+// the features go to x0, dense
 int extract(const Call &c) {
-    const gist_gat_step_plan *p = c.p;
-    if (!(c.flags & GIST_STEP_EXTRACT)) return GIST_OK;
-    const gist_gat_layer_desc &l0 = p->layer[0];
-    if (c.by_parts) {
-        const gist_extract_parts_desc x = parts_desc(p, c.ids, c.n, p->batch_index, l0.n_in, p->x0, l0.n_in);
-        GIST_TRY(gist_extract_parts_desc_batch(&x, c.s));
-    } else {
-        GIST_TRY(gist_extract_batch(p->g_rowptr, p->g_col, p->g_t_rowptr, p->g_t_col, c.ids, c.n, p->remap, p->rowptr,
-                                    p->col, p->t_rowptr, p->t_col, p->col_capacity, p->norm, p->feat, p->ld_feat,
-                                    l0.n_in, p->x0, l0.n_in, p->labels_all, p->labels, c.s));
-    }
-    return GIST_OK;
+    const int64_t f = c.p->layer[0].n_in;
+    return gist::extract(c.p, c.by_parts, c.flags, c.ids, c.n, f, c.p->x0, f, c.s);
 }
 
 // ---- forward (modules.GAT.forward: h = F.elu(layer(g, h)) for every layer, the last included), then the mean CE over
@@ -267,18 +186,10 @@ int backward(const Call &c) {
     return GIST_OK;
 }
 
-// ---- one optimiser launch over the arena; with EXTRACT_NEXT the next batch is extracted in its grid -----
-int optimise(const Call &c, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t adam_step) {
-    const gist_gat_step_plan *p = c.p;
-    if (c.flags & GIST_STEP_EXTRACT_NEXT) {
-        const gist_extract_parts_desc x = parts_desc(p, p->next_ids, p->next_n, p->next_batch_index, p->layer[0].n_in, p->x0,
-                                                     p->layer[0].n_in);
-        return gist_adam_segments_extract_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1,
-                                              beta2, eps, weight_decay, adam_step, nullptr, 0, nullptr, 0, 0, nullptr,
-                                              &x, c.s);
-    }
-    return gist_adam_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1, beta2, eps,
-                         weight_decay, adam_step, c.s);
+// the optimiser launch; with GIST_STEP_EXTRACT_NEXT the next batch's features go to x0 as well
+int optimise(const Call &c, const AdamHyper &a) {
+    const int64_t f = c.p->layer[0].n_in;
+    return gist::optimise(c.p, c.flags, f, c.p->x0, f, a, c.s);
 }
 }  // namespace
 
@@ -293,7 +204,7 @@ extern "C" int gist_gat_step(const gist_gat_step_plan *p, const int32_t *ids, in
     GIST_TRY(forward(c));
     if (!(run & RUN_BACKWARD)) return GIST_OK;
     GIST_TRY(backward(c));
-    return optimise(c, lr, beta1, beta2, eps, weight_decay, adam_step);
+    return optimise(c, AdamHyper{lr, beta1, beta2, eps, weight_decay, adam_step});
 }
 
 // One third of gist_gat_step's iteration: the functions above, one phase per call (include/gist_hip.h).  No state is
@@ -311,5 +222,5 @@ extern "C" int gist_gat_step_phase(const gist_gat_step_plan *p, const int32_t *i
         GIST_TRY(extract(c));
         return forward(c);
     }
-    return run == RUN_BACKWARD ? backward(c) : optimise(c, lr, beta1, beta2, eps, weight_decay, adam_step);
+    return run == RUN_BACKWARD ? backward(c) : optimise(c, AdamHyper{lr, beta1, beta2, eps, weight_decay, adam_step});
 }

@@ -13,12 +13,9 @@ using namespace gist;
 namespace {
 constexpr float kLnEps = 1e-5f;      // nn.LayerNorm's default, modules.py:120
 
-int64_t round_up2(int64_t x) { return x + (x & 1); }
-
 // layer count and shapes only: what the size helpers and the step both need before they look at a pointer
 bool shapes_ok(const gist_graphsage_step_plan *p) {
-    if (p == nullptr || p->n_layers < 1 || p->n_layers > GIST_MAX_LAYERS || p->n_max <= 0 || p->n_max >= (1LL << 31))
-        return false;
+    if (!plan_sizes_ok(p)) return false;
     for (int k = 0; k < p->n_layers; ++k) {
         const gist_graphsage_layer_desc &l = p->layer[k];
         if (l.n_in < 1 || l.n_out < 1 || l.n_in >= (1LL << 22) || l.n_out >= (1LL << 22)) return false;
@@ -27,8 +24,7 @@ bool shapes_ok(const gist_graphsage_step_plan *p) {
     return true;
 }
 
-// the three projections of layer k on a batch of n rows as (m, n, k) of gist_gemm_{nt,tn,nn}_f32
-struct GemmShape { int64_t m, n, k; };
+// the three projections of layer k on a batch of n rows
 void layer_gemms(const gist_graphsage_layer_desc &l, int64_t n, GemmShape (&g)[3]) {
     g[0] = GemmShape{n, l.n_out, 2 * l.n_in};      // Y = Z . W^T
     g[1] = GemmShape{l.n_out, 2 * l.n_in, n};      // dW = dY^T . Z
@@ -44,21 +40,9 @@ bool layer_folds(const gist_graphsage_step_plan *p, int k) {
 }
 }  // namespace
 
-// Bytes of gist_graphsage_step_plan.workspace: the largest gist_gemm_workspace_bytes over every projection of every
-// layer and every batch size up to n_max (the split-K choice is not monotone in the row count).  Host function.
+// Bytes of gist_graphsage_step_plan.workspace (step_host.h, step_workspace_bytes).  Host function.
 extern "C" int64_t gist_graphsage_step_workspace_bytes(const gist_graphsage_step_plan *p) {
-    if (!shapes_ok(p)) return 0;
-    int64_t need = 0;
-    for (int k = 0; k < p->n_layers; ++k)
-        for (int64_t n = 1; n <= p->n_max; ++n) {
-            GemmShape g[3];
-            layer_gemms(p->layer[k], n, g);
-            for (int q = 0; q < (k > 0 ? 3 : 2); ++q) {
-                const int64_t b = gist_gemm_workspace_bytes(g[q].m, g[q].n, g[q].k);
-                need = b > need ? b : need;
-            }
-        }
-    return need;
+    return shapes_ok(p) ? step_workspace_bytes(p, layer_gemms) : 0;
 }
 
 // Floats of gist_graphsage_step_plan.ln_workspace: the widest hidden layer's gist_ln_affine_bwd_workspace_floats at
@@ -80,7 +64,6 @@ extern "C" int gist_graphsage_step_folds(const gist_graphsage_step_plan *p, int3
 
 namespace {
 // One call's decisions, made once by validate() before any device work and read by the phase functions.
-struct Ws { void *p; int64_t bytes; };
 struct Call {
     const gist_graphsage_step_plan *p;
     const int32_t *ids;
@@ -102,28 +85,12 @@ struct Call {
 int validate(const gist_graphsage_step_plan *p, const int32_t *ids, int64_t n, uint64_t drop_offset, int64_t adam_step,
              int flags, gist_stream_t s, Call &c) {
     const char *who = "gist_graphsage_step";
-    GIST_REQUIRE(p != nullptr, "%s: null plan", who);
-    GIST_REQUIRE(p->n_layers >= 1 && p->n_layers <= GIST_MAX_LAYERS,
-                 "%s: bad n_layers (1 .. GIST_MAX_LAYERS = %d, the output layer included)", who, GIST_MAX_LAYERS);
-    GIST_REQUIRE(shapes_ok(p), "%s: bad layer shapes (a layer's n_in must be its predecessor's n_out) or n_max", who);
-    GIST_REQUIRE(n > 0, "%s: empty batch", who);
-    GIST_REQUIRE(n <= p->n_max, "%s: batch of %lld rows exceeds n_max = %lld", who, (long long)n, (long long)p->n_max);
-    const int phases = GIST_STEP_PHASE_FORWARD | GIST_STEP_PHASE_BACKWARD | GIST_STEP_PHASE_OPTIMIZER;
-    const int known = GIST_STEP_EXTRACT | GIST_STEP_TRAIN | GIST_STEP_EXTRACT_NEXT | GIST_STEP_PREEXTRACTED;
-    GIST_REQUIRE(!(flags & (phases | GIST_STEP_DLOGITS_GIVEN)),
-                 "%s: GIST_STEP_PHASE_* / GIST_STEP_DLOGITS_GIVEN are not supported (one call per iteration; this step "
-                 "has no phase calls)", who);
-    GIST_REQUIRE((flags & ~known) == 0, "%s: unknown flag bits", who);
-    GIST_REQUIRE(!((flags & GIST_STEP_EXTRACT) && (flags & GIST_STEP_PREEXTRACTED)),
-                 "%s: GIST_STEP_EXTRACT and GIST_STEP_PREEXTRACTED exclude each other", who);
+    GIST_TRY(check_plan(who, p, shapes_ok(p), n));
+    GIST_TRY(check_flags(who, flags, false, nullptr));
     const bool train = (flags & GIST_STEP_TRAIN) != 0;
-    GIST_REQUIRE(!(flags & (GIST_STEP_EXTRACT_NEXT | GIST_STEP_PREEXTRACTED)) || train,
-                 "%s: GIST_STEP_EXTRACT_NEXT / GIST_STEP_PREEXTRACTED belong to training steps", who);
     GIST_REQUIRE(p->p_drop >= 0.f && p->p_drop < 1.f, "%s: p_drop must be in [0,1)", who);
     const int L = p->n_layers;
-    GIST_REQUIRE(p->rowptr && p->col && p->t_rowptr && p->t_col && p->norm && p->labels && p->dlogits && p->row_loss &&
-                     p->loss,
-                 "%s: null batch / loss buffer", who);
+    GIST_TRY(check_batch_buffers(who, p, p->norm != nullptr));
     for (int k = 0; k < L; ++k) {
         const gist_graphsage_layer_desc &l = p->layer[k];
         const bool hidden = k + 1 < L;
@@ -139,8 +106,7 @@ int validate(const gist_graphsage_step_plan *p, const int32_t *ids, int64_t n, u
     GIST_REQUIRE(p->row_blocks == nullptr || p->n_row_blocks > 0, "%s: row_blocks given but n_row_blocks <= 0", who);
     if (train) {
         GIST_REQUIRE(p->partials && (L == 1 || p->dZ), "%s: null backward scratch", who);
-        GIST_REQUIRE(p->params && p->grads && p->exp_avg && p->exp_avg_sq && p->n_params > 0, "%s: null arena", who);
-        GIST_REQUIRE(adam_step >= 1, "%s: adam_step is 1-based", who);
+        GIST_TRY(check_arena(who, p, adam_step));
         GIST_REQUIRE(p->ln_workspace_floats >= 0 && (p->ln_workspace || p->ln_workspace_floats == 0),
                      "%s: bad ln_workspace", who);
     }
@@ -149,51 +115,26 @@ int validate(const gist_graphsage_step_plan *p, const int32_t *ids, int64_t n, u
     c.layer0_aggregates = !(p->use_pp && train);
     const int64_t F = p->layer[0].n_in;
     c.n_feat = c.layer0_aggregates ? F : 2 * F;
-    c.by_parts = p->node_part && p->part_slot && p->extract_scratch && p->batch_index >= 0 &&
-                 gist_extract_parts_supported(p->n_max) == 1;
-    if (flags & GIST_STEP_EXTRACT) {
-        GIST_REQUIRE(ids != nullptr, "%s: null ids", who);
-        GIST_REQUIRE(p->g_rowptr && p->g_col && p->g_t_rowptr && p->g_t_col && p->feat && p->ld_feat >= c.n_feat &&
-                         p->col_capacity >= 0,
-                     "%s: null / bad resident graph (with use_pp the features are 2 * n_in wide)", who);
-        GIST_REQUIRE(c.by_parts || p->remap != nullptr, "%s: extraction needs the part tables or remap", who);
-    }
-    if (flags & GIST_STEP_EXTRACT_NEXT)
-        GIST_REQUIRE(p->node_part && p->part_slot && p->extract_scratch && p->next_ids && p->next_batch_index >= 0 &&
-                         p->next_n > 0 && p->next_n <= p->n_max && gist_extract_parts_supported(p->n_max) == 1 &&
-                         p->g_rowptr && p->g_col && p->g_t_rowptr && p->g_t_col && p->feat && p->ld_feat >= c.n_feat,
-                     "%s: GIST_STEP_EXTRACT_NEXT needs the part tables, the scratch and next_*", who);
+    c.by_parts = extracts_by_parts(p);
+    if (flags & GIST_STEP_EXTRACT)
+        GIST_TRY(check_extract(who, p, ids, c.by_parts, p->ld_feat >= c.n_feat,
+                               " (with use_pp the features are 2 * n_in wide)"));
+    if (flags & GIST_STEP_EXTRACT_NEXT) GIST_TRY(check_extract_next(who, p, p->ld_feat >= c.n_feat));
     // the dropout counter space of this step and which layers fold their mask into their producers
     uint64_t off = drop_offset;
     for (int k = 0; k < L; ++k) {
         c.offs[k] = off;
-        off += (uint64_t)round_up2(n * 2 * p->layer[k].n_in);
+        off += round_up2((uint64_t)n * 2 * p->layer[k].n_in);
         c.folds[k] = train && layer_folds(p, k);
     }
     c.folds[L] = false;
-    // every projection gets what the op-level wrappers give it (the split-K choice depends on the bytes): nothing where
-    // gist_gemm_workspace_bytes says 0, the plan's workspace otherwise
     for (int k = 0; k < L; ++k) {
         GemmShape g[3];
         layer_gemms(p->layer[k], n, g);
-        for (int q = 0; q < 3; ++q) {
-            const bool runs = q == 0 || (train && (q == 1 || k > 0));      // (layer 0 has no dZ projection)
-            const int64_t need = runs ? gist_gemm_workspace_bytes(g[q].m, g[q].n, g[q].k) : 0;
-            if (need > 0 && (p->workspace == nullptr || p->workspace_bytes < need)) {
-                set_error("%s: workspace too small (%lld < %lld bytes)", who, (long long)p->workspace_bytes,
-                          (long long)need);
-                return GIST_ENOSPACE;
-            }
-            c.ws[k][q] = need > 0 ? Ws{p->workspace, p->workspace_bytes} : Ws{nullptr, 0};
-        }
-        if (train && k + 1 < L) {
-            const int64_t need = gist_ln_affine_bwd_workspace_floats(n, p->layer[k].n_out);
-            if (need > p->ln_workspace_floats) {
-                set_error("%s: ln_workspace too small (%lld < %lld floats)", who, (long long)p->ln_workspace_floats,
-                          (long long)need);
-                return GIST_ENOSPACE;
-            }
-        }
+        GIST_TRY(pick_workspaces(who, p, k, g, true, train, c.ws[k]));
+        if (train && k + 1 < L)
+            GIST_TRY(enough(who, "ln_workspace", p->ln_workspace_floats,
+                            gist_ln_affine_bwd_workspace_floats(n, p->layer[k].n_out), "floats"));
     }
     return GIST_OK;
 }
@@ -208,22 +149,6 @@ int aggregate(const Call &c, const int32_t *rowptr, const int32_t *col, const fl
         return gist_spmm_csr_blocked_f32(rowptr, col, x, ldx, y, ldy, c.n, d, out_scale, src_scale, accumulate,
                                          p->row_blocks, p->n_row_blocks, c.s);
     return gist_spmm_csr_f32(rowptr, col, x, ldx, y, ldy, c.n, d, out_scale, src_scale, accumulate, c.s);
-}
-
-// ---- extraction: the features into Z_0's left half, or (use_pp while training) [X | A^X] into all of it ----
-int extract(const Call &c) {
-    const gist_graphsage_step_plan *p = c.p;
-    if (!(c.flags & GIST_STEP_EXTRACT)) return GIST_OK;
-    const gist_graphsage_layer_desc &l0 = p->layer[0];
-    if (c.by_parts) {
-        const gist_extract_parts_desc x = parts_desc(p, c.ids, c.n, p->batch_index, c.n_feat, l0.Z, 2 * l0.n_in);
-        GIST_TRY(gist_extract_parts_desc_batch(&x, c.s));
-    } else {
-        GIST_TRY(gist_extract_batch(p->g_rowptr, p->g_col, p->g_t_rowptr, p->g_t_col, c.ids, c.n, p->remap, p->rowptr,
-                                    p->col, p->t_rowptr, p->t_col, p->col_capacity, p->norm, p->feat, p->ld_feat,
-                                    c.n_feat, l0.Z, 2 * l0.n_in, p->labels_all, p->labels, c.s));
-    }
-    return GIST_OK;
 }
 
 // ---- forward (modules.py:133-147 per layer, :185-189), then the mean CE over the batch rows and its gradient ----
@@ -296,20 +221,6 @@ int backward(const Call &c) {
     }
     return GIST_OK;
 }
-
-// ---- one optimiser launch over the arena; with EXTRACT_NEXT the next batch is extracted in its grid -----
-int optimise(const Call &c, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t adam_step) {
-    const gist_graphsage_step_plan *p = c.p;
-    if (c.flags & GIST_STEP_EXTRACT_NEXT) {
-        const gist_extract_parts_desc x = parts_desc(p, p->next_ids, p->next_n, p->next_batch_index, c.n_feat,
-                                                     p->layer[0].Z, 2 * p->layer[0].n_in);
-        return gist_adam_segments_extract_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1,
-                                              beta2, eps, weight_decay, adam_step, nullptr, 0, nullptr, 0, 0, nullptr,
-                                              &x, c.s);
-    }
-    return gist_adam_f32(p->params, p->grads, p->exp_avg, p->exp_avg_sq, p->n_params, lr, beta1, beta2, eps,
-                         weight_decay, adam_step, c.s);
-}
 }  // namespace
 
 extern "C" int gist_graphsage_step(const gist_graphsage_step_plan *p, const int32_t *ids, int64_t n,
@@ -318,9 +229,12 @@ extern "C" int gist_graphsage_step(const gist_graphsage_step_plan *p, const int3
     Call c;
     GIST_TRY(validate(p, ids, n, drop_offset, adam_step, flags, s, c));
     ActiveTimer active(p->timer);
-    GIST_TRY(extract(c));
+    // the features into Z_0's left half, or (use_pp while training) [X | A^X] into all of it
+    float *z0 = p->layer[0].Z;
+    const int64_t ldz0 = 2 * p->layer[0].n_in;
+    GIST_TRY(extract(p, c.by_parts, flags, ids, n, c.n_feat, z0, ldz0, s));
     GIST_TRY(forward(c));
     if (!c.train) return GIST_OK;
     GIST_TRY(backward(c));
-    return optimise(c, lr, beta1, beta2, eps, weight_decay, adam_step);
+    return optimise(p, flags, c.n_feat, z0, ldz0, AdamHyper{lr, beta1, beta2, eps, weight_decay, adam_step}, s);
 }

@@ -13,8 +13,6 @@
 
 using namespace gist;
 
-static inline uint64_t round_up2(uint64_t x) { return x + (x & 1ULL); }
-
 // ---- HIP-event timer ------------------------------------------------------------------
 struct gist_timer {
     int64_t capacity, count;

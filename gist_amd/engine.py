@@ -120,10 +120,16 @@ _BARRIER_TIMEOUT = ('gist_amd: gist_extract_parts_batch timed out at its grid ba
 
 
 class StepEngine(object):
-    """What SageEngine and GATEngine share around their one-call steps: the graph and batch-buffer part of the plan, the
-    start and the end of a step, the one-launch extraction's scratch and error word, and the HIP-event step timer."""
+    """What SageEngine, GATEngine and GraphSAGEEngine share around their one-call steps: the graph, batch-buffer and arena
+    parts of the plan, the start and the end of a step, the next batch's extraction beside the optimiser, the dropout
+    counter, the one-launch extraction's scratch and error word, and the HIP-event step timer."""
 
-    def __init__(self, device, n_max):
+    def __init__(self, device, n_max, n_layers=0):
+        who = type(self).__name__
+        if n_max is None or int(n_max) <= 0:
+            raise ValueError('gist_amd: %s needs n_max > 0 (the iterator\'s n_max)' % who)
+        if n_layers > _lib.GIST_MAX_LAYERS:
+            raise ValueError('gist_amd: more than %d %s layers' % (_lib.GIST_MAX_LAYERS, who[:-len('Engine')]))
         self.device, self.n_max = device, int(n_max)
         self.plan = self._plan_keep = None      # the native step plan (attach_batcher) and every buffer it points into
         # True: a training step's optimiser launch also extracts the NEXT batch of the epoch into the batch buffers
@@ -146,6 +152,69 @@ class StepEngine(object):
         P.t_rowptr, P.t_col = batcher.t_rowptr.data_ptr(), batcher.t_col.data_ptr()
         P.col_capacity = batcher.col.numel()
         P.norm, P.labels = batcher.norm.data_ptr(), batcher.lab.data_ptr()
+
+    def _bind_arena(self, P):
+        """The arena's five fields of a plan."""
+        A = self.arena
+        P.params, P.grads = A.params.data_ptr(), A.grads.data_ptr()
+        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
+        P.n_params = A.numel
+
+    def _finish_plan(self, P, batcher, workspace_bytes, keep):
+        """The end of GATEngine's and GraphSAGEEngine's attach_batcher.  The split-K scratch of the projections: each gets
+        what hip._ws_for(m, n, k) gives the op-level call (nothing where the library asks for nothing), so the split
+        decisions -- and the bits -- are the op-by-op sequence's.  keep: the family's buffers the plan points into."""
+        self._ws = torch.empty(max(int(workspace_bytes), 1 << 20), dtype=torch.uint8, device=self.device)
+        P.workspace, P.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
+        self._bind_arena(P)
+        if batcher.n_max > self.n_max:
+            raise ValueError('gist_amd: the batcher yields up to %d rows, the engine was sized for %d'
+                             % (batcher.n_max, self.n_max))
+        self._bind_graph(P, batcher)
+        P.batch_index = P.next_batch_index = -1
+        self.plan = P
+        self._plan_keep = (batcher, batcher.g, self._ws) + keep      # keep every buffer alive
+        return P
+
+    def _need_plan(self):
+        if self.plan is None:
+            raise RuntimeError('gist_amd: %s needs attach_batcher (EngineClusterIter.bind) first' % type(self).__name__)
+
+    def reset_optimizer(self):
+        self.arena.reset_optimizer()
+
+    def _advance_drop_calls(self, n, train):
+        """-> this step's base in the dropout counter space; a training step with dropout takes every layer's [n, 2 * in]
+        elements, rounded up to even, as op_by_op.decide does."""
+        off = self.drop_calls
+        if train and self.p_drop > 0.0:
+            for (i, o) in self.dims:
+                numel = n * 2 * i
+                self.drop_calls += numel + (numel & 1)
+        return off
+
+    def _bind_row_blocks(self, b):
+        """The batch's row blocks into the plan -> how many there are (0: none)."""
+        P, rb = self.plan, b.row_blocks
+        if rb is not None and rb.numel() > 1:
+            P.row_blocks, P.n_row_blocks = rb.data_ptr(), rb.numel() - 1
+        else:
+            P.row_blocks, P.n_row_blocks = None, 0
+        return P.n_row_blocks
+
+    def _plan_next(self, b, flags):
+        """The NEXT batch of the epoch, extracted in the optimiser's grid (GIST_STEP_EXTRACT_NEXT): only for callers that
+        promise not to look at the batch buffers (labels, CSR, layer 0's input) after a training step.  Returns (the
+        key the next step must match, flags)."""
+        P = self.plan
+        if (self.prefetch and (flags & _lib.GIST_STEP_TRAIN) and b.batcher is not None and b.next_info is not None
+                and P.node_part is not None):
+            nids, nj = b.next_info
+            if 0 < nids.numel() <= self.n_max:
+                P.next_ids, P.next_n, P.next_batch_index = nids.data_ptr(), nids.numel(), int(nj)
+                return (self._batch_key(P.part_slot, nj, nids.numel(), nids.data_ptr(), ()),
+                        flags | _lib.GIST_STEP_EXTRACT_NEXT)
+        return None, flags
 
     def _batch_key(self, part_slot, j, n, ids_ptr, tail):
         """The key under which an optimiser launch leaves the batch it extracted ahead (ClusterBatcher.prefetched).
@@ -192,8 +261,8 @@ class StepEngine(object):
         _OPTIMIZER: one third of it (the module path: model(cluster), loss.backward(), optimizer.step(),
         gist_amd/module_engine.py); the backward and optimiser calls reuse the forward call's batch, flags and extra
         argument.  given: the caller wrote its own dlogits.  adam_step: the optimiser's own count (else the arena's).
-        A family states _open_step (the start of a forward: -> flags, ids pointer, extra), _plan_next, _call_step (the
-        one C-ABI call) and, if it has one, _close_step."""
+        A family states _open_step (the start of a forward: -> flags, ids pointer, extra), _call_step (the one C-ABI
+        call) and, if it has them, a _plan_next of its own and _close_step."""
         nxt = None
         if phase in (_lib.GIST_STEP_PHASE_BACKWARD, _lib.GIST_STEP_PHASE_OPTIMIZER):
             cb, flags, ids_ptr, extra = self._phase_ctx
@@ -363,9 +432,7 @@ class SageEngine(StepEngine):
         P.row_loss, P.loss = self.row_loss.data_ptr(), self.loss.data_ptr()
         P.workspace, P.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
         P.workspace2, P.workspace2_bytes = self._ws2.data_ptr(), self._ws2.numel()
-        P.params, P.grads = A.params.data_ptr(), A.grads.data_ptr()
-        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
-        P.n_params = A.numel
+        self._bind_arena(P)
         self._bind_graph(P, batcher)
         fi = batcher.feat_intra
         if fi is not None and self.fuse:
@@ -415,25 +482,18 @@ class SageEngine(StepEngine):
     def _open_step(self, b, train):
         """-> (flags, ids pointer, this step's dropout offset); the per-batch fields of the plan are written."""
         L, P = _lib.load(), self.plan
-        off = self.drop_calls
         # (the GEMM mode decides whether layer 0's mask was folded into a pre-extraction's feature gather)
-        flags, ids_ptr = self._begin_step(b, train, (off, L.gist_gemm_get_mode()), one_launch=self.fuse)
-        if train and self.p_drop > 0.0:
-            for (i, o) in self.dims:
-                numel = b.n * 2 * i
-                self.drop_calls += numel + (numel & 1)
-        rb = b.row_blocks
+        flags, ids_ptr = self._begin_step(b, train, (self.drop_calls, L.gist_gemm_get_mode()), one_launch=self.fuse)
+        off = self._advance_drop_calls(b.n, train)
         P.sibling_parts = 1 if b.siblings else 0
-        if rb is not None and rb.numel() > 1:
-            P.row_blocks, P.n_row_blocks = rb.data_ptr(), rb.numel() - 1
+        n_blocks = self._bind_row_blocks(b)
+        if n_blocks:
             # room for the batch's prepared block structure (include/gist_hip.h, spmm_prepared):
             # both orientations, grown to the largest block count seen
-            need = 2 * L.gist_spmm_blocks_bytes(rb.numel() - 1)
+            need = 2 * L.gist_spmm_blocks_bytes(n_blocks)
             if self._spmm_prep is None or self._spmm_prep.numel() < need:
                 self._spmm_prep = torch.empty(need + need // 4, dtype=torch.uint8, device=self.device)
                 P.spmm_prepared, P.spmm_prepared_bytes = self._spmm_prep.data_ptr(), self._spmm_prep.numel()
-        else:
-            P.row_blocks, P.n_row_blocks = None, 0
         return flags, ids_ptr, off
 
     def _call_step(self, ids_ptr, n, off, lr, betas, eps, weight_decay, t, flags, phase):

@@ -42,11 +42,7 @@ class GATEngine(StepEngine):
         self.arena = arena.with_grads()
         arena.__dict__['_engine'] = weakref.ref(self)      # (module_engine.bind_gat steps an adopted arena through it)
         self.dims = [(int(i), int(o), int(h)) for (i, o, h) in arena.dims]
-        if n_max is None or int(n_max) <= 0:
-            raise ValueError('gist_amd: GATEngine needs n_max > 0 (the iterator\'s n_max)')
-        if len(self.dims) > _lib.GIST_MAX_LAYERS:
-            raise ValueError('gist_amd: more than %d GAT layers' % _lib.GIST_MAX_LAYERS)
-        StepEngine.__init__(self, arena.device if device is None else device, n_max)
+        StepEngine.__init__(self, arena.device if device is None else device, n_max, len(self.dims))
         n = self.n_max
         self.n_classes = self.ldc = self.dims[-1][1]         # (the logits are dense: no padded columns)
         # columns of every layer's output: the next layer's input width (the step checks it is out_k or heads_k * out_k)
@@ -104,24 +100,9 @@ class GATEngine(StepEngine):
         self._attn_partials = torch.zeros(max(nf, 1), dtype=torch.float32, device=self.device)
         P.attn_partials, P.attn_partial_floats = self._attn_partials.data_ptr(), nf
         P.dlogits, P.row_loss, P.loss = self.dlogits.data_ptr(), self.row_loss.data_ptr(), self.loss.data_ptr()
-        # split-K scratch of the projections: each gets what hip._ws_for(m, n, k) gives the op-level call (nothing where
-        # the library asks for nothing), so the split decisions -- and the bits -- are the module path's
-        nb = int(L.gist_gat_step_workspace_bytes(ctypes.byref(P)))
-        self._ws = torch.empty(max(nb, 1 << 20), dtype=torch.uint8, device=self.device)
-        P.workspace, P.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
-        P.params, P.grads = A.params.data_ptr(), A.grads.data_ptr()
-        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
-        P.n_params = A.numel
-        if batcher.n_max > self.n_max:
-            raise ValueError('gist_amd: the batcher yields up to %d rows, the engine was sized for %d'
-                             % (batcher.n_max, self.n_max))
         if batcher.feat.shape[1] != self.dims[0][0]:
             raise ValueError('gist_amd: %d input features, layer 0 takes %d' % (batcher.feat.shape[1], self.dims[0][0]))
-        self._bind_graph(P, batcher)
-        P.batch_index = P.next_batch_index = -1
-        self.plan = P
-        self._plan_keep = (batcher, batcher.g, self._ws, self._attn_partials)      # keep every buffer alive
-        return P
+        return self._finish_plan(P, batcher, L.gist_gat_step_workspace_bytes(ctypes.byref(P)), (self._attn_partials,))
 
     def z0_left(self, n):
         """Layer 0's input rows (ld = n_in; a GAT layer has no [h | ah] right half)."""
@@ -129,9 +110,6 @@ class GATEngine(StepEngine):
 
     def logits(self, n):
         return self.out[-1][:n]
-
-    def reset_optimizer(self):
-        self.arena.reset_optimizer()
 
     @property
     def model(self):
@@ -150,20 +128,6 @@ class GATEngine(StepEngine):
         self._model = self.arena.bind(gat)
         return self._model
 
-    def _plan_next(self, b, flags):
-        """The NEXT batch of the epoch, extracted in the optimiser's grid (GIST_STEP_EXTRACT_NEXT): only for callers that
-        promise not to look at the batch buffers (labels, CSR, layer 0's input) after a training step.  Returns (the
-        key the next step must match, flags)."""
-        P = self.plan
-        if (self.prefetch and (flags & _lib.GIST_STEP_TRAIN) and b.batcher is not None and b.next_info is not None
-                and P.node_part is not None):
-            nids, nj = b.next_info
-            if 0 < nids.numel() <= self.n_max:
-                P.next_ids, P.next_n, P.next_batch_index = nids.data_ptr(), nids.numel(), int(nj)
-                return (self._batch_key(P.part_slot, nj, nids.numel(), nids.data_ptr(), ()),
-                        flags | _lib.GIST_STEP_EXTRACT_NEXT)
-        return None, flags
-
     def _open_step(self, b, train):
         return self._begin_step(b, train, ()) + (None,)
 
@@ -177,8 +141,7 @@ class GATEngine(StepEngine):
               lent=False):
         """One gist_gat_step call (phase = 0: the whole iteration), or one gist_gat_step_phase call, one third of it
         (StepEngine._run), on the engine's own logits, loss and moment buffers unless a binding lent the plan its own."""
-        if self.plan is None:
-            raise RuntimeError('gist_amd: GATEngine needs attach_batcher (EngineClusterIter.bind) first')
+        self._need_plan()
         if self._lent and not lent:
             self._reclaim()
         return self._run(b, lr, weight_decay, train, betas, eps, phase, given, adam_step)

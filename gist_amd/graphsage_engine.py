@@ -30,12 +30,8 @@ from .engine import StepEngine
 class GraphSAGEEngine(StepEngine):
     def __init__(self, dims, dropout, n_max, device, seed=0, use_pp=False, arena=None):
         """dims = [(in_k, out_k)] of ALL layers, the output layer included (gist_amd.arena.graphsage_dims)."""
-        if n_max is None or int(n_max) <= 0:
-            raise ValueError('gist_amd: GraphSAGEEngine needs n_max > 0 (the iterator\'s n_max)')
-        StepEngine.__init__(self, device, n_max)
         self.dims = [(int(i), int(o)) for (i, o) in dims]
-        if len(self.dims) > _lib.GIST_MAX_LAYERS:
-            raise ValueError('gist_amd: more than %d GraphSAGE layers' % _lib.GIST_MAX_LAYERS)
+        StepEngine.__init__(self, device, n_max, len(self.dims))
         if arena is not None and [tuple(d) for d in arena.dims] != self.dims:
             raise ValueError('gist_amd: the arena\'s dims %s are not the engine\'s %s' % (arena.dims, self.dims))
         self.arena = (arena if arena is not None else GraphSAGEArena(self.dims, device)).with_grads()
@@ -84,27 +80,12 @@ class GraphSAGEEngine(StepEngine):
         nf = int(L.gist_graphsage_step_ln_workspace_floats(ctypes.byref(P)))
         self._ln_ws = torch.zeros(max(nf, 4), dtype=torch.float32, device=self.device)
         P.ln_workspace, P.ln_workspace_floats = self._ln_ws.data_ptr(), self._ln_ws.numel()
-        # split-K scratch of the projections: each gets what hip._ws_for(m, n, k) gives the op-level call (nothing where
-        # the library asks for nothing), so the split decisions -- and the bits -- are the op-by-op sequence's
-        nb = int(L.gist_graphsage_step_workspace_bytes(ctypes.byref(P)))
-        self._ws = torch.empty(max(nb, 1 << 20), dtype=torch.uint8, device=self.device)
-        P.workspace, P.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
-        P.params, P.grads = A.params.data_ptr(), A.grads.data_ptr()
-        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
-        P.n_params = A.numel
-        if batcher.n_max > self.n_max:
-            raise ValueError('gist_amd: the batcher yields up to %d rows, the engine was sized for %d'
-                             % (batcher.n_max, self.n_max))
         want = (2 if self.use_pp else 1) * self.dims[0][0]
         if batcher.feat.shape[1] != want:
             raise ValueError('gist_amd: %d resident feature columns, layer 0 takes %d%s'
                              % (batcher.feat.shape[1], want,
                                 ' (use_pp: the iterator\'s [X | A^X])' if self.use_pp else ''))
-        self._bind_graph(P, batcher)
-        P.batch_index = P.next_batch_index = -1
-        self.plan = P
-        self._plan_keep = (batcher, batcher.g, self._ws, self._ln_ws)      # keep every buffer alive
-        return P
+        return self._finish_plan(P, batcher, L.gist_graphsage_step_workspace_bytes(ctypes.byref(P)), (self._ln_ws,))
 
     def z0_left(self, n):
         """Where an eager extraction gathers the resident features: layer 0's h, or with use_pp all of [h | ah]."""
@@ -112,9 +93,6 @@ class GraphSAGEEngine(StepEngine):
 
     def logits(self, n):
         return self.Y[-1][:n]
-
-    def reset_optimizer(self):
-        self.arena.reset_optimizer()
 
     def folds(self, k):
         """Does a training step fold layer k's dropout into its producers (gist_graphsage_step_folds, for the plan's
@@ -131,35 +109,11 @@ class GraphSAGEEngine(StepEngine):
     def model(self):
         return self._model
 
-    def _plan_next(self, b, flags):
-        """The NEXT batch of the epoch, extracted in the optimiser's grid (GIST_STEP_EXTRACT_NEXT): only for callers that
-        promise not to look at the batch buffers (labels, CSR, layer 0's input) after a training step.  Returns (the
-        key the next step must match, flags)."""
-        P = self.plan
-        if (self.prefetch and (flags & _lib.GIST_STEP_TRAIN) and b.batcher is not None and b.next_info is not None
-                and P.node_part is not None):
-            nids, nj = b.next_info
-            if 0 < nids.numel() <= self.n_max:
-                P.next_ids, P.next_n, P.next_batch_index = nids.data_ptr(), nids.numel(), int(nj)
-                return (self._batch_key(P.part_slot, nj, nids.numel(), nids.data_ptr(), ()),
-                        flags | _lib.GIST_STEP_EXTRACT_NEXT)
-        return None, flags
-
     def _open_step(self, b, train):
         """-> (flags, ids pointer, this step's dropout offset); drop_calls advances as op_by_op.decide does."""
-        P = self.plan
-        off = self.drop_calls
         flags, ids_ptr = self._begin_step(b, train, ())
-        if train and self.p_drop > 0.0:
-            for (i, o) in self.dims:
-                numel = b.n * 2 * i
-                self.drop_calls += numel + (numel & 1)
-        rb = b.row_blocks
-        if rb is not None and rb.numel() > 1:
-            P.row_blocks, P.n_row_blocks = rb.data_ptr(), rb.numel() - 1
-        else:
-            P.row_blocks, P.n_row_blocks = None, 0
-        return flags, ids_ptr, off
+        self._bind_row_blocks(b)
+        return flags, ids_ptr, self._advance_drop_calls(b.n, train)
 
     def _call_step(self, ids_ptr, n, off, lr, betas, eps, weight_decay, t, flags, phase):
         if phase:
@@ -173,8 +127,7 @@ class GraphSAGEEngine(StepEngine):
             b.z0_dropped = True      # (one training step per extraction: Z_0 now holds dropped values)
 
     def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
-        if self.plan is None:
-            raise RuntimeError('gist_amd: GraphSAGEEngine needs attach_batcher (EngineClusterIter.bind) first')
+        self._need_plan()
         if b.ready and b.z0_dropped:
             raise RuntimeError('gist_amd: one step per extraction -- this Batch was already trained on with dropout, '
                                'its layer-0 buffer holds dropped values; take a fresh batch from the iterator')
