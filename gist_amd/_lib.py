@@ -164,6 +164,7 @@ SIGNATURES = {
     'gist_ln_affine_fwd_f32': (_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _int, _f, _p]),
     'gist_ln_affine_fwd_drop_f32': (_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _int, _f,
                                            _f, _u64, _u64, _i64, _p]),
+    'gist_ln_affine_infer_f32': (_int, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _int, _f, _p]),
     'gist_graphsage_step_workspace_bytes': (_i64, [_p]),
     'gist_graphsage_step_ln_workspace_floats': (_i64, [_p]),
     'gist_graphsage_step_folds': (_int, [_p, _i32]),

@@ -2,7 +2,8 @@
 // + ReLU in one forward launch, and a backward that leaves dx and the three column sums (d gamma, d beta, d bias of the
 // projection) as partials per 16-row chunk, finished in a fixed order by a second launch.  No float atomics.  The
 // forward's DROP instantiations (gist_ln_affine_fwd_drop_f32) also fold the NEXT layer's dropout into the store: out
-// under gist_dropout_f32's mask, the undropped value to out2.
+// under gist_dropout_f32's mask, the undropped value to out2.  Its inference instantiations (gist_ln_affine_infer_f32,
+// the full-graph evaluator's tail) store out alone.
 //
 // A row is owned by one wave (d <= 1024) or by one 256-thread workgroup; with up to kE = 16 elements per thread it
 // stays in registers (d <= 16 * TPR: every wave row, workgroup rows up to 4096) and is read once; wider rows are
@@ -157,20 +158,26 @@ __device__ __forceinline__ void mask_pack(Pack<VEC> &r, uint64_t idx0, const Spm
 
 // ---------------------------------------------------------------------------
 // forward: v = x + lin_bias; yhat = (v - mean) * rstd; out = relu?(gamma * yhat + beta)
-// DROP: out2 = that value, out = it under the next layer's dropout mask (LnaDrop)
+// kLnaDrop: out2 = that value, out = it under the next layer's dropout mask (LnaDrop)
+// kLnaInfer: the same arithmetic in the same order, but yhat and rstd stay in registers (both pointers NULL): only out is
+// stored (gist_ln_affine_infer_f32)
 // ---------------------------------------------------------------------------
-template <int TPR, int VEC, bool DROP = false>
+enum LnaMode { kLnaTrain = 0, kLnaDrop = 1, kLnaInfer = 2 };
+
+template <int TPR, int VEC, int MODE = kLnaTrain>
 __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
     const float *__restrict__ x, int64_t ldx, const float *__restrict__ lin_bias, const float *__restrict__ gamma,
     const float *__restrict__ beta, float *__restrict__ yhat, int64_t ldy, float *__restrict__ out, int64_t ldo,
     float *__restrict__ rstd_out, int n_rows, int d, int relu, float eps, LnaDrop dr) {
     __shared__ float red[4];
     constexpr int RPB = 256 / TPR;
+    constexpr bool DROP = MODE == kLnaDrop, SAVE = MODE != kLnaInfer;      // SAVE: yhat and rstd are written
     const int row = blockIdx.x * RPB + threadIdx.x / TPR;
     const int t = threadIdx.x % TPR;
     const bool live = row < n_rows;
     const float *xr = x + (int64_t)(live ? row : 0) * ldx;
-    float *yr = yhat + (int64_t)(live ? row : 0) * ldy;
+    float *yr = nullptr;
+    if constexpr (SAVE) yr = yhat + (int64_t)(live ? row : 0) * ldy;
     float *orow = out + (int64_t)(live ? row : 0) * ldo;
     float *o2row = nullptr;
     uint64_t ibase = 0;
@@ -197,10 +204,12 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
         const float var = lna_row_sum<TPR>(sum_elems<VEC>(sq), red) / (float)d;
         const float rstd = 1.0f / sqrtf(var + eps);
         if (!live) return;
-        if (t == 0) rstd_out[row] = rstd;
+        if constexpr (SAVE) {
+            if (t == 0) rstd_out[row] = rstd;
+        }
 #pragma unroll
         for (int e = 0; e < kE; ++e) v[e] *= rstd;
-        store_elems<TPR, VEC>(v, yr, t, d);
+        if constexpr (SAVE) store_elems<TPR, VEC>(v, yr, t, d);
         float g[kE], b[kE];
         load_elems<TPR, VEC>(g, gamma, t, d, true);
         load_elems<TPR, VEC>(b, beta, t, d, true);
@@ -238,13 +247,15 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
         }
         const float var = lna_row_sum<TPR>(q, red) / (float)d;
         const float rstd = 1.0f / sqrtf(var + eps);
-        if (t == 0) rstd_out[row] = rstd;
+        if constexpr (SAVE) {
+            if (t == 0) rstd_out[row] = rstd;
+        }
         for (int c = t * VEC; c < d; c += 256 * VEC) {
             Pack<VEC> p = value(c);
             const Pack<VEC> g = ld<VEC>(gamma + c), b = ld<VEC>(beta + c);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) p.v[k] = (p.v[k] - mean) * rstd;
-            st<VEC>(yr + c, p);
+            if constexpr (SAVE) st<VEC>(yr + c, p);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 p.v[k] = affine_pre(p.v[k], g.v[k], b.v[k]);
@@ -427,20 +438,23 @@ __global__ __launch_bounds__(256) void ln_affine_finish_kernel(const float *__re
 }  // namespace gist
 
 namespace gist {
-// drop = NULL, or p = 0 and out2 = NULL: the plain instantiations
+// drop = NULL, or p = 0 and out2 = NULL: the plain instantiations.  infer (gist_ln_affine_infer_f32; no drop): yhat and
+// rstd are NULL and ldy is 0 -- not required, not in the vector predicate, not written; everything else is the same
+// decision: a call whose yhat shares out's pitch and alignment class picks the same (regime, VEC) either way
 static int ln_affine_fwd_ex(const char *name, const float *x, int64_t ldx, const float *lin_bias, const float *gamma,
                             const float *beta, float *yhat, int64_t ldy, float *out, int64_t ldo, float *rstd,
-                            int64_t n_rows, int64_t d, int relu, float eps, const LnaDrop *drop, hipStream_t st) {
+                            int64_t n_rows, int64_t d, int relu, float eps, const LnaDrop *drop, bool infer,
+                            hipStream_t st) {
     GIST_REQUIRE(n_rows >= 0 && d >= 0, "%s: negative size", name);
     if (n_rows == 0 || d == 0) return GIST_OK;
-    GIST_REQUIRE(x && gamma && beta && yhat && out && rstd, "%s: null pointer", name);
-    GIST_REQUIRE(ldx >= d && ldy >= d && ldo >= d, "%s: leading dimension < d", name);
+    GIST_REQUIRE(x && gamma && beta && out && (infer || (yhat && rstd)), "%s: null pointer", name);
+    GIST_REQUIRE(ldx >= d && (infer || ldy >= d) && ldo >= d, "%s: leading dimension < d", name);
     GIST_REQUIRE(n_rows < (1LL << 31) && d < (1LL << 31), "%s: size >= 2^31", name);
     GIST_REQUIRE(eps >= 0.f, "%s: negative eps", name);
     bool v4 = d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(yhat) &&
               aligned16(out) && aligned16(gamma) && aligned16(beta) && aligned16(lin_bias);
     LnaDrop dr{};
-    const bool dropping = drop != nullptr && (drop->m.p > 0.f || drop->out2 != nullptr);
+    const bool dropping = !infer && drop != nullptr && (drop->m.p > 0.f || drop->out2 != nullptr);
     if (dropping) {
         dr = *drop;
         if (dr.out2 != nullptr) {
@@ -450,18 +464,19 @@ static int ln_affine_fwd_ex(const char *name, const float *x, int64_t ldx, const
     }
     const bool wide = d > 1024;
     const unsigned grid = (unsigned)(wide ? n_rows : ceil_div(n_rows, 4));
-#define L(TPR, V)                                                                                                    \
-    do {                                                                                                             \
-        if (dropping)                                                                                                \
-            hipLaunchKernelGGL((ln_affine_fwd_kernel<TPR, V, true>), dim3(grid), dim3(256), 0, st, x, ldx, lin_bias, \
-                               gamma, beta, yhat, ldy, out, ldo, rstd, (int)n_rows, (int)d, relu, eps, dr);          \
-        else                                                                                                         \
-            hipLaunchKernelGGL((ln_affine_fwd_kernel<TPR, V, false>), dim3(grid), dim3(256), 0, st, x, ldx, lin_bias, \
-                               gamma, beta, yhat, ldy, out, ldo, rstd, (int)n_rows, (int)d, relu, eps, dr);          \
+#define LM(TPR, V, MODE)                                                                                              \
+    hipLaunchKernelGGL((ln_affine_fwd_kernel<TPR, V, MODE>), dim3(grid), dim3(256), 0, st, x, ldx, lin_bias, gamma, beta, \
+                       yhat, ldy, out, ldo, rstd, (int)n_rows, (int)d, relu, eps, dr)
+#define L(TPR, V)                                                                                                     \
+    do {                                                                                                              \
+        if (infer) LM(TPR, V, kLnaInfer);                                                                             \
+        else if (dropping) LM(TPR, V, kLnaDrop);                                                                      \
+        else LM(TPR, V, kLnaTrain);                                                                                   \
     } while (0)
     if (wide) { if (v4) L(256, 4); else L(256, 1); }
     else { if (v4) L(64, 4); else L(64, 1); }
 #undef L
+#undef LM
     return launch_status(name);
 }
 }  // namespace gist
@@ -471,7 +486,7 @@ extern "C" int gist_ln_affine_fwd_f32(const float *x, int64_t ldx, const float *
                                       float *rstd, int64_t n_rows, int64_t d, int relu, float eps,
                                       gist_stream_t stream) {
     return gist::ln_affine_fwd_ex("gist_ln_affine_fwd_f32", x, ldx, lin_bias, gamma, beta, yhat, ldy, out, ldo, rstd,
-                                  n_rows, d, relu, eps, nullptr, gist::as_stream(stream));
+                                  n_rows, d, relu, eps, nullptr, false, gist::as_stream(stream));
 }
 
 extern "C" int gist_ln_affine_fwd_drop_f32(const float *x, int64_t ldx, const float *lin_bias, const float *gamma,
@@ -485,7 +500,14 @@ extern "C" int gist_ln_affine_fwd_drop_f32(const float *x, int64_t ldx, const fl
     dr.out2 = out2; dr.ldo2 = ldo2;
     dr.m = gist::spmm_drop_of(1, p, seed, offset, 0, mask_ld);
     return gist::ln_affine_fwd_ex("gist_ln_affine_fwd_drop_f32", x, ldx, lin_bias, gamma, beta, yhat, ldy, out, ldo,
-                                  rstd, n_rows, d, relu, eps, &dr, gist::as_stream(stream));
+                                  rstd, n_rows, d, relu, eps, &dr, false, gist::as_stream(stream));
+}
+
+extern "C" int gist_ln_affine_infer_f32(const float *x, int64_t ldx, const float *lin_bias, const float *gamma,
+                                        const float *beta, float *out, int64_t ldo, int64_t n_rows, int64_t d, int relu,
+                                        float eps, gist_stream_t stream) {
+    return gist::ln_affine_fwd_ex("gist_ln_affine_infer_f32", x, ldx, lin_bias, gamma, beta, nullptr, 0, out, ldo, nullptr,
+                                  n_rows, d, relu, eps, nullptr, true, gist::as_stream(stream));
 }
 
 extern "C" int64_t gist_ln_affine_bwd_workspace_floats(int64_t n_rows, int64_t d) {

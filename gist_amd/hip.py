@@ -551,6 +551,21 @@ def ln_affine_fwd_drop(x, lin_bias, gamma, beta, yhat, out, out2, rstd, relu, p,
     return out
 
 
+def ln_affine_infer(x, lin_bias, gamma, beta, out, relu, eps=LN_EPS):
+    """out = ln_affine_fwd's out and nothing else (gist_ln_affine_infer_f32): the tail of an evaluation, which keeps no
+    yhat and no rstd.  x and out must not overlap."""
+    L = _lib.load()
+    xp, ldx = _mat(x, 'x')
+    op, ldo = _mat(out, 'out')
+    n, d = x.shape
+    if tuple(out.shape) != (n, d):
+        raise ValueError('gist_amd: ln_affine_infer shape mismatch')
+    _lib.check(L.gist_ln_affine_infer_f32(xp, ldx, _opt(lin_bias, 'lin_bias', torch.float32, d),
+                                          _vec(gamma, 'gamma', torch.float32, d), _vec(beta, 'beta', torch.float32, d),
+                                          op, ldo, n, d, int(bool(relu)), eps, _stream()), 'gist_ln_affine_infer_f32')
+    return out
+
+
 def ln_affine_bwd(d_out, yhat, rstd, gamma, beta, relu, dx, dgamma, dbeta, dlin_bias=None, ws=None):
     """dx and the column sums dgamma, dbeta (and dlin_bias = the column sums of dx, unless None) of ln_affine_fwd
     (gist_ln_affine_bwd_f32).  ws: float32 scratch of gist_ln_affine_bwd_workspace_floats(n, d) elements (None: taken

@@ -50,18 +50,24 @@ def build_parser():
     # (module_engine.bind_gat) -- the engine's launches as three gist_gat_step_phase calls per iteration; step (graphsage):
     # one gist_graphsage_step per iteration (gist_amd/graphsage_engine.py); engine and module keep that family's module loop
     parser.add_argument("--host-path", choices=['engine', 'module', 'phases', 'step'], default='engine')
-    # (not a flag of the reference; --model-type gat) how evaluate() runs the full-graph forward: layers = the model's own
+    # (not a flag of the reference; --model-type gat and graphsage) how evaluate() runs the full-graph forward: layers = the model's own
     # forward, layer by layer on the training kernels; blocked = gist_amd.gat_eval.GATFullGraphEvaluator (preallocated
-    # buffers, two-pass softmax, the graph's node blocks as dense products on the matrix cores)
-    parser.add_argument("--eval-path", choices=['layers', 'blocked'], default='layers')
+    # buffers, two-pass softmax, the graph's node blocks as dense products on the matrix cores); rows (--model-type
+    # graphsage) = gist_amd.graphsage_eval.GraphSAGEFullGraphEvaluator (preallocated buffers, row block by row block, the
+    # node blocks on the matrix cores, layer 0's aggregation kept, a tail kernel that stores its result alone)
+    parser.add_argument("--eval-path", choices=['layers', 'blocked', 'rows'], default='layers')
     return parser
 
 
 def attach_eval_path(args, model, arena=None):
-    """--eval-path blocked: route evaluate(model, g, ...) through a GATFullGraphEvaluator."""
+    """--eval-path blocked: route evaluate(model, g, ...) through a GATFullGraphEvaluator; --eval-path rows: through a
+    GraphSAGEFullGraphEvaluator."""
     if getattr(args, 'eval_path', 'layers') == 'blocked':
         from gist_amd.gat_eval import GATFullGraphEvaluator
         GATFullGraphEvaluator.attach(model, arena=arena)
+    elif getattr(args, 'eval_path', 'layers') == 'rows':
+        from gist_amd.graphsage_eval import GraphSAGEFullGraphEvaluator
+        GraphSAGEFullGraphEvaluator.attach(model, arena=arena)
 
 
 def main(args, dataset=None, log=print):
@@ -75,6 +81,9 @@ def main(args, dataset=None, log=print):
         raise SystemExit('gist_amd runs on the GPU only (no CPU fallback): --gpu >= 0, no --eval-cpu')
     if args.model_type not in ('sage', 'gat', 'graphsage'):
         raise NotImplementedError(f'{args.model_type} is not a supported model type')
+    if getattr(args, 'eval_path', 'layers') == 'rows' and args.model_type != 'graphsage':
+        raise SystemExit('gist_amd: --eval-path rows is the GraphSAGE family\'s evaluator (--model-type graphsage); the SAGE '
+                         'engine path already evaluates with trainer.FullGraphEvaluator, the GAT has --eval-path blocked')
     data = dataset if dataset is not None else load_data(args)
     g = data.g
     device = torch.device('cuda', args.gpu)
@@ -100,7 +109,7 @@ def main(args, dataset=None, log=print):
         model_holder['m'] = m
         return m
     host_path = getattr(args, 'host_path', 'engine')
-    if getattr(args, 'eval_path', 'layers') != 'layers' and args.model_type != 'gat':
+    if getattr(args, 'eval_path', 'layers') == 'blocked' and args.model_type != 'gat':
         raise SystemExit('gist_amd: --eval-path blocked is the GAT evaluator (--model-type gat); the SAGE engine path '
                          'already evaluates with trainer.FullGraphEvaluator')
     if host_path == 'phases' and args.model_type != 'gat':
@@ -209,6 +218,7 @@ def main_graphsage_engine(args, data, g, device, in_feats, n_classes, par_li, ps
     engine.bind(model)                                     # the model's parameters are the arena's views from here on
     it.bind(engine)
     engine.prefetch = True                                 # (the loop only reads the loss of a step)
+    attach_eval_path(args, model, engine.arena)
     total_time, val_accs, test_accs = 0., [], []
     for epoch in range(args.n_epochs):                     # cluster_gcn.py:89-127
         log(f'Running epoch {epoch} / {args.n_epochs}', flush=True)
@@ -259,7 +269,7 @@ def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, 
     if args.model_type == 'gat' and getattr(args, 'host_path', 'engine') == 'phases':
         from gist_amd.module_engine import bind_gat
         bind_gat(model, cluster_iterator)            # model(cluster), loss.backward(), optimizer.step(): the fused step's phases
-    if args.model_type == 'gat':
+    if args.model_type in ('gat', 'graphsage'):
         attach_eval_path(args, model)
     loss_f = CrossEntropyLoss()                                                                        # :76
     optimizer = Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)                   # :77-80

@@ -115,14 +115,27 @@ class FullGraphEvaluator(object):
     def invalidate_input_aggregation(self):
         self._ah0_ready = False
 
+    # -- what a model family states (gist_amd.graphsage_eval.GraphSAGEFullGraphEvaluator overrides both) --
+    def _layer_params(self, k):
+        """Layer k's parameters as they are NOW: (W [out, 2*in], b [out], whatever else _hidden_block reads)."""
+        return self.arena.W[k], self.arena.b[k]
+
+    def _hidden_block(self, params, z, dst):
+        """A hidden layer on one row block: dst [rows, out] = the layer's tail of the projection of z [rows, 2*in]."""
+        W, b = params
+        y = self.yb[:z.shape[0], :dst.shape[1]]
+        hip.gemm_nt(z, W, b, y)
+        hip.ln_relu_fwd(y, dst, None, self.use_layernorm, True)
+
     def forward(self):
         """GCN.forward (modules.py:310-314) in eval mode over the full graph -> logits [N, C]."""
-        g, A, n = self.g, self.arena, self.n
+        g, n = self.g, self.n
         L1 = len(self.dims)
         cur = self.feat
         for k, (i, o) in enumerate(self.dims):
             last = k == L1 - 1
-            W, b = A.W[k], A.b[k]
+            params = self._layer_params(k)
+            W, b = params[0], params[1]
             if last and self.project_first:
                 p = self.pbuf[:, :o]
                 out = self.logits[:, :o]
@@ -172,9 +185,7 @@ class FullGraphEvaluator(object):
                 if last:
                     hip.gemm_nt(z, W, b, dst[r0:r1, :o])
                 else:
-                    y = self.yb[:r1 - r0, :o]
-                    hip.gemm_nt(z, W, b, y)
-                    hip.ln_relu_fwd(y, dst[r0:r1, :o], None, self.use_layernorm, True)
+                    self._hidden_block(params, z, dst[r0:r1, :o])
             if keep_ah:
                 self._ah0_ready = True
             cur = dst

@@ -471,6 +471,20 @@ int gist_ln_affine_fwd_drop_f32(const float *x, int64_t ldx, const float *lin_bi
                                 float *yhat, int64_t ldy, float *out, int64_t ldo, float *out2, int64_t ldo2, float *rstd,
                                 int64_t n_rows, int64_t d, int relu, float eps, float p, uint64_t seed, uint64_t offset,
                                 int64_t mask_ld, gist_stream_t stream);
+/* gist_ln_affine_fwd_f32 without the training state: the tail of a GraphSAGELayer in a full-graph evaluation
+ * (cluster_gcn/modules.py:144-147 under utils.py:70-80, model.eval() and torch.no_grad()): out = relu ? max(pre, 0) : pre
+ * and nothing else -- no yhat, no rstd.  The same kernel body as the training forward (mean, variance, the fused
+ * multiply-add and the ReLU are the same code in the same order), so for a call whose yhat would share out's pitch and
+ * alignment class `out` equals gist_ln_affine_fwd_f32's bit for bit.  x and out must not overlap (a row of out is
+ * written while other rows of x are still being read, and the pointers are declared restrict).  16-byte accesses when
+ * d % 4 == 0, ldx % 4 == 0, ldo % 4 == 0 and x, out, gamma, beta and lin_bias are 16-byte aligned, scalar otherwise; a
+ * wave owns a row for d <= 1024, a workgroup above.  Traffic: rows up to 4096 floats are read once and written once,
+ * 2 * n_rows * d * 4 bytes (the training forward moves 3 * n_rows * d * 4 plus rstd); wider rows are read three times
+ * and written once, 4 * n_rows * d * 4 bytes (training: 5 * n_rows * d * 4 plus rstd); the three vectors come from
+ * cache.  n_rows = 0 or d = 0: OK, no launch.  NULL x, gamma, beta or out, ldx < d, ldo < d, eps < 0: GIST_EINVAL. */
+int gist_ln_affine_infer_f32(const float *x, int64_t ldx, const float *lin_bias, const float *gamma, const float *beta,
+                             float *out, int64_t ldo, int64_t n_rows, int64_t d, int relu, float eps,
+                             gist_stream_t stream);
 /* Its backward from the saved yhat and rstd (autograd of modules.py:120,144-147):
  *   g' = (pre > 0) ? d_out : 0 when relu (pre recomputed by the forward's own fused multiply-add: the gate agrees
  *   with the forward's out bit for bit; no gradient at pre = 0), else d_out;  dyh = g' * gamma;
