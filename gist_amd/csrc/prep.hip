@@ -39,15 +39,17 @@ __global__ __launch_bounds__(256) void col_stat_partial_kernel(
                                                 (red[2][threadIdx.x] + red[3][threadIdx.x]));
 }
 
-// out[c] = (sum over blocks of partial[blk][c]) / count  (+ add[c]); fixed order
+// out[c] = (sum over blocks of partial[blk][c]) / count  (+ add[c]); fixed order.  A DIVISION, as numpy's mean: times
+// 1 / count the mean of a constant column is off by an ulp for about one count in five (-3.5 * 300 * (1.0 / 300) !=
+// -3.5), its variance then 1e-31 instead of 0, and the column comes out as +-1 instead of sklearn's 0
 __global__ void col_stat_final_kernel(const double *__restrict__ partial, int64_t n_blocks, int d,
-                                      double inv_count, const double *__restrict__ add,
+                                      double count, const double *__restrict__ add,
                                       double *__restrict__ out) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= d) return;
     double s = 0.0;
     for (int64_t b = 0; b < n_blocks; ++b) s += partial[b * d + c];
-    out[c] = s * inv_count + (add ? add[c] : 0.0);
+    out[c] = s / count + (add ? add[c] : 0.0);
 }
 
 __global__ __launch_bounds__(256) void standardize_kernel(float *__restrict__ x, int64_t ld,
@@ -97,11 +99,11 @@ extern "C" int gist_standard_scaler_f32(float *x, int64_t ld, int64_t n_rows, in
     hipLaunchKernelGGL((col_stat_partial_kernel<false>), grid, dim3(256), 0, st, x, ld, fit_rows,
                        n_fit_rows, (int)d, (const double *)nullptr, partial);
     hipLaunchKernelGGL(col_stat_final_kernel, dim3(fin), dim3(256), 0, st, partial, nblk, (int)d,
-                       1.0 / (double)n_fit_rows, (const double *)nullptr, mean);
+                       (double)n_fit_rows, (const double *)nullptr, mean);
     hipLaunchKernelGGL((col_stat_partial_kernel<true>), grid, dim3(256), 0, st, x, ld, fit_rows,
                        n_fit_rows, (int)d, (const double *)mean, partial);
     hipLaunchKernelGGL(col_stat_final_kernel, dim3(fin), dim3(256), 0, st, partial, nblk, (int)d,
-                       1.0 / (double)n_fit_rows, (const double *)nullptr, var);
+                       (double)n_fit_rows, (const double *)nullptr, var);
     const dim3 g2((unsigned)ceil_div(d, 64), (unsigned)ceil_div(n_rows, 64));
     hipLaunchKernelGGL(standardize_kernel, g2, dim3(256), 0, st, x, ld, n_rows, (int)d, mean, var);
     return launch_status("gist_standard_scaler_f32");

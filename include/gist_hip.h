@@ -18,6 +18,10 @@
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*;
  *     NULL = the default stream); nothing allocates, nothing synchronises, the
  *     caller owns every buffer (workspaces are passed in).
+ *   - borrowed memory: a call given `workspace_bytes = B` (or any scratch, slab, partial-sum or prepared-structure
+ *     buffer with its size: a byte, float or row count, or the value of the size query named beside it) writes nothing
+ *     outside those bytes, and no result depends on what the buffer held before the call -- no scratch has to be zeroed
+ *     or preserved by the caller unless its parameter says so (extract_scratch: "ZEROED ONCE by the caller").
  *   - return value: 0 on success, a negative GIST_E* code otherwise; no C++
  *     exception crosses the boundary.  gist_last_error() returns a static
  *     string describing the last failure on the calling thread.
