@@ -39,7 +39,7 @@ struct ClassArgs {
     float *dlog; int64_t ldg;
     float *row_nll;
     float *dz; int64_t lddz;          // NULL: forward + loss only
-    float p, scale; uint64_t sm, offset;
+    DropMask m; uint64_t offset;
     float *col_partials;              // [ceil(n / 16)][C] or NULL
     int n_rows, n_classes, k;
 };
@@ -201,10 +201,10 @@ __global__ __launch_bounds__(256) void class_layer_kernel(ClassArgs a) {
             const int row = r0 + 4 * q + i;
             if (row >= a.n_rows) continue;
             float v0 = d0[i], v1 = d1[i];
-            if (a.p > 0.f) {
+            if (a.m.p > 0.f) {
                 const uint64_t idx = a.offset + (uint64_t)row * (uint64_t)K + (uint64_t)(n0 + r);
-                v0 *= drop_keep(idx, a.sm, a.p, a.scale);
-                v1 *= drop_keep(idx + 16, a.sm, a.p, a.scale);
+                v0 *= drop_keep(idx, a.m);
+                v1 *= drop_keep(idx + 16, a.m);
             }
             float *o = a.dz + (int64_t)row * a.lddz + n0 + r;
             o[0] = v0;
@@ -267,8 +267,7 @@ extern "C" int gist_class_layer_f32(const float *z, int64_t ldz, const float *w,
     a.z = z; a.ldz = ldz; a.w = w; a.ldw = ldw; a.bias = bias; a.labels = labels;
     a.inv_count = 1.0f / (float)count;
     a.logits = logits; a.ldl = ldl; a.dlog = d_logits; a.ldg = ldg; a.row_nll = row_loss;
-    a.dz = dz; a.lddz = lddz; a.p = p; a.scale = p > 0.f ? 1.0f / (1.0f - p) : 1.f;
-    a.sm = seed * 0x9E3779B97F4A7C15ULL; a.offset = offset;
+    a.dz = dz; a.lddz = lddz; a.m = drop_mask_of(p, seed); a.offset = offset;
     a.col_partials = dlogits_col_partials;
     a.n_rows = (int)n_rows; a.n_classes = (int)n_classes; a.k = (int)k;
     hipLaunchKernelGGL(class_layer_kernel, dim3((unsigned)ceil_div(n_rows, kRows)), dim3(256), 0,

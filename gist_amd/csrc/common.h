@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "../../include/gist_hip.h"
+#include "dropout.h"
 #include "gemm_plan.h"
 
 namespace gist {
@@ -50,13 +51,6 @@ static inline int launch_status(const char *what) {
 extern thread_local gist_timer *tl_timer;
 int64_t timer_begin(gist_timer *t, int kind, int64_t m, int64_t n, int64_t k, hipStream_t s);
 void timer_end(gist_timer *t, int64_t slot, hipStream_t s);
-
-// dropout's counter-based generator (rowops.hip; also applied inside the split pre-pass)
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
 
 // The projection family.  How a projection runs -- path, tile, k slices, tail units, scratch -- is plan_gemm()'s answer
 // (gemm_plan.h); what follows are the launchers that read it and the pre-passes.
@@ -114,11 +108,11 @@ int splitk_reduce(const char *name, const float *slabs, int64_t slab, int splits
                   int64_t ldc, int64_t m, int64_t n, hipStream_t st);
 
 // spmm.hip: dropout folded into an aggregation (gist_spmm_csr_drop_f32); element (row, c) of y has mask
-// index y_base + row * ld + c, of x src_base + row * ld + c (sm = seed * golden ratio)
+// index y_base + row * ld + c, of x src_base + row * ld + c
 struct SpmmDrop {
     int mode;                 // 0 none, 1 forward (mask what is stored), 2 backward (mask x and the old y)
-    float p, scale;
-    uint64_t sm, y_base, src_base;
+    DropMask m;
+    uint64_t y_base, src_base;
     int64_t ld;
 };
 // LayerNorm + ReLU backward of the layer BELOW in the store of a reverse aggregation (mode 2, d <= 256: a wave holds a
@@ -135,8 +129,8 @@ struct SpmmLnBwd {
 // gist_spmm_csr_drop_f32's arguments as a SpmmDrop (a mode other than 1 and 2 becomes -1, which spmm_run refuses)
 static inline SpmmDrop spmm_drop_of(int mode, float p, uint64_t seed, uint64_t y_offset, uint64_t src_offset, int64_t ld) {
     SpmmDrop dr{};
-    dr.mode = (mode == 1 || mode == 2) ? mode : -1; dr.p = p; dr.scale = (p > 0.f && p < 1.f) ? 1.0f / (1.0f - p) : 1.f;
-    dr.sm = seed * 0x9E3779B97F4A7C15ULL; dr.y_base = y_offset; dr.src_base = src_offset; dr.ld = ld;
+    dr.mode = (mode == 1 || mode == 2) ? mode : -1; dr.m = drop_mask_of(p, seed);
+    dr.y_base = y_offset; dr.src_base = src_offset; dr.ld = ld;
     return dr;
 }
 // rows of x and y start on 16-byte boundaries and are whole float4s
@@ -204,32 +198,6 @@ __device__ __forceinline__ float wave_sum(float v) {
     const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
     return (r0 + r1) + (r2 + r3);
 }
-// gist_dropout_f32's keep/scale factor of element idx, of VEC consecutive elements, of an aligned quad
-__device__ __forceinline__ float drop_keep(uint64_t idx, uint64_t sm, float p, float scale) {
-    const uint64_t h = splitmix64((idx >> 1) + sm);
-    const uint32_t w = (idx & 1) ? (uint32_t)(h >> 32) : (uint32_t)h;
-    return ((float)(w >> 8) * (1.0f / 16777216.0f) >= p) ? scale : 0.f;
-}
-template <int VEC>
-__device__ __forceinline__ void drop_vec(float (&v)[VEC], uint64_t idx0, const SpmmDrop &dr) {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) v[k] *= drop_keep(idx0 + k, dr.sm, dr.p, dr.scale);
-}
-__device__ __forceinline__ void drop_f4(float4 &v, uint64_t idx0, const SpmmDrop &dr) {
-    const float inv = 1.0f / 16777216.0f;
-    if ((idx0 & 1) == 0) {                 // the usual case: two hashes cover the quad
-        const uint64_t pair = idx0 >> 1;
-        const uint64_t h0 = splitmix64(pair + dr.sm), h1 = splitmix64(pair + 1 + dr.sm);
-        v.x *= ((float)((uint32_t)h0 >> 8) * inv >= dr.p) ? dr.scale : 0.f;
-        v.y *= ((float)((uint32_t)(h0 >> 32) >> 8) * inv >= dr.p) ? dr.scale : 0.f;
-        v.z *= ((float)((uint32_t)h1 >> 8) * inv >= dr.p) ? dr.scale : 0.f;
-        v.w *= ((float)((uint32_t)(h1 >> 32) >> 8) * inv >= dr.p) ? dr.scale : 0.f;
-    } else {
-        v.x *= drop_keep(idx0, dr.sm, dr.p, dr.scale); v.y *= drop_keep(idx0 + 1, dr.sm, dr.p, dr.scale);
-        v.z *= drop_keep(idx0 + 2, dr.sm, dr.p, dr.scale); v.w *= drop_keep(idx0 + 3, dr.sm, dr.p, dr.scale);
-    }
-}
-
 #endif
 // spmm_mfma.hip: the block-dense aggregation kernel behind gist_spmm_csr_blocked_f32 / _prepared_f32
 // (prepared = NULL: every workgroup builds its block's counts itself).  pairs: may the batch have sibling blocks?  false

@@ -81,7 +81,7 @@ constexpr int B3S_PITCH = 25;                          // 16-B chunks per image 
 struct B3SplitJob {
     B3Dual d;
     int64_t ldd_r, ldd_t;
-    float keep;                       // 1 / (1 - p)
+    DropMask mask;                    // drop_mask_of(d.p, d.seed): what the kernel reads; d.p and d.seed it does not
     int gx, gy;                       // 64 x 64 tiles of this job
     int first;                        // its first block
 };
@@ -157,22 +157,15 @@ __global__ __launch_bounds__(B3S_THREADS) void b3_split_kernel(B3SplitList L) {
                 v[i][e] = r < d.rows && c + e < d.cols ? d.src[r * d.ld + c + e] : 0.f;
         }
     }
-    if (d.p > 0.f) {
-        const uint64_t sm = d.seed * 0x9E3779B97F4A7C15ULL;
-        const float inv24 = 1.0f / 16777216.0f;
+    if (J.mask.p > 0.f) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int64_t r = r0 + 8 * rg + i;
             if (r >= d.rows) continue;
-            const uint64_t idx0 = d.offset + (uint64_t)r * (uint64_t)d.cols + (uint64_t)c;
-            const uint64_t pair = idx0 >> 1;
-            const uint64_t h0 = splitmix64(pair + sm), h1 = splitmix64(pair + 1 + sm), h2 = splitmix64(pair + 2 + sm);
-            // the 32-bit words of element indices idx0 .. idx0 + 3 (pair idx >> 1, low word for even idx)
-            const bool odd = (idx0 & 1) != 0;
-            const uint32_t w[4] = {odd ? (uint32_t)(h0 >> 32) : (uint32_t)h0, odd ? (uint32_t)h1 : (uint32_t)(h0 >> 32),
-                                   odd ? (uint32_t)(h1 >> 32) : (uint32_t)h1, odd ? (uint32_t)h2 : (uint32_t)(h1 >> 32)};
+            float f[4];
+            drop_factors4_flat(f, d.offset + (uint64_t)r * (uint64_t)d.cols + (uint64_t)c, J.mask);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[i][e] *= ((float)(w[e] >> 8) * inv24 >= d.p) ? J.keep : 0.f;
+            for (int e = 0; e < 4; ++e) v[i][e] *= f[e];
         }
     }
     if (d.col_partials != nullptr) {      // column sums of this 64-row chunk, in the order gist_colsum_f32 uses
@@ -759,7 +752,7 @@ int b3_split_jobs(const B3Dual *jobs, int n_jobs, hipStream_t st) {
         J.d = d;
         J.d.vec4 = aligned16(d.src) && d.ld % 4 == 0;
         J.ldd_r = b3_kpad(d.cols); J.ldd_t = b3_kpad(d.rows);
-        J.keep = d.p > 0.f ? 1.0f / (1.0f - d.p) : 1.0f;
+        J.mask = drop_mask_of(d.p, d.seed);
         J.gx = (int)ceil_div(d.dst_r ? J.ldd_r : d.cols, 64);
         J.gy = (int)ceil_div(d.dst_t ? J.ldd_t : d.rows, 64);
         J.first = (int)blocks;

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void h3_split_t_kernel(const float *__restrict
 // fly with gist_dropout_f32's generator (element index offset + r * cols + c), so the fp32
 // dropped tensor never has to exist.
 __global__ __launch_bounds__(256) void h3_dual_split_kernel(H3Dual d, int64_t ldd_r, int64_t ldd_t,
-                                                            float keep) {
+                                                            DropMask mask) {
     __shared__ float tile[64][65];
     __shared__ float srow[64], scol[64];
     const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
@@ -233,8 +233,6 @@ __global__ __launch_bounds__(256) void h3_dual_split_kernel(H3Dual d, int64_t ld
         }
     }
     const int c4 = (t & 15) * 4;
-    const uint64_t sm = d.seed * 0x9E3779B97F4A7C15ULL;
-    const float inv24 = 1.0f / 16777216.0f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int rr = (t >> 4) + 16 * i;
@@ -250,16 +248,7 @@ __global__ __launch_bounds__(256) void h3_dual_split_kernel(H3Dual d, int64_t ld
                 for (int j = 0; j < 3; ++j)
                     if (c0 + c4 + j < d.cols) v[j] = p[j];
             }
-            if (d.p > 0.f) {
-                const uint64_t idx0 = d.offset + (uint64_t)r * (uint64_t)d.cols + (uint64_t)(c0 + c4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint64_t idx = idx0 + j;
-                    const uint64_t h = splitmix64((idx >> 1) + sm);
-                    const uint32_t w = (idx & 1) ? (uint32_t)(h >> 32) : (uint32_t)h;
-                    v[j] *= ((float)(w >> 8) * inv24 >= d.p) ? keep : 0.f;
-                }
-            }
+            if (mask.p > 0.f) drop_vec<4>(v, d.offset + (uint64_t)r * (uint64_t)d.cols + (uint64_t)(c0 + c4), mask);
         }
         tile[rr][c4 + 0] = v[0]; tile[rr][c4 + 1] = v[1];
         tile[rr][c4 + 2] = v[2]; tile[rr][c4 + 3] = v[3];
@@ -594,7 +583,7 @@ int h3_dual_split(const H3Dual &d, hipStream_t st) {
     const int64_t ldd_r = h3_kpad(d.cols), ldd_t = h3_kpad(d.rows);
     const int64_t gx = ceil_div(d.dst_r ? ldd_r : d.cols, 64), gy = ceil_div(d.dst_t ? ldd_t : d.rows, 64);
     hipLaunchKernelGGL(h3_dual_split_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, d,
-                       ldd_r, ldd_t, d.p > 0.f ? 1.0f / (1.0f - d.p) : 1.0f);
+                       ldd_r, ldd_t, drop_mask_of(d.p, d.seed));
     return launch_status("h3_dual_split");
 }
 

@@ -117,16 +117,18 @@ __device__ __forceinline__ float sum_pack(const Pack<VEC> &r) {
 }
 
 // The next layer's dropout folded into the forward's store (gist_ln_affine_fwd_drop_f32): what goes to row r, column c
-// of `out` is multiplied by gist_dropout_f32's keep/scale factor of element m.y_base + r * m.ld + c (m.p = 0: no mask,
+// of `out` is multiplied by gist_dropout_f32's keep/scale factor of element offset + r * mask_ld + c (m.p = 0: no mask,
 // nothing hashed); the value before the mask goes to out2 (NULL: none).  Only the DROP instantiations read it.
 struct LnaDrop {
     float *out2; int64_t ldo2;
-    SpmmDrop m;
+    DropMask m;
+    uint64_t offset;
+    int64_t mask_ld;
 };
 
 // the mask on the thread's kE elements of the row whose element 0 has index ibase
 template <int TPR, int VEC>
-__device__ __forceinline__ void mask_elems(float (&v)[kE], uint64_t ibase, int t, int d, const SpmmDrop &m) {
+__device__ __forceinline__ void mask_elems(float (&v)[kE], uint64_t ibase, int t, int d, const DropMask &m) {
     if constexpr (VEC == 4) {
 #pragma unroll
         for (int u = 0; u < kE / 4; ++u) {
@@ -141,18 +143,8 @@ __device__ __forceinline__ void mask_elems(float (&v)[kE], uint64_t ibase, int t
 #pragma unroll
         for (int e = 0; e < kE; ++e) {
             const int c = t + e * TPR;
-            if (c < d) v[e] *= drop_keep(ibase + (uint64_t)c, m.sm, m.p, m.scale);
+            if (c < d) v[e] *= drop_keep(ibase + (uint64_t)c, m);
         }
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void mask_pack(Pack<VEC> &r, uint64_t idx0, const SpmmDrop &m) {
-    if constexpr (VEC == 4) {
-        float4 q = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-        drop_f4(q, idx0, m);
-        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
-    } else {
-        r.v[0] *= drop_keep(idx0, m.sm, m.p, m.scale);
     }
 }
 
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
     uint64_t ibase = 0;
     if constexpr (DROP) {
         if (dr.out2 != nullptr) o2row = dr.out2 + (int64_t)(live ? row : 0) * dr.ldo2;
-        ibase = dr.m.y_base + (uint64_t)(live ? row : 0) * (uint64_t)dr.m.ld;
+        ibase = dr.offset + (uint64_t)(live ? row : 0) * (uint64_t)dr.mask_ld;
     }
     if (TPR == 64 || d <= kE * TPR) {
         float v[kE];
@@ -263,7 +255,7 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
             }
             if constexpr (DROP) {
                 if (o2row != nullptr) st<VEC>(o2row + c, p);
-                if (dr.m.p > 0.f) mask_pack<VEC>(p, ibase + (uint64_t)c, dr.m);
+                if (dr.m.p > 0.f) drop_vec<VEC>(p.v, ibase + (uint64_t)c, dr.m);
             }
             st<VEC>(orow + c, p);
         }
@@ -498,7 +490,7 @@ extern "C" int gist_ln_affine_fwd_drop_f32(const float *x, int64_t ldx, const fl
     GIST_REQUIRE(mask_ld >= d || p == 0.f, "gist_ln_affine_fwd_drop_f32: mask_ld < d");
     gist::LnaDrop dr{};
     dr.out2 = out2; dr.ldo2 = ldo2;
-    dr.m = gist::spmm_drop_of(1, p, seed, offset, 0, mask_ld);
+    dr.m = gist::drop_mask_of(p, seed); dr.offset = offset; dr.mask_ld = mask_ld;
     return gist::ln_affine_fwd_ex("gist_ln_affine_fwd_drop_f32", x, ldx, lin_bias, gamma, beta, yhat, ldy, out, ldo,
                                   rstd, n_rows, d, relu, eps, &dr, false, gist::as_stream(stream));
 }

@@ -29,44 +29,13 @@ __device__ __forceinline__ float row_sum(float v, float *red) {
     }
 }
 
-// ---------------------------------------------------------------------------
-// dropout's generator: counter based (splitmix64 finaliser of the seed-mixed element index); one hash
-// serves two consecutive elements (even index -> low word, odd -> high word)
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ float keep_scale(uint64_t seed, uint64_t idx, float p, float scale) {
-    const uint64_t h = splitmix64((idx >> 1) + seed * 0x9E3779B97F4A7C15ULL);
-    const uint32_t w = (idx & 1) ? (uint32_t)(h >> 32) : (uint32_t)h;
-    const float u = (float)(w >> 8) * (1.0f / 16777216.0f);
-    return u >= p ? scale : 0.f;
-}
-
-// the mask of gist_dropout_f32 for the 4 consecutive element indices idx0 .. idx0 + 3 (sm = seed *
-// golden ratio): two hashes when idx0 is even, three otherwise
-__device__ __forceinline__ void drop_quad(float4 &v, uint64_t idx0, uint64_t sm, float p, float scale) {
-    const float inv = 1.0f / 16777216.0f;
-    const uint64_t pair = idx0 >> 1;
-    const uint64_t h0 = splitmix64(pair + sm), h1 = splitmix64(pair + 1 + sm);
-    if ((idx0 & 1) == 0) {
-        v.x *= ((float)((uint32_t)h0 >> 8) * inv >= p) ? scale : 0.f;
-        v.y *= ((float)((uint32_t)(h0 >> 32) >> 8) * inv >= p) ? scale : 0.f;
-        v.z *= ((float)((uint32_t)h1 >> 8) * inv >= p) ? scale : 0.f;
-        v.w *= ((float)((uint32_t)(h1 >> 32) >> 8) * inv >= p) ? scale : 0.f;
-    } else {
-        const uint64_t h2 = splitmix64(pair + 2 + sm);
-        v.x *= ((float)((uint32_t)(h0 >> 32) >> 8) * inv >= p) ? scale : 0.f;
-        v.y *= ((float)((uint32_t)h1 >> 8) * inv >= p) ? scale : 0.f;
-        v.z *= ((float)((uint32_t)(h1 >> 32) >> 8) * inv >= p) ? scale : 0.f;
-        v.w *= ((float)((uint32_t)h2 >> 8) * inv >= p) ? scale : 0.f;
-    }
-}
-
 // Dropout folded into a producer (gist_ln_relu_fwd_drop_f32): what the producer stores at row r,
 // column c of `out` is multiplied by the mask gist_dropout_f32 would apply to element index
 // offset + r * mask_ld + c; the value before the mask goes to out2 (the aggregation's source).
 struct DropOut {
     float *out2; int64_t ldo2;      // undropped copy (NULL: none)
-    float p, scale;                 // p = 0: no mask (out = the plain value)
-    uint64_t sm, offset;            // seed * golden ratio; counter base
+    DropMask m;                     // p = 0: no mask (out = the plain value)
+    uint64_t offset;                // counter base
     int64_t mask_ld;
     // the pre-norm input still as split-K slabs of its projection (gist_ln_relu_fwd_slabs_f32): row r, column c =
     // sum_s slabs[s * slab_stride + r * d + c] + bias[c], formed here in gist_gemm's own order (n_slabs = 0: y as is)
@@ -99,19 +68,14 @@ __global__ __launch_bounds__(256) void ln_relu_fwd_kernel(float *__restrict__ y,
     auto put4 = [&](int c, float4 w) {
         if constexpr (DROP) {
             if (o2row != nullptr) *reinterpret_cast<float4 *>(o2row + c) = w;
-            if (dr.p > 0.f) drop_quad(w, ibase + (uint64_t)c, dr.sm, dr.p, dr.scale);
+            if (dr.m.p > 0.f) drop_f4(w, ibase + (uint64_t)c, dr.m);
         }
         *reinterpret_cast<float4 *>(orow + c) = w;
     };
     auto put1 = [&](int c, float v) {
         if constexpr (DROP) {
             if (o2row != nullptr) o2row[c] = v;
-            if (dr.p > 0.f) {
-                const uint64_t idx = ibase + (uint64_t)c;
-                const uint64_t h = splitmix64((idx >> 1) + dr.sm);
-                const uint32_t w = (idx & 1) ? (uint32_t)(h >> 32) : (uint32_t)h;
-                v *= ((float)(w >> 8) * (1.0f / 16777216.0f) >= dr.p) ? dr.scale : 0.f;
-            }
+            if (dr.m.p > 0.f) v *= drop_keep(ibase + (uint64_t)c, dr.m);
         }
         orow[c] = v;
     };
@@ -541,39 +505,33 @@ __global__ __launch_bounds__(256) void colsum_chunks_kernel(const float *__restr
 }
 
 // ---------------------------------------------------------------------------
-// dropout: counter based (splitmix64 finaliser of seed-mixed element index)
+// dropout in place (the generator: dropout.h)
 // ---------------------------------------------------------------------------
 // Fast path (d % 4 == 0, 16-B aligned rows, even offset): one thread = 4 consecutive
 // elements of one row = two hashes, one 16-B load and store, one 64-bit division.
-__global__ void dropout_vec4_kernel(float *__restrict__ z, int64_t ldz, int64_t n_rows, int64_t d,
-                                    float p, float scale, uint64_t seed, uint64_t offset) {
+__global__ void dropout_vec4_kernel(float *__restrict__ z, int64_t ldz, int64_t n_rows, int64_t d, DropMask m,
+                                    uint64_t offset) {
     const int64_t quads = n_rows * (d >> 2);
-    const uint64_t sm = seed * 0x9E3779B97F4A7C15ULL;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads;
          q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t e0 = q << 2;
         const int64_t r = e0 / d, c = e0 - r * d;
         float4 *ptr = reinterpret_cast<float4 *>(z + r * ldz + c);
         float4 v = *ptr;
-        const uint64_t pair = (offset + (uint64_t)e0) >> 1;
-        const uint64_t h0 = splitmix64(pair + sm), h1 = splitmix64(pair + 1 + sm);
-        const float inv = 1.0f / 16777216.0f;
-        v.x *= ((float)((uint32_t)h0 >> 8) * inv >= p) ? scale : 0.f;
-        v.y *= ((float)((uint32_t)(h0 >> 32) >> 8) * inv >= p) ? scale : 0.f;
-        v.z *= ((float)((uint32_t)h1 >> 8) * inv >= p) ? scale : 0.f;
-        v.w *= ((float)((uint32_t)(h1 >> 32) >> 8) * inv >= p) ? scale : 0.f;
+        __builtin_assume((offset & 1) == 0);      // (the launcher's condition: two hashes cover the quad)
+        drop_f4(v, offset + (uint64_t)e0, m);
         *ptr = v;
     }
 }
 
-__global__ void dropout_kernel(float *__restrict__ z, int64_t ldz, int64_t n_rows, int64_t d,
-                               float p, float scale, uint64_t seed, uint64_t offset) {
+__global__ void dropout_kernel(float *__restrict__ z, int64_t ldz, int64_t n_rows, int64_t d, DropMask m,
+                               uint64_t offset) {
     const int64_t total = n_rows * d;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i / d, c = i - r * d;
         float *q = z + r * ldz + c;
-        *q = *q * keep_scale(seed, offset + (uint64_t)i, p, scale);
+        *q = *q * drop_keep(offset + (uint64_t)i, m);
     }
 }
 
@@ -587,8 +545,8 @@ __global__ void dropout_kernel(float *__restrict__ z, int64_t ldz, int64_t n_row
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void narrow_nn_drop_kernel(
     const float *__restrict__ dy, int64_t lddy, const float *__restrict__ w, int64_t ldw,
-    float *__restrict__ dz, int64_t lddz, int n_rows, int n_cols, int kc, float p, float scale,
-    uint64_t seed, uint64_t offset, float *__restrict__ dy_col_partials) {
+    float *__restrict__ dz, int64_t lddz, int n_rows, int n_cols, int kc, DropMask m, uint64_t offset,
+    float *__restrict__ dy_col_partials) {
     __shared__ __attribute__((aligned(16))) float sdy[64][16];
     const int r0 = blockIdx.y * 16;
     const int c0 = blockIdx.x * 1024 + threadIdx.x * 4;
@@ -632,19 +590,14 @@ __global__ __launch_bounds__(256) void narrow_nn_drop_kernel(
     }
     for (; c < kc; ++c)
         fma_row(c, *reinterpret_cast<const float4 *>(w + (int64_t)c * ldw + c0));
-    const uint64_t sm = seed * 0x9E3779B97F4A7C15ULL;
-    const float inv24 = 1.0f / 16777216.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         if (r0 + r >= n_rows) break;
         float4 v = acc[r];
-        if (p > 0.f) {      // offset and n_cols are even, c0 % 4 == 0: two hashes cover the quad
-            const uint64_t pair = (offset + (uint64_t)(r0 + r) * (uint64_t)n_cols + (uint64_t)c0) >> 1;
-            const uint64_t h0 = splitmix64(pair + sm), h1 = splitmix64(pair + 1 + sm);
-            v.x *= ((float)((uint32_t)h0 >> 8) * inv24 >= p) ? scale : 0.f;
-            v.y *= ((float)((uint32_t)(h0 >> 32) >> 8) * inv24 >= p) ? scale : 0.f;
-            v.z *= ((float)((uint32_t)h1 >> 8) * inv24 >= p) ? scale : 0.f;
-            v.w *= ((float)((uint32_t)(h1 >> 32) >> 8) * inv24 >= p) ? scale : 0.f;
+        if (m.p > 0.f) {      // offset and n_cols are even, c0 % 4 == 0: two hashes cover the quad
+            const uint64_t idx0 = offset + (uint64_t)(r0 + r) * (uint64_t)n_cols + (uint64_t)c0;
+            __builtin_assume((idx0 & 1) == 0);
+            drop_f4(v, idx0, m);
         }
         *reinterpret_cast<float4 *>(dz + (int64_t)(r0 + r) * lddz + c0) = v;
     }
@@ -875,7 +828,7 @@ static int ln_relu_fwd_ex(const char *name, float *y, int64_t ldy, float *out, i
     if (n_rows >= (1LL << 31) || d >= (1LL << 31)) { set_error("%s: size >= 2^31", name); return GIST_EINVAL; }
     bool v4 = d % 4 == 0 && ldy % 4 == 0 && ldo % 4 == 0 && aligned16(y) && aligned16(out);
     DropOut dr{};
-    const bool dropping = drop != nullptr && (drop->p > 0.f || drop->out2 != nullptr);
+    const bool dropping = drop != nullptr && (drop->m.p > 0.f || drop->out2 != nullptr);
     if (drop != nullptr && drop->n_slabs > 0) {
         if (drop->slabs == nullptr || drop->slab_stride < n_rows * d) { set_error("%s: bad slabs", name); return GIST_EINVAL; }
         dr.slabs = drop->slabs; dr.slab_stride = drop->slab_stride; dr.n_slabs = drop->n_slabs; dr.bias = drop->bias;
@@ -922,8 +875,7 @@ extern "C" int gist_ln_relu_fwd_drop_f32(float *y, int64_t ldy, float *out, int6
     GIST_REQUIRE(p >= 0.f && p < 1.f, "gist_ln_relu_fwd_drop_f32: p must be in [0,1)");
     GIST_REQUIRE(mask_ld >= d || p == 0.f, "gist_ln_relu_fwd_drop_f32: mask_ld < d");
     gist::DropOut dr{};
-    dr.out2 = out2; dr.ldo2 = ldo2; dr.p = p; dr.scale = p > 0.f ? 1.0f / (1.0f - p) : 1.f;
-    dr.sm = seed * 0x9E3779B97F4A7C15ULL; dr.offset = offset; dr.mask_ld = mask_ld;
+    dr.out2 = out2; dr.ldo2 = ldo2; dr.m = drop_mask_of(p, seed); dr.offset = offset; dr.mask_ld = mask_ld;
     return gist::ln_relu_fwd_ex("gist_ln_relu_fwd_drop_f32", y, ldy, out, ldo, rstd, n_rows, d, use_lynorm,
                                 relu, eps, &dr, gist::as_stream(stream));
 }
@@ -938,8 +890,7 @@ extern "C" int gist_ln_relu_fwd_slabs_f32(float *y, int64_t ldy, const float *sl
     GIST_REQUIRE(n_slabs >= 0 && n_slabs < 4096, "gist_ln_relu_fwd_slabs_f32: bad n_slabs");
     GIST_REQUIRE(n_slabs == 0 || slabs != nullptr, "gist_ln_relu_fwd_slabs_f32: null slabs");
     gist::DropOut dr{};
-    dr.out2 = out2; dr.ldo2 = ldo2; dr.p = p; dr.scale = p > 0.f ? 1.0f / (1.0f - p) : 1.f;
-    dr.sm = seed * 0x9E3779B97F4A7C15ULL; dr.offset = offset; dr.mask_ld = mask_ld;
+    dr.out2 = out2; dr.ldo2 = ldo2; dr.m = drop_mask_of(p, seed); dr.offset = offset; dr.mask_ld = mask_ld;
     dr.slabs = slabs; dr.slab_stride = slab_stride; dr.n_slabs = n_slabs; dr.bias = n_slabs > 0 ? bias : nullptr;
     return gist::ln_relu_fwd_ex("gist_ln_relu_fwd_slabs_f32", y, ldy, out, ldo, rstd, n_rows, d, use_lynorm,
                                 relu, eps, &dr, gist::as_stream(stream));
@@ -1101,16 +1052,17 @@ extern "C" int gist_dropout_f32(float *z, int64_t ldz, int64_t n_rows, int64_t d
     if (n_rows == 0 || d == 0 || p == 0.f) return GIST_OK;
     GIST_REQUIRE(z && ldz >= d, "gist_dropout_f32: bad buffer");
     const int64_t total = n_rows * d;
+    // (offset even: dropout_vec4_kernel ASSUMES it -- __builtin_assume -- and hashes each quad twice)
     if (d % 4 == 0 && ldz % 4 == 0 && aligned16(z) && (offset & 1) == 0) {
         const int64_t quads = total / 4;
         const unsigned grid = (unsigned)(ceil_div(quads, 256) < 16384 ? ceil_div(quads, 256) : 16384);
         hipLaunchKernelGGL(dropout_vec4_kernel, dim3(grid), dim3(256), 0, as_stream(stream), z, ldz,
-                           n_rows, d, p, 1.0f / (1.0f - p), seed, offset);
+                           n_rows, d, drop_mask_of(p, seed), offset);
         return launch_status("gist_dropout_f32");
     }
     const unsigned grid = (unsigned)(ceil_div(total, 256) < 8192 ? ceil_div(total, 256) : 8192);
     hipLaunchKernelGGL(dropout_kernel, dim3(grid), dim3(256), 0, as_stream(stream), z, ldz, n_rows,
-                       d, p, 1.0f / (1.0f - p), seed, offset);
+                       d, drop_mask_of(p, seed), offset);
     return launch_status("gist_dropout_f32");
 }
 
@@ -1125,6 +1077,8 @@ int gemm_nn_dropout_ex(const char *name, const float *g, int64_t ldg, const floa
                         ldw % 4 == 0 && ldz % 4 == 0 && aligned16(w) && aligned16(z) &&
                         (offset & 1) == 0 && ldg >= k && ldw >= n && ldz >= n &&
                         m < (1LL << 31) && n < (1LL << 31);
+    // (offset even and n % 4 == 0 are more than a fast-path choice: narrow_nn_drop_kernel ASSUMES an even first index of
+    // every quad -- __builtin_assume -- so neither condition may be relaxed without that line)
     if (!narrow) {      // any other shape: the projection kernel, then the mask in place
         int rc = gist_gemm_nn_f32(g, ldg, w, ldw, z, ldz, m, n, k, workspace, workspace_bytes, st);
         if (rc == GIST_OK && p != 0.f) rc = gist_dropout_f32(z, ldz, m, n, p, seed, offset, st);
@@ -1132,8 +1086,8 @@ int gemm_nn_dropout_ex(const char *name, const float *g, int64_t ldg, const floa
         return rc;
     }
     hipLaunchKernelGGL(narrow_nn_drop_kernel, dim3((unsigned)ceil_div(n, 1024), (unsigned)ceil_div(m, 16)),
-                       dim3(256), 0, st, g, ldg, w, ldw, z, ldz, (int)m, (int)n, (int)k, p,
-                       p > 0.f ? 1.0f / (1.0f - p) : 1.0f, seed, offset, dy_col_partials);
+                       dim3(256), 0, st, g, ldg, w, ldw, z, ldz, (int)m, (int)n, (int)k, drop_mask_of(p, seed), offset,
+                       dy_col_partials);
     return launch_status(name);
 }
 }  // namespace gist

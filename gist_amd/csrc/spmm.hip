@@ -53,7 +53,7 @@ constexpr int kSpmmWavesPerBlock = 4;
 //   mode 1 (forward):  what the aggregation stores to y is multiplied by y's mask;
 //   mode 2 (backward): x is read through its mask (base = src_base) and the old y of the `y +=` through
 //                      y's -- the aggregation of a gradient whose dropout pass has not run.
-// (drop_keep / drop_vec / drop_f4: common.h -- the matrix-core kernel of spmm_mfma.hip applies the same masks)
+// (drop_keep / drop_vec / drop_f4: dropout.h -- the matrix-core kernel of spmm_mfma.hip applies the same masks)
 template <int VEC, int LPR, bool DROP = false>
 __global__ __launch_bounds__(256) void spmm_csr_kernel(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(
 #pragma unroll
             for (int k = 0; k < VEC; ++k) o[k] = os * acc[k];
         }
-        if constexpr (DROP) drop_vec<VEC>(o, dr.y_base + (uint64_t)row * (uint64_t)dr.ld + (uint64_t)c0, dr);
+        if constexpr (DROP) drop_vec<VEC>(o, dr.y_base + (uint64_t)row * (uint64_t)dr.ld + (uint64_t)c0, dr.m);
         vstore<VEC>(yp, o);
     }
 }
@@ -270,8 +270,8 @@ __global__ __launch_bounds__(256) void spmm_csr_rowsplit_kernel(
             hi[0] = fmaf(os, acc[2], hi[0]); hi[1] = fmaf(os, acc[3], hi[1]);
             if constexpr (DROP) {
                 const uint64_t i0 = dr.y_base + (uint64_t)row * (uint64_t)dr.ld + (uint64_t)c0;
-                drop_vec<2>(lo, i0, dr);
-                drop_vec<2>(hi, i0 + 2, dr);
+                drop_vec<2>(lo, i0, dr.m);
+                drop_vec<2>(hi, i0 + 2, dr.m);
             }
             vstore<2>(yp, lo);
             if (upper) vstore<2>(yp + 2, hi);
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(256) void spmm_csr_rowsplit_kernel(
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) o[k] = os * acc[k];
             }
-            if constexpr (DROP) drop_vec<VEC>(o, dr.y_base + (uint64_t)row * (uint64_t)dr.ld + (uint64_t)c0, dr);
+            if constexpr (DROP) drop_vec<VEC>(o, dr.y_base + (uint64_t)row * (uint64_t)dr.ld + (uint64_t)c0, dr.m);
             vstore<VEC>(yp, o);
         }
     }
@@ -398,7 +398,7 @@ __device__ __forceinline__ void l2_remote(const float *xc, int64_t ldx, bool act
             if (on && active) {
                 rv[t] = *reinterpret_cast<const float4 *>(xc + (int64_t)uu * ldx);
                 if constexpr (SRC_DROP)
-                    drop_f4(rv[t], dr.src_base + (uint64_t)uu * (uint64_t)dr.ld + (uint64_t)c0, dr);
+                    drop_f4(rv[t], dr.src_base + (uint64_t)uu * (uint64_t)dr.ld + (uint64_t)c0, dr.m);
             }
         }
 #pragma unroll
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(kL2Threads) void spmm_csr_lds2_kernel(L2Args a) {
             const int r = wave + t * kL2Waves;
             if (r < nloc) {
                 if constexpr (DROP == 2)
-                    if (active) drop_f4(v[t], a.dr.src_base + (uint64_t)(r0 + r) * (uint64_t)a.dr.ld + (uint64_t)c0, a.dr);
+                    if (active) drop_f4(v[t], a.dr.src_base + (uint64_t)(r0 + r) * (uint64_t)a.dr.ld + (uint64_t)c0, a.dr.m);
                 v[t].x *= sc[t]; v[t].y *= sc[t]; v[t].z *= sc[t]; v[t].w *= sc[t];
                 *reinterpret_cast<float4 *>(tb + (r << 10)) = v[t];
             }
@@ -562,14 +562,14 @@ __global__ __launch_bounds__(kL2Threads) void spmm_csr_lds2_kernel(L2Args a) {
         float4 *yp = reinterpret_cast<float4 *>(a.y + (int64_t)row * a.ldy + c0);
         float4 o = make_float4(fmaf(os, sx, prev.x), fmaf(os, sy, prev.y), fmaf(os, sz, prev.z),
                                fmaf(os, sw, prev.w));
-        if constexpr (DROP == 1) drop_f4(o, a.dr.y_base + (uint64_t)row * (uint64_t)a.dr.ld + (uint64_t)c0, a.dr);
+        if constexpr (DROP == 1) drop_f4(o, a.dr.y_base + (uint64_t)row * (uint64_t)a.dr.ld + (uint64_t)c0, a.dr.m);
         *yp = o;
     };
     auto previous = [&](int lr) {                          // y's old value, read early (accumulate)
         float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
         if (a.accumulate && active) {
             p = *reinterpret_cast<const float4 *>(a.y + (int64_t)(r0 + lr) * a.ldy + c0);
-            if constexpr (DROP == 2) drop_f4(p, a.dr.y_base + (uint64_t)(r0 + lr) * (uint64_t)a.dr.ld + (uint64_t)c0, a.dr);
+            if constexpr (DROP == 2) drop_f4(p, a.dr.y_base + (uint64_t)(r0 + lr) * (uint64_t)a.dr.ld + (uint64_t)c0, a.dr.m);
         }
         return p;
     };
@@ -694,7 +694,7 @@ __global__ void in_degree_norm_kernel(const int32_t *__restrict__ rowptr, int64_
 
 template <int VEC, bool HALF = false>
 static int launch_spmm(const SpmmCall &c) {
-    const bool dropping = c.dr.mode == 1 && c.dr.p > 0.f;
+    const bool dropping = c.dr.mode == 1 && c.dr.m.p > 0.f;
     const SpmmDrop dr = dropping ? c.dr : SpmmDrop{};
     const int lanes = (int)ceil_div(c.d, VEC);
     int lpr = 8;
@@ -768,7 +768,7 @@ static int launch_spmm_lds2(const SpmmCall &c) {
     L2Args a;
     a.dr = SpmmDrop{};
     a.ln = c.ln ? *c.ln : SpmmLnBwd{};
-    const int dmode = c.dr.p > 0.f ? c.dr.mode : 0;
+    const int dmode = c.dr.m.p > 0.f ? c.dr.mode : 0;
     if (dmode) a.dr = c.dr;
     a.rowptr = c.rowptr; a.col = c.col; a.x = c.x; a.ldx = c.ldx; a.y = c.y; a.ldy = c.ldy;
     a.n_rows = (int)c.n_rows; a.d = (int)c.d; a.out_scale = c.out_scale; a.src_scale = c.src_scale;
@@ -887,7 +887,7 @@ SpmmChoice spmm_choose(const SpmmCall &c) {
             return {SPMM_ROWS, false, "this shape cannot carry the mask (use gist_dropout_f32)"};
         if (c.ln != nullptr) {
             const SpmmLnBwd &ln = *c.ln;
-            const bool ok = c.dr.mode == 2 && c.dr.p > 0.f && c.d <= 256 && !D32 && ln.yhat && ln.dy && ln.col_partials &&
+            const bool ok = c.dr.mode == 2 && c.dr.m.p > 0.f && c.d <= 256 && !D32 && ln.yhat && ln.dy && ln.col_partials &&
                             ln.ldy >= c.d && ln.lddy >= c.d && ln.ldy % 4 == 0 && ln.lddy % 4 == 0 && aligned16(ln.yhat) &&
                             aligned16(ln.dy) && aligned16(ln.col_partials);
             return {SPMM_LDS2, false, ok ? nullptr : "this call cannot carry the LayerNorm backward"};
@@ -920,7 +920,7 @@ int spmm_run(const SpmmCall &c) {
     GIST_REQUIRE(c.n_rows < (1LL << 31) && c.d < (1LL << 31), "%s: size >= 2^31", c.entry);
     GIST_REQUIRE(c.blocks != SPMM_BLOCKS_GIVEN || c.n_row_blocks > 0, "%s: row_blocks given but n_row_blocks <= 0", c.entry);
     GIST_REQUIRE(c.dr.mode >= 0, "%s: mode must be 1 or 2", c.entry);
-    GIST_REQUIRE(c.dr.mode == 0 || (c.dr.p >= 0.f && c.dr.p < 1.f && c.dr.ld >= c.d), "%s: bad mask description", c.entry);
+    GIST_REQUIRE(c.dr.mode == 0 || (c.dr.m.p >= 0.f && c.dr.m.p < 1.f && c.dr.ld >= c.d), "%s: bad mask description", c.entry);
     const SpmmChoice ch = spmm_choose(c);
     GIST_REQUIRE(ch.refusal == nullptr, "%s: %s", c.entry, ch.refusal);
     switch (ch.kernel) {

@@ -42,7 +42,7 @@ template <int MODE>
 __device__ __forceinline__ float d32_src(const D32Args &a, int g_row, int col) {      // scaled, masked x[g_row][col]
     float v = a.x[(int64_t)g_row * a.ldx + col];
     if constexpr (MODE == 2)      // (the mask first, then the scale: as gist_dropout_f32 in front of the plain call)
-        v *= drop_keep(a.dr.src_base + (uint64_t)g_row * (uint64_t)a.dr.ld + (uint64_t)col, a.dr.sm, a.dr.p, a.dr.scale);
+        v *= drop_keep(a.dr.src_base + (uint64_t)g_row * (uint64_t)a.dr.ld + (uint64_t)col, a.dr.m);
     if (a.src_scale) v *= a.src_scale[g_row];
     return v;
 }
@@ -56,11 +56,11 @@ __device__ __forceinline__ void d32_store(const D32Args &a, int g_row, int col, 
     if (a.accumulate) {
         float old = *o;
         // (__fmul_rn: no contraction into an FMA with the add -- the separate dropout pass rounds the product)
-        if constexpr (MODE == 2) old = __fmul_rn(old, drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale));
+        if constexpr (MODE == 2) old = __fmul_rn(old, drop_keep(yi, a.dr.m));
         v += old;
     }
     // (mode 1 masks the whole stored value, the old y included: the dropout pass behind the plain call)
-    if constexpr (MODE == 1) v *= drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale);
+    if constexpr (MODE == 1) v *= drop_keep(yi, a.dr.m);
     *o = v;
 }
 
@@ -223,10 +223,10 @@ __global__ __launch_bounds__(256) void spmm_dense32_kernel(D32Args a) {
                 const uint64_t yi = a.dr.y_base + (uint64_t)g_row * (uint64_t)a.dr.ld + (uint64_t)col;
                 if (a.accumulate) {
                     float o_ = old[t][i];
-                    if constexpr (MODE == 2) o_ = __fmul_rn(o_, drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale));
+                    if constexpr (MODE == 2) o_ = __fmul_rn(o_, drop_keep(yi, a.dr.m));
                     v += o_;
                 }
-                if constexpr (MODE == 1) v *= drop_keep(yi, a.dr.sm, a.dr.p, a.dr.scale);
+                if constexpr (MODE == 1) v *= drop_keep(yi, a.dr.m);
                 a.y[(int64_t)g_row * a.ldy + col] = v;
             }
         }

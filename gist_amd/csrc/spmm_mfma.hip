@@ -726,7 +726,7 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 if constexpr (DROP == 1) {
                     int rv_ = r;                       // (opaque: hoisted out of the tile loop, the four row
                     asm volatile("" : "+v"(rv_));      // products r * dld were spilled to scratch)
-                    drop_f4(o, dyb + (uint32_t)(rv_ * dld + gc), a.dr);
+                    drop_f4(o, dyb + (uint32_t)(rv_ * dld + gc), a.dr.m);
                 }
                 *reinterpret_cast<float4 *>(yblk + (uint32_t)(r * ldy32 + gc)) = o;
             }
@@ -747,7 +747,7 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 if (a.accumulate) yo = *reinterpret_cast<const float4 *>(yp);
                 const float s = a.out_scale ? a.out_scale[r0 + r] : 1.f;
                 float4 o = make_float4(fmaf(s, vo.x, yo.x), fmaf(s, vo.y, yo.y), fmaf(s, vo.z, yo.z), fmaf(s, vo.w, yo.w));
-                if constexpr (DROP == 1) drop_f4(o, yi, a.dr);
+                if constexpr (DROP == 1) drop_f4(o, yi, a.dr.m);
                 *reinterpret_cast<float4 *>(yp) = o;
             }
         }
@@ -898,7 +898,7 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 if constexpr (DROP == 1) {
                     int rv_ = r;                       // (opaque: hoisted out of the tile loop, the four row
                     asm volatile("" : "+v"(rv_));      // products r * dld were spilled to scratch)
-                    drop_f4(o, dyb + (uint32_t)(rv_ * dld + gc), a.dr);
+                    drop_f4(o, dyb + (uint32_t)(rv_ * dld + gc), a.dr.m);
                 }
                 *reinterpret_cast<float4 *>(yblk + (uint32_t)(r * ldy32 + gc)) = o;
             }
@@ -919,7 +919,7 @@ __device__ __forceinline__ void mf_body(const MfArgs &a, unsigned char *mf_smem,
                 if (a.accumulate) yo = *reinterpret_cast<const float4 *>(yp);
                 const float s = a.out_scale ? a.out_scale[r0 + r] : 1.f;
                 float4 o = make_float4(fmaf(s, vo.x, yo.x), fmaf(s, vo.y, yo.y), fmaf(s, vo.z, yo.z), fmaf(s, vo.w, yo.w));
-                if constexpr (DROP == 1) drop_f4(o, yi, a.dr);
+                if constexpr (DROP == 1) drop_f4(o, yi, a.dr.m);
                 *reinterpret_cast<float4 *>(yp) = o;
             }
         }

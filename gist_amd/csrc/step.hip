@@ -129,7 +129,7 @@ H3Step h3_layout(const gist_step_plan *p, char *base, int mode) {
         return q;
     };
     int64_t max_out = 0;
-    const double keep = p->p_drop > 0.f ? 1.0 / (1.0 - (double)p->p_drop) : 1.0;
+    const double keep = drop_scale_of(p->p_drop);      // the fp32 factor the kernels multiply a kept element by
     for (int k = 0; k < L1; ++k) {
         const gist_layer_desc &l = p->layer[k];
         const int64_t i2 = 2 * l.n_in, o = l.n_out;

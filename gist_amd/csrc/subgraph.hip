@@ -190,15 +190,10 @@ __global__ __launch_bounds__(256) void induced_fill2_kernel(CsrPair p,
 // source of layer 0's aggregation).
 struct GatherDrop {
     float *x0; int64_t ldx0;
-    float p, scale;
-    uint64_t sm, offset;
+    DropMask m;
+    uint64_t offset;
     int64_t mask_ld;
 };
-__device__ __forceinline__ float gather_keep(uint64_t idx, const GatherDrop &g) {
-    const uint64_t h = splitmix64((idx >> 1) + g.sm);
-    const uint32_t w = (idx & 1) ? (uint32_t)(h >> 32) : (uint32_t)h;
-    return ((float)(w >> 8) * (1.0f / 16777216.0f) >= g.p) ? g.scale : 0.f;
-}
 
 // features + label of batch row i, and remap[ids[i]] back to -1 (runs after both fills)
 template <int VEC, bool DROP = false>
@@ -226,7 +221,7 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const float *__restri
 #pragma unroll
             for (int k = 0; k < VEC; ++k) o2[c + k] = t[k];
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) o[c + k] = t[k] * gather_keep(i0 + k, gd);
+            for (int k = 0; k < VEC; ++k) o[c + k] = t[k] * drop_keep(i0 + k, gd.m);
             continue;
         }
         if constexpr (VEC == 4) *reinterpret_cast<float4 *>(o + c) = *reinterpret_cast<const float4 *>(s + c);
@@ -348,7 +343,7 @@ __device__ __forceinline__ void aggregate_row_regs(const PartsArgs &a, const int
         const int c = t * kWave + lane;
         if (c >= a.d) continue;
         float val = acc[t] * nrm;
-        if (a.drop) val *= gather_keep(i0 + (uint64_t)c, a.gd);
+        if (a.drop) val *= drop_keep(i0 + (uint64_t)c, a.gd.m);
         o[c] = val;
     }
 }
@@ -402,7 +397,7 @@ __device__ __forceinline__ void extract_parts_block(const PartsArgs &a, const in
                 if (c >= a.d) continue;
                 if (a.drop) {
                     o2[c] = t[u];
-                    o[c] = t[u] * gather_keep(i0 + (uint64_t)c, a.gd);
+                    o[c] = t[u] * drop_keep(i0 + (uint64_t)c, a.gd.m);
                 } else {
                     o[c] = t[u];
                 }
@@ -535,7 +530,7 @@ __device__ __forceinline__ void extract_parts_block(const PartsArgs &a, const in
                 const int c = c0 + t * kWave + lane;
                 if (c >= a.d) continue;
                 float val = acc[t] * nrm;
-                if (a.drop) val *= gather_keep(i0 + (uint64_t)c, a.gd);
+                if (a.drop) val *= drop_keep(i0 + (uint64_t)c, a.gd.m);
                 o[c] = val;
             }
         }
@@ -929,7 +924,7 @@ static int extract_impl(const int32_t *g_rowptr, const int32_t *g_col,
     GatherDrop gd{};
     if (drop != nullptr) {
         gd = *drop;
-        GIST_REQUIRE(gd.x0 != nullptr && gd.ldx0 >= n_feat && gd.mask_ld >= n_feat && gd.p >= 0.f && gd.p < 1.f,
+        GIST_REQUIRE(gd.x0 != nullptr && gd.ldx0 >= n_feat && gd.mask_ld >= n_feat && gd.m.p >= 0.f && gd.m.p < 1.f,
                      "gist_extract_batch_drop: bad dropout arguments");
         if (n_feat % 2 == 0)
             hipLaunchKernelGGL((gather_batch_kernel<2, true>), dim3(nb4), dim3(256), 0, st, feat, ld_feat, ids,
@@ -974,8 +969,7 @@ extern "C" int gist_extract_batch_drop(const int32_t *g_rowptr, const int32_t *g
                                        float p, uint64_t seed, uint64_t offset, int64_t mask_ld,
                                        gist_stream_t stream) {
     GatherDrop gd{};
-    gd.x0 = x0; gd.ldx0 = ldx0; gd.p = p; gd.scale = (p > 0.f && p < 1.f) ? 1.0f / (1.0f - p) : 1.f;
-    gd.sm = seed * 0x9E3779B97F4A7C15ULL; gd.offset = offset; gd.mask_ld = mask_ld;
+    gd.x0 = x0; gd.ldx0 = ldx0; gd.m = drop_mask_of(p, seed); gd.offset = offset; gd.mask_ld = mask_ld;
     return extract_impl(g_rowptr, g_col, g_t_rowptr, g_t_col, ids, n, remap, rowptr, col, t_rowptr, t_col,
                         col_capacity, norm, feat, ld_feat, n_feat, z0, ldz0, labels_all, labels, &gd, stream);
 }
@@ -1023,8 +1017,7 @@ static int parts_args(const char *name, const gist_extract_parts_desc &x, PartsA
     if (x.x0 != nullptr) {
         GIST_REQUIRE(x.ldx0 >= x.n_feat && x.mask_ld >= x.n_feat && x.p >= 0.f && x.p < 1.f, "%s: bad dropout arguments", name);
         a.drop = 1;
-        a.gd.x0 = x.x0; a.gd.ldx0 = x.ldx0; a.gd.p = x.p; a.gd.scale = x.p > 0.f ? 1.0f / (1.0f - x.p) : 1.f;
-        a.gd.sm = x.seed * 0x9E3779B97F4A7C15ULL; a.gd.offset = x.offset; a.gd.mask_ld = x.mask_ld;
+        a.gd.x0 = x.x0; a.gd.ldx0 = x.ldx0; a.gd.m = drop_mask_of(x.p, x.seed); a.gd.offset = x.offset; a.gd.mask_ld = x.mask_ld;
     }
     if (x.ah != nullptr) {
         GIST_REQUIRE(x.feat_intra != nullptr && x.ld_intra >= x.n_feat, "%s: bad feat_intra", name);

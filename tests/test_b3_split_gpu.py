@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import dropout_ref
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
@@ -27,17 +29,7 @@ def _dropped(x, p, seed, offset):
     if p <= 0.0:
         return x
     n, d = x.shape
-    idx = np.arange(n * d, dtype=np.uint64) + np.uint64(offset)
-    with np.errstate(over='ignore'):
-        z = (idx >> np.uint64(1)) + np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    w = np.where(idx & np.uint64(1), z >> np.uint64(32), z & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    u = (w >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-    keep = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
-    scale = np.where(u >= np.float32(p), keep, np.float32(0.0)).astype(np.float32).reshape(n, d)
-    return x * scale
+    return x * dropout_ref.factors(n, d, p, seed, offset)
 
 
 def _split_ref(x):
@@ -124,6 +116,14 @@ def test_one_layout(hip, want_r, want_t):
 @pytest.mark.parametrize('rows,cols,shift', [(257, 300, 0), (129, 67, 1)])
 def test_dropout_odd_offset(hip, rows, cols, shift):
     _check(hip, rows, cols, ld=cols + 5, shift=shift, p=0.3, seed=12345, offset=1001, partials=True)
+
+
+@pytest.mark.parametrize('want_r,want_t', [(True, True), (False, True)])
+def test_dropout_odd_offset_on_the_16_byte_loads(hip, want_r, want_t):
+    # 65 x 68, ld = 68, aligned: one whole 64-column tile on the float4 loads, the row and the column edge; every quad's
+    # first mask index is odd (68 is even); p = 0 on the same call
+    _check(hip, 65, 68, p=0.3, seed=12345, offset=1001, want_r=want_r, want_t=want_t, partials=True)
+    _check(hip, 65, 68, p=0.0, seed=12345, offset=1001, want_r=want_r, want_t=want_t, partials=True)
 
 
 def test_nothing_past_the_padding(hip):

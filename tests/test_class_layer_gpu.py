@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import dropout_ref
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
@@ -19,16 +21,7 @@ def hip():
     return h
 
 
-def _mask(n, d, p, seed, offset):
-    idx = np.arange(n * d, dtype=np.uint64) + np.uint64(offset)
-    with np.errstate(over='ignore'):
-        z = (idx >> np.uint64(1)) + np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    w = np.where(idx & np.uint64(1), z >> np.uint64(32), z & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    u = (w >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-    return (u >= np.float32(p)).reshape(n, d)
+_mask = dropout_ref.keep_mask      # (n, d, p, seed, offset) -> bool [n, d]
 
 
 @pytest.mark.parametrize('n,c,k,p,with_dz', [
@@ -36,6 +29,16 @@ def _mask(n, d, p, seed, offset):
     (50, 7, 64, 0.5, True), (17, 3, 128, 0.0, True), (300, 48, 192, 0.2, True), (2046, 41, 256, 0.2, True),
     (333, 41, 1024, 0.0, False), (16, 1, 64, 0.2, True)])
 def test_class_layer_against_float64(hip, n, c, k, p, with_dz):
+    _class_layer_case(hip, n, c, k, p, with_dz, 2 * 77)
+
+
+@pytest.mark.parametrize('n,c,k', [(50, 7, 64), (17, 3, 128)])
+def test_class_layer_odd_mask_offset(hip, n, c, k):
+    """dZ's mask with an odd first index (every row's: k is even), zero pattern against the host generator"""
+    _class_layer_case(hip, n, c, k, 0.5, True, 155)
+
+
+def _class_layer_case(hip, n, c, k, p, with_dz, off):
     rs = np.random.RandomState(n + c + k)
     ldz, ldc = k + 8, (c + 3) // 4 * 4
     z = (rs.randn(n, ldz) * 0.7).astype(np.float32)
@@ -51,7 +54,7 @@ def test_class_layer_against_float64(hip, n, c, k, p, with_dz):
     dz = torch.full((n, k + 4), 9.0, device=DEV) if with_dz else None
     chunks = (n + 15) // 16
     part = torch.full((chunks * c,), 5.0, device=DEV)
-    seed, off = 1234, 2 * 77
+    seed = 1234
     hip.class_layer(zt[:, :k], wt, bt, lt, n, logits[:, :c], dlog, row_loss, dz[:, :k] if with_dz else None, p, seed,
                     off, part)
     z64, w64 = z[:, :k].astype(np.float64), w.astype(np.float64)

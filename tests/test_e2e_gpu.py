@@ -301,6 +301,19 @@ def test_native_step_kept_splits_small_batch(n_layers, n_feats, n_hidden, split)
     threshold lowered through the tuning hooks: 256 x 128 tiles, this batch has 32 of them) against
     the same step in mode f32, same dropout stream -- losses of 4 steps within 1e-4 (of their magnitude: this toy run
     diverges to losses ~20), parameters close."""
+    _kept_splits_against_f32(n_layers, n_feats, n_hidden, split, 0)
+
+
+def test_native_step_kept_splits_odd_mask_offset():
+    """The same comparison in mode f16x3 with the dropout counter started at an odd value: every layer's mask offset is odd
+    (a layer advances the counter by an even count), n_feats and n_hidden are even, so every quad h3_dual_split_kernel masks
+    starts on an odd index.  The f32 step's masks come from other kernels (the extraction, the LayerNorm tail, the
+    aggregation, gist_dropout_f32) at the same offsets: a wrong word in the split's odd-index path is another mask on Z
+    than the backward's and the f32 run's, far outside the bounds."""
+    _kept_splits_against_f32(2, 64, 2048, 'f16x3', 1001)
+
+
+def _kept_splits_against_f32(n_layers, n_feats, n_hidden, split, drop_calls):
     from gist_amd import datasets, hip
     from gist_amd.engine import SageEngine, dims_for
     from gist_amd.sampler import EngineClusterIter
@@ -325,6 +338,7 @@ def test_native_step_kept_splits_small_batch(n_layers, n_feats, n_hidden, split)
                 s_ = 1.0 / np.sqrt(2 * i)
                 eng.arena.W[k].copy_((torch.rand(o, 2 * i, generator=gen) - 0.5) * 2 * s_)
                 eng.arena.b[k].copy_((torch.rand(o, generator=gen) - 0.5) * 2 * s_)
+            eng.drop_calls = drop_calls
             it.bind(eng)
             assert (eng.plan.h3_workspace is not None) == (mode != 'f32')
             losses = []

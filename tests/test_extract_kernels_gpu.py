@@ -625,10 +625,10 @@ def scratch_is_clean(scratch):
 class PartsLaunch(object):
     """one gist_extract_parts_desc (and everything it points to) for batch j of an epoch; nothing here synchronises"""
 
-    def __init__(self, epoch, j, d, kind, geom, scratch, n_max=None, cap=None, drop_offset=None, with_ah=True):
+    def __init__(self, epoch, j, d, kind, geom, scratch, n_max=None, cap=None, drop_offset=None, with_ah=True, p=P_DROP):
         from gist_amd import _lib
         S = self.S = ref_struct(epoch, j)
-        self.d, self.kind, self.drop_offset, self.with_ah = d, kind, drop_offset, with_ah
+        self.d, self.kind, self.drop_offset, self.with_ah, self.p = d, kind, drop_offset, with_ah, p
         ldf, ldi, ldz, ldx, self.mask_ld = geom
         self.feat, self.intra = features(S.G.name, d, kind)
         dg = dev_graph(S.G.name)
@@ -655,7 +655,7 @@ class PartsLaunch(object):
         x.labels_all = dg.labels.data_ptr()
         if drop_offset is not None:
             x.x0, x.ldx0 = self.x0.mat.data_ptr(), ldx
-            x.p, x.seed, x.offset, x.mask_ld = P_DROP, SEED, drop_offset, self.mask_ld
+            x.p, x.seed, x.offset, x.mask_ld = p, SEED, drop_offset, self.mask_ld
         x.scratch = scratch.data_ptr()
         if with_ah:
             x.feat_intra, x.ld_intra = self.it.mat.data_ptr(), ldi
@@ -683,23 +683,23 @@ class PartsLaunch(object):
             assert bits_equal(wins[0], want)
             self.x0.windows(n, [])
         else:
-            m = mask_at(n, d, P_DROP, self.drop_offset, self.mask_ld)
-            assert bits_equal(wins[0], R.dropped(want, m, P_DROP)), 'z0 is not the dropped features'
+            m = mask_at(n, d, self.p, self.drop_offset, self.mask_ld)
+            assert bits_equal(wins[0], R.dropped(want, m, self.p)), 'z0 is not the dropped features'
             assert bits_equal(self.x0.windows(n, [(0, d)])[0], want), 'x0 is not the features'
         if self.with_ah:
             if self.drop_offset is None:
                 r = cmp_ah(S, self.kind, self.feat, self.intra, ah, fam)
                 assert r <= 1.0, ('ah err / bound', r)
             else:
-                m = mask_at(n, d, P_DROP, self.drop_offset, self.mask_ld, d)
-                assert bits_equal(ah, R.dropped(plain_ah, m, P_DROP)), 'ah is not the dropped aggregation'
+                m = mask_at(n, d, self.p, self.drop_offset, self.mask_ld, d)
+                assert bits_equal(ah, R.dropped(plain_ah, m, self.p)), 'ah is not the dropped aggregation'
         return ah
 
 
-def plain_then_dropped(hip, epoch, j, d, kind, geom, offset, scratch, n_max=None):
+def plain_then_dropped(hip, epoch, j, d, kind, geom, offset, scratch, n_max=None, p=P_DROP):
     """the same batch without and with layer 0's dropout, back to back on one scratch; both checked"""
     a = PartsLaunch(epoch, j, d, kind, geom, scratch, n_max=n_max).launch(hip)
-    b = PartsLaunch(epoch, j, d, kind, geom, scratch, n_max=n_max, drop_offset=offset).launch(hip)
+    b = PartsLaunch(epoch, j, d, kind, geom, scratch, n_max=n_max, drop_offset=offset, p=p).launch(hip)
     torch.cuda.synchronize()
     b.check(plain_ah=a.check())
     assert scratch_is_clean(scratch)
@@ -721,6 +721,14 @@ def test_parts_batch_sizes(hip, epoch, j, d):
     S = ref_struct(epoch, j)
     n_max = S.n + (40 if S.n == 17 else 5)
     plain_then_dropped(hip, epoch, j, d, 'int', width_geom(d, S.n), OFFSETS[S.n % 3], new_scratch(n_max), n_max=n_max)
+
+
+@pytest.mark.parametrize('d', [20, 7])
+def test_parts_dropout_with_p_zero(hip, d):
+    """p = 0 with x0 given: the mask code runs with a factor of 1 everywhere -- z0 and ah are the plain launch's bits
+    (an odd first index, an even and an odd width)"""
+    S = ref_struct('spec', 0)
+    plain_then_dropped(hip, 'spec', 0, d, 'gauss', width_geom(d, 1), 77, new_scratch(S.n + 5), p=0.0)
 
 
 @pytest.mark.parametrize('kind', CAP_KINDS)
@@ -764,7 +772,7 @@ def test_parts_many_launches_on_one_scratch(hip):
 # ========================================================================================================================
 # the five-launch extraction
 # ========================================================================================================================
-def _five_launch(hip, case, cap=None):
+def _five_launch(hip, case, cap=None, p=P_DROP):
     n, d, ldf, ldz, off_f, off_z, drop, offset = case
     S = ref_struct('big', 0, n)
     dg = dev_graph('big')
@@ -782,7 +790,7 @@ def _five_launch(hip, case, cap=None):
             z.view(n, 0, d), dg.labels, out['labels'])
     mask_ld = d + 5
     if drop:
-        hip.extract_batch_drop(*args, x0.view(n, 0, d), P_DROP, SEED, offset, mask_ld)
+        hip.extract_batch_drop(*args, x0.view(n, 0, d), p, SEED, offset, mask_ld)
     else:
         hip.extract_batch(*args)
     torch.cuda.synchronize()
@@ -790,7 +798,7 @@ def _five_launch(hip, case, cap=None):
     assert struct_mismatches(S, cap, n_max, col_len, got) == []
     want = gather_ref(feat, S.ids)
     if drop:
-        assert bits_equal(z.windows(n, [(0, d)])[0], R.dropped(want, mask_at(n, d, P_DROP, offset, mask_ld), P_DROP))
+        assert bits_equal(z.windows(n, [(0, d)])[0], R.dropped(want, mask_at(n, d, p, offset, mask_ld), p))
         assert bits_equal(x0.windows(n, [(0, d)])[0], want)
     else:
         assert bits_equal(z.windows(n, [(0, d)])[0], want)
@@ -802,6 +810,12 @@ def _five_launch(hip, case, cap=None):
 @pytest.mark.parametrize('case', FIVE_CASES, ids=lambda c: '-'.join(str(v) for v in c))
 def test_five_launch_extraction(hip, case):
     _five_launch(hip, case)
+
+
+@pytest.mark.parametrize('d', [12, 13])
+def test_five_launch_dropout_with_p_zero(hip, d):
+    """p = 0 through gist_extract_batch_drop (gather_batch_kernel<2 | 1, true>), an odd first index: z0 = x0 = the features"""
+    _five_launch(hip, (17, d, d + 3, d + 3, 0, 0, True, 77), p=0.0)
 
 
 @pytest.mark.parametrize('drop', [False, True])

@@ -70,6 +70,48 @@ def test_spmm_forward_mask_equals_dropout_after(hip, n, d, blocks):
     assert 0.2 < frac < 0.45          # the mask is really applied
 
 
+# (n, d, row blocks given, is mode 2 taken: only the LDS-staged kernel carries it -- 16-byte rows of 128 <= d < 1536 on given
+# blocks, spmm_choose; the other shapes run the lane-group / row-split kernels in mode 1)
+@pytest.mark.parametrize('n,d,blocks,mode2', [(257, 100, True, False), (300, 128, True, True), (300, 128, False, False),
+                                              (130, 64, False, False), (200, 256, True, True)])
+def test_spmm_masks_at_odd_offsets(hip, n, d, blocks, mode2):
+    """Both modes with odd mask offsets (every quad of a 16-byte kernel starts on an odd index) on the lane-group / row-split
+    and the LDS-staged kernels, bit for bit against the plain aggregation under the host generator's factors
+    (tests/dropout_ref.py); p = 0 is the plain call.  (The matrix-core kernels: tests/test_kernels_gpu.py, the fp32
+    block-dense one: tests/test_spmm_dense32_gpu.py.)"""
+    from tests import dropout_ref
+    rp, cl, trp, tcl, rb = block_graph(n, 5, 10, 3, seed=n + d, hub=60)
+    rbs = rb if blocks else None
+    gen = torch.Generator(device=DEV).manual_seed(3)
+    norm = hip.in_degree_norm(rp)
+    p, seed, off = 0.3, 17, 1001
+    fac = lambda base: torch.from_numpy(dropout_ref.factors(n, d, p, seed, base, 2 * d)).to(DEV)
+    # mode 1
+    x = torch.randn(n, d, device=DEV, generator=gen)
+    z_ref, z_new, z_p0 = (torch.zeros(n, 2 * d, device=DEV) for _ in range(3))
+    assert hip.spmm_drop_takes(1, d, x, z_new[:, d:], blocks)
+    hip.spmm(rp, cl, x, z_ref[:, d:], out_scale=norm, row_blocks=rbs)
+    hip.spmm_drop(rp, cl, x, z_new[:, d:], 1, p, seed, off + d, 0, 2 * d, out_scale=norm, row_blocks=rbs)
+    assert torch.equal(z_new[:, d:], z_ref[:, d:] * fac(off + d))
+    hip.spmm_drop(rp, cl, x, z_p0[:, d:], 1, 0.0, seed, off + d, 0, 2 * d, out_scale=norm, row_blocks=rbs)
+    assert torch.equal(z_p0[:, d:], z_ref[:, d:])
+    # mode 2
+    dz = torch.randn(n, 2 * d, device=DEV, generator=gen)
+    assert hip.spmm_drop_takes(2, d, dz[:, d:], dz[:, :d], blocks) == mode2
+    if mode2:
+        ref, new, p0, plain = dz.clone(), dz.clone(), dz.clone(), dz.clone()
+        ref[:, :d] *= fac(off)
+        ref[:, d:] *= fac(off + d)
+        hip.spmm(trp, tcl, ref[:, d:], ref[:, :d], src_scale=norm, accumulate=True, row_blocks=rbs)
+        hip.spmm_drop(trp, tcl, new[:, d:], new[:, :d], 2, p, seed, off, off + d, 2 * d, src_scale=norm, accumulate=True,
+                      row_blocks=rbs)
+        assert torch.equal(new[:, :d], ref[:, :d])
+        hip.spmm(trp, tcl, plain[:, d:], plain[:, :d], src_scale=norm, accumulate=True, row_blocks=rbs)
+        hip.spmm_drop(trp, tcl, p0[:, d:], p0[:, :d], 2, 0.0, seed, off, off + d, 2 * d, src_scale=norm, accumulate=True,
+                      row_blocks=rbs)
+        assert torch.equal(p0[:, :d], plain[:, :d])
+
+
 @pytest.mark.parametrize('n,d', [(700, 512), (333, 128), (900, 1024)])
 def test_spmm_backward_masks_equal_dropout_before(hip, n, d):
     """mode 2: the reverse aggregation of a gradient whose dropout pass has not run == dropout on

@@ -702,6 +702,32 @@ def test_spmm_sibling_parts_as_dense_pairs(hip, d):
     close(xft, reff)
 
 
+@pytest.mark.parametrize('d', [2048, 1540])
+def test_spmm_matrix_core_mask_at_an_odd_offset(hip, d):
+    """Mode 1 on the matrix-core kernels with an odd mask offset -- every stored quad starts on an odd index: prepared (a
+    batch with sibling parts, so the pairs kernel stores rows too) and unprepared, each BIT FOR BIT the plain call of the
+    same kernel times the host generator's factors (tests/dropout_ref.py); p = 0: the plain call's bits."""
+    from tests import dropout_ref
+    rs = np.random.RandomState(d + 1)
+    n, cuts, src, dst = _sibling_graph(rs, extra_hub=500)
+    rowptr, col = O.csr_from_edges(src, dst, n)
+    rb, rp, cl = dev(cuts, torch.int32), dev(rowptr, torch.int32), dev(col, torch.int32)
+    norm = dev(O.in_degree_norm(rowptr))
+    prep = hip.spmm_prepare(rp, cl, rb)
+    x = dev(rs.randn(n, d).astype(np.float32))
+    p_, seed, off = 0.3, 11, 1001
+    fac = dev(dropout_ref.factors(n, d, p_, seed, off + d, 2 * d))
+    assert float((fac == 0).float().mean().item()) > 0.2
+    for pr in (prep, None):
+        plain, got, got0 = (torch.zeros(n, 2 * d, device=DEV) for _ in range(3))
+        hip.spmm(rp, cl, x, plain[:, d:], out_scale=norm, row_blocks=rb, blocked=True, prepared=pr)
+        hip.spmm_drop(rp, cl, x, got[:, d:], 1, p_, seed, off + d, off, 2 * d, out_scale=norm, row_blocks=rb, prepared=pr)
+        hip.spmm_drop(rp, cl, x, got0[:, d:], 1, 0.0, seed, off + d, off, 2 * d, out_scale=norm, row_blocks=rb, prepared=pr)
+        assert torch.equal(got[:, d:], plain[:, d:] * fac), 'prepared' if pr is not None else 'unprepared'
+        assert torch.equal(got0[:, d:], plain[:, d:])
+        assert bool((got[:, :d] == 0).all()) and bool((got0[:, :d] == 0).all())
+
+
 def _phased_sibling_step(fwd_pairs, bwd_pairs):
     """One training iteration of gist_sage_step as its three phase calls (the module path's form) on a batch with two pairs
     of sibling parts, width 2048 (the layer-1 aggregations on the prepared matrix-core kernel), plan.sibling_parts =

@@ -145,6 +145,24 @@ def test_dense32_masks_equal_dropout_around_the_plain_call(hip, n, d):
         assert torch.equal(new[:, :d] == 0, ref[:, :d] == 0)
 
 
+def test_dense32_forward_mask_at_an_odd_offset(hip):
+    """Mode 1 with an odd mask offset, bit for bit against the plain prepared call under the host generator's factors
+    (tests/dropout_ref.py); p = 0 is the plain call."""
+    from tests import dropout_ref
+    n, d = 300, 128
+    _, (rp, cl, trp, tcl, rb) = _graph(n, np.linspace(0, n, 4).astype(int), 10, 3, seed=n, hub=30)
+    norm = hip.in_degree_norm(rp)
+    prep = hip.spmm_prepare(rp, cl, rb)
+    x = torch.randn(n, d, device=DEV, generator=torch.Generator(device=DEV).manual_seed(4))
+    z_ref, z_new, z_p0 = (torch.zeros(n, 2 * d, device=DEV) for _ in range(3))
+    hip.spmm(rp, cl, x, z_ref[:, d:], out_scale=norm, row_blocks=rb, prepared=prep)
+    hip.spmm_drop(rp, cl, x, z_new[:, d:], 1, 0.3, 17, 1001 + d, 0, 2 * d, out_scale=norm, row_blocks=rb, prepared=prep)
+    fac = torch.from_numpy(dropout_ref.factors(n, d, 0.3, 17, 1001 + d, 2 * d)).to(DEV)
+    assert torch.equal(z_new[:, d:], z_ref[:, d:] * fac)
+    hip.spmm_drop(rp, cl, x, z_p0[:, d:], 1, 0.0, 17, 1001 + d, 0, 2 * d, out_scale=norm, row_blocks=rb, prepared=prep)
+    assert torch.equal(z_p0[:, d:], z_ref[:, d:])
+
+
 def test_dense32_row_tile_groups_agree(hip):
     """The launcher's split of a block's row tiles over 2 or 4 waves changes no value (tuning hook spmm_split)."""
     n, d = 700, 256

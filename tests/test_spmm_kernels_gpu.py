@@ -36,6 +36,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import dropout_ref
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device('cuda', 0)
@@ -516,26 +518,12 @@ def case_coverage():
 
 
 # -- reference and checks ----------------------------------------------------------------------------------------------
-def mask_keep(idx, p):
-    """gist_dropout_f32's keep decision of mask indices idx (uint64 numpy)."""
-    with np.errstate(over='ignore'):
-        z = (idx >> np.uint64(1)) + np.uint64(SEED) * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    w = np.where(idx & np.uint64(1), z >> np.uint64(32), z & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    return (w >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0) >= np.float32(p)
-
-
 SEED, P = 29, 0.5                      # p = 0.5: keep scale 2, exact, so the integer cases stay exact under the masks
 
 
 def mask64(n, d, base, ld):
     """float64 [n, d] mask value (0 or the fp32 keep scale) of element (r, c) = index base + r * ld + c."""
-    idx = (np.uint64(base) + np.arange(n, dtype=np.uint64)[:, None] * np.uint64(ld)
-           + np.arange(d, dtype=np.uint64)[None, :])
-    scale = np.float32(1.0) / (np.float32(1.0) - np.float32(P))
-    return torch.from_numpy(np.where(mask_keep(idx, P), float(scale), 0.0)).to(DEV)
+    return torch.from_numpy(dropout_ref.factors(n, d, P, SEED, base, ld).astype(np.float64)).to(DEV)
 
 
 def aggregate64(rowptr, col, x64, n):

@@ -34,6 +34,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import dropout_ref
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda', 0)
 TOL = 1e-4
@@ -42,16 +44,8 @@ LR = 0.01
 
 
 def _mask(n, d, p, seed, offset):
-    """The step's dropout mask of one layer (gist_dropout_f32's generator: one splitmix64 per element pair)."""
-    idx = np.arange(n * d, dtype=np.uint64) + np.uint64(offset)
-    with np.errstate(over='ignore'):
-        z = (idx >> np.uint64(1)) + np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    w = np.where(idx & np.uint64(1), z >> np.uint64(32), z & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    u = (w >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-    return (u >= np.float32(p)).reshape(n, d).astype(np.float32)
+    """The step's dropout mask of one layer (gist_dropout_f32's generator: tests/dropout_ref.py), 1.0 where kept."""
+    return dropout_ref.keep_mask(n, d, p, seed, offset).astype(np.float32)
 
 
 def _flat(pairs):
