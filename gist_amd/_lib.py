@@ -75,6 +75,9 @@ SIGNATURES = {
     'gist_block_gather_f32': (_int, [_p, _i64, _p, _p, _i64, _i64, _p, _i64, _p]),
     'gist_block_scatter_f32': (_int, [_p, _i64, _p, _p, _i64, _i64, _p, _i64, _p]),
     'gist_mean_rows_f32': (_int, [_p, _i64, _i64, _i64, _p, _p]),
+    'gist_arena_moves_packed_bytes': (_i64, [_i64]),
+    'gist_arena_moves_pack': (_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p]),
+    'gist_arena_moves_f32': (_int, [_p, _i64, _i64, _p, _p, _p, _p]),
     'gist_standard_scaler_workspace_bytes': (_i64, [_i64, _i64]),
     'gist_standard_scaler_f32': (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
     'gist_timer_create': (_p, [_i64]),
@@ -186,6 +189,9 @@ GIST_STEP_PHASE_FORWARD = 16
 GIST_STEP_PHASE_BACKWARD = 32
 GIST_STEP_PHASE_OPTIMIZER = 64
 GIST_STEP_DLOGITS_GIVEN = 128
+GIST_MOVE_GATHER = 0
+GIST_MOVE_SCATTER = 1
+GIST_MOVE_MEAN = 2
 
 
 class GemmPlan(ctypes.Structure):
@@ -283,6 +289,12 @@ class ExtractPartsDesc(ctypes.Structure):
                 ('labels_all', _p), ('labels', _p),
                 ('x0', _p), ('ldx0', _i64), ('p', _f), ('seed', _u64), ('offset', _u64), ('mask_ld', _i64),
                 ('scratch', _p), ('feat_intra', _p), ('ld_intra', _i64), ('ah', _p)]
+
+
+class ArenaMove(ctypes.Structure):
+    """struct gist_arena_move (include/gist_hip.h)."""
+    _fields_ = [('src_off', _i64), ('dst_off', _i64), ('lds', _i64), ('ldd', _i64), ('n_rows', _i64), ('n_cols', _i64),
+                ('row_idx', _i64), ('col_idx', _i64), ('kind', _i32), ('reserved', _i32)]
 
 
 class GradSegment(ctypes.Structure):

@@ -13,6 +13,7 @@
 // adjacency rows, 2 x 4 B per full-graph edge of the batch rows.
 #include "common.h"
 #include "adam_body.h"
+#include "mean_tree.h"
 
 namespace gist {
 
@@ -710,24 +711,12 @@ __global__ __launch_bounds__(256) void block_move_kernel(const float *__restrict
     }
 }
 
-// Pairwise (tree) summation over the sources: for identical copies and a power-of-two
-// count every partial sum is exact, so "dispatch -> sync without training" leaves the shared
-// bias bit-identical (a sequential sum rounds at 3x).  Deterministic for any count.
+// out[j] = the mean over the sources in mean_tree's order (mean_tree.h: a pairwise tree, then the tail)
 __global__ void mean_rows_kernel(const float *__restrict__ src, int64_t stride, int n_src, int64_t n,
                                  float *__restrict__ out) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    constexpr int kMax = 64;
-    float v[kMax];
-    float tail = 0.f;
-    const int m = n_src < kMax ? n_src : kMax;
-    for (int k = 0; k < kMax; ++k) v[k] = k < m ? src[(int64_t)k * stride + j] : 0.f;
-    for (int k = kMax; k < n_src; ++k) tail += src[(int64_t)k * stride + j];
-#pragma unroll
-    for (int w = 1; w < kMax; w <<= 1)
-#pragma unroll
-        for (int k = 0; k + w < kMax; k += 2 * w) v[k] += v[k + w];
-    out[j] = (v[0] + tail) / (float)n_src;
+    out[j] = mean_tree(src + j, stride, n_src);
 }
 
 }  // namespace gist

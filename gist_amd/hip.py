@@ -787,6 +787,51 @@ def mean_rows(src, stride, n_src, n, out):
     return out
 
 
+MOVE_KINDS = {'gather': _lib.GIST_MOVE_GATHER, 'scatter': _lib.GIST_MOVE_SCATTER, 'mean': _lib.GIST_MOVE_MEAN}
+
+
+class ArenaMoves(object):
+    """A packed table of the grouped block mover (gist_arena_moves_pack): built and validated once on the host, uploaded
+    once, run with arena_moves() as ONE launch.  moves = [(kind, src_off, dst_off, lds, ldd, n_rows, n_cols, row_idx,
+    col_idx)], kind 'gather' / 'scatter' / 'mean' (or its GIST_MOVE_* number), row_idx / col_idx starts in the index
+    pool or -1; src_numel / dst_numel / idx_len: the sizes of the two arenas and of the pool the table will run on."""
+
+    def __init__(self, moves, src_numel, dst_numel, idx_len, device):
+        L = _lib.load()
+        n = len(moves)
+        arr = (_lib.ArenaMove * max(n, 1))()
+        for a, m in zip(arr, moves):
+            kind = MOVE_KINDS.get(m[0], m[0])
+            (a.src_off, a.dst_off, a.lds, a.ldd, a.n_rows, a.n_cols, a.row_idx, a.col_idx) = [int(v) for v in m[1:]]
+            a.kind = int(kind)
+        nbytes = int(L.gist_arena_moves_packed_bytes(n))
+        host = torch.zeros(max(nbytes, 16), dtype=torch.uint8)
+        tiles = ctypes.c_int64(0)
+        _lib.check(L.gist_arena_moves_pack(arr, n, int(src_numel), int(dst_numel), int(idx_len), host.data_ptr(),
+                                           nbytes, ctypes.byref(tiles)), 'gist_arena_moves_pack')
+        self.n_moves, self.n_tiles = n, int(tiles.value)
+        self.src_numel, self.dst_numel, self.idx_len = int(src_numel), int(dst_numel), int(idx_len)
+        self.uses_idx = any(int(m[7]) >= 0 or int(m[8]) >= 0 for m in moves)
+        self.host = host
+        self.packed = host.to(device)
+
+
+def arena_moves(table, idx, src, dst):
+    """Run an ArenaMoves table: every move between the flat fp32 tensors `src` and `dst` in one launch (none for a table
+    without tiles).  idx: the int32 index pool (None if no move has a list)."""
+    L = _lib.load()
+    sp = _vec(src, 'src', torch.float32, table.src_numel)
+    dp = _vec(dst, 'dst', torch.float32, table.dst_numel)
+    if sp < dp + 4 * dst.numel() and dp < sp + 4 * src.numel():
+        raise ValueError('gist_amd: src and dst overlap (a table moves blocks between two arenas, never inside one)')
+    if table.uses_idx and idx is None:
+        raise ValueError('gist_amd: the table has index lists, idx is None')
+    ip = _opt(idx, 'idx', torch.int32, table.idx_len)
+    _lib.check(L.gist_arena_moves_f32(_vec(table.packed, 'packed', torch.uint8), table.n_moves, table.n_tiles, ip, sp, dp,
+                                      _stream()), 'gist_arena_moves_f32')
+    return dst
+
+
 # -- fused forms (include/gist_hip.h: dropout folded into producers / consumers, deferred reductions) --
 def spmm_drop_takes(mode, d, x, y, has_row_blocks):
     L = _lib.load()

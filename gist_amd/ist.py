@@ -10,11 +10,13 @@ Reference: cluster_gcn/cluster_gcn_ist_distrib_gat.py
   DistributedGATWrapper       :67-391   (gist_amd.arena.GATArena: the flat per-head layout)
   train_gat                   :393-480  (the loop on the drop-in classes, or on GATEngine's one-call step)
 
-The two families share everything but a few facts, and those are all that a family's subclass states.
+The families share everything but a few facts, and those are all that a family's subclass states.
 _DistributedWrapper holds construction, dispatch and sync, written against a per-site, per-layer plan of index
-vectors; DistributedGNNWrapper and DistributedGATWrapper give it their dims, arena, model, binding and plan
-(_site_plan), and keep what is their own (the SAGE engine and evaluator; the GAT heads).  _run_schedule is the loop of
-both; train and train_gat hand it one step and one evaluation.
+vectors; DistributedGNNWrapper, DistributedGATWrapper and DistributedGraphSAGEWrapper (gist_amd.modules.GraphSAGE: the
+GCN split, the LayerNorm's gamma and beta following the bias; one grouped mover launch per dispatch and per sync) give
+it their dims, arena, model, binding and plan (_site_plan), and keep what is their own (the SAGE engine and evaluator;
+the GAT heads).  _run_schedule is the loop of all; train, train_gat and train_graphsage hand it one step and one
+evaluation.
 
 What is kept identical (parity surface): the partition sampler (python `random`,
 same call order on every rank), which block of which base tensor each site owns
@@ -149,11 +151,18 @@ def _row(t):
 
 
 class _DistributedWrapper(object):
-    """What the GraphSAGE and the GAT wrapper share: the construction in the reference's torch RNG order, the
-    replicated base, dispatch and sync.  Both families lay a layer out as two tensors in a gist_amd.arena.FlatArena, and
-    a site owns of layer k the block (rows, cols) of tensor 1 and the columns cols2 of tensor 2 (None = all); the last
-    layer's tensor 2 is shared and becomes the mean over the sites.  A family supplies _dims, _new_arena, _new_model,
-    _module_params, _bind and _site_plan."""
+    """What the wrappers of the three families share: the construction in the reference's torch RNG order, the
+    replicated base, dispatch and sync.  A family lays a layer out in a gist_amd.arena.FlatArena as one matrix and m
+    vectors (m = 1: the SAGE GCN's bias, the GAT's stacked attn vectors; m = 3: GraphSAGE's bias, gamma, beta), and a
+    site owns of layer k the block (rows, cols) of the matrix and the columns cols2 of every vector (None = all); the
+    last layer has one vector, which is shared and becomes the mean over the sites.  A family supplies _dims,
+    _new_arena, _new_model, _module_params, _bind and _site_plan.
+
+    Movers: per-tensor calls on `blocks` (HipBlocks, or a test double), one per (site, layer, tensor); or, for a family
+    with GROUPED set, no `blocks` given and a GPU, the grouped mover: ONE gist_arena_moves_f32 launch per dispatch and
+    per sync over descriptor tables built once here (block sizes never change, H % S == 0), the indices of a partition
+    pooled into one int32 tensor that is uploaded once per _set_partition."""
+    GROUPED = False
 
     def __init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm):
         self.args = args
@@ -164,6 +173,7 @@ class _DistributedWrapper(object):
         assert self.H % self.S == 0
         self.h = self.H // self.S
         self.rank = args.rank
+        self.grouped = bool(self.GROUPED and blocks is None and torch.device(device).type == 'cuda')
         self.blocks = blocks if blocks is not None else HipBlocks()
         self.comm = comm if comm is not None else TorchDistComm()
         self.base_dims, self.sub_dims = self._dims(False), self._dims(True)
@@ -189,6 +199,8 @@ class _DistributedWrapper(object):
             self.comm.register(self.base, self.sub)
         self.current_partition = None
         self._plan = None
+        if self.grouped:
+            self._build_tables()
 
     # -- partitions ------------------------------------------------------------------
     def sample_partitions(self):
@@ -196,8 +208,15 @@ class _DistributedWrapper(object):
         return [create_partition(self.S, self.H) for _ in range(self.L)]
 
     def _set_partition(self, part):
-        """_plan[site][layer] = (rows, cols, cols2) as int32 device index vectors; each vector is uploaded once."""
+        """_plan[site][layer] = (rows, cols, cols2) as int32 device index vectors; each vector is uploaded once.  On the
+        grouped mover: the same vectors back to back in one int32 pool (_pool_layout), one upload."""
         self.current_partition = part
+        if self.grouped:
+            starts, tensors, total = self._pool_layout(part)
+            if starts != self._pool_starts or total != self._pool_len:
+                raise RuntimeError('gist_amd: the partition does not have the block sizes the move tables were built for')
+            self._pool = torch.cat(tensors).to(torch.int32).to(self.device)
+            return
         done = {}
 
         def i32(t):
@@ -208,14 +227,81 @@ class _DistributedWrapper(object):
             return done[id(t)][1]
         self._plan = [[tuple(i32(t) for t in layer) for layer in self._site_plan(part, s)] for s in range(self.S)]
 
+    # -- the grouped mover -------------------------------------------------------------
+    def _pool_layout(self, part):
+        """Where the index vectors of `part` go in the pool: (starts[site][layer] = (rows, cols, cols2) as pool offsets,
+        -1 for None; the vectors in pool order; the pool's length).  A vector a site's plan names twice is stored once."""
+        starts, tensors, total = [], [], 0
+        for s in range(self.S):
+            seen, layers = {}, []
+            for layer in self._site_plan(part, s):
+                ent = []
+                for t in layer:
+                    if t is not None and id(t) not in seen:
+                        seen[id(t)] = total
+                        tensors.append(t)                      # (kept: its id stays its own)
+                        total += t.numel()
+                    ent.append(-1 if t is None else seen[id(t)])
+                layers.append(tuple(ent))
+            starts.append(layers)
+        return starts, tensors, total
+
+    def _layer_blocks(self, k):
+        """Per tensor j of layer k: (j, base offset, base (rows, cols), sub offset, sub (rows, cols)), a vector as the
+        [1, n] matrix the movers take."""
+        def as2d(shape):
+            return tuple(shape) if len(shape) == 2 else (1, shape[0])
+        return [(j, self.base.offsets[k][j], as2d(self.base._shapes[k][j]), self.sub.offsets[k][j], as2d(ss))
+                for j, ss in enumerate(self.sub._shapes[k])]
+
+    def _build_tables(self):
+        """The move tables of this rank's dispatch (base -> sub: the gathers of _gather_own) and of a sync (gathered
+        -> base: the scatters and the mean of sync_apply), packed and uploaded once.  The pool's layout does not depend
+        on the partition's values: it is taken from a partition drawn on a private generator."""
+        from . import hip
+        probe = [create_partition(self.S, self.H, rng=_pyrandom.Random(0)) for _ in range(self.L)]
+        self._pool_starts, tensors, self._pool_len = self._pool_layout(probe)
+        length, pos = {}, 0                              # start in the pool -> the list's length
+        for t in tensors:
+            length[pos] = t.numel()
+            pos += t.numel()
+        P, last = self.sub.numel, len(self.sub_dims) - 1
+
+        def listed(start, n, what):
+            if start >= 0 and length[start] != n:
+                raise RuntimeError('gist_amd: %s list of %d indices for a block of %d' % (what, length[start], n))
+            return start
+        dispatch, sync = [], []
+        for s in range(self.S):
+            for k, (rows, cols, cols2) in enumerate(self._pool_starts[s]):
+                for j, boff, (R, C), soff, (r, c) in self._layer_blocks(k):
+                    ri, ci = (rows, cols) if j == 0 else (-1, cols2)
+                    listed(ri, r, 'row')
+                    listed(ci, c, 'column')
+                    if s == self.rank:
+                        dispatch.append(('gather', boff, soff, C, c, r, c, ri, ci))
+                    if j == 0 or k < last:
+                        sync.append(('scatter', s * P + soff, boff, c, C, r, c, ri, ci))
+        n_shared = self.sub.views[1][last].numel()
+        sync.append(('mean', self.sub.offsets[last][1], self.base.offsets[last][1], P, 0, self.S, n_shared, -1, -1))
+        self._dispatch_table = hip.ArenaMoves(dispatch, self.base.numel, self.sub.numel, self._pool_len, self.device)
+        self._sync_table = hip.ArenaMoves(sync, self.S * P, self.base.numel, self._pool_len, self.device)
+        self._pool = None
+
     # -- dispatch ----------------------------------------------------------------------
     def _gather_own(self):
-        """Slice the (local replica of the) base model into this rank's sub-model: one gather per (layer, tensor); the
-        shared last tensor 2 is copied whole."""
-        (base1, base2), (sub1, sub2) = self.base.views, self.sub.views
+        """Slice the (local replica of the) base model into this rank's sub-model: one gather per (layer, tensor) -- or
+        all of them in one launch; the shared last vector is copied whole."""
+        if self.grouped:
+            from . import hip
+            hip.arena_moves(self._dispatch_table, self._pool, self.base.params, self.sub.params)
+            return
+        base, sub = self.base.views, self.sub.views
         for k, (rows, cols, cols2) in enumerate(self._plan[self.rank]):
-            self.blocks.gather(base1[k], rows, cols, sub1[k])
-            self.blocks.gather(_row(base2[k]), None, cols2, _row(sub2[k]))
+            self.blocks.gather(base[0][k], rows, cols, sub[0][k])
+            for bv, sv in zip(base[1:], sub[1:]):
+                if sv[k] is not None:
+                    self.blocks.gather(_row(bv[k]), None, cols2, _row(sv[k]))
 
     def ini_sync_dispatch_model(self, part=None):
         """The base model leaves rank 0 once (replication), then every rank slices its own sub-model locally.  `part`
@@ -241,23 +327,29 @@ class _DistributedWrapper(object):
             self.gathered[:self.sub.numel].copy_(self.sub.params)
 
     def sync_apply(self):
-        """Phase 2: index-scatter all S sites' blocks into the local base replica (at most two scatters per site and
-        layer); the shared last tensor 2 becomes the mean of the S copies in site order (bitwise equal on all ranks) --
-        also in the sub-model, as the reference's in-place all-reduce does."""
+        """Phase 2: index-scatter all S sites' blocks into the local base replica (one scatter per site, layer and
+        tensor, or all of them in one launch); the shared last vector becomes the mean of the S copies in site order
+        (bitwise equal on all ranks) -- also in the sub-model, as the reference's in-place all-reduce does."""
         P = self.sub.numel
         last = len(self.sub_dims) - 1
-        base1, base2 = self.base.views
+        base = self.base.views
+        shared = self.sub.views[1][last]
+        if self.grouped:
+            from . import hip
+            hip.arena_moves(self._sync_table, self._pool, self.gathered, self.base.params)
+            shared.copy_(base[1][last])
+            return
         for s in range(self.S):
             site = self.gathered[s * P:(s + 1) * P]
             for k, (rows, cols, cols2) in enumerate(self._plan[s]):
-                t1, t2 = self.sub.layer_views(site, k)
-                self.blocks.scatter(t1, rows, cols, base1[k])
+                tensors = self.sub.layer_views(site, k)
+                self.blocks.scatter(tensors[0], rows, cols, base[0][k])
                 if k < last:
-                    self.blocks.scatter(_row(t2), None, cols2, _row(base2[k]))
-        shared = self.sub.views[1][last]
+                    for j in range(1, len(tensors)):
+                        self.blocks.scatter(_row(tensors[j]), None, cols2, _row(base[j][k]))
         self.blocks.mean_rows(self.gathered[self.sub.offsets[last][1]:], P, self.S, shared.numel(),
-                              base2[last].view(-1))
-        shared.copy_(base2[last])
+                              base[1][last].view(-1))
+        shared.copy_(base[1][last])
 
     def sync_model(self):
         """One all-gather of the flat sub arenas, then on-device scatters."""
@@ -414,6 +506,84 @@ class DistributedGATWrapper(_DistributedWrapper):
         return layers
 
 
+class DistributedGraphSAGEWrapper(_DistributedWrapper):
+    """One rank's view of GIST for the GraphSAGE family (gist_amd.modules.GraphSAGE, the model --use-pp was written
+    for): a replica of the base model and its sub-model of width n_hidden / num_subnet, over the flat arenas `base` and
+    `sub` (GraphSAGEArena: per layer W, b and -- but for the output layer -- the LayerNorm's gamma, beta).
+
+    Constructor as the other two wrappers' (`args` needs num_subnet, n_hidden, n_layers, rank, dropout; use_pp is read
+    if present).  Called with the five arguments only, it draws the initial weights from the torch RNG in the wrappers'
+    order: on rank 0 the base GraphSAGE, then on every rank the sub one.  `base_init` = per layer (W, b, gamma, beta) --
+    (W, b) for the output layer -- on rank 0 (others pass None): given, even as None, nothing is drawn.  `sub_model`
+    (every rank) and `base_model` (rank 0; None elsewhere) are gist_amd.modules.GraphSAGE whose Parameters are views of
+    the arenas, names and state_dict keys kept.
+
+    The split is the reference's GCN split (cluster_gcn_ist_distrib.py:197-367), the LayerNorm vectors following the
+    bias:
+
+        layer        W (rows, columns)                                    b, gamma, beta
+        first        idx_0, all (use_pp too: it reads the full [X | A^X])  idx_0
+        middle k     idx_k, full_k-1                                      idx_k
+        last         all, full_last-1                                     b shared: the site mean; no gamma / beta
+
+    `blocks` given (a test double, or HipBlocks()): one mover call per (site, layer, tensor).  Not given, on a GPU: the
+    grouped mover -- one gist_arena_moves_f32 launch per dispatch and per sync (_DistributedWrapper)."""
+    GROUPED = True
+
+    def __init__(self, args, g, in_feats, n_classes, device, *, base_init=_UNSET, blocks=None, comm=None, seed=0):
+        from .arena import GraphSAGEArena, graphsage_dims
+        from .modules import GraphSAGE
+        self._GraphSAGE, self._Arena, self._graphsage_dims = GraphSAGE, GraphSAGEArena, graphsage_dims
+        self.use_pp = bool(getattr(args, 'use_pp', False))
+        self.seed = int(seed)
+        _DistributedWrapper.__init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm)
+        self.engine = None                                    # attach_engine: train_graphsage(..., host_path='step')
+
+    def attach_engine(self, n_max, x0=None):
+        """The GraphSAGEEngine that steps `sub` in place (dispatch and sync keep moving the same storage, `sub_model`
+        keeps viewing it), sized for batches of up to n_max rows; kept as `engine` across dispatches, with its dropout
+        counter.  x0 is accepted for the GAT wrapper's call shape: every GraphSAGE engine owns its layer-0 buffer."""
+        from .graphsage_engine import GraphSAGEEngine
+        e = self.engine
+        if e is None or e.n_max != int(n_max):
+            self.engine = GraphSAGEEngine(self.sub_dims, self.args.dropout, n_max, self.device,
+                                          seed=self.seed * 131 + self.rank, use_pp=self.use_pp, arena=self.sub)
+        return self.engine
+
+    def _dims(self, sub):
+        return self._graphsage_dims(self.in_feats, self.h if sub else self.H, self.n_classes, self.L)
+
+    def _new_arena(self, dims, trains):
+        return self._Arena(dims, self.device)                 # (gradients: the autograd's, or GraphSAGEEngine's with_grads)
+
+    def _new_model(self, sub):
+        import torch.nn.functional as F
+        return self._GraphSAGE(self.in_feats, self.h if sub else self.H, self.n_classes, self.L, F.relu,
+                               self.args.dropout, self.use_pp)
+
+    def _module_params(self, model):
+        per_layer = []
+        for layer in model.layers:
+            group = [layer.linear.weight.data, layer.linear.bias.data]
+            if isinstance(layer.lynorm, torch.nn.LayerNorm):
+                group += [layer.lynorm.weight.data, layer.lynorm.bias.data]
+            per_layer.append(tuple(group))
+        return per_layer
+
+    def _bind(self, arena, model, requires_grad):
+        """Make every parameter of `model` a Parameter over its block of `arena` (no copy)."""
+        import torch.nn as nn
+        for k, layer in enumerate(model.layers):
+            layer.linear.weight = nn.Parameter(arena.W[k], requires_grad=requires_grad)
+            layer.linear.bias = nn.Parameter(arena.b[k], requires_grad=requires_grad)
+            if arena.gamma[k] is not None:
+                layer.lynorm.weight = nn.Parameter(arena.gamma[k], requires_grad=requires_grad)
+                layer.lynorm.bias = nn.Parameter(arena.beta[k], requires_grad=requires_grad)
+        return model
+
+    _site_plan = DistributedGNNWrapper._site_plan             # (the same split: the vectors share idx_k)
+
+
 def _run_schedule(models, args, cluster_iterator, log, at_dispatch, step, before_eval, accuracies):
     """The GIST schedule of both families (cluster_gcn_ist_distrib.py:385-450): no re-dispatch in epoch 0, a fresh
     optimiser at every dispatch point, sync at multiples of iter_per_site and at the very last iteration, evaluation
@@ -553,7 +723,7 @@ def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask,
     if eval_path == 'blocked' and models[0].base_model is not None:
         from .gat_eval import GATFullGraphEvaluator
         GATFullGraphEvaluator.attach(models[0].base_model, arena=models[0].base)
-    steps = {'module': _gat_module_steps, 'engine': _gat_engine_steps, 'phases': _gat_phase_steps}[host_path]
+    steps = {'module': _module_steps, 'engine': _gat_engine_steps, 'phases': _gat_phase_steps}[host_path]
     at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
 
     def accuracies():
@@ -563,8 +733,9 @@ def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask,
                          before_eval, accuracies)
 
 
-def _gat_module_steps(models, args, cluster_iterator):
-    """train_gat's (at_dispatch, step, before_eval) on the drop-in classes: the reference's loop body."""
+def _module_steps(models, args, cluster_iterator):
+    """(at_dispatch, step, before_eval) of the module loops (train_gat, train_graphsage) on the drop-in classes: the
+    reference's loop body on every site's `sub_model`."""
     from .nn import CrossEntropyLoss
     from .optim import Adam
     dev = models[0].device
@@ -592,7 +763,7 @@ def _gat_module_steps(models, args, cluster_iterator):
 
 
 def _gat_phase_steps(models, args, cluster_iterator):
-    """train_gat's (at_dispatch, step, before_eval) for host_path='phases': _gat_module_steps' loop body, with every
+    """train_gat's (at_dispatch, step, before_eval) for host_path='phases': _module_steps' loop body, with every
     site's sub_model bound to the iterator first.  Each wrapper's GATEngine steps its sub arena in place (attach_engine;
     the further sites of one process read the first engine's layer-0 input buffer), so dispatch and sync keep moving
     the storage the step trains."""
@@ -610,7 +781,7 @@ def _gat_phase_steps(models, args, cluster_iterator):
         engine = m.attach_engine(it.n_max, x0=None if first is None else first.X0)
         first = engine if first is None else first
         bind_gat(m.sub_model, it)
-    at_dispatch, step, _ = _gat_module_steps(models, args, cluster_iterator)
+    at_dispatch, step, _ = _module_steps(models, args, cluster_iterator)
 
     def before_eval():                               # (the device is idle: every extraction so far was complete)
         for m in models:
@@ -651,6 +822,94 @@ def _gat_engine_steps(models, args, cluster_iterator):
 
     def step(si, batch):
         return models[si].engine.train_step(batch, args.lr, args.weight_decay)[0].clone()      # (0-dim, as 'module')
+
+    def before_eval():                               # (the device is idle: every extraction so far was complete)
+        for m in models:
+            m.engine.check_extract()
+    return at_dispatch, step, before_eval
+
+
+def train_graphsage(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module',
+                    eval_path='layers'):
+    """The GIST loop (cluster_gcn_ist_distrib.py:370-479, _run_schedule) for the GraphSAGE family.
+
+    host_path='module': the reference's loop body on `ist_model.sub_model` -- masked gist_amd.nn.CrossEntropyLoss, a
+    new gist_amd.optim.Adam at every dispatch point; `cluster_iterator` is a ClusterIter (use_pp as the wrapper's).
+    GPU-only, like 'step': the model's forward runs on torch.ops.gist.* (spmm_sum, matmul, layer_norm_affine), which
+    are registered for the GPU alone, and the project has no CPU fallback.  With `blocks` and `comm` doubles the wrapper
+    itself -- construction, dispatch, sync -- runs on the CPU; a training loop does not.
+    host_path='step': every site's step is ONE gist_graphsage_step call on its wrapper's GraphSAGEEngine, which steps
+    `sub` in place; `cluster_iterator` is an EngineClusterIter (use_pp as the wrapper's).  `sub.reset_optimizer()` is
+    the fresh optimiser of a dispatch point; an engine's dropout counter runs on across dispatches.  The dropout masks
+    are the step's counter-based generator's, not torch's: with dropout 0 the two paths compute the same function.
+
+    `ist_model` is this rank's DistributedGraphSAGEWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites
+    then run in this process, the partition sampled once per dispatch.  eval_path='rows': rank 0's `base_model` is
+    evaluated by a gist_amd.graphsage_eval.GraphSAGEFullGraphEvaluator over the base arena ('layers': its own forward).
+    Returns what train_gat returns."""
+    from .utils import evaluate
+    models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
+    if host_path not in ('module', 'step'):
+        raise ValueError("gist_amd: train_graphsage host_path must be 'module' or 'step' (got %r)" % (host_path,))
+    if eval_path not in ('layers', 'rows'):
+        raise ValueError("gist_amd: train_graphsage eval_path must be 'layers' or 'rows' (got %r)" % (eval_path,))
+    if host_path == 'module' and torch.device(models[0].device).type != 'cuda':
+        raise ValueError("gist_amd: train_graphsage(host_path='module') runs the model's forward on torch.ops.gist.*, "
+                         "which is GPU-only (the wrapper is on %s); there is no CPU fallback" % (models[0].device,))
+    if eval_path == 'rows' and models[0].base_model is not None:
+        from .graphsage_eval import GraphSAGEFullGraphEvaluator
+        GraphSAGEFullGraphEvaluator.attach(models[0].base_model, arena=models[0].base)
+    steps = {'module': _module_steps, 'step': _graphsage_engine_steps}[host_path]
+    at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
+
+    def accuracies():
+        base_model = models[0].base_model
+        return evaluate(base_model, g, labels, val_mask), evaluate(base_model, g, labels, test_mask)
+    return _run_schedule(models, args, cluster_iterator, lambda line: log(line, flush=True), at_dispatch, step,
+                         before_eval, accuracies)
+
+
+def _graphsage_engine_steps(models, args, cluster_iterator):
+    """train_graphsage's (at_dispatch, step, before_eval) on the fused step: one GraphSAGEEngine per wrapper over its sub
+    arena.
+
+    One site in the process (the distributed run): the optimiser launch of a step extracts the next batch of the epoch
+    beside it, as in train().  S sites in one process: the first site's step extracts the batch -- CSR, reversed CSR,
+    labels -- into the iterator's batch buffers, which every engine's plan points into; layer 0's input is an engine's
+    own buffer (a training step with dropout leaves dropped values in it), so every further site gathers the batch's
+    features into its Z_0 first (fill_features).  Batch.z0_dropped then speaks of the engine that stepped last, not of
+    the buffer about to be read: it is cleared with the refill."""
+    from .sampler import EngineClusterIter
+    if models[0].device.type != 'cuda':
+        raise ValueError("gist_amd: train_graphsage(host_path='step') runs the fused step gist_graphsage_step, which is "
+                         "GPU-only (the wrapper is on %s); use host_path='module' there" % (models[0].device,))
+    if not isinstance(cluster_iterator, EngineClusterIter):
+        raise ValueError("gist_amd: train_graphsage(host_path='step') needs a gist_amd.sampler.EngineClusterIter as "
+                         "cluster_iterator (got %s): it describes the batches the step extracts on the device"
+                         % type(cluster_iterator).__name__)
+    it = cluster_iterator
+    if bool(it.use_pp) != models[0].use_pp:
+        raise ValueError('gist_amd: the iterator\'s use_pp (%s) is not the wrapper\'s (%s)' % (it.use_pp, models[0].use_pp))
+    first = models[0].attach_engine(it.n_max)
+    if it.engine is not first:
+        it.bind(first)
+    for m in models[1:]:
+        engine = m.attach_engine(it.n_max)
+        if engine.plan is None or engine._plan_keep[0] is not it.batcher:
+            engine.attach_batcher(it.batcher)
+    for m in models:
+        m.engine.prefetch = len(models) == 1
+
+    def at_dispatch():
+        for m in models:
+            m.sub.reset_optimizer()
+
+    def step(si, batch):
+        engine = models[si].engine
+        if si > 0:
+            it.fill_features(batch, engine)
+            batch.z0_dropped = False
+        return engine.train_step(batch, args.lr, args.weight_decay)[0].clone()      # (0-dim, as 'module')
 
     def before_eval():                               # (the device is idle: every extraction so far was complete)
         for m in models:

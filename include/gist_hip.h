@@ -805,6 +805,53 @@ int gist_block_scatter_f32(const float *src, int64_t lds, const int32_t *row_idx
 int gist_mean_rows_f32(const float *src, int64_t stride, int64_t n_src, int64_t n,
                        float *out, gist_stream_t stream);
 
+/* Grouped block mover: ONE launch moves every block of a dispatch or of a sync between two flat arenas (`src`, `dst`:
+ * one float pointer each; a block is named by its float offset into its arena).  A dispatch is the gathers of
+ * gist_block_gather_f32 over (base -> sub) for every layer and tensor of one site
+ * (cluster_gcn_ist_distrib.py:197-367); a sync is the scatters of gist_block_scatter_f32 over (all-gathered subs ->
+ * base) for every site, layer and tensor (:106-133,136-195) plus the gist_mean_rows_f32 of the shared last bias
+ * (:38-41,103).  Block sizes never change between partitions (n_hidden % num_subnet == 0), so the table is packed and
+ * uploaded once; only the index pool is rewritten per partition.
+ *
+ * row_idx / col_idx: start of the block's int32 index list in ONE shared index pool, -1 = identity.
+ *   GIST_MOVE_GATHER    dst[dst_off + i*ldd + j] = src[src_off + row[i]*lds + col[j]]      i < n_rows, j < n_cols
+ *   GIST_MOVE_SCATTER   dst[dst_off + row[i]*ldd + col[j]] = src[src_off + i*lds + j]
+ *   GIST_MOVE_MEAN      dst[dst_off + j] = mean over s < n_rows of src[src_off + s*lds + j]  (the bits of
+ *                       gist_mean_rows_f32(src + src_off, lds, n_rows, n_cols, dst + dst_off); no index lists)
+ * Contract: the src and dst arenas do not overlap at all (the kernel reads src through a no-alias pointer: a table
+ * never moves blocks inside one arena); the moves of one call never write the same cell (there are no atomics and no
+ * order between moves); and the index VALUES keep every access inside its arena -- as for gist_block_gather_f32, they
+ * are the caller's. */
+#define GIST_MOVE_GATHER 0
+#define GIST_MOVE_SCATTER 1
+#define GIST_MOVE_MEAN 2
+struct gist_arena_move {
+    int64_t src_off, dst_off;   /* float offsets of the block's first cell in the src / dst arena; any value >= 0 */
+    int64_t lds, ldd;           /* row pitches in floats (MEAN: lds = the stride between sources, ldd unused) */
+    int64_t n_rows, n_cols;     /* < 2^31 each; a move with n_rows == 0 or n_cols == 0 moves nothing */
+    int64_t row_idx, col_idx;   /* starts in the index pool, or -1 */
+    int32_t kind;               /* GIST_MOVE_* */
+    int32_t reserved;           /* 0 */
+};
+
+/* Bytes of the packed device-format table of n_moves moves (descriptors + tile prefix); < 0 for n_moves < 0. */
+int64_t gist_arena_moves_packed_bytes(int64_t n_moves);
+
+/* HOST ONLY.  Validates `moves` as far as that is possible without the index values and writes the table into the HOST
+ * buffer out_host[out_bytes], which the caller uploads once (16-byte aligned on the device); *n_tiles = the launch's
+ * grid.  GIST_EINVAL: a negative size or one >= 2^31, a negative offset, an unknown kind, a pitch smaller than n_cols on
+ * a side whose columns are identity-indexed, a block whose identity-indexed extent ends past src_numel / dst_numel, an
+ * index range outside [0, idx_len), index lists on a MEAN (or a MEAN of no sources), more than 2^31 - 1 tiles;
+ * GIST_ENOSPACE: out_bytes < gist_arena_moves_packed_bytes(n_moves).  Message in gist_last_error. */
+int gist_arena_moves_pack(const struct gist_arena_move *moves, int64_t n_moves, int64_t src_numel,
+                          int64_t dst_numel, int64_t idx_len, void *out_host, int64_t out_bytes,
+                          int64_t *n_tiles);
+
+/* Run a packed table: one kernel launch (none when n_tiles == 0).  packed_dev: the uploaded table; idx_dev: the index
+ * pool (may be NULL if no move has a list).  n_moves and n_tiles are those of the pack call. */
+int gist_arena_moves_f32(const void *packed_dev, int64_t n_moves, int64_t n_tiles, const int32_t *idx_dev,
+                         const float *src, float *dst, gist_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * Whole training iteration in one call (native step driver)
  * ------------------------------------------------------------------------- */
