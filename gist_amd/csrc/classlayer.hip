@@ -158,6 +158,8 @@ __global__ __launch_bounds__(256) void class_layer_kernel(ClassArgs a) {
             dls[row][c] = g;
             if (live && c < a.ldg) a.dlog[(int64_t)(r0 + row) * a.ldg + c] = g;
         }
+        // pad columns 48 .. ldg - 1 of a caller with ldg in 49 .. 64 (the three tiles above stop at column 47)
+        if (live && cl + kCpad < a.ldg) a.dlog[(int64_t)(r0 + row) * a.ldg + cl + kCpad] = 0.f;
 #pragma unroll
         for (int off = 8; off > 0; off >>= 1) at_label += __shfl_xor(at_label, off);
         if (live && cl == 0) a.row_nll[r0 + row] = -((at_label - mx) - logf(se));

@@ -533,7 +533,8 @@ int gist_gemm_nn_dropout_colsum_f32(const float *g, int64_t ldg, const float *w,
 
 /* The CLASS LAYER of a training step in one launch (round 4): logits = z . w^T + bias (z [n_rows, k] = the layer's
  * dropped input [h | ah], w [n_classes, k]); the mean cross entropy of gist_softmax_xent_f32 (row_loss[n_rows] = -log p,
- * d_logits [n_rows, ldg] = (softmax - onehot) / count, zero in the pad columns; the caller reduces row_loss, e.g. inside
+ * d_logits [n_rows, ldg] = (softmax - onehot) / count, zero in the pad columns n_classes .. ldg - 1 (n_classes <= ldg <= 64:
+ * also in columns 48 .. 63, beyond the kernel's three class tiles); the caller reduces row_loss, e.g. inside
  * gist_adam_segments_f32); dz [n_rows, k] = (d_logits . w) under the dropout mask of the layer's input (p, seed, offset:
  * gist_dropout_f32's generator, element index offset + row * k + col; dz = NULL: forward and loss only); and
  * dlogits_col_partials[gist_row_chunks16(n_rows)][n_classes] = d_logits' column sums per 16 rows (the bias gradient in

@@ -86,8 +86,12 @@ def _class_layer_case(hip, n, c, k, p, with_dz, off):
             ref_dz = ref_dz * _mask(n, k, p, seed, off) / (1.0 - p)
         got = dz.cpu().numpy()
         assert np.abs(got[:, :k] - ref_dz).max() < 2e-5 * max(np.abs(ref_dz).max(), 1e-12)
-        if p > 0:
-            assert np.array_equal(got[:, :k] == 0, ~_mask(n, k, p, seed, off) | (ref_dz == 0))
+        if p > 0 and c > 1:
+            keep = _mask(n, k, p, seed, off)
+            assert np.all((g @ w64)[keep] != 0)                          # the reference has no zero of its own where it keeps
+            assert np.array_equal(got[:, :k] == 0, ~keep)                # so the zeros are the mask and nothing but the mask
+        elif p > 0:
+            assert np.all(got[:, :k] == 0)                               # (one class: d_logits = 0, and dz with it)
         assert np.all(got[:, k:] == 9.0)
 
 
