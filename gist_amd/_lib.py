@@ -172,6 +172,7 @@ SIGNATURES = {
     'gist_graphsage_step_ln_workspace_floats': (_i64, [_p]),
     'gist_graphsage_step_folds': (_int, [_p, _i32]),
     'gist_graphsage_step': (_int, [_p, _p, _i64, _u64, _f, _f, _f, _f, _f, _i64, _int, _p]),
+    'gist_graphsage_step_phase': (_int, [_p, _p, _i64, _u64, _f, _f, _f, _f, _f, _i64, _int, _p]),
     'gist_ln_affine_bwd_workspace_floats': (_i64, [_i64, _i64]),
     'gist_ln_affine_bwd_f32': (_int, [_p, _i64, _p, _i64, _p, _p, _p, _int, _p, _i64, _p, _p, _p, _i64, _i64, _p, _i64,
                                       _p]),

@@ -167,6 +167,11 @@ class GraphSAGEArena(FlatArena):
             if g is not None:
                 g.fill_(1.0)                # nn.LayerNorm's initial weight
 
+    def bind_module(self, model):
+        """ParamArena.bind_module for a gist_amd.modules.GraphSAGE whose Parameters its owner (gist_amd.ist.
+        DistributedGraphSAGEWrapper) made views of this arena: module_engine.bind_graphsage then steps the arena in place."""
+        model.__dict__['_gist_arena'] = weakref.ref(self)
+
     @staticmethod
     def module_params(model):
         """The Parameters of a gist_amd.modules.GraphSAGE, in `model.parameters()` order."""

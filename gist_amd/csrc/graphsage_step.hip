@@ -63,6 +63,10 @@ extern "C" int gist_graphsage_step_folds(const gist_graphsage_step_plan *p, int3
 }
 
 namespace {
+// What one call runs.  gist_graphsage_step runs all of them (the forward alone without GIST_STEP_TRAIN);
+// gist_graphsage_step_phase exactly one.  The extraction belongs to the forward.
+enum { RUN_FORWARD = 1, RUN_BACKWARD = 2, RUN_OPTIMIZER = 4 };
+
 // One call's decisions, made once by validate() before any device work and read by the phase functions.
 struct Call {
     const gist_graphsage_step_plan *p;
@@ -81,46 +85,55 @@ struct Call {
     hipStream_t st;
 };
 
-// Every check and every workspace decision of an iteration, all of it before any device work.
-int validate(const gist_graphsage_step_plan *p, const int32_t *ids, int64_t n, uint64_t drop_offset, int64_t adam_step,
-             int flags, gist_stream_t s, Call &c) {
-    const char *who = "gist_graphsage_step";
+// Every check and every workspace decision of the parts `run` of an iteration, all of it before any device work.  `who`
+// names the entry point in the messages; phase_call: the flags are gist_graphsage_step_phase's (one phase bit,
+// GIST_STEP_TRAIN).  Each part checks what it reads: the forward the batch and loss buffers, the layers' W b Z Y (gamma
+// beta yhat rstd), the EXTRACT inputs; the backward the gradient views and its scratch; the optimiser the arena and the
+// EXTRACT_NEXT inputs.
+int validate(const char *who, const gist_graphsage_step_plan *p, const int32_t *ids, int64_t n, uint64_t drop_offset,
+             int64_t adam_step, int flags, int run, bool phase_call, gist_stream_t s, Call &c) {
     GIST_TRY(check_plan(who, p, shapes_ok(p), n));
-    GIST_TRY(check_flags(who, flags, false, nullptr));
+    GIST_TRY(check_flags(who, flags, phase_call, phase_call ? "gist_graphsage_step" : "gist_graphsage_step_phase"));
     const bool train = (flags & GIST_STEP_TRAIN) != 0;
+    const bool fwd = (run & RUN_FORWARD) != 0, bwd = (run & RUN_BACKWARD) != 0, opt = (run & RUN_OPTIMIZER) != 0;
     GIST_REQUIRE(p->p_drop >= 0.f && p->p_drop < 1.f, "%s: p_drop must be in [0,1)", who);
     const int L = p->n_layers;
-    GIST_TRY(check_batch_buffers(who, p, p->norm != nullptr));
-    for (int k = 0; k < L; ++k) {
+    if (fwd || bwd) GIST_TRY(check_batch_buffers(who, p, p->norm != nullptr));
+    for (int k = 0; (fwd || bwd) && k < L; ++k) {
         const gist_graphsage_layer_desc &l = p->layer[k];
         const bool hidden = k + 1 < L;
         GIST_REQUIRE(l.W && l.b && l.Z && l.Y, "%s: null buffer in layer %d", who, k);
         GIST_REQUIRE(!hidden || (l.gamma && l.beta && l.yhat && l.rstd), "%s: null LayerNorm buffer in layer %d", who, k);
-        if (train) {
+        if (bwd) {
             GIST_REQUIRE(l.dW && l.db, "%s: null gradient view in layer %d", who, k);
             GIST_REQUIRE(!hidden || (l.dgamma && l.dbeta), "%s: null LayerNorm gradient view in layer %d", who, k);
         }
     }
-    GIST_REQUIRE(p->loss_mask == nullptr || (p->loss_count > 0 && p->loss_count <= n),
-                 "%s: loss_mask given but loss_count is not in 1 .. n", who);
-    GIST_REQUIRE(p->row_blocks == nullptr || p->n_row_blocks > 0, "%s: row_blocks given but n_row_blocks <= 0", who);
-    if (train) {
-        GIST_REQUIRE(p->partials && (L == 1 || p->dZ), "%s: null backward scratch", who);
-        GIST_TRY(check_arena(who, p, adam_step));
+    if (fwd)
+        GIST_REQUIRE(p->loss_mask == nullptr || (p->loss_count > 0 && p->loss_count <= n),
+                     "%s: loss_mask given but loss_count is not in 1 .. n", who);
+    if (fwd || bwd)
+        GIST_REQUIRE(p->row_blocks == nullptr || p->n_row_blocks > 0, "%s: row_blocks given but n_row_blocks <= 0", who);
+    if (bwd) GIST_REQUIRE(p->partials && (L == 1 || p->dZ), "%s: null backward scratch", who);
+    if (opt) GIST_TRY(check_arena(who, p, adam_step));
+    if (bwd)
         GIST_REQUIRE(p->ln_workspace_floats >= 0 && (p->ln_workspace || p->ln_workspace_floats == 0),
                      "%s: bad ln_workspace", who);
-    }
     c.p = p; c.ids = ids; c.n = n; c.flags = flags; c.train = train; c.s = s; c.st = as_stream(s);
     c.p_drop = train ? p->p_drop : 0.f;
     c.layer0_aggregates = !(p->use_pp && train);
     const int64_t F = p->layer[0].n_in;
     c.n_feat = c.layer0_aggregates ? F : 2 * F;
     c.by_parts = extracts_by_parts(p);
-    if (flags & GIST_STEP_EXTRACT)
+    if (fwd && (flags & GIST_STEP_EXTRACT))
         GIST_TRY(check_extract(who, p, ids, c.by_parts, p->ld_feat >= c.n_feat,
                                " (with use_pp the features are 2 * n_in wide)"));
-    if (flags & GIST_STEP_EXTRACT_NEXT) GIST_TRY(check_extract_next(who, p, p->ld_feat >= c.n_feat));
-    // the dropout counter space of this step and which layers fold their mask into their producers
+    // (the extraction in the optimiser's grid writes every batch buffer the next forward reads)
+    if (opt && (flags & GIST_STEP_EXTRACT_NEXT))
+        GIST_TRY(check_extract_next(who, p, p->ld_feat >= c.n_feat && p->layer[0].Z && p->norm && p->rowptr && p->col &&
+                                                p->t_rowptr && p->t_col && p->labels));
+    // the dropout counter space of this step and which layers fold their mask into their producers: from the plan
+    // alone, so the forward and the backward phase of an iteration decide alike
     uint64_t off = drop_offset;
     for (int k = 0; k < L; ++k) {
         c.offs[k] = off;
@@ -131,8 +144,8 @@ int validate(const gist_graphsage_step_plan *p, const int32_t *ids, int64_t n, u
     for (int k = 0; k < L; ++k) {
         GemmShape g[3];
         layer_gemms(p->layer[k], n, g);
-        GIST_TRY(pick_workspaces(who, p, k, g, true, train, c.ws[k]));
-        if (train && k + 1 < L)
+        GIST_TRY(pick_workspaces(who, p, k, g, fwd, bwd, c.ws[k]));
+        if (bwd && k + 1 < L)
             GIST_TRY(enough(who, "ln_workspace", p->ln_workspace_floats,
                             gist_ln_affine_bwd_workspace_floats(n, p->layer[k].n_out), "floats"));
     }
@@ -221,20 +234,48 @@ int backward(const Call &c) {
     }
     return GIST_OK;
 }
+
+// the features into Z_0's left half, or (use_pp while training) [X | A^X] into all of it
+int extract(const Call &c) {
+    return gist::extract(c.p, c.by_parts, c.flags, c.ids, c.n, c.n_feat, c.p->layer[0].Z, 2 * c.p->layer[0].n_in, c.s);
+}
+
+// the optimiser launch; with GIST_STEP_EXTRACT_NEXT the next batch's features go to Z_0 as well
+int optimise(const Call &c, const AdamHyper &a) {
+    return gist::optimise(c.p, c.flags, c.n_feat, c.p->layer[0].Z, 2 * c.p->layer[0].n_in, a, c.s);
+}
 }  // namespace
 
 extern "C" int gist_graphsage_step(const gist_graphsage_step_plan *p, const int32_t *ids, int64_t n,
                                    uint64_t drop_offset, float lr, float beta1, float beta2, float eps,
                                    float weight_decay, int64_t adam_step, int flags, gist_stream_t s) {
+    const int run = (flags & GIST_STEP_TRAIN) ? RUN_FORWARD | RUN_BACKWARD | RUN_OPTIMIZER : RUN_FORWARD;
     Call c;
-    GIST_TRY(validate(p, ids, n, drop_offset, adam_step, flags, s, c));
+    GIST_TRY(validate("gist_graphsage_step", p, ids, n, drop_offset, adam_step, flags, run, false, s, c));
     ActiveTimer active(p->timer);
-    // the features into Z_0's left half, or (use_pp while training) [X | A^X] into all of it
-    float *z0 = p->layer[0].Z;
-    const int64_t ldz0 = 2 * p->layer[0].n_in;
-    GIST_TRY(extract(p, c.by_parts, flags, ids, n, c.n_feat, z0, ldz0, s));
+    GIST_TRY(extract(c));
     GIST_TRY(forward(c));
-    if (!c.train) return GIST_OK;
+    if (!(run & RUN_BACKWARD)) return GIST_OK;
     GIST_TRY(backward(c));
-    return optimise(p, flags, c.n_feat, z0, ldz0, AdamHyper{lr, beta1, beta2, eps, weight_decay, adam_step}, s);
+    return optimise(c, AdamHyper{lr, beta1, beta2, eps, weight_decay, adam_step});
+}
+
+// One third of gist_graphsage_step's iteration: the functions above, one phase per call (include/gist_hip.h).  No state
+// is kept between the calls: the plan's buffers are the state, and the phase order is the caller's contract.  The
+// forward and the backward phase of an iteration get the same drop_offset (the backward's gist_gemm_nn_dropout_f32
+// re-derives the masks); the optimiser phase reads none.
+extern "C" int gist_graphsage_step_phase(const gist_graphsage_step_plan *p, const int32_t *ids, int64_t n,
+                                         uint64_t drop_offset, float lr, float beta1, float beta2, float eps,
+                                         float weight_decay, int64_t adam_step, int flags, gist_stream_t s) {
+    const int run = (flags & GIST_STEP_PHASE_FORWARD)    ? RUN_FORWARD
+                    : (flags & GIST_STEP_PHASE_BACKWARD) ? RUN_BACKWARD
+                                                         : RUN_OPTIMIZER;
+    Call c;
+    GIST_TRY(validate("gist_graphsage_step_phase", p, ids, n, drop_offset, adam_step, flags, run, true, s, c));
+    ActiveTimer active(p->timer);
+    if (run == RUN_FORWARD) {
+        GIST_TRY(extract(c));
+        return forward(c);
+    }
+    return run == RUN_BACKWARD ? backward(c) : optimise(c, AdamHyper{lr, beta1, beta2, eps, weight_decay, adam_step});
 }

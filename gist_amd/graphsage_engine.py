@@ -17,8 +17,14 @@ One engine = one model on one GPU.  Everything lives in HBM for the whole run an
 Dropout is gist_dropout_f32's counter-based generator under the SAGE step's counter scheme (`seed`, a running element
 offset `drop_calls`), not torch's Philox stream: same distribution, other masks than nn.Dropout's.  With p = 0 the step
 computes the module path's function (tests/test_graphsage_step_gpu.py).  DESIGN.md section 10.
+
+The same iteration as three gist_graphsage_step_phase calls (StepEngine._run with phase=...) is what
+module_engine.bind_graphsage puts under `model(cluster)`, `loss.backward()` and `optimizer.step()`: the forward phase
+advances `drop_calls`, the backward phase is handed the same offset, and Batch.z0_dropped is set as soon as the forward
+phase has dropped Z_0.
 """
 import ctypes
+import weakref
 
 import torch
 
@@ -35,6 +41,7 @@ class GraphSAGEEngine(StepEngine):
         if arena is not None and [tuple(d) for d in arena.dims] != self.dims:
             raise ValueError('gist_amd: the arena\'s dims %s are not the engine\'s %s' % (arena.dims, self.dims))
         self.arena = (arena if arena is not None else GraphSAGEArena(self.dims, device)).with_grads()
+        self.arena.__dict__['_engine'] = weakref.ref(self)   # (module_engine.bind_graphsage steps a wrapper's arena through it)
         self.p_drop = float(dropout) if dropout else 0.0
         self.seed = int(seed)
         self.use_pp = bool(use_pp)
@@ -55,6 +62,7 @@ class GraphSAGEEngine(StepEngine):
         self.loss = torch.zeros(1, **f32)
         self.partials = torch.zeros(max(1, _lib.load().gist_colsum_partials(n)) * self.n_classes, **f32)
         self._model = None
+        self._lent = False                      # the plan's logits / loss / moment pointers are a GraphSAGEModuleEngine's
 
     def attach_batcher(self, batcher):
         """Build the native step plan (struct gist_graphsage_step_plan) over `batcher`'s resident graph and batch
@@ -116,21 +124,48 @@ class GraphSAGEEngine(StepEngine):
         return flags, ids_ptr, self._advance_drop_calls(b.n, train)
 
     def _call_step(self, ids_ptr, n, off, lr, betas, eps, weight_decay, t, flags, phase):
-        if phase:
-            raise RuntimeError('gist_amd: gist_graphsage_step has no phase calls')
-        rc = _lib.load().gist_graphsage_step(ctypes.byref(self.plan), ids_ptr, n, off, lr, betas[0], betas[1], eps,
-                                             weight_decay, t, flags, hip._stream())
-        _lib.check(rc, 'gist_graphsage_step')
+        """One gist_graphsage_step call (phase = 0), or one gist_graphsage_step_phase call.  off: the forward's dropout
+        offset (StepEngine._run hands the backward and the optimiser phase the one _open_step returned for the forward:
+        drop_calls advances once per iteration)."""
+        name = 'gist_graphsage_step_phase' if phase else 'gist_graphsage_step'
+        rc = getattr(_lib.load(), name)(ctypes.byref(self.plan), ids_ptr, n, off, lr, betas[0], betas[1], eps,
+                                        weight_decay, t, flags | phase, hip._stream())
+        _lib.check(rc, name)
 
     def _close_step(self, b, train):
+        # (after a whole step and after each phase call: the forward phase is the one that drops Z_0)
         if train and self.p_drop > 0.0:
             b.z0_dropped = True      # (one training step per extraction: Z_0 now holds dropped values)
 
-    def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
-        self._need_plan()
+    def _check_fresh(self, b):
         if b.ready and b.z0_dropped:
             raise RuntimeError('gist_amd: one step per extraction -- this Batch was already trained on with dropout, '
                                'its layer-0 buffer holds dropped values; take a fresh batch from the iterator')
+
+    def _native_step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, phase=0, given=False,
+                     adam_step=None):
+        """One call for module_engine.GraphSAGEModuleEngine (the name ModuleEngine calls its engine's phases by), which
+        points the plan's logits, loss and Adam moments at buffers of its own before it calls: the forward-only step of an
+        evaluation-mode forward (phase = 0), or one gist_graphsage_step_phase call.  The mean CE is over all batch rows."""
+        self._need_plan()
+        if phase in (0, _lib.GIST_STEP_PHASE_FORWARD):
+            self._check_fresh(b)
+            self.plan.loss_mask, self.plan.loss_count = None, 0
+        self._lent = True
+        return self._run(b, lr, weight_decay, train, betas, eps, phase, given, adam_step)
+
+    def _reclaim(self):
+        """Point the plan's logits, loss and Adam moments back at the engine's own buffers (a binding lent them)."""
+        P, A = self.plan, self.arena
+        P.layer[len(self.dims) - 1].Y, P.loss = self.Y[-1].data_ptr(), self.loss.data_ptr()
+        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
+        self._lent = False
+
+    def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
+        self._need_plan()
+        self._check_fresh(b)
+        if self._lent:
+            self._reclaim()
         P = self.plan
         if mask is None:
             P.loss_mask, P.loss_count = None, 0

@@ -571,7 +571,8 @@ class DistributedGraphSAGEWrapper(_DistributedWrapper):
         return per_layer
 
     def _bind(self, arena, model, requires_grad):
-        """Make every parameter of `model` a Parameter over its block of `arena` (no copy)."""
+        """Make every parameter of `model` a Parameter over its block of `arena` (no copy) and record the arena on the
+        model, so a GraphSAGEModuleEngine built for it trains the arena in place."""
         import torch.nn as nn
         for k, layer in enumerate(model.layers):
             layer.linear.weight = nn.Parameter(arena.W[k], requires_grad=requires_grad)
@@ -579,6 +580,7 @@ class DistributedGraphSAGEWrapper(_DistributedWrapper):
             if arena.gamma[k] is not None:
                 layer.lynorm.weight = nn.Parameter(arena.gamma[k], requires_grad=requires_grad)
                 layer.lynorm.bias = nn.Parameter(arena.beta[k], requires_grad=requires_grad)
+        arena.bind_module(model)
         return model
 
     _site_plan = DistributedGNNWrapper._site_plan             # (the same split: the vectors share idx_k)
@@ -842,6 +844,10 @@ def train_graphsage(ist_model, args, g, cluster_iterator, labels, val_mask, test
     `sub` in place; `cluster_iterator` is an EngineClusterIter (use_pp as the wrapper's).  `sub.reset_optimizer()` is
     the fresh optimiser of a dispatch point; an engine's dropout counter runs on across dispatches.  The dropout masks
     are the step's counter-based generator's, not torch's: with dropout 0 the two paths compute the same function.
+    host_path='phases': the loop body of 'module', statement for statement, with every `sub_model` bound to the iterator
+    (gist_amd.module_engine.bind_graphsage): the forward, `loss.backward()` and `optimizer.step()` are the three
+    gist_graphsage_step_phase calls on the wrapper's GraphSAGEEngine (_graphsage_phase_steps).  `cluster_iterator` is a
+    plain ClusterIter on the GPU (use_pp as the wrapper's).  Bit for bit 'step'.
 
     `ist_model` is this rank's DistributedGraphSAGEWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites
     then run in this process, the partition sampled once per dispatch.  eval_path='rows': rank 0's `base_model` is
@@ -849,8 +855,9 @@ def train_graphsage(ist_model, args, g, cluster_iterator, labels, val_mask, test
     Returns what train_gat returns."""
     from .utils import evaluate
     models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
-    if host_path not in ('module', 'step'):
-        raise ValueError("gist_amd: train_graphsage host_path must be 'module' or 'step' (got %r)" % (host_path,))
+    if host_path not in ('module', 'step', 'phases'):
+        raise ValueError("gist_amd: train_graphsage host_path must be 'module' or 'step', or 'phases' for the module loop "
+                         "bound to the fused step (got %r)" % (host_path,))
     if eval_path not in ('layers', 'rows'):
         raise ValueError("gist_amd: train_graphsage eval_path must be 'layers' or 'rows' (got %r)" % (eval_path,))
     if host_path == 'module' and torch.device(models[0].device).type != 'cuda':
@@ -859,7 +866,7 @@ def train_graphsage(ist_model, args, g, cluster_iterator, labels, val_mask, test
     if eval_path == 'rows' and models[0].base_model is not None:
         from .graphsage_eval import GraphSAGEFullGraphEvaluator
         GraphSAGEFullGraphEvaluator.attach(models[0].base_model, arena=models[0].base)
-    steps = {'module': _module_steps, 'step': _graphsage_engine_steps}[host_path]
+    steps = {'module': _module_steps, 'step': _graphsage_engine_steps, 'phases': _graphsage_phase_steps}[host_path]
     at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
 
     def accuracies():
@@ -867,6 +874,38 @@ def train_graphsage(ist_model, args, g, cluster_iterator, labels, val_mask, test
         return evaluate(base_model, g, labels, val_mask), evaluate(base_model, g, labels, test_mask)
     return _run_schedule(models, args, cluster_iterator, lambda line: log(line, flush=True), at_dispatch, step,
                          before_eval, accuracies)
+
+
+def _graphsage_phase_steps(models, args, cluster_iterator):
+    """train_graphsage's (at_dispatch, step, before_eval) for host_path='phases': _module_steps' loop body, with every
+    site's sub_model bound to the iterator first (module_engine.bind_graphsage).  Each wrapper's GraphSAGEEngine
+    (attach_engine: the seed and the dropout counter of 'step') steps its sub arena in place, so dispatch and sync keep
+    writing the storage the step trains and nothing is re-homed; the fresh gist_amd.optim.Adam of a dispatch point
+    brings fresh flat moments and its own step count.  S sites in one process: every forward phase extracts the batch
+    into its own engine's Z_0 (GraphSAGEModuleEngine)."""
+    from .module_engine import bind_graphsage
+    from .sampler import ClusterIter
+    if torch.device(models[0].device).type != 'cuda':
+        raise ValueError("gist_amd: train_graphsage(host_path='phases') runs the fused step's phase calls, which are "
+                         "GPU-only (the wrapper is on %s); there is no CPU fallback" % (models[0].device,))
+    it = cluster_iterator
+    if not isinstance(it, ClusterIter):
+        raise ValueError("gist_amd: train_graphsage(host_path='phases') needs a gist_amd.sampler.ClusterIter as "
+                         "cluster_iterator (got %s)" % type(it).__name__)
+    if bool(it.use_pp) != models[0].use_pp:
+        raise ValueError('gist_amd: the iterator\'s use_pp (%s) is not the wrapper\'s (%s)' % (it.use_pp, models[0].use_pp))
+    if not (it.feed_precalculated() if it.use_pp else it.feed()):
+        raise ValueError("gist_amd: train_graphsage(host_path='phases') needs an iterator that describes its batches for "
+                         "on-device extraction (on the GPU, parts that partition the train graph)")
+    for m in models:
+        m.attach_engine(it.n_max)
+        bind_graphsage(m.sub_model, it)
+    at_dispatch, step, _ = _module_steps(models, args, cluster_iterator)
+
+    def before_eval():                               # (the device is idle: every extraction so far was complete)
+        for m in models:
+            m.engine.check_extract()
+    return at_dispatch, step, before_eval
 
 
 def _graphsage_engine_steps(models, args, cluster_iterator):

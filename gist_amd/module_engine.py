@@ -29,12 +29,17 @@ step reads (they run on the step's stream, after the optimiser launch that extra
 parameter).  Parameters after a step are bitwise those of the engine path (tests/test_module_engine_gpu.py).  GIST_MODULE_ENGINE=0 turns the binding off (the
 op-by-op module path of gist_amd/autograd.py, one dispatcher op per layer: the parity twin).
 
-That is ONE binding, ModuleEngine, for two families.  What is said above of the GCN holds for gist_amd.modules.GAT on
+That is ONE binding, ModuleEngine, for three families.  What is said above of the GCN holds for gist_amd.modules.GAT on
 gist_gat_step_phase, with `gist::gat_forward` / `gist::gat_backward` as its two ops: GATModuleEngine states only where
 the families differ -- how the engine is built and tied to the iterator, which plan field takes the logits, and that the
 logits are saved on the tape (the last GAT layer's ELU backward reads them).  A GAT gets it only when it was bound
 explicitly: `bind_gat(model, cluster_iterator)`.  An unbound gist_amd.modules.GAT keeps the op-by-op path, the
-independent twin its tests compare the fused step with.
+independent twin its tests compare the fused step with.  gist_amd.modules.GraphSAGE likewise, on
+gist_graphsage_step_phase with `gist::graphsage_forward` / `gist::graphsage_backward`, through
+`bind_graphsage(model, cluster_iterator, seed)`: GraphSAGEModuleEngine states how the engine is built and tied to the
+iterator (with use_pp: on the iterator's [X | A^X]); its logits go to the last layer's Y and need not be saved (the
+output layer has no activation).  Its dropout masks are the step's, not nn.Dropout's: bitwise the one-call step, and at
+p > 0 not the unbound loop (bind_graphsage's docstring).
 """
 import os
 import weakref
@@ -79,9 +84,9 @@ def _backward_fake(d_logits, handle, token, given):
     return [d_logits.new_empty(v.shape) for v in _REGISTRY[handle].grad_views]
 
 
-# one pair of ops per family, the forward and backward phases of gist_sage_step / gist_gat_step_phase: the same look-up
-# (the handle names the engine) under the names the traces and the tests know
-for _family in ('gcn', 'gat'):
+# one pair of ops per family, the forward and backward phases of gist_sage_step / gist_gat_step_phase /
+# gist_graphsage_step_phase: the same look-up (the handle names the engine) under the names the traces and the tests know
+for _family in ('gcn', 'gat', 'graphsage'):
     _lib_def.define(_family + '_forward(Tensor[] params, int handle, int token, int n, int ldc, bool train) -> Tensor')
     _lib_def.define(_family + '_backward(Tensor d_logits, int handle, int token, bool given) -> Tensor[]')
     _lib_def.impl(_family + '_forward', _forward_cuda, 'CUDA')
@@ -99,7 +104,7 @@ class _StepForward(torch.autograd.Function):
     # and a strong reference would close engine -> buffer -> node -> engine through C++, where no collector looks)
     @staticmethod
     def forward(ctx, me, token, n, ldc, *params):
-        ctx.me, ctx.token, ctx.n_in = weakref.ref(me), token, 4 + len(params)
+        ctx.me, ctx.token, ctx.n_in, ctx.family = weakref.ref(me), token, 4 + len(params), me.family
         y = me._forward_op(list(params), me.handle, token, n, ldc, True)
         if me._saves_logits:
             ctx.save_for_backward(y)
@@ -109,8 +114,8 @@ class _StepForward(torch.autograd.Function):
     def backward(ctx, d_y):
         me = ctx.me()
         if me is None:
-            raise RuntimeError('gist_amd: backward through the forward of a model that no longer exists')
-        ctx.saved_tensors                              # (raises if saved logits were modified in place)
+            raise RuntimeError('gist_amd: backward through the forward of a %s model that no longer exists' % ctx.family)
+        ctx.saved_tensors                             # (raises if saved logits were modified in place)
         me.autograd_backward(ctx.token, d_y)
         return (None,) * ctx.n_in                      # (the gradients were delivered to p.grad: arena views)
 
@@ -120,15 +125,15 @@ class _FusedLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, me, token):
-        ctx.me, ctx.token = weakref.ref(me), token
+        ctx.me, ctx.token, ctx.who = weakref.ref(me), token, (me.family, me._twin_hint)
         return me._loss0.detach()                      # (an alias: the node hangs on it, not on the ring's own tensor)
 
     @staticmethod
     def backward(ctx, g):
         me = ctx.me()
         if me is None or me.token != ctx.token or me.state != _FWD_DONE:
-            raise RuntimeError('gist_amd: backward through a loss whose forward is no longer the model\'s latest '
-                               '(the engine reuses its buffers; GIST_MODULE_ENGINE=0 for the op-by-op path)')
+            raise RuntimeError('gist_amd: backward through a loss whose %s forward is no longer the model\'s latest '
+                               '(the engine reuses its buffers; %s)' % ctx.who)
         n = me._pending[0].n
         return me.engine.dlogits[:n, :me.n_classes] * g, None, None
 
@@ -564,4 +569,159 @@ def bind_gat(model, cluster_iterator):
 def gat_engine_for(model, g):
     """The GATModuleEngine bind_gat made for the iterator of cluster batch g, or None."""
     mes = model.__dict__.get('_gat_engines')
+    return mes.get(id(g._it)) if mes else None
+
+
+# ---- the GraphSAGE family: gist_amd.modules.GraphSAGE bound to a ClusterIter, on gist_graphsage_step_phase -----------
+def graphsage_model_dims(model):
+    """[(in, out)] of a gist_amd.modules.GraphSAGE as GraphSAGEArena lays it out; ValueError, with the reason, unless the
+    model is exactly the network gist_graphsage_step implements: GraphSAGELayers only, each with a bias; an affine
+    nn.LayerNorm (eps = hip.LN_EPS) and ReLU on all but the last layer, neither on the last; one dropout probability;
+    use_pp on layer 0 at most; in_k = out_{k-1}; at most GIST_MAX_LAYERS layers."""
+    import torch.nn as nn
+    from .modules import GraphSAGELayer
+    layers = list(getattr(model, 'layers', ()))
+    if not layers:
+        raise ValueError('gist_amd: bind_graphsage needs a gist_amd.modules.GraphSAGE (got %s)' % type(model).__name__)
+    if len(layers) > _lib.GIST_MAX_LAYERS:
+        raise ValueError('gist_amd: bind_graphsage: %d layers, the step plan holds %d' % (len(layers), _lib.GIST_MAX_LAYERS))
+    dims = []
+    for k, l in enumerate(layers):
+        last = k == len(layers) - 1
+        if type(l) is not GraphSAGELayer:
+            raise ValueError('gist_amd: bind_graphsage: layer %d is not a GraphSAGELayer' % k)
+        if l.linear.bias is None:
+            raise ValueError('gist_amd: bind_graphsage: layer %d has no bias (bias=False); the step\'s tail adds one' % k)
+        ln = l.lynorm
+        if last:
+            if isinstance(ln, nn.Module) or l.activation:
+                raise ValueError('gist_amd: bind_graphsage: layer %d is the output layer, which the step runs without '
+                                 'norm and activation' % k)
+        else:
+            if not (isinstance(ln, nn.LayerNorm) and ln.elementwise_affine and ln.bias is not None
+                    and ln.eps == hip.LN_EPS and tuple(ln.normalized_shape) == (l.linear.out_features,)):
+                raise ValueError('gist_amd: bind_graphsage: layer %d has no nn.LayerNorm with affine and eps = %g over '
+                                 'its output; the step\'s tail is one' % (k, hip.LN_EPS))
+            if not l.activation or not _is_relu(l.activation):
+                raise ValueError('gist_amd: bind_graphsage: the activation of layer %d is not ReLU' % k)
+        if _p_drop(l) != _p_drop(layers[0]):
+            raise ValueError('gist_amd: bind_graphsage: layer %d drops with p = %g, layer 0 with p = %g; the step has '
+                             'one dropout probability' % (k, _p_drop(l), _p_drop(layers[0])))
+        if k > 0 and l.use_pp:
+            raise ValueError('gist_amd: bind_graphsage: layer %d has use_pp; only layer 0 reads [X | A^X]' % k)
+        i, o = l.linear.in_features // 2, l.linear.out_features
+        if l.linear.in_features != 2 * i or (k > 0 and i != dims[-1][1]):
+            raise ValueError('gist_amd: bind_graphsage: layer %d reads %d columns, layer %d gives 2 x %d'
+                             % (k, l.linear.in_features, k - 1, dims[-1][1] if dims else 0))
+        dims.append((i, o))
+    return dims
+
+
+def _p_drop(layer):
+    """The dropout probability of a GraphSAGELayer (its `dropout` is an nn.Dropout, or 0.)."""
+    d = layer.dropout
+    return float(d.p) if isinstance(d, torch.nn.Dropout) else 0.0
+
+
+class GraphSAGEModuleEngine(ModuleEngine):
+    """One gist_amd.modules.GraphSAGE bound to one ClusterIter (bind_graphsage): the GraphSAGEEngine behind
+    `model(cluster)`.  The surface is ModuleEngine's on gist_graphsage_step_phase.  The forward phase advances the
+    engine's dropout counter once; the backward phase gets the same offset back from StepEngine._run."""
+    family = 'GraphSAGE'
+    _forward_op, _backward_op = torch.ops.gist.graphsage_forward, torch.ops.gist.graphsage_backward
+    _saves_logits = False       # (the output layer has no activation: an in-place edit of pred before backward() is legal)
+    _twin_hint = 'an unbound model runs op by op'
+
+    def __init__(self, model, it, dims, seed=0):
+        self._seed = int(seed)
+        ModuleEngine.__init__(self, model, it, dims)
+
+    def _bind_engine(self, model, it, dims):
+        from .graphsage_engine import GraphSAGEEngine
+        others = [m for m in (r() for r in it.__dict__.setdefault('_graphsage_bound', [])) if m is not None]
+        p, use_pp = _p_drop(model.layers[0]), bool(model.layers[0].use_pp)
+        # a DistributedGraphSAGEWrapper's sub_model already IS its arena: the engine steps that arena in place (dispatch
+        # and sync write it between steps) -- the wrapper's own engine (attach_engine: its seed, its dropout counter) if
+        # it has a fitting one; any other model is re-homed into an arena of the engine's own
+        shared = shared_arena(model, dims, need_grads=False)
+        eng = None
+        if shared is not None:
+            ref = shared.__dict__.get('_engine')
+            eng = ref() if ref is not None else None
+            if eng is not None and (eng.n_max != it.n_max or eng.use_pp != use_pp or eng.p_drop != p):
+                eng = None
+        if eng is None:
+            eng = GraphSAGEEngine(dims, p, it.n_max, it.g.device, seed=self._seed, use_pp=use_pp, arena=shared)
+        if shared is None:
+            eng.arena.adopt_module(model)
+        if not others:
+            if it.engine is not eng or eng.plan is None:
+                it.bind(eng)                  # the iterator's engine: its epoch-end extraction check
+        elif eng.plan is None or eng._plan_keep[0] is not it.batcher:
+            eng.attach_batcher(it.batcher)
+        # GATModuleEngine's rule.  One model on the iterator: the optimiser launch extracts the next batch.  Several (the
+        # S sites of one process): they share the batch buffers, and a training step leaves dropped values in its own
+        # Z_0, so nobody extracts ahead and every forward phase extracts its batch into its own engine's Z_0
+        it._graphsage_bound = [weakref.ref(m) for m in others] + [weakref.ref(self)]
+        for m in others:
+            m.engine.prefetch = False
+        eng.prefetch = not others
+        return eng
+
+
+def bind_graphsage(model, cluster_iterator, seed=0):
+    """Bind a gist_amd.modules.GraphSAGE to a gist_amd.sampler.ClusterIter: from now on `model(cluster)` on that
+    iterator's batches, gist_amd.nn.CrossEntropyLoss on the result, `loss.backward()` and gist_amd.optim.Adam.step() are
+    the three phase calls of gist_graphsage_step_phase on one preallocated plan -- the engine path's launches.  Any
+    other loss on `pred` is an ordinary autograd graph that ends in the backward phase with the caller's d_logits; two
+    backwards before one step accumulate.  Explicit and opt-in: an unbound GraphSAGE runs op by op, as before.  Legal
+    before or after the optimiser is built.  With use_pp (the model's layer 0 and the iterator alike) the iterator's
+    device feed is turned on: its resident features are the [X | A^X] precalc built.
+
+    Dropout: the masks come from the step's counter-based generator (`seed`, the engine's running `drop_calls`), not from
+    nn.Dropout's Philox stream.  A bound loop is therefore bitwise the one-call step (GraphSAGEEngine.train_step, same
+    seed and batch order) and its op-by-op twin; against the UNBOUND loop it has the same distribution but, at p > 0,
+    not the same bits ("Dropout").  With p = 0 it computes the unbound loop's function.
+
+    Returns the GraphSAGEModuleEngine; a second call with the same iterator returns the same one.  ValueError, with the
+    reason, if the model or the iterator cannot run on the fused step: nothing falls back silently."""
+    from .arena import GraphSAGEArena
+    from .sampler import ClusterIter
+    dims = graphsage_model_dims(model)
+    it = cluster_iterator
+    if not isinstance(it, ClusterIter):
+        raise ValueError('gist_amd: bind_graphsage needs a gist_amd.sampler.ClusterIter (got %s)' % type(it).__name__)
+    mes = model.__dict__.get('_graphsage_engines')
+    if mes:
+        me = mes.get(id(it))
+        if me is not None:
+            return me
+        raise ValueError('gist_amd: bind_graphsage: this model is already bound to another iterator')
+    use_pp = bool(model.layers[0].use_pp)
+    if use_pp != bool(it.use_pp):
+        raise ValueError('gist_amd: bind_graphsage: the model\'s use_pp (%s) is not the iterator\'s (%s)' % (use_pp, it.use_pp))
+    params = GraphSAGEArena.module_params(model)
+    dev = it.g.device
+    if dev.type != 'cuda' or not (it.feed_precalculated() if use_pp else it.feed()):
+        raise ValueError('gist_amd: bind_graphsage: the iterator does not describe its batches for on-device extraction '
+                         '(device %s, GIST_MODULE_ENGINE=%s): the fused step is GPU-only and extracts the batch itself'
+                         % (dev, os.environ.get('GIST_MODULE_ENGINE', '1')))
+    for p in params:
+        if p.dtype != torch.float32 or p.device != dev:
+            raise ValueError('gist_amd: bind_graphsage: parameters must be fp32 on %s (found %s on %s); model.to(device) '
+                             'first' % (dev, p.dtype, p.device))
+    want = (2 if use_pp else 1) * dims[0][0]
+    if want != it.batcher.feat.shape[1]:
+        raise ValueError('gist_amd: bind_graphsage: the model takes %d input features%s, the iterator\'s graph has %d'
+                         % (dims[0][0], ' ([X | A^X]: %d columns)' % want if use_pp else '', it.batcher.feat.shape[1]))
+    if hip._prof is not None:
+        raise ValueError('gist_amd: bind_graphsage: the op profiler is on; the fused step has no per-op records')
+    me = GraphSAGEModuleEngine(model, it, dims, seed)
+    model.__dict__.setdefault('_graphsage_engines', {})[id(it)] = me
+    return me
+
+
+def graphsage_engine_for(model, g):
+    """The GraphSAGEModuleEngine bind_graphsage made for the iterator of cluster batch g, or None."""
+    mes = model.__dict__.get('_graphsage_engines')
     return mes.get(id(g._it)) if mes else None

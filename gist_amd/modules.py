@@ -131,7 +131,15 @@ class GraphSAGE(nn.Module):
                                           use_lynorm=False))
 
     def forward(self, g):
-        """modules.py:185-189, on a cluster batch and on the full graph alike."""
+        """modules.py:185-189, on a cluster batch and on the full graph alike.  A model that module_engine.bind_graphsage
+        bound to an iterator runs that iterator's batches on the fused step instead (one dispatcher op,
+        gist::graphsage_forward; in evaluation mode the forward-only step, where layer 0 aggregates even under use_pp,
+        GraphSAGELayer.forward); everything else -- the full graph of an evaluation, a hand-built graph, a batch of another
+        iterator, an unbound model -- takes the layers below."""
+        if type(g) is ClusterBatch and '_graphsage_engines' in self.__dict__:
+            me = module_engine.graphsage_engine_for(self, g)
+            if me is not None:
+                return me.forward(g, self.training)
         h = g.ndata['feat']
         for layer in self.layers:
             h = layer(g, h)

@@ -136,21 +136,39 @@ class ClusterIter(object):
         return self.max
 
     def feed(self):
-        """True when this iterator describes its batches for on-device extraction (lazily set up on first use)."""
+        """True when this iterator describes its batches for on-device extraction (lazily set up on first use).  Not with
+        use_pp, unless feed_precalculated() turned it on."""
         if self._feed is None:
-            self._feed = False
-            tg = self.g
-            ok = (os.environ.get('GIST_MODULE_ENGINE', '1') != '0' and not self.use_pp and tg.device.type == 'cuda'
-                  and 'feat' in tg.ndata and 'label' in tg.ndata and tg.ndata['feat'].dim() == 2
-                  and tg.ndata['feat'].dtype == torch.float32 and self.max > 0)
-            if ok:
-                self._init_feed()
-                self._feed = self._node_part is not None and hip._lib.load().gist_extract_parts_supported(self.n_max) == 1
-                if self._feed:
-                    tm = tg.ndata.get('train_mask')
-                    self._all_train = bool(tm.all().item()) if tm is not None else False
-                    self._ones = torch.ones(self.n_max, dtype=torch.bool, device=tg.device)
+            self._feed = (not self.use_pp) and self._try_feed()
         return self._feed
+
+    def feed_precalculated(self):
+        """feed() for a use_pp iterator, on request (module_engine.bind_graphsage: the one consumer whose step takes the
+        [X | A^X] that precalc built as its resident features).  Nobody asking, such an iterator keeps building every
+        cluster eagerly.  Call it between epochs: the batches of an epoch under way stay what they were."""
+        if self.use_pp and not self._feed:
+            self._feed = False
+            if self._try_feed():
+                self._upload_epoch()          # (the tables a ClusterBatch reads, should the first epoch have begun)
+                self._epoch_cols = {}
+                self._feed = True
+        return self.feed()
+
+    def _try_feed(self):
+        """Set the device feed up if this iterator can have one -> does it?"""
+        tg = self.g
+        ok = (os.environ.get('GIST_MODULE_ENGINE', '1') != '0' and tg.device.type == 'cuda'
+              and 'feat' in tg.ndata and 'label' in tg.ndata and tg.ndata['feat'].dim() == 2
+              and tg.ndata['feat'].dtype == torch.float32 and self.max > 0)
+        if not ok:
+            return False
+        self._init_feed()
+        if self._node_part is None or hip._lib.load().gist_extract_parts_supported(self.n_max) != 1:
+            return False
+        tm = tg.ndata.get('train_mask')
+        self._all_train = bool(tm.all().item()) if tm is not None else False
+        self._ones = torch.ones(self.n_max, dtype=torch.bool, device=tg.device)
+        return True
 
     def _bound_run_ahead(self):
         """An epoch that was left early (a `break`, a step cap) never reached the deferred check at its end, which is also

@@ -10,7 +10,9 @@ gist_amd.ist.DistributedGraphSAGEWrapper and gist_amd.ist.train_graphsage.
     done; wait
 
 `--host-path module` (the default) is the reference's loop body on `ist_model.sub_model`; `--host-path step` runs every
-iteration as one gist_graphsage_step call on the wrapper's GraphSAGEEngine.  `--eval-path rows` evaluates rank 0's base
+iteration as one gist_graphsage_step call on the wrapper's GraphSAGEEngine; `--host-path phases` keeps the loop body of
+`module` and binds the sub-model to the iterator, so its forward, `loss.backward()` and `optimizer.step()` are the three
+gist_graphsage_step_phase calls on that engine (bitwise `step`).  `--eval-path rows` evaluates rank 0's base
 model with the row-blocked GraphSAGEFullGraphEvaluator instead of the model's own forward.  `--use-pp` is honoured: the
 iterator's train features become [X | A^X] and layer 0 only projects them while training.  `--use_layernorm` is accepted:
 this family's LayerNorm (with affine) is always on.  Set-up (seeds, device, process group, --normalize, data loading) is
@@ -28,7 +30,7 @@ def build_parser():
     parser = add_ist_args(argparse.ArgumentParser(description='GCN'))
     parser.add_argument("--exp_name", type=str, default='distributed_gnn_ist')
     # (not flags of the reference) gist_amd.ist.train_graphsage's host_path and eval_path
-    parser.add_argument("--host-path", choices=['step', 'module'], default='module')
+    parser.add_argument("--host-path", choices=['step', 'module', 'phases'], default='module')
     parser.add_argument("--eval-path", choices=['layers', 'rows'], default='layers')
     return parser
 

@@ -1356,12 +1356,45 @@ int gist_graphsage_step_folds(const gist_graphsage_step_plan *plan, int32_t k);
  * flags: GIST_STEP_EXTRACT, GIST_STEP_TRAIN (without it: forward + loss only, no dropout, no parameter touched),
  * GIST_STEP_EXTRACT_NEXT (the optimiser launch is gist_adam_segments_extract_f32 with no segments and also extracts
  * plan->next_*) and GIST_STEP_PREEXTRACTED, with their gist_sage_step meaning.  The GIST_STEP_PHASE_* bits and
- * GIST_STEP_DLOGITS_GIVEN are GIST_EINVAL: this step has no phase calls.  Every argument is checked (null pointers,
- * sizes, n > n_max, more than GIST_MAX_LAYERS layers, mismatched widths: GIST_EINVAL; a workspace too small for this n:
- * GIST_ENOSPACE) before any device work. */
+ * GIST_STEP_DLOGITS_GIVEN are gist_graphsage_step_phase's (below), here GIST_EINVAL.  Every argument is checked (null
+ * pointers, sizes, n > n_max, more than GIST_MAX_LAYERS layers, mismatched widths: GIST_EINVAL; a workspace too small
+ * for this n: GIST_ENOSPACE) before any device work. */
 int gist_graphsage_step(const gist_graphsage_step_plan *plan, const int32_t *ids, int64_t n, uint64_t drop_offset,
                         float lr, float beta1, float beta2, float eps, float weight_decay, int64_t adam_step,
                         int flags, gist_stream_t stream);
+
+/* The same iteration as three calls, for a script that keeps the reference's loop body (cluster_gcn/cluster_gcn.py:96-105,
+ * cluster_gcn_ist_distrib.py:408-417: `pred = model(cluster)`, `loss = loss_f(...)`, `loss.backward()`,
+ * `optimizer.step()`: gist_amd/module_engine.py, bind_graphsage).  flags = GIST_STEP_TRAIN | exactly one
+ * GIST_STEP_PHASE_* bit | the iteration's other flags; the three calls get the same (plan, ids, n, other flags):
+ *   FORWARD    reads EXTRACT / PREEXTRACTED: the extraction, then per layer the aggregation, the dropout, gist_gemm_nt_f32
+ *              and the tail, then gist_softmax_xent_f32.  In stream order plan->loss, plan->dlogits and the logits in
+ *              layer[n_layers - 1].Y are complete.  It checks the batch and loss buffers, per layer W b Z Y (gamma beta
+ *              yhat rstd of a hidden layer), the EXTRACT inputs and the workspace of every layer's forward product; the
+ *              gradient views may be NULL;
+ *   BACKWARD   the reverse layer loop from plan->dlogits; the gradient arena is COMPLETE on return.  It checks the
+ *              gradient views, partials, dZ (n_layers > 1), ln_workspace and the workspace of the two gradient products.
+ *              With GIST_STEP_DLOGITS_GIVEN the caller has overwritten plan->dlogits [n, n_classes] with the gradient of
+ *              ITS loss w.r.t. the logits (the forward's gist_softmax_xent_f32 still ran): the output layer has no
+ *              activation, so nothing is recomputed;
+ *   OPTIMIZER  the one Adam launch over the arena from plan->grads and plan->exp_avg / exp_avg_sq as they stand at the
+ *              call (lr ... adam_step, 1-based, are read by this phase only); with EXTRACT_NEXT it is
+ *              gist_adam_segments_extract_f32 with no segments, which also extracts plan->next_*.
+ * drop_offset places the layers' masks in the counter space exactly as in gist_graphsage_step.  The FORWARD and the
+ * BACKWARD call of an iteration get the SAME value: the backward's gist_gemm_nn_dropout_f32 re-derives each mask from
+ * it; the OPTIMIZER call ignores it.  Which layers fold their dropout (gist_graphsage_step_folds) is decided from the
+ * plan alone in every call, so the plan -- p_drop, seed, the layers' H and Z, row_blocks -- MUST NOT CHANGE between the
+ * FORWARD and the BACKWARD call of an iteration.
+ * The three calls issue exactly the launches of one gist_graphsage_step call, in its order, through the same functions:
+ * parameters, loss and moments are bitwise the one-call step's.  The ORDER of the phases is the caller's contract: the
+ * driver keeps no state between calls (the plan's buffers are the state), so a BACKWARD without its FORWARD reads
+ * whatever the buffers hold.  The logits, loss and moment pointers are plan fields the host may set per call.
+ * Every call checks what ITS phase reads before any device work: no phase bit or more than one, no GIST_STEP_TRAIN,
+ * DLOGITS_GIVEN without BACKWARD, EXTRACT with PREEXTRACTED, null buffers, bad shapes, n > n_max: GIST_EINVAL; a
+ * workspace or ln_workspace too small for this n: GIST_ENOSPACE. */
+int gist_graphsage_step_phase(const gist_graphsage_step_plan *plan, const int32_t *ids, int64_t n,
+                              uint64_t drop_offset, float lr, float beta1, float beta2, float eps, float weight_decay,
+                              int64_t adam_step, int flags, gist_stream_t stream);
 
 #ifdef __cplusplus
 }
