@@ -176,6 +176,10 @@ SIGNATURES = {
     'gist_ln_affine_bwd_workspace_floats': (_i64, [_i64, _i64]),
     'gist_ln_affine_bwd_f32': (_int, [_p, _i64, _p, _i64, _p, _p, _p, _int, _p, _i64, _p, _p, _p, _i64, _i64, _p, _i64,
                                       _p]),
+    'gist_gcn_tail_fwd_f32': (_int, [_p, _p, _p, _p, _p, _i64, _i64, _int, _int, _f, _f, _u64, _u64, _p, _p]),
+    'gist_gcn_tail_infer_f32': (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _f, _p, _p]),
+    'gist_gcn_tail_bwd_workspace_floats': (_i64, [_i64, _i64]),
+    'gist_gcn_tail_bwd_f32': (_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _int, _int, _f, _u64, _u64, _p, _i64, _p]),
 }
 
 GIST_MAX_LAYERS = 16

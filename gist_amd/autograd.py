@@ -7,6 +7,7 @@ in libgist_hip.so.
   sage_layer(...)       one whole ISTSAGELayer.forward, fused      (modules.py:218-237)
   gat_layer(...)        one whole MultiHeadGATLayer.forward, fused (modules.py:57-76)
   layer_norm_affine(...) bias + nn.LayerNorm(affine) + relu of a GraphSAGELayer (modules.py:120,144-147)
+  gcn_tail(...)         bias + relu + whole-tensor LayerNorm + next dropout of a BaselineGCN layer (modules.py:345-348)
   matmul, layer_norm_rows, whole_tensor_layer_norm, layer_norm_all (gcn/gcn.py:30-67)
 """
 import torch
@@ -64,6 +65,15 @@ def layer_norm_affine(x, weight, bias, lin_bias=None, relu=False):
     """nn.LayerNorm(d, elementwise_affine=True) of x + lin_bias (the projection's bias; None: x), optional relu, as one
     launch in each direction (modules.py:120,144-147)."""
     return torch.ops.gist.layer_norm_affine_fwd(x, weight, bias, lin_bias, bool(relu))[0]
+
+
+def gcn_tail(x, bias, relu, norm, p=0.0, seed=0):
+    """The tail of a BaselineGCN layer on x = the aggregated projection [n, d] (modules.py:345-348): GraphConv's bias and
+    relu, F.layer_norm(h, h.shape) when `norm`, and the NEXT layer's dropout with probability p under the project's
+    generator, as two launches forward (one without norm) and three backward (two)."""
+    p = float(p)
+    off = next_dropout_offset(x.numel()) if p > 0.0 else 0
+    return torch.ops.gist.gcn_tail_fwd(x, bias, bool(relu), bool(norm), p, int(seed), off)[0]
 
 
 def whole_tensor_layer_norm(h):

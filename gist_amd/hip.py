@@ -590,6 +590,64 @@ def ln_affine_bwd(d_out, yhat, rstd, gamma, beta, relu, dx, dgamma, dbeta, dlin_
     return dx
 
 
+def _tail_args(x, b, name):
+    """x [n, d] dense (ld == d) and b [d] of a gcn_tail_* call -> (x ptr, b ptr, n, d)"""
+    _dev(x, 'x', torch.float32)
+    if x.dim() != 2 or not x.is_contiguous():
+        raise ValueError('gist_amd: %s wants a dense 2-D x' % name)
+    n, d = x.shape
+    return x.data_ptr(), _vec(b, 'b', torch.float32, d), n, d
+
+
+def _tail_partials(n, device, norm, ws):
+    """the forward's scratch: the caller's float32 tensor of gist_ln_all_partials(n) elements, or the shared workspace"""
+    if ws is not None:
+        return _vec(ws, 'ws', torch.float32, int(_lib.load().gist_ln_all_partials(n)))
+    return _ln_all_partials(n, device) if norm else None
+
+
+def gcn_tail_fwd(x, b, yhat, out, stats, relu, norm, p=0.0, seed=0, offset=0, eps=LN_EPS, ws=None):
+    """The BaselineGCN layer tail of x [n, d] (gist_gcn_tail_fwd_f32): yhat = the whole-tensor LayerNorm (when `norm`) of
+    relu?(x + b), stats <- (mean, rstd), out = yhat under gist_dropout_f32's mask at offset + r * d + c.  p = 0: out may
+    be None or yhat."""
+    L = _lib.load()
+    xp, bp, n, d = _tail_args(x, b, 'gcn_tail_fwd')
+    ws = _tail_partials(n * d, x.device, norm, ws)
+    _lib.check(L.gist_gcn_tail_fwd_f32(xp, bp, None if yhat is None else _flat(yhat, 'yhat', n * d),
+                                       None if out is None else _flat(out, 'out', n * d),
+                                       _opt(stats, 'stats', torch.float32, 2), n, d, int(bool(relu)), int(bool(norm)),
+                                       eps, float(p), int(seed), int(offset), ws, _stream()), 'gist_gcn_tail_fwd_f32')
+    return yhat if out is None else out
+
+
+def gcn_tail_infer(x, b, out, relu, norm, stats=None, eps=LN_EPS, ws=None):
+    """out = gcn_tail_fwd's yhat and nothing else (gist_gcn_tail_infer_f32); out may be x itself."""
+    L = _lib.load()
+    xp, bp, n, d = _tail_args(x, b, 'gcn_tail_infer')
+    ws = _tail_partials(n * d, x.device, norm, ws)
+    _lib.check(L.gist_gcn_tail_infer_f32(xp, bp, _flat(out, 'out', n * d), _opt(stats, 'stats', torch.float32, 2), n, d,
+                                         int(bool(relu)), int(bool(norm)), eps, ws, _stream()),
+               'gist_gcn_tail_infer_f32')
+    return out
+
+
+def gcn_tail_bwd(d_out, x, b, yhat, stats, dx, dbias, relu, norm, p=0.0, seed=0, offset=0, ws=None):
+    """dx and dbias = the column sums of dx of gcn_tail_fwd (gist_gcn_tail_bwd_f32).  yhat and stats may be None without
+    `norm`.  ws: float32 scratch of gist_gcn_tail_bwd_workspace_floats(n, d) elements (None: taken here)."""
+    L = _lib.load()
+    xp, bp, n, d = _tail_args(x, b, 'gcn_tail_bwd')
+    need = int(L.gist_gcn_tail_bwd_workspace_floats(n, d))
+    if ws is None:
+        ws = torch.empty(max(need, 2), dtype=torch.float32, device=x.device)
+    _lib.check(L.gist_gcn_tail_bwd_f32(_flat(d_out, 'd_out', n * d), xp, bp,
+                                       None if yhat is None else _flat(yhat, 'yhat', n * d),
+                                       _opt(stats, 'stats', torch.float32, 2), _flat(dx, 'dx', n * d),
+                                       _vec(dbias, 'dbias', torch.float32, d), n, d, int(bool(relu)), int(bool(norm)),
+                                       float(p), int(seed), int(offset), _vec(ws, 'ws', torch.float32, need), ws.numel(),
+                                       _stream()), 'gist_gcn_tail_bwd_f32')
+    return dx
+
+
 def dropout_(z, p, seed, offset):
     L = _lib.load()
     zp, ldz = _mat(z, 'z')

@@ -201,6 +201,70 @@ class GCN(nn.Module):
         return h
 
 
+class BaselineGCN(nn.Module):
+    """The reference's BaselineGCN (cluster_gcn/modules.py:316-349), the plain GCN of the Cluster-GCN and GIST papers: a
+    stack of GraphConv layers (symmetric normalisation, activation inside the layer), dropout in front of every layer
+    but the first, F.layer_norm(h, h.shape) -- ONE mean and variance over the whole tensor -- after every layer but the
+    last.  The reference's seven constructor arguments, its attributes (`layers[k].weight / .bias`, `dropout`,
+    `use_layernorm`) and its initialisation order (xavier-uniform weight, zero bias per layer, :331-338).
+
+    tail='fused' (with a ReLU activation): a layer is aggregation and projection in GraphConv's order and then ONE tail
+    op (autograd.gcn_tail: bias, ReLU, the whole-tensor norm and the NEXT layer's dropout).  The masks are the project's
+    generator's (gist_dropout_f32), not torch's: at p > 0 the same distribution as the reference, not the same bits.
+    tail='composed', or any other activation: the reference's loop body, literally."""
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout, use_layernorm=True, *,
+                 tail='fused'):
+        super().__init__()
+        from .dgl_compat.nn.pytorch import GraphConv
+        if tail not in ('fused', 'composed'):
+            raise ValueError("gist_amd: tail must be 'fused' or 'composed' (got %r)" % (tail,))
+        self.layers = nn.ModuleList()
+        self.use_layernorm = use_layernorm
+        self.layers.append(GraphConv(in_feats, n_hidden, activation=activation))
+        for i in range(n_layers - 1):
+            self.layers.append(GraphConv(n_hidden, n_hidden, activation=activation))
+        self.layers.append(GraphConv(n_hidden, n_classes))
+        self.dropout = nn.Dropout(p=dropout)
+        self.tail = tail
+        self.drop_seed = 0
+
+    def set_dropout_seed(self, seed):
+        self.drop_seed = int(seed)
+
+    def _fused(self):
+        return self.tail == 'fused' and all(_is_relu(layer._activation) for layer in self.layers[:-1])
+
+    def forward(self, g):
+        h = g.ndata['feat']
+        if not self._fused():
+            for i, layer in enumerate(self.layers):                # modules.py:343-348
+                if i != 0:
+                    h = self.dropout(h)
+                h = layer(g, h)
+                if i < len(self.layers) - 1 and self.use_layernorm:
+                    h = autograd.layer_norm_all(h)
+            return h
+        # the degree scales of GraphConv.forward, once for all layers
+        ns = torch.pow((g.t_rowptr[1:] - g.t_rowptr[:-1]).float().clamp(min=1), -0.5).contiguous()
+        nd = torch.pow((g.rowptr[1:] - g.rowptr[:-1]).float().clamp(min=1), -0.5).contiguous()
+        p = float(self.dropout.p) if self.training else 0.0
+        last = len(self.layers) - 1
+        for i, layer in enumerate(self.layers):
+            if layer._in_feats > layer._out_feats:
+                h = autograd.spmm_sum(g, autograd.matmul(h, layer.weight), out_scale=nd, src_scale=ns)
+            else:
+                h = autograd.matmul(autograd.spmm_sum(g, h, out_scale=nd, src_scale=ns), layer.weight)
+            hidden = i < last
+            norm = hidden and bool(self.use_layernorm)
+            if torch.is_grad_enabled() or (hidden and p > 0.0):
+                h = autograd.gcn_tail(h, layer.bias, hidden, norm, p if hidden else 0.0, self.drop_seed)
+            else:
+                # an evaluation keeps nothing for a backward: the tail rewrites the layer's own output in place
+                h = hip.gcn_tail_infer(h, layer.bias.detach(), h, hidden, norm)
+        return h
+
+
 def _stack_heads(heads):
     """The heads' fc weights stacked [H*F, in] and attn_fc weights stacked [H, 2F] (differentiable: the per-head
     Parameters stay the model's parameters, so a GIST split can slice them head by head)."""

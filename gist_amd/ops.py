@@ -20,6 +20,7 @@ are themselves gist ops.  There is NO CPU implementation: a CPU tensor fails in 
   gist::matmul, gist::layer_norm_rows   pieces of the GraphConv path      gcn/gcn.py:30-67
   gist::layer_norm_all     F.layer_norm(h, h.shape) over the grid         gcn/gcn.py:65-66
   gist::layer_norm_affine_fwd/bwd  bias + nn.LayerNorm(affine) + relu of a GraphSAGELayer   modules.py:120,144-147
+  gist::gcn_tail_fwd/bwd   bias + relu + F.layer_norm(h, h.shape) + next dropout of a BaselineGCN layer   modules.py:345-348
 
 The reversed CSR travels with every aggregation op (t_rowptr, t_col): the backward of an
 aggregation is the same op on the reversed graph with the two scales swapped.
@@ -545,8 +546,70 @@ def _lna_backward(ctx, g, g_yhat, g_rstd):
 
 layer_norm_affine_fwd.register_autograd(_lna_backward, setup_context=_lna_setup)
 
+
+# -- the BaselineGCN layer tail (cluster_gcn/modules.py:345-348) ---------------------------------------------
+@torch.library.custom_op('gist::gcn_tail_fwd', mutates_args=(), device_types='cuda')
+def gcn_tail_fwd(x: Tensor, bias: Tensor, relu: bool, norm: bool, p: float, seed: int,
+                 offset: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """GraphConv's bias and relu, F.layer_norm(h, h.shape) (eps 1e-5) and the next layer's dropout, two launches (one
+    without norm): (out, yhat, stats).  yhat is only a tensor of its own when the backward needs one that differs from
+    out (norm and p > 0), otherwise it is empty."""
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    stats = torch.empty(2, dtype=torch.float32, device=x.device)
+    yhat = torch.empty_like(x) if norm and p > 0.0 else None
+    if x.numel() > 0:
+        if p > 0.0:
+            hip.gcn_tail_fwd(x, bias.contiguous(), yhat, out, stats, relu, norm, p, seed, offset)
+        else:
+            hip.gcn_tail_fwd(x, bias.contiguous(), out, None, stats, relu, norm)
+    return out, x.new_empty(0) if yhat is None else yhat, stats
+
+
+@gcn_tail_fwd.register_fake
+def _(x, bias, relu, norm, p, seed, offset):
+    return x.new_empty(x.shape), x.new_empty(x.shape if norm and p > 0.0 else (0,)), x.new_empty(2)
+
+
+@torch.library.custom_op('gist::gcn_tail_bwd', mutates_args=(), device_types='cuda')
+def gcn_tail_bwd(g: Tensor, x: Tensor, bias: Tensor, yhat: Tensor, stats: Tensor, relu: bool, norm: bool, p: float,
+                 seed: int, offset: int) -> Tuple[Tensor, Tensor]:
+    """(dx, dbias): the sums of no rows are zeros."""
+    n, d = x.shape
+    dx = torch.empty_like(x)
+    db = (torch.zeros if x.numel() == 0 else torch.empty)(d, dtype=torch.float32, device=x.device)
+    if x.numel() > 0:
+        hip.gcn_tail_bwd(g.contiguous(), x, bias.contiguous(), yhat if norm else None, stats if norm else None, dx, db,
+                         relu, norm, p, seed, offset)
+    return dx, db
+
+
+@gcn_tail_bwd.register_fake
+def _(g, x, bias, yhat, stats, relu, norm, p, seed, offset):
+    return x.new_empty(x.shape), x.new_empty(x.shape[1])
+
+
+def _tail_setup(ctx, inputs, output):
+    x, bias, relu, norm, p, seed, offset = inputs
+    out, yhat, stats = output
+    # without a mask out IS yhat; without norm the backward reads neither (yhat is the empty tensor then)
+    ctx.save_for_backward(x.contiguous(), bias, out if norm and p == 0.0 else yhat, stats)
+    ctx.flags = (relu, norm, p, seed, offset)
+
+
+def _tail_backward(ctx, g, g_yhat, g_stats):
+    x, bias, yhat, stats = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    if not (need[0] or need[1]):
+        return (None,) * 7
+    dx, db = torch.ops.gist.gcn_tail_bwd(g, x, bias, yhat, stats, *ctx.flags)
+    return (dx if need[0] else None, db.reshape(bias.shape) if need[1] else None, None, None, None, None, None)
+
+
+gcn_tail_fwd.register_autograd(_tail_backward, setup_context=_tail_setup)
+
 OPS = ('spmm_sum', 'sage_layer', 'sage_layer_fwd', 'sage_layer_bwd', 'gat_layer', 'gat_layer_fwd', 'gat_layer_bwd',
        'induced_subgraph',
        'block_gather', 'block_scatter_', 'adam_step_', 'matmul', 'matmul_nt', 'matmul_tn',
        'layer_norm_rows_fwd', 'layer_norm_rows_bwd', 'layer_norm_all', 'layer_norm_all_bwd',
-       'layer_norm_affine_fwd', 'layer_norm_affine_bwd')
+       'layer_norm_affine_fwd', 'layer_norm_affine_bwd', 'gcn_tail_fwd', 'gcn_tail_bwd')

@@ -34,7 +34,7 @@ def build_parser():
     parser.add_argument("--use-pp", action='store_true', help="whether to use precomputation")
     parser.add_argument("--normalize", action='store_true', help="whether to use normalized feature")
     parser.add_argument("--weight-decay", type=float, default=0, help="Weight for L2 loss")
-    parser.add_argument("--model-type", type=str, default='sage', help="sage, gat or graphsage")
+    parser.add_argument("--model-type", type=str, default='sage', help="sage, gat, graphsage or baseline")
     parser.add_argument("--n-heads", type=int, default=4, help="attention heads of the GAT layers")
     # (not a flag of the reference) cat: the hidden GAT layers concatenate their heads (its comment, modules.py:87-89)
     parser.add_argument("--head-merge", choices=['mean', 'cat'], default='mean',
@@ -70,20 +70,9 @@ def attach_eval_path(args, model, arena=None):
         GraphSAGEFullGraphEvaluator.attach(model, arena=arena)
 
 
-def main(args, dataset=None, log=print):
+def load_graph(args, dataset, log):
+    """the dataset's graph, the device, and the sizes every path of main needs (cluster_gcn.py:24-43)"""
     from gist_amd.dgl_compat.data import load_data
-    from gist_amd.modules import GCN
-    from gist_amd.trainer import ClusterGCNTrainer
-    torch.manual_seed(args.rnd_seed)                       # cluster_gcn.py:20-22
-    np.random.seed(args.rnd_seed)
-    random.seed(args.rnd_seed)
-    if args.gpu < 0 or args.eval_cpu:
-        raise SystemExit('gist_amd runs on the GPU only (no CPU fallback): --gpu >= 0, no --eval-cpu')
-    if args.model_type not in ('sage', 'gat', 'graphsage'):
-        raise NotImplementedError(f'{args.model_type} is not a supported model type')
-    if getattr(args, 'eval_path', 'layers') == 'rows' and args.model_type != 'graphsage':
-        raise SystemExit('gist_amd: --eval-path rows is the GraphSAGE family\'s evaluator (--model-type graphsage); the SAGE '
-                         'engine path already evaluates with trainer.FullGraphEvaluator, the GAT has --eval-path blocked')
     data = dataset if dataset is not None else load_data(args)
     g = data.g
     device = torch.device('cuda', args.gpu)
@@ -100,6 +89,25 @@ def main(args, dataset=None, log=print):
     psize = len(par_li) if par_li is not None else args.psize
     log('labels shape:', g.ndata['label'].shape)
     log("features shape, ", g.ndata['feat'].shape)
+    return data, g, device, in_feats, n_classes, par_li, psize
+
+
+def main(args, dataset=None, log=print):
+    from gist_amd.modules import GCN
+    from gist_amd.trainer import ClusterGCNTrainer
+    torch.manual_seed(args.rnd_seed)                       # cluster_gcn.py:20-22
+    np.random.seed(args.rnd_seed)
+    random.seed(args.rnd_seed)
+    if args.gpu < 0 or args.eval_cpu:
+        raise SystemExit('gist_amd runs on the GPU only (no CPU fallback): --gpu >= 0, no --eval-cpu')
+    if args.model_type == 'baseline':
+        return main_baseline(args, dataset, log)
+    if args.model_type not in ('sage', 'gat', 'graphsage'):
+        raise NotImplementedError(f'{args.model_type} is not a supported model type')
+    if getattr(args, 'eval_path', 'layers') == 'rows' and args.model_type != 'graphsage':
+        raise SystemExit('gist_amd: --eval-path rows is the GraphSAGE family\'s evaluator (--model-type graphsage); the SAGE '
+                         'engine path already evaluates with trainer.FullGraphEvaluator, the GAT has --eval-path blocked')
+    data, g, device, in_feats, n_classes, par_li, psize = load_graph(args, dataset, log)
     # construction order as in the reference: ClusterIter (one shuffle) before the model
     model_holder = {}
 
@@ -149,6 +157,23 @@ def main(args, dataset=None, log=print):
     log(f'Best Test: {max(test_accs):.4f}', flush=True)
     return dict(total_time=trainer.total_time, val_accs=val_accs, test_accs=test_accs,
                 model=model_holder['m'])
+
+
+def main_baseline(args, dataset, log):
+    """--model-type baseline: modules.BaselineGCN (cluster_gcn/modules.py:316-349, the plain GCN of GraphConv layers) in
+    the reference's loop body.  The family has no fused step, no precomputation and no evaluator of its own: the model's
+    own full-graph forward evaluates, its tail in place."""
+    if args.use_pp:
+        raise SystemExit('gist_amd: --use-pp is the GraphSAGE layer\'s precomputation (--model-type graphsage); '
+                         '--model-type baseline aggregates in every layer')
+    if getattr(args, 'eval_path', 'layers') != 'layers':
+        raise SystemExit('gist_amd: --eval-path %s is another family\'s evaluator; --model-type baseline evaluates with '
+                         'its own full-graph forward (--eval-path layers)' % args.eval_path)
+    host_path = getattr(args, 'host_path', 'engine')
+    if host_path != 'module':
+        log('--model-type baseline has no fused step: --host-path %s runs the module loop, layer by layer' % host_path)
+    data, g, device, in_feats, n_classes, par_li, psize = load_graph(args, dataset, log)
+    return main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log)
 
 
 def main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log):
@@ -241,10 +266,10 @@ def main_graphsage_engine(args, data, g, device, in_feats, n_classes, par_li, ps
 
 
 def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log):
-    """cluster_gcn/cluster_gcn.py:24-136 on the drop-in classes: ClusterIter, GCN (or GAT, or GraphSAGE),
+    """cluster_gcn/cluster_gcn.py:24-136 on the drop-in classes: ClusterIter, GCN (or GAT, GraphSAGE, BaselineGCN),
     CrossEntropyLoss, Adam, evaluate."""
     import time
-    from gist_amd.modules import GAT, GCN, GraphSAGE
+    from gist_amd.modules import GAT, GCN, BaselineGCN, GraphSAGE
     from gist_amd.nn import CrossEntropyLoss
     from gist_amd.optim import Adam
     from gist_amd.sampler import ClusterIter
@@ -261,6 +286,10 @@ def main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, 
     elif args.model_type == 'graphsage':
         model = GraphSAGE(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout, args.use_pp)
         model.cuda()
+    elif args.model_type == 'baseline':
+        model = BaselineGCN(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout, args.use_layernorm)
+        model.cuda()
+        model.set_dropout_seed(args.rnd_seed)
     else:
         model = GCN(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout,
                     args.use_layernorm, False, False, 1, True)                                         # :66-69

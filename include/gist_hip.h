@@ -504,6 +504,48 @@ int gist_ln_affine_bwd_f32(const float *d_out, int64_t ldg, const float *yhat, i
                            float *dbeta, float *dlin_bias, int64_t n_rows, int64_t d, float *workspace,
                            int64_t workspace_floats, gist_stream_t stream);
 
+/* The tail of a BaselineGCN layer (cluster_gcn/modules.py:316-349) on a dense row-major x[n_rows, d] (ld == d), b = the
+ * GraphConv bias [d]:
+ *   a = relu ? max(x + b, 0) : x + b                      :346, GraphConv's bias and activation
+ *   yhat = norm ? (a - mean) * rstd : a                   :347-348, F.layer_norm(h, h.shape): ONE mean and biased
+ *                                                         variance over all n_rows * d values of a; stats = {mean, rstd}
+ *   out = yhat * factor                                   :345, the NEXT layer's self.dropout: gist_dropout_f32's factor
+ *                                                         at element index offset + r * d + c
+ * x is read only (the backward recomputes the gate from it).  p = 0: out may be NULL (yhat alone is stored) or yhat itself;
+ * p > 0: out is a buffer of its own, and yhat may be NULL (a caller without norm has no use for it).  The statistics are gist_ln_all_fwd_f32's -- its geometry (a function of n_rows * d
+ * and x's alignment), its slice partials, its fixed-order fp64 merge; no float atomics -- so on tensors of one alignment
+ * class yhat and stats equal gist_ln_all_fwd_f32 of a stored relu(x + b) bit for bit, and out equals gist_dropout_f32 of
+ * that yhat.  d % 4 != 0 (16-byte units straddle rows) works like any other width: the bias column is (flat index) % d.
+ * Launches: two with norm, one without.  `ws`: gist_ln_all_partials(n_rows * d) floats of scratch, 8-byte aligned (norm
+ * = 0: unused, may be NULL); what it held before does not matter and nothing outside it is written.  n_rows * d = 0: OK,
+ * nothing is touched.  Negative sizes, p outside [0, 1), NULL pointers, x == yhat or x == out: GIST_EINVAL before any
+ * device work. */
+int gist_gcn_tail_fwd_f32(const float *x, const float *b, float *yhat, float *out, float *stats, int64_t n_rows, int64_t d,
+                          int relu, int norm, float eps, float p, uint64_t seed, uint64_t offset, float *ws,
+                          gist_stream_t stream);
+/* The same tail in a full-graph evaluation (cluster_gcn/modules.py:346-348 under model.eval() and torch.no_grad(); :345 is
+ * the identity there): out = the training forward's yhat bit for bit, and nothing else -- no dropout, stats optional (NULL:
+ * not stored).  out may be x: every thread rewrites only elements it has read itself, after the statistics launch has
+ * finished, so a [N, H] activation needs no second buffer.  `ws` as above. */
+int gist_gcn_tail_infer_f32(const float *x, const float *b, float *out, float *stats, int64_t n_rows, int64_t d, int relu,
+                            int norm, float eps, float *ws, gist_stream_t stream);
+/* Its backward (autograd of cluster_gcn/modules.py:345-348) from the forward's x, b, yhat and stats:
+ *   g = d_out * factor                                    :345, the forward's indices
+ *   da = norm ? rstd * (g - mean(g) - yhat * mean(g * yhat)) : g      :347-348, both means over the whole tensor:
+ *                                                         gist_ln_all_bwd_f32's slice sums in double, merged in fixed order
+ *   dx = (!relu || x + b > 0) ? da : 0                    :346, the forward's own add: the gate agrees with the forward
+ *                                                         bit for bit; no gradient at exactly 0
+ *   dbias[c] = sum_r dx[r, c]                             :346, column sums per 16-row chunk into `ws`, finished in
+ *                                                         gist_colsum_chunks_f32's order
+ * No float atomics: the same inputs give the same bits.  Launches: three with norm (slice sums; dx and chunk sums; finish),
+ * two without (yhat and stats unused, may be NULL).  `ws`: gist_gcn_tail_bwd_workspace_floats(n_rows, d) floats of scratch
+ * (a host function), 8-byte aligned; what it held before does not matter and nothing outside its ws_floats is written.
+ * dx overlaps no input.  n_rows * d = 0: OK, nothing is touched (the sums of no rows are the caller's zeros). */
+int64_t gist_gcn_tail_bwd_workspace_floats(int64_t n_rows, int64_t d);
+int gist_gcn_tail_bwd_f32(const float *d_out, const float *x, const float *b, const float *yhat, const float *stats,
+                          float *dx, float *dbias, int64_t n_rows, int64_t d, int relu, int norm, float p, uint64_t seed,
+                          uint64_t offset, float *ws, int64_t ws_floats, gist_stream_t stream);
+
 /* In place inverted dropout on z[n_rows, d]: keep with prob 1-p, scale by
  * 1/(1-p).  The mask is a pure function of (seed, offset + row*d + col) so
  * the backward regenerates it by calling the same function on the gradient.
