@@ -180,6 +180,10 @@ SIGNATURES = {
     'gist_gcn_tail_infer_f32': (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _f, _p, _p]),
     'gist_gcn_tail_bwd_workspace_floats': (_i64, [_i64, _i64]),
     'gist_gcn_tail_bwd_f32': (_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _int, _int, _f, _u64, _u64, _p, _i64, _p]),
+    'gist_gcn_degree_scales_f32': (_int, [_p, _p, _i64, _p, _p, _p]),
+    'gist_baseline_gcn_step_workspace_bytes': (_i64, [_p]),
+    'gist_baseline_gcn_step_tail_ws_floats': (_i64, [_p]),
+    'gist_baseline_gcn_step': (_int, [_p, _p, _i64, _u64, _f, _f, _f, _f, _f, _i64, _int, _p]),
 }
 
 GIST_MAX_LAYERS = 16
@@ -273,6 +277,30 @@ class GraphSAGEStepPlan(ctypes.Structure):
                 ('dZ', _p), ('dlogits', _p), ('row_loss', _p), ('loss', _p), ('loss_mask', _p),
                 ('loss_count', _i64), ('partials', _p),
                 ('ln_workspace', _p), ('ln_workspace_floats', _i64), ('workspace', _p), ('workspace_bytes', _i64),
+                ('params', _p), ('grads', _p), ('exp_avg', _p), ('exp_avg_sq', _p), ('n_params', _i64),
+                ('g_rowptr', _p), ('g_col', _p), ('g_t_rowptr', _p), ('g_t_col', _p),
+                ('feat', _p), ('ld_feat', _i64), ('labels_all', _p), ('remap', _p),
+                ('rowptr', _p), ('col', _p), ('t_rowptr', _p), ('t_col', _p),
+                ('col_capacity', _i64), ('norm', _p), ('labels', _p),
+                ('row_blocks', _p), ('n_row_blocks', _i64),
+                ('node_part', _p), ('part_slot', _p), ('batch_index', _i32), ('extract_scratch', _p),
+                ('next_ids', _p), ('next_n', _i64), ('next_batch_index', _i32),
+                ('n_max', _i64), ('timer', _p)]
+
+
+class BaselineGCNLayerDesc(ctypes.Structure):
+    """struct gist_baseline_gcn_layer_desc (include/gist_hip.h)."""
+    _fields_ = [('n_in', _i64), ('n_out', _i64), ('W', _p), ('b', _p), ('dW', _p), ('db', _p), ('X', _p), ('T', _p),
+                ('Y', _p), ('yhat', _p), ('stats', _p)]
+
+
+class BaselineGCNStepPlan(ctypes.Structure):
+    """struct gist_baseline_gcn_step_plan (include/gist_hip.h)."""
+    _fields_ = [('n_layers', _i32), ('use_layernorm', _i32), ('p_drop', _f), ('seed', _u64),
+                ('layer', BaselineGCNLayerDesc * GIST_MAX_LAYERS),
+                ('nd', _p), ('ns', _p), ('logits', _p), ('tail_ws', _p), ('tail_ws_floats', _i64), ('bwd', _p * 2),
+                ('dlogits', _p), ('row_loss', _p), ('loss', _p), ('loss_mask', _p), ('loss_count', _i64),
+                ('partials', _p), ('workspace', _p), ('workspace_bytes', _i64),
                 ('params', _p), ('grads', _p), ('exp_avg', _p), ('exp_avg_sq', _p), ('n_params', _i64),
                 ('g_rowptr', _p), ('g_col', _p), ('g_t_rowptr', _p), ('g_t_col', _p),
                 ('feat', _p), ('ld_feat', _i64), ('labels_all', _p), ('remap', _p),

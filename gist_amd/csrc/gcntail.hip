@@ -13,6 +13,8 @@
 //             64 * VEC columns, dx = gate ? da : 0 and the chunk's column sums of dx; then colsum_finish adds the chunks in
 //             gist_colsum_chunks_f32's order.  no norm: the last two launches alone.
 //
+//   scales    GraphConv's two degree vectors 1 / sqrt(max(degree, 1)) from rowptr and t_rowptr, one launch (at the end).
+//
 // Columns.  A 16-byte unit of the flat walk lies inside a row only when d % 4 == 0 and the tensor starts on a 16-byte
 // boundary; otherwise it straddles rows.  The bias column of flat element i is i % d either way: a thread computes the
 // column of its first unit with one 64-bit remainder and steps it by (256 * VEC) % d from unit to unit.
@@ -265,10 +267,47 @@ int tail_fwd_launch(const char *name, const float *x, const float *b, float *yha
     return launch_status(name);
 }
 
+// ---------------------------------------------------------------------------
+// the degree scales of GraphConv.forward (dgl_compat/nn/pytorch.py:27-30), both vectors in one launch
+// ---------------------------------------------------------------------------
+// 1 / sqrt(max(deg, 1)).  The build has no fast-math flag, so hipcc's default for HIP holds (correctly rounded fp32
+// divide and square root: the v_sqrt_f32 / v_rcp_f32 results with their fix-up sequences, never v_rsq_f32); the
+// __fsqrt_rn / __fdiv_rn spellings would NOT be stronger -- without OCML_BASIC_ROUNDED_OPERATIONS the first is the
+// native square root.  The pragma keeps the two operations apart whatever flags a later build adds.
+__device__ __forceinline__ float degree_scale(const int32_t *__restrict__ rowptr, int64_t v) {
+#pragma clang fp reassociate(off) contract(off) reciprocal(off)
+    const int deg = rowptr[v + 1] - rowptr[v];
+    const float f = (float)(deg > 1 ? deg : 1);
+    return 1.0f / __builtin_sqrtf(f);
+}
+
+__global__ __launch_bounds__(256) void gcn_degree_scales_kernel(const int32_t *__restrict__ rowptr,
+                                                                const int32_t *__restrict__ t_rowptr, int64_t n_rows,
+                                                                float *__restrict__ nd, float *__restrict__ ns) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n_rows) return;
+    nd[v] = degree_scale(rowptr, v);
+    ns[v] = degree_scale(t_rowptr, v);
+}
+
 }  // namespace
 }  // namespace gist
 
 using namespace gist;
+
+extern "C" int gist_gcn_degree_scales_f32(const int32_t *rowptr, const int32_t *t_rowptr, int64_t n_rows, float *nd,
+                                          float *ns, gist_stream_t stream) {
+    const char *name = "gist_gcn_degree_scales_f32";
+    GIST_REQUIRE(n_rows >= 0 && n_rows < (1LL << 31), "%s: n_rows must be in 0 .. 2^31 - 1", name);
+    if (n_rows == 0) return GIST_OK;
+    GIST_REQUIRE(rowptr && t_rowptr && nd && ns, "%s: null pointer", name);
+    GIST_REQUIRE(((reinterpret_cast<uintptr_t>(rowptr) | reinterpret_cast<uintptr_t>(t_rowptr) |
+                   reinterpret_cast<uintptr_t>(nd) | reinterpret_cast<uintptr_t>(ns)) & 3u) == 0,
+                 "%s: misaligned buffer", name);
+    hipLaunchKernelGGL(gcn_degree_scales_kernel, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, as_stream(stream),
+                       rowptr, t_rowptr, n_rows, nd, ns);
+    return launch_status(name);
+}
 
 extern "C" int gist_gcn_tail_fwd_f32(const float *x, const float *b, float *yhat, float *out, float *stats, int64_t n_rows,
                                      int64_t d, int relu, int norm, float eps, float p, uint64_t seed, uint64_t offset,

@@ -648,6 +648,23 @@ def gcn_tail_bwd(d_out, x, b, yhat, stats, dx, dbias, relu, norm, p=0.0, seed=0,
     return dx
 
 
+def gcn_degree_scales(rowptr, t_rowptr, nd=None, ns=None):
+    """(nd, ns) = 1 / sqrt(max(degree, 1)) from rowptr and from t_rowptr (int32 [n + 1] each), both in one launch
+    (gist_gcn_degree_scales_f32): GraphConv's in- and out-degree scales, bitwise numpy's float32 values."""
+    L = _lib.load()
+    n = rowptr.numel() - 1
+    if t_rowptr.numel() != n + 1:
+        raise ValueError('gist_amd: gcn_degree_scales wants two rowptr arrays of one length')
+    if nd is None:
+        nd = torch.empty(n, dtype=torch.float32, device=rowptr.device)
+    if ns is None:
+        ns = torch.empty(n, dtype=torch.float32, device=rowptr.device)
+    _lib.check(L.gist_gcn_degree_scales_f32(_vec(rowptr, 'rowptr', torch.int32), _vec(t_rowptr, 't_rowptr', torch.int32),
+                                            n, _vec(nd, 'nd', torch.float32, n), _vec(ns, 'ns', torch.float32, n),
+                                            _stream()), 'gist_gcn_degree_scales_f32')
+    return nd, ns
+
+
 def dropout_(z, p, seed, offset):
     L = _lib.load()
     zp, ldz = _mat(z, 'z')

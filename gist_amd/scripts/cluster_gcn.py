@@ -48,7 +48,8 @@ def build_parser():
     # nn.CrossEntropyLoss / optim.Adam / sampler.ClusterIter (gist_amd/module_engine.py); engine: one gist_sage_step (sage) or
     # gist_gat_step (gat) per iteration; phases (gat): the module loop with the model bound to its iterator
     # (module_engine.bind_gat) -- the engine's launches as three gist_gat_step_phase calls per iteration; step (graphsage):
-    # one gist_graphsage_step per iteration (gist_amd/graphsage_engine.py); engine and module keep that family's module loop
+    # one gist_graphsage_step per iteration (gist_amd/graphsage_engine.py); step (baseline): one gist_baseline_gcn_step per
+    # iteration (gist_amd/baseline_gcn_engine.py); engine and module keep those families' module loop
     parser.add_argument("--host-path", choices=['engine', 'module', 'phases', 'step'], default='engine')
     # (not a flag of the reference; --model-type gat and graphsage) how evaluate() runs the full-graph forward: layers = the model's own
     # forward, layer by layer on the training kernels; blocked = gist_amd.gat_eval.GATFullGraphEvaluator (preallocated
@@ -124,8 +125,8 @@ def main(args, dataset=None, log=print):
         raise SystemExit('gist_amd: --host-path phases binds a GAT to its iterator (--model-type gat); the SAGE module '
                          'path already runs on the phase calls of the fused step: use --host-path module')
     if host_path == 'step' and args.model_type != 'graphsage':
-        raise SystemExit('gist_amd: --host-path step is the GraphSAGE family\'s one-call step (--model-type graphsage); '
-                         'the other families run theirs under --host-path engine')
+        raise SystemExit('gist_amd: --host-path step is the one-call step of the GraphSAGE and BaselineGCN families '
+                         '(--model-type graphsage, baseline); the other families run theirs under --host-path engine')
     if args.model_type == 'graphsage' and host_path == 'step':
         return main_graphsage_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     if args.model_type == 'graphsage':
@@ -161,8 +162,8 @@ def main(args, dataset=None, log=print):
 
 def main_baseline(args, dataset, log):
     """--model-type baseline: modules.BaselineGCN (cluster_gcn/modules.py:316-349, the plain GCN of GraphConv layers) in
-    the reference's loop body.  The family has no fused step, no precomputation and no evaluator of its own: the model's
-    own full-graph forward evaluates, its tail in place."""
+    the reference's loop body; its fused step is opt-in (--host-path step, main_baseline_engine).  The family has no
+    precomputation and no evaluator of its own: the model's own full-graph forward evaluates, its tail in place."""
     if args.use_pp:
         raise SystemExit('gist_amd: --use-pp is the GraphSAGE layer\'s precomputation (--model-type graphsage); '
                          '--model-type baseline aggregates in every layer')
@@ -170,10 +171,58 @@ def main_baseline(args, dataset, log):
         raise SystemExit('gist_amd: --eval-path %s is another family\'s evaluator; --model-type baseline evaluates with '
                          'its own full-graph forward (--eval-path layers)' % args.eval_path)
     host_path = getattr(args, 'host_path', 'engine')
+    if host_path == 'step':
+        data, g, device, in_feats, n_classes, par_li, psize = load_graph(args, dataset, log)
+        return main_baseline_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log)
     if host_path != 'module':
-        log('--model-type baseline has no fused step: --host-path %s runs the module loop, layer by layer' % host_path)
+        log('--model-type baseline has no fused step under --host-path %s (its step is --host-path step): the module loop '
+            'runs, layer by layer' % host_path)
     data, g, device, in_feats, n_classes, par_li, psize = load_graph(args, dataset, log)
     return main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log)
+
+
+def main_baseline_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log):
+    """--model-type baseline --host-path step: one gist_baseline_gcn_step per iteration (gist_amd/baseline_gcn_engine.py),
+    fed by EngineClusterIter.  Same construction order, RNG draws for the weights and batch order as main_module_path;
+    the dropout masks come from autograd.gcn_tail's generator, seed and counter scheme, counted by the engine from 0
+    instead of by the process-wide counter."""
+    import time
+    from gist_amd.arena import baseline_gcn_dims
+    from gist_amd.baseline_gcn_engine import BaselineGCNEngine
+    from gist_amd.modules import BaselineGCN
+    from gist_amd.sampler import EngineClusterIter
+    from gist_amd.utils import evaluate
+    train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
+    it = EngineClusterIter(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li, device=device)
+    g = g.to(device)
+    labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
+    model = BaselineGCN(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout, args.use_layernorm)
+    model.cuda()
+    model.set_dropout_seed(args.rnd_seed)
+    engine = BaselineGCNEngine(baseline_gcn_dims(in_feats, args.n_hidden, n_classes, args.n_layers), args.use_layernorm,
+                               args.dropout, it.n_max, device, seed=args.rnd_seed)
+    engine.bind(model)                                     # the model's parameters are the arena's views from here on
+    it.bind(engine)
+    engine.prefetch = True                                 # (the loop only reads the loss of a step)
+    total_time, val_accs, test_accs = 0., [], []
+    for epoch in range(args.n_epochs):                     # cluster_gcn.py:89-127
+        log(f'Running epoch {epoch} / {args.n_epochs}', flush=True)
+        torch.cuda.synchronize(device)
+        start_time = time.time()
+        for batch in it:
+            engine.train_step(batch, args.lr, args.weight_decay)
+        torch.cuda.synchronize(device)
+        total_time += time.time() - start_time
+        engine.check_extract()                             # (outside the timed interval)
+        val_accs.append(evaluate(model, g, labels, val_mask, 'f1' if args.use_f1 else 'acc'))
+        test_accs.append(evaluate(model, g, labels, test_mask, 'f1' if args.use_f1 else 'acc'))
+        log(f'Val acc {val_accs[-1]}', flush=True)
+    log(f'Training Time: {total_time:.4f}', flush=True)    # :132-136
+    log(f'Last Val: {val_accs[-1]:.4f}', flush=True)
+    log(f'Best Val: {max(val_accs):.4f}', flush=True)
+    log(f'Last Test: {test_accs[-1]:.4f}', flush=True)
+    log(f'Best Test: {max(test_accs):.4f}', flush=True)
+    return dict(total_time=total_time, val_accs=val_accs, test_accs=test_accs, model=model, engine=engine)
 
 
 def main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log):

@@ -546,6 +546,17 @@ int gist_gcn_tail_bwd_f32(const float *d_out, const float *x, const float *b, co
                           float *dx, float *dbias, int64_t n_rows, int64_t d, int relu, int norm, float p, uint64_t seed,
                           uint64_t offset, float *ws, int64_t ws_floats, gist_stream_t stream);
 
+/* The two degree scales of a GraphConv layer (dgl_compat.nn.pytorch.GraphConv.forward :27-30) of a batch graph, both in
+ * ONE launch:
+ *   nd[v] = 1 / sqrt((float)max(rowptr[v + 1] - rowptr[v], 1))          the in-degree scale (the aggregation's out_scale)
+ *   ns[v] = 1 / sqrt((float)max(t_rowptr[v + 1] - t_rowptr[v], 1))      the out-degree scale (its src_scale)
+ * with a correctly rounded fp32 square root and a correctly rounded fp32 divide: bit for bit numpy's
+ * np.float32(1) / np.sqrt(deg.astype(np.float32)).  It reads the two rowptr arrays [n_rows + 1] only (never a column
+ * array) and writes n_rows floats to each of nd and ns, nothing else.  n_rows = 0: OK, no launch, nothing touched.  A NULL
+ * pointer, a negative n_rows or n_rows >= 2^31: GIST_EINVAL before any device work. */
+int gist_gcn_degree_scales_f32(const int32_t *rowptr, const int32_t *t_rowptr, int64_t n_rows, float *nd, float *ns,
+                               gist_stream_t stream);
+
 /* In place inverted dropout on z[n_rows, d]: keep with prob 1-p, scale by
  * 1/(1-p).  The mask is a pure function of (seed, offset + row*d + col) so
  * the backward regenerates it by calling the same function on the gradient.
@@ -1437,6 +1448,100 @@ int gist_graphsage_step(const gist_graphsage_step_plan *plan, const int32_t *ids
 int gist_graphsage_step_phase(const gist_graphsage_step_plan *plan, const int32_t *ids, int64_t n,
                               uint64_t drop_offset, float lr, float beta1, float beta2, float eps, float weight_decay,
                               int64_t adam_step, int flags, gist_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Whole BaselineGCN training iteration in one call (an addition: no existing signature changed, ABI 16)
+ * ------------------------------------------------------------------------- */
+
+/* One GraphConv layer's buffers (cluster_gcn/modules.py:316-349; all device pointers, all preallocated by the caller for
+ * n_max rows, every matrix dense: its leading dimension is its width).  W, b are views of the flat parameter arena
+ * (gist_amd.arena.BaselineGCNArena: GraphConv's own [n_in, n_out] weight, read as stored), dW, db the same views of the
+ * gradient arena.  GraphConv multiplies first iff n_in > n_out, else it aggregates first. */
+typedef struct gist_baseline_gcn_layer_desc {
+    int64_t n_in, n_out;
+    float *W, *b;              /* [n_in, n_out], [n_out]                                         */
+    float *dW, *db;
+    float *X;                  /* [n_max, n_in]: the layer's input: layer 0: the extracted features (written by the
+                                  extraction alone, never by a step); layer k > 0: the tail's `out` of layer k - 1 */
+    float *T;                  /* [n_max, min(n_in, n_out)]: A^ X (aggregate first) or X W (multiply first) */
+    float *Y;                  /* [n_max, n_out]: T W or A^ T: the tail's read-only x            */
+    float *yhat;               /* [n_max, n_out]: hidden layers with use_layernorm of a plan with p_drop > 0: the tail's
+                                  yhat, kept for its backward.  Unused (may be NULL) otherwise: without the norm no yhat is
+                                  stored at all, and at p = 0 yhat IS the tail's result, stored once, in layer k + 1's X */
+    float *stats;              /* [2]: hidden layers with use_layernorm: the tail's (mean, rstd)  */
+} gist_baseline_gcn_layer_desc;
+
+typedef struct gist_baseline_gcn_step_plan {
+    int32_t n_layers;              /* ALL layers of gist_amd.modules.BaselineGCN, the output layer included; layer k + 1's
+                                      n_in must be layer k's n_out                                  */
+    int32_t use_layernorm;         /* modules.py:347-348: F.layer_norm(h, h.shape) after every hidden layer */
+    float p_drop; uint64_t seed;   /* self.dropout on the input of layers >= 1, applied by the tail of the layer before
+                                      under gist_dropout_f32's generator: element (r, c) of hidden layer k's result has
+                                      index drop_offset + sum_{j<k} round_up2(n * n_out_j) + r * n_out_k + c */
+    gist_baseline_gcn_layer_desc layer[GIST_MAX_LAYERS];
+    float *nd, *ns;                /* [n_max] each: gist_gcn_degree_scales_f32 of the batch, written by every forward */
+    float *logits;                 /* [n_max, n_classes]: the output layer's Y + b                  */
+    float *tail_ws; int64_t tail_ws_floats;    /* gist_baseline_gcn_step_tail_ws_floats(plan); 8-byte aligned */
+    float *bwd[2];                 /* backward ping-pong, each n_max * max(1, max_k min(n_in_k, n_out_k), max_{k>=1} n_in_k)
+                                      floats: dT and dX of layer k alternate with the dY of layers k and k - 1
+                                      (gist_gcn_tail_bwd_f32's dx overlaps none of its inputs)      */
+    float *dlogits;                /* [n_max, n_classes]                                            */
+    float *row_loss, *loss;        /* [n_max], [1]                                                  */
+    const uint8_t *loss_mask; int64_t loss_count;   /* as in gist_graphsage_step_plan               */
+    float *partials;               /* [gist_colsum_partials(n_max) * n_classes]: the output layer's db */
+    void *workspace; int64_t workspace_bytes;            /* split-K scratch: gist_baseline_gcn_step_workspace_bytes(plan) */
+    float *params, *grads, *exp_avg, *exp_avg_sq; int64_t n_params;   /* flat arenas */
+    /* resident training graph + the batch buffers the extraction fills (as in gist_graphsage_step_plan; the extraction
+     * writes `norm`, which this family does not read) */
+    const int32_t *g_rowptr, *g_col, *g_t_rowptr, *g_t_col;
+    const float *feat; int64_t ld_feat;
+    const int32_t *labels_all;
+    int32_t *remap;
+    int32_t *rowptr, *col, *t_rowptr, *t_col; int64_t col_capacity;
+    float *norm; int32_t *labels;
+    const int32_t *row_blocks; int64_t n_row_blocks;    /* set per call; NULL: gist_spmm_csr_f32 */
+    const int32_t *node_part, *part_slot;
+    int32_t batch_index;
+    void *extract_scratch;
+    const int32_t *next_ids;
+    int64_t next_n;
+    int32_t next_batch_index;
+    int64_t n_max;
+    struct gist_timer *timer;      /* NULL = no timing; records the GEMM (kind 1) and aggregation (kind 0) calls */
+} gist_baseline_gcn_step_plan;
+
+/* Sizes the caller cannot derive from the shapes alone (host functions; 0 for a NULL plan or bad shapes): the bytes of
+ * `workspace` -- the largest gist_gemm_workspace_bytes over the three products of every layer, (m, n, k) = (rows, n_out,
+ * n_in), (n_in, n_out, rows), (rows, n_in, n_out) in either GraphConv order (layer 0 has no third), at every batch size up
+ * to n_max -- and the floats of `tail_ws`: the largest of gist_ln_all_partials(n_max * n_out) and
+ * gist_gcn_tail_bwd_workspace_floats(n_max, n_out) over the hidden layers (0 for a model that is its output layer alone). */
+int64_t gist_baseline_gcn_step_workspace_bytes(const gist_baseline_gcn_step_plan *plan);
+int64_t gist_baseline_gcn_step_tail_ws_floats(const gist_baseline_gcn_step_plan *plan);
+
+/* One iteration of the reference's loop with --model-type baseline (cluster_gcn/cluster_gcn.py:96-105 on
+ * cluster_gcn/modules.py:341-349) on the batch whose node ids are ids[0..n).  With A^ = D_in^-1/2 A D_out^-1/2:
+ *   extraction (features into X_0), gist_gcn_degree_scales_f32 (in every forward, also on a pre-extracted batch);
+ *   per layer, aggregate first (n_in <= n_out): T = A^ X (gist_spmm_csr_f32 / _blocked_f32, out_scale = nd, src_scale =
+ *   ns), Y = T W (gist_gemm_nn_f32); multiply first: T = X W, Y = A^ T; then gist_gcn_tail_fwd_f32(Y, b): hidden layers
+ *   relu = 1, norm = use_layernorm, the NEXT layer's dropout, out = X_{k+1} (at p = 0 with the norm: yhat = X_{k+1}, one
+ *   store); the output layer relu = norm = 0, p = 0, out = logits;
+ *   gist_softmax_xent_f32 (mean over the batch rows, or over the rows of plan->loss_mask);
+ *   per layer in reverse: dY = dlogits and db by gist_colsum_f32 (output layer), or gist_gcn_tail_bwd_f32 from dX_{k+1}
+ *   into a ping-pong buffer with db straight into the gradient arena (hidden layer); aggregate first: dW = T^T dY
+ *   (gist_gemm_tn_f32) and for k > 0 dT = dY W^T (gist_gemm_nt_f32), dX = A^^T dT (the aggregation on t_rowptr / t_col,
+ *   out_scale = ns, src_scale = nd); multiply first: dT = A^^T dY (also for k = 0), dW = X^T dT and for k > 0 dX = dT W^T;
+ *   one gist_adam_f32 over the arena.
+ * The driver launches no kernel of its own, so an op-by-op caller that issues the same entry points gets the same bits.
+ * X_0 is never written by a step: any number of steps may follow one extraction.  `plan` is HOST memory; drop_offset is
+ * the step's base in the dropout counter space; adam_step is 1-based; no host synchronisation.
+ * flags: GIST_STEP_EXTRACT, GIST_STEP_TRAIN (without it: forward + loss only, p = 0, no parameter touched),
+ * GIST_STEP_EXTRACT_NEXT and GIST_STEP_PREEXTRACTED, with their gist_graphsage_step meaning.  The GIST_STEP_PHASE_* bits
+ * and GIST_STEP_DLOGITS_GIVEN: GIST_EINVAL (this family has no phase calls).  Every argument is checked (null pointers,
+ * sizes, n > n_max, more than GIST_MAX_LAYERS layers, mismatched widths, p_drop outside [0, 1): GIST_EINVAL; a workspace
+ * or tail_ws too small for this n: GIST_ENOSPACE) before any device work. */
+int gist_baseline_gcn_step(const gist_baseline_gcn_step_plan *plan, const int32_t *ids, int64_t n, uint64_t drop_offset,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, int64_t adam_step,
+                           int flags, gist_stream_t stream);
 
 #ifdef __cplusplus
 }
