@@ -1,6 +1,9 @@
 /* A plain-C consumer of the boundary that does DEVICE work (tests/test_cabi_device_gpu.py builds and runs it on the
  * GPU box): no Python, no torch in the process -- hipMalloc'ed buffers, the library's entry points on the NULL stream,
- * results against C loops.  A 300-node random multigraph (duplicate edges, self loops, one node without in-edges):
+ * results against C loops; then the same calls once more on a stream of the program's own (hipStreamNonBlocking),
+ * back to back into second output buffers, synchronised once: the same bytes, and the same C-loop checks
+ * (equal bytes; the pass has no delay, so it does not show ordering: tests/test_stream_order_gpu.py does).
+ * A 300-node random multigraph (duplicate edges, self loops, one node without in-edges):
  *   gist_in_degree_norm_f32          vs 1 / in_degree, 0 for degree 0            (cluster_gcn/modules.py:239-243)
  *   gist_spmm_csr_f32, forward form  y = norm . sum over in-edges of x          (modules.py:223-226)
  *   gist_spmm_csr_f32, reversed + accumulate form: dX += A^T (norm . dAH)       (autograd of the same op)
@@ -46,6 +49,9 @@ int main(void) {
     static float x[N * D], norm_ref[N], y_ref[N * D], dx_ref[N * D], dah[N * D], dx0[N * D];
     static float a[N * 2 * D], w[M_OUT * 2 * D], bias[M_OUT], yg_ref[N * M_OUT];
     static float got[N * 2 * D];
+    static float keep_norm[N], keep_y[N * D], keep_dx[N * D], keep_yg[N * M_OUT];      /* the NULL-stream pass's bytes */
+    float *d_norm2, *d_y2, *d_dx2, *d_yg2;
+    hipStream_t side;
     int32_t *d_rowptr, *d_col, *d_t_rowptr, *d_t_col;
     float *d_x, *d_y, *d_norm, *d_dah, *d_dx, *d_a, *d_w, *d_bias, *d_yg;
     void *d_ws = NULL;
@@ -120,6 +126,7 @@ int main(void) {
     HIP_OK(hipMemcpy(got, d_norm, sizeof norm_ref, hipMemcpyDeviceToHost));
     for (i = 0; i < N; ++i) if (got[i] != norm_ref[i]) { printf("norm[%d] %g != %g\n", i, got[i], norm_ref[i]); return 10; }
     if (norm_ref[N - 1] != 0.0f) return 11;
+    memcpy(keep_norm, got, sizeof keep_norm);
 
     /* 2. forward aggregation, fused 1/deg */
     GIST_OK_(gist_spmm_csr_f32(d_rowptr, d_col, d_x, D, d_y, D, N, D, d_norm, NULL, 0, NULL));
@@ -128,6 +135,7 @@ int main(void) {
     worst = 0.0;
     for (i = 0; i < N * D; ++i) { double d_ = fabs((double)got[i] - y_ref[i]); if (d_ > worst) worst = d_; }
     if (worst > 1e-5) { printf("spmm forward: max error %g\n", worst); return 12; }
+    memcpy(keep_y, got, sizeof keep_y);
 
     /* 3. reversed graph, source scale, accumulate */
     GIST_OK_(gist_spmm_csr_f32(d_t_rowptr, d_t_col, d_dah, D, d_dx, D, N, D, NULL, d_norm, 1, NULL));
@@ -136,6 +144,7 @@ int main(void) {
     worst = 0.0;
     for (i = 0; i < N * D; ++i) { double d_ = fabs((double)got[i] - dx_ref[i]); if (d_ > worst) worst = d_; }
     if (worst > 1e-5) { printf("spmm reversed + accumulate: max error %g\n", worst); return 13; }
+    memcpy(keep_dx, got, sizeof keep_dx);
 
     /* 4. projection */
     GIST_OK_(gist_gemm_nt_f32(d_a, 2 * D, d_w, 2 * D, d_bias, d_yg, M_OUT, N, M_OUT, 2 * D, d_ws, ws_bytes, NULL));
@@ -144,9 +153,46 @@ int main(void) {
     worst = 0.0;
     for (i = 0; i < N * M_OUT; ++i) { double d_ = fabs((double)got[i] - yg_ref[i]); if (d_ > worst) worst = d_; }
     if (worst > 1e-4) { printf("gemm_nt: max error %g\n", worst); return 14; }
+    memcpy(keep_yg, got, sizeof keep_yg);
 
     /* 5. error behaviour on device arguments: a leading dimension below the width is refused, nothing launched */
     if (gist_spmm_csr_f32(d_rowptr, d_col, d_x, D - 1, d_y, D, N, D, NULL, NULL, 0, NULL) != GIST_EINVAL) return 15;
+
+    /* 6. the same four calls on a non-blocking stream of the program's own, nothing between them but the stream's order
+     * (the aggregations read the norm the first call writes), into second buffers; one synchronise; the NULL-stream
+     * pass's bytes, and the C-loop checks again */
+    HIP_OK(hipMalloc((void **)&d_norm2, sizeof norm_ref)); HIP_OK(hipMalloc((void **)&d_y2, sizeof x));
+    HIP_OK(hipMalloc((void **)&d_dx2, sizeof dx0)); HIP_OK(hipMalloc((void **)&d_yg2, sizeof yg_ref));
+    HIP_OK(hipMemset(d_norm2, 0xFF, sizeof norm_ref)); HIP_OK(hipMemset(d_y2, 0xFF, sizeof x));
+    HIP_OK(hipMemset(d_yg2, 0xFF, sizeof yg_ref));
+    HIP_OK(hipMemcpy(d_dx2, dx0, sizeof dx0, hipMemcpyHostToDevice));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+    GIST_OK_(gist_in_degree_norm_f32(d_rowptr, N, d_norm2, side));
+    GIST_OK_(gist_spmm_csr_f32(d_rowptr, d_col, d_x, D, d_y2, D, N, D, d_norm2, NULL, 0, side));
+    GIST_OK_(gist_spmm_csr_f32(d_t_rowptr, d_t_col, d_dah, D, d_dx2, D, N, D, NULL, d_norm2, 1, side));
+    GIST_OK_(gist_gemm_nt_f32(d_a, 2 * D, d_w, 2 * D, d_bias, d_yg2, M_OUT, N, M_OUT, 2 * D, d_ws, ws_bytes, side));
+    HIP_OK(hipStreamSynchronize(side));
+    HIP_OK(hipMemcpy(got, d_norm2, sizeof norm_ref, hipMemcpyDeviceToHost));
+    if (memcmp(got, keep_norm, sizeof keep_norm)) { printf("norm on the side stream differs from the NULL stream's\n"); return 20; }
+    for (i = 0; i < N; ++i) if (got[i] != norm_ref[i]) { printf("side stream: norm[%d] %g != %g\n", i, got[i], norm_ref[i]); return 21; }
+    HIP_OK(hipMemcpy(got, d_y2, sizeof x, hipMemcpyDeviceToHost));
+    if (memcmp(got, keep_y, sizeof keep_y)) { printf("spmm forward on the side stream differs from the NULL stream's\n"); return 22; }
+    worst = 0.0;
+    for (i = 0; i < N * D; ++i) { double d_ = fabs((double)got[i] - y_ref[i]); if (d_ > worst) worst = d_; }
+    if (worst > 1e-5) { printf("side stream: spmm forward: max error %g\n", worst); return 23; }
+    HIP_OK(hipMemcpy(got, d_dx2, sizeof dx0, hipMemcpyDeviceToHost));
+    if (memcmp(got, keep_dx, sizeof keep_dx)) { printf("spmm reversed on the side stream differs from the NULL stream's\n"); return 24; }
+    worst = 0.0;
+    for (i = 0; i < N * D; ++i) { double d_ = fabs((double)got[i] - dx_ref[i]); if (d_ > worst) worst = d_; }
+    if (worst > 1e-5) { printf("side stream: spmm reversed + accumulate: max error %g\n", worst); return 25; }
+    HIP_OK(hipMemcpy(got, d_yg2, sizeof yg_ref, hipMemcpyDeviceToHost));
+    if (memcmp(got, keep_yg, sizeof keep_yg)) { printf("gemm_nt on the side stream differs from the NULL stream's\n"); return 26; }
+    worst = 0.0;
+    for (i = 0; i < N * M_OUT; ++i) { double d_ = fabs((double)got[i] - yg_ref[i]); if (d_ > worst) worst = d_; }
+    if (worst > 1e-4) { printf("side stream: gemm_nt: max error %g\n", worst); return 27; }
+    HIP_OK(hipStreamDestroy(side));
+    hipFree(d_norm2); hipFree(d_y2); hipFree(d_dx2); hipFree(d_yg2);
 
     hipFree(d_rowptr); hipFree(d_col); hipFree(d_t_rowptr); hipFree(d_t_col); hipFree(d_x); hipFree(d_y);
     hipFree(d_norm); hipFree(d_dah); hipFree(d_dx); hipFree(d_a); hipFree(d_w); hipFree(d_bias); hipFree(d_yg);
