@@ -17,7 +17,8 @@ One engine = one model on one GPU.  Everything lives in HBM for the whole run an
 
 A step never writes X_0: any number of steps may follow one extraction, so this engine has no one-step-per-extraction
 check (GraphSAGEEngine's guards its in-place dropout on Z_0; here the dropout of layer k >= 1 is the tail's of layer k - 1
-and layer 0's input is not dropped, modules.py:343-345).
+and layer 0's input is not dropped, modules.py:343-345).  For the same reason several engines of one process may read
+ONE X_0: BaselineGCNEngine(..., x0=first.X[0]) (gist_amd.ist.train_baseline_gcn with S sites in one process).
 
 Dropout is gist_dropout_f32's counter-based generator under autograd.gcn_tail's counter scheme (`seed`, a running element
 offset `drop_calls`: every hidden layer's [n, out] result, rounded up to even), not torch's Philox stream.  DESIGN.md
@@ -32,10 +33,29 @@ from .arena import BaselineGCNArena
 from .engine import StepEngine
 
 
+def _describe(t):
+    """A refused x0 in words: its shape, dtype and device."""
+    if not isinstance(t, torch.Tensor):
+        return type(t).__name__
+    return '%s %s on %s%s' % (str(t.dtype).replace('torch.', ''), list(t.shape), t.device,
+                              '' if t.is_contiguous() else ', not contiguous')
+
+
 class BaselineGCNEngine(StepEngine):
-    def __init__(self, dims, use_layernorm, dropout, n_max, device, seed=0, arena=None):
-        """dims = [(in_k, out_k)] of ALL layers, the output layer included (gist_amd.arena.baseline_gcn_dims)."""
+    def __init__(self, dims, use_layernorm, dropout, n_max, device, seed=0, arena=None, x0=None):
+        """dims = [(in_k, out_k)] of ALL layers, the output layer included (gist_amd.arena.baseline_gcn_dims).
+
+        x0 = ANOTHER engine's X[0] to read layer 0's input rows from instead of a buffer of its own (GATEngine's x0):
+        several sub-models of one process (gist_amd.ist.train_baseline_gcn) bound to the same batcher step on the batch
+        the first of them extracted.  The step never writes X_0, so nothing of one site's step reaches another's."""
         self.dims = [(int(i), int(o)) for (i, o) in dims]
+        if x0 is not None:
+            # (checked before anything else is built: a tensor of the wrong kind never reaches a plan)
+            want = (int(n_max) if n_max is not None else 0, self.dims[0][0])
+            if (not isinstance(x0, torch.Tensor) or tuple(x0.shape) != want or x0.dtype != torch.float32
+                    or x0.device.type != torch.device(device).type or not x0.is_contiguous()):
+                raise ValueError('gist_amd: a shared x0 must be a contiguous fp32 [%d, %d] tensor on %s (got %s)'
+                                 % (want + (device, _describe(x0))))
         StepEngine.__init__(self, device, n_max, len(self.dims))
         if arena is not None and [tuple(d) for d in arena.dims] != self.dims:
             raise ValueError('gist_amd: the arena\'s dims %s are not the engine\'s %s' % (arena.dims, self.dims))
@@ -49,7 +69,7 @@ class BaselineGCNEngine(StepEngine):
         self.fuse = False
         n = self.n_max
         f32 = dict(dtype=torch.float32, device=device)
-        self.X = [torch.zeros(n, i, **f32) for (i, o) in self.dims]
+        self.X = [x0 if (k == 0 and x0 is not None) else torch.zeros(n, i, **f32) for k, (i, o) in enumerate(self.dims)]
         self.T = [torch.zeros(n, min(i, o), **f32) for (i, o) in self.dims]
         self.Y = [torch.zeros(n, o, **f32) for (i, o) in self.dims]
         own_yhat = self.use_layernorm and self.p_drop > 0.0

@@ -17,8 +17,10 @@ class GraphConv(nn.Module):
         if norm != 'both' or not weight or not bias:
             raise NotImplementedError('gist_amd: GraphConv supports norm="both" with weight and bias')
         self._in_feats, self._out_feats = in_feats, out_feats
-        self.weight = nn.Parameter(torch.Tensor(in_feats, out_feats))
-        self.bias = nn.Parameter(torch.Tensor(out_feats))
+        # (torch.empty, not torch.Tensor(...): the same uninitialised fp32 storage, but it follows a `with torch.device`
+        # scope -- under 'meta' nothing is allocated and the initialisation below draws nothing from the RNG)
+        self.weight = nn.Parameter(torch.empty(in_feats, out_feats))
+        self.bias = nn.Parameter(torch.empty(out_feats))
         nn.init.xavier_uniform_(self.weight)
         nn.init.zeros_(self.bias)
         self._activation = activation

@@ -15,8 +15,9 @@ _DistributedWrapper holds construction, dispatch and sync, written against a per
 vectors; DistributedGNNWrapper, DistributedGATWrapper and DistributedGraphSAGEWrapper (gist_amd.modules.GraphSAGE: the
 GCN split, the LayerNorm's gamma and beta following the bias; one grouped mover launch per dispatch and per sync) give
 it their dims, arena, model, binding and plan (_site_plan), and keep what is their own (the SAGE engine and evaluator;
-the GAT heads).  _run_schedule is the loop of all; train, train_gat and train_graphsage hand it one step and one
-evaluation.
+the GAT heads); DistributedBaselineGCNWrapper (gist_amd.modules.BaselineGCN: the GCN split transposed for GraphConv's
+[in, out] weight, on the grouped mover too) does the same.  _run_schedule is the loop of all; train, train_gat,
+train_graphsage and train_baseline_gcn hand it one step and one evaluation.
 
 What is kept identical (parity surface): the partition sampler (python `random`,
 same call order on every rank), which block of which base tensor each site owns
@@ -586,6 +587,86 @@ class DistributedGraphSAGEWrapper(_DistributedWrapper):
     _site_plan = DistributedGNNWrapper._site_plan             # (the same split: the vectors share idx_k)
 
 
+class DistributedBaselineGCNWrapper(_DistributedWrapper):
+    """One rank's view of GIST for the BaselineGCN family (gist_amd.modules.BaselineGCN, the plain GraphConv stack of the
+    Cluster-GCN and GIST papers): a replica of the base model and its sub-model of width n_hidden / num_subnet, over the
+    flat arenas `base` and `sub` (BaselineGCNArena: per layer GraphConv's own W [in, out] and b [out], every view on a
+    16-byte boundary).
+
+    Constructor as the other wrappers' (`args` needs num_subnet, n_hidden, n_layers, rank, dropout, use_layernorm).
+    Called with the five arguments only, it draws the initial weights from the torch RNG in the wrappers' order: on rank
+    0 the base BaselineGCN, then on every rank the sub one.  `base_init` = per layer (W [in, out], b) on rank 0 (others
+    pass None): given, even as None, nothing is drawn.  `sub_model` (every rank) and `base_model` (rank 0; None
+    elsewhere) are gist_amd.modules.BaselineGCN whose `layers.k.weight` / `.bias` are Parameters over the arena views,
+    names and state_dict keys kept.
+
+    The split is the reference's GCN split (cluster_gcn_ist_distrib.py:197-367) TRANSPOSED -- GraphConv stores [in, out],
+    so what the GCN's nn.Linear cuts by rows is cut by columns here and the other way round -- and without the
+    concatenated half: a GraphConv layer reads h alone, not [h | ah], so the input side of a layer takes idx_k-1 where the
+    GCN takes full_k-1 = [idx | idx + H].  Only `idx` of create_partition's (idx, full) is used:
+
+        layer        W rows        W columns      b
+        first        all           idx_0          idx_0
+        middle k     idx_k-1       idx_k          idx_k
+        last         idx_L-1       all            shared: the mean over the sites
+
+    With use_layernorm the norm is the model's whole-tensor one: a sub-model normalises over [n, H / S], the base over
+    [n, H].  `blocks` given (a test double, or HipBlocks()): one mover call per (site, layer, tensor).
+    Not given, on a GPU: the grouped mover -- one gist_arena_moves_f32 launch per dispatch and per sync."""
+    GROUPED = True
+
+    def __init__(self, args, g, in_feats, n_classes, device, *, base_init=_UNSET, blocks=None, comm=None, seed=0):
+        from .arena import BaselineGCNArena, baseline_gcn_dims
+        from .modules import BaselineGCN
+        self._BaselineGCN, self._Arena, self._baseline_gcn_dims = BaselineGCN, BaselineGCNArena, baseline_gcn_dims
+        self.seed = int(seed)
+        _DistributedWrapper.__init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm)
+        # the fused tail's dropout stream of this rank: the same as the engine's below
+        self.sub_model.set_dropout_seed(self.seed * 131 + self.rank)
+        self.engine = None                                    # attach_engine: train_baseline_gcn(..., host_path='step')
+
+    def attach_engine(self, n_max, x0=None):
+        """The BaselineGCNEngine that steps `sub` in place (dispatch and sync keep moving the same storage, `sub_model`
+        keeps viewing it), sized for batches of up to n_max rows; kept as `engine` across dispatches, with its dropout
+        counter, and rebuilt only for another n_max.  x0: the first site's layer-0 input buffer, for the further sites
+        of one process (BaselineGCNEngine)."""
+        from .baseline_gcn_engine import BaselineGCNEngine
+        e = self.engine
+        if e is None or e.n_max != int(n_max):
+            self.engine = BaselineGCNEngine(self.sub_dims, self.args.use_layernorm, self.args.dropout, n_max, self.device,
+                                            seed=self.seed * 131 + self.rank, arena=self.sub, x0=x0)
+        return self.engine
+
+    def _dims(self, sub):
+        return self._baseline_gcn_dims(self.in_feats, self.h if sub else self.H, self.n_classes, self.L)
+
+    def _new_arena(self, dims, trains):
+        return self._Arena(dims, self.device)                 # (gradients: the autograd's, or the engine's with_grads)
+
+    def _new_model(self, sub):
+        import torch.nn.functional as F
+        return self._BaselineGCN(self.in_feats, self.h if sub else self.H, self.n_classes, self.L, F.relu,
+                                 self.args.dropout, self.args.use_layernorm)
+
+    def _module_params(self, model):
+        return [(layer.weight.data, layer.bias.data) for layer in model.layers]
+
+    def _bind(self, arena, model, requires_grad):
+        """Make every parameter of `model` a Parameter over its block of `arena` (no copy) and record the arena on the
+        model."""
+        import torch.nn as nn
+        for k, layer in enumerate(model.layers):
+            layer.weight = nn.Parameter(arena.W[k], requires_grad=requires_grad)
+            layer.bias = nn.Parameter(arena.b[k], requires_grad=requires_grad)
+        arena.bind_module(model)
+        return model
+
+    def _site_plan(self, part, site):
+        idx = [layer[site][0] for layer in part]
+        return ([(None, idx[0], idx[0])] + [(idx[k - 1], idx[k], idx[k]) for k in range(1, self.L)] +
+                [(idx[self.L - 1], None, None)])
+
+
 def _run_schedule(models, args, cluster_iterator, log, at_dispatch, step, before_eval, accuracies):
     """The GIST schedule of both families (cluster_gcn_ist_distrib.py:385-450): no re-dispatch in epoch 0, a fresh
     optimiser at every dispatch point, sync at multiples of iter_per_site and at the very last iteration, evaluation
@@ -949,6 +1030,88 @@ def _graphsage_engine_steps(models, args, cluster_iterator):
             it.fill_features(batch, engine)
             batch.z0_dropped = False
         return engine.train_step(batch, args.lr, args.weight_decay)[0].clone()      # (0-dim, as 'module')
+
+    def before_eval():                               # (the device is idle: every extraction so far was complete)
+        for m in models:
+            m.engine.check_extract()
+    return at_dispatch, step, before_eval
+
+
+def train_baseline_gcn(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module'):
+    """The GIST loop (cluster_gcn_ist_distrib.py:370-479, _run_schedule) for the BaselineGCN family.
+
+    host_path='module': the reference's loop body on `ist_model.sub_model` -- masked gist_amd.nn.CrossEntropyLoss, a
+    new gist_amd.optim.Adam at every dispatch point; `cluster_iterator` is a ClusterIter.  GPU-only, like 'step': the
+    model's forward runs on torch.ops.gist.*, which are registered for the GPU alone, and the project has no CPU
+    fallback.  With `blocks` and `comm` doubles the wrapper itself -- construction, dispatch, sync -- runs on the CPU; a
+    training loop does not.
+    host_path='step': every site's step is ONE gist_baseline_gcn_step call on its wrapper's BaselineGCNEngine, which
+    steps `sub` in place; `cluster_iterator` is an EngineClusterIter.  `sub.reset_optimizer()` is the fresh optimiser of
+    a dispatch point; an engine's dropout counter runs on across dispatches (_baseline_engine_steps).
+    The family has no phase calls: there is no 'phases'.
+
+    `ist_model` is this rank's DistributedBaselineGCNWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites
+    then run in this process, the partition sampled once per dispatch.  Rank 0's `base_model` is scored by
+    utils.evaluate: the model's own full-graph forward.  Returns what train_graphsage returns."""
+    from .utils import evaluate
+    models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
+    if host_path not in ('module', 'step'):
+        raise ValueError("gist_amd: train_baseline_gcn host_path must be 'module' or 'step' (got %r)" % (host_path,))
+    if host_path == 'module' and torch.device(models[0].device).type != 'cuda':
+        raise ValueError("gist_amd: train_baseline_gcn(host_path='module') runs the model's forward on torch.ops.gist.*, "
+                         "which is GPU-only (the wrapper is on %s); there is no CPU fallback" % (models[0].device,))
+    if host_path == 'module':
+        from .sampler import ClusterIter, EngineClusterIter
+        if not isinstance(cluster_iterator, ClusterIter) or isinstance(cluster_iterator, EngineClusterIter):
+            raise ValueError("gist_amd: train_baseline_gcn(host_path='module') needs a gist_amd.sampler.ClusterIter as "
+                             "cluster_iterator (got %s)" % type(cluster_iterator).__name__)
+    steps = {'module': _module_steps, 'step': _baseline_engine_steps}[host_path]
+    at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
+
+    def accuracies():
+        base_model = models[0].base_model
+        return evaluate(base_model, g, labels, val_mask), evaluate(base_model, g, labels, test_mask)
+    return _run_schedule(models, args, cluster_iterator, lambda line: log(line, flush=True), at_dispatch, step,
+                         before_eval, accuracies)
+
+
+def _baseline_engine_steps(models, args, cluster_iterator):
+    """train_baseline_gcn's (at_dispatch, step, before_eval) on the fused step: one BaselineGCNEngine per wrapper over
+    its sub arena.
+
+    One site in the process (the distributed run): the optimiser launch of a step extracts the next batch of the epoch
+    beside it, as in train().  S sites in one process: the first layer of every sub-model takes the full input width
+    and the step never writes X_0, so the extracted batch -- CSR, reversed CSR, labels, layer 0's
+    input rows -- is the same for every site.  All engines are bound to the iterator's batcher and read ONE layer-0
+    input buffer, the first engine's; the first site's step extracts the batch, the others step on the buffers as they
+    stand.  No site gathers features of its own."""
+    from .sampler import EngineClusterIter
+    if torch.device(models[0].device).type != 'cuda':
+        raise ValueError("gist_amd: train_baseline_gcn(host_path='step') runs the fused step gist_baseline_gcn_step, which "
+                         "is GPU-only (the wrapper is on %s); use host_path='module' there" % (models[0].device,))
+    if not isinstance(cluster_iterator, EngineClusterIter):
+        raise ValueError("gist_amd: train_baseline_gcn(host_path='step') needs a gist_amd.sampler.EngineClusterIter as "
+                         "cluster_iterator (got %s): it describes the batches the step extracts on the device"
+                         % type(cluster_iterator).__name__)
+    it = cluster_iterator
+    first = models[0].attach_engine(it.n_max)
+    if it.engine is not first:
+        it.bind(first)
+    for m in models[1:]:
+        if m.engine is not None and m.engine.X[0] is not first.X[0]:
+            m.engine = None                          # (an engine with a layer-0 buffer of its own: rebuilt on the shared one)
+        engine = m.attach_engine(it.n_max, x0=first.X[0])
+        if engine.plan is None or engine._plan_keep[0] is not it.batcher:
+            engine.attach_batcher(it.batcher)
+    for m in models:
+        m.engine.prefetch = len(models) == 1
+
+    def at_dispatch():
+        for m in models:
+            m.sub.reset_optimizer()
+
+    def step(si, batch):
+        return models[si].engine.train_step(batch, args.lr, args.weight_decay)[0].clone()      # (0-dim, as 'module')
 
     def before_eval():                               # (the device is idle: every extraction so far was complete)
         for m in models:
