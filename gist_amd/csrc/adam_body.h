@@ -1,6 +1,6 @@
 // Adam over a flat arena with DEFERRED gradient reductions: the device code of gist_adam_segments_f32, in a header
-// because two kernels run it -- adam_segments_kernel (rowops.hip) and adam_extract_kernel (subgraph.hip: the
-// optimiser's workgroups and the NEXT batch's extraction in one grid).
+// because several kernels run it -- adam_stream_kernel and adam_segments_kernel (rowops.hip) and adam_extract_kernel
+// (subgraph.hip: the optimiser's workgroups and the NEXT batch's extraction in one grid).
 //
 // Inside a listed segment [begin, end) the gradient of element i is not grads[i] but the sum of n_src arrays
 // src[s * stride + (i - begin)] -- the split-K slabs of a weight-gradient projection, or the per-row-chunk column
@@ -79,17 +79,28 @@ __device__ __forceinline__ float chunk_partial4(const float *__restrict__ src, i
     return acc;
 }
 
+// One element's update with every rounding spelled out: the fused multiply-adds are written, everything else stays
+// the single operation it reads as (no contraction), so that how a caller unrolls or vectorises around it cannot
+// change a bit.  sqrt and the division are the correctly rounded ones.
+struct AdamNext { float p, m, v; };
+__device__ __forceinline__ AdamNext adam_value(float pv, float gv, float m0, float v0, float beta1, float beta2,
+                                               float eps, float wd, float step_size, float inv_bc2_sqrt) {
+#pragma clang fp contract(off)
+    if (wd != 0.f) gv = __builtin_fmaf(wd, pv, gv);
+    const float vv = beta2 * v0 + ((1.f - beta2) * gv) * gv;
+    const float mv = __builtin_fmaf(1.f - beta1, gv - m0, m0);      // lerp_ like torch
+    const float denom = __builtin_fmaf(sqrtf(vv), inv_bc2_sqrt, eps);
+    return {__builtin_fmaf(-step_size, mv / denom, pv), mv, vv};
+}
+
 __device__ __forceinline__ void adam_update(float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
                                             int64_t i, float gv, float beta1, float beta2, float eps, float wd,
                                             float step_size, float inv_bc2_sqrt) {
-    const float pv = p[i];
-    if (wd != 0.f) gv = fmaf(wd, pv, gv);
-    const float mv = m[i] + (1.f - beta1) * (gv - m[i]);        // lerp_ like torch
-    const float vv = beta2 * v[i] + (1.f - beta2) * gv * gv;
-    m[i] = mv;
-    v[i] = vv;
-    const float denom = sqrtf(vv) * inv_bc2_sqrt + eps;
-    p[i] = pv - step_size * (mv / denom);
+    const float pv = p[i], v0 = v[i], m0 = m[i];
+    const AdamNext o = adam_value(pv, gv, m0, v0, beta1, beta2, eps, wd, step_size, inv_bc2_sqrt);
+    m[i] = o.m;
+    v[i] = o.v;
+    p[i] = o.p;
 }
 
 // virtual block vb (arena chunks first, then the dedicated blocks), thread vt of its 256; no barrier inside.
@@ -159,6 +170,91 @@ __device__ __forceinline__ void adam_virtual_block(const AdamArgs &A, int64_t vb
         }
         if (kUpdate) adam_update(A.p, A.m, A.v, i, gv, A.beta1, A.beta2, A.eps, A.wd, A.step_size, A.inv_bc2_sqrt);
     }
+}
+
+// ---- the arena at stream rate (adam_stream_kernel, rowops.hip) --------------------------------------------------------
+// A SPAN is kAdamSpanBlocks consecutive arena blocks, one workgroup's work.  Where a span is whole, 16-byte aligned and
+// either outside every segment or inside ONE inline segment, thread vt takes four consecutive elements of each of its
+// blocks: every load of the span is a 16-byte load and all of them are issued before the first use (8 to 8 + 2 n_src
+// in flight per thread; adam_virtual_block loads one element's four dwords, uses them, and loads the next).  The
+// arithmetic per element is adam_value's and the slab sum is acc = 0, acc += src[k] in source order, as there: the
+// same bits.  g, m, v and the slabs are read and written non-temporally (nothing reads them again before a gigabyte
+// of other traffic) -- that hint is most of the gain, without it the span kernel is no faster than the block kernel;
+// p is not: the next step's split pre-pass reads it right behind this launch.  Any other span: false, and the caller
+// runs its blocks one by one.  Measured out (profiles/NEGATIVES.md): four blocks per span, 2048 looping workgroups.
+constexpr int kAdamSpanBlocks = 2;
+typedef float adam_f4 __attribute__((ext_vector_type(4)));
+template <bool kNT> __device__ __forceinline__ adam_f4 adam_ld4(const float *p) {
+    const adam_f4 *q = reinterpret_cast<const adam_f4 *>(p);
+    return kNT ? __builtin_nontemporal_load(q) : *q;
+}
+template <bool kNT> __device__ __forceinline__ void adam_st4(float *p, adam_f4 x) {
+    adam_f4 *q = reinterpret_cast<adam_f4 *>(p);
+    if (kNT) __builtin_nontemporal_store(x, q);
+    else *q = x;
+}
+__host__ __device__ inline int64_t adam_spans(int64_t n) {
+    return (adam_arena_blocks(n) + kAdamSpanBlocks - 1) / kAdamSpanBlocks;
+}
+
+__device__ __forceinline__ bool adam_stream_span(const AdamArgs &A, int64_t span, int vt) {
+    const AdamSegs &segs = A.segs;
+    const int64_t lo = span * (1024 * kAdamSpanBlocks), hi = lo + 1024 * kAdamSpanBlocks;
+    if (hi > A.n) return false;
+    if ((((uintptr_t)A.p | (uintptr_t)A.g | (uintptr_t)A.m | (uintptr_t)A.v) & 15) != 0) return false;
+    int sg = -1;                                           // uniform: the one inline segment that holds the span
+    for (int s = 0; s < segs.n; ++s)
+        if (segs.begin[s] < hi && segs.end[s] > lo) {
+            if (sg >= 0 || segs.ded_first[s] >= 0 || segs.begin[s] > lo || segs.end[s] < hi) return false;
+            sg = s;
+        }
+    const float *src = nullptr;
+    int64_t stride = 0;
+    int ns = 0;
+    if (sg >= 0) {
+        src = segs.src[sg] + (lo - segs.begin[sg]);
+        stride = segs.stride[sg];
+        ns = segs.n_src[sg];
+        if (((uintptr_t)src & 15) != 0 || (stride & 3) != 0) return false;
+    }
+    // uniform bases and one 32-bit lane offset (scalar-base addressing where the compiler takes it)
+    float *const pb = A.p + lo, *const gb = A.g + lo, *const mb = A.m + lo, *const vb = A.v + lo;
+    const unsigned e = 4u * (unsigned)vt;
+    adam_f4 pv[kAdamSpanBlocks], gv[kAdamSpanBlocks], mv[kAdamSpanBlocks], vv[kAdamSpanBlocks];
+#pragma unroll
+    for (int j = 0; j < kAdamSpanBlocks; ++j) {
+        pv[j] = adam_ld4<false>(pb + (e + 1024u * j));
+        mv[j] = adam_ld4<true>(mb + (e + 1024u * j));
+        vv[j] = adam_ld4<true>(vb + (e + 1024u * j));
+        if (sg < 0) gv[j] = adam_ld4<true>(gb + (e + 1024u * j));
+    }
+    if (sg >= 0) {
+#pragma unroll
+        for (int j = 0; j < kAdamSpanBlocks; ++j) gv[j] = adam_f4{0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < ns; ++k, src += stride) {      // source order
+            adam_f4 t[kAdamSpanBlocks];
+#pragma unroll
+            for (int j = 0; j < kAdamSpanBlocks; ++j) t[j] = adam_ld4<true>(src + (e + 1024u * j));
+#pragma unroll
+            for (int j = 0; j < kAdamSpanBlocks; ++j) gv[j] += t[j];
+        }
+#pragma unroll
+        for (int j = 0; j < kAdamSpanBlocks; ++j) adam_st4<true>(gb + (e + 1024u * j), gv[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < kAdamSpanBlocks; ++j) {
+        adam_f4 po, mo, vo;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const AdamNext o = adam_value(pv[j][c], gv[j][c], mv[j][c], vv[j][c], A.beta1, A.beta2, A.eps, A.wd,
+                                          A.step_size, A.inv_bc2_sqrt);
+            po[c] = o.p; mo[c] = o.m; vo[c] = o.v;
+        }
+        adam_st4<true>(mb + (e + 1024u * j), mo);
+        adam_st4<true>(vb + (e + 1024u * j), vo);
+        adam_st4<false>(pb + (e + 1024u * j), po);
+    }
+    return true;
 }
 
 // what gist_adam_segments_f32 checks and derives from its arguments (rowops.hip), shared with the fused launch

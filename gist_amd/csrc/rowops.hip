@@ -770,6 +770,33 @@ __global__ __launch_bounds__(256) void adam_segments_kernel(AdamArgs A) {
     adam_virtual_block(A, blockIdx.x, threadIdx.x);
 }
 
+// The same launch at stream rate (what gist_adam_segments_f32 launches; tuning hook GIST_TUNE_ADAM_STREAM = 1: the
+// kernel above).  Workgroups in the order of their own latency: the dedicated blocks (chunk sums walked source by
+// source) and the loss block first, then one workgroup per span of the arena.  A span that adam_stream_span does not
+// take (a segment's edge, a dedicated segment's range, the arena's tail, unaligned arenas) runs block by block
+// through adam_virtual_block: every element is written by the code that wrote it before.
+__global__ __launch_bounds__(256) void adam_stream_kernel(AdamArgs A) {
+    __shared__ float red[4];
+    int64_t w = blockIdx.x;
+    const int64_t n_arena = adam_arena_blocks(A.n);
+    if (w < A.segs.n_ded) {
+        adam_virtual_block(A, n_arena + w, threadIdx.x);
+        return;
+    }
+    w -= A.segs.n_ded;
+    if (A.row_nll != nullptr) {
+        if (w == 0) {
+            loss_reduce_256(A.row_nll, A.n_loss_rows, A.inv_count, A.loss, red);
+            return;
+        }
+        --w;
+    }
+    if (adam_stream_span(A, w, threadIdx.x)) return;
+#pragma unroll 1
+    for (int j = 0; j < kAdamSpanBlocks; ++j)
+        if (w * kAdamSpanBlocks + j < n_arena) adam_virtual_block(A, w * kAdamSpanBlocks + j, threadIdx.x);
+}
+
 // The deferred gradient sums WITHOUT the optimiser (gist_grad_segments_finish_f32): the same device code with the update
 // left out.  Grid: the inline segments' own arena chunks, then the dedicated blocks.
 __global__ __launch_bounds__(256) void grad_finish_kernel(AdamArgs A) {
@@ -1283,8 +1310,13 @@ extern "C" int gist_adam_segments_f32(float *param, float *grad, float *exp_avg,
                                             loss_count, loss, &A);
     if (rc != GIST_OK) return rc;
     if (n == 0 && row_loss == nullptr) return GIST_OK;
-    const int64_t blocks = gist::adam_arena_blocks(n) + A.segs.n_ded + (row_loss ? 1 : 0);
-    hipLaunchKernelGGL(gist::adam_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, gist::as_stream(stream), A);
+    if ((int)gist::tune(GIST_TUNE_ADAM_STREAM) == 1) {
+        const int64_t blocks = gist::adam_arena_blocks(n) + A.segs.n_ded + (row_loss ? 1 : 0);
+        hipLaunchKernelGGL(gist::adam_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, gist::as_stream(stream), A);
+        return gist::launch_status("gist_adam_segments_f32");
+    }
+    const int64_t blocks = A.segs.n_ded + (row_loss ? 1 : 0) + gist::adam_spans(n);
+    hipLaunchKernelGGL(gist::adam_stream_kernel, dim3((unsigned)blocks), dim3(256), 0, gist::as_stream(stream), A);
     return gist::launch_status("gist_adam_segments_f32");
 }
 

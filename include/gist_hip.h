@@ -353,7 +353,8 @@ int gist_b3_split_f32(const float *src, int64_t ld, int64_t rows, int64_t cols, 
 #define GIST_TUNE_B3C_SPLITS 13   /* k slices of the convert-on-load bf16x3 GEMM (0 = its own choice) */
 #define GIST_TUNE_B3_TAIL 14      /* bf16x3 GEMM: 1 = no k slices for the tiles past the last full round of 256 (whole tiles) */
 #define GIST_TUNE_B3_WIDE 15      /* bf16x3 GEMM: 1 = never the 256x256 output tile (always 256x128) */
-#define GIST_TUNE_COUNT 16
+#define GIST_TUNE_ADAM_STREAM 16 /* gist_adam_segments_f32: 1 = one short workgroup per 1024 elements, dword loads (not the span kernel) */
+#define GIST_TUNE_COUNT 17
 int gist_tuning_set(int knob, double value);
 double gist_tuning_get(int knob);
 
