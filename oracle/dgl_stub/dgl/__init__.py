@@ -7,11 +7,21 @@ that `oracle/gen_golden.py` can import the reference UNCHANGED and record
 golden input/output vectors from the reference's own arithmetic.
 
 It is never imported by the product (`gist_amd/`), by `bench.py` or by the GPU
-tests; only `oracle/gen_golden.py` puts this directory on `sys.path`.
+tests; only `oracle/gen_golden.py`, the `scripts/record_*_golden.py` recorders and
+a child process of `tests/test_gat_golden.py` (which checks the UDF path against
+the built-in one) put this directory on `sys.path`.
 
 Semantics restated (they are mathematically unambiguous):
   * update_all(copy_src, sum): y[v] = sum over in-edges (u->v) of x[u]
     (duplicate edges count twice, self loops are ordinary edges)
+  * apply_edges(fn): fn sees every edge once, in edge-id order: edges.src[k] / edges.dst[k] are the ndata[k] rows of
+    each edge's source / destination, edges.data[k] the edata[k] rows; the dict it returns goes into edata
+  * update_all(message_fn, reduce_fn) with callables (DGL's user-defined functions, as GATLayer uses them): the message
+    function sees the edges as apply_edges does; then DGL's degree bucketing: for every distinct in-degree d > 0 the
+    reduce function is called once with the nodes of that in-degree, nodes.mailbox[k] of shape [n_d, d, ...] holding
+    each node's d incoming messages ordered by edge id (a duplicate edge is two messages, a self loop an ordinary
+    one), nodes.data[k] their ndata rows; what it returns is written to those rows of ndata, and a row without
+    in-edges gets zeros
   * in_degrees(): number of in-edges per node
   * subgraph(ids): node-induced subgraph, node i of the result is ids[i],
     edges keep their original relative order, ndata rows are gathered
@@ -30,11 +40,29 @@ class _NData(dict):
         return dict.pop(self, k, *a)
 
 
+class _EdgeBatch(object):
+    """What an edge function sees: per-edge rows of the endpoints' node data and of the edge data."""
+
+    def __init__(self, g):
+        src, dst = torch.from_numpy(g._src), torch.from_numpy(g._dst)
+        self.src = {k: v[src] for k, v in g.ndata.items()}
+        self.dst = {k: v[dst] for k, v in g.ndata.items()}
+        self.data = dict(g.edata)
+
+
+class _NodeBatch(object):
+    """What a reduce function sees: the nodes of one in-degree, their data and their mailboxes."""
+
+    def __init__(self, data, mailbox):
+        self.data, self.mailbox = data, mailbox
+
+
 class DGLGraph(object):
     """Directed multigraph stored as an edge list (src -> dst)."""
 
     def __init__(self, data=None, num_nodes=None, idtype=torch.int64):
         self.ndata = _NData()
+        self.edata = _NData()
         self._idtype = idtype
         self._device = torch.device('cpu')
         if data is None:
@@ -88,9 +116,33 @@ class DGLGraph(object):
         g = DGLGraph.__new__(DGLGraph)
         g.__dict__.update(self.__dict__)
         g.ndata = _NData(self.ndata)
+        g.edata = _NData(self.edata)
         return g
 
+    def apply_edges(self, fn):
+        self.edata.update(fn(_EdgeBatch(self)))
+
+    def _update_all_udf(self, message_fn, reduce_fn):
+        """Degree bucketing: one reduce call per distinct in-degree d > 0, mailboxes [n_d, d, ...] in edge-id order."""
+        msgs = message_fn(_EdgeBatch(self))
+        deg = np.bincount(self._dst, minlength=self._n)
+        order = np.argsort(self._dst, kind='stable')          # edge ids grouped by destination, ascending inside a group
+        start = np.concatenate([[0], np.cumsum(deg)[:-1]])
+        out = {}
+        for d in np.unique(deg[deg > 0]):
+            nodes = np.nonzero(deg == d)[0]
+            eid = torch.from_numpy(order[start[nodes][:, None] + np.arange(d)[None, :]])          # [n_d, d]
+            nid = torch.from_numpy(nodes)
+            res = reduce_fn(_NodeBatch({k: v[nid] for k, v in self.ndata.items()}, {k: m[eid] for k, m in msgs.items()}))
+            for k, v in res.items():
+                if k not in out:
+                    out[k] = torch.zeros((self._n,) + tuple(v.shape[1:]), dtype=v.dtype)
+                out[k] = out[k].index_copy(0, nid, v)
+        self.ndata.update(out)
+
     def update_all(self, msg, red, apply_fn=None):
+        if callable(msg) and callable(red):
+            return self._update_all_udf(msg, red)
         assert msg[0] == 'copy_src' and red[0] == 'sum'
         _, src_field, m_field = msg
         _, m_field2, out_field = red

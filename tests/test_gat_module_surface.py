@@ -32,7 +32,9 @@ def test_gat_layer_sizing_and_parameter_names(num_layers):
 
 def _reference_init(num_layers, in_dim, hidden, out_dim, heads):
     """The reference's RNG calls in order: per head nn.Linear(fc), nn.Linear(attn_fc) (their default init), then
-    xavier_normal_ with the relu gain on fc and on attn_fc; head by head, layer by layer."""
+    xavier_normal_ with the relu gain on fc and on attn_fc; head by head, layer by layer.  A restatement with a
+    witness: tests/golden/G9_gat_toy*.npz holds what the reference's own classes drew at one seed, and
+    tests/test_gat_golden.py holds gist_amd.modules.GAT to those values bit for bit."""
     sizes = [(in_dim, hidden, heads)] + [(hidden, hidden, heads)] * (num_layers - 2) + [(hidden, out_dim, 1)]
     out = []
     gain = nn.init.calculate_gain('relu')
