@@ -28,20 +28,15 @@ import ctypes
 
 import torch
 
-from . import _lib, hip
+from . import _lib
 from .arena import BaselineGCNArena
 from .engine import StepEngine
 
 
-def _describe(t):
-    """A refused x0 in words: its shape, dtype and device."""
-    if not isinstance(t, torch.Tensor):
-        return type(t).__name__
-    return '%s %s on %s%s' % (str(t.dtype).replace('torch.', ''), list(t.shape), t.device,
-                              '' if t.is_contiguous() else ', not contiguous')
-
-
 class BaselineGCNEngine(StepEngine):
+    STEP = 'gist_baseline_gcn_step'     # (the family has no phase calls)
+    LOSS_MASK = True
+
     def __init__(self, dims, use_layernorm, dropout, n_max, device, seed=0, arena=None, x0=None):
         """dims = [(in_k, out_k)] of ALL layers, the output layer included (gist_amd.arena.baseline_gcn_dims).
 
@@ -49,14 +44,9 @@ class BaselineGCNEngine(StepEngine):
         several sub-models of one process (gist_amd.ist.train_baseline_gcn) bound to the same batcher step on the batch
         the first of them extracted.  The step never writes X_0, so nothing of one site's step reaches another's."""
         self.dims = [(int(i), int(o)) for (i, o) in dims]
-        if x0 is not None:
-            # (checked before anything else is built: a tensor of the wrong kind never reaches a plan)
-            want = (int(n_max) if n_max is not None else 0, self.dims[0][0])
-            if (not isinstance(x0, torch.Tensor) or tuple(x0.shape) != want or x0.dtype != torch.float32
-                    or x0.device.type != torch.device(device).type or not x0.is_contiguous()):
-                raise ValueError('gist_amd: a shared x0 must be a contiguous fp32 [%d, %d] tensor on %s (got %s)'
-                                 % (want + (device, _describe(x0))))
         StepEngine.__init__(self, device, n_max, len(self.dims))
+        # (checked before anything else is built: a tensor of the wrong kind never reaches a plan)
+        self.x0 = self._shared_x0(x0, self.dims[0][0])
         if arena is not None and [tuple(d) for d in arena.dims] != self.dims:
             raise ValueError('gist_amd: the arena\'s dims %s are not the engine\'s %s' % (arena.dims, self.dims))
         self.arena = (arena if arena is not None else BaselineGCNArena(self.dims, device)).with_grads()
@@ -69,7 +59,7 @@ class BaselineGCNEngine(StepEngine):
         self.fuse = False
         n = self.n_max
         f32 = dict(dtype=torch.float32, device=device)
-        self.X = [x0 if (k == 0 and x0 is not None) else torch.zeros(n, i, **f32) for k, (i, o) in enumerate(self.dims)]
+        self.X = [self.x0] + [torch.zeros(n, i, **f32) for (i, o) in self.dims[1:]]
         self.T = [torch.zeros(n, min(i, o), **f32) for (i, o) in self.dims]
         self.Y = [torch.zeros(n, o, **f32) for (i, o) in self.dims]
         own_yhat = self.use_layernorm and self.p_drop > 0.0
@@ -82,7 +72,6 @@ class BaselineGCNEngine(StepEngine):
         self.row_loss = torch.zeros(n, **f32)
         self.loss = torch.zeros(1, **f32)
         self.partials = torch.zeros(max(1, _lib.load().gist_colsum_partials(n)) * self.n_classes, **f32)
-        self._model = None
 
     @staticmethod
     def bwd_width(dims):
@@ -129,17 +118,6 @@ class BaselineGCNEngine(StepEngine):
     def logits(self, n):
         return self._logits[:n]
 
-    def bind(self, model):
-        """Make a gist_amd.modules.BaselineGCN's Parameters views of the arena (values: the model's; names and state_dict
-        keys unchanged) and remember it as `model`: utils.evaluate(model, g, ...) scores the live weights with the model's
-        own in-place full-graph forward."""
-        self._model = self.arena.adopt_module(model)
-        return self._model
-
-    @property
-    def model(self):
-        return self._model
-
     def _advance_drop_calls(self, n, train):
         """-> this step's base in the dropout counter space; a training step with dropout takes every hidden layer's
         [n, out] elements, rounded up to even, as autograd.gcn_tail does."""
@@ -149,40 +127,3 @@ class BaselineGCNEngine(StepEngine):
                 numel = n * o
                 self.drop_calls += numel + (numel & 1)
         return off
-
-    def _open_step(self, b, train):
-        """-> (flags, ids pointer, this step's dropout offset)."""
-        flags, ids_ptr = self._begin_step(b, train, ())
-        self._bind_row_blocks(b)
-        return flags, ids_ptr, self._advance_drop_calls(b.n, train)
-
-    def _call_step(self, ids_ptr, n, off, lr, betas, eps, weight_decay, t, flags, phase):
-        """One gist_baseline_gcn_step call (the family has no phase calls: phase is 0)."""
-        rc = _lib.load().gist_baseline_gcn_step(ctypes.byref(self.plan), ids_ptr, n, off, lr, betas[0], betas[1], eps,
-                                                weight_decay, t, flags | phase, hip._stream())
-        _lib.check(rc, 'gist_baseline_gcn_step')
-
-    def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
-        self._need_plan()
-        P = self.plan
-        if mask is None:
-            P.loss_mask, P.loss_count = None, 0
-        else:
-            if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or mask.numel() < b.n:
-                raise ValueError('gist_amd: the loss mask must be a contiguous uint8 GPU tensor of at least n elements')
-            P.loss_mask = mask.data_ptr()
-            P.loss_count = int(count) if count is not None else int(mask[:b.n].count_nonzero().item())
-        return self._run(b, lr, weight_decay, train, betas, eps)
-
-    def train_step(self, b, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
-        """One iteration of the reference's loop as ONE gist_baseline_gcn_step call.  Returns the device loss tensor: the
-        mean CE over the batch rows, or over the `count` rows where `mask` (uint8 [n]) is not zero -- pred[train_mask] of
-        the reference's loop; a cluster of the train graph needs none.  Nothing synchronises with the host (give `count`
-        with a mask), nothing is allocated."""
-        return self._step(b, lr, weight_decay, True, betas, eps, mask, count)
-
-    def forward(self, b):
-        """BaselineGCN.forward in evaluation mode on the batch (extracted first if it is only described; no dropout) and
-        its loss; parameters untouched.  Returns the logits view [n, C]; the loss is in `self.loss`."""
-        self._step(b, 0.0, 0.0, False)
-        return self.logits(b.n)

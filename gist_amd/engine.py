@@ -122,7 +122,19 @@ _BARRIER_TIMEOUT = ('gist_amd: gist_extract_parts_batch timed out at its grid ba
 class StepEngine(object):
     """What SageEngine, GATEngine and GraphSAGEEngine share around their one-call steps: the graph, batch-buffer and arena
     parts of the plan, the start and the end of a step, the next batch's extraction beside the optimiser, the dropout
-    counter, the one-launch extraction's scratch and error word, and the HIP-event step timer."""
+    counter, the one-launch extraction's scratch and error word, and the HIP-event step timer -- and, for the families
+    whose whole iteration is one C call on a plan of their own, the step surface: _step / train_step / forward on the
+    engine's own logits, loss and moments, _native_step on a module binding's.
+
+    A family states: STEP, its C entry point (its phase calls, if it has them, are STEP + '_phase'); DROP_OFFSET, whether
+    that call takes a dropout offset; LOSS_MASK, whether its plan takes a loss mask; LOGITS, the field of the plan's last
+    layer that holds the logits pointer, for a module binding to point at its own buffer (BaselineGCNEngine, which has no
+    binding, keeps its logits beside the layers); `x0`, its layer-0 input buffer, whatever else the family calls it
+    (GATEngine.X0, BaselineGCNEngine.X[0], Z[0])."""
+    STEP = None
+    DROP_OFFSET = True
+    LOSS_MASK = False
+    LOGITS = 'Y'
 
     def __init__(self, device, n_max, n_layers=0):
         who = type(self).__name__
@@ -140,6 +152,23 @@ class StepEngine(object):
         self._mark, self._mark_np, self._mark_tag = None, None, 0     # check_extract_deferred's pinned progress mark
         # the last forward phase: (batch, flags, ids pointer, what else the family's call takes -- SageEngine's dropout offset)
         self._phase_ctx = (None, 0, None, None)
+        self._model = None
+        self._lent = False                      # the plan's logits / loss / moment pointers are a module binding's
+
+    def _shared_x0(self, x0, width):
+        """-> x0, ANOTHER engine's layer-0 input buffer to read instead of one of this engine's own (several sub-models of
+        one process, bound to the same batcher, step on the batch the first of them extracted; the step only reads it),
+        checked before it reaches a plan; None: a fresh buffer."""
+        want = (self.n_max, width)
+        if x0 is None:
+            return torch.zeros(*want, dtype=torch.float32, device=self.device)
+        if (not isinstance(x0, torch.Tensor) or tuple(x0.shape) != want or x0.dtype != torch.float32
+                or x0.device.type != torch.device(self.device).type or not x0.is_contiguous()):
+            got = type(x0).__name__ if not isinstance(x0, torch.Tensor) else '%s %s on %s%s' % (
+                str(x0.dtype).replace('torch.', ''), list(x0.shape), x0.device, '' if x0.is_contiguous() else ', not contiguous')
+            raise ValueError('gist_amd: a shared x0 must be a contiguous fp32 [%d, %d] tensor on %s (got %s)'
+                             % (want + (self.device, got)))
+        return x0
 
     def _bind_graph(self, P, batcher):
         """The fields both plan structs share: the resident training graph and the batcher's batch buffers."""
@@ -291,6 +320,97 @@ class StepEngine(object):
     def _close_step(self, b, train):
         pass
 
+    def _open_step(self, b, train):
+        """-> (flags, ids pointer, this step's dropout offset); the per-batch fields of the plan are written."""
+        flags, ids_ptr = self._begin_step(b, train, ())
+        self._bind_row_blocks(b)
+        return flags, ids_ptr, self._advance_drop_calls(b.n, train)
+
+    def _call_step(self, ids_ptr, n, off, lr, betas, eps, weight_decay, t, flags, phase):
+        """One STEP call (phase = 0), or one STEP + '_phase' call.  off: the forward's dropout offset (_run hands the
+        backward and the optimiser phase the one _open_step returned for the forward: drop_calls advances once per
+        iteration)."""
+        name = self.STEP + '_phase' if phase else self.STEP
+        call, plan = getattr(_lib.load(), name), ctypes.byref(self.plan)
+        if self.DROP_OFFSET:
+            rc = call(plan, ids_ptr, n, off, lr, betas[0], betas[1], eps, weight_decay, t, flags | phase, hip._stream())
+        else:
+            rc = call(plan, ids_ptr, n, lr, betas[0], betas[1], eps, weight_decay, t, flags | phase, hip._stream())
+        _lib.check(rc, name)
+
+    def _check_fresh(self, b):
+        """Refuse a batch whose layer-0 buffer a step has already written over (GraphSAGEEngine)."""
+
+    def _loss_rows(self, b, mask, count):
+        """The rows the mean CE is over into the plan: all of the batch, or the `count` ones where `mask` is not zero."""
+        P = self.plan
+        if mask is None:
+            P.loss_mask, P.loss_count = None, 0
+        else:
+            if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or mask.numel() < b.n:
+                raise ValueError('gist_amd: the loss mask must be a contiguous uint8 GPU tensor of at least n elements')
+            P.loss_mask = mask.data_ptr()
+            P.loss_count = int(count) if count is not None else int(mask[:b.n].count_nonzero().item())
+
+    def _point_logits(self, ptr):
+        """Where the plan takes the address of a step's logits (a module binding's buffer, or the engine's own)."""
+        setattr(self.plan.layer[len(self.dims) - 1], self.LOGITS, ptr)
+
+    def _reclaim(self):
+        """Point the plan's logits, loss and Adam moments back at the engine's own buffers (a binding lent them)."""
+        P, A = self.plan, self.arena
+        self._point_logits(self.logits(1).data_ptr())
+        P.loss = self.loss.data_ptr()
+        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
+        self._lent = False
+
+    def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None, *, phase=0,
+              given=False, adam_step=None, lent=False):
+        """One call of the family's step (phase = 0: the whole iteration, or, train=False, its forward and loss), or one
+        phase call, one third of it (_run), on the engine's own logits, loss and moment buffers unless a binding lent the
+        plan its own.  A forward refuses a stale batch and sets the rows the mean CE is over; a mask for a family whose
+        plan takes none is an error, not ignored."""
+        self._need_plan()
+        if mask is not None and not self.LOSS_MASK:
+            raise ValueError('gist_amd: %s has no loss mask: its mean CE is over all batch rows' % self.STEP)
+        if phase in (0, _lib.GIST_STEP_PHASE_FORWARD):
+            self._check_fresh(b)
+            if self.LOSS_MASK:
+                self._loss_rows(b, mask, count)
+        if lent:
+            self._lent = True
+        elif self._lent:
+            self._reclaim()
+        return self._run(b, lr, weight_decay, train, betas, eps, phase, given, adam_step)
+
+    def _native_step(self, *args, **kw):
+        """_step for a module binding (the name ModuleEngine calls its engine's phases by), which points the plan's
+        logits, loss and Adam moments at buffers of its own before it calls.  The mean CE is over all batch rows."""
+        return self._step(*args, lent=True, **kw)
+
+    def train_step(self, b, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
+        """One iteration of the reference's loop as ONE call of the family's step.  Returns the device loss tensor: the
+        mean CE over the batch rows, or over the `count` rows where `mask` (uint8 [n]) is not zero -- pred[train_mask] of
+        the reference's loop; a cluster of the train graph needs none.  Nothing synchronises with the host (give `count`
+        with a mask), nothing is allocated."""
+        return self._step(b, lr, weight_decay, True, betas, eps, mask, count)
+
+    def forward(self, b):
+        """The model's forward in evaluation mode on the batch (extracted first if it is only described; no dropout) and
+        its loss; parameters untouched.  Returns the logits view [n, C]; the loss is in `self.loss`."""
+        self._step(b, 0.0, 0.0, False)
+        return self.logits(b.n)
+
+    def bind(self, model):
+        """Make the Parameters of the family's nn.Module views of the arena (values: the model's; names and state_dict
+        keys unchanged) and remember it as `model`: utils.evaluate(model, g, ...) scores the live weights."""
+        self._model = self.arena.adopt_module(model)
+        return self._model
+
+    @property
+    def model(self):
+        return self._model
+
     def _extraction_scratch(self):
         """The barrier ticket + counts of the one-launch extraction (allocated at its first use)."""
         if self._extract_scratch is None:
@@ -373,6 +493,7 @@ class SageEngine(StepEngine):
         self.arena = arena if arena is not None else ParamArena(self.dims, device)
         f32 = dict(dtype=torch.float32, device=device)
         self.Z = [torch.zeros(self.n_max, 2 * i, **f32) for (i, o) in self.dims]
+        self.x0 = self.Z[0]
         self.n_classes = self.dims[-1][1]
         self.ldc = _round_up(self.n_classes, 4)
         self.Y = [torch.zeros(self.n_max, o, **f32) for (i, o) in self.dims[:-1]]

@@ -21,12 +21,16 @@ import weakref
 
 import torch
 
-from . import _lib, hip
+from . import _lib
 from .arena import GATArena
 from .engine import StepEngine
 
 
 class GATEngine(StepEngine):
+    STEP = 'gist_gat_step'
+    DROP_OFFSET = False                 # (the GAT has no dropout)
+    LOGITS = 'out'
+
     def __init__(self, dims=None, n_max=None, device=None, arena=None, x0=None):
         """dims = [(in_k, out_k, heads_k)] (gist_amd.arena.gat_dims), or `arena` = a GATArena to adopt (its dims).  The
         dims say how a layer's heads are combined, as in the plan: layer k + 1 reading heads_k * out_k columns means
@@ -52,13 +56,7 @@ class GATEngine(StepEngine):
         # extraction cannot form it), a dense layer-0 input buffer
         self.fuse = False
         f32 = dict(dtype=torch.float32, device=self.device)
-        if x0 is None:
-            x0 = torch.zeros(n, self.dims[0][0], **f32)
-        elif (x0.shape != (n, self.dims[0][0]) or x0.dtype != torch.float32 or x0.device.type != torch.device(self.device).type
-              or not x0.is_contiguous()):
-            raise ValueError('gist_amd: a shared x0 must be a contiguous fp32 [%d, %d] tensor on %s'
-                             % (n, self.dims[0][0], self.device))
-        self.X0 = x0
+        self.x0 = self.X0 = self._shared_x0(x0, self.dims[0][0])
         self.Z = [torch.zeros(n, h * o, **f32) for (i, o, h) in self.dims]
         self.out = [torch.zeros(n, w, **f32) for w in widths]
         self.s_src = [torch.zeros(n, h, **f32) for (i, o, h) in self.dims]
@@ -76,8 +74,6 @@ class GATEngine(StepEngine):
         self.dlogits = torch.zeros(n, self.n_classes, **f32)
         self.row_loss = torch.zeros(n, **f32)
         self.loss = torch.zeros(1, **f32)
-        self._model = None
-        self._lent = False                      # the plan's logits / loss / moment pointers are a GATModuleEngine's
 
     def attach_batcher(self, batcher):
         """Build the native step plan (struct gist_gat_step_plan) over `batcher`'s resident graph and batch buffers."""
@@ -131,40 +127,7 @@ class GATEngine(StepEngine):
     def _open_step(self, b, train):
         return self._begin_step(b, train, ()) + (None,)
 
-    def _call_step(self, ids_ptr, n, extra, lr, betas, eps, weight_decay, t, flags, phase):
-        name = 'gist_gat_step_phase' if phase else 'gist_gat_step'
-        rc = getattr(_lib.load(), name)(ctypes.byref(self.plan), ids_ptr, n, lr, betas[0], betas[1], eps, weight_decay, t,
-                                        flags | phase, hip._stream())
-        _lib.check(rc, name)
-
-    def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, phase=0, given=False, adam_step=None,
-              lent=False):
-        """One gist_gat_step call (phase = 0: the whole iteration), or one gist_gat_step_phase call, one third of it
-        (StepEngine._run), on the engine's own logits, loss and moment buffers unless a binding lent the plan its own."""
-        self._need_plan()
-        if self._lent and not lent:
-            self._reclaim()
-        return self._run(b, lr, weight_decay, train, betas, eps, phase, given, adam_step)
-
-    def _native_step(self, *args, **kw):
-        """_step for module_engine.GATModuleEngine (the name ModuleEngine calls its engine's phases by), which points
-        the plan's logits, loss and Adam moments at buffers of its own before it calls."""
-        return self._step(*args, lent=True, **kw)
-
-    def _reclaim(self):
-        """Point the plan's logits, loss and Adam moments back at the engine's own buffers (a binding lent them)."""
-        P, A = self.plan, self.arena
-        P.layer[len(self.dims) - 1].out, P.loss = self.out[-1].data_ptr(), self.loss.data_ptr()
-        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
-        self._lent = False
-
     def train_step(self, b, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
         """One iteration of the reference's GAT loop as ONE gist_gat_step call.  Returns the device loss tensor (mean CE
         over the batch rows); nothing synchronises with the host, nothing is allocated."""
         return self._step(b, lr, weight_decay, True, betas, eps)
-
-    def forward(self, b):
-        """GAT.forward on the batch (extracted first if it is only described) and its loss; parameters untouched.
-        Returns the logits view [n, C]; the loss is in `self.loss`."""
-        self._step(b, 0.0, 0.0, False)
-        return self.logits(b.n)

@@ -28,12 +28,15 @@ import weakref
 
 import torch
 
-from . import _lib, hip
+from . import _lib
 from .arena import GraphSAGEArena
 from .engine import StepEngine
 
 
 class GraphSAGEEngine(StepEngine):
+    STEP = 'gist_graphsage_step'
+    LOSS_MASK = True
+
     def __init__(self, dims, dropout, n_max, device, seed=0, use_pp=False, arena=None):
         """dims = [(in_k, out_k)] of ALL layers, the output layer included (gist_amd.arena.graphsage_dims)."""
         self.dims = [(int(i), int(o)) for (i, o) in dims]
@@ -52,6 +55,7 @@ class GraphSAGEEngine(StepEngine):
         n = self.n_max
         f32 = dict(dtype=torch.float32, device=device)
         self.Z = [torch.zeros(n, 2 * i, **f32) for (i, o) in self.dims]
+        self.x0 = self.Z[0]                      # (an engine's own: a training step with dropout drops it in place)
         self.H = [None] + [torch.zeros(n, i, **f32) if self.p_drop > 0.0 else None for (i, o) in self.dims[1:]]
         self.Y = [torch.zeros(n, o, **f32) for (i, o) in self.dims]
         self.yhat = [torch.zeros(n, o, **f32) for (i, o) in self.dims[:-1]]
@@ -61,8 +65,6 @@ class GraphSAGEEngine(StepEngine):
         self.row_loss = torch.zeros(n, **f32)
         self.loss = torch.zeros(1, **f32)
         self.partials = torch.zeros(max(1, _lib.load().gist_colsum_partials(n)) * self.n_classes, **f32)
-        self._model = None
-        self._lent = False                      # the plan's logits / loss / moment pointers are a GraphSAGEModuleEngine's
 
     def attach_batcher(self, batcher):
         """Build the native step plan (struct gist_graphsage_step_plan) over `batcher`'s resident graph and batch
@@ -107,31 +109,6 @@ class GraphSAGEEngine(StepEngine):
         current row blocks)?"""
         return int(_lib.load().gist_graphsage_step_folds(ctypes.byref(self.plan), k)) == 1
 
-    def bind(self, model):
-        """Make a gist_amd.modules.GraphSAGE's Parameters views of the arena (values: the model's; names and state_dict
-        keys unchanged) and remember it as `model`: utils.evaluate(model, g, ...) scores the live weights."""
-        self._model = self.arena.adopt_module(model)
-        return self._model
-
-    @property
-    def model(self):
-        return self._model
-
-    def _open_step(self, b, train):
-        """-> (flags, ids pointer, this step's dropout offset); drop_calls advances as op_by_op.decide does."""
-        flags, ids_ptr = self._begin_step(b, train, ())
-        self._bind_row_blocks(b)
-        return flags, ids_ptr, self._advance_drop_calls(b.n, train)
-
-    def _call_step(self, ids_ptr, n, off, lr, betas, eps, weight_decay, t, flags, phase):
-        """One gist_graphsage_step call (phase = 0), or one gist_graphsage_step_phase call.  off: the forward's dropout
-        offset (StepEngine._run hands the backward and the optimiser phase the one _open_step returned for the forward:
-        drop_calls advances once per iteration)."""
-        name = 'gist_graphsage_step_phase' if phase else 'gist_graphsage_step'
-        rc = getattr(_lib.load(), name)(ctypes.byref(self.plan), ids_ptr, n, off, lr, betas[0], betas[1], eps,
-                                        weight_decay, t, flags | phase, hip._stream())
-        _lib.check(rc, name)
-
     def _close_step(self, b, train):
         # (after a whole step and after each phase call: the forward phase is the one that drops Z_0)
         if train and self.p_drop > 0.0:
@@ -141,51 +118,3 @@ class GraphSAGEEngine(StepEngine):
         if b.ready and b.z0_dropped:
             raise RuntimeError('gist_amd: one step per extraction -- this Batch was already trained on with dropout, '
                                'its layer-0 buffer holds dropped values; take a fresh batch from the iterator')
-
-    def _native_step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, phase=0, given=False,
-                     adam_step=None):
-        """One call for module_engine.GraphSAGEModuleEngine (the name ModuleEngine calls its engine's phases by), which
-        points the plan's logits, loss and Adam moments at buffers of its own before it calls: the forward-only step of an
-        evaluation-mode forward (phase = 0), or one gist_graphsage_step_phase call.  The mean CE is over all batch rows."""
-        self._need_plan()
-        if phase in (0, _lib.GIST_STEP_PHASE_FORWARD):
-            self._check_fresh(b)
-            self.plan.loss_mask, self.plan.loss_count = None, 0
-        self._lent = True
-        return self._run(b, lr, weight_decay, train, betas, eps, phase, given, adam_step)
-
-    def _reclaim(self):
-        """Point the plan's logits, loss and Adam moments back at the engine's own buffers (a binding lent them)."""
-        P, A = self.plan, self.arena
-        P.layer[len(self.dims) - 1].Y, P.loss = self.Y[-1].data_ptr(), self.loss.data_ptr()
-        P.exp_avg, P.exp_avg_sq = A.exp_avg.data_ptr(), A.exp_avg_sq.data_ptr()
-        self._lent = False
-
-    def _step(self, b, lr, weight_decay, train, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
-        self._need_plan()
-        self._check_fresh(b)
-        if self._lent:
-            self._reclaim()
-        P = self.plan
-        if mask is None:
-            P.loss_mask, P.loss_count = None, 0
-        else:
-            if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or mask.numel() < b.n:
-                raise ValueError('gist_amd: the loss mask must be a contiguous uint8 GPU tensor of at least n elements')
-            P.loss_mask = mask.data_ptr()
-            P.loss_count = int(count) if count is not None else int(mask[:b.n].count_nonzero().item())
-        return self._run(b, lr, weight_decay, train, betas, eps)
-
-    def train_step(self, b, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, mask=None, count=None):
-        """One iteration of the reference's loop as ONE gist_graphsage_step call.  Returns the device loss tensor: the mean
-        CE over the batch rows, or over the `count` rows where `mask` (uint8 [n]) is not zero -- pred[train_mask] of the
-        reference's loop; a cluster of the train graph needs none.  Nothing synchronises with the host (give `count`
-        with a mask), nothing is allocated."""
-        return self._step(b, lr, weight_decay, True, betas, eps, mask, count)
-
-    def forward(self, b):
-        """GraphSAGE.forward in evaluation mode on the batch (extracted first if it is only described; every layer
-        aggregates, no dropout) and its loss; parameters untouched.  Returns the logits view [n, C]; the loss is in
-        `self.loss`."""
-        self._step(b, 0.0, 0.0, False)
-        return self.logits(b.n)

@@ -16,8 +16,10 @@ vectors; DistributedGNNWrapper, DistributedGATWrapper and DistributedGraphSAGEWr
 GCN split, the LayerNorm's gamma and beta following the bias; one grouped mover launch per dispatch and per sync) give
 it their dims, arena, model, binding and plan (_site_plan), and keep what is their own (the SAGE engine and evaluator;
 the GAT heads); DistributedBaselineGCNWrapper (gist_amd.modules.BaselineGCN: the GCN split transposed for GraphConv's
-[in, out] weight, on the grouped mover too) does the same.  _run_schedule is the loop of all; train, train_gat,
-train_graphsage and train_baseline_gcn hand it one step and one evaluation.
+[in, out] weight, on the grouped mover too) does the same.  _run_schedule is the loop of all.  train hands it
+one step and one evaluation; so does _train, the one body of train_gat, train_graphsage and train_baseline_gcn.  Its step
+comes from _module_steps, _engine_steps or _phase_steps, each written once against the facts a wrapper class states: its
+host paths and evaluators, whether its sites share layer 0's input buffer, and what it asks of the iterator.
 
 What is kept identical (parity surface): the partition sampler (python `random`,
 same call order on every rank), which block of which base tensor each site owns
@@ -157,13 +159,29 @@ class _DistributedWrapper(object):
     vectors (m = 1: the SAGE GCN's bias, the GAT's stacked attn vectors; m = 3: GraphSAGE's bias, gamma, beta), and a
     site owns of layer k the block (rows, cols) of the matrix and the columns cols2 of every vector (None = all); the
     last layer has one vector, which is shared and becomes the mean over the sites.  A family supplies _dims,
-    _new_arena, _new_model, _module_params, _bind and _site_plan.
+    _new_arena, _new_model and _site_plan; _module_params and _bind are the arena's own statements (module_params,
+    param_views, bind_module), the GAT's its arena's stacked-heads ones.
 
     Movers: per-tensor calls on `blocks` (HipBlocks, or a test double), one per (site, layer, tensor); or, for a family
     with GROUPED set, no `blocks` given and a GPU, the grouped mover: ONE gist_arena_moves_f32 launch per dispatch and
     per sync over descriptor tables built once here (block sizes never change, H % S == 0), the indices of a partition
-    pooled into one int32 tensor that is uploaded once per _set_partition."""
+    pooled into one int32 tensor that is uploaded once per _set_partition.
+
+    The family's training loop (train_gat, train_graphsage, train_baseline_gcn: _train) reads the facts below, and builds
+    the engine of the one-call and the phase path through attach_engine, for which the family supplies
+    _new_engine(n_max, x0)."""
     GROUPED = False
+    TRAIN = None                # the family's public loop, for its messages
+    STEP_PATH = 'step'          # what host_path calls the one-call path
+    PHASES = None               # host_path='phases': gist_amd.module_engine's binder, by name; None: no phase calls
+    SHARES_X0 = False           # S sites in one process: do the further engines read the first one's layer-0 buffer?
+    MODULE_ON_CPU = False       # does the module loop run without a GPU?
+    EVAL_PATHS = {'layers': None}       # eval_path -> (module, class) of the evaluator of rank 0's base_model; None: its forward
+    use_pp = None               # what the iterator's use_pp must be; None: the family has none, the iterator's own feed()
+
+    @staticmethod
+    def _module_iterator(it):
+        """host_path='module': refuse an iterator the family's module loop cannot run on (ValueError)."""
 
     def __init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm):
         self.args = args
@@ -202,6 +220,33 @@ class _DistributedWrapper(object):
         self._plan = None
         if self.grouped:
             self._build_tables()
+        self.engine = None                                    # attach_engine: the family's loop on its one-call step
+
+    def _module_params(self, model):
+        """The values of `model`'s parameters, per layer its tensors, as the arena's load takes them."""
+        flat = iter(p.data for p in self.sub.module_params(model))
+        return [tuple(next(flat) for _ in shapes) for shapes in self.sub._shapes]
+
+    def _bind(self, arena, model, requires_grad):
+        """Make every parameter of `model` a Parameter over its block of `arena` (no copy; the name and the state_dict
+        key are kept) and record the arena on the model, so a module binding built for it trains the arena in place."""
+        import torch.nn as nn
+        names = dict((id(p), name) for name, p in model.named_parameters())
+        for p, view in zip(arena.module_params(model), arena.param_views()):
+            owner, _, attr = names[id(p)].rpartition('.')
+            setattr(model.get_submodule(owner), attr, nn.Parameter(view, requires_grad=requires_grad))
+        arena.bind_module(model)
+        return model
+
+    def attach_engine(self, n_max, x0=None):
+        """The family's engine that steps `sub` in place (dispatch and sync keep moving the same storage, `sub_model`
+        keeps viewing it), sized for batches of up to n_max rows; kept as `engine` across dispatches, with its dropout
+        counter, and rebuilt only for another n_max or -- x0: the first site's layer-0 input buffer, for the further sites
+        of one process -- when that is not the buffer the engine reads."""
+        e = self.engine
+        if e is None or e.n_max != int(n_max) or (x0 is not None and e.x0 is not x0):
+            self.engine = self._new_engine(n_max, x0)
+        return self.engine
 
     # -- partitions ------------------------------------------------------------------
     def sample_partitions(self):
@@ -383,17 +428,20 @@ class DistributedGNNWrapper(_DistributedWrapper):
                  comm=None, n_max=None, seed=0):
         from .modules import GCN
         self._GCN = GCN                  # (imported here, not in _new_model: that also runs under torch.device('meta'))
+        self.seed = int(seed)
         _DistributedWrapper.__init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm)
         # the fused step's dropout stream of this rank: the same as the engine path's below
-        self.sub_model.set_dropout_seed(seed * 131 + self.rank)
+        self.sub_model.set_dropout_seed(self.seed * 131 + self.rank)
         if self.base_model is not None:
             # utils.evaluate(base_model, g, ...) runs FullGraphEvaluator on the replica
             self.base_model._gist_full_graph = self._full_graph_evaluator
         self._evaluators = {}
-        self.engine = None
         if n_max is not None:
-            self.engine = SageEngine(self.sub_dims, args.use_layernorm, args.dropout, n_max,
-                                     device, seed=seed * 131 + self.rank, arena=self.sub)
+            self.attach_engine(n_max)
+
+    def _new_engine(self, n_max, x0):
+        return SageEngine(self.sub_dims, self.args.use_layernorm, self.args.dropout, n_max, self.device,
+                          seed=self.seed * 131 + self.rank, arena=self.sub)
 
     def _dims(self, sub):
         return dims_for(self.in_feats, self.H, self.n_classes, self.L, split_output=sub,
@@ -406,19 +454,6 @@ class DistributedGNNWrapper(_DistributedWrapper):
         import torch.nn.functional as F
         return self._GCN(self.in_feats, self.H, self.n_classes, self.L, F.relu, self.args.dropout, self.args.use_layernorm,
                    False, sub, self.S if sub else 1, True)
-
-    def _module_params(self, gcn):
-        return [(l.linear.weight.data, l.linear.bias.data) for l in gcn.layers]
-
-    def _bind(self, arena, gcn, requires_grad):
-        """Make every parameter of `gcn` a Parameter over its block of `arena` (no copy) and record the arena on the
-        model, so a ModuleEngine built for it trains the arena in place."""
-        import torch.nn as nn
-        for k, layer in enumerate(gcn.layers):
-            layer.linear.weight = nn.Parameter(arena.W[k], requires_grad=requires_grad)
-            layer.linear.bias = nn.Parameter(arena.b[k], requires_grad=requires_grad)
-        arena.bind_module(gcn)
-        return gcn
 
     def _site_plan(self, part, site):
         idx = [layer[site][0] for layer in part]
@@ -458,6 +493,12 @@ class DistributedGATWrapper(_DistributedWrapper):
     `args.head_merge` = 'cat' (absent: 'mean'): the hidden layers concatenate their heads, so layer k > 0 reads
     nh * H columns (the sub-GAT nh * h) and its fc columns -- the last layer's too -- are the previous boundary's indices
     expanded over the previous layer's heads, h'*H + idx_k-1, as the rows are.  Rows and attn columns are the same."""
+    TRAIN = 'train_gat'
+    STEP_PATH = 'engine'
+    PHASES = 'bind_gat'
+    SHARES_X0 = True            # (a GAT's first layer takes the full input width and the step only reads X_0)
+    MODULE_ON_CPU = True        # (the GAT's layers run on the CPU too: train_gat has never refused a CPU wrapper there)
+    EVAL_PATHS = {'layers': None, 'blocked': ('gat_eval', 'GATFullGraphEvaluator')}
 
     def __init__(self, args, g, in_feats, n_classes, device, *, base_init=_UNSET, blocks=None, comm=None, seed=0):
         from .modules import GAT
@@ -466,16 +507,9 @@ class DistributedGATWrapper(_DistributedWrapper):
         self.merge = getattr(args, 'head_merge', 'mean')
         _DistributedWrapper.__init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm)
         self.n_bound = len(self.sub_dims) - 1                 # hidden boundaries that take a partition
-        self.engine = None                                    # attach_engine: train_gat(..., host_path='engine')
 
-    def attach_engine(self, n_max, x0=None):
-        """The GATEngine that steps `sub` in place (adopted: dispatch and sync keep moving the same storage, `sub_model`
-        keeps viewing it), sized for batches of up to n_max rows; kept as `engine`.  x0: the first site's layer-0 input
-        buffer, for the further sites of one process (GATEngine)."""
-        e = self.engine
-        if e is None or e.n_max != int(n_max) or (x0 is not None and e.X0 is not x0):
-            self.engine = GATEngine(arena=self.sub, n_max=n_max, x0=x0)
-        return self.engine
+    def _new_engine(self, n_max, x0):
+        return GATEngine(arena=self.sub, n_max=n_max, x0=x0)
 
     def _dims(self, sub):
         return gat_dims(self.in_feats, self.h if sub else self.H, self.n_classes, self.L, self.nh, self.merge)
@@ -530,6 +564,9 @@ class DistributedGraphSAGEWrapper(_DistributedWrapper):
     `blocks` given (a test double, or HipBlocks()): one mover call per (site, layer, tensor).  Not given, on a GPU: the
     grouped mover -- one gist_arena_moves_f32 launch per dispatch and per sync (_DistributedWrapper)."""
     GROUPED = True
+    TRAIN = 'train_graphsage'
+    PHASES = 'bind_graphsage'
+    EVAL_PATHS = {'layers': None, 'rows': ('graphsage_eval', 'GraphSAGEFullGraphEvaluator')}
 
     def __init__(self, args, g, in_feats, n_classes, device, *, base_init=_UNSET, blocks=None, comm=None, seed=0):
         from .arena import GraphSAGEArena, graphsage_dims
@@ -538,18 +575,12 @@ class DistributedGraphSAGEWrapper(_DistributedWrapper):
         self.use_pp = bool(getattr(args, 'use_pp', False))
         self.seed = int(seed)
         _DistributedWrapper.__init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm)
-        self.engine = None                                    # attach_engine: train_graphsage(..., host_path='step')
 
-    def attach_engine(self, n_max, x0=None):
-        """The GraphSAGEEngine that steps `sub` in place (dispatch and sync keep moving the same storage, `sub_model`
-        keeps viewing it), sized for batches of up to n_max rows; kept as `engine` across dispatches, with its dropout
-        counter.  x0 is accepted for the GAT wrapper's call shape: every GraphSAGE engine owns its layer-0 buffer."""
+    def _new_engine(self, n_max, x0):
+        # (x0 is never given: every GraphSAGE engine owns its layer-0 buffer, which a step with dropout drops in place)
         from .graphsage_engine import GraphSAGEEngine
-        e = self.engine
-        if e is None or e.n_max != int(n_max):
-            self.engine = GraphSAGEEngine(self.sub_dims, self.args.dropout, n_max, self.device,
-                                          seed=self.seed * 131 + self.rank, use_pp=self.use_pp, arena=self.sub)
-        return self.engine
+        return GraphSAGEEngine(self.sub_dims, self.args.dropout, n_max, self.device, seed=self.seed * 131 + self.rank,
+                               use_pp=self.use_pp, arena=self.sub)
 
     def _dims(self, sub):
         return self._graphsage_dims(self.in_feats, self.h if sub else self.H, self.n_classes, self.L)
@@ -561,28 +592,6 @@ class DistributedGraphSAGEWrapper(_DistributedWrapper):
         import torch.nn.functional as F
         return self._GraphSAGE(self.in_feats, self.h if sub else self.H, self.n_classes, self.L, F.relu,
                                self.args.dropout, self.use_pp)
-
-    def _module_params(self, model):
-        per_layer = []
-        for layer in model.layers:
-            group = [layer.linear.weight.data, layer.linear.bias.data]
-            if isinstance(layer.lynorm, torch.nn.LayerNorm):
-                group += [layer.lynorm.weight.data, layer.lynorm.bias.data]
-            per_layer.append(tuple(group))
-        return per_layer
-
-    def _bind(self, arena, model, requires_grad):
-        """Make every parameter of `model` a Parameter over its block of `arena` (no copy) and record the arena on the
-        model, so a GraphSAGEModuleEngine built for it trains the arena in place."""
-        import torch.nn as nn
-        for k, layer in enumerate(model.layers):
-            layer.linear.weight = nn.Parameter(arena.W[k], requires_grad=requires_grad)
-            layer.linear.bias = nn.Parameter(arena.b[k], requires_grad=requires_grad)
-            if arena.gamma[k] is not None:
-                layer.lynorm.weight = nn.Parameter(arena.gamma[k], requires_grad=requires_grad)
-                layer.lynorm.bias = nn.Parameter(arena.beta[k], requires_grad=requires_grad)
-        arena.bind_module(model)
-        return model
 
     _site_plan = DistributedGNNWrapper._site_plan             # (the same split: the vectors share idx_k)
 
@@ -614,6 +623,15 @@ class DistributedBaselineGCNWrapper(_DistributedWrapper):
     [n, H].  `blocks` given (a test double, or HipBlocks()): one mover call per (site, layer, tensor).
     Not given, on a GPU: the grouped mover -- one gist_arena_moves_f32 launch per dispatch and per sync."""
     GROUPED = True
+    TRAIN = 'train_baseline_gcn'
+    SHARES_X0 = True            # (the first layer takes the full input width and the step never writes X_0, DESIGN.md §11.1)
+
+    @staticmethod
+    def _module_iterator(it):
+        from .sampler import ClusterIter, EngineClusterIter
+        if not isinstance(it, ClusterIter) or isinstance(it, EngineClusterIter):
+            raise ValueError("gist_amd: train_baseline_gcn(host_path='module') needs a gist_amd.sampler.ClusterIter as "
+                             "cluster_iterator (got %s)" % type(it).__name__)
 
     def __init__(self, args, g, in_feats, n_classes, device, *, base_init=_UNSET, blocks=None, comm=None, seed=0):
         from .arena import BaselineGCNArena, baseline_gcn_dims
@@ -623,19 +641,11 @@ class DistributedBaselineGCNWrapper(_DistributedWrapper):
         _DistributedWrapper.__init__(self, args, g, in_feats, n_classes, device, base_init, blocks, comm)
         # the fused tail's dropout stream of this rank: the same as the engine's below
         self.sub_model.set_dropout_seed(self.seed * 131 + self.rank)
-        self.engine = None                                    # attach_engine: train_baseline_gcn(..., host_path='step')
 
-    def attach_engine(self, n_max, x0=None):
-        """The BaselineGCNEngine that steps `sub` in place (dispatch and sync keep moving the same storage, `sub_model`
-        keeps viewing it), sized for batches of up to n_max rows; kept as `engine` across dispatches, with its dropout
-        counter, and rebuilt only for another n_max.  x0: the first site's layer-0 input buffer, for the further sites
-        of one process (BaselineGCNEngine)."""
+    def _new_engine(self, n_max, x0):
         from .baseline_gcn_engine import BaselineGCNEngine
-        e = self.engine
-        if e is None or e.n_max != int(n_max):
-            self.engine = BaselineGCNEngine(self.sub_dims, self.args.use_layernorm, self.args.dropout, n_max, self.device,
-                                            seed=self.seed * 131 + self.rank, arena=self.sub, x0=x0)
-        return self.engine
+        return BaselineGCNEngine(self.sub_dims, self.args.use_layernorm, self.args.dropout, n_max, self.device,
+                                 seed=self.seed * 131 + self.rank, arena=self.sub, x0=x0)
 
     def _dims(self, sub):
         return self._baseline_gcn_dims(self.in_feats, self.h if sub else self.H, self.n_classes, self.L)
@@ -647,19 +657,6 @@ class DistributedBaselineGCNWrapper(_DistributedWrapper):
         import torch.nn.functional as F
         return self._BaselineGCN(self.in_feats, self.h if sub else self.H, self.n_classes, self.L, F.relu,
                                  self.args.dropout, self.args.use_layernorm)
-
-    def _module_params(self, model):
-        return [(layer.weight.data, layer.bias.data) for layer in model.layers]
-
-    def _bind(self, arena, model, requires_grad):
-        """Make every parameter of `model` a Parameter over its block of `arena` (no copy) and record the arena on the
-        model."""
-        import torch.nn as nn
-        for k, layer in enumerate(model.layers):
-            layer.weight = nn.Parameter(arena.W[k], requires_grad=requires_grad)
-            layer.bias = nn.Parameter(arena.b[k], requires_grad=requires_grad)
-        arena.bind_module(model)
-        return model
 
     def _site_plan(self, part, site):
         idx = [layer[site][0] for layer in part]
@@ -737,6 +734,19 @@ def _run_schedule(models, args, cluster_iterator, log, at_dispatch, step, before
                 test_accs=test_accs, trn_losses=trn_losses)
 
 
+def _arena_loop(models):
+    """The (at_dispatch, before_eval) of every loop whose sites step their sub arena through their wrapper's engine."""
+    def at_dispatch():
+        for m in models:
+            m.sub.reset_optimizer()
+
+    def before_eval():                               # (the device is idle: every extraction so far was complete)
+        for m in models:
+            if m.engine is not None:
+                m.engine.check_extract()
+    return at_dispatch, before_eval
+
+
 def train(ist_model, args, cluster_iterator, evaluator=None, log=print):
     """The GIST loop, cluster_gcn_ist_distrib.py:370-479, on the engine fast path.
 
@@ -753,10 +763,7 @@ def train(ist_model, args, cluster_iterator, evaluator=None, log=print):
     for m in models:
         if m.engine is not None:
             m.engine.prefetch = len(models) == 1
-
-    def at_dispatch():
-        for m in models:
-            m.sub.reset_optimizer()
+    at_dispatch, before_eval = _arena_loop(models)
 
     def step(si, batch):
         engine = models[si].engine
@@ -764,15 +771,68 @@ def train(ist_model, args, cluster_iterator, evaluator=None, log=print):
             cluster_iterator.fill_features(batch, engine)
         return engine.train_step(batch, args.lr, args.weight_decay).clone()
 
-    def before_eval():                               # (the device is idle: every extraction so far was complete)
-        for m in models:
-            if m.engine is not None:
-                m.engine.check_extract()
-
     def accuracies():
         return evaluator.accuracy('val_mask'), evaluator.accuracy('test_mask')
     return _run_schedule(models, args, cluster_iterator, log, at_dispatch, step, before_eval,
                          accuracies if evaluator is not None else None)
+
+
+def _train(family, ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log, host_path, eval_path):
+    """The one body of train_gat, train_graphsage and train_baseline_gcn.  family: the wrapper class, whose facts say
+    which host paths and evaluators there are and what each asks of the device and of the iterator; every refusal is a
+    ValueError raised before anything touches the device."""
+    from .utils import evaluate
+    who = family.TRAIN
+    models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
+    if host_path not in ('module', family.STEP_PATH) + (('phases',) if family.PHASES else ()):
+        raise ValueError("gist_amd: %s host_path must be 'module' or '%s'%s (got %r)" % (
+            who, family.STEP_PATH, ", or 'phases' for the module loop bound to the fused step" if family.PHASES else '',
+            host_path))
+    if eval_path not in family.EVAL_PATHS:
+        raise ValueError("gist_amd: %s eval_path must be %s (got %r)"
+                         % (who, ' or '.join(repr(p) for p in family.EVAL_PATHS), eval_path))
+    dev = torch.device(models[0].device)
+    if dev.type != 'cuda' and not (host_path == 'module' and family.MODULE_ON_CPU):
+        runs = {'module': "the model's forward on torch.ops.gist.*", 'phases': "the fused step's phase calls"}
+        raise ValueError("gist_amd: %s(host_path=%r) runs %s, which is GPU-only (the wrapper is on %s); %s" % (
+            who, host_path, runs.get(host_path, 'the fused step'), dev,
+            "use host_path='module' there" if family.MODULE_ON_CPU else 'there is no CPU fallback'))
+    if host_path == 'module':
+        family._module_iterator(cluster_iterator)
+        steps = _module_steps(models, args, cluster_iterator)
+    else:
+        _check_iterator(family, models[0], cluster_iterator, host_path)
+        build = _phase_steps if host_path == 'phases' else _engine_steps
+        steps = build(family, models, args, cluster_iterator)
+    evaluator = family.EVAL_PATHS[eval_path]
+    if evaluator is not None and models[0].base_model is not None:
+        import importlib
+        getattr(importlib.import_module('.' + evaluator[0], __package__), evaluator[1]).attach(
+            models[0].base_model, arena=models[0].base)
+
+    def accuracies():
+        base_model = models[0].base_model
+        return evaluate(base_model, g, labels, val_mask), evaluate(base_model, g, labels, test_mask)
+    return _run_schedule(models, args, cluster_iterator, lambda line: log(line, flush=True), *steps,
+                         accuracies=accuracies)
+
+
+def _check_iterator(family, model, it, host_path):
+    """What the one-call path (an EngineClusterIter) and the phase path (a ClusterIter that feeds the device) ask of the
+    iterator, and -- a family with use_pp -- that the iterator's is the wrapper's."""
+    from .sampler import ClusterIter, EngineClusterIter
+    who = "gist_amd: %s(host_path=%r)" % (family.TRAIN, host_path)
+    if host_path != 'phases':
+        if not isinstance(it, EngineClusterIter):
+            raise ValueError("%s needs a gist_amd.sampler.EngineClusterIter as cluster_iterator (got %s): it describes "
+                             "the batches the step extracts on the device" % (who, type(it).__name__))
+    elif not isinstance(it, ClusterIter):
+        raise ValueError("%s needs a gist_amd.sampler.ClusterIter as cluster_iterator (got %s)" % (who, type(it).__name__))
+    if model.use_pp is not None and bool(it.use_pp) != model.use_pp:
+        raise ValueError('gist_amd: the iterator\'s use_pp (%s) is not the wrapper\'s (%s)' % (it.use_pp, model.use_pp))
+    if host_path == 'phases' and not (it.feed_precalculated() if model.use_pp else it.feed()):
+        raise ValueError("%s needs an iterator that describes its batches for on-device extraction (on the GPU, parts "
+                         "that partition the train graph%s)" % (who, '' if model.use_pp is not None else ', no use_pp'))
 
 
 def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module',
@@ -781,13 +841,13 @@ def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask,
     masked gist_amd.nn.CrossEntropyLoss, a new gist_amd.optim.Adam at every dispatch point, `evaluate(base_model, g,
     ...)` on rank 0 (`g` on the device).  The schedule is the SAGE one (_run_schedule).
 
-    host_path='engine': every site's step is ONE gist_gat_step call on its wrapper's GATEngine (_gat_engine_steps)
+    host_path='engine': every site's step is ONE gist_gat_step call on its wrapper's GATEngine (_engine_steps)
     instead; `cluster_iterator` is then an EngineClusterIter.  Same launches in the same order on the same layouts:
     losses, arenas and accuracies are those of 'module' bit for bit.
 
     host_path='phases': the loop body of 'module', statement for statement, with every `sub_model` bound to the
     iterator (gist_amd.module_engine.bind_gat): the forward, `loss.backward()` and `optimizer.step()` are the three
-    gist_gat_step_phase calls on the wrapper's GATEngine (_gat_phase_steps).  `cluster_iterator` is a plain ClusterIter
+    gist_gat_step_phase calls on the wrapper's GATEngine (_phase_steps).  `cluster_iterator` is a plain ClusterIter
     on the GPU.  Bit for bit 'module' again.
 
     `ist_model` is this rank's DistributedGATWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites then
@@ -796,29 +856,59 @@ def train_gat(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask,
     layer).  The step losses stay on the device (the reference's
     per-step `float(loss)` would wait for it every step); each evaluation averages them.  Returns total_time,
     per-site step losses, events, accuracies and the mean training loss per evaluation."""
-    from .utils import evaluate
-    models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
-    if host_path not in ('module', 'engine', 'phases'):
-        raise ValueError("gist_amd: train_gat host_path must be 'module' or 'engine', or 'phases' for the module loop "
-                         "bound to the fused step (got %r)" % (host_path,))
-    if eval_path not in ('layers', 'blocked'):
-        raise ValueError("gist_amd: train_gat eval_path must be 'layers' or 'blocked' (got %r)" % (eval_path,))
-    if eval_path == 'blocked' and models[0].base_model is not None:
-        from .gat_eval import GATFullGraphEvaluator
-        GATFullGraphEvaluator.attach(models[0].base_model, arena=models[0].base)
-    steps = {'module': _module_steps, 'engine': _gat_engine_steps, 'phases': _gat_phase_steps}[host_path]
-    at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
+    return _train(DistributedGATWrapper, ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log,
+                  host_path, eval_path)
 
-    def accuracies():
-        base_model = models[0].base_model
-        return evaluate(base_model, g, labels, val_mask), evaluate(base_model, g, labels, test_mask)
-    return _run_schedule(models, args, cluster_iterator, lambda line: log(line, flush=True), at_dispatch, step,
-                         before_eval, accuracies)
+
+def train_graphsage(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module',
+                    eval_path='layers'):
+    """The GIST loop (cluster_gcn_ist_distrib.py:370-479, _run_schedule) for the GraphSAGE family.
+
+    host_path='module': the reference's loop body on `ist_model.sub_model` -- masked gist_amd.nn.CrossEntropyLoss, a
+    new gist_amd.optim.Adam at every dispatch point; `cluster_iterator` is a ClusterIter (use_pp as the wrapper's).
+    GPU-only, like 'step': the model's forward runs on torch.ops.gist.* (spmm_sum, matmul, layer_norm_affine), which
+    are registered for the GPU alone, and the project has no CPU fallback.  With `blocks` and `comm` doubles the wrapper
+    itself -- construction, dispatch, sync -- runs on the CPU; a training loop does not.
+    host_path='step': every site's step is ONE gist_graphsage_step call on its wrapper's GraphSAGEEngine, which steps
+    `sub` in place; `cluster_iterator` is an EngineClusterIter (use_pp as the wrapper's).  `sub.reset_optimizer()` is
+    the fresh optimiser of a dispatch point; an engine's dropout counter runs on across dispatches.  The dropout masks
+    are the step's counter-based generator's, not torch's: with dropout 0 the two paths compute the same function.
+    host_path='phases': the loop body of 'module', statement for statement, with every `sub_model` bound to the iterator
+    (gist_amd.module_engine.bind_graphsage): the forward, `loss.backward()` and `optimizer.step()` are the three
+    gist_graphsage_step_phase calls on the wrapper's GraphSAGEEngine (_phase_steps).  `cluster_iterator` is a
+    plain ClusterIter on the GPU (use_pp as the wrapper's).  Bit for bit 'step'.
+
+    `ist_model` is this rank's DistributedGraphSAGEWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites
+    then run in this process, the partition sampled once per dispatch.  eval_path='rows': rank 0's `base_model` is
+    evaluated by a gist_amd.graphsage_eval.GraphSAGEFullGraphEvaluator over the base arena ('layers': its own forward).
+    Returns what train_gat returns."""
+    return _train(DistributedGraphSAGEWrapper, ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log,
+                  host_path, eval_path)
+
+
+def train_baseline_gcn(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module'):
+    """The GIST loop (cluster_gcn_ist_distrib.py:370-479, _run_schedule) for the BaselineGCN family.
+
+    host_path='module': the reference's loop body on `ist_model.sub_model` -- masked gist_amd.nn.CrossEntropyLoss, a
+    new gist_amd.optim.Adam at every dispatch point; `cluster_iterator` is a ClusterIter.  GPU-only, like 'step': the
+    model's forward runs on torch.ops.gist.*, which are registered for the GPU alone, and the project has no CPU
+    fallback.  With `blocks` and `comm` doubles the wrapper itself -- construction, dispatch, sync -- runs on the CPU; a
+    training loop does not.
+    host_path='step': every site's step is ONE gist_baseline_gcn_step call on its wrapper's BaselineGCNEngine, which
+    steps `sub` in place; `cluster_iterator` is an EngineClusterIter.  `sub.reset_optimizer()` is the fresh optimiser of
+    a dispatch point; an engine's dropout counter runs on across dispatches (_engine_steps).
+    The family has no phase calls: there is no 'phases'.
+
+    `ist_model` is this rank's DistributedBaselineGCNWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites
+    then run in this process, the partition sampled once per dispatch.  Rank 0's `base_model` is scored by
+    utils.evaluate: the model's own full-graph forward.  Returns what train_graphsage returns."""
+    return _train(DistributedBaselineGCNWrapper, ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log,
+                  host_path, 'layers')
 
 
 def _module_steps(models, args, cluster_iterator):
-    """(at_dispatch, step, before_eval) of the module loops (train_gat, train_graphsage) on the drop-in classes: the
-    reference's loop body on every site's `sub_model`."""
+    """(at_dispatch, step, before_eval) of the module loops (train_gat, train_graphsage, train_baseline_gcn) on the
+    drop-in classes: the reference's loop body on every site's `sub_model`."""
     from .nn import CrossEntropyLoss
     from .optim import Adam
     dev = models[0].device
@@ -845,278 +935,57 @@ def _module_steps(models, args, cluster_iterator):
     return at_dispatch, step, lambda: None
 
 
-def _gat_phase_steps(models, args, cluster_iterator):
-    """train_gat's (at_dispatch, step, before_eval) for host_path='phases': _module_steps' loop body, with every
-    site's sub_model bound to the iterator first.  Each wrapper's GATEngine steps its sub arena in place (attach_engine;
-    the further sites of one process read the first engine's layer-0 input buffer), so dispatch and sync keep moving
-    the storage the step trains."""
-    from .module_engine import bind_gat
-    from .sampler import ClusterIter
-    if models[0].device.type != 'cuda':
-        raise ValueError("gist_amd: train_gat(host_path='phases') runs the fused step's phase calls, which are GPU-only "
-                         "(the wrapper is on %s); use host_path='module' there" % (models[0].device,))
+def _phase_steps(family, models, args, cluster_iterator):
+    """(at_dispatch, step, before_eval) for host_path='phases': _module_steps' loop body, with every site's sub_model
+    bound to the iterator first (family.PHASES: module_engine.bind_gat, bind_graphsage).  Each wrapper's engine
+    (attach_engine: the seed and the dropout counter of the one-call path) steps its sub arena in place, so dispatch and
+    sync keep writing the storage the step trains and nothing is re-homed; the fresh gist_amd.optim.Adam of a dispatch
+    point brings fresh flat moments and its own step count.  S sites in one process: with SHARES_X0 the further engines
+    read the first one's layer-0 input buffer, else every forward phase extracts the batch into its own engine's."""
+    from . import module_engine
+    bind, share = getattr(module_engine, family.PHASES), family.SHARES_X0
     it = cluster_iterator
-    if not isinstance(it, ClusterIter) or not it.feed():
-        raise ValueError("gist_amd: train_gat(host_path='phases') needs a gist_amd.sampler.ClusterIter that describes its "
-                         "batches for on-device extraction (on the GPU, no use_pp; got %s)" % type(it).__name__)
     first = None
     for m in models:
-        engine = m.attach_engine(it.n_max, x0=None if first is None else first.X0)
+        engine = m.attach_engine(it.n_max, x0=first.x0 if (share and first is not None) else None)
         first = engine if first is None else first
-        bind_gat(m.sub_model, it)
-    at_dispatch, step, _ = _module_steps(models, args, cluster_iterator)
-
-    def before_eval():                               # (the device is idle: every extraction so far was complete)
-        for m in models:
-            m.engine.check_extract()
-    return at_dispatch, step, before_eval
+        bind(m.sub_model, it)
+    at_dispatch, step, _ = _module_steps(models, args, it)
+    return at_dispatch, step, _arena_loop(models)[1]
 
 
-def _gat_engine_steps(models, args, cluster_iterator):
-    """train_gat's (at_dispatch, step, before_eval) on the fused step: one GATEngine per wrapper over its sub arena.
-
-    One site in the process (the distributed run): the optimiser launch of a step extracts the next batch of the epoch
-    beside it, as in train().  S sites in one process: a GAT's first layer takes the full input width, so the extracted
-    batch -- CSR, reversed CSR, labels, layer 0's input rows -- is the same for every site.  All engines are bound to
-    the iterator's batcher and read ONE layer-0 input buffer, the first engine's; the first site's step extracts the
-    batch, the others step on the buffers as they stand."""
-    from .sampler import EngineClusterIter
-    if models[0].device.type != 'cuda':
-        raise ValueError("gist_amd: train_gat(host_path='engine') runs the fused step gist_gat_step, which is GPU-only "
-                         "(the wrapper is on %s); use host_path='module' there" % (models[0].device,))
-    if not isinstance(cluster_iterator, EngineClusterIter):
-        raise ValueError("gist_amd: train_gat(host_path='engine') needs a gist_amd.sampler.EngineClusterIter as "
-                         "cluster_iterator (got %s): it describes the batches the step extracts on the device"
-                         % type(cluster_iterator).__name__)
-    it = cluster_iterator
-    first = models[0].attach_engine(it.n_max)
-    if it.engine is not first:
-        it.bind(first)
-    for m in models[1:]:
-        engine = m.attach_engine(it.n_max, x0=first.X0)
-        if engine.plan is None or engine._plan_keep[0] is not it.batcher:
-            engine.attach_batcher(it.batcher)
-    for m in models:
-        m.engine.prefetch = len(models) == 1
-
-    def at_dispatch():
-        for m in models:
-            m.sub.reset_optimizer()
-
-    def step(si, batch):
-        return models[si].engine.train_step(batch, args.lr, args.weight_decay)[0].clone()      # (0-dim, as 'module')
-
-    def before_eval():                               # (the device is idle: every extraction so far was complete)
-        for m in models:
-            m.engine.check_extract()
-    return at_dispatch, step, before_eval
-
-
-def train_graphsage(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module',
-                    eval_path='layers'):
-    """The GIST loop (cluster_gcn_ist_distrib.py:370-479, _run_schedule) for the GraphSAGE family.
-
-    host_path='module': the reference's loop body on `ist_model.sub_model` -- masked gist_amd.nn.CrossEntropyLoss, a
-    new gist_amd.optim.Adam at every dispatch point; `cluster_iterator` is a ClusterIter (use_pp as the wrapper's).
-    GPU-only, like 'step': the model's forward runs on torch.ops.gist.* (spmm_sum, matmul, layer_norm_affine), which
-    are registered for the GPU alone, and the project has no CPU fallback.  With `blocks` and `comm` doubles the wrapper
-    itself -- construction, dispatch, sync -- runs on the CPU; a training loop does not.
-    host_path='step': every site's step is ONE gist_graphsage_step call on its wrapper's GraphSAGEEngine, which steps
-    `sub` in place; `cluster_iterator` is an EngineClusterIter (use_pp as the wrapper's).  `sub.reset_optimizer()` is
-    the fresh optimiser of a dispatch point; an engine's dropout counter runs on across dispatches.  The dropout masks
-    are the step's counter-based generator's, not torch's: with dropout 0 the two paths compute the same function.
-    host_path='phases': the loop body of 'module', statement for statement, with every `sub_model` bound to the iterator
-    (gist_amd.module_engine.bind_graphsage): the forward, `loss.backward()` and `optimizer.step()` are the three
-    gist_graphsage_step_phase calls on the wrapper's GraphSAGEEngine (_graphsage_phase_steps).  `cluster_iterator` is a
-    plain ClusterIter on the GPU (use_pp as the wrapper's).  Bit for bit 'step'.
-
-    `ist_model` is this rank's DistributedGraphSAGEWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites
-    then run in this process, the partition sampled once per dispatch.  eval_path='rows': rank 0's `base_model` is
-    evaluated by a gist_amd.graphsage_eval.GraphSAGEFullGraphEvaluator over the base arena ('layers': its own forward).
-    Returns what train_gat returns."""
-    from .utils import evaluate
-    models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
-    if host_path not in ('module', 'step', 'phases'):
-        raise ValueError("gist_amd: train_graphsage host_path must be 'module' or 'step', or 'phases' for the module loop "
-                         "bound to the fused step (got %r)" % (host_path,))
-    if eval_path not in ('layers', 'rows'):
-        raise ValueError("gist_amd: train_graphsage eval_path must be 'layers' or 'rows' (got %r)" % (eval_path,))
-    if host_path == 'module' and torch.device(models[0].device).type != 'cuda':
-        raise ValueError("gist_amd: train_graphsage(host_path='module') runs the model's forward on torch.ops.gist.*, "
-                         "which is GPU-only (the wrapper is on %s); there is no CPU fallback" % (models[0].device,))
-    if eval_path == 'rows' and models[0].base_model is not None:
-        from .graphsage_eval import GraphSAGEFullGraphEvaluator
-        GraphSAGEFullGraphEvaluator.attach(models[0].base_model, arena=models[0].base)
-    steps = {'module': _module_steps, 'step': _graphsage_engine_steps, 'phases': _graphsage_phase_steps}[host_path]
-    at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
-
-    def accuracies():
-        base_model = models[0].base_model
-        return evaluate(base_model, g, labels, val_mask), evaluate(base_model, g, labels, test_mask)
-    return _run_schedule(models, args, cluster_iterator, lambda line: log(line, flush=True), at_dispatch, step,
-                         before_eval, accuracies)
-
-
-def _graphsage_phase_steps(models, args, cluster_iterator):
-    """train_graphsage's (at_dispatch, step, before_eval) for host_path='phases': _module_steps' loop body, with every
-    site's sub_model bound to the iterator first (module_engine.bind_graphsage).  Each wrapper's GraphSAGEEngine
-    (attach_engine: the seed and the dropout counter of 'step') steps its sub arena in place, so dispatch and sync keep
-    writing the storage the step trains and nothing is re-homed; the fresh gist_amd.optim.Adam of a dispatch point
-    brings fresh flat moments and its own step count.  S sites in one process: every forward phase extracts the batch
-    into its own engine's Z_0 (GraphSAGEModuleEngine)."""
-    from .module_engine import bind_graphsage
-    from .sampler import ClusterIter
-    if torch.device(models[0].device).type != 'cuda':
-        raise ValueError("gist_amd: train_graphsage(host_path='phases') runs the fused step's phase calls, which are "
-                         "GPU-only (the wrapper is on %s); there is no CPU fallback" % (models[0].device,))
-    it = cluster_iterator
-    if not isinstance(it, ClusterIter):
-        raise ValueError("gist_amd: train_graphsage(host_path='phases') needs a gist_amd.sampler.ClusterIter as "
-                         "cluster_iterator (got %s)" % type(it).__name__)
-    if bool(it.use_pp) != models[0].use_pp:
-        raise ValueError('gist_amd: the iterator\'s use_pp (%s) is not the wrapper\'s (%s)' % (it.use_pp, models[0].use_pp))
-    if not (it.feed_precalculated() if it.use_pp else it.feed()):
-        raise ValueError("gist_amd: train_graphsage(host_path='phases') needs an iterator that describes its batches for "
-                         "on-device extraction (on the GPU, parts that partition the train graph)")
-    for m in models:
-        m.attach_engine(it.n_max)
-        bind_graphsage(m.sub_model, it)
-    at_dispatch, step, _ = _module_steps(models, args, cluster_iterator)
-
-    def before_eval():                               # (the device is idle: every extraction so far was complete)
-        for m in models:
-            m.engine.check_extract()
-    return at_dispatch, step, before_eval
-
-
-def _graphsage_engine_steps(models, args, cluster_iterator):
-    """train_graphsage's (at_dispatch, step, before_eval) on the fused step: one GraphSAGEEngine per wrapper over its sub
-    arena.
+def _engine_steps(family, models, args, cluster_iterator):
+    """(at_dispatch, step, before_eval) on the fused step: one engine per wrapper over its sub arena (attach_engine).
 
     One site in the process (the distributed run): the optimiser launch of a step extracts the next batch of the epoch
     beside it, as in train().  S sites in one process: the first site's step extracts the batch -- CSR, reversed CSR,
-    labels -- into the iterator's batch buffers, which every engine's plan points into; layer 0's input is an engine's
-    own buffer (a training step with dropout leaves dropped values in it), so every further site gathers the batch's
-    features into its Z_0 first (fill_features).  Batch.z0_dropped then speaks of the engine that stepped last, not of
-    the buffer about to be read: it is cleared with the refill."""
-    from .sampler import EngineClusterIter
-    if models[0].device.type != 'cuda':
-        raise ValueError("gist_amd: train_graphsage(host_path='step') runs the fused step gist_graphsage_step, which is "
-                         "GPU-only (the wrapper is on %s); use host_path='module' there" % (models[0].device,))
-    if not isinstance(cluster_iterator, EngineClusterIter):
-        raise ValueError("gist_amd: train_graphsage(host_path='step') needs a gist_amd.sampler.EngineClusterIter as "
-                         "cluster_iterator (got %s): it describes the batches the step extracts on the device"
-                         % type(cluster_iterator).__name__)
-    it = cluster_iterator
-    if bool(it.use_pp) != models[0].use_pp:
-        raise ValueError('gist_amd: the iterator\'s use_pp (%s) is not the wrapper\'s (%s)' % (it.use_pp, models[0].use_pp))
+    labels -- into the iterator's batch buffers, which every engine's plan points into.  Layer 0's input rows, by the
+    family's SHARES_X0: where the first layer of every sub-model takes the full input width and the step only reads X_0
+    (GAT, BaselineGCN), all engines read ONE buffer, the first engine's, and the further sites step on the buffers as
+    they stand; where the buffer is an engine's own (GraphSAGE: a training step with dropout leaves dropped values in it),
+    every further site gathers the batch's features into its own first (fill_features).  Batch.z0_dropped then speaks of
+    the engine that stepped last, not of the buffer about to be read: it is cleared with the refill."""
+    it, share = cluster_iterator, family.SHARES_X0
     first = models[0].attach_engine(it.n_max)
     if it.engine is not first:
         it.bind(first)
     for m in models[1:]:
-        engine = m.attach_engine(it.n_max)
+        engine = m.attach_engine(it.n_max, x0=first.x0 if share else None)
         if engine.plan is None or engine._plan_keep[0] is not it.batcher:
             engine.attach_batcher(it.batcher)
     for m in models:
         m.engine.prefetch = len(models) == 1
-
-    def at_dispatch():
-        for m in models:
-            m.sub.reset_optimizer()
-
-    def step(si, batch):
-        engine = models[si].engine
-        if si > 0:
-            it.fill_features(batch, engine)
-            batch.z0_dropped = False
-        return engine.train_step(batch, args.lr, args.weight_decay)[0].clone()      # (0-dim, as 'module')
-
-    def before_eval():                               # (the device is idle: every extraction so far was complete)
-        for m in models:
-            m.engine.check_extract()
-    return at_dispatch, step, before_eval
-
-
-def train_baseline_gcn(ist_model, args, g, cluster_iterator, labels, val_mask, test_mask, log=print, host_path='module'):
-    """The GIST loop (cluster_gcn_ist_distrib.py:370-479, _run_schedule) for the BaselineGCN family.
-
-    host_path='module': the reference's loop body on `ist_model.sub_model` -- masked gist_amd.nn.CrossEntropyLoss, a
-    new gist_amd.optim.Adam at every dispatch point; `cluster_iterator` is a ClusterIter.  GPU-only, like 'step': the
-    model's forward runs on torch.ops.gist.*, which are registered for the GPU alone, and the project has no CPU
-    fallback.  With `blocks` and `comm` doubles the wrapper itself -- construction, dispatch, sync -- runs on the CPU; a
-    training loop does not.
-    host_path='step': every site's step is ONE gist_baseline_gcn_step call on its wrapper's BaselineGCNEngine, which
-    steps `sub` in place; `cluster_iterator` is an EngineClusterIter.  `sub.reset_optimizer()` is the fresh optimiser of
-    a dispatch point; an engine's dropout counter runs on across dispatches (_baseline_engine_steps).
-    The family has no phase calls: there is no 'phases'.
-
-    `ist_model` is this rank's DistributedBaselineGCNWrapper, or a LIST of S wrappers sharing a LocalCommGroup: all sites
-    then run in this process, the partition sampled once per dispatch.  Rank 0's `base_model` is scored by
-    utils.evaluate: the model's own full-graph forward.  Returns what train_graphsage returns."""
-    from .utils import evaluate
-    models = list(ist_model) if isinstance(ist_model, (list, tuple)) else [ist_model]
-    if host_path not in ('module', 'step'):
-        raise ValueError("gist_amd: train_baseline_gcn host_path must be 'module' or 'step' (got %r)" % (host_path,))
-    if host_path == 'module' and torch.device(models[0].device).type != 'cuda':
-        raise ValueError("gist_amd: train_baseline_gcn(host_path='module') runs the model's forward on torch.ops.gist.*, "
-                         "which is GPU-only (the wrapper is on %s); there is no CPU fallback" % (models[0].device,))
-    if host_path == 'module':
-        from .sampler import ClusterIter, EngineClusterIter
-        if not isinstance(cluster_iterator, ClusterIter) or isinstance(cluster_iterator, EngineClusterIter):
-            raise ValueError("gist_amd: train_baseline_gcn(host_path='module') needs a gist_amd.sampler.ClusterIter as "
-                             "cluster_iterator (got %s)" % type(cluster_iterator).__name__)
-    steps = {'module': _module_steps, 'step': _baseline_engine_steps}[host_path]
-    at_dispatch, step, before_eval = steps(models, args, cluster_iterator)
-
-    def accuracies():
-        base_model = models[0].base_model
-        return evaluate(base_model, g, labels, val_mask), evaluate(base_model, g, labels, test_mask)
-    return _run_schedule(models, args, cluster_iterator, lambda line: log(line, flush=True), at_dispatch, step,
-                         before_eval, accuracies)
-
-
-def _baseline_engine_steps(models, args, cluster_iterator):
-    """train_baseline_gcn's (at_dispatch, step, before_eval) on the fused step: one BaselineGCNEngine per wrapper over
-    its sub arena.
-
-    One site in the process (the distributed run): the optimiser launch of a step extracts the next batch of the epoch
-    beside it, as in train().  S sites in one process: the first layer of every sub-model takes the full input width
-    and the step never writes X_0, so the extracted batch -- CSR, reversed CSR, labels, layer 0's
-    input rows -- is the same for every site.  All engines are bound to the iterator's batcher and read ONE layer-0
-    input buffer, the first engine's; the first site's step extracts the batch, the others step on the buffers as they
-    stand.  No site gathers features of its own."""
-    from .sampler import EngineClusterIter
-    if torch.device(models[0].device).type != 'cuda':
-        raise ValueError("gist_amd: train_baseline_gcn(host_path='step') runs the fused step gist_baseline_gcn_step, which "
-                         "is GPU-only (the wrapper is on %s); use host_path='module' there" % (models[0].device,))
-    if not isinstance(cluster_iterator, EngineClusterIter):
-        raise ValueError("gist_amd: train_baseline_gcn(host_path='step') needs a gist_amd.sampler.EngineClusterIter as "
-                         "cluster_iterator (got %s): it describes the batches the step extracts on the device"
-                         % type(cluster_iterator).__name__)
-    it = cluster_iterator
-    first = models[0].attach_engine(it.n_max)
-    if it.engine is not first:
-        it.bind(first)
-    for m in models[1:]:
-        if m.engine is not None and m.engine.X[0] is not first.X[0]:
-            m.engine = None                          # (an engine with a layer-0 buffer of its own: rebuilt on the shared one)
-        engine = m.attach_engine(it.n_max, x0=first.X[0])
-        if engine.plan is None or engine._plan_keep[0] is not it.batcher:
-            engine.attach_batcher(it.batcher)
-    for m in models:
-        m.engine.prefetch = len(models) == 1
-
-    def at_dispatch():
-        for m in models:
-            m.sub.reset_optimizer()
+    at_dispatch, before_eval = _arena_loop(models)
 
     def step(si, batch):
         return models[si].engine.train_step(batch, args.lr, args.weight_decay)[0].clone()      # (0-dim, as 'module')
 
-    def before_eval():                               # (the device is idle: every extraction so far was complete)
-        for m in models:
-            m.engine.check_extract()
-    return at_dispatch, step, before_eval
+    def refill_and_step(si, batch):
+        if si > 0:
+            it.fill_features(batch, models[si].engine)
+            batch.z0_dropped = False
+        return step(si, batch)
+    return at_dispatch, step if share else refill_and_step, before_eval
 
 
 def print_results(res, log=print):

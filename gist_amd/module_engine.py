@@ -31,9 +31,10 @@ op-by-op module path of gist_amd/autograd.py, one dispatcher op per layer: the p
 
 That is ONE binding, ModuleEngine, for three families.  What is said above of the GCN holds for gist_amd.modules.GAT on
 gist_gat_step_phase, with `gist::gat_forward` / `gist::gat_backward` as its two ops: GATModuleEngine states only where
-the families differ -- how the engine is built and tied to the iterator, which plan field takes the logits, and that the
-logits are saved on the tape (the last GAT layer's ELU backward reads them).  A GAT gets it only when it was bound
-explicitly: `bind_gat(model, cluster_iterator)`.  An unbound gist_amd.modules.GAT keeps the op-by-op path, the
+the families differ -- how the engine is built, and that the logits are saved on the tape (the last GAT layer's ELU
+backward reads them).  _BoundModuleEngine ties the engine to the iterator; the engine itself states which plan field
+takes the logits (StepEngine.LOGITS).  A GAT gets the binding only when it was bound explicitly:
+`bind_gat(model, cluster_iterator)`.  An unbound gist_amd.modules.GAT keeps the op-by-op path, the
 independent twin its tests compare the fused step with.  gist_amd.modules.GraphSAGE likewise, on
 gist_graphsage_step_phase with `gist::graphsage_forward` / `gist::graphsage_backward`, through
 `bind_graphsage(model, cluster_iterator, seed)`: GraphSAGEModuleEngine states how the engine is built and tied to the
@@ -222,10 +223,6 @@ class ModuleEngine(object):
         it.bind(eng)
         return eng
 
-    def _point_logits(self, P, ptr):
-        """Where the plan takes the address of this step's logits."""
-        P.layer[self._last].Y = ptr
-
     def __init__(self, model, it, dims=None):
         self._model, self.it = weakref.ref(model), it
         self.engine = eng = self._bind_engine(model, it, dims)
@@ -249,7 +246,6 @@ class ModuleEngine(object):
         self._loss0 = None
         self._pred = None           # _saves_logits: (weak reference to the logits handed out, their version then)
         self._f32 = dict(dtype=torch.float32, device=it.g.device)
-        self._last = len(eng.dims) - 1
         self._first_step = True
         # logits and loss of a step live in small rings (no allocator call in the loop).  A slot whose tensor the caller
         # still holds (the tensor, a view of it, `preds.append(model(c))`) is NOT reused: the ring gets a fresh buffer
@@ -293,7 +289,7 @@ class ModuleEngine(object):
         else:                                              # (the first n rows of the slot: _run_forward hands them out)
             y = self._ring_slot(self._logit_ring, self.token & 3,
                                 lambda: torch.empty(self.it.n_max, self.ldc, **self._f32))
-        self._point_logits(P, y.data_ptr())
+        eng._point_logits(y.data_ptr())
         self._loss0 = self._ring_slot(self._loss_ring, self.token & 63, lambda: torch.zeros((), **self._f32))
         P.loss = self._loss0.data_ptr()
         self._pending = (b, g)
@@ -480,50 +476,89 @@ def gat_model_dims(model):
     return dims
 
 
-class GATModuleEngine(ModuleEngine):
-    """One gist_amd.modules.GAT bound to one ClusterIter (bind_gat): the GATEngine behind `model(cluster)`.  The surface
-    is ModuleEngine's -- forward, fused loss, fast and taped backward, the optimiser's hooks -- on gist_gat_step_phase."""
-    family = 'GAT'
-    _forward_op, _backward_op = torch.ops.gist.gat_forward, torch.ops.gist.gat_backward
-    _saves_logits = True        # (the last layer's ELU backward reads them)
-    _twin_hint = 'an unbound model runs op by op'
+class _BoundModuleEngine(ModuleEngine):
+    """What the explicitly bound families (bind_gat, bind_graphsage) share: how the engine behind `model(cluster)` is
+    found or built and tied to the iterator.  A family states _new_engine (how its engine is built, and on which layer-0
+    buffer), _fits (may the engine a wrapper already has for the model's arena serve?) and BOUND, the attribute of the
+    iterator that holds the weak list of this family's bindings."""
+    BOUND = None
 
     def _bind_engine(self, model, it, dims):
-        from .gat_engine import GATEngine
-        others = [m for m in (r() for r in it.__dict__.setdefault('_gat_bound', [])) if m is not None]
-        first = others[0] if others else None
-        x0 = first.engine.X0 if first is not None else None
-        # a DistributedGATWrapper's sub_model already IS its arena: the engine steps that arena in place (dispatch and
-        # sync write it between steps) -- the wrapper's own engine if it has a fitting one; any other model is re-homed
-        # into an arena of the engine's own
+        bound = self.BOUND
+        others = [m for m in (r() for r in it.__dict__.setdefault(bound, [])) if m is not None]
+        # a gist_amd.ist wrapper's sub_model already IS its arena: the engine steps that arena in place (dispatch and
+        # sync write it between steps) -- the wrapper's own engine (attach_engine: its seed, its dropout counter) if it
+        # has a fitting one; any other model is re-homed into an arena of the engine's own
         shared = shared_arena(model, dims, need_grads=False)
         eng = None
         if shared is not None:
             ref = shared.__dict__.get('_engine')
             eng = ref() if ref is not None else None
-            if eng is not None and eng.n_max != it.n_max:
+            if eng is not None and (eng.n_max != it.n_max or not self._fits(eng, model)):
                 eng = None
         if eng is None:
-            eng = GATEngine(dims, it.n_max, it.g.device, arena=shared, x0=x0)
+            eng = self._new_engine(model, it, dims, shared, others[0].engine if others else None)
         if shared is None:
             eng.arena.adopt_module(model)
-        if first is None:
+        if not others:
             if it.engine is not eng or eng.plan is None:
                 it.bind(eng)                  # the iterator's engine: its epoch-end extraction check
         elif eng.plan is None or eng._plan_keep[0] is not it.batcher:
             eng.attach_batcher(it.batcher)
         # one model on the iterator: the optimiser launch extracts the next batch.  Several (the S sites of one process):
-        # they share the batch buffers and layer 0's input rows (the first engine's X0), so nobody extracts ahead and
-        # every forward phase extracts its batch itself (one launch; the buffers then hold what they held)
-        it._gat_bound = [weakref.ref(m) for m in others] + [weakref.ref(self)]
+        # they share the batch buffers (the GAT's layer 0's input rows too, the first engine's X0; a GraphSAGE training
+        # step leaves dropped values in its own Z_0), so nobody extracts ahead and every forward phase extracts its batch
+        # itself (one launch; shared buffers then hold what they held)
+        setattr(it, bound, [weakref.ref(m) for m in others] + [weakref.ref(self)])
         for m in others:
             m.engine.prefetch = False
         eng.prefetch = not others
         return eng
 
-    def _point_logits(self, P, ptr):
-        self.engine._lent = True      # (the plan's logits, loss and moment pointers are this binding's until reclaimed)
-        P.layer[self._last].out = ptr
+
+def _check_binding(who, it, params, feeds, columns, takes):
+    """The refusals bind_gat and bind_graphsage share, after the family's own: `it` feeds the device (feeds: its test),
+    `params` are fp32 on its GPU, its resident features have `columns` columns (takes: the model's input width in
+    words), the profiler is off."""
+    dev = it.g.device
+    if dev.type != 'cuda' or not feeds():
+        raise ValueError('gist_amd: %s: the iterator does not describe its batches for on-device extraction '
+                         '(use_pp=%s, device %s, GIST_MODULE_ENGINE=%s): the fused step is GPU-only and extracts the '
+                         'batch itself' % (who, it.use_pp, dev, os.environ.get('GIST_MODULE_ENGINE', '1')))
+    for p in params:
+        if p.dtype != torch.float32 or p.device != dev:
+            raise ValueError('gist_amd: %s: parameters must be fp32 on %s (found %s on %s); model.to(device) first'
+                             % (who, dev, p.dtype, p.device))
+    if columns != it.batcher.feat.shape[1]:
+        raise ValueError('gist_amd: %s: the model takes %s, the iterator\'s graph has %d'
+                         % (who, takes, it.batcher.feat.shape[1]))
+    if hip._prof is not None:
+        raise ValueError('gist_amd: %s: the op profiler is on; the fused step has no per-op records' % who)
+
+
+def _bound_to(who, model, it, engines):
+    """`it` checked, and the binding `model` already has for it (model.__dict__[engines]), or None."""
+    from .sampler import ClusterIter
+    if not isinstance(it, ClusterIter):
+        raise ValueError('gist_amd: %s needs a gist_amd.sampler.ClusterIter (got %s)' % (who, type(it).__name__))
+    return (model.__dict__.get(engines) or {}).get(id(it))
+
+
+class GATModuleEngine(_BoundModuleEngine):
+    """One gist_amd.modules.GAT bound to one ClusterIter (bind_gat): the GATEngine behind `model(cluster)`.  The surface
+    is ModuleEngine's -- forward, fused loss, fast and taped backward, the optimiser's hooks -- on gist_gat_step_phase."""
+    family = 'GAT'
+    BOUND = '_gat_bound'
+    _forward_op, _backward_op = torch.ops.gist.gat_forward, torch.ops.gist.gat_backward
+    _saves_logits = True        # (the last layer's ELU backward reads them)
+    _twin_hint = 'an unbound model runs op by op'
+
+    def _new_engine(self, model, it, dims, arena, first):
+        from .gat_engine import GATEngine
+        return GATEngine(dims, it.n_max, it.g.device, arena=arena, x0=first.x0 if first is not None else None)
+
+    def _fits(self, eng, model):
+        return True
 
 
 def bind_gat(model, cluster_iterator):
@@ -534,33 +569,15 @@ def bind_gat(model, cluster_iterator):
     Parameters keep their identity; their .data moves onto the arena).  Returns the GATModuleEngine; a second call with
     the same iterator returns the same one.  ValueError, with the reason, if the model or the iterator cannot run on
     the fused step: nothing falls back silently."""
-    from .sampler import ClusterIter
     dims = gat_model_dims(model)
     it = cluster_iterator
-    if not isinstance(it, ClusterIter):
-        raise ValueError('gist_amd: bind_gat needs a gist_amd.sampler.ClusterIter (got %s)' % type(it).__name__)
-    mes = model.__dict__.get('_gat_engines')
-    if mes:
-        me = mes.get(id(it))
-        if me is not None:
-            return me
-        if any(m is not None for m in mes.values()):
-            raise ValueError('gist_amd: bind_gat: this model is already bound to another iterator')
-    params = GATArena.module_params(model)
-    dev = it.g.device
-    if dev.type != 'cuda' or not it.feed():
-        raise ValueError('gist_amd: bind_gat: the iterator does not describe its batches for on-device extraction '
-                         '(use_pp=%s, device %s, GIST_MODULE_ENGINE=%s): the fused step is GPU-only and extracts the '
-                         'batch itself' % (it.use_pp, dev, os.environ.get('GIST_MODULE_ENGINE', '1')))
-    for p in params:
-        if p.dtype != torch.float32 or p.device != dev:
-            raise ValueError('gist_amd: bind_gat: parameters must be fp32 on %s (found %s on %s); model.to(device) first'
-                             % (dev, p.dtype, p.device))
-    if dims[0][0] != it.batcher.feat.shape[1]:
-        raise ValueError('gist_amd: bind_gat: the model takes %d input features, the iterator\'s graph has %d'
-                         % (dims[0][0], it.batcher.feat.shape[1]))
-    if hip._prof is not None:
-        raise ValueError('gist_amd: bind_gat: the op profiler is on; the fused step has no per-op records')
+    me = _bound_to('bind_gat', model, it, '_gat_engines')
+    if me is not None:
+        return me
+    if any(m is not None for m in model.__dict__.get('_gat_engines', {}).values()):
+        raise ValueError('gist_amd: bind_gat: this model is already bound to another iterator')
+    _check_binding('bind_gat', it, GATArena.module_params(model), it.feed, dims[0][0],
+                   '%d input features' % dims[0][0])
     me = GATModuleEngine(model, it, dims)
     model.__dict__.setdefault('_gat_engines', {})[id(it)] = me
     return me
@@ -623,11 +640,12 @@ def _p_drop(layer):
     return float(d.p) if isinstance(d, torch.nn.Dropout) else 0.0
 
 
-class GraphSAGEModuleEngine(ModuleEngine):
+class GraphSAGEModuleEngine(_BoundModuleEngine):
     """One gist_amd.modules.GraphSAGE bound to one ClusterIter (bind_graphsage): the GraphSAGEEngine behind
     `model(cluster)`.  The surface is ModuleEngine's on gist_graphsage_step_phase.  The forward phase advances the
     engine's dropout counter once; the backward phase gets the same offset back from StepEngine._run."""
     family = 'GraphSAGE'
+    BOUND = '_graphsage_bound'
     _forward_op, _backward_op = torch.ops.gist.graphsage_forward, torch.ops.gist.graphsage_backward
     _saves_logits = False       # (the output layer has no activation: an in-place edit of pred before backward() is legal)
     _twin_hint = 'an unbound model runs op by op'
@@ -636,37 +654,14 @@ class GraphSAGEModuleEngine(ModuleEngine):
         self._seed = int(seed)
         ModuleEngine.__init__(self, model, it, dims)
 
-    def _bind_engine(self, model, it, dims):
+    def _new_engine(self, model, it, dims, arena, first):
+        # (every engine owns its Z_0: a training step with dropout leaves dropped values in it)
         from .graphsage_engine import GraphSAGEEngine
-        others = [m for m in (r() for r in it.__dict__.setdefault('_graphsage_bound', [])) if m is not None]
-        p, use_pp = _p_drop(model.layers[0]), bool(model.layers[0].use_pp)
-        # a DistributedGraphSAGEWrapper's sub_model already IS its arena: the engine steps that arena in place (dispatch
-        # and sync write it between steps) -- the wrapper's own engine (attach_engine: its seed, its dropout counter) if
-        # it has a fitting one; any other model is re-homed into an arena of the engine's own
-        shared = shared_arena(model, dims, need_grads=False)
-        eng = None
-        if shared is not None:
-            ref = shared.__dict__.get('_engine')
-            eng = ref() if ref is not None else None
-            if eng is not None and (eng.n_max != it.n_max or eng.use_pp != use_pp or eng.p_drop != p):
-                eng = None
-        if eng is None:
-            eng = GraphSAGEEngine(dims, p, it.n_max, it.g.device, seed=self._seed, use_pp=use_pp, arena=shared)
-        if shared is None:
-            eng.arena.adopt_module(model)
-        if not others:
-            if it.engine is not eng or eng.plan is None:
-                it.bind(eng)                  # the iterator's engine: its epoch-end extraction check
-        elif eng.plan is None or eng._plan_keep[0] is not it.batcher:
-            eng.attach_batcher(it.batcher)
-        # GATModuleEngine's rule.  One model on the iterator: the optimiser launch extracts the next batch.  Several (the
-        # S sites of one process): they share the batch buffers, and a training step leaves dropped values in its own
-        # Z_0, so nobody extracts ahead and every forward phase extracts its batch into its own engine's Z_0
-        it._graphsage_bound = [weakref.ref(m) for m in others] + [weakref.ref(self)]
-        for m in others:
-            m.engine.prefetch = False
-        eng.prefetch = not others
-        return eng
+        return GraphSAGEEngine(dims, _p_drop(model.layers[0]), it.n_max, it.g.device, seed=self._seed,
+                               use_pp=bool(model.layers[0].use_pp), arena=arena)
+
+    def _fits(self, eng, model):
+        return eng.use_pp == bool(model.layers[0].use_pp) and eng.p_drop == _p_drop(model.layers[0])
 
 
 def bind_graphsage(model, cluster_iterator, seed=0):
@@ -686,36 +681,20 @@ def bind_graphsage(model, cluster_iterator, seed=0):
     Returns the GraphSAGEModuleEngine; a second call with the same iterator returns the same one.  ValueError, with the
     reason, if the model or the iterator cannot run on the fused step: nothing falls back silently."""
     from .arena import GraphSAGEArena
-    from .sampler import ClusterIter
     dims = graphsage_model_dims(model)
     it = cluster_iterator
-    if not isinstance(it, ClusterIter):
-        raise ValueError('gist_amd: bind_graphsage needs a gist_amd.sampler.ClusterIter (got %s)' % type(it).__name__)
-    mes = model.__dict__.get('_graphsage_engines')
-    if mes:
-        me = mes.get(id(it))
-        if me is not None:
-            return me
+    me = _bound_to('bind_graphsage', model, it, '_graphsage_engines')
+    if me is not None:
+        return me
+    if model.__dict__.get('_graphsage_engines'):
         raise ValueError('gist_amd: bind_graphsage: this model is already bound to another iterator')
     use_pp = bool(model.layers[0].use_pp)
     if use_pp != bool(it.use_pp):
         raise ValueError('gist_amd: bind_graphsage: the model\'s use_pp (%s) is not the iterator\'s (%s)' % (use_pp, it.use_pp))
-    params = GraphSAGEArena.module_params(model)
-    dev = it.g.device
-    if dev.type != 'cuda' or not (it.feed_precalculated() if use_pp else it.feed()):
-        raise ValueError('gist_amd: bind_graphsage: the iterator does not describe its batches for on-device extraction '
-                         '(device %s, GIST_MODULE_ENGINE=%s): the fused step is GPU-only and extracts the batch itself'
-                         % (dev, os.environ.get('GIST_MODULE_ENGINE', '1')))
-    for p in params:
-        if p.dtype != torch.float32 or p.device != dev:
-            raise ValueError('gist_amd: bind_graphsage: parameters must be fp32 on %s (found %s on %s); model.to(device) '
-                             'first' % (dev, p.dtype, p.device))
     want = (2 if use_pp else 1) * dims[0][0]
-    if want != it.batcher.feat.shape[1]:
-        raise ValueError('gist_amd: bind_graphsage: the model takes %d input features%s, the iterator\'s graph has %d'
-                         % (dims[0][0], ' ([X | A^X]: %d columns)' % want if use_pp else '', it.batcher.feat.shape[1]))
-    if hip._prof is not None:
-        raise ValueError('gist_amd: bind_graphsage: the op profiler is on; the fused step has no per-op records')
+    _check_binding('bind_graphsage', it, GraphSAGEArena.module_params(model),
+                   it.feed_precalculated if use_pp else it.feed, want,
+                   '%d input features%s' % (dims[0][0], ' ([X | A^X]: %d columns)' % want if use_pp else ''))
     me = GraphSAGEModuleEngine(model, it, dims, seed)
     model.__dict__.setdefault('_graphsage_engines', {})[id(it)] = me
     return me

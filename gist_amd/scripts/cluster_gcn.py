@@ -181,29 +181,13 @@ def main_baseline(args, dataset, log):
     return main_module_path(args, data, g, device, in_feats, n_classes, par_li, psize, log)
 
 
-def main_baseline_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log):
-    """--model-type baseline --host-path step: one gist_baseline_gcn_step per iteration (gist_amd/baseline_gcn_engine.py),
-    fed by EngineClusterIter.  Same construction order, RNG draws for the weights and batch order as main_module_path;
-    the dropout masks come from autograd.gcn_tail's generator, seed and counter scheme, counted by the engine from 0
-    instead of by the process-wide counter."""
+def engine_epochs(args, it, engine, model, g, device, log):
+    """The epochs of the one-call paths (main_baseline_engine, main_gat_engine, main_graphsage_engine): one train_step per
+    batch of `it`, timed per epoch between two synchronises; `model`, whose parameters are the engine's arena, evaluated
+    on the device graph `g` after each; the five result lines.  -> (total_time, val_accs, test_accs)."""
     import time
-    from gist_amd.arena import baseline_gcn_dims
-    from gist_amd.baseline_gcn_engine import BaselineGCNEngine
-    from gist_amd.modules import BaselineGCN
-    from gist_amd.sampler import EngineClusterIter
     from gist_amd.utils import evaluate
-    train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
-    it = EngineClusterIter(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li, device=device)
-    g = g.to(device)
     labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
-    model = BaselineGCN(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout, args.use_layernorm)
-    model.cuda()
-    model.set_dropout_seed(args.rnd_seed)
-    engine = BaselineGCNEngine(baseline_gcn_dims(in_feats, args.n_hidden, n_classes, args.n_layers), args.use_layernorm,
-                               args.dropout, it.n_max, device, seed=args.rnd_seed)
-    engine.bind(model)                                     # the model's parameters are the arena's views from here on
-    it.bind(engine)
-    engine.prefetch = True                                 # (the loop only reads the loss of a step)
     total_time, val_accs, test_accs = 0., [], []
     for epoch in range(args.n_epochs):                     # cluster_gcn.py:89-127
         log(f'Running epoch {epoch} / {args.n_epochs}', flush=True)
@@ -222,6 +206,30 @@ def main_baseline_engine(args, data, g, device, in_feats, n_classes, par_li, psi
     log(f'Best Val: {max(val_accs):.4f}', flush=True)
     log(f'Last Test: {test_accs[-1]:.4f}', flush=True)
     log(f'Best Test: {max(test_accs):.4f}', flush=True)
+    return total_time, val_accs, test_accs
+
+
+def main_baseline_engine(args, data, g, device, in_feats, n_classes, par_li, psize, log):
+    """--model-type baseline --host-path step: one gist_baseline_gcn_step per iteration (gist_amd/baseline_gcn_engine.py),
+    fed by EngineClusterIter.  Same construction order, RNG draws for the weights and batch order as main_module_path;
+    the dropout masks come from autograd.gcn_tail's generator, seed and counter scheme, counted by the engine from 0
+    instead of by the process-wide counter."""
+    from gist_amd.arena import baseline_gcn_dims
+    from gist_amd.baseline_gcn_engine import BaselineGCNEngine
+    from gist_amd.modules import BaselineGCN
+    from gist_amd.sampler import EngineClusterIter
+    train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
+    it = EngineClusterIter(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li, device=device)
+    g = g.to(device)
+    model = BaselineGCN(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout, args.use_layernorm)
+    model.cuda()
+    model.set_dropout_seed(args.rnd_seed)
+    engine = BaselineGCNEngine(baseline_gcn_dims(in_feats, args.n_hidden, n_classes, args.n_layers), args.use_layernorm,
+                               args.dropout, it.n_max, device, seed=args.rnd_seed)
+    engine.bind(model)                                     # the model's parameters are the arena's views from here on
+    it.bind(engine)
+    engine.prefetch = True                                 # (the loop only reads the loss of a step)
+    total_time, val_accs, test_accs = engine_epochs(args, it, engine, model, g, device, log)
     return dict(total_time=total_time, val_accs=val_accs, test_accs=test_accs, model=model, engine=engine)
 
 
@@ -229,16 +237,13 @@ def main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, l
     """--model-type gat on the fused step: one gist_gat_step per iteration (gist_amd/gat_engine.py), fed by
     EngineClusterIter.  Same construction order, RNG draws, batch order and arithmetic as main_module_path: same-seed
     weights are bit-identical whatever the host path."""
-    import time
     from gist_amd.gat_engine import GATEngine
     from gist_amd.ist import gat_dims, gat_params
     from gist_amd.modules import GAT
     from gist_amd.sampler import EngineClusterIter
-    from gist_amd.utils import evaluate
     train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
     it = EngineClusterIter(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li, device=device)
     g = g.to(device)
-    labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
     merge = getattr(args, 'head_merge', 'mean')
     model = GAT(args.n_layers, in_feats, args.n_hidden, n_classes, args.n_heads,   # cluster_gcn_ist_distrib_gat.py:77-79
                 merge=merge)
@@ -249,24 +254,7 @@ def main_gat_engine(args, data, g, device, in_feats, n_classes, par_li, psize, l
     it.bind(engine)
     engine.prefetch = True                                 # (the loop only reads the loss of a step)
     attach_eval_path(args, model, engine.arena)
-    total_time, val_accs, test_accs = 0., [], []
-    for epoch in range(args.n_epochs):                     # cluster_gcn.py:89-127
-        log(f'Running epoch {epoch} / {args.n_epochs}', flush=True)
-        torch.cuda.synchronize(device)
-        start_time = time.time()
-        for batch in it:
-            engine.train_step(batch, args.lr, args.weight_decay)
-        torch.cuda.synchronize(device)
-        total_time += time.time() - start_time
-        engine.check_extract()                             # (outside the timed interval)
-        val_accs.append(evaluate(model, g, labels, val_mask, 'f1' if args.use_f1 else 'acc'))
-        test_accs.append(evaluate(model, g, labels, test_mask, 'f1' if args.use_f1 else 'acc'))
-        log(f'Val acc {val_accs[-1]}', flush=True)
-    log(f'Training Time: {total_time:.4f}', flush=True)    # :132-136
-    log(f'Last Val: {val_accs[-1]:.4f}', flush=True)
-    log(f'Best Val: {max(val_accs):.4f}', flush=True)
-    log(f'Last Test: {test_accs[-1]:.4f}', flush=True)
-    log(f'Best Test: {max(test_accs):.4f}', flush=True)
+    total_time, val_accs, test_accs = engine_epochs(args, it, engine, model, g, device, log)
     return dict(total_time=total_time, val_accs=val_accs, test_accs=test_accs, model=model)
 
 
@@ -274,17 +262,14 @@ def main_graphsage_engine(args, data, g, device, in_feats, n_classes, par_li, ps
     """--model-type graphsage --host-path step: one gist_graphsage_step per iteration (gist_amd/graphsage_engine.py), fed
     by EngineClusterIter (with --use-pp: its [X | A^X] features).  Same construction order, RNG draws for the weights and
     batch order as main_module_path; the dropout masks come from the step's counter-based generator, not torch's."""
-    import time
     from gist_amd.arena import graphsage_dims
     from gist_amd.graphsage_engine import GraphSAGEEngine
     from gist_amd.modules import GraphSAGE
     from gist_amd.sampler import EngineClusterIter
-    from gist_amd.utils import evaluate
     train_nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
     it = EngineClusterIter(args.dataset, g, psize, args.batch_size, train_nid, use_pp=args.use_pp, par_li=par_li,
                            device=device)
     g = g.to(device)
-    labels, val_mask, test_mask = g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask']
     model = GraphSAGE(in_feats, args.n_hidden, n_classes, args.n_layers, F.relu, args.dropout, args.use_pp)
     model.cuda()
     engine = GraphSAGEEngine(graphsage_dims(in_feats, args.n_hidden, n_classes, args.n_layers), args.dropout, it.n_max,
@@ -293,24 +278,7 @@ def main_graphsage_engine(args, data, g, device, in_feats, n_classes, par_li, ps
     it.bind(engine)
     engine.prefetch = True                                 # (the loop only reads the loss of a step)
     attach_eval_path(args, model, engine.arena)
-    total_time, val_accs, test_accs = 0., [], []
-    for epoch in range(args.n_epochs):                     # cluster_gcn.py:89-127
-        log(f'Running epoch {epoch} / {args.n_epochs}', flush=True)
-        torch.cuda.synchronize(device)
-        start_time = time.time()
-        for batch in it:
-            engine.train_step(batch, args.lr, args.weight_decay)
-        torch.cuda.synchronize(device)
-        total_time += time.time() - start_time
-        engine.check_extract()                             # (outside the timed interval)
-        val_accs.append(evaluate(model, g, labels, val_mask, 'f1' if args.use_f1 else 'acc'))
-        test_accs.append(evaluate(model, g, labels, test_mask, 'f1' if args.use_f1 else 'acc'))
-        log(f'Val acc {val_accs[-1]}', flush=True)
-    log(f'Training Time: {total_time:.4f}', flush=True)    # :132-136
-    log(f'Last Val: {val_accs[-1]:.4f}', flush=True)
-    log(f'Best Val: {max(val_accs):.4f}', flush=True)
-    log(f'Last Test: {test_accs[-1]:.4f}', flush=True)
-    log(f'Best Test: {max(test_accs):.4f}', flush=True)
+    total_time, val_accs, test_accs = engine_epochs(args, it, engine, model, g, device, log)
     return dict(total_time=total_time, val_accs=val_accs, test_accs=test_accs, model=model, engine=engine)
 
 

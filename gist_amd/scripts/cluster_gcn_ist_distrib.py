@@ -113,6 +113,68 @@ def setup(args, dataset=None, log=print):
     return device, data, g, in_feats, n_classes, train_nid, par_li, psize
 
 
+def add_family_args(parser, family):
+    """--exp_name and (not flags of the reference) --host-path and --eval-path of a family's GIST script: host_path and
+    eval_path of its gist_amd.ist loop, the choices those the wrapper class `family` states."""
+    parser.add_argument("--exp_name", type=str, default='distributed_gnn_ist')
+    parser.add_argument("--host-path", choices=['module', family.STEP_PATH] + (['phases'] if family.PHASES else []),
+                        default='module')
+    if len(family.EVAL_PATHS) > 1:
+        parser.add_argument("--eval-path", choices=list(family.EVAL_PATHS), default='layers')
+    return parser
+
+
+def report_family(args, res, log, lines):
+    """With --save_results the pickle {total_time, trn_losses, val_accs, test_accs} goes to
+    ./results/{exp_name}_result.pckl (returns its path); otherwise lines(res, log=log) prints the result lines."""
+    if args.save_results:
+        import os
+        import pickle
+        os.makedirs('./results', exist_ok=True)
+        path = os.path.join('./results', args.exp_name + '_result.pckl')
+        with open(path, 'wb') as f:
+            pickle.dump({'total_time': res['total_time'], 'trn_losses': res['trn_losses'],
+                         'val_accs': res['val_accs'], 'test_accs': res['test_accs']}, f)
+        return path
+    lines(res, log=log)
+    return None
+
+
+def main_family(args, dataset, log, setup, wrapper, train, report, comm=None):
+    """The body of a family's GIST script after its own refusals: its set-up, the iterator (get_data: one shuffle; the
+    one-call path's describes its batches), the family's wrapper, the initial dispatch, its gist_amd.ist loop `train`,
+    rank 0's report, the end of the group.
+
+    setup, wrapper, train and report are handed in, and the sampler's classes are looked up when this runs, because each
+    family script resolves them in its own namespace or on gist_amd.ist at call time: a test that stands in for one of
+    them there (tests/test_baseline_gcn_ist.py does, for all four and for EngineClusterIter) must be what runs here.
+    use_pp reaches the iterator only when it is set (its default is off): a family that refuses --use-pp never names it."""
+    import gist_amd.sampler as sampler
+    assert (args.n_hidden % args.num_subnet) == 0
+    host_path = getattr(args, 'host_path', 'module')
+    device, data, g, in_feats, n_classes, train_nid, par_li, psize = setup(args, dataset, log)
+    iter_cls = sampler.ClusterIter if host_path in ('module', 'phases') else sampler.EngineClusterIter
+    cluster_iterator = iter_cls(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li, device=device,
+                                **(dict(use_pp=True) if args.use_pp else {}))
+    g = g.to(device)
+    ist_model = wrapper(args, g, in_feats, n_classes, device, comm=comm, seed=args.rnd_seed)
+    log(f'{args.rank}: start initial dispatch', flush=True)
+    ist_model.ini_sync_dispatch_model()
+    log(f'{args.rank}: finish initial dispatch', flush=True)
+    paths = dict(host_path=host_path)
+    if hasattr(args, 'eval_path'):                   # (a family with one evaluator has no --eval-path)
+        paths['eval_path'] = args.eval_path
+    res = train(ist_model, args, g, cluster_iterator, g.ndata['label'], g.ndata['val_mask'], g.ndata['test_mask'],
+                log=log, **paths)
+    if args.rank == 0:
+        path = report(args, res, log=log)
+        if path is not None:
+            res['results_path'] = path
+    dist.destroy_process_group()
+    res['model'] = ist_model
+    return res
+
+
 def main(args=None, dataset=None, log=print, ultra_wide=False):
     from gist_amd import ist
     from gist_amd.modules import GCN

@@ -19,66 +19,34 @@ forward.  Set-up (seeds, device, process group, --normalize, data loading) is cl
 import argparse
 import os
 
-import torch.distributed as dist
+from gist_amd import ist
+# (dist: the process group setup() opens and main_family ends)
+from gist_amd.scripts.cluster_gcn_ist_distrib import add_family_args, add_ist_args, dist, main_family, report_family, setup
 
-from gist_amd.scripts.cluster_gcn_ist_distrib import add_ist_args, setup
+FAMILY = ist.DistributedBaselineGCNWrapper        # its facts are the choices of --host-path and --eval-path
 
 
 def build_parser():
-    parser = add_ist_args(argparse.ArgumentParser(description='GCN'))
-    parser.add_argument("--exp_name", type=str, default='distributed_gnn_ist')
-    # (not a flag of the reference) gist_amd.ist.train_baseline_gcn's host_path
-    parser.add_argument("--host-path", choices=['module', 'step'], default='module')
-    return parser
+    return add_family_args(add_ist_args(argparse.ArgumentParser(description='GCN')), FAMILY)
 
 
 def report(args, res, log=print):
     """With --save_results the pickle {total_time, trn_losses, val_accs, test_accs} goes to
     ./results/{exp_name}_result.pckl (returns its path); otherwise the five result lines (:475-479)."""
-    from gist_amd import ist
-    if args.save_results:
-        import pickle
-        os.makedirs('./results', exist_ok=True)
-        path = os.path.join('./results', args.exp_name + '_result.pckl')
-        with open(path, 'wb') as f:
-            pickle.dump({'total_time': res['total_time'], 'trn_losses': res['trn_losses'],
-                         'val_accs': res['val_accs'], 'test_accs': res['test_accs']}, f)
-        return path
-    ist.print_results(res, log=log)
-    return None
+    return report_family(args, res, log, ist.print_results)
 
 
 def main(args=None, dataset=None, log=print, comm=None):
     """comm: the wrapper's collectives (None: gist_amd.ist.TorchDistComm over the process group set up here)."""
-    from gist_amd import ist
-    from gist_amd.sampler import ClusterIter, EngineClusterIter
     if args is None:
         args = build_parser().parse_args()
-    assert (args.n_hidden % args.num_subnet) == 0
-    host_path = getattr(args, 'host_path', 'module')
     if args.use_pp:
         raise SystemExit('gist_amd: --use-pp is not offered for the BaselineGCN family (a GraphConv layer reads h alone, '
                          'there is no [X | A^X] input to precompute)')
     if args.cuda_id < 0:
         raise SystemExit('gist_amd: the BaselineGCN family runs on a GPU (--cuda-id >= 0)')
-    device, data, g, in_feats, n_classes, train_nid, par_li, psize = setup(args, dataset, log)
-    iter_cls = EngineClusterIter if host_path == 'step' else ClusterIter
-    cluster_iterator = iter_cls(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li,
-                                device=device)                                       # get_data (one shuffle)
-    g = g.to(device)
-    ist_model = ist.DistributedBaselineGCNWrapper(args, g, in_feats, n_classes, device, comm=comm, seed=args.rnd_seed)
-    log(f'{args.rank}: start initial dispatch', flush=True)
-    ist_model.ini_sync_dispatch_model()
-    log(f'{args.rank}: finish initial dispatch', flush=True)
-    res = ist.train_baseline_gcn(ist_model, args, g, cluster_iterator, g.ndata['label'], g.ndata['val_mask'],
-                                 g.ndata['test_mask'], log=log, host_path=host_path)
-    if args.rank == 0:
-        path = report(args, res, log=log)
-        if path is not None:
-            res['results_path'] = path
-    dist.destroy_process_group()
-    res['model'] = ist_model
-    return res
+    # (the wrapper and the loop as gist_amd.ist has them now: a stand-in there is what runs)
+    return main_family(args, dataset, log, setup, ist.DistributedBaselineGCNWrapper, ist.train_baseline_gcn, report, comm=comm)
 
 
 if __name__ == '__main__':

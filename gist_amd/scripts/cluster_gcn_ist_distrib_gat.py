@@ -20,9 +20,11 @@ where it cannot run as written: DESIGN.md §9.
 import argparse
 import os
 
-import torch.distributed as dist
+from gist_amd import ist
+# (dist: the process group setup() opens and main_family ends)
+from gist_amd.scripts.cluster_gcn_ist_distrib import add_family_args, add_ist_args, dist, main_family, report_family, setup
 
-from gist_amd.scripts.cluster_gcn_ist_distrib import add_ist_args, setup
+FAMILY = ist.DistributedGATWrapper        # its facts are the choices of --host-path and --eval-path
 
 
 def build_parser():
@@ -30,42 +32,29 @@ def build_parser():
     parser.add_argument('--n-heads', type=int, default=4)
     # (not a flag of the reference) cat: the hidden layers concatenate their heads (its comment, modules.py:87-89)
     parser.add_argument('--head-merge', choices=['mean', 'cat'], default='mean')
-    parser.add_argument("--exp_name", type=str, default='distributed_gnn_ist')
-    # (not a flag of the reference) module: the reference's loop on ist_model.sub_model / base_model; engine: one
-    # gist_gat_step per iteration; phases: the module loop with sub_model bound to the iterator, three
-    # gist_gat_step_phase calls per iteration (gist_amd.ist.train_gat, host_path)
-    parser.add_argument("--host-path", choices=['module', 'engine', 'phases'], default='module')
-    # (not a flag of the reference) blocked: rank 0's evaluate(base_model, g, ...) runs gist_amd.gat_eval's
-    # GATFullGraphEvaluator instead of the model's own forward (gist_amd.ist.train_gat, eval_path)
-    parser.add_argument("--eval-path", choices=['layers', 'blocked'], default='layers')
-    return parser
+    # --host-path module: the reference's loop on ist_model.sub_model / base_model; engine: one gist_gat_step per
+    # iteration; phases: the module loop with sub_model bound to the iterator, three gist_gat_step_phase calls per
+    # iteration.  --eval-path blocked: rank 0's evaluate(base_model, g, ...) runs gist_amd.gat_eval's
+    # GATFullGraphEvaluator instead of the model's own forward (gist_amd.ist.train_gat)
+    return add_family_args(parser, FAMILY)
 
 
-def report(args, res, log=print):
-    """:481-499 -- with --save_results the pickle {total_time, trn_losses, val_accs, test_accs} goes to
-    ./results/{exp_name}_result.pckl (returns its path); otherwise exactly four lines in the reference's order, which
-    its sweep reads by position."""
-    if args.save_results:
-        import pickle
-        os.makedirs('./results', exist_ok=True)
-        path = os.path.join('./results', args.exp_name + '_result.pckl')
-        with open(path, 'wb') as f:
-            pickle.dump({'total_time': res['total_time'], 'trn_losses': res['trn_losses'],
-                         'val_accs': res['val_accs'], 'test_accs': res['test_accs']}, f)
-        return path
+def _four_lines(res, log=print):
+    """:494-499 -- exactly four lines in the reference's order, which its sweep reads by position."""
     log(f"Training Time: {res['total_time']:.4f}")
     log(f"Last Test: {res['test_accs'][-1]:.4f}")
     log(f"Best Test: {max(res['test_accs']):.4f}")
     log(f"Best Val: {max(res['val_accs']):.4f}")
-    return None
+
+
+def report(args, res, log=print):
+    """:481-499 -- the results pickle with --save_results (returns its path), otherwise the four result lines."""
+    return report_family(args, res, log, _four_lines)
 
 
 def main(args=None, dataset=None, log=print):
-    from gist_amd import ist
-    from gist_amd.sampler import ClusterIter, EngineClusterIter
     if args is None:
         args = build_parser().parse_args()
-    assert (args.n_hidden % args.num_subnet) == 0
     host_path = getattr(args, 'host_path', 'module')
     if host_path in ('engine', 'phases') and (args.use_pp or args.cuda_id < 0):
         raise SystemExit('gist_amd: --host-path %s is the fused GAT step: it runs on a GPU (--cuda-id >= 0) and '
@@ -75,27 +64,8 @@ def main(args=None, dataset=None, log=print):
         raise NotImplementedError(
             'gist_amd: --use-pp cannot work with the GAT in the reference either (the feature width doubles after '
             'in_feats was read)')
-    device, data, g, in_feats, n_classes, train_nid, par_li, psize = setup(args, dataset, log)
-    iter_cls = EngineClusterIter if host_path == 'engine' else ClusterIter
-    cluster_iterator = iter_cls(args.dataset, g, psize, args.batch_size, train_nid, par_li=par_li,
-                                device=device)                                       # get_data (one shuffle)
-    g = g.to(device)
-    ist_model = ist.DistributedGATWrapper(args, g, in_feats, n_classes, device, seed=args.rnd_seed)   # :609
-    log(f'{args.rank}: start initial dispatch', flush=True)
-    ist_model.ini_sync_dispatch_model()
-    log(f'{args.rank}: finish initial dispatch', flush=True)
-    if host_path == 'engine':
-        cluster_iterator.bind(ist_model.attach_engine(cluster_iterator.n_max))
-    res = ist.train_gat(ist_model, args, g, cluster_iterator, g.ndata['label'], g.ndata['val_mask'],
-                        g.ndata['test_mask'], log=log, host_path=host_path,
-                        eval_path=getattr(args, 'eval_path', 'layers'))
-    if args.rank == 0:
-        path = report(args, res, log=log)
-        if path is not None:
-            res['results_path'] = path
-    dist.destroy_process_group()
-    res['model'] = ist_model
-    return res
+    # (the wrapper and the loop as gist_amd.ist has them now: a stand-in there is what runs)
+    return main_family(args, dataset, log, setup, ist.DistributedGATWrapper, ist.train_gat, report)
 
 
 if __name__ == '__main__':

@@ -125,31 +125,6 @@ def movers(args, dev):
     return rows
 
 
-def own_x0_steps(models, args, it):
-    """gist_amd.ist._baseline_engine_steps without the shared X_0: every engine owns its layer-0 buffer and every further
-    site of the process gathers the batch's features into it."""
-    first = models[0].attach_engine(it.n_max)
-    it.bind(first)
-    for m in models[1:]:
-        m.attach_engine(it.n_max).attach_batcher(it.batcher)
-    for m in models:
-        m.engine.prefetch = len(models) == 1
-
-    def at_dispatch():
-        for m in models:
-            m.sub.reset_optimizer()
-
-    def step(si, batch):
-        if si > 0:
-            it.fill_features(batch, models[si].engine)
-        return models[si].engine.train_step(batch, args.lr, args.weight_decay)[0].clone()
-
-    def before_eval():
-        for m in models:
-            m.engine.check_extract()
-    return at_dispatch, step, before_eval
-
-
 def loop(args, dev):
     from gist_amd import _lib, datasets, ist
     from gist_amd.sampler import ClusterIter, EngineClusterIter
@@ -162,7 +137,7 @@ def loop(args, dev):
     lib = _lib.load()
     rows = []
     S, L = 2, 2
-    product_steps = ist._baseline_engine_steps
+    family = ist.DistributedBaselineGCNWrapper
     for H in ((32,) if args.quick else (256, 1024)):
         for use_ln in (True, False):
             runs = {}
@@ -183,7 +158,9 @@ def loop(args, dev):
 
             def one(name):
                 ws, it = runs[name]
-                ist._baseline_engine_steps = own_x0_steps if name == 'own_x0' else product_steps
+                # own X_0: gist_amd.ist._engine_steps with the family's SHARES_X0 off -- every engine owns its layer-0
+                # buffer and every further site of the process gathers the batch's features into it
+                family.SHARES_X0 = name != 'own_x0'
                 try:
                     torch.cuda.synchronize()
                     c0 = lib.gist_launch_count()
@@ -194,7 +171,7 @@ def loop(args, dev):
                     n = res['events'].count('step')
                     return 1e3 * res['total_time'] / n, n, (lib.gist_launch_count() - c0) / float(n)
                 finally:
-                    ist._baseline_engine_steps = product_steps
+                    family.SHARES_X0 = True
             for name in runs:
                 one(name)                                      # warm-up: one window of each
             win = {name: [] for name in runs}

@@ -10,7 +10,7 @@ on Reddit-like cluster batches (datasets.reddit_synth, psize 1500, batch size 20
     python scripts/gat_ist_step.py --out profiles/gat_ist_step.json
 
 An iteration = the S site steps on one batch, exactly what the loop runs between two schedule points: the tool takes the
-loop's own step functions (ist._gat_engine_steps / ist._module_steps) after an initial dispatch and a fresh
+loop's own step functions (ist._engine_steps / ist._module_steps) after an initial dispatch and a fresh
 optimiser, and calls nothing else -- no dispatch, no sync, no evaluation inside a window.  Both paths compute the same
 bits (tests/test_ist_gat_engine_gpu.py); this tool only times them.  Per shape (sites, width per head of the sub-GAT,
 merge; 4 heads, --n-layers layers, in = 602, 41 classes) it runs, after --warmup iterations of each path, --reps pairs
@@ -29,6 +29,7 @@ path's launches per iteration, set-up and warm-up excluded.
 """
 import argparse
 import csv
+import functools
 import json
 import os
 import random
@@ -86,7 +87,8 @@ class Paths(object):
         """-> (the engine path's wrappers, its iteration function, the module path's iteration function)"""
         from gist_amd import ist
         fns = []
-        for steps, it in ((ist._gat_engine_steps, self.eng_it), (ist._module_steps, self.mod_it)):
+        engine_steps = functools.partial(ist._engine_steps, ist.DistributedGATWrapper)
+        for steps, it in ((engine_steps, self.eng_it), (ist._module_steps, self.mod_it)):
             ws = self._wrappers(S, width, layers, merge)
             at_dispatch, step, _ = steps(ws, ws[0].args, it)
             at_dispatch()

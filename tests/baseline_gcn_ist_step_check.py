@@ -24,34 +24,10 @@ def schedule_args(S, H, L, p_drop, rank, use_layernorm):
                               weight_decay=5e-4, dropout=p_drop, rank=rank, use_layernorm=use_layernorm)
 
 
-def own_x0_steps(models, args, it):
-    """_baseline_engine_steps without the shared X_0: every engine owns its layer-0 buffer (x0=None) and every further
-    site of the process gathers the batch's features into it (fill_features) -- what the shared buffer saves."""
-    first = models[0].attach_engine(it.n_max)
-    it.bind(first)
-    for m in models[1:]:
-        m.attach_engine(it.n_max).attach_batcher(it.batcher)
-    for m in models:
-        m.engine.prefetch = len(models) == 1
-
-    def at_dispatch():
-        for m in models:
-            m.sub.reset_optimizer()
-
-    def step(si, batch):
-        if si > 0:
-            it.fill_features(batch, models[si].engine)
-        return models[si].engine.train_step(batch, args.lr, args.weight_decay)[0].clone()
-
-    def before_eval():
-        for m in models:
-            m.engine.check_extract()
-    return at_dispatch, step, before_eval
-
-
-def run_product(S, H, L, p_drop, use_layernorm, dev, ranks, comm_for, steps=None, around_train=None):
-    """Pass 1.  steps: a replacement for gist_amd.ist._baseline_engine_steps (own_x0_steps), None = the product's;
-    around_train = (before, after): called right before and right after train_baseline_gcn (the set-up -- the iterator's
+def run_product(S, H, L, p_drop, use_layernorm, dev, ranks, comm_for, own_x0=False, around_train=None):
+    """Pass 1.  own_x0: gist_amd.ist._engine_steps with the family's SHARES_X0 off -- every engine owns its layer-0 buffer
+    and every further site of the process gathers the batch's features into it (fill_features), what the shared buffer
+    saves; around_train = (before, after): called right before and right after train_baseline_gcn (the set-up -- the iterator's
     train subgraph, the initial dispatch -- is then behind, the device idle).
     Returns (failures, wrappers, records per site, train_baseline_gcn's result, facts)."""
     from gist_amd import ist
@@ -103,9 +79,10 @@ def run_product(S, H, L, p_drop, use_layernorm, dev, ranks, comm_for, steps=None
         rec.append(('sub', w.sub.params.clone()))
         hook(i, w, rec)
     gd = ds.g.to(dev)
-    saved = ist._baseline_engine_steps
-    if steps is not None:
-        ist._baseline_engine_steps = steps
+    family = ist.DistributedBaselineGCNWrapper
+    saved = family.SHARES_X0
+    if own_x0:
+        family.SHARES_X0 = False
     try:
         if around_train is not None:
             torch.cuda.synchronize(dev)
@@ -113,7 +90,7 @@ def run_product(S, H, L, p_drop, use_layernorm, dev, ranks, comm_for, steps=None
         res = ist.train_baseline_gcn(ws if local else ws[0], ws[0].args, gd, it, gd.ndata['label'], gd.ndata['val_mask'],
                                      gd.ndata['test_mask'], log=lambda *a, **k: None, host_path='step')
     finally:
-        ist._baseline_engine_steps = saved
+        family.SHARES_X0 = saved
     torch.cuda.synchronize(dev)
     if around_train is not None:
         around_train[1]()

@@ -154,13 +154,13 @@ def test_shared_x0(monkeypatch, L, H, use_layernorm, p_drop):
     step), no feature gather, S step calls -- and the bits of engines that own their layer-0 buffer and gather the features
     themselves, which cost one gist_gather_rows_f32 launch per further site and iteration."""
     from gist_amd import _lib, ist
-    from tests.baseline_gcn_ist_step_check import own_x0_steps, run_product
+    from tests.baseline_gcn_ist_step_check import run_product
     S, iters = 2, 12
     proxy = RecordingLib(_lib.load())
     monkeypatch.setattr(_lib, '_lib', proxy)
     launches = proxy._lib.gist_launch_count
 
-    def run(steps):
+    def run(own_x0):
         seen = {}
 
         def before():                                   # the loop alone is counted: set-up is behind
@@ -171,10 +171,10 @@ def test_shared_x0(monkeypatch, L, H, use_layernorm, p_drop):
         def after():
             seen.update(calls=dict(proxy.calls), flags=list(proxy.step_flags), launches=launches() - seen['launches'])
         errs, ws, recs, res, facts = run_product(S, H, L, p_drop, use_layernorm, DEV, [0, 1], ist.LocalCommGroup(S).handle,
-                                                 steps=steps, around_train=(before, after))
+                                                 own_x0=own_x0, around_train=(before, after))
         assert errs == [], errs[:8]
         return facts, seen['calls'], seen['flags'], seen['launches']
-    shared, calls, flags, n_shared = run(None)
+    shared, calls, flags, n_shared = run(False)
     extract = _lib.GIST_STEP_EXTRACT
     assert calls['gist_baseline_gcn_step'] == S * iters and 'gist_gather_rows_f32' not in calls
     # no extraction entry point beside the step's own extraction (the two host-side queries of a step launch nothing)
@@ -184,7 +184,7 @@ def test_shared_x0(monkeypatch, L, H, use_layernorm, p_drop):
     assert [bool(f & extract) for f in flags] == [True, False] * iters
     assert not any(f & _lib.GIST_STEP_EXTRACT_NEXT for f in flags)      # prefetch is off with S sites in one process
     assert shared['x0'][0] == shared['x0'][1]
-    own, calls_own, flags_own, n_own = run(own_x0_steps)
+    own, calls_own, flags_own, n_own = run(True)
     assert own['x0'][0] != own['x0'][1]
     assert calls_own['gist_baseline_gcn_step'] == S * iters and calls_own['gist_gather_rows_f32'] == (S - 1) * iters
     assert [bool(f & extract) for f in flags_own] == [True, False] * iters
