@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, 'csrc')
 # A/B runs against another build (GIST_LIB_OUT, loaded through GIST_LIB_PATH); the kernels have no build variants
 OUT = os.environ.get('GIST_LIB_OUT', os.path.join(HERE, 'libgist_hip.so'))
 EXTRA = os.environ.get('GIST_EXTRA_FLAGS', '').split()
-SOURCES = ['capi.hip', 'spmm.hip', 'spmm_mfma.hip', 'spmm_dense32.hip', 'gemm.hip', 'gemm_h3.hip', 'gemm_b3.hip', 'gemm_b3c.hip', 'gemm_plan.cpp', 'rowops.hip', 'classlayer.hip', 'subgraph.hip', 'step.hip',
+SOURCES = ['capi.hip', 'spmm.hip', 'spmm_mfma.hip', 'spmm_dense32.hip', 'gemm.hip', 'gemm_h3.hip', 'gemm_b3.hip', 'gemm_b3c.hip', 'gemm_bf16.hip', 'gemm_plan.cpp', 'rowops.hip', 'classlayer.hip', 'subgraph.hip', 'step.hip',
            'partition.hip', 'prep.hip', 'gat.hip', 'gat_step.hip', 'gat_eval.hip', 'lnall.hip', 'lnaffine.hip',
            'graphsage_step.hip', 'arena_moves.hip', 'gcntail.hip', 'baseline_gcn_step.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

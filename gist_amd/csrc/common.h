@@ -97,6 +97,9 @@ int b3_gemm_presplit(const char *name, const uint16_t *sa, const uint16_t *sb, c
 int gemm_slabs(int layout, const float *a, int64_t lda, const float *b, int64_t ldb, const float *bias, float *c,
                int64_t ldc, int64_t m, int64_t n, int64_t k, void *slabs, int64_t slab_bytes, int *n_slabs,
                hipStream_t st, GemmCall call = GEMM_CALL_SPLITS);      // GEMM_CALL_SLABS: `slabs` was sized by gemm_slab_bytes
+// gemm.hip: gist_gemm_nn_f32 for a caller with an epilogue of its own (in GEMM mode 3 it keeps the fp32 kernel)
+int gemm_nn_epilogue_call(const float *g, int64_t ldg, const float *w, int64_t ldw, float *z, int64_t ldz,
+                          int64_t m, int64_t n, int64_t k, void *workspace, int64_t workspace_bytes, hipStream_t st);
 // gemm.hip: dz = dy . w (NN) and dW = dy^T . z (TN, slabs) in one launch of the fp32 kernel's tiles
 bool gemm_dual_takes(int64_t m, int64_t n1, int64_t k1, int64_t lddy, int64_t ldw, int64_t ldz, int64_t lddz,
                      const float *dy, const float *w, const float *z, const float *dz);

@@ -588,7 +588,7 @@ int splitk_reduce(const char *name, const float *slabs, int64_t slab, int splits
 }
 
 // ---- host side: plan (gemm_plan.h), fill the kernel's argument struct, launch ---------------------------
-// gemm_h3.hip / gemm_b3.hip / gemm_b3c.hip: a gist_gemm_* call that the plan sends to their kernels
+// gemm_h3.hip / gemm_b3.hip / gemm_b3c.hip / gemm_bf16.hip: a gist_gemm_* call that the plan sends to their kernels
 int h3_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
             int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws, hipStream_t st);
 int b3_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
@@ -596,6 +596,8 @@ int b3_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const fl
 int b3c_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
              int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws,
              hipStream_t st, int *deferred);
+int x1_gemm(const char *name, const GemmPlan &pl, bool a_kc, bool b_kc, const float *a, int64_t lda, const float *b,
+            int64_t ldb, const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k, void *ws, hipStream_t st);
 
 template <bool A_KC, bool B_KC, int T>
 static int launch_tile(const char *name, GemmArgs &g, bool aligned, int splits, hipStream_t st) {
@@ -636,7 +638,7 @@ template <bool A_KC, bool B_KC>
 static int launch_gemm(const char *name, const float *a, int64_t lda, const float *b, int64_t ldb,
                        const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k,
                        void *ws, int64_t ws_bytes, hipStream_t st, int *deferred = nullptr,
-                       GemmCall call = GEMM_CALL_SPLITS) {
+                       GemmCall call = GEMM_CALL_SPLITS, int mode = -1) {      // mode < 0: the process-wide one, read here
     if (deferred) *deferred = 1;
     if (m < 0 || n < 0 || k < 0) { set_error("%s: negative size", name); return GIST_EINVAL; }
     if (m == 0 || n == 0) return GIST_OK;
@@ -649,12 +651,13 @@ static int launch_gemm(const char *name, const float *a, int64_t lda, const floa
         set_error("%s: leading dimension >= 2^22 elements", name); return GIST_EINVAL;
     }
     const bool aligned = aligned16(a) && (lda % 4 == 0) && lda >= 4 && aligned16(b) && (ldb % 4 == 0) && ldb >= 4;
-    const GemmPlan pl = plan_gemm(GemmQuery{A_KC, B_KC, m, n, k, gemm_mode(), aligned, ldc, call,
+    const GemmPlan pl = plan_gemm(GemmQuery{A_KC, B_KC, m, n, k, mode < 0 ? gemm_mode() : mode, aligned, ldc, call,
                                             deferred != nullptr, ws != nullptr && ws_bytes > 0 ? ws_bytes : 0, aligned16(ws)});
     switch (pl.path) {
         case GEMM_PATH_H3: return h3_gemm(name, pl, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, st);
         case GEMM_PATH_B3: return b3_gemm(name, pl, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, st);
         case GEMM_PATH_B3C: return b3c_gemm(name, pl, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, st, deferred);
+        case GEMM_PATH_BF16X1: return x1_gemm(name, pl, A_KC, B_KC, a, lda, b, ldb, bias, c, ldc, m, n, k, ws, st);
         default: break;
     }
     GemmArgs g;
@@ -724,6 +727,17 @@ int gemm_dual_nn_tn(const char *name, const float *dy, int64_t lddy, const float
                        n1b, tiles1, tiles2);
     *n_slabs = pl.splits;
     return launch_status(name);
+}
+
+// gist_gemm_nn_f32 for a caller with an epilogue of its own (gist_gemm_nn_dropout*_f32).  The mode is read ONCE here and
+// handed down: in mode 3 (bf16x1) such a call keeps the fp32 kernel -- a GEMM_CALL_SLABS plan, the record mode 0 gives --
+// and in every other mode it is the gist_gemm_nn_f32 call it always was.
+int gemm_nn_epilogue_call(const float *g, int64_t ldg, const float *w, int64_t ldw, float *z, int64_t ldz,
+                          int64_t m, int64_t n, int64_t k, void *workspace, int64_t workspace_bytes, hipStream_t st) {
+    GIST_REQUIRE(ldg >= k && ldw >= n && ldz >= n, "gist_gemm_nn_f32: leading dimension too small");
+    const int mode = gemm_mode();
+    return launch_gemm<true, false>("gist_gemm_nn_f32", g, ldg, w, ldw, nullptr, z, ldz, m, n, k, workspace, workspace_bytes, st,
+                                    nullptr, mode == 3 ? GEMM_CALL_SLABS : GEMM_CALL_SPLITS, mode);
 }
 
 int gemm_slabs(int layout, const float *a, int64_t lda, const float *b, int64_t ldb, const float *bias, float *c,

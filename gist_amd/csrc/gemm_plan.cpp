@@ -12,7 +12,9 @@
 
 namespace gist {
 
-static_assert(GEMM_PATH_B3C == GIST_GEMM_PATH_BF16X3_LOAD && GEMM_CALL_SLABS == GIST_GEMM_CALL_SLABS, "gemm_plan.h's enums are gist_hip.h's codes");
+static_assert(GEMM_PATH_B3C == GIST_GEMM_PATH_BF16X3_LOAD && GEMM_CALL_SLABS == GIST_GEMM_CALL_SLABS &&
+                  GEMM_PATH_BF16X1 == GIST_GEMM_PATH_BF16X1,
+              "gemm_plan.h's enums are gist_hip.h's codes");
 
 // ---- the process-wide mode ---------------------------------------------------------------------------
 static std::atomic<int> g_gemm_mode{-1};      // -1: read GIST_GEMM_MODE on first use
@@ -27,6 +29,7 @@ int gemm_mode() {
         if (e && (!strcmp(e, "f32") || !strcmp(e, "0"))) m = 0;
         else if (e && (!strcmp(e, "f16x3") || !strcmp(e, "1"))) m = 1;
         else if (e && (!strcmp(e, "bf16x3") || !strcmp(e, "2"))) m = 2;
+        else if (e && (!strcmp(e, "bf16x1") || !strcmp(e, "3"))) m = 3;
         int expected = -1;
         g_gemm_mode.compare_exchange_strong(expected, m, std::memory_order_relaxed);
         m = g_gemm_mode.load(std::memory_order_relaxed);
@@ -345,6 +348,57 @@ void plan_b3c(const GemmQuery &q, GemmPlan &p) {
     p.launches = 1 + (p.tail_splits > 1) + (p.splits > 1 && !q.deferred);
 }
 
+// ---- bf16x1: operands rounded to bf16 once by a cast pre-pass, one MFMA term (gemm_bf16.hip) -------------
+// Mode 3 only, and only a gist_gemm_* call that reduces its own k slices (GEMM_CALL_SPLITS, not deferred): the step's
+// slab and kept calls and the fused-epilogue entry points get the record mode 0 gives them.  By default a shape comes
+// here from 2.5 GFLOP with m, n, k >= 64, an output that is not mostly tile padding and, k slices included, at least 128
+// workgroups.  Measured per call with the pre-pass in the call, against the fp32 kernel (profiles/gemm_bf16x1.md): 2046 x
+// 512 x 1204 (2.52 GFLOP) 25.2 -> 22.4 us, its TN and NN forms too, and everything larger wins, up to 4.2x; 1024 x 1024 x 1024
+// (2.15 GFLOP) loses in every layout (21.5 -> 22.6 .. 24.7 us), as do 2046 x 41 x 8192 and everything below 1.1 GFLOP.  Tuning
+// hook GIST_TUNE_BF16X1: 1 = never, 2 = every shape with m, n, k >= 1.
+// k slices: an output with fewer than 384 tiles of 128 x 128 (two workgroups per CU: 512 slots) is cut along k into
+// slices of >= 8 k tiles (>= 2 under the hook), whose fp32 slabs splitk_reduce sums in slice order (+ bias).
+int x1_splits(int64_t m, int64_t n, int64_t k, bool any_shape) {
+    const int64_t tiles = ceil_div(m, X1_T) * ceil_div(n, X1_T), n_kt = x1_kpad(k) / X1_BK;
+    const int forced = (int)tune(GIST_TUNE_GEMM_SPLITS);
+    int64_t s = forced > 0 ? forced : (tiles >= 384 ? 1 : 512 / tiles);
+    const int64_t min_kt = any_shape ? 2 : 8;
+    if (forced <= 0 && s > n_kt / min_kt) s = n_kt / min_kt;
+    if (s > n_kt) s = n_kt;
+    if (s > 64) s = 64;
+    if (s < 1) s = 1;
+    return (int)ceil_div(n_kt, ceil_div(n_kt, s));
+}
+
+bool plan_x1(const GemmQuery &q, GemmPlan &p) {
+    const int hook = (int)tune(GIST_TUNE_BF16X1);
+    const int64_t m = q.m, n = q.n, k = q.k;
+    if (q.mode != 3 || hook == 1 || q.call != GEMM_CALL_SPLITS || q.deferred) return false;
+    // 32-bit byte offsets of the DMA staging (128 rows x pitch) and of the slab stores (128 rows x n); the grid
+    if (m < 1 || n < 1 || k < 1 || x1_kpad(k) >= (1LL << 22) || n >= (1LL << 22)) return false;
+    if (ceil_div(m, X1_T) * ceil_div(n, X1_T) >= (1LL << 30)) return false;
+    const int splits = x1_splits(m, n, k, hook == 2);
+    const int64_t tiles = ceil_div(m, X1_T) * ceil_div(n, X1_T);
+    if (hook != 2) {
+        if (m < 64 || n < 64 || k < 64) return false;
+        if (tiles * splits < 128) return false;
+        if ((double)m * (double)n < 0.6 * (double)(tiles * X1_T * X1_T)) return false;      // mostly padding
+        if (2.0 * (double)m * (double)n * (double)k < 2.5e9) return false;
+    }
+    const int64_t n_kt = x1_kpad(k) / X1_BK, kt_per = ceil_div(n_kt, splits);
+    p.path = GEMM_PATH_BF16X1;
+    p.tile_m = p.tile_n = X1_T;
+    p.splits = splits; p.k_per_split = kt_per * X1_BK;
+    p.whole_tiles = (int32_t)tiles; p.tail_splits = 1;
+    p.operand_offset = 0;
+    p.operand_bytes = ceil_div((m + n) * x1_kpad(k) * 2, 256) * 256;
+    p.scratch_offset = p.operand_bytes;
+    p.scratch_bytes = splits > 1 ? (int64_t)splits * m * n * 4 : 0;
+    p.workspace_bytes = p.operand_bytes + p.scratch_bytes;
+    p.launches = 2 + (splits > 1);      // the cast of both operands, the main kernel, the slab sum
+    return q.scratch_aligned && fits(q, p.workspace_bytes);
+}
+
 }  // namespace
 
 GemmPlan plan_gemm(const GemmQuery &q) {
@@ -361,6 +415,8 @@ GemmPlan plan_gemm(const GemmQuery &q) {
     }
     if (q.call != GEMM_CALL_SLABS && q.mode == 2 && plan_b3(q, p) && q.scratch_aligned && fits(q, p.workspace_bytes)) return p;
     p = none;
+    if (q.mode == 3 && plan_x1(q, p)) return p;
+    p = none;
     if (b3c_takes(q)) plan_b3c(q, p);
     else plan_f32(q, p);
     return p;
@@ -372,6 +428,7 @@ GemmDualPlan plan_gemm_dual(int64_t m, int64_t n1, int64_t k1, int mode, int64_t
     GemmDualPlan d{false, 1, 64};
     if (m <= 0 || n1 <= 0 || k1 <= 0 || (int)tune(GIST_TUNE_GEMM_DUAL) == 1) return d;
     if (tune(GIST_TUNE_GEMM_TILE) != 0.0 || tune(GIST_TUNE_GEMM_SPLITS) != 0.0) return d;
+    if (mode == 3) mode = 0;      // (bf16x1: the fused pair stays on the fp32 kernel, with the shapes mode 0 gives it)
     // neither product may be one that a gist_gemm_* call would run on split operands
     const GemmPlan nn = plan_gemm(gemm_query(1, m, n1, k1, mode, GEMM_CALL_SPLITS, false));
     const GemmPlan tn = plan_gemm(gemm_query(2, k1, n1, m, mode, GEMM_CALL_SPLITS, true));
@@ -393,8 +450,8 @@ int64_t gemm_slab_bytes(int layout, int64_t m, int64_t n, int64_t k, int mode) {
 }  // namespace gist
 
 extern "C" int gist_gemm_set_mode(int mode) {
-    GIST_REQUIRE(mode >= 0 && mode <= 2,
-                 "gist_gemm_set_mode: mode must be 0 (fp32 MFMA), 1 (f16x3 split) or 2 (bf16x3 split)");
+    GIST_REQUIRE(mode >= 0 && mode <= 3,
+                 "gist_gemm_set_mode: mode must be 0 (fp32 MFMA), 1 (f16x3 split), 2 (bf16x3 split) or 3 (bf16x1)");
     gist::g_gemm_mode.store(mode, std::memory_order_relaxed);
     return GIST_OK;
 }

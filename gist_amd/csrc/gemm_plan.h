@@ -9,7 +9,7 @@
 
 namespace gist {
 
-int gemm_mode();                      // 0 fp32 MFMA, 1 f16x3, 2 bf16x3 (gist_gemm_set_mode; GIST_GEMM_MODE at first use)
+int gemm_mode();                      // 0 fp32 MFMA, 1 f16x3, 2 bf16x3, 3 bf16x1 (gist_gemm_set_mode; GIST_GEMM_MODE at first use)
 
 // geometry of the kernels that the planner and the callers that lay out split operands share
 constexpr int H3_T = 128;             // f16x3: block tile edge (A tile 64 or 128 rows)
@@ -21,9 +21,12 @@ constexpr int C3_BK = 32;             // convert-on-load: k per tile
 // split operand = [rows][kpad(k)] elements: f16x3 32-bit words (+ one scale per row), bf16x3 6 bytes
 static inline int64_t h3_kpad(int64_t k) { return (k + H3_BK - 1) / H3_BK * H3_BK; }
 static inline int64_t b3_kpad(int64_t k) { return (k + 2 * B3_BK - 1) / (2 * B3_BK) * (2 * B3_BK); }   // an even number of k tiles
+// bf16x1 (gemm_bf16.hip): operand image = [rows][x1_kpad(k)] bf16, zeros past k; 128 x 128 tile, 64 k per tile
+constexpr int X1_T = 128, X1_BK = 64;
+static inline int64_t x1_kpad(int64_t k) { return (k + X1_BK - 1) / X1_BK * X1_BK; }
 
 // (paths and kinds of call: include/gist_hip.h, GIST_GEMM_PATH_* and GIST_GEMM_CALL_*)
-enum GemmPath { GEMM_PATH_F32, GEMM_PATH_H3, GEMM_PATH_B3, GEMM_PATH_B3C };
+enum GemmPath { GEMM_PATH_F32, GEMM_PATH_H3, GEMM_PATH_B3, GEMM_PATH_B3C, GEMM_PATH_BF16X1 };
 enum GemmCall { GEMM_CALL_SPLITS, GEMM_CALL_KEPT, GEMM_CALL_SLABS };
 constexpr int64_t kScratchUnbounded = -1;
 

@@ -1107,7 +1107,8 @@ int gemm_nn_dropout_ex(const char *name, const float *g, int64_t ldg, const floa
     // (offset even and n % 4 == 0 are more than a fast-path choice: narrow_nn_drop_kernel ASSUMES an even first index of
     // every quad -- __builtin_assume -- so neither condition may be relaxed without that line)
     if (!narrow) {      // any other shape: the projection kernel, then the mask in place
-        int rc = gist_gemm_nn_f32(g, ldg, w, ldw, z, ldz, m, n, k, workspace, workspace_bytes, st);
+        // (GEMM mode 3, bf16x1, keeps this entry point on the fp32 kernel: gemm_nn_epilogue_call decides, once)
+        int rc = gemm_nn_epilogue_call(g, ldg, w, ldw, z, ldz, m, n, k, workspace, workspace_bytes, st);
         if (rc == GIST_OK && p != 0.f) rc = gist_dropout_f32(z, ldz, m, n, p, seed, offset, st);
         if (rc == GIST_OK && dy_col_partials != nullptr) rc = colsum_rows16(g, ldg, m, k, dy_col_partials, false, st);
         return rc;

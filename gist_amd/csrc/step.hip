@@ -631,8 +631,12 @@ int forward(const gist_step_plan *p, const StepDecisions &d, const StepState &x,
                 GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
                                     fl.logit_slabs, fl.logit_bytes, &logit_slabs, st, GEMM_CALL_SLABS));
             } else if (d.defer && k + 1 < L1 && fl.y_slabs != nullptr &&
-                       !splits_operands(plan_gemm(gemm_query(0, n, l.n_out, 2 * l.n_in, d.gemm_mode, GEMM_CALL_SPLITS, true)))) {
-                // the LayerNorm sums the slabs (a projection the per-call split paths take keeps their workspace)
+                       !splits_operands(plan_gemm(gemm_query(0, n, l.n_out, 2 * l.n_in, d.gemm_mode, GEMM_CALL_SPLITS, false)))) {
+                // the LayerNorm sums the slabs (a projection the per-call split paths take keeps their workspace).  The query is
+                // gist_gemm_splits_operands' own -- a call that reduces its own slices, not a deferred one -- because that is
+                // the question the op-by-op twin asks (hip.gemm_splits_own_operands) and the one the workspace was sized by:
+                // modes 0-2 answer both forms alike, mode 3 (bf16x1) takes no deferred call and would send the step to slabs
+                // where the twin and the size query say gist_gemm_nt_f32
                 GIST_TRY(gemm_slabs(0, l.Z, l.ldz, l.W, 2 * l.n_in, l.b, l.Y, l.ldy, n, l.n_out, 2 * l.n_in,
                                     fl.y_slabs, fl.y_bytes, &y_slabs_n, st, GEMM_CALL_SLABS));
                 y_slabs = fl.y_slabs;

@@ -194,19 +194,25 @@ def _ws_for(m, n, k, device):
     return w.data_ptr(), w.numel()
 
 
+GEMM_MODES = ('f32', 'f16x3', 'bf16x3', 'bf16x1')
+
+
 def gemm_mode(mode=None):
     """Get (and with an argument, set) how large projections form their products
     (include/gist_hip.h gist_gemm_set_mode): 'bf16x3' (default) = three bf16 pieces per fp32 operand
     (all 24 bits), six cross terms on the bf16 matrix cores, fp32-MFMA-level error; 'f32' =
     v_mfma_f32_32x32x2_f32 everywhere, fp32 products like the reference; 'f16x3' (opt-in) = two f16
-    halves per operand (22 bits).  Small shapes are fp32 MFMA in every mode.  Process-wide."""
+    halves per operand (22 bits); 'bf16x1' (opt-in) = ordinary mixed precision: every operand rounded once to bf16
+    (nearest even), one term on the bf16 matrix cores, fp32 accumulation, outputs, master weights and optimiser -- the
+    error of an 8-bit significand, not fp32's.  Small shapes are fp32 MFMA in every mode.  Process-wide: set the
+    mode before building an engine, which sizes its workspaces from the library's queries in the mode of that moment."""
     L = _lib.load()
     if mode is not None:
-        code = {'f32': 0, 'f16x3': 1, 'bf16x3': 2, 0: 0, 1: 1, 2: 2}.get(mode)
+        code = {'f32': 0, 'f16x3': 1, 'bf16x3': 2, 'bf16x1': 3, 0: 0, 1: 1, 2: 2, 3: 3}.get(mode)
         if code is None:
-            raise ValueError("gist_amd: gemm mode must be 'f32', 'f16x3' or 'bf16x3'")
+            raise ValueError("gist_amd: gemm mode must be 'f32', 'f16x3', 'bf16x3' or 'bf16x1'")
         _lib.check(L.gist_gemm_set_mode(code), 'gist_gemm_set_mode')
-    return ('f32', 'f16x3', 'bf16x3')[L.gist_gemm_get_mode()]
+    return GEMM_MODES[L.gist_gemm_get_mode()]
 
 
 def gemm_splits_own_operands(m, n, k):
@@ -215,7 +221,7 @@ def gemm_splits_own_operands(m, n, k):
 
 
 GEMM_LAYOUTS = {'nt': 0, 'nn': 1, 'tn': 2}
-GEMM_PATHS = ('f32', 'f16x3', 'bf16x3', 'bf16x3_load')
+GEMM_PATHS = ('f32', 'f16x3', 'bf16x3', 'bf16x3_load', 'bf16x1')
 GEMM_CALLS = {'splits': 0, 'kept': 1, 'slabs': 2}
 
 

@@ -255,7 +255,7 @@ int gist_gemm_slabs_f32(int layout, const float *a, int64_t lda, const float *b,
                         const float *bias, float *c, int64_t ldc, int64_t m, int64_t n, int64_t k,
                         void *slabs, int64_t slab_bytes, int32_t *n_slabs, gist_stream_t stream);
 
-/* How the three entry points above form their products (GIST_GEMM_MODE = bf16x3 | f32 | f16x3 is
+/* How the three entry points above form their products (GIST_GEMM_MODE = bf16x3 | f32 | f16x3 | bf16x1 is
  * read once at first use; gist_gemm_set_mode overrides it; process-wide: set it before sizing
  * workspaces).  Inputs, outputs and accumulation are fp32 in every mode, and small or skinny shapes
  * always run on v_mfma_f32_32x32x2_f32.
@@ -276,7 +276,20 @@ int gist_gemm_slabs_f32(int layout, const float *a, int64_t lda, const float *b,
  *     v_mfma_f32_16x16x32_f16 -- error at mode 0's level on the step's operands
  *     (tests/test_gemm_h3_gpu.py) at about half the time, but narrower operand arithmetic than fp32
  *     by construction.
- * In the split modes a NaN or Inf in an operand row makes the corresponding output row / column
+ *   Mode 3, bf16x1 (opt-in): ordinary mixed precision.  Each fp32 operand element is rounded ONCE to bf16, to nearest
+ *     with ties to even (8 significant bits, fp32's exponent range: a NaN stays a NaN, a finite value at or beyond
+ *     bf16's range becomes +-Inf); the products are exact in fp32 and are summed in fp32 on v_mfma_f32_16x16x32_bf16;
+ *     bias, outputs, master weights and the optimiser stay fp32.  One MFMA term where mode 2 issues six: the error is
+ *     that of the operand rounding, ~2^-9 relative per operand, NOT mode 0's.  Taken by gist_gemm_nt_f32 / _nn_f32 /
+ *     _tn_f32 calls from 2.5 GFLOP with m, n, k >= 64, at least 128 workgroups of 128 x 128 tiles x k slices, an output
+ *     that fills at least 0.6 of its tiles (not mostly tile padding), n < 2^22 and k (padded to a multiple of 64) < 2^22 -- anything else runs as in mode 0 -- operands
+ *     of any alignment (tuning hook GIST_TUNE_BF16X1), with a workspace of gist_gemm_workspace_bytes: 2 bytes per
+ *     operand element (k padded to a multiple of 64) plus the fp32 slabs of the k slices.  Smaller and skinny shapes,
+ *     gist_gemm_slabs_f32, the fused-epilogue entry points (gist_gemm_nn_dropout*_f32, gist_gemm_nn_tn_dual_f32,
+ *     gist_class_layer_f32) and the slab projections inside gist_sage_step run as in mode 0, and gist_sage_step keeps
+ *     no split operands (gist_step_h3_workspace_bytes_mode(plan, 3) == 0).  Like every mode: set it before building an
+ *     engine, which sizes its workspaces from these queries.
+ * In the split modes and in mode 3 a NaN or Inf in an operand row makes the corresponding output row / column
  * non-finite (NaN where fp32 would give Inf) and leaves all other outputs unchanged.  All three
  * replace the same call, self.linear(h), cluster_gcn/modules.py:233, and its autograd.
  * The aggregations (gist_spmm_*) and non-finite sources: the gather kernels (lane-group, row-split, LDS-staged) make
@@ -293,6 +306,7 @@ int gist_gemm_get_mode(void);
 #define GIST_GEMM_PATH_F16X3 1        /* mode 1, operands split by a pre-pass                            */
 #define GIST_GEMM_PATH_BF16X3 2       /* mode 2, operands split by a pre-pass (or kept by gist_sage_step) */
 #define GIST_GEMM_PATH_BF16X3_LOAD 3  /* mode 2, operands converted on load                              */
+#define GIST_GEMM_PATH_BF16X1 4       /* mode 3, operands rounded to bf16 once by a cast pre-pass         */
 #define GIST_GEMM_CALL_SPLITS 0       /* a gist_gemm_* call: a pre-split path splits its operands into the workspace */
 #define GIST_GEMM_CALL_KEPT 1         /* gist_sage_step's kept pre-split operands; scratch = the slab buffer        */
 #define GIST_GEMM_CALL_SLABS 2        /* a gist_gemm_* call whose workspace is a slab buffer: no room for operands  */
@@ -354,7 +368,8 @@ int gist_b3_split_f32(const float *src, int64_t ld, int64_t rows, int64_t cols, 
 #define GIST_TUNE_B3_TAIL 14      /* bf16x3 GEMM: 1 = no k slices for the tiles past the last full round of 256 (whole tiles) */
 #define GIST_TUNE_B3_WIDE 15      /* bf16x3 GEMM: 1 = never the 256x256 output tile (always 256x128) */
 #define GIST_TUNE_ADAM_STREAM 16 /* gist_adam_segments_f32: 1 = one short workgroup per 1024 elements, dword loads (not the span kernel) */
-#define GIST_TUNE_COUNT 17
+#define GIST_TUNE_BF16X1 17      /* bf16x1 GEMM (mode 3): 1 = never, 2 = every gist_gemm_* call with m, n, k >= 1 */
+#define GIST_TUNE_COUNT 18
 int gist_tuning_set(int knob, double value);
 double gist_tuning_get(int knob);
 
