@@ -14,7 +14,7 @@ one process, each window between two HIP events and ended by a synchronise:
   sync       sync_apply() over a filled `gathered`: the scatters, the shared bias' mean and its copy into the sub-model
 
 A time per call is the larger of the host's issue time and the device time per call.  The report gives the median ms per
-call, every window, and the launches the library issued per call (gist_launch_count; the copy of the shared bias and the
+call, every window, and the launches the library issued per call (its launch counter; the copy of the shared bias and the
 index uploads are torch's and not in it).  No speed-up is fixed in advance: a row says "shorter" only where EVERY grouped
 window is shorter than EVERY per-tensor window, else that the windows overlap.
 
@@ -26,7 +26,7 @@ is shorter than every module window; the module run's own window spread (max - m
 
 Shared X_0: the 'step' loop as the product runs it (every site's engine reads the first engine's layer-0 input buffer)
 against the same loop with engines that own their buffer (x0=None) and gather the batch's features into it
-(EngineClusterIter.fill_features): launches per iteration of both (gist_launch_count over the window, dispatches, syncs and
+(EngineClusterIter.fill_features): launches per iteration of both (its launch counter over the window, dispatches, syncs and
 evaluations included -- they are the same on both sides) and ms per iteration, windows alternating, the same rule.
 """
 import argparse
@@ -42,6 +42,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from scripts.measure import COUNTER, alternate, event_window, launches_during, require_gpu, split_counts, verdict
+
 FIN, NCLS = 602, 41
 SITES, LAYERS, WIDTHS = (2, 4, 8), (2, 4), (256, 1024, 4096)
 
@@ -55,28 +57,6 @@ def wrapper(S, L, H, dev, blocks):
     w.base.params.copy_(torch.randn(w.base.numel, device=dev, generator=gen))
     w.gathered.copy_(torch.randn(w.gathered.numel(), device=dev, generator=gen))
     return w
-
-
-def window(fn, iters):
-    from gist_amd import _lib
-    L = _lib.load()
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0 = L.gist_launch_count()
-    a.record()
-    for _ in range(iters):
-        fn()
-    z.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(z) / iters, (L.gist_launch_count() - c0) / float(iters)
-
-
-def verdict(a, b, a_name, b_name):
-    """The only claim a row may make: every window of a against every window of b."""
-    if max(a) < min(b):
-        return 'every %s window is shorter than every %s window' % (a_name, b_name)
-    if max(b) < min(a):
-        return 'every %s window is shorter than every %s window' % (b_name, a_name)
-    return 'the windows overlap'
 
 
 def movers(args, dev):
@@ -101,21 +81,18 @@ def movers(args, dev):
                         tf()
                     torch.cuda.synchronize()
                     # calls per window: at least --iters, and enough for a window of --min-window-ms (from a short one)
-                    gi = max(args.iters, int(args.min_window_ms / window(gf, 50)[0]) + 1)
-                    ti = max(args.iters, int(args.min_window_ms / window(tf, 50)[0]) + 1)
-                    gw, tw, gl, tl = [], [], [], []
-                    for _ in range(args.reps):             # alternating: a drift of the box hits both movers alike
-                        ms, n = window(gf, gi)
-                        gw.append(ms)
-                        gl.append(n)
-                        ms, n = window(tf, ti)
-                        tw.append(ms)
-                        tl.append(n)
+                    calls = {gf: max(args.iters, int(args.min_window_ms / event_window(gf, 50)) + 1),
+                             tf: max(args.iters, int(args.min_window_ms / event_window(tf, 50)) + 1)}
+                    gi, ti = calls[gf], calls[tf]
+                    # alternating: a drift of the box hits both movers alike
+                    ms, nl = split_counts(alternate({'grouped': gf, 'per_tensor': tf},
+                                                    lambda f: event_window(f, calls[f], count=True), args.reps))
+                    gw, tw, gl, tl = ms['grouped'], ms['per_tensor'], nl['grouped'], nl['per_tensor']
                     tm, gm = float(np.median(tw)), float(np.median(gw))
                     rows.append(dict(op=name, S=S, L=L, H=H, grouped_ms=gm, per_tensor_ms=tm, grouped_windows=gw,
                                      per_tensor_windows=tw, grouped_calls=gi, per_tensor_calls=ti,
                                      grouped_launches=float(np.median(gl)), per_tensor_launches=float(np.median(tl)),
-                                     verdict=verdict(gw, tw, 'grouped', 'per-tensor')))
+                                     verdict=verdict(gw, tw, 'grouped', 'per-tensor', style='windows')))
                     print('%-8s S=%d L=%d H=%-4d grouped %.4f ms  per-tensor %.4f ms  (%s)' % (name, S, L, H, gm, tm,
                                                                                            rows[-1]['verdict']), flush=True)
                 if not torch.equal(g.base.params, t.base.params):
@@ -126,7 +103,7 @@ def movers(args, dev):
 
 
 def loop(args, dev):
-    from gist_amd import _lib, datasets, ist
+    from gist_amd import datasets, ist
     from gist_amd.sampler import ClusterIter, EngineClusterIter
     ds = datasets.toy(train_frac=1.0) if args.quick else datasets.reddit_synth()
     psize, bsize = (len(ds.par_li), 4) if args.quick else (1500, 20)
@@ -134,7 +111,6 @@ def loop(args, dev):
     nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
     fin, ncls = g.ndata['feat'].shape[1], ds.num_classes
     gd = g.to(dev)
-    lib = _lib.load()
     rows = []
     S, L = 2, 2
     family = ist.DistributedBaselineGCNWrapper
@@ -163,31 +139,27 @@ def loop(args, dev):
                 family.SHARES_X0 = name != 'own_x0'
                 try:
                     torch.cuda.synchronize()
-                    c0 = lib.gist_launch_count()
-                    res = ist.train_baseline_gcn(ws, ws[0].args, gd, it, gd.ndata['label'], gd.ndata['val_mask'],
-                                                 gd.ndata['test_mask'], log=lambda *a, **k: None,
-                                                 host_path='module' if name == 'module' else 'step')
+                    res, launched = launches_during(lambda: ist.train_baseline_gcn(
+                        ws, ws[0].args, gd, it, gd.ndata['label'], gd.ndata['val_mask'], gd.ndata['test_mask'],
+                        log=lambda *a, **k: None, host_path='module' if name == 'module' else 'step'))
                     torch.cuda.synchronize()
                     n = res['events'].count('step')
-                    return 1e3 * res['total_time'] / n, n, (lib.gist_launch_count() - c0) / float(n)
+                    return 1e3 * res['total_time'] / n, n, launched / float(n)
                 finally:
                     family.SHARES_X0 = True
             for name in runs:
                 one(name)                                      # warm-up: one window of each
-            win = {name: [] for name in runs}
-            launches = {}
-            for _ in range(args.loop_reps):                    # alternating
-                for name in runs:
-                    ms, n, per_iter = one(name)
-                    win[name].append(ms)
-                    launches[name] = per_iter
+            wins = alternate({name: name for name in runs}, one, args.loop_reps)
+            win = {name: [w[0] for w in v] for name, v in wins.items()}
+            launches = {name: v[-1][2] for name, v in wins.items()}
+            n = wins['own_x0'][-1][1]
             if runs['step'][0][1].engine.X[0].data_ptr() != runs['step'][0][0].engine.X[0].data_ptr():
                 raise SystemExit('baseline_gcn_ist: the step loop\'s engines do not share X_0')
             rows.append(dict(S=S, L=L, H=H, use_layernorm=use_ln, iterations=n, windows=win, launches=launches,
                              median={k: float(np.median(v)) for k, v in win.items()},
                              module_spread=max(win['module']) - min(win['module']),
-                             step_vs_module=verdict(win['step'], win['module'], 'step', 'module'),
-                             shared_vs_own=verdict(win['step'], win['own_x0'], 'shared-X_0', 'own-X_0')))
+                             step_vs_module=verdict(win['step'], win['module'], 'step', 'module', style='windows'),
+                             shared_vs_own=verdict(win['step'], win['own_x0'], 'shared-X_0', 'own-X_0', style='windows')))
             print('loop H=%d use_layernorm=%s: step %.4f ms / iteration, module %.4f (%s); own X_0 %.4f (%s)' % (
                 H, use_ln, rows[-1]['median']['step'], rows[-1]['median']['module'], rows[-1]['step_vs_module'],
                 rows[-1]['median']['own_x0'], rows[-1]['shared_vs_own']), flush=True)
@@ -210,7 +182,7 @@ def main():
     ap.add_argument('--loop-reps', type=int, default=3)
     ap.add_argument('--quick', action='store_true', help='the toy graph for the loop (rehearsal)')
     args = ap.parse_args()
-    assert torch.cuda.is_available(), 'baseline_gcn_ist.py measures on the GPU'
+    require_gpu('baseline_gcn_ist.py')
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
     t0 = time.time()
@@ -220,9 +192,9 @@ def main():
            '',
            'Tool: `scripts/baseline_gcn_ist.py` on %s; %d windows per mover and operation, alternating, each of at least %d '
            'calls and at least %g ms, after %d warm-up calls and a calibration window; in = %d, %d classes.  Times in ms per '
-           'call; launches = the library\'s own (gist_launch_count) per call -- the copy of the shared bias (one torch kernel '
+           'call; launches = the library\'s own (%s) per call -- the copy of the shared bias (one torch kernel '
            'per sync on either mover) and the index uploads are not in it.'
-           % (torch.cuda.get_device_name(0), args.reps, args.iters, args.min_window_ms, args.warmup, FIN, NCLS), '',
+           % (torch.cuda.get_device_name(0), args.reps, args.iters, args.min_window_ms, args.warmup, FIN, NCLS, COUNTER), '',
            'What a figure is: a window is a run of back-to-back calls ended by one synchronise, so a time per call is the '
            'larger of the host\'s issue time per call and the device time per call.  The last column is the only claim a '
            'row makes: every window of one mover against every window of the other.  Every window is listed below.', '',

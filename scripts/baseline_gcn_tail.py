@@ -20,9 +20,7 @@ and nothing else; --trace-stats hands the two kernel_stats csv files to the page
 import argparse
 import csv
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -31,6 +29,9 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from scripts.measure import (alternate, cycle, event_window, host_window, reference_loop, require_gpu, summary,
+                             write_lines)
 
 ROWS, WIDTHS, P, SEED = 3100, (256, 1024, 4096), 0.2, 5
 TRACE_CALLS, TRACE_WIDTH = 10, 1024
@@ -73,16 +74,6 @@ def paths(x, b, p):
     return {'fused': fused, 'composed': composed}
 
 
-def window(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / iters      # us per call
-
-
 def make(n, d, dev):
     gen = torch.Generator(device=dev).manual_seed(d)
     x = torch.randn(n, d, device=dev, generator=gen, requires_grad=True)
@@ -121,18 +112,9 @@ def measure(n, d, dev, warmup, iters, reps):
             for _ in range(warmup):
                 f()
         torch.cuda.synchronize()
-        times = {name: [] for name in fns}
-        for _ in range(reps):
-            for name, f in fns.items():      # alternating
-                times[name].append(window(f, iters))
-        res[mode] = {name: (statistics.median(t), min(t), max(t)) for name, t in times.items()}
+        times = alternate(fns, lambda f: event_window(f, iters) * 1e3, reps)      # us per call
+        res[mode] = {name: summary(t) for name, t in times.items()}
     return res, diff
-
-
-def cycle(it):
-    while True:
-        for b in it:
-            yield b
 
 
 def loop_iteration(ds, it, hidden, tail, dev):
@@ -141,28 +123,7 @@ def loop_iteration(ds, it, hidden, tail, dev):
     from gist_amd.optim import Adam
     torch.manual_seed(0)
     model = BaselineGCN(ds.g.ndata['feat'].shape[1], hidden, ds.num_classes, LAYERS, F.relu, P, True, tail=tail).to(dev)
-    loss_f, opt, batches = CrossEntropyLoss(), Adam(model.parameters(), lr=LR), cycle(it)
-
-    def one():                                  # cluster_gcn.py:96-105, as main_module_path runs it
-        cluster = next(batches).to(torch.cuda.current_device())
-        model.train()
-        pred = model(cluster)
-        labels, mask = cluster.ndata['label'], cluster.ndata['train_mask']
-        loss = loss_f(pred[mask], labels[mask])
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        return loss
-    return one
-
-
-def wall_window(fn, iters, dev):
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize(dev)
-    return (time.perf_counter() - t0) * 1e3 / iters
+    return reference_loop(model, cycle(it), CrossEntropyLoss(), Adam(model.parameters(), lr=LR), dev)
 
 
 def module_loop(dev, nodes, warmup, iters, reps):
@@ -181,11 +142,8 @@ def module_loop(dev, nodes, warmup, iters, reps):
         for f in fns.values():
             for _ in range(warmup):
                 f()
-        times = {k: [] for k in fns}
-        for _ in range(reps):
-            for k, f in fns.items():
-                times[k].append(wall_window(f, iters, dev))
-        rows.append((hidden,) + tuple((statistics.median(times[k]), min(times[k]), max(times[k])) for k in ('fused', 'composed')))
+        times = alternate(fns, lambda f: host_window(f, iters, dev), reps)
+        rows.append((hidden,) + tuple(summary(times[k]) for k in ('fused', 'composed')))
     return ds, rows
 
 
@@ -219,8 +177,7 @@ def main():
     ap.add_argument('--trace', choices=['fused', 'composed'])
     ap.add_argument('--trace-stats', nargs=2, metavar=('FUSED_CSV', 'COMPOSED_CSV'))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('baseline_gcn_tail.py measures on the GPU; there is none here')
+    require_gpu('baseline_gcn_tail.py')
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
     if a.trace:
@@ -267,10 +224,7 @@ def main():
                                                              sum(r[1] for r in rows) / float(TRACE_CALLS)), '',
                   '| kernel | calls | total us |', '|---|---|---|']
             L += ['| `%s` | %d | %.1f |' % (r[0][:90], r[1], r[2] / 1e3) for r in rows] + ['']
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as fh:
-        fh.write('\n'.join(L) + '\n')
-    print('\n'.join(L))
+    write_lines(a.out, L)
 
 
 if __name__ == '__main__':

@@ -23,6 +23,7 @@ ap.add_argument('--localities', type=str, default='0,0.8,1')
 ap.add_argument('--pair-min-edges', type=int, default=300)
 args = ap.parse_args()
 
+from scripts.measure import event_window
 from gist_amd import datasets, hip
 from gist_amd.engine import ParamArena, dims_for
 from gist_amd.trainer import FullGraphEvaluator
@@ -33,11 +34,7 @@ N_BLOCKS = 2278
 
 def timeit(f, iters=5):
     f(); torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); f(); b.record(); torch.cuda.synchronize(); ts.append(a.elapsed_time(b))
-    ts.sort()
+    ts = sorted(event_window(f, 1) for _ in range(iters))
     return ts[len(ts) // 2]
 
 

@@ -28,21 +28,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-
-def window(fn, iters):
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    z.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(z) / iters
+from scripts.measure import alternate, event_window, every_window_shorter, require_gpu
 
 
 def median_of(fn, iters, reps):
     fn()
     torch.cuda.synchronize()
-    return float(np.median([window(fn, iters) for _ in range(reps)]))
+    return float(np.median([event_window(fn, iters) for _ in range(reps)]))
 
 
 def main():
@@ -55,7 +47,7 @@ def main():
     ap.add_argument('--shapes', default='', help='heads:width:merge,... (default: all)')
     ap.add_argument('--notes', default='')
     args = ap.parse_args()
-    assert torch.cuda.is_available(), 'gat_eval.py measures on the GPU'
+    require_gpu('gat_eval.py')
     from gist_amd import datasets, hip
     from gist_amd.gat_eval import GATFullGraphEvaluator, eval_dims
     from gist_amd.modules import GAT
@@ -96,10 +88,8 @@ def main():
                 layers()
                 ev.forward()
             torch.cuda.synchronize()
-            lw, bw = [], []
-            for _ in range(args.reps):                       # interleaved windows
-                lw.append(window(layers, args.iters))
-                bw.append(window(ev.forward, args.iters))
+            win = alternate({'layers': layers, 'blocked': ev.forward}, lambda f: event_window(f, args.iters), args.reps)
+            lw, bw = win['layers'], win['blocked']
             walker_ms = median_of(walk.forward, args.iters, args.reps)
             # the new path's launch groups alone, on the evaluator's own buffers (left as the last forward filled them)
             kernels = []
@@ -127,7 +117,7 @@ def main():
                 cur = out
         r = dict(heads=heads, out=f, merge=merge, layers_ms=round(float(np.median(lw)), 3),
                  blocked_ms=round(float(np.median(bw)), 3), speedup=round(float(np.median(lw) / np.median(bw)), 2),
-                 wins=bool(max(bw) < min(lw)), walker_ms=round(walker_ms, 3), max_rel_diff=diff,
+                 wins=every_window_shorter(bw, lw), walker_ms=round(walker_ms, 3), max_rel_diff=diff,
                  layers_windows=[round(v, 3) for v in lw], blocked_windows=[round(v, 3) for v in bw], kernels=kernels)
         res.append(r)
         print(json.dumps({k: v for k, v in r.items() if k != 'kernels'}), flush=True)

@@ -17,7 +17,7 @@ merge; 4 heads, --n-layers layers, in = 602, 41 classes) it runs, after --warmup
 of windows of --iters iterations, engine and module ALTERNATING in one process, each window between two HIP events and
 ended by a synchronise.  It reports the median ms per iteration of each path, the run-to-run spread of each
 ((max - min) / median over the windows), the ratio, and the launches the library itself issued per iteration
-(gist_launch_count; torch's own kernels of the module path are not in it).
+(its launch counter; torch's own kernels of the module path are not in it).
 
     rocprofv3 --kernel-trace --output-format csv -d DIR -- \\
         python scripts/gat_ist_step.py --trace engine --sites 2 --width 64 --steps 40
@@ -43,15 +43,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from scripts.measure import alternate, cycle, event_window, require_gpu, split_counts, spread
+
 SITES, WIDTHS, HEADS = (2, 4), (16, 64, 256), 4
 LR, WD = 0.01, 5e-4
 MARK = 'spin_kernel'
-
-
-def cycle(it):
-    while True:
-        for b in it:
-            yield b
 
 
 class Paths(object):
@@ -102,23 +98,6 @@ class Paths(object):
         return fns[0][0], fns[0][1], fns[1][1]
 
 
-def window(fn, iters):
-    from gist_amd import _lib
-    L = _lib.load()
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0 = L.gist_launch_count()
-    a.record()
-    for _ in range(iters):
-        fn()
-    z.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(z) / iters, (L.gist_launch_count() - c0) / float(iters)
-
-
-def spread(v):
-    return (max(v) - min(v)) / float(np.median(v))
-
-
 def count_trace(path, steps):
     """Kernel dispatches between the two marks of a --trace run, per iteration, and the kernels they are."""
     with open(path, newline='') as fh:
@@ -157,7 +136,7 @@ def main():
     if args.count_trace:
         count_trace(args.count_trace, args.steps)
         return
-    assert torch.cuda.is_available(), 'gat_ist_step.py measures on the GPU'
+    require_gpu('gat_ist_step.py')
     from gist_amd import datasets, hip
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
@@ -190,14 +169,10 @@ def main():
             eng_iter()
             mod_iter()
         torch.cuda.synchronize()
-        e_ms, m_ms, e_l, m_l = [], [], [], []
-        for _ in range(args.reps):                     # alternating: a drift of the box hits both paths alike
-            ms, nl = window(eng_iter, args.iters)
-            e_ms.append(ms)
-            e_l.append(nl)
-            ms, nl = window(mod_iter, args.iters)
-            m_ms.append(ms)
-            m_l.append(nl)
+        # alternating: a drift of the box hits both paths alike
+        ms, nl = split_counts(alternate({'engine': eng_iter, 'module': mod_iter},
+                                        lambda f: event_window(f, args.iters, count=True), args.reps))
+        e_ms, m_ms, e_l, m_l = ms['engine'], ms['module'], nl['engine'], nl['module']
         for w in ws:
             w.engine.check_extract()
         e, m = float(np.median(e_ms)), float(np.median(m_ms))

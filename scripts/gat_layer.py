@@ -34,6 +34,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from scripts.measure import event_window, require_gpu
+
 PEAK_BPS = 8.0e12
 
 
@@ -65,14 +67,8 @@ def timed(fn, batches, iters, reps, warmup):
     torch.cuda.synchronize()
     out = []
     for _ in range(reps):
-        a = torch.cuda.Event(enable_timing=True)
-        z = torch.cuda.Event(enable_timing=True)
-        a.record()
-        for k in range(iters):
-            fn(batches[k % len(batches)])
-        z.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(z) / iters)
+        turn = iter(range(iters))                   # every window on the same batches, from the first
+        out.append(event_window(lambda: fn(batches[next(turn) % len(batches)]), iters))
     return float(np.median(out)), [round(v, 4) for v in out]
 
 
@@ -86,7 +82,7 @@ def main():
     ap.add_argument('--quick', action='store_true', help='one small shape (rehearsal)')
     ap.add_argument('--head-merge', choices=['mean', 'cat', 'both'], default='mean')
     args = ap.parse_args()
-    assert torch.cuda.is_available(), 'gat_layer.py measures on the GPU'
+    require_gpu('gat_layer.py')
     from gist_amd import autograd, datasets, hip
     from gist_amd.sampler import ClusterIter
     dev = torch.device('cuda', 0)

@@ -17,7 +17,7 @@ Both paths compute the same bits (tests/test_gat_step_gpu.py); this tool only ti
 width per head; in = 602, 41 classes) it runs, after --warmup steps of each path, --reps pairs of windows of --iters
 steps, the paths (--paths, default engine,module) ALTERNATING in one process, each window between two HIP events and ended by a synchronise.
 It reports the median ms per step of each path, the run-to-run spread of each ((max - min) / median over the windows),
-the ratio, and the launches the library itself issued per step (gist_launch_count; torch's own kernels of the module
+the ratio, and the launches the library itself issued per step (its launch counter; torch's own kernels of the module
 path -- cat, mul, zero_ -- are not in it).
 
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/gat_step.py --trace engine --shape 2,4,64 --steps 40
@@ -43,14 +43,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from scripts.measure import (alternate, cycle, event_window, every_window_shorter, reference_loop, require_gpu,
+                             split_counts, spread)
+
 SHAPES = ([(2, h, w) for h in (1, 4) for w in (16, 32, 64, 256)] + [(3, 4, 32), (3, 4, 64), (3, 4, 256)])
 LR, WD = 0.01, 5e-4
-
-
-def cycle(it):
-    while True:
-        for b in it:
-            yield b
 
 
 class Paths(object):
@@ -81,19 +78,7 @@ class Paths(object):
 
         def module_loop(model, it):
             """The reference's loop body on `model` and the batches of `it`."""
-            opt = Adam(model.parameters(), lr=LR, weight_decay=WD)
-            batches = cycle(it)
-
-            def step():
-                cluster = next(batches).to(self.dev)
-                model.train()
-                pred = model(cluster)
-                tm, lab = cluster.ndata['train_mask'], cluster.ndata['label']
-                loss = loss_f(pred[tm], lab[tm])
-                opt.zero_grad()
-                loss.backward()
-                opt.step()
-            return step
+            return reference_loop(model, cycle(it), loss_f, Adam(model.parameters(), lr=LR, weight_decay=WD), self.dev)
         mod_step = module_loop(model, self.mod_it)
         # the same loop, the same initial weights, the model bound to its iterator
         from gist_amd.module_engine import bind_gat
@@ -116,23 +101,6 @@ class Paths(object):
         return eng, dict(engine=eng_step, phases=ph_step, module=mod_step)
 
 
-def window(fn, iters):
-    from gist_amd import _lib
-    L = _lib.load()
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0 = L.gist_launch_count()
-    a.record()
-    for _ in range(iters):
-        fn()
-    z.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(z) / iters, (L.gist_launch_count() - c0) / float(iters)
-
-
-def spread(v):
-    return (max(v) - min(v)) / float(np.median(v))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='gat_step.json')
@@ -147,7 +115,7 @@ def main():
     ap.add_argument('--steps', type=int, default=40, help='--trace: steps to run')
     ap.add_argument('--head-merge', choices=['mean', 'cat', 'both'], default='mean')
     args = ap.parse_args()
-    assert torch.cuda.is_available(), 'gat_step.py measures on the GPU'
+    require_gpu('gat_step.py')
     from gist_amd import datasets, hip
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
@@ -179,12 +147,9 @@ def main():
             for n in names:
                 steps[n]()
         torch.cuda.synchronize()
-        ms, nl = dict((n, []) for n in names), dict((n, []) for n in names)
-        for _ in range(args.reps):                     # alternating: a drift of the box hits every path alike
-            for n in names:
-                t, c = window(steps[n], args.iters)
-                ms[n].append(t)
-                nl[n].append(c)
+        # alternating: a drift of the box hits every path alike
+        ms, nl = split_counts(alternate({n: steps[n] for n in names}, lambda f: event_window(f, args.iters, count=True),
+                                        args.reps))
         eng.check_extract()
         med = dict((n, float(np.median(ms[n]))) for n in names)
         r = dict(merge=merge, layers=layers, heads=heads, width=width, n_in=paths.fin)
@@ -203,7 +168,7 @@ def main():
             if 'module' in med:
                 r['module_over_phases'] = round(med['module'] / med['phases'], 3)
                 # the criterion of profiles/gat_ist_step.md: every phases window shorter than every module window
-                r['phases_below_every_module_window'] = bool(max(ms['phases']) < min(ms['module']))
+                r['phases_below_every_module_window'] = every_window_shorter(ms['phases'], ms['module'])
         res.append(r)
         print(json.dumps({k: v for k, v in r.items() if not k.endswith('_windows')}), flush=True)
         del eng, steps

@@ -24,19 +24,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from scripts.measure import event_window, require_gpu
+
 LN_SIZES = [(2708, 16), (19717, 16), (19717, 256)]
 EPOCH_SETS = [('cora-synth', 16), ('pubmed-sized', 16), ('pubmed-sized', 256)]
-
-
-def window(fn, iters):
-    import torch
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    z.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(z) / iters
 
 
 def median_of(fn, iters, reps, warmup):
@@ -45,7 +36,7 @@ def median_of(fn, iters, reps, warmup):
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
-    w = [window(fn, iters) for _ in range(reps)]
+    w = [event_window(fn, iters) for _ in range(reps)]
     return dict(median_ms=round(float(np.median(w)), 5), min_ms=round(min(w), 5), max_ms=round(max(w), 5))
 
 
@@ -168,7 +159,7 @@ def main():
     assert args.reps >= 20, 'at least 20 repeats'
     if args.region:
         import torch
-        assert torch.cuda.is_available(), 'gcn_ist.py measures on the GPU'
+        require_gpu('gcn_ist.py')
         torch.cuda.set_device(0)
         r = run_region(args.region, args)
         r['device'] = torch.cuda.get_device_name(0)

@@ -24,15 +24,18 @@ import os
 import random
 import statistics
 import sys
-import time
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from scripts.baseline_gcn_step import FAMILY as BASELINE_GCN
+from scripts.graphsage_step import FAMILY as GRAPHSAGE
+from scripts.measure import alternate, cell, host_window, require_gpu, verdict, write_lines
+from scripts.step_tool import BATCH, step_path
 
 PEAK_BF16 = 2.5e15
 BIG = (('nt', 2200, 4096, 8192), ('nn', 2200, 8192, 4096), ('tn', 4096, 8192, 2200))
@@ -43,7 +46,7 @@ SMALL = (('nt', 512, 512, 512), ('nt', 1024, 512, 512), ('nt', 1024, 1024, 512),
          ('tn', 1024, 1024, 1024), ('nt', 2046, 1024, 1024), ('tn', 1024, 1024, 2046), ('nt', 2046, 512, 1204),
          ('tn', 512, 1204, 2046), ('nn', 2046, 1204, 512), ('nn', 2046, 1024, 1024), ('nt', 1200, 1024, 1024),
          ('nt', 2046, 41, 8192), ('nt', 2046, 256, 512), ('tn', 256, 512, 2046))
-LAYERS, DROPOUT, BATCH, LR = 2, 0.2, 20, 0.01
+STEPS = {'graphsage': (GRAPHSAGE, False), 'baseline_gcn': (BASELINE_GCN, True)}      # (use_pp off; layer norm on)
 
 
 def operands(form, m, n, k, dev):
@@ -60,27 +63,18 @@ def caller(hip, form, a, b, c):
     return (lambda: hip.gemm_nn(a, b, c)) if form == 'nn' else (lambda: hip.gemm_tn(a, b, c))
 
 
-def window(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e6 / iters
-
-
-def alternate(settings, fn, warmup, iters, reps):
-    """{name: [window us]} for settings = {name: function that puts the setting in force}, windows alternating"""
+def alternating(settings, fn, warmup, iters, reps):
+    """{name: [window ms]} for settings = {name: function that puts the setting in force}, windows alternating"""
     for s in settings.values():
         s()
         for _ in range(warmup):
             fn()
-    times = {k: [] for k in settings}
-    for _ in range(reps):
-        for k, s in settings.items():
-            s()
-            times[k].append(window(fn, iters))
-    return times
+    return alternate({k: fn for k in settings}, lambda f: host_window(f, iters), reps, before=lambda k: settings[k]())
+
+
+def us(times):
+    """the GEMM tables are in us per call; the windows are in ms"""
+    return {k: [v * 1e3 for v in ws] for k, ws in times.items()}
 
 
 def kernel_us(fn, calls=10):
@@ -98,14 +92,6 @@ def kernel_us(fn, calls=10):
     return out
 
 
-def fmt(ts):
-    return '%.1f (%.1f .. %.1f)' % (statistics.median(ts), min(ts), max(ts))
-
-
-def verdict(new, old, new_name, old_name):
-    return new_name + ' faster' if max(new) < min(old) else (old_name + ' faster' if max(old) < min(new) else 'within the spread')
-
-
 def part_gemm(hip, a, out, dev):
     out += ['## Projections of the step, per call', '',
             '| layout | m | n | k | bf16x3 us | bf16x1 us | x3 / x1 | bf16x1 share of 2.5 PF | cast alone us | main kernel alone us | '
@@ -113,8 +99,8 @@ def part_gemm(hip, a, out, dev):
     for form, m, n, k in BIG + MORE:
         ops = operands(form, m, n, k, dev)
         fn = caller(hip, form, *ops)
-        t = alternate({'bf16x3': lambda: hip.gemm_mode('bf16x3'), 'bf16x1': lambda: hip.gemm_mode('bf16x1')}, fn, a.warmup,
-                      a.iters, a.reps)
+        t = us(alternating({'bf16x3': lambda: hip.gemm_mode('bf16x3'), 'bf16x1': lambda: hip.gemm_mode('bf16x1')}, fn,
+                           a.warmup, a.iters, a.reps))
         hip.gemm_mode('bf16x1')
         plan = hip.gemm_plan(form, m, n, k)
         ku = kernel_us(fn)
@@ -122,7 +108,7 @@ def part_gemm(hip, a, out, dev):
         main = sum(v for kk, v in ku.items() if 'gemm_bf16x1' in kk or 'splitk_reduce' in kk)
         x3, x1 = t['bf16x3'], t['bf16x1']
         out.append('| %s | %d | %d | %d | %s | %s | %.2f | %.3f | %.1f | %.1f | %s, %d slices | %s |' % (
-            form, m, n, k, fmt(x3), fmt(x1), statistics.median(x3) / statistics.median(x1),
+            form, m, n, k, cell(x3, 1), cell(x1, 1), statistics.median(x3) / statistics.median(x1),
             2.0 * m * n * k / (statistics.median(x1) * 1e-6) / PEAK_BF16, cast, main, plan['path'], plan['splits'],
             verdict(x1, x3, 'bf16x1', 'bf16x3')))
         print(out[-1], flush=True)
@@ -138,44 +124,17 @@ def part_threshold(hip, a, out, dev):
     for form, m, n, k in SMALL + MORE:
         ops = operands(form, m, n, k, dev)
         fn = caller(hip, form, *ops)
-        t = alternate({'f32': lambda: hip.tuning('bf16x1', 1), 'bf16x1': lambda: hip.tuning('bf16x1', 2)}, fn, a.warmup, a.iters,
-                      a.reps)
+        t = us(alternating({'f32': lambda: hip.tuning('bf16x1', 1), 'bf16x1': lambda: hip.tuning('bf16x1', 2)}, fn, a.warmup,
+                           a.iters, a.reps))
         hip.tuning('bf16x1', 0)
         f, x = t['f32'], t['bf16x1']
         out.append('| %s | %d | %d | %d | %.2f | %s | %s | %.2f | %s | %s |' % (
-            form, m, n, k, 2e-9 * m * n * k, fmt(f), fmt(x), statistics.median(f) / statistics.median(x),
+            form, m, n, k, 2e-9 * m * n * k, cell(f, 1), cell(x, 1), statistics.median(f) / statistics.median(x),
             verdict(x, f, 'bf16x1', 'f32'), hip.gemm_plan(form, m, n, k)['path']))
         print(out[-1], flush=True)
         del ops, fn
     hip.gemm_mode('bf16x3')
     out.append('')
-
-
-def cycle(it):
-    while True:
-        for b in it:
-            yield b
-
-
-def make_step(family, ds, it, hidden, dev, seed=0):
-    from gist_amd import arena
-    in_feats = ds.g.ndata['feat'].shape[1]
-    torch.manual_seed(seed)
-    if family == 'graphsage':
-        from gist_amd.graphsage_engine import GraphSAGEEngine
-        from gist_amd.modules import GraphSAGE
-        model = GraphSAGE(in_feats, hidden, ds.num_classes, LAYERS, F.relu, DROPOUT, False).to(dev)
-        eng = GraphSAGEEngine(arena.graphsage_dims(in_feats, hidden, ds.num_classes, LAYERS), DROPOUT, it.n_max, dev)
-    else:
-        from gist_amd.baseline_gcn_engine import BaselineGCNEngine
-        from gist_amd.modules import BaselineGCN
-        model = BaselineGCN(in_feats, hidden, ds.num_classes, LAYERS, F.relu, DROPOUT, True).to(dev)
-        eng = BaselineGCNEngine(arena.baseline_gcn_dims(in_feats, hidden, ds.num_classes, LAYERS), True, DROPOUT, it.n_max, dev)
-    eng.bind(model)
-    it.bind(eng)
-    eng.prefetch = True
-    batches = cycle(it)
-    return (lambda: eng.train_step(next(batches), LR)), eng, model
 
 
 def iterator(ds, dev):
@@ -189,11 +148,12 @@ def part_steps(hip, a, out, dev, ds):
     out += ['## One-call steps on reddit-synth (%d nodes, batches of %d parts), ms per iteration' % (ds.g.number_of_nodes(), BATCH), '',
             '| family | n-hidden | bf16x3 ms | bf16x1 ms | x3 / x1 | verdict |', '|---|---|---|---|---|---|']
     for family in ('graphsage', 'baseline_gcn'):
+        fam, flag = STEPS[family]
         for hidden in (4096, 1024):
             fns, keep = {}, []
             for mode in ('bf16x3', 'bf16x1'):
                 hip.gemm_mode(mode)                       # before the engine: it sizes its workspaces in this mode
-                one, eng, model = make_step(family, ds, iterator(ds, dev), hidden, dev)
+                one, eng, model = step_path(fam, ds, iterator(ds, dev), hidden, flag, dev)
                 fns[mode] = one
                 keep.append((eng, model))
             current = [None]
@@ -206,11 +166,11 @@ def part_steps(hip, a, out, dev, ds):
                     hip.gemm_mode(mode)
                     current[0] = mode
                 return s
-            t = alternate({m: setter(m) for m in fns}, both, a.step_warmup, a.step_iters, a.reps)
-            x3, x1 = [v / 1e3 for v in t['bf16x3']], [v / 1e3 for v in t['bf16x1']]
-            out.append('| %s | %d | %.3f (%.3f .. %.3f) | %.3f (%.3f .. %.3f) | %.2f | %s |' % (
-                family, hidden, statistics.median(x3), min(x3), max(x3), statistics.median(x1), min(x1), max(x1),
-                statistics.median(x3) / statistics.median(x1), verdict(x1, x3, 'bf16x1', 'bf16x3')))
+            t = alternating({m: setter(m) for m in fns}, both, a.step_warmup, a.step_iters, a.reps)
+            x3, x1 = t['bf16x3'], t['bf16x1']
+            out.append('| %s | %d | %s | %s | %.2f | %s |' % (
+                family, hidden, cell(x3), cell(x1), statistics.median(x3) / statistics.median(x1),
+                verdict(x1, x3, 'bf16x1', 'bf16x3')))
             print(out[-1], flush=True)
             del fns, keep
             torch.cuda.empty_cache()
@@ -230,7 +190,7 @@ def part_accuracy(hip, a, out, dev, ds):
         hip.gemm_mode(mode)
         for seed in range(5):
             it = iterator(ds, dev)
-            one, eng, model = make_step('graphsage', ds, it, a.acc_hidden, dev, seed=seed)
+            one, eng, model = step_path(GRAPHSAGE, ds, it, a.acc_hidden, False, dev, seed=seed)
             loss = None
             for _ in range(a.epochs * len(it)):
                 loss = one()
@@ -261,8 +221,7 @@ def main():
     ap.add_argument('--acc-hidden', type=int, default=1024)
     ap.add_argument('--epochs', type=int, default=1)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('gemm_bf16x1.py measures on the GPU; there is none here')
+    require_gpu('gemm_bf16x1.py')
     from gist_amd import datasets, hip
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
@@ -282,10 +241,7 @@ def main():
             part_steps(hip, a, out, dev, ds)
         if 'accuracy' in parts:
             part_accuracy(hip, a, out, dev, ds)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as fh:
-        fh.write('\n'.join(out) + '\n')
-    print('\n'.join(out))
+    write_lines(a.out, out)
 
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 """Dev tool: sweep (tile, splits) per GEMM shape in SUBPROCESSES (the override is read once
 per process) and print the best configuration -- input for gemm_plan.cpp:choose_cfg (hip.gemm_plan prints what the planner chooses)."""
-import json, os, subprocess, sys
+import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [('nt', 2046, 4096, 8192), ('nt', 2046, 4096, 1204), ('tn', 4096, 1204, 2046),
           ('tn', 4096, 8192, 2046), ('nn', 2046, 8192, 4096),
@@ -14,10 +14,14 @@ SHAPES = [('nt', 2046, 4096, 8192), ('nt', 2046, 4096, 1204), ('tn', 4096, 1204,
           ('nt', 2046, 256, 1204), ('nt', 2046, 256, 512), ('tn', 256, 512, 2046), ('nn', 2046, 512, 256)]
 if os.environ.get('GIST_SWEEP_SHAPES'):      # e.g. 'nt,1140,512,1024;nn,1140,1024,512'
     SHAPES = [(t.split(',')[0],) + tuple(int(v) for v in t.split(',')[1:]) for t in os.environ['GIST_SWEEP_SHAPES'].split(';')]
+ap = argparse.ArgumentParser(description=__doc__)
+ap.add_argument('--quick', action='store_true', help='seven configurations instead of the whole (tile, splits) product')
+args = ap.parse_args()
 CHILD = r'''
 import sys, json, os, torch
 sys.path.insert(0, %r)
 from gist_amd import hip
+from scripts.measure import event_window
 dev = torch.device('cuda', 0)
 if os.environ.get('GIST_B3C'):
     hip.tuning('b3c', int(os.environ['GIST_B3C']))
@@ -39,16 +43,13 @@ for (lay, m, n, k) in shapes:
     hip.workspace(32 * m * n * 4, dev)
     for _ in range(3): f()
     torch.cuda.synchronize()
-    ts = []
-    for _ in range(7):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); f(); e1.record(); torch.cuda.synchronize(); ts.append(e0.elapsed_time(e1))
-    ts.sort(); out.append(ts[len(ts)//2])
+    ts = sorted(event_window(f, 1) for _ in range(7))
+    out.append(ts[len(ts)//2])
 print(json.dumps(out))
 ''' % ROOT
 res = {}
 import itertools
-CONFIGS = [(128, 1), (128, 2), (64, 1), (64, 2), (64, 4), (64, 8), (64, 16)] if '--quick' in sys.argv else list(itertools.product((128, 64), (1, 2, 4, 8, 16, 32)))
+CONFIGS = [(128, 1), (128, 2), (64, 1), (64, 2), (64, 4), (64, 8), (64, 16)] if args.quick else list(itertools.product((128, 64), (1, 2, 4, 8, 16, 32)))
 for tile, sp in CONFIGS:
     if True:
         env = dict(os.environ, GIST_GEMM_TILE=str(tile), GIST_GEMM_SPLITS=str(sp))

@@ -22,7 +22,6 @@ import json
 import math
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -31,33 +30,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-
-def host_window(fn, iters, dev):
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize(dev)
-    return (time.perf_counter() - t0) * 1e3 / iters
-
-
-def event_window(fn, iters):
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    z.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(z) / iters
+from scripts.measure import alternate, event_window, host_window, require_gpu, stats, verdict
 
 
 def iters_for(ms_per_call, min_window_s):
     return max(1, int(math.ceil(min_window_s * 1e3 / max(ms_per_call, 1e-4))))
-
-
-def stats(ws):
-    return dict(median=round(float(np.median(ws)), 4), min=round(min(ws), 4), max=round(max(ws), 4),
-                windows=[round(w, 4) for w in ws])
 
 
 def measure_shape(g, ds, hidden, use_pp, args, dev):
@@ -108,13 +85,11 @@ def measure_shape(g, ds, hidden, use_pp, args, dev):
         rows()
     it_l = iters_for(host_window(layers, 2, dev), args.min_window)
     it_r = iters_for(host_window(rows, 2, dev), args.min_window)
-    lw, rw = [], []
-    for _ in range(args.reps):                                 # alternating windows
-        lw.append(host_window(layers, it_l, dev))
-        rw.append(host_window(rows, it_r, dev))
-    verdict = 'rows faster' if max(rw) < min(lw) else ('layers faster' if max(lw) < min(rw) else 'within the spread')
+    calls = {layers: it_l, rows: it_r}
+    win = alternate({'layers': layers, 'rows': rows}, lambda f: host_window(f, calls[f], dev), args.reps)
+    lw, rw = win['layers'], win['rows']
     r = dict(hidden=hidden, use_pp=bool(use_pp), layers_ms=stats(lw), rows_ms=stats(rw), layers_iters=it_l, rows_iters=it_r,
-             ratio=round(float(np.median(lw) / np.median(rw)), 3), verdict=verdict,
+             ratio=round(float(np.median(lw) / np.median(rw)), 3), verdict=verdict(rw, lw, 'rows', 'layers'),
              layers_peak_mb=round(peak_l / 2 ** 20, 1), rows_peak_mb=round(peak_r / 2 ** 20, 1),
              rows_resident_mb=round(resident / 2 ** 20, 1), max_rel_diff=diff, acc_layers=acc_l, acc_rows=acc_r,
              row_blocks=len(ev.row_cuts) - 1, dense=ev.split is not None)
@@ -150,10 +125,9 @@ def measure_tail(d, args, dev, n=2046):
     same = bool(torch.equal(out_t, out_i))
     it_t = iters_for(event_window(train, 200), args.min_window)
     it_i = iters_for(event_window(infer, 200), args.min_window)
-    tw, iw = [], []
-    for _ in range(args.reps):
-        tw.append(event_window(train, it_t))
-        iw.append(event_window(infer, it_i))
+    calls = {train: it_t, infer: it_i}
+    win = alternate({'train': train, 'infer': infer}, lambda f: event_window(f, calls[f]), args.reps)
+    tw, iw = win['train'], win['infer']
     reads = 1 if d <= 4096 else 3
     bytes_i, bytes_t = (reads + 1) * n * d * 4, (reads + 2) * n * d * 4 + 4 * n
     return dict(rows=n, d=d, fwd_ms=stats(tw), infer_ms=stats(iw), fwd_iters=it_t, infer_iters=it_i, fwd_bytes=bytes_t,
@@ -172,7 +146,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--min-window', type=float, default=0.5, help='seconds of work per window, at least')
     args = ap.parse_args()
-    assert torch.cuda.is_available(), 'graphsage_eval.py measures on the GPU'
+    require_gpu('graphsage_eval.py')
     from gist_amd import datasets
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)

@@ -15,7 +15,7 @@ one process, each window between two HIP events and ended by a synchronise:
 
 A time per call is the larger of the host's issue time and the device time per call: at the narrow shapes both movers
 are bound by the host, and the grouped figure is one ctypes call plus torch's index upload or bias copy, not kernel time.
-It reports the median ms per call, every window, the launches the library issued per call (gist_launch_count; the copy
+It reports the median ms per call, every window, the launches the library issued per call (its launch counter; the copy
 of the shared bias and the index uploads are torch's and not in it) and the acceptance conditions:
 
   A  at every shape no grouped window is longer than the per-tensor median plus that run's own window spread
@@ -39,6 +39,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from scripts.measure import COUNTER, alternate, event_window, every_window_shorter, require_gpu, split_counts
+
 FIN, NCLS = 602, 41
 SITES, LAYERS, WIDTHS = (2, 4, 8), (2, 4), (256, 1024, 4096)
 
@@ -52,19 +54,6 @@ def wrapper(S, L, H, dev, blocks):
     w.base.params.copy_(torch.randn(w.base.numel, device=dev, generator=gen))
     w.gathered.copy_(torch.randn(w.gathered.numel(), device=dev, generator=gen))
     return w
-
-
-def window(fn, iters):
-    from gist_amd import _lib
-    L = _lib.load()
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0 = L.gist_launch_count()
-    a.record()
-    for _ in range(iters):
-        fn()
-    z.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(z) / iters, (L.gist_launch_count() - c0) / float(iters)
 
 
 def movers(args, dev):
@@ -89,23 +78,20 @@ def movers(args, dev):
                         tf()
                     torch.cuda.synchronize()
                     # calls per window: at least --iters, and enough for a window of --min-window-ms (from a short one)
-                    gi = max(args.iters, int(args.min_window_ms / window(gf, 50)[0]) + 1)
-                    ti = max(args.iters, int(args.min_window_ms / window(tf, 50)[0]) + 1)
-                    gw, tw, gl, tl = [], [], [], []
-                    for _ in range(args.reps):             # alternating: a drift of the box hits both movers alike
-                        ms, n = window(gf, gi)
-                        gw.append(ms)
-                        gl.append(n)
-                        ms, n = window(tf, ti)
-                        tw.append(ms)
-                        tl.append(n)
+                    calls = {gf: max(args.iters, int(args.min_window_ms / event_window(gf, 50)) + 1),
+                             tf: max(args.iters, int(args.min_window_ms / event_window(tf, 50)) + 1)}
+                    gi, ti = calls[gf], calls[tf]
+                    # alternating: a drift of the box hits both movers alike
+                    ms, nl = split_counts(alternate({'grouped': gf, 'per_tensor': tf},
+                                                    lambda f: event_window(f, calls[f], count=True), args.reps))
+                    gw, tw, gl, tl = ms['grouped'], ms['per_tensor'], nl['grouped'], nl['per_tensor']
                     tm, gm = float(np.median(tw)), float(np.median(gw))
                     rows.append(dict(op=name, S=S, L=L, H=H, grouped_ms=gm, per_tensor_ms=tm, ratio=tm / gm,
                                      grouped_windows=gw, per_tensor_windows=tw, grouped_calls=gi, per_tensor_calls=ti,
                                      grouped_launches=float(np.median(gl)),
                                      per_tensor_launches=float(np.median(tl)),
                                      cond_a=max(gw) <= tm + (max(tw) - min(tw)),
-                                     cond_b=(max(gw) < min(tw)) if (H == 256 and name == 'sync') else None))
+                                     cond_b=every_window_shorter(gw, tw) if (H == 256 and name == 'sync') else None))
                     print('%-8s S=%d L=%d H=%-4d grouped %.4f ms  per-tensor %.4f ms  x%.2f' % (name, S, L, H, gm, tm, tm / gm),
                           flush=True)
                 if not torch.equal(g.base.params, t.base.params):
@@ -150,12 +136,8 @@ def loop(args, dev):
             return 1e3 * res['total_time'] / res['events'].count('step'), res['events'].count('step')
         one('step')
         one('module')                                      # warm-up: one window of each
-        sw, mw = [], []
-        for _ in range(args.loop_reps):
-            ms, n = one('step')
-            sw.append(ms)
-            ms, n = one('module')
-            mw.append(ms)
+        ms, ns = split_counts(alternate({hp: hp for hp in runs}, one, args.loop_reps))
+        sw, mw, n = ms['step'], ms['module'], ns['module'][-1]
         rows.append(dict(S=S, L=L, H=H, iterations=n, step_ms=float(np.median(sw)), module_ms=float(np.median(mw)),
                          step_windows=sw, module_windows=mw))
         print('loop H=%d: step %.4f ms / iteration, module %.4f' % (H, rows[-1]['step_ms'], rows[-1]['module_ms']), flush=True)
@@ -177,7 +159,7 @@ def main():
     ap.add_argument('--quick', action='store_true', help='the toy graph for the loop (rehearsal)')
     ap.add_argument('--script-val', default='', help='text for the report: the script test\'s measured accuracies')
     args = ap.parse_args()
-    assert torch.cuda.is_available(), 'graphsage_ist.py measures on the GPU'
+    require_gpu('graphsage_ist.py')
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
     t0 = time.time()
@@ -189,9 +171,9 @@ def main():
     out = ['# GIST for GraphSAGE: dispatch and sync on the two block movers, the loop on its two host paths', '',
            'Tool: `scripts/graphsage_ist.py` on %s; %d windows per mover and operation, alternating, each of at least %d '
            'calls and at least %g ms (the grouped mover\'s narrow shapes take up to 20000 calls), after %d warm-up calls and '
-           'a calibration window; in = %d, %d classes.  Times in ms per call; launches = the library\'s own (gist_launch_count) per '
+           'a calibration window; in = %d, %d classes.  Times in ms per call; launches = the library\'s own (%s) per '
            'call -- the copy of the shared bias (one torch kernel per sync on either mover) and the index uploads are not in it.'
-           % (torch.cuda.get_device_name(0), args.reps, args.iters, args.min_window_ms, args.warmup, FIN, NCLS), '',
+           % (torch.cuda.get_device_name(0), args.reps, args.iters, args.min_window_ms, args.warmup, FIN, NCLS, COUNTER), '',
            'What a figure is: a window is a run of back-to-back calls ended by one synchronise, so a time per call is the '
            'larger of the host\'s issue time per call and the device time per call.  At the narrow shapes the grouped '
            'figures (0.01-0.05 ms) are the HOST\'s: one ctypes call -- for a dispatch also the concatenation and upload of the '

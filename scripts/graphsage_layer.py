@@ -16,7 +16,6 @@ and gradients of the two paths are compared at every shape.  The report ends wit
 graph's labels are random, chance is 0.2)."""
 import argparse
 import os
-import statistics
 import sys
 
 import torch
@@ -25,6 +24,8 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from scripts.measure import alternate, event_window, require_gpu, summary, write_lines
 
 ROWS, WIDTHS = 2046, (256, 4096)
 
@@ -58,14 +59,8 @@ def paths(x, ln, lin_bias):
             'torch': lambda: F.relu(ln(x + lin_bias))}
 
 
-def window(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / iters      # us per call
+def us_per_call(fn, iters):
+    return event_window(fn, iters) * 1e3      # the page is in us; the windows are in ms
 
 
 def measure(n, d, dev, warmup, iters, reps):
@@ -99,11 +94,8 @@ def measure(n, d, dev, warmup, iters, reps):
             for _ in range(warmup):
                 f()
         torch.cuda.synchronize()
-        times = {name: [] for name in fns}
-        for _ in range(reps):
-            for name, f in fns.items():      # alternating
-                times[name].append(window(f, iters))
-        res[mode] = {name: (statistics.median(t), min(t), max(t)) for name, t in times.items()}
+        times = alternate(fns, lambda f: us_per_call(f, iters), reps)
+        res[mode] = {name: summary(t) for name, t in times.items()}
     return res, diff
 
 
@@ -124,8 +116,7 @@ def kernel_times(n, d, dev, warmup, iters, reps):
         for _ in range(warmup):
             f()
         torch.cuda.synchronize()
-        t = [window(f, iters) for _ in range(reps)]
-        res[name] = (statistics.median(t), min(t), max(t))
+        res[name] = summary([us_per_call(f, iters) for _ in range(reps)])
     return res
 
 
@@ -150,8 +141,7 @@ def main():
     ap.add_argument('--reps', type=int, default=15)
     ap.add_argument('--epochs', type=int, default=10)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('graphsage_layer.py measures on the GPU; there is none here')
+    require_gpu('graphsage_layer.py')
     dev = torch.device('cuda', 0)
     L = ['# GraphSAGE layer tail: fused kernels against torch add + nn.LayerNorm + relu', '',
          '`python scripts/graphsage_layer.py` on %s; rows = %d; %d warm-up calls, %d windows of %d calls per path, '
@@ -183,10 +173,7 @@ def main():
           '', '| --use-pp | last val | best val | last test | best test |', '|---|---|---|---|---|']
     for row in cli_accuracies(a.epochs):
         L.append('| %s | %.4f | %.4f | %.4f | %.4f |' % (('yes' if row[0] else 'no',) + row[1:]))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as fh:
-        fh.write('\n'.join(L) + '\n')
-    print('\n'.join(L))
+    write_lines(a.out, L)
 
 
 if __name__ == '__main__':

@@ -10,7 +10,7 @@ Per shape (--n-hidden 256, 1024, 4096; --n-layers 2; dropout 0.2; with and witho
 paths alternate in windows of --iters iterations after --warmup iterations each; a window is timed on the host clock
 between two device synchronisations (the whole loop body, the iterator included), --reps windows per path.  Reported:
 ms per iteration as the median window (min .. max over the windows) and the kernel launches per iteration the library
-counts (gist_launch_count, as scripts/graphsage_step.py counts them), taken after the timed windows over the same
+counts (measure.lib_launches, as scripts/graphsage_step.py counts them), taken after the timed windows over the same
 batches on every path: each path restarts an epoch in the same part order and runs --iters of its batches.  Three
 statements per shape:
 
@@ -29,13 +29,15 @@ import sys
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from scripts.graphsage_step import BATCH, DROPOUT, LAYERS, LR, WIDTHS, window
+from scripts.graphsage_step import FAMILY
+from scripts.measure import (COUNTER, alternate, cell, every_window_shorter, host_window, lib_launches, reference_loop,
+                             require_gpu, write_lines)
+from scripts.step_tool import BATCH, DROPOUT, LAYERS, LR, WIDTHS
 
 
 class Feed(object):
@@ -57,18 +59,14 @@ class Feed(object):
 
 
 def new_model(ds, hidden, use_pp, dev):
-    from gist_amd.modules import GraphSAGE
     torch.manual_seed(0)
-    return GraphSAGE(ds.g.ndata['feat'].shape[1], hidden, ds.num_classes, LAYERS, F.relu, DROPOUT, use_pp).to(dev)
+    return FAMILY['model'](ds.g.ndata['feat'].shape[1], hidden, ds.num_classes, use_pp, dev)
 
 
 def step_path(ds, feed, hidden, use_pp, dev):
     """one gist_graphsage_step call per iteration (scripts/graphsage_step.py's step path)"""
-    from gist_amd.arena import graphsage_dims
-    from gist_amd.graphsage_engine import GraphSAGEEngine
     it = feed.it
-    eng = GraphSAGEEngine(graphsage_dims(ds.g.ndata['feat'].shape[1], hidden, ds.num_classes, LAYERS), DROPOUT, it.n_max,
-                          dev, use_pp=use_pp)
+    eng = FAMILY['engine'](ds.g.ndata['feat'].shape[1], hidden, ds.num_classes, use_pp, it.n_max, dev)
     eng.bind(new_model(ds, hidden, use_pp, dev))
     it.bind(eng)
     eng.prefetch = True
@@ -78,24 +76,11 @@ def step_path(ds, feed, hidden, use_pp, dev):
     return one, eng
 
 
-def module_loop(model, feed):
-    """cluster_gcn.py:96-105 on `model` and the batches of `feed`, as main_module_path runs it"""
+def module_loop(model, feed, dev):
+    """the reference's loop body on `model` and the batches of `feed`"""
     from gist_amd.nn import CrossEntropyLoss
     from gist_amd.optim import Adam
-    loss_f = CrossEntropyLoss()
-    opt = Adam(model.parameters(), lr=LR)
-
-    def one():
-        cluster = next(feed).to(torch.cuda.current_device())
-        model.train()
-        pred = model(cluster)
-        labels, mask = cluster.ndata['label'], cluster.ndata['train_mask']
-        loss = loss_f(pred[mask], labels[mask])
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        return loss
-    return one
+    return reference_loop(model, feed, CrossEntropyLoss(), Adam(model.parameters(), lr=LR), dev)
 
 
 def bound_path(ds, feed, hidden, use_pp, dev):
@@ -105,16 +90,7 @@ def bound_path(ds, feed, hidden, use_pp, dev):
     gc.collect()                                   # (the previous shape's bound model is gone: one model per iterator)
     me = bind_graphsage(model, feed.it)
     assert me.engine.prefetch, 'another model is still bound to this iterator'
-    return module_loop(model, feed), me
-
-
-def lib_launches(fn, iters):
-    from gist_amd import _lib
-    L = _lib.load()
-    before = L.gist_launch_count()
-    for _ in range(iters):
-        fn()
-    return (L.gist_launch_count() - before) / float(iters)
+    return module_loop(model, feed, dev), me
 
 
 def main():
@@ -125,8 +101,7 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--nodes', type=int, default=153431, help='nodes of reddit-synth (its default: the full stand-in)')
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('graphsage_step_phases.py measures on the GPU; there is none here')
+    require_gpu('graphsage_step_phases.py')
     from gist_amd import datasets
     from gist_amd.sampler import ClusterIter, EngineClusterIter
     dev = torch.device('cuda', 0)
@@ -137,11 +112,11 @@ def main():
            '`python scripts/graphsage_step_phases.py` on %s; reddit-synth (%d nodes, %d parts, batches of %d parts), '
            '--n-layers %d, dropout %g; %d warm-up iterations, %d windows of %d iterations per path, alternating; ms per '
            'iteration: median window (min .. max).  `lib` = launches per iteration through the library '
-           '(gist_launch_count) over the same %d batches on every path, after the timed windows.  A bound iteration is 2 '
+           '(%s) over the same %d batches on every path, after the timed windows.  A bound iteration is 2 '
            'dispatcher ops (gist::graphsage_forward, gist::graphsage_backward) and 3 C calls; a one-call step is 1 C call '
            'and no dispatcher op.'
            % (torch.cuda.get_device_name(0), ds.g.number_of_nodes(), len(ds.par_li), BATCH, LAYERS, DROPOUT, a.warmup,
-              a.reps, a.iters, a.iters), '',
+              a.reps, a.iters, COUNTER, a.iters), '',
            '| --use-pp | n-hidden | step ms | bound ms | unbound ms | bound / step | unbound / bound | step lib | bound lib '
            '| unbound lib | bound < unbound | launches equal | inside step range |',
            '|---|---|---|---|---|---|---|---|---|---|---|---|---|']
@@ -156,15 +131,12 @@ def main():
             s_one, eng = step_path(ds, feeds['step'], hidden, use_pp, dev)
             b_one, me = bound_path(ds, feeds['bound'], hidden, use_pp, dev)
             fns = {'step': s_one, 'bound': b_one,
-                   'unbound': module_loop(new_model(ds, hidden, use_pp, dev), feeds['unbound'])}
+                   'unbound': module_loop(new_model(ds, hidden, use_pp, dev), feeds['unbound'], dev)}
             for f in fns.values():
                 for _ in range(a.warmup):
                     loss = f()
                 assert bool(torch.isfinite(loss).all())
-            times = {k: [] for k in fns}
-            for _ in range(a.reps):
-                for k, f in fns.items():      # alternating
-                    times[k].append(window(f, a.iters, dev))
+            times = alternate(fns, lambda f: host_window(f, a.iters, dev), a.reps)
             eng.check_extract()
             me.engine.check_extract()
             # launches over the same a.iters batches of one epoch, in the same order, on every path
@@ -175,13 +147,12 @@ def main():
                 lib[k] = lib_launches(f, min(a.iters, len(feeds[k].it)))
             torch.cuda.synchronize(dev)
             s, b, u = times['step'], times['bound'], times['unbound']
-            row = dict(use_pp=use_pp, hidden=hidden, faster=max(b) < min(u), equal=lib['bound'] == lib['step'],
+            row = dict(use_pp=use_pp, hidden=hidden, faster=every_window_shorter(b, u), equal=lib['bound'] == lib['step'],
                        inside=min(s) <= statistics.median(b) <= max(s))
             rows.append(row)
-            out.append('| %s | %d | %.3f (%.3f .. %.3f) | %.3f (%.3f .. %.3f) | %.3f (%.3f .. %.3f) | %.3f | %.2f | %.3f '
-                       '| %.3f | %.3f | %s | %s | %s |' % (
-                           'yes' if use_pp else 'no', hidden, statistics.median(s), min(s), max(s), statistics.median(b),
-                           min(b), max(b), statistics.median(u), min(u), max(u), statistics.median(b) / statistics.median(s),
+            out.append('| %s | %d | %s | %s | %s | %.3f | %.2f | %.3f | %.3f | %.3f | %s | %s | %s |' % (
+                           'yes' if use_pp else 'no', hidden, cell(s), cell(b), cell(u),
+                           statistics.median(b) / statistics.median(s),
                            statistics.median(u) / statistics.median(b), lib['step'], lib['bound'], lib['unbound'],
                            'yes' if row['faster'] else 'NO', 'yes' if row['equal'] else 'NO',
                            'yes' if row['inside'] else 'no'))
@@ -194,10 +165,7 @@ def main():
     out += ['', 'Bound loop not below every unbound window: %s.' % where('faster', True),
             'Launches per iteration differ from the one-call step: %s.' % where('equal', True),
             'Bound median outside the one-call step\'s own window range: %s.' % where('inside', True)]
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as fh:
-        fh.write('\n'.join(out) + '\n')
-    print('\n'.join(out))
+    write_lines(a.out, out)
 
 
 if __name__ == '__main__':

@@ -15,7 +15,6 @@ import json
 import os
 import random
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -30,6 +29,7 @@ ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--dropout', type=float, default=0.2)
 args = ap.parse_args()
 
+from scripts.measure import cycle, host_window
 from gist_amd import datasets, ist
 from gist_amd.nn import CrossEntropyLoss
 from gist_amd.optim import Adam
@@ -40,17 +40,6 @@ torch.cuda.set_device(dev)
 ds = datasets.reddit_synth()
 g = ds.g
 nid = np.nonzero(g.ndata['train_mask'].numpy())[0].astype(np.int64)
-
-
-def batches(it, n):
-    """n batches of `it`, across epoch boundaries."""
-    k = 0
-    while True:
-        for b in it:
-            if k == n:
-                return
-            yield b
-            k += 1
 
 
 def run(S, kind):
@@ -64,17 +53,16 @@ def run(S, kind):
     w = ist.DistributedGNNWrapper(ns, g, g.ndata['feat'].shape[1], ds.num_classes, dev,
                                   comm=ist.LocalCommGroup(S).handle(0), n_max=None if module else it.n_max)
     w.ini_sync_dispatch_model()
-    n = args.warmup + args.steps
-    t0 = None
+    batches = cycle(it)                           # (across epoch boundaries)
     if module:
         loss_f = CrossEntropyLoss()
         w.sub_model.train()
         optimizer = Adam(w.sub_model.parameters(), lr=0.01, weight_decay=5e-4)
         running = 0.0
-        for j, cluster in enumerate(batches(it, n)):
-            if j == args.warmup:
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
+
+        def step():
+            nonlocal running
+            cluster = next(batches)
             optimizer.zero_grad()
             pred = w.sub_model(cluster)
             mask = cluster.ndata['train_mask']
@@ -83,19 +71,19 @@ def run(S, kind):
             if kind == 'module_float':
                 running += float(loss)
             optimizer.step()
-        assert [m for m in w.sub_model._module_engines.values() if m], 'sub_model did not bind to the fused step'
     else:
         w.engine.prefetch = True
         it.bind(w.engine)
         w.sub.reset_optimizer()
-        for j, b in enumerate(batches(it, n)):
-            if j == args.warmup:
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
-            w.engine.train_step(b, 0.01, 5e-4)
-    torch.cuda.synchronize(dev)
-    ms = (time.perf_counter() - t0) * 1e3 / args.steps
-    if not module:
+
+        def step():
+            w.engine.train_step(next(batches), 0.01, 5e-4)
+    for _ in range(args.warmup):
+        step()
+    ms = host_window(step, args.steps, dev)
+    if module:
+        assert [m for m in w.sub_model._module_engines.values() if m], 'sub_model did not bind to the fused step'
+    else:
         w.engine.check_extract()
     return ms
 

@@ -16,7 +16,11 @@ import sys
 import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(REPO, 'tests', 'golden')
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+from scripts.golden_common import OUT, reference_paths, toy_edges
+
 # the widths 12 -> 16, 16 -> 16 and 16 -> 5 take both of GraphConv's orders (multiply first iff in > out)
 # GRAPH_SEED: G7's graph, features, labels and mask.  SEED (the model's): Adam's first update is lr * g / (|g| + 1e-8),
 # whose slope in g is lr * 1e-8 / (|g| + 1e-8)^2: a gradient of 1e-7 turns float32's own ~1e-9 of error in it into 1e-5
@@ -26,21 +30,11 @@ OUT = os.path.join(REPO, 'tests', 'golden')
 N, IN, HIDDEN, CLASSES, LAYERS, GRAPH_SEED, SEED, LR = 40, 12, 16, 5, 2, 12, 1, 0.01
 
 
-def toy_edges(n, seed):
-    """a directed multigraph: a node without in-edges (n - 1), self loops on even nodes, five duplicate edges"""
-    rs = np.random.RandomState(seed)
-    src, dst = rs.randint(0, n, 4 * n), rs.randint(0, n - 1, 4 * n)
-    loops = np.arange(0, n - 1, 2)
-    return (np.concatenate([src, loops, src[:5]]).astype(np.int64),
-            np.concatenate([dst, loops, dst[:5]]).astype(np.int64))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reference', required=True, help='root of the reference project')
     a = ap.parse_args()
-    for p in (os.path.join(REPO, 'oracle', 'dgl_stub'), os.path.join(a.reference, 'cluster_gcn')):
-        sys.path.insert(0, p)
+    reference_paths(a.reference)
     import dgl
     import torch
     import torch.nn.functional as F

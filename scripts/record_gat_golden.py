@@ -53,7 +53,11 @@ import tempfile
 import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(REPO, 'tests', 'golden')
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+from scripts.golden_common import OUT, reference_paths, toy_edges
+
 N, IN, HIDDEN, CLASSES, HEADS, LR = 40, 12, 16, 5, 3, 0.01
 CAT_HIDDEN = 8
 LAYER_WIDTHS = (1, 5, 16)
@@ -61,22 +65,6 @@ FIRST_SEED, SEED = 11, 13
 MIN_GRAD = 1e-6
 CAP = 64 * 1024
 IST = dict(H=16, fin=6, ncls=5, seed=3, n_heads=1, n_layers=1)
-
-
-def toy_edges(n, seed):
-    """a directed multigraph: a node without in-edges (n - 1), self loops on even nodes, five duplicate edges"""
-    rs = np.random.RandomState(seed)
-    src, dst = rs.randint(0, n, 4 * n), rs.randint(0, n - 1, 4 * n)
-    loops = np.arange(0, n - 1, 2)
-    return (np.concatenate([src, loops, src[:5]]).astype(np.int64),
-            np.concatenate([dst, loops, dst[:5]]).astype(np.int64))
-
-
-def _setup_paths(reference):
-    for p in (os.path.join(REPO, 'oracle', 'dgl_stub'), os.path.join(reference, 'cluster_gcn')):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    os.environ.setdefault('MPLBACKEND', 'Agg')
 
 
 def forward(layers, g, h, cat):
@@ -201,7 +189,7 @@ def record_toy(seed):
 
 def _ist_worker(rank, S, port, outdir, reference):
     """oracle/gen_golden.py:_ist_worker on the GAT wrapper; parameters by state_dict() key."""
-    _setup_paths(reference)
+    reference_paths(reference)
     import torch
     import torch.distributed as dist
     import cluster_gcn_ist_distrib_gat as ref
@@ -271,7 +259,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reference', required=True, help='root of the reference project')
     a = ap.parse_args()
-    _setup_paths(a.reference)
+    reference_paths(a.reference)
     for seed in range(FIRST_SEED, FIRST_SEED + 32):
         files, smallest = record_toy(seed)
         if smallest > MIN_GRAD:
