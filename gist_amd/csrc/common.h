@@ -10,6 +10,7 @@
 #include "../../include/gist_hip.h"
 #include "dropout.h"
 #include "gemm_plan.h"
+#include "kernel_kit.h"      // the device primitives the kernels share (wave_sum, the tile map, the C-tile store, ...)
 
 namespace gist {
 
@@ -181,27 +182,6 @@ struct SpmmChoice {
 SpmmChoice spmm_choose(const SpmmCall &c);
 int spmm_run(const SpmmCall &c);
 int64_t spmm_lnb_units(int64_t n_row_blocks);      // partial rows a call with SpmmLnBwd writes
-#ifdef __HIPCC__
-// Sum over the 64 lanes of a wave, the same bits in every lane.  Within a row of 16 lanes on the DPP path of the vector unit
-// (lane ^ 1, lane ^ 2 as quad permutes; the other quad of the half row and the other half row as mirrors -- every lane of a
-// quad / half row holds the same partial sum by then), the four rows through the scalar unit: 4 + 4 + 3 instructions, none of
-// them on the LDS pipe (the __shfl_xor butterfly is six dependent ds_bpermute round trips).
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    v += dpp_move<0xB1>(v);       // quad_perm [1, 0, 3, 2]
-    v += dpp_move<0x4E>(v);       // quad_perm [2, 3, 0, 1]
-    v += dpp_move<0x141>(v);      // row_half_mirror
-    v += dpp_move<0x140>(v);      // row_mirror
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-    return (r0 + r1) + (r2 + r3);
-}
-#endif
 // spmm_mfma.hip: the block-dense aggregation kernel behind gist_spmm_csr_blocked_f32 / _prepared_f32
 // (prepared = NULL: every workgroup builds its block's counts itself).  pairs: may the batch have sibling blocks?  false
 // (gist_sage_step with plan->sibling_parts == 0): the prepare kernel looks for none and no pairs launch follows an
@@ -262,9 +242,5 @@ struct DeviceOnce {
         if (dev >= 0) mask.fetch_or(1ULL << dev, std::memory_order_release);
     }
 };
-
-// XCDs of the device the library runs on (gfx950: 8); blockIdx -> tile maps deal work round-robin
-// to XCDs the way the hardware dispatches consecutive workgroups.
-constexpr int kXcds = 8;
 
 }  // namespace gist

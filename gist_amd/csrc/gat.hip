@@ -25,27 +25,6 @@ constexpr float kGatSlope = 0.01f;       // F.leaky_relu's default negative slop
 constexpr int kGatRowsPerBlock = 4;      // one row per wave, four waves per workgroup
 constexpr int kGatStatRows = 256;        // rows per partial slab of the attention-vector gradient
 
-template <int VEC>
-__device__ __forceinline__ void gat_load(float (&v)[VEC], const float *p) {
-    if constexpr (VEC == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) v[k] = p[k];
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void gat_store(float *p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
-        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) p[k] = v[k];
-    }
-}
-
 // sum over the lanes of one group (xor offsets below LPG): pure adds, the same bits in every lane of the group
 template <int LPG>
 __device__ __forceinline__ float group_sum(float v) {
@@ -128,7 +107,7 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(
                 l = l * corr + p;
                 if (active) {
                     float z[VEC];
-                    gat_load<VEC>(z, zh + (int64_t)j * ldz);
+                    vload<VEC>(zh + (int64_t)j * ldz, z);
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) acc[k] = acc[k] * corr + p * z[k];
                 }
@@ -160,7 +139,7 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(
                 if (grp == 0 && active) {
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) o[k] = (elu && !(o[k] > 0.f)) ? expm1f(o[k]) : o[k];
-                    gat_store<VEC>(out + row * ldo + (int64_t)h * F + c, o);
+                    vstore<VEC>(out + row * ldo + (int64_t)h * F + c, o);
                 }
             }
         }
@@ -170,7 +149,7 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(
                 const float v = o[k] * inv_h;
                 o[k] = (elu && !(v > 0.f)) ? expm1f(v) : v;
             }
-            gat_store<VEC>(out + row * ldo + c, o);
+            vstore<VEC>(out + row * ldo + c, o);
         }
     }
 }
@@ -227,8 +206,8 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
             float part = 0.f;
             for (int c = li * VEC; c < F; c += LPG * VEC) {
                 float g[VEC], z[VEC];
-                gat_load<VEC>(g, gi + c);
-                gat_load<VEC>(z, zh + (int64_t)j * ldz + c);
+                vload<VEC>(gi + c, g);
+                vload<VEC>(zh + (int64_t)j * ldz + c, z);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) part = fmaf(g[k], z[k], part);
             }
@@ -282,8 +261,8 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
                 float part = 0.f;
                 for (int c = li * VEC; c < F; c += LPG * VEC) {
                     float g[VEC], z[VEC];
-                    gat_load<VEC>(g, gi + c);
-                    gat_load<VEC>(z, zj + c);
+                    vload<VEC>(gi + c, g);
+                    vload<VEC>(zj + c, z);
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) part = fmaf(g[k], z[k], part);
                     if (c == cw) {                // (the dot's loop passes this lane's output columns once)
@@ -303,7 +282,7 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
                 float v[VEC];
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) v[k] = acc[k] + dsrc * ah[cw + k] + sdj * ah[F + cw + k];
-                gat_store<VEC>(dZ + row * lddz + (int64_t)h * F + cw, v);
+                vstore<VEC>(dZ + row * lddz + (int64_t)h * F + cw, v);
             }
             if (c0 == 0 && lane == 0) ds_src[row * H + h] = dsrc;
         }

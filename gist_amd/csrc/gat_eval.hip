@@ -151,25 +151,6 @@ __global__ __launch_bounds__(256) void gat_blocks_dense_kernel(
     }
 }
 
-template <int VEC>
-__device__ __forceinline__ void eval_load(float (&v)[VEC], const float *p) {
-    if constexpr (VEC == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        v[0] = p[0];
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void eval_store(float *p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
-        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        p[0] = v[0];
-    }
-}
-
 // Remainder and epilogue: out = act(((dense part, read from out) + sum over the out-of-block edges) [/ H]).  One wave
 // per row, four rows per workgroup, as gat_aggregate_kernel (a workgroup per block would leave the chip a few thousand
 // waves for a latency-bound gather); the wave finds its row's block by bisection of block_ptr.  The wave's lanes form
@@ -213,7 +194,7 @@ __global__ __launch_bounds__(256) void gat_blocks_rest_kernel(
                 if ((j >= b0 && j < b1) || !active) continue;      // (inside the block: the dense kernel's)
                 const double p = (double)(expf(eval_score(s_src[(int64_t)j * H + h], sd) - m) * inv_l);
                 float z[VEC];
-                eval_load<VEC>(z, zh + (int64_t)j * ldz);
+                vload<VEC>(zh + (int64_t)j * ldz, z);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) acc[k] = fma(p, (double)z[k], acc[k]);
             }
@@ -226,26 +207,26 @@ __global__ __launch_bounds__(256) void gat_blocks_rest_kernel(
             if (cat && grp == 0 && active) {
                 float *dst = out + row * ldo + (int64_t)h * F + c;
                 float d[VEC];
-                eval_load<VEC>(d, dst);
+                vload<VEC>(dst, d);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) {
                     const float v = d[k] + o[k];
                     d[k] = (elu && !(v > 0.f)) ? expm1f(v) : v;
                     o[k] = 0.f;
                 }
-                eval_store<VEC>(dst, d);
+                vstore<VEC>(dst, d);
             }
         }
         if (!cat && grp == 0 && active) {
             float *dst = out + row * ldo + c;
             float d[VEC];
-            eval_load<VEC>(d, dst);
+            vload<VEC>(dst, d);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 const float v = (d[k] + o[k]) * scale;
                 d[k] = (elu && !(v > 0.f)) ? expm1f(v) : v;
             }
-            eval_store<VEC>(dst, d);
+            vstore<VEC>(dst, d);
         }
     }
 }

@@ -63,7 +63,7 @@ struct TailLoad {
     __device__ __forceinline__ void unit(int64_t u, float (&v)[VEC]) {
         float bb[VEC];
         bias(column(u), bb);
-        ln_all_load<VEC>(xb, u, v);
+        vload<VEC>(xb, u, v);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) v[k] = act(v[k] + bb[k]);
     }
@@ -78,8 +78,8 @@ struct TailLoadG {
     DropMask m;
     uint64_t offset;
     __device__ __forceinline__ void unit(int64_t u, float (&v)[VEC], float (&w)[VEC]) const {
-        ln_all_load<VEC>(gb, u, v);
-        ln_all_load<VEC>(yb, u, w);
+        vload<VEC>(gb, u, v);
+        vload<VEC>(yb, u, w);
         if (m.p > 0.f) {
             const uint64_t i0 = offset + (uint64_t)(head + u * VEC);
             if constexpr (VEC == 4) {
@@ -132,10 +132,10 @@ __global__ __launch_bounds__(256) void gcn_tail_write_kernel(const float *x, con
 #pragma unroll
             for (int k = 0; k < VEC; ++k) v[k] = ln_all_norm(v[k], mf, rstd);
         }
-        if (yhat != nullptr) ln_all_store<VEC>(yhat + ge.head, u, v);
+        if (yhat != nullptr) vstore<VEC>(yhat + ge.head, u, v);
         if (out != nullptr) {
             if (m.p > 0.f) drop_vec<VEC>(v, offset + (uint64_t)(ge.head + u * VEC), m);
-            ln_all_store<VEC>(out + ge.head, u, v);
+            vstore<VEC>(out + ge.head, u, v);
         }
     }
     const int64_t e = ln_all_edge(ge, VEC);
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void gcn_tail_bwd_apply_kernel(
     float bb[VEC], cs[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) cs[k] = 0.f;
-    if (live) ln_all_load<VEC>(b + c, 0, bb);
+    if (live) vload<VEC>(b + c, bb);
     if (live) {
 #pragma unroll
         for (int j = 0; j < kChunkRows / 4; ++j) {
@@ -190,9 +190,9 @@ __global__ __launch_bounds__(256) void gcn_tail_bwd_apply_kernel(
             if (row >= n_rows) break;
             const int64_t i0 = (int64_t)row * d + c;
             float g[VEC], xv[VEC], y[VEC] = {};
-            ln_all_load<VEC>(d_out + i0, 0, g);
-            ln_all_load<VEC>(x + i0, 0, xv);
-            if (norm) ln_all_load<VEC>(yhat + i0, 0, y);
+            vload<VEC>(d_out + i0, g);
+            vload<VEC>(x + i0, xv);
+            if (norm) vload<VEC>(yhat + i0, y);
             if (m.p > 0.f) {
                 if constexpr (VEC == 4) {
                     float f[4];
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void gcn_tail_bwd_apply_kernel(
                 g[k] = (!relu || xv[k] + bb[k] > 0.f) ? da : 0.f;      // the forward's own add; no gradient at 0
                 cs[k] += g[k];
             }
-            ln_all_store<VEC>(dx + i0, 0, g);
+            vstore<VEC>(dx + i0, g);
         }
     }
     if (wave > 0) {
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void gcn_tail_bwd_apply_kernel(
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
             o[k] = ((cs[k] + part[0][lane * VEC + k]) + part[1][lane * VEC + k]) + part[2][lane * VEC + k];
-        ln_all_store<VEC>(col_sums + (int64_t)blockIdx.x * d + c, 0, o);
+        vstore<VEC>(col_sums + (int64_t)blockIdx.x * d + c, o);
     }
 }
 

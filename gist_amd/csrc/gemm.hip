@@ -273,18 +273,6 @@ __device__ __forceinline__ void dma_offsets_mc(int64_t ld, int col0, int wave, i
     }
 }
 
-template <int IT>
-__device__ __forceinline__ void dma_image(const float *ubase, const uint32_t *off, float *image,
-                                          int wave) {
-    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(ubase), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-    for (int jj = 0; jj < IT; ++jj)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsrc, (__attribute__((address_space(3))) void *)(image + (IT * wave + jj) * 256), 16,
-            off[jj], 0, 0, 0);
-}
-
 // ---- LDS -> fragment ---------------------------------------------------------
 // The 4 values a lane feeds to MFMA steps j = 0..3 of k block q (k = 8q + 4hh .. +3) of the
 // 32-row (or 32-column) slab whose row for this lane is `row`.
@@ -326,18 +314,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const int block
     // buffer b: A image at smem + b*(TA+TB), B image right behind it
 
     // ---- block -> output tile, 8x8 super-tiles per XCD ------------------------
-    const int nwg = g.tiles_m * g.tiles_n;
-    const int orig = block_x;
-    const int qd = nwg / kXcds, rm = nwg % kXcds, xcd = orig % kXcds;
-    const int L = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + orig / kXcds;
-    constexpr int GM = 8;
-    const int width = GM * g.tiles_n;
-    const int group = L / width;
-    const int first_m = group * GM;
-    const int gsz = min(g.tiles_m - first_m, GM);
-    const int bm = first_m + (L % width) % gsz;
-    const int bn = (L % width) / gsz;
-    const int row0 = bm * T, col0 = bn * T;
+    const TileOf tile = tile_of_linear(xcd_linear(block_x, g.tiles_m * g.tiles_n), g.tiles_m, g.tiles_n);
+    const int row0 = tile.bm * T, col0 = tile.bn * T;
 
     const int k_begin = block_z * g.k_per_split;
     const int k_end = min(g.k, k_begin + g.k_per_split);
@@ -374,8 +352,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs &g, const int block
     auto dma = [&](int buf, int kt) {
         const int k0 = k_begin + kt * BK;
         float *sa = smem + buf * (TA + TB);
-        dma_image<IT>(originA + (A_KC ? (int64_t)k0 : (int64_t)k0 * g.lda), offA, sa, wave_u);
-        dma_image<IT>(originB + (B_KC ? (int64_t)k0 : (int64_t)k0 * g.ldb), offB, sa + TA, wave_u);
+        lds_dma_image<IT>(originA + (A_KC ? (int64_t)k0 : (int64_t)k0 * g.lda), offA, reinterpret_cast<char *>(sa), IT * wave_u);
+        lds_dma_image<IT>(originB + (B_KC ? (int64_t)k0 : (int64_t)k0 * g.ldb), offB, reinterpret_cast<char *>(sa + TA), IT * wave_u);
     };
     auto gload = [&](int kt) {
         const int k0 = k_begin + kt * BK;

@@ -90,11 +90,6 @@ struct B3SplitList {
     int n;
 };
 
-__device__ __forceinline__ uint32_t b3_pack(__bf16 lo, __bf16 hi) {
-    return (uint32_t)__builtin_bit_cast(unsigned short, lo) |
-           ((uint32_t)__builtin_bit_cast(unsigned short, hi) << 16);
-}
-
 // x -> RNE bf16(x), bf16(x - b1), bf16(x - b1 - b2) (both differences exact)
 __device__ __forceinline__ void b3_pieces(float x, __bf16 (&p)[3]) {
     p[0] = (__bf16)x;
@@ -197,7 +192,7 @@ __global__ __launch_bounds__(B3S_THREADS) void b3_split_kernel(B3SplitList L) {
             b3_pieces(v[i][e], a);
             b3_pieces(v[i + 1][e], b);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) tw[e][q][i >> 1] = b3_pack(a[q], b[q]);
+            for (int q = 0; q < 3; ++q) tw[e][q][i >> 1] = pack_bf16x2(a[q], b[q]);
         }
     }
 #pragma unroll
@@ -279,18 +274,6 @@ __device__ __forceinline__ void b3_mfma(b3_f32x4 &acc, const bf16x8 &a, const bf
     asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
 
-template <int NI>
-__device__ __forceinline__ void b3_dma_image(const char *base, const uint32_t (&off)[NI], char *image,
-                                             int first) {
-    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(base), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-    for (int jj = 0; jj < NI; ++jj)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsrc, (__attribute__((address_space(3))) void *)(image + (first + jj) * 1024), 16, off[jj],
-            0, 0, 0);
-}
-
 __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
     extern __shared__ __attribute__((aligned(16))) char b3_smem[];
     constexpr int NI = 4, NJ = 4;                 // 16-row slabs per wave: 64 x 64 wave tile
@@ -299,17 +282,8 @@ __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
     const bool tail = orig >= nwg;       // a k slice of one of the tiles past the last full round
     const int tail_tile = tail ? (orig - nwg) / g.tail_splits : 0;
     const int tail_slice = tail ? (orig - nwg) % g.tail_splits : 0;
-    const int qd = nwg / kXcds, rm = nwg % kXcds, xcd = orig % kXcds;
-    const int L = tail ? nwg + tail_tile
-                       : (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + orig / kXcds;
-    constexpr int GM = 8;
-    const int width = GM * g.tiles_n;
-    const int group = L / width;
-    const int first_m = group * GM;
-    const int gsz = min(g.tiles_m - first_m, GM);
-    const int bm = first_m + (L % width) % gsz;
-    const int bn = (L % width) / gsz;
-    const int row0 = bm * B3_TM, col0 = bn * B3_TN;
+    const TileOf tile = tile_of_linear(tail ? nwg + tail_tile : xcd_linear(orig, nwg), g.tiles_m, g.tiles_n);
+    const int row0 = tile.bm * B3_TM, col0 = tile.bn * B3_TN;
     // split-K: this workgroup's k tiles
     const int kt0 = tail ? tail_slice * g.tail_kt : (int)blockIdx.y * g.kt_per_split;
     const int n_kt = min(g.kpad / B3_BK - kt0, tail ? g.tail_kt : g.kt_per_split);
@@ -337,8 +311,8 @@ __global__ __launch_bounds__(B3_THREADS, 2) void gemm_b3_kernel(B3Args g) {
     const char *originB = reinterpret_cast<const char *>(g.b) + (int64_t)col0 * g.ldb * 6 + (int64_t)kt0 * B3_KT_BYTES;
     auto dma = [&](int buf, int kt) {
         char *sa = b3_smem + buf * B3_BUF_BYTES;
-        b3_dma_image<DA>(originA + (int64_t)kt * B3_KT_BYTES, offA, sa, DA * wave);
-        b3_dma_image<DB>(originB + (int64_t)kt * B3_KT_BYTES, offB, sa + B3_A_BYTES, DB * wave);
+        lds_dma_image<DA>(originA + (int64_t)kt * B3_KT_BYTES, offA, sa, DA * wave);
+        lds_dma_image<DB>(originB + (int64_t)kt * B3_KT_BYTES, offB, sa + B3_A_BYTES, DB * wave);
     };
 
     // fragment addresses: chunk c = 3 kg + piece of row rr of slab s sits at slot
@@ -531,16 +505,8 @@ __global__ __launch_bounds__(B3_THREADS, 1) void gemm_b3_wide_kernel(B3Args g) {
     constexpr int NI = 4, NJ = 8;                 // 16-row slabs per wave: 64 x 128 wave tile
     const int nwg = g.dp_tiles;
     const int orig = blockIdx.x;
-    const int qd = nwg / kXcds, rm = nwg % kXcds, xcd = orig % kXcds;
-    const int L = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + orig / kXcds;
-    constexpr int GM = 8;
-    const int width = GM * g.tiles_n;
-    const int group = L / width;
-    const int first_m = group * GM;
-    const int gsz = min(g.tiles_m - first_m, GM);
-    const int bm = first_m + (L % width) % gsz;
-    const int bn = (L % width) / gsz;
-    const int row0 = bm * B3_TM, col0 = bn * B3W_TN;
+    const TileOf tile = tile_of_linear(xcd_linear(orig, nwg), g.tiles_m, g.tiles_n);
+    const int row0 = tile.bm * B3_TM, col0 = tile.bn * B3W_TN;
     const int n_kt = g.kpad / B3_BK;
 
     const int lane = threadIdx.x & 63;
@@ -564,8 +530,8 @@ __global__ __launch_bounds__(B3_THREADS, 1) void gemm_b3_wide_kernel(B3Args g) {
     const char *originA = reinterpret_cast<const char *>(g.a) + (int64_t)row0 * g.lda * 6;
     const char *originB = reinterpret_cast<const char *>(g.b) + (int64_t)col0 * g.ldb * 6;
     auto dma = [&](int bbuf, int kt) {
-        b3_dma_image<DA>(originA + (int64_t)kt * B3_KT_BYTES, offA, b3_smem, DA * wave);
-        b3_dma_image<DB>(originB + (int64_t)kt * B3_KT_BYTES, offB, b3_smem + B3_A_BYTES + bbuf * B3W_B_BYTES,
+        lds_dma_image<DA>(originA + (int64_t)kt * B3_KT_BYTES, offA, b3_smem, DA * wave);
+        lds_dma_image<DB>(originB + (int64_t)kt * B3_KT_BYTES, offB, b3_smem + B3_A_BYTES + bbuf * B3W_B_BYTES,
                          DB * wave);
     };
 
@@ -715,12 +681,9 @@ __global__ __launch_bounds__(B3_THREADS, 1) void gemm_b3_wide_kernel(B3Args g) {
 // The tiles the tail units computed: C tile = sum over its k slices of the partials, in slice order (+ bias).
 // Grid (tile, accumulator register 0..15); a thread holds the element(s) its twin in gemm_b3_kernel held.
 __global__ __launch_bounds__(B3_THREADS) void gemm_b3_tail_sum_kernel(B3Args g) {
-    constexpr int NI = 4, NJ = 4, GM = 8;
-    const int L = g.dp_tiles + (int)blockIdx.x;
-    const int width = GM * g.tiles_n;
-    const int first_m = (L / width) * GM;
-    const int gsz = min(g.tiles_m - first_m, GM);
-    const int row0 = (first_m + (L % width) % gsz) * B3_TM, col0 = ((L % width) / gsz) * B3_TN;
+    constexpr int NI = 4, NJ = 4;
+    const TileOf tile = tile_of_linear(g.dp_tiles + (int)blockIdx.x, g.tiles_m, g.tiles_n);
+    const int row0 = tile.bm * B3_TM, col0 = tile.bn * B3_TN;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1, rr = lane & 15, kg = lane >> 4;
     const int reg = blockIdx.y, i = reg / NJ, j = reg % NJ;

@@ -223,22 +223,13 @@ __global__ __launch_bounds__(512, 1) void gemm_b3c_kernel(C3Args g) {
     constexpr int WM = TM / 2, WN = TN / 2;                  // consumer wave tile (2 x 2 waves)
     constexpr int NI = WM / 16, NJ = WN / 16;                // 16 x 16 MFMA tiles per wave
 
-    // ---- block -> output tile, 8 x 8 super-tiles per XCD (as gemm.hip) ----
+    // ---- block -> output tile (kernel_kit.h); a tail unit is a k slice of one of the tiles past the last full round ----
     const int nwg = g.dp_tiles;
     const int orig = blockIdx.x;
     const bool tailu = orig >= nwg;
     const int tail_unit = tailu ? orig - nwg : 0;
-    const int qd = nwg / kXcds, rm = nwg % kXcds, xcd = orig % kXcds;
-    const int L = tailu ? nwg + tail_unit / g.tail_splits
-                        : (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + orig / kXcds;
-    constexpr int GM = 8;
-    const int width = GM * g.tiles_n;
-    const int group = L / width;
-    const int first_m = group * GM;
-    const int gsz = min(g.tiles_m - first_m, GM);
-    const int bm = first_m + (L % width) % gsz;
-    const int bn = (L % width) / gsz;
-    const int row0 = bm * TM, col0 = bn * TN;
+    const TileOf tile = tile_of_linear(tailu ? nwg + tail_unit / g.tail_splits : xcd_linear(orig, nwg), g.tiles_m, g.tiles_n);
+    const int row0 = tile.bm * TM, col0 = tile.bn * TN;
     const int k_begin = tailu ? (tail_unit % g.tail_splits) * g.tail_k : blockIdx.z * g.k_per_split;
     const int k_end = min(g.k, k_begin + (tailu ? g.tail_k : g.k_per_split));
     const int n_kt = (k_end - k_begin + C3_BK - 1) / C3_BK;
@@ -513,10 +504,8 @@ __global__ __launch_bounds__(512, 1) void gemm_b3c_kernel(C3Args g) {
 
 // C tile = sum over its k slices of the tail units' results, in slice order (+ bias).  Grid (tail tile, TM * TN / 1024).
 __global__ __launch_bounds__(256) void gemm_b3c_tail_sum_kernel(C3Args g, int tm, int tn) {
-    const int L = g.dp_tiles + (int)blockIdx.x;
-    constexpr int GM = 8;
-    const int width = GM * g.tiles_n, first_m = (L / width) * GM, gsz = min(g.tiles_m - first_m, GM);
-    const int row0 = (first_m + (L % width) % gsz) * tm, col0 = ((L % width) / gsz) * tn;
+    const TileOf tile = tile_of_linear(g.dp_tiles + (int)blockIdx.x, g.tiles_m, g.tiles_n);
+    const int row0 = tile.bm * tm, col0 = tile.bn * tn;
     const int e4 = ((int)blockIdx.y * 256 + (int)threadIdx.x) * 4;      // four consecutive columns of one tile row
     const int r = e4 / tn, c = e4 % tn;
     if (r >= tm || row0 + r >= g.m) return;

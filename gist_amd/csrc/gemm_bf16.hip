@@ -43,8 +43,7 @@ struct X1CastJob {
 struct X1CastList { X1CastJob job[2]; };
 
 __device__ __forceinline__ uint32_t x1_pack(float lo, float hi) {
-    return (uint32_t)__builtin_bit_cast(unsigned short, (__bf16)lo) |
-           ((uint32_t)__builtin_bit_cast(unsigned short, (__bf16)hi) << 16);
+    return pack_bf16x2((__bf16)lo, (__bf16)hi);
 }
 
 __global__ __launch_bounds__(X1_THREADS) void x1_cast_kernel(X1CastList L) {
@@ -81,16 +80,7 @@ __global__ __launch_bounds__(X1_THREADS) void x1_cast_kernel(X1CastList L) {
         for (int i = 0; i < 4; ++i) {
             const int64_t kk = k0 + kr + 16 * i;
             float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (kk < J.k) {
-                const float *s = J.src + kk * J.ld + c;
-                if (whole) q = *reinterpret_cast<const float4 *>(s);
-                else {
-                    if (c + 0 < J.rows) q.x = s[0];
-                    if (c + 1 < J.rows) q.y = s[1];
-                    if (c + 2 < J.rows) q.z = s[2];
-                    if (c + 3 < J.rows) q.w = s[3];
-                }
-            }
+            if (kk < J.k) load4_ragged(J.src + kk * J.ld + c, c, J.rows, whole, q);
             float *d = &tile[kr + 16 * i][4 * cq];
             d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
         }
@@ -133,26 +123,10 @@ __device__ __forceinline__ void x1_dma_offsets(int64_t pitch, int rows, int row0
     }
 }
 
-__device__ __forceinline__ void x1_dma_image(const uint16_t *ubase, const uint32_t (&off)[X1_DMA], char *image, int wave) {
-    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(ubase), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-    for (int jj = 0; jj < X1_DMA; ++jj)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(image + (X1_DMA * wave + jj) * 1024),
-                                                 16, off[jj], 0, 0, 0);
-}
-
 __global__ __launch_bounds__(X1_THREADS, 2) void gemm_bf16x1_kernel(X1Args g) {
     extern __shared__ __attribute__((aligned(16))) char x1_smem[];
-    // ---- block -> output tile, 8-row super-tiles per XCD (gemm.hip) ----
-    const int nwg = g.tiles_m * g.tiles_n;
-    const int orig = (int)blockIdx.x;
-    const int qd = nwg / kXcds, rm = nwg % kXcds, xcd = orig % kXcds;
-    const int L = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + orig / kXcds;
-    constexpr int GM = 8;
-    const int width = GM * g.tiles_n;
-    const int first_m = (L / width) * GM;
-    const int gsz = min(g.tiles_m - first_m, GM);
-    const int row0 = (first_m + (L % width) % gsz) * X1_T, col0 = ((L % width) / gsz) * X1_T;
+    const TileOf tile = tile_of_linear(xcd_linear((int)blockIdx.x, g.tiles_m * g.tiles_n), g.tiles_m, g.tiles_n);
+    const int row0 = tile.bm * X1_T, col0 = tile.bn * X1_T;
 
     const int n_kt_all = g.kpad / X1_BK;
     const int kt_begin = (int)blockIdx.z * g.kt_per_split;
@@ -176,8 +150,8 @@ __global__ __launch_bounds__(X1_THREADS, 2) void gemm_bf16x1_kernel(X1Args g) {
     const uint16_t *originB = g.b + (int64_t)col0 * g.kpad + (int64_t)kt_begin * X1_BK;
     auto dma = [&](int buf, int kt) {
         char *sa = x1_smem + buf * X1_STAGE_BYTES;
-        x1_dma_image(originA + (int64_t)kt * X1_BK, offA, sa, wave);
-        x1_dma_image(originB + (int64_t)kt * X1_BK, offB, sa + X1_IMG_BYTES, wave);
+        lds_dma_image<X1_DMA>(originA + (int64_t)kt * X1_BK, offA, sa, X1_DMA * wave);
+        lds_dma_image<X1_DMA>(originB + (int64_t)kt * X1_BK, offB, sa + X1_IMG_BYTES, X1_DMA * wave);
     };
     // fragment byte offsets inside an image: tile i of the wave, k step s (32 k): row, chunk 4 s + kg
     int aoff[4][2], boff[4][2];

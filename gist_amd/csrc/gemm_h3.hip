@@ -41,12 +41,6 @@ constexpr int H3_BUF_BYTES = 2 * H3_IMG * 4;      // A + B image of one stage
 // One power-of-two scale per ROW of a split operand (= per output row for A, per output column
 // for B): a row's error depends on its own magnitude only, whatever the spread between rows
 // (gradient rows differ by orders of magnitude).
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 // x * scale has its largest magnitude in [2^13, 2^14): hi never overflows f16 (65504), lo of
 // every element above 2^-17 of the row maximum is a normal f16, and the representation error
 // of any element is below max(2^-22 |x|, 2^-39 row max).
@@ -128,15 +122,8 @@ __global__ __launch_bounds__(256) void h3_colmax_kernel(const float *__restrict_
     for (int i = 0; i < 16; ++i) {
         const int kk = k0 + kr + 16 * i;
         if (kk < k) {
-            const float *p = src + (int64_t)kk * ld + c0 + c4;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c0 + c4 + 3 < cols) {
-                v = *reinterpret_cast<const float4 *>(p);
-            } else {
-                if (c0 + c4 + 0 < cols) v.x = p[0];
-                if (c0 + c4 + 1 < cols) v.y = p[1];
-                if (c0 + c4 + 2 < cols) v.z = p[2];
-            }
+            load4_ragged(src + (int64_t)kk * ld + c0 + c4, c0 + c4, cols, v);
             m.x = fmaxf(m.x, fabsf(v.x)); m.y = fmaxf(m.y, fabsf(v.y));
             m.z = fmaxf(m.z, fabsf(v.z)); m.w = fmaxf(m.w, fabsf(v.w));
         }
@@ -172,16 +159,7 @@ __global__ __launch_bounds__(256) void h3_split_t_kernel(const float *__restrict
     for (int i = 0; i < 4; ++i) {
         const int kk = (t >> 4) + 16 * i;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (k0 + kk < k) {
-            const float *p = src + (int64_t)(k0 + kk) * ld + c0 + c4;
-            if (c0 + c4 + 3 < cols) {
-                v = *reinterpret_cast<const float4 *>(p);
-            } else {
-                if (c0 + c4 + 0 < cols) v.x = p[0];
-                if (c0 + c4 + 1 < cols) v.y = p[1];
-                if (c0 + c4 + 2 < cols) v.z = p[2];
-            }
-        }
+        if (k0 + kk < k) load4_ragged(src + (int64_t)(k0 + kk) * ld + c0 + c4, c0 + c4, cols, v);
         tile[kk][c4 + 0] = v.x; tile[kk][c4 + 1] = v.y;
         tile[kk][c4 + 2] = v.z; tile[kk][c4 + 3] = v.w;
     }
@@ -320,18 +298,6 @@ struct H3Args {
     int tiles_m, tiles_n;
 };
 
-template <int NI>
-__device__ __forceinline__ void h3_dma_image(const uint32_t *ubase, const uint32_t (&off)[NI],
-                                             char *image, int wave) {
-    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint32_t *>(ubase), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-    for (int jj = 0; jj < NI; ++jj)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsrc, (__attribute__((address_space(3))) void *)(image + (NI * wave + jj) * 1024), 16,
-            off[jj], 0, 0, 0);
-}
-
 // 128 x 128 x 32 block tile, 256 threads = 4 waves in 2x2, each wave 64x64 = 4x4 tiles of
 // v_mfma_f32_16x16x32_f16 (48 MFMAs of 16 cycles per k tile), two LDS stages of 32 KiB, two
 // workgroups per CU, LDS-DMA staging issued one k tile ahead.  The 16x16x32 shape is chosen over
@@ -369,18 +335,8 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(H3Args g) {
     constexpr int A_BYTES = TM * 128;            // A image of one stage
     constexpr int BUF_BYTES = A_BYTES + H3_IMG * 4;
 
-    const int nwg = g.tiles_m * g.tiles_n;
-    const int orig = blockIdx.x;
-    const int qd = nwg / kXcds, rm = nwg % kXcds, xcd = orig % kXcds;
-    const int L = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + orig / kXcds;
-    constexpr int GM = 8;
-    const int width = GM * g.tiles_n;
-    const int group = L / width;
-    const int first_m = group * GM;
-    const int gsz = min(g.tiles_m - first_m, GM);
-    const int bm = first_m + (L % width) % gsz;
-    const int bn = (L % width) / gsz;
-    const int row0 = bm * TM, col0 = bn * T;
+    const TileOf tile = tile_of_linear(xcd_linear(blockIdx.x, g.tiles_m * g.tiles_n), g.tiles_m, g.tiles_n);
+    const int row0 = tile.bm * TM, col0 = tile.bn * T;
     const int n_kt = g.kpad / H3_BK;
 
     const int lane = threadIdx.x & 63;
@@ -403,8 +359,8 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(H3Args g) {
     const uint32_t *originB = g.b + (int64_t)col0 * g.ldb;
     auto dma = [&](int buf, int kt) {
         char *sa = h3_smem + buf * BUF_BYTES;
-        h3_dma_image<NI>(originA + (int64_t)kt * H3_BK, offA, sa, wave);
-        h3_dma_image<4>(originB + (int64_t)kt * H3_BK, offB, sa + A_BYTES, wave);
+        lds_dma_image<NI>(originA + (int64_t)kt * H3_BK, offA, sa, NI * wave);
+        lds_dma_image<4>(originB + (int64_t)kt * H3_BK, offB, sa + A_BYTES, 4 * wave);
     };
 
     // fragment byte offsets inside an image: [16-row slab][hi/lo]

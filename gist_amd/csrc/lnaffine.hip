@@ -16,20 +16,6 @@ namespace {
 constexpr int kE = 16;
 constexpr int kChunkRows = 16;      // gist_row_chunks16
 
-template <int TPR>
-__device__ __forceinline__ float lna_row_sum(float v, float *red) {
-    v = wave_sum(v);
-    if constexpr (TPR == 64) {
-        return v;
-    } else {
-        const int w = threadIdx.x >> 6;
-        __syncthreads();                      // red[] may still be read from a previous call
-        if ((threadIdx.x & 63) == 0) red[w] = v;
-        __syncthreads();
-        return red[0] + red[1] + red[2] + red[3];
-    }
-}
-
 // gamma * yhat + beta as ONE fused multiply-add: the forward's ReLU and the backward's gate call this on the same
 // float32 operands, so they see the same bits
 __device__ __forceinline__ float affine_pre(float yh, float g, float b) { return fmaf(g, yh, b); }
@@ -91,7 +77,8 @@ __device__ __forceinline__ float sum_elems(const float (&v)[kE]) {
     return s;
 }
 
-// VEC consecutive floats at p (re-reading path)
+// VEC consecutive floats at p (re-reading path).  Not kernel_kit.h's vload / vstore / vsum on float[VEC]: written
+// that way the five TPR = 256 kernels that re-read come out with other address arithmetic and more instructions.
 template <int VEC>
 struct Pack { float v[VEC]; };
 template <int VEC>
@@ -186,14 +173,14 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
 #pragma unroll
             for (int e = 0; e < kE; ++e) v[e] += b[e];
         }
-        const float mean = lna_row_sum<TPR>(sum_elems<VEC>(v), red) / (float)d;
+        const float mean = row_sum<TPR>(sum_elems<VEC>(v), red) / (float)d;
         float sq[kE];
 #pragma unroll
         for (int e = 0; e < kE; ++e) {
             v[e] = elem_col<TPR, VEC>(t, e) < d ? v[e] - mean : 0.f;
             sq[e] = v[e] * v[e];
         }
-        const float var = lna_row_sum<TPR>(sum_elems<VEC>(sq), red) / (float)d;
+        const float var = row_sum<TPR>(sum_elems<VEC>(sq), red) / (float)d;
         const float rstd = 1.0f / sqrtf(var + eps);
         if (!live) return;
         if constexpr (SAVE) {
@@ -229,7 +216,7 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
         };
         float s = 0.f;
         for (int c = t * VEC; c < d; c += 256 * VEC) s += sum_pack<VEC>(value(c));
-        const float mean = lna_row_sum<TPR>(s, red) / (float)d;
+        const float mean = row_sum<TPR>(s, red) / (float)d;
         float q = 0.f;
         for (int c = t * VEC; c < d; c += 256 * VEC) {
             Pack<VEC> p = value(c);
@@ -237,7 +224,7 @@ __global__ __launch_bounds__(256) void ln_affine_fwd_kernel(
             for (int k = 0; k < VEC; ++k) { p.v[k] -= mean; p.v[k] *= p.v[k]; }
             q += sum_pack<VEC>(p);
         }
-        const float var = lna_row_sum<TPR>(q, red) / (float)d;
+        const float var = row_sum<TPR>(q, red) / (float)d;
         const float rstd = 1.0f / sqrtf(var + eps);
         if constexpr (SAVE) {
             if (t == 0) rstd_out[row] = rstd;
@@ -304,8 +291,8 @@ __global__ __launch_bounds__(256) void ln_affine_bwd_kernel(
                 a[e] = g[e] * ga[e];
                 b[e] = a[e] * y[e];
             }
-            const float m1 = lna_row_sum<TPR>(sum_elems<VEC>(a), red) / (float)d;
-            const float m2 = lna_row_sum<TPR>(sum_elems<VEC>(b), red) / (float)d;
+            const float m1 = row_sum<TPR>(sum_elems<VEC>(a), red) / (float)d;
+            const float m2 = row_sum<TPR>(sum_elems<VEC>(b), red) / (float)d;
             const float rstd = rstd_in[row];
 #pragma unroll
             for (int e = 0; e < kE; ++e) {
@@ -378,8 +365,8 @@ __global__ __launch_bounds__(256) void ln_affine_bwd_kernel(
                 s1 += sum_pack<VEC>(a);
                 s2 += sum_pack<VEC>(b);
             }
-            const float m1 = lna_row_sum<TPR>(s1, red) / (float)d;
-            const float m2 = lna_row_sum<TPR>(s2, red) / (float)d;
+            const float m1 = row_sum<TPR>(s1, red) / (float)d;
+            const float m2 = row_sum<TPR>(s2, red) / (float)d;
             const float rstd = rstd_in[row];
             for (int c = t * VEC; c < d; c += 256 * VEC) {
                 const Pack<VEC> y = ld<VEC>(yr + c);

@@ -77,30 +77,6 @@ __device__ __forceinline__ int64_t ln_all_edge(const LnAllGeom &ge, int vec) {
     return -1;
 }
 
-template <int VEC>
-__device__ __forceinline__ void ln_all_load(const float *p, int64_t u, float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
-        const float4 q = *reinterpret_cast<const float4 *>(p + 4 * u);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = p[u];
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void ln_all_store(float *p, int64_t u, const float (&v)[VEC]) {
-    if constexpr (VEC == 4)
-        *reinterpret_cast<float4 *>(p + 4 * u) = make_float4(v[0], v[1], v[2], v[3]);
-    else
-        p[u] = v[0];
-}
-
-template <int VEC>
-__device__ __forceinline__ float ln_all_add(const float (&v)[VEC]) {
-    if constexpr (VEC == 4) return (v[0] + v[1]) + (v[2] + v[3]);
-    else return v[0];
-}
-
 // the double sums of the partial array every workgroup of a second launch forms, in one fixed order
 template <int VEC, typename F>
 __device__ __forceinline__ double ln_all_merge(const LnAllGeom &ge, double *red, F term) {
@@ -135,7 +111,7 @@ __device__ __forceinline__ void ln_all_fwd_partials(const LnAllGeom &ge, L &ld, 
     for (int64_t u = u0 + threadIdx.x; u < u1; u += 256) {
         float v[VEC];
         ld.unit(u, v);
-        s += ln_all_add<VEC>(v);
+        s += vsum<VEC>(v);
     }
     if (e >= 0) s += ld.edge(e);
     const double S = block_sum_f64((double)s, red);
@@ -147,8 +123,8 @@ __device__ __forceinline__ void ln_all_fwd_partials(const LnAllGeom &ge, L &ld, 
         ld.unit(u, v);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { v[k] -= m; w[k] = v[k] * v[k]; }
-        c += ln_all_add<VEC>(v);
-        q += ln_all_add<VEC>(w);
+        c += vsum<VEC>(v);
+        q += vsum<VEC>(w);
     }
     if (e >= 0) { const float a = ld.edge(e) - m; c += a; q += a * a; }
     const double Q = block_sum_f64((double)q, red);
@@ -185,10 +161,10 @@ __device__ __forceinline__ void ln_all_bwd_partials(const LnAllGeom &ge, L &ld, 
     for (int64_t u = u0 + threadIdx.x; u < u1; u += 256) {
         float v[VEC], y[VEC];
         ld.unit(u, v, y);
-        s1 += ln_all_add<VEC>(v);
+        s1 += vsum<VEC>(v);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) y[k] *= v[k];
-        s2 += ln_all_add<VEC>(y);
+        s2 += vsum<VEC>(y);
     }
     const int64_t e = ln_all_edge(ge, VEC);
     if (e >= 0) {

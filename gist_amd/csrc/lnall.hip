@@ -26,15 +26,15 @@ namespace gist {
 template <int VEC>
 struct LnAllPlain {
     const float *x, *xb;      // element 0, unit 0
-    __device__ __forceinline__ void unit(int64_t u, float (&v)[VEC]) const { ln_all_load<VEC>(xb, u, v); }
+    __device__ __forceinline__ void unit(int64_t u, float (&v)[VEC]) const { vload<VEC>(xb, u, v); }
     __device__ __forceinline__ float edge(int64_t e) const { return x[e]; }
 };
 template <int VEC>
 struct LnAllPlain2 {
     const float *g, *gb, *y, *yb;
     __device__ __forceinline__ void unit(int64_t u, float (&v)[VEC], float (&w)[VEC]) const {
-        ln_all_load<VEC>(gb, u, v);
-        ln_all_load<VEC>(yb, u, w);
+        vload<VEC>(gb, u, v);
+        vload<VEC>(yb, u, w);
     }
     __device__ __forceinline__ void edge(int64_t e, float &a, float &b) const { a = g[e]; b = y[e]; }
 };
@@ -64,10 +64,10 @@ __global__ __launch_bounds__(256) void ln_all_fwd_norm_kernel(const float *x, fl
 #pragma unroll 4
     for (int64_t u = u0 + threadIdx.x; u < u1; u += 256) {
         float v[VEC];
-        ln_all_load<VEC>(xb, u, v);
+        vload<VEC>(xb, u, v);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) v[k] = ln_all_norm(v[k], mf, rstd);
-        ln_all_store<VEC>(yb, u, v);
+        vstore<VEC>(yb, u, v);
     }
     const int64_t e = ln_all_edge(ge, VEC);
     if (e >= 0) yhat[e] = ln_all_norm(x[e], mf, rstd);
@@ -100,11 +100,11 @@ __global__ __launch_bounds__(256) void ln_all_bwd_apply_kernel(const float *g, c
 #pragma unroll 4
     for (int64_t u = u0 + threadIdx.x; u < u1; u += 256) {
         float v[VEC], y[VEC];
-        ln_all_load<VEC>(gb, u, v);
-        ln_all_load<VEC>(yb, u, y);
+        vload<VEC>(gb, u, v);
+        vload<VEC>(yb, u, y);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) v[k] = ln_all_dx(v[k], y[k], m1, m2, rstd);
-        ln_all_store<VEC>(db, u, v);
+        vstore<VEC>(db, u, v);
     }
     const int64_t e = ln_all_edge(ge, VEC);
     if (e >= 0) dx[e] = ln_all_dx(g[e], yhat[e], m1, m2, rstd);

@@ -1,7 +1,10 @@
-// Row-wise (HBM-bound) pieces of one ISTSAGELayer step on gfx950:
-// LayerNorm(no affine)+ReLU forward/backward, dropout, bias gradient (column sum),
-// softmax cross-entropy, Adam, argmax accuracy.  Reference lines are cited at the
-// C-ABI declarations in include/gist_hip.h.
+// Row-wise (HBM-bound) kernels on gfx950, written for one ISTSAGELayer step and since shared by the steps of every
+// model family: LayerNorm(no affine)+ReLU forward (alone, with the next layer's dropout folded in, or reading its input
+// as split-K slabs) and backward (alone, with the bias gradient's 16-row chunk partials, with the class layer's dW),
+// dropout (alone, or in a narrow NN projection), bias gradient (column sum, in stages or from chunk partials), softmax
+// cross-entropy, Adam (one tensor, segments, stream) with the gradient finish, argmax accuracy.  The affine LayerNorm
+// tail is lnaffine.hip, the whole-tensor LayerNorm lnall.hip.  Reference lines are cited at the C-ABI declarations in
+// include/gist_hip.h.
 //
 // Each kernel streams its rows once or twice with 16-B accesses where alignment
 // allows; rows are owned by one wave (d <= 1024) or one 256-thread workgroup.
@@ -13,21 +16,7 @@
 
 namespace gist {
 
-// (wave_sum: common.h)
-// Sum over the TPR threads that own one row (TPR = 64: a wave; TPR = 256: the block).
-template <int TPR>
-__device__ __forceinline__ float row_sum(float v, float *red) {
-    v = wave_sum(v);
-    if constexpr (TPR == 64) {
-        return v;
-    } else {
-        const int w = threadIdx.x >> 6;
-        __syncthreads();                      // red[] may still be read from a previous call
-        if ((threadIdx.x & 63) == 0) red[w] = v;
-        __syncthreads();
-        return red[0] + red[1] + red[2] + red[3];
-    }
-}
+// (wave_sum, wave_max, row_sum: kernel_kit.h)
 
 // Dropout folded into a producer (gist_ln_relu_fwd_drop_f32): what the producer stores at row r,
 // column c of `out` is multiplied by the mask gist_dropout_f32 would apply to element index
@@ -249,7 +238,7 @@ __global__ __launch_bounds__(256) void ln_relu_bwd_kernel(
                 *reinterpret_cast<float4 *>(dr + c) = o;
                 mx = fmaxf(mx, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
             }
-            if (rowmax != nullptr) {
+            if (rowmax != nullptr) {      // (wave_max open-coded, here and below: as a call it changes this kernel's code)
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
                 __syncthreads();
@@ -685,12 +674,6 @@ __global__ void colsum_stage2_kernel(const float *__restrict__ partials, int chu
 // ---------------------------------------------------------------------------
 // softmax cross entropy (mean over masked rows) + gradient; one wave per row
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-
 // slabs != NULL: the logits are still the split-K partial sums of the class layer's projection (dense
 // [n_slabs][n_rows][n_classes]); the row's logits = slabs summed in slab order + bias are formed here
 // exactly as the split-K reduce pass would (gemm.hip) and stored to `logits` first.

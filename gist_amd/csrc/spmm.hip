@@ -22,30 +22,6 @@
 
 namespace gist {
 
-template <int VEC> struct Vec;
-template <> struct Vec<1> { using T = float; };
-template <> struct Vec<2> { using T = float2; };
-template <> struct Vec<4> { using T = float4; };
-
-template <int VEC>
-__device__ __forceinline__ void vload(const float *p, float (&v)[VEC]) {
-    using T = typename Vec<VEC>::T;
-    T t = *reinterpret_cast<const T *>(p);
-    if constexpr (VEC == 1) { v[0] = t; }
-    if constexpr (VEC == 2) { v[0] = t.x; v[1] = t.y; }
-    if constexpr (VEC == 4) { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-}
-
-template <int VEC>
-__device__ __forceinline__ void vstore(float *p, const float (&v)[VEC]) {
-    using T = typename Vec<VEC>::T;
-    T t;
-    if constexpr (VEC == 1) { t = v[0]; }
-    if constexpr (VEC == 2) { t.x = v[0]; t.y = v[1]; }
-    if constexpr (VEC == 4) { t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3]; }
-    *reinterpret_cast<T *>(p) = t;
-}
-
 constexpr int kSpmmWavesPerBlock = 4;
 
 // gist_dropout_f32's mask applied where a value is produced or consumed instead of by a pass of its own

@@ -109,11 +109,6 @@ struct MfArgs {
     int pairs;                       // prepared blocks: the structure may hold pairs (prepare: look for them)
 };
 
-__device__ __forceinline__ uint32_t mf_pack(__bf16 lo, __bf16 hi) {
-    return (uint32_t)__builtin_bit_cast(unsigned short, lo) |
-           ((uint32_t)__builtin_bit_cast(unsigned short, hi) << 16);
-}
-
 // Workgroup barrier that waits for this wave's LDS traffic only: the global loads of the next tile stay
 // in flight across it (__syncthreads() waits for vmcnt(0) as well, i.e. for every prefetch).
 __device__ __forceinline__ void mf_barrier() {
@@ -392,7 +387,7 @@ __device__ __forceinline__ void mf_build_block(const MfArgs &a, int rbk, int r0,
             const bool big = __ballot(c0 > 256u || c1 > 256u) != 0ULL;
             if (big && lane == 0) atomicOr(&big_row[wave + MF_WAVES * i], 1);
             a32[((lane >> 2) * MF_ROWS + wave + MF_WAVES * i) * 4 + (lane & 3)] =
-                mf_pack((__bf16)(float)c0, (__bf16)(float)c1);
+                pack_bf16x2((__bf16)(float)c0, (__bf16)(float)c1);
         }
     }
     if constexpr (PAIRS) {
@@ -408,7 +403,7 @@ __device__ __forceinline__ void mf_build_block(const MfArgs &a, int rbk, int r0,
                 const bool big = __ballot(c0 > 256u || c1 > 256u) != 0ULL;
                 if (big && lane == 0) atomicOr(&big_row[wave + MF_WAVES * i], 1);
                 q32[((lane >> 2) * MF_ROWS + wave + MF_WAVES * i) * 4 + (lane & 3)] =
-                    mf_pack((__bf16)(float)c0, (__bf16)(float)c1);
+                    pack_bf16x2((__bf16)(float)c0, (__bf16)(float)c1);
             }
         }
     }

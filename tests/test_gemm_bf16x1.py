@@ -52,6 +52,9 @@ def _cases():
 
 
 X1_CASES = _cases()
+# the block -> tile map (kernel_kit.h: xcd_linear, tile_of_linear) past the edges above: 9 x 1 tiles -- a second super-tile, one
+# tile row deep, 9 workgroups dealt unevenly to the 8 XCDs -- and 3 x 3 tiles, k of two tiles
+X1_TILE_MAP_CASES = [_case('nt', 8 * T + 1, T, 128, 'tight/16', True), _case('tn', 2 * T + 3, 2 * T + 3, 128, 'tight/16', False)]
 
 
 # -- the rounding, from its definition ---------------------------------------------------------------------------------
@@ -248,7 +251,7 @@ def test_plans_of_the_case_table(hip):
     """every case of the GPU table takes the path with the tile and slice count the table states, in one launch of the cast,
     one of the main kernel and, with slices, one of the slab sum; the table covers what it claims"""
     from tests.test_gemm_kernels_gpu import configured, plan_key, plan_of
-    for c in X1_CASES:
+    for c in X1_CASES + X1_TILE_MAP_CASES:
         with configured(hip, c):
             p = plan_of(hip, c)
         assert p['path'] == 'bf16x1' and plan_key(p) == c.want and p['k_per_split'] == k_per_of(c), (c, p)

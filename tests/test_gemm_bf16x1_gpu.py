@@ -11,7 +11,7 @@ import torch
 
 from tests import test_stream_order_gpu as SO
 from tests.scratch_guard import Guarded
-from tests.test_gemm_bf16x1 import BIG_SHAPES, HOOKS, X1_CASES, T, _case, bar, rne_bf16
+from tests.test_gemm_bf16x1 import BIG_SHAPES, HOOKS, X1_CASES, X1_TILE_MAP_CASES, T, _case, bar, rne_bf16
 from tests.test_gemm_kernels_gpu import (DEV, FORMS, _id, cmp_f32, configured, inputs, plan_key, plan_of, poke_nonfinite,
                                          put, ref64, run, to_dev)
 
@@ -26,7 +26,7 @@ def hip():
     return h
 
 
-@pytest.mark.parametrize('case', X1_CASES, ids=_id)
+@pytest.mark.parametrize('case', X1_CASES + X1_TILE_MAP_CASES, ids=_id)
 def test_case_table(hip, case):
     c = case
     a, b, bias = inputs(c)

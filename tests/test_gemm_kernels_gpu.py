@@ -339,7 +339,30 @@ F32_CASES = _f32_cases()
 H3_CASES = _h3_cases()
 B3_CASES = _b3_cases()
 B3C_CASES = _b3c_cases()
-TABLES = {'f32': F32_CASES + K0_CASES + DUAL_CASES, 'f16x3': H3_CASES, 'bf16x3': B3_CASES, 'bf16x3_load': B3C_CASES}
+
+
+# The block -> tile map every kernel here shares (kernel_kit.h: xcd_linear, tile_of_linear) goes wrong only at particular tile
+# counts, which the edge shapes above (at most 3 tile rows) do not reach: 9 x 1 tiles of the kernel's own tile -- a second
+# super-tile, one tile row deep, and 9 workgroups dealt unevenly to the 8 XCDs -- with k of two tiles; 3 x 3 tiles where no
+# case above has more than 8 tiles that are no multiple of 8.  The 256 x 256 tile runs from 256 tiles on: 9 x 29.
+def _tile_map_cases():
+    f32 = lambda t, form, m, n, k, bias: _f32(form, t, 1, m, n, k, 'tight/16', 1, bias=bias)
+    h3 = lambda tm, form, m, n, bias: Case('f16x3', 'f16x3', H3_HOOKS + (('h3_tm', tm),), form, m, n, 64, 'tight/16', bias, 'call',
+                                           'normal', (tm, 128, 1, 1))
+    b3 = lambda form, m, n, bias, tn: Case('bf16x3', 'bf16x3', H3_HOOKS, form, m, n, 64, 'tight/16', bias, 'call', 'normal',
+                                           (256, tn, 1, 1))
+    b3c = lambda hook, tm, tn, form, m, n, bias: Case('bf16x3_load', 'bf16x3', (('b3c', 2), ('gemm_tile', hook)), form, m, n, 64,
+                                                      'window/16', bias, 'call', 'normal', (tm, tn, 1, 1))
+    return {'f32': [f32(64, 'nt', 513, 64, 128, True), f32(128, 'nn', 1025, 128, 64, False)],
+            'f16x3': [h3(64, 'nt', 513, 128, True), h3(128, 'nn', 1025, 128, False), h3(128, 'tn', 257, 257, False)],
+            'bf16x3': [b3('nt', 2049, 128, True, 128), b3('nn', 2049, 7169, False, 256)],
+            'bf16x3_load': [b3c(64, 64, 64, 'nt', 513, 64, True), b3c(128, 128, 64, 'nn', 1025, 64, False),
+                            b3c(128128, 128, 128, 'tn', 1025, 128, False)]}
+
+
+TILE_MAP_CASES = _tile_map_cases()
+TABLES = {'f32': F32_CASES + K0_CASES + DUAL_CASES + TILE_MAP_CASES['f32'], 'f16x3': H3_CASES + TILE_MAP_CASES['f16x3'],
+          'bf16x3': B3_CASES + TILE_MAP_CASES['bf16x3'], 'bf16x3_load': B3C_CASES + TILE_MAP_CASES['bf16x3_load']}
 ALL_CASES = [c for t in TABLES.values() for c in t]
 
 
@@ -606,22 +629,22 @@ def check_case(hip, c):
         assert ok, (c, stats)
 
 
-@pytest.mark.parametrize('case', F32_CASES, ids=_id)
+@pytest.mark.parametrize('case', F32_CASES + TILE_MAP_CASES['f32'], ids=_id)
 def test_f32_kernel(hip, case):
     check_case(hip, case)
 
 
-@pytest.mark.parametrize('case', H3_CASES, ids=_id)
+@pytest.mark.parametrize('case', H3_CASES + TILE_MAP_CASES['f16x3'], ids=_id)
 def test_f16x3_kernels(hip, case):
     check_case(hip, case)
 
 
-@pytest.mark.parametrize('case', B3_CASES, ids=_id)
+@pytest.mark.parametrize('case', B3_CASES + TILE_MAP_CASES['bf16x3'], ids=_id)
 def test_bf16x3_kernels(hip, case):
     check_case(hip, case)
 
 
-@pytest.mark.parametrize('case', B3C_CASES, ids=_id)
+@pytest.mark.parametrize('case', B3C_CASES + TILE_MAP_CASES['bf16x3_load'], ids=_id)
 def test_bf16x3_convert_on_load_kernel(hip, case):
     check_case(hip, case)
 
